@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: composed queries/sec of the encode -> fuse -> rank path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 One STEP on one GPU = one batch of composed queries, inputs already resident in HBM:
     encode_image(B x 3xSxS) -> encode_text(B x 77 tokens, one tower pass)
@@ -20,9 +20,11 @@ fuses ONLY its own rows (seed + rank), then one all_gather replicates the fused 
 value = N x B x K / max-over-ranks time), with no data-path collective.  c5 also reports the gallery-sharded variant
 (all-gather queries, local top-K with idx_offset, all-gather candidates, merge).
 
-After the timed region the same step runs with libfern's HIP-event instrumentation (events on the launch stream around
-every GEMM / attention / sweep launch) to fill `roofline`; on rank 0 at N = 1 the CPU oracle is timed on bounded samples
-for `cpu_baseline` and used as the checker of the GPU result.
+A plain run sets up, warms up, times the K steps and prints the headline line (`--dump-outputs DIR`: and writes what the last
+timed step returned).  With `--full`, after the timed region the same step runs with libfern's HIP-event instrumentation (events
+on the launch stream around every GEMM / attention / sweep launch) to fill `roofline`; on rank 0 at N = 1 the CPU oracle is timed
+on bounded samples for `cpu_baseline` and used as the checker of the GPU result; the secondary legs and the c3 / c4 / c5 child
+runs follow.
 """
 import argparse
 import json
@@ -115,7 +117,7 @@ def parse_args():
     ap.add_argument("--precision", choices=["fp32", "f32x3", "bf16", "fp8", "mx8", "mx8mlp", "mx8img"], default=None,
                     help="override the encoder operand precision of the TIMED path (fp32 = parity mode, the c2 headline)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the secondary legs (reduced-precision modes, lookup variant, 1M-row bf16 sweep, encode rate): the GEMM "
+                    help="--full: skip the secondary legs (reduced-precision modes, lookup variant, 1M-row bf16 sweep, encode rate): the GEMM "
                          "dispatches of the run are then the headline step's, for comparing rocprofv3 averages with `roofline`")
     ap.add_argument("--pmc-mode", action="store_true",
                     help="for `rocprofv3 --pmc`: warm up, emit a marker dispatch, run exactly --steps steps on one stream, exit (no JSON)")
@@ -127,10 +129,18 @@ def parse_args():
                     help="cpu_baseline: also time ONE query with torch's pool on every schedulable core (256 threads on the GPU box: ~70 s, a "
                          "documented pathology of the pool -- not part of the default run since round 6)")
     ap.add_argument("--full-record", type=str, default=os.path.join(ROOT, "bench_full.json"),
-                    help="where rank 0 writes the FULL record (every leg, notes, tile table); stdout carries the compact line (< 4 KB)")
+                    help="--full: where rank 0 writes the FULL record (every leg, notes, tile table); stdout carries the compact line (< 4 KB)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default c2 run at N = 1: do not also run the c3 / c4 / c5 workloads (short child runs of this script, reported "
+                    help="--full c2 run at N = 1: do not also run the c3 / c4 / c5 workloads (short child runs of this script, reported "
                          "under `other_configs`)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the benchmark measures and checks: roofline passes, the "
+                         "gallery-build and all-gather figures, the reduced-precision and quality legs, the CPU baseline with its parity "
+                         "check, the c3 / c4 / c5 child runs, the full record.  Without it a run sets up, warms up, times the steps and "
+                         "prints the headline line")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="rank 0 writes what the timed path returned in its last step to DIR/<name>.npy (float32 / float64): the "
+                         "top-K scores and indices, the fused query features and, for c4, the member scores")
     return ap.parse_args()
 
 
@@ -158,8 +168,8 @@ def other_config_lines(steps: int) -> dict:
         t0 = time.perf_counter()
         fd_, full_path = tempfile.mkstemp(prefix=f"fern_bench_{name}_", suffix=".json")
         os.close(fd_)
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", "4", "--no-cpu-baseline", "--no-other-configs",
-               "--full-record", full_path]
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", "4", "--full", "--no-cpu-baseline",
+               "--no-other-configs", "--full-record", full_path]
         if name != "c5":
             cmd.append("--headline-only")      # c5 keeps its secondary leg: the ranking agreement of the fp8 encoder with the fp32 one
         try:
@@ -188,12 +198,12 @@ def other_config_lines(steps: int) -> dict:
     return out
 
 
-def multi_gpu_preflight(torch, dist, fd, rank, world, local, device, backend):
+def multi_gpu_preflight(torch, dist, fd, rank, world, local, device, backend, measure=True):
     """`--gpus N`, N > 1: before any model work, every rank reports where it runs and the job times the path's one collective
     shape on the wire -- so that the first run on a real multi-GPU node is self-diagnosing: RCCL world size,
     per-rank device (index, name, PCI bus id), two ranks on one device (refused unless the FERN_BENCH_SHARE_GPU debug layout), and
-    the all-gather rate of 64 MiB-per-rank bf16 blocks (the C5 shard is 128 MB) against 7 x 153 GB/s of xGMI.  Printed to stderr by
-    rank 0 and carried in the JSON line under `preflight`."""
+    (`measure`, i.e. --full) the all-gather rate of 64 MiB-per-rank bf16 blocks (the C5 shard is 128 MB) against 7 x 153 GB/s of xGMI.
+    Printed to stderr by rank 0 and carried in the full record under `preflight`."""
     props = torch.cuda.get_device_properties(device)
     me = {"rank": rank, "local_rank": local, "device": device.index, "name": props.name, "host": socket.gethostname(),
           "pci_bus_id": getattr(props, "pci_bus_id", None), "hsa_ipc_legacy": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY")}
@@ -206,6 +216,8 @@ def multi_gpu_preflight(torch, dist, fd, rank, world, local, device, backend):
             raise SystemExit(f"bench preflight: ranks {seen[key]} and {e['rank']} both run on {key}: one process per GPU is the layout "
                              "(LOCAL_RANK -> cuda:LOCAL_RANK); set FERN_BENCH_SHARE_GPU=1 only for the one-GPU debug rehearsal")
         seen[key] = e["rank"]
+    if not measure:      # a run without --full: the layout check only
+        return {"rccl_world": world if backend == "nccl" else f"{world} (debug backend {backend})", "backend": backend, "ranks": everyone}
     per = 64 << 20
     block = torch.full((per // 2,), float(rank), dtype=torch.bfloat16, device=device)
     out = torch.empty((world * (per // 2),), dtype=torch.bfloat16, device=device)
@@ -539,6 +551,17 @@ def harness_leg(torch, eng, clip, model, cfg, D, device, n_gal, lookup_qps, enc_
     return out
 
 
+def dump_outputs(out_dir: str, res) -> None:
+    """--dump-outputs: what the timed path returned for its last batch (a pipeline QueryResult) as DIR/<name>.npy -- top-K scores
+    and gallery indices, the fused query features, c4's member scores; float32, indices as float64 (exact).  A few hundred KB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    scores, idx = res.wait()
+    for name, t in (("topk_scores", scores), ("topk_idx", idx), ("fused_queries", res.fused), ("member_scores", res.member_scores)):
+        if t is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), (t.float() if t.is_floating_point() else t.double()).cpu().numpy())
+
+
 COMPACT_CAP_BYTES = 4000      # the driver reads ONE stdout line; round 5's 24.6 KB line came back unparsed (VERDICT r5 item 1)
 
 
@@ -566,14 +589,15 @@ def compact_record(full: dict, cap: int = COMPACT_CAP_BYTES) -> dict:
                                          "batches_in_flight", "hw_queues") if k in cfg}
     out["config"]["parallelism"] = str(cfg.get("parallelism", "")).split(";")[0]
     out["encoder_precision"] = full.get("encoder_precision")
-    roof = full.get("roofline") or {}
-    r = _pick(roof, "bound", "achieved", "peak", "unit", "frac")
-    r["traffic"] = roof.get("traffic")                      # HBM counter bytes per launch; None unless measured at this HEAD
-    r["kernel"] = str(roof.get("kernel", "")).split(" (")[0][:60]
-    r.update(_pick(roof, "algorithmic_bytes_per_launch", "gemm_ms_per_step", "gemm_gflop_per_step"))
-    if isinstance(roof.get("step_level"), dict):
-        r["step_level"] = _pick(roof["step_level"], "achieved", "frac")
-    out["roofline"] = r
+    roof = full.get("roofline")
+    if roof:                                                # --full
+        r = _pick(roof, "bound", "achieved", "peak", "unit", "frac")
+        r["traffic"] = roof.get("traffic")                  # HBM counter bytes per launch; None unless measured at this HEAD
+        r["kernel"] = str(roof.get("kernel", "")).split(" (")[0][:60]
+        r.update(_pick(roof, "algorithmic_bytes_per_launch", "gemm_ms_per_step", "gemm_gflop_per_step"))
+        if isinstance(roof.get("step_level"), dict):
+            r["step_level"] = _pick(roof["step_level"], "achieved", "frac")
+        out["roofline"] = r
     cb = full.get("cpu_baseline")
     if cb:
         c = _pick(cb, "value", "unit", "cores", "host_cores", "cpu_model", "kind")
@@ -638,7 +662,8 @@ def compact_record(full: dict, cap: int = COMPACT_CAP_BYTES) -> dict:
         extras.append(("all_gather", _pick(ag, "ms", "GBs_per_rank", "frac_of_xgmi", sig=4)))
     if full.get("timing_s"):
         extras.append(("timing_s", full["timing_s"]))
-    out["full_record"] = full.get("full_record")
+    if full.get("full_record"):
+        out["full_record"] = full["full_record"]
     for k, v in extras:
         out[k] = v
     while len(json.dumps(out)) > cap and extras:
@@ -675,7 +700,7 @@ def main():
     D, B, K, n_gal = w["d"], w["batch"], w["k"], w["gallery"]
     backend = dist.get_backend() if world > 1 else None
     gloo = backend == "gloo"
-    preflight = multi_gpu_preflight(torch, dist, fd, rank, world, local, device, backend) if world > 1 else None
+    preflight = multi_gpu_preflight(torch, dist, fd, rank, world, local, device, backend, measure=args.full) if world > 1 else None
 
     def dev_randn(shape, seed):
         g = torch.Generator(device=device)
@@ -705,7 +730,7 @@ def main():
     # sources) sits in small physical fragments and the same sweep kernel streams it ~20 % slower (209 vs 171 us on one box).
     _s0, _s1, _per = fd.shard_rows(n_gal, rank, world)
     gallery_store = torch.empty((world * _per, D), dtype=torch.bfloat16 if w["bf16_gallery"] else torch.float32, device=device)
-    if not args.headline_only and args.config == "c2" and precision == "fp32":
+    if args.full and not args.headline_only and args.config == "c2" and precision == "fp32":
         # the 1M-row bf16 gallery of the HBM-bound ranking leg is allocated NOW, like a serving process allocates its gallery at start-up:
         # allocated after a minute of other work (workspaces of three lanes, four precision modes, a freed 2 GB fp32 source) the same
         # kernel streams it 20 % slower (209 vs 171 us on one box) -- the buffer then sits in small physical fragments
@@ -761,24 +786,25 @@ def main():
     shard = build_shard()
     gallery = gather(shard)                    # warm (RCCL connection setup, workspaces)
     barrier()
-    t0 = time.perf_counter()
-    shard = build_shard()
-    torch.cuda.synchronize()
-    fuse_s = time.perf_counter() - t0
-    prepare_ms = None
-    if use_prepared:                           # this rank's share of the preparation (its shard), timed on its own
-        torch.cuda.synchronize()
+    fuse_s = prepare_ms = ag_ms = None
+    if args.full:                              # the gallery build's own figures: the same build again, timed
         t0 = time.perf_counter()
-        eng.prepare_gallery(shard)
+        shard = build_shard()
         torch.cuda.synchronize()
-        prepare_ms = (time.perf_counter() - t0) * 1e3
-    barrier()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    gallery = gather(shard)
-    ev1.record()
-    torch.cuda.synchronize()
-    ag_ms = ev0.elapsed_time(ev1)
+        fuse_s = time.perf_counter() - t0
+        if use_prepared:                       # this rank's share of the preparation (its shard), timed on its own
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.prepare_gallery(shard)
+            torch.cuda.synchronize()
+            prepare_ms = (time.perf_counter() - t0) * 1e3
+        barrier()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        gallery = gather(shard)
+        ev1.record()
+        torch.cuda.synchronize()
+        ag_ms = ev0.elapsed_time(ev1)
     ag_bytes = (world - 1) * per * D * (shard.element_size() + (2 if use_prepared else 0))      # bytes this rank receives (fp32 rows + their bf16 copy)
     shard_start = start
     gallery_raw = gallery.f32 if use_prepared else gallery
@@ -862,6 +888,29 @@ def main():
     stamp("timed_region_done")
     value = world * B * args.steps / elapsed
     headline_latency = last_latency[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    head = {
+        "metric": "composed queries/sec", "value": value, "unit": "queries/sec", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": {"fp32": "f32", "f32x3": "bf16x3", "bf16": "bf16", "fp8": "fp8", "mx8": "fp8", "mx8mlp": "fp8", "mx8img": "fp8"}[precision], "data": "synthetic",
+        "config": {"workload": w["text"], "name": args.config, "clip": cfg.name, "query_batch_per_gpu": B, "gallery_rows": n_gal,
+                   "gallery_dtype": "bf16" if w["bf16_gallery"] else "f32", "feature_dim": D, "top_k": K,
+                   "image": f"3x{cfg.image_size}x{cfg.image_size}", "tokens": 77, "patch_feats": 13, "batches_in_flight": args.lanes,
+                   "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
+                   "input_batches_rotated": n_batches,
+                   "parallelism": f"dp{world} queries; gallery built sharded ({per} rows per rank, seed + rank), fused blocks all-gathered once"},
+        "ms_per_step_event_median": gap_median,
+        "latency_ms_per_batch": headline_latency,
+        "encoder_precision": precision,
+    }
+    if not args.full:      # the headline line only; everything below is --full
+        if rank == 0:
+            print(json.dumps(compact_record(head)), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- c5 only: gallery-SHARDED ranking (SURVEY 8e alternative): all-gather the fused queries, sweep the local shard for all of
     # them, all-gather the candidates, merge -- every rank reads N/W gallery rows per batch instead of N
@@ -1152,17 +1201,7 @@ def main():
                 traffic_src = ("omitted: " + os.path.basename(traffic_file) + " was measured on other kernel sources (" +
                                json.dumps(tr.get("measured")) + "), this tree is csrc_sha16 " + csrc_sha16())
         result = {
-            "metric": "composed queries/sec", "value": value, "unit": "queries/sec", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": {"fp32": "f32", "f32x3": "bf16x3", "bf16": "bf16", "fp8": "fp8", "mx8": "fp8", "mx8mlp": "fp8", "mx8img": "fp8"}[precision], "data": "synthetic",
-            "config": {"workload": w["text"], "name": args.config, "clip": cfg.name, "query_batch_per_gpu": B, "gallery_rows": n_gal,
-                       "gallery_dtype": "bf16" if w["bf16_gallery"] else "f32", "feature_dim": D, "top_k": K,
-                       "image": f"3x{cfg.image_size}x{cfg.image_size}", "tokens": 77, "patch_feats": 13, "batches_in_flight": args.lanes,
-                       "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
-                       "input_batches_rotated": n_batches,
-                       "parallelism": f"dp{world} queries; gallery built sharded ({per} rows per rank, seed + rank), fused blocks all-gathered once"},
-            "ms_per_step_event_median": gap_median,
-            "latency_ms_per_batch": headline_latency,
+            **head,
             "rccl_world": world if backend == "nccl" else (1 if world == 1 else f"{world} (debug backend {backend})"),
             "preflight": preflight,
             "all_gather": {"ms": ag_ms if world > 1 else 0.0, "bytes_received_per_rank": ag_bytes,
@@ -1212,7 +1251,6 @@ def main():
             "encoder_mx8mlp": mx8mlp_info,
             "encoder_mx8img": mx8img_info,
             "reduced_modes": quality,
-            "encoder_precision": precision,
             "accuracy_vs_fp32_encoder": accuracy,
             "sharded_merge": sharded_info,
             "attention": {"achieved_tflops": attn_tflops, "ms_per_step": st["attn_ms"] / prof_steps},

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_help_and_workloads_without_a_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--config"):
+    for flag in ("--gpus", "--steps", "--warmup", "--config", "--full", "--dump-outputs"):
         assert flag in r.stdout
     src = open(os.path.join(ROOT, "bench.py")).read()
     for cfg in ("c2", "c3", "c4", "c5"):
@@ -85,7 +85,7 @@ def _run_bench(tmp_path, *flags, env=None):
 @pytest.mark.gpu
 @pytest.mark.parametrize("config", ["c2", "c5"])
 def test_bench_line_has_the_contract_keys(config, tmp_path):
-    r, full_path = _run_bench(tmp_path, "--config", config, "--steps", "3", "--warmup", "1", "--headline-only", "--no-cpu-baseline")
+    r, full_path = _run_bench(tmp_path, "--config", config, "--steps", "3", "--warmup", "1", "--full", "--headline-only", "--no-cpu-baseline")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, "rank 0 prints exactly ONE line on stdout"
@@ -105,13 +105,41 @@ def test_bench_line_has_the_contract_keys(config, tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_prints_the_headline_line_and_dumps_the_last_step(tmp_path):
+    """Without --full a run times the steps and prints the headline line, nothing else (no roofline pass, no full record);
+    --dump-outputs writes what the last timed step returned, and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    dumps = []
+    for j in range(2):
+        out_dir = tmp_path / f"out{j}"
+        r, full_path = _run_bench(tmp_path, "--config", "c4", "--steps", "4", "--warmup", "2", "--dump-outputs", str(out_dir))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, "rank 0 prints exactly ONE line on stdout"
+        d = json.loads(lines[0])
+        assert d["metric"] == "composed queries/sec" and d["unit"] == "queries/sec" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["config"]["name"] == "c4"
+        assert d["value"] > 0 and abs(d["value"] - 128 * 4 / (d["ms_per_step"] * 4e-3)) / d["value"] < 1e-4
+        assert "roofline" not in d and "cpu_baseline" not in d and not os.path.exists(full_path)
+        got = {f[:-4]: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))}
+        assert set(got) == {"topk_scores", "topk_idx", "fused_queries", "member_scores"}
+        assert got["topk_scores"].shape == got["topk_idx"].shape == (128, 51) and got["fused_queries"].shape == (128, 512)
+        assert got["member_scores"].shape == (128, 6) and all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert np.isfinite(got["topk_scores"]).all() and (got["topk_idx"] == np.round(got["topk_idx"])).all()
+        dumps.append(got)
+    for name in dumps[0]:
+        np.testing.assert_allclose(dumps[1][name], dumps[0][name], rtol=1e-5, atol=1e-6, err_msg=name)
+    assert np.array_equal(dumps[1]["topk_idx"], dumps[0]["topk_idx"])
+
+
+@pytest.mark.gpu
 @pytest.mark.slow
 def test_bench_default_command_prints_one_compact_line(tmp_path):
-    """The command the DRIVER runs (no flags but the step counts): cpu_baseline, the secondary legs and the c3 / c4 / c5 child runs
+    """`--full` with no other flags but the step counts: cpu_baseline, the secondary legs and the c3 / c4 / c5 child runs
     all happen, and stdout still ends in ONE line under the cap that carries `roofline` + `cpu_baseline`."""
     import time
     t0 = time.time()
-    r, full_path = _run_bench(tmp_path, "--steps", "3", "--warmup", "1")
+    r, full_path = _run_bench(tmp_path, "--steps", "3", "--warmup", "1", "--full")
     wall = time.time() - t0
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -136,7 +164,7 @@ def test_bench_multi_rank_preflight_and_latency_keys(tmp_path):
     are refused without the debug switch, and the line carries the per-batch latency and the roofline regime label."""
     env = dict(os.environ, FERN_DIST_BACKEND="gloo", FERN_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     full_path = str(tmp_path / "full2.json")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "c4", "--steps", "2", "--warmup", "1", "--headline-only",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "c4", "--steps", "2", "--warmup", "1", "--full", "--headline-only",
            "--no-cpu-baseline", "--full-record", full_path]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

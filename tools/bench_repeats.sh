@@ -7,7 +7,7 @@ out = {}
 for cfg in ("c2", "c5"):
     runs = []
     for _ in range(5):
-        r = subprocess.run([sys.executable, "bench.py", "--config", cfg, "--headline-only", "--no-cpu-baseline", "--no-other-configs", "--steps", "40",
+        r = subprocess.run([sys.executable, "bench.py", "--config", cfg, "--full", "--headline-only", "--no-cpu-baseline", "--no-other-configs", "--steps", "40",
                             "--full-record", "/tmp/fern_repeat_full.json"], capture_output=True, text=True, timeout=600)
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         runs.append({"value": d["value"], "ms_per_step": d["ms_per_step"], "roofline_frac": d["roofline"]["frac"], "precision": d["encoder_precision"]})

@@ -15,7 +15,7 @@ cd /tmp && export TMPDIR=/tmp
 for cfg in c2 c5; do
   # one set of tuner choices (tiles, pair forms) for both counter passes: they are separate runs, and a pair that is one launch in the
   # FETCH pass and two in the WRITE pass would mix two launch populations in the per-launch figure
-  timeout 600 python3 $R/bench.py --no-cpu-baseline --headline-only --no-other-configs --lanes 1 --steps 4 --config $cfg --save-tiles /tmp/pmc_tiles_$cfg.txt --full-record /tmp/pmc_tiles_$cfg.json > /dev/null 2>&1
+  timeout 600 python3 $R/bench.py --full --no-cpu-baseline --headline-only --no-other-configs --lanes 1 --steps 4 --config $cfg --save-tiles /tmp/pmc_tiles_$cfg.txt --full-record /tmp/pmc_tiles_$cfg.json > /dev/null 2>&1
   export FERN_GEMM_TILES=/tmp/pmc_tiles_$cfg.txt
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_${cfg}_$c
@@ -27,5 +27,5 @@ for cfg in c2 c5; do
 done
 cd $R
 cp $O/pmc_traffic.json $O/pmc_traffic_c5.json profiles/        # the driver's command below reads them (only on this box: copy them back in the dev container too)
-( time python bench.py --gpus 1 --steps 20 --warmup 5 --full-record $O/bench_full.json > $O/bench.out 2> $O/bench.err ) 2> $O/bench.time
+( time python bench.py --gpus 1 --steps 20 --warmup 5 --full --full-record $O/bench_full.json > $O/bench.out 2> $O/bench.err ) 2> $O/bench.time
 tail -c 1200 $O/bench.out; cat $O/bench.time

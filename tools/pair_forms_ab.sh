@@ -4,7 +4,7 @@
 OUT=${1:-gpurun_out/pair_forms.txt}; shift
 mkdir -p $(dirname $OUT); : > $OUT
 run() {
-  python bench.py --headline-only --no-cpu-baseline --no-other-configs --steps 40 --full-record /tmp/fern_pf_full.json 2>/dev/null | tail -1 |
+  python bench.py --full --headline-only --no-cpu-baseline --no-other-configs --steps 40 --full-record /tmp/fern_pf_full.json 2>/dev/null | tail -1 |
     python -c "import json,sys; d=json.loads(sys.stdin.readline()); print('$1', round(d['value'],1), d['ms_per_step'], d['roofline']['frac'])" >> $OUT
 }
 for rep in 1 2; do

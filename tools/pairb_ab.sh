@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/pairb_ab.txt}
 : > "$OUT"
 for rep in 1 2 3; do
   for pair in 1 0; do
-    FERN_GEMM_PAIR=$pair python bench.py --config c5 --headline-only --no-cpu-baseline --no-other-configs --steps 40 --full-record /tmp/fern_pairb_full.json \
+    FERN_GEMM_PAIR=$pair python bench.py --config c5 --full --headline-only --no-cpu-baseline --no-other-configs --steps 40 --full-record /tmp/fern_pairb_full.json \
       --save-tiles /tmp/fern_pairb_tiles_$pair.txt 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.readline())

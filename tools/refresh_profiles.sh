@@ -26,16 +26,16 @@ cd /tmp && export TMPDIR=/tmp
 run_stats() {   # name, bench args...
     local name=$1; shift
     rm -rf /tmp/prof_$name
-    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -o p -- python3 $R/bench.py --no-cpu-baseline --full-record $O/${name}_under_rocprof_full.json "$@" > $O/${name}_under_rocprof.json 2> /tmp/${name}.err
+    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -o p -- python3 $R/bench.py --full --no-cpu-baseline --full-record $O/${name}_under_rocprof_full.json "$@" > $O/${name}_under_rocprof.json 2> /tmp/${name}.err
     python3 $R/tools/kstats.py /tmp/prof_$name 16 $O/${name}_kernel_stats.csv > $O/${name}_kernel_stats_top.txt 2>&1
 }
 # tile choices of this box first; the profiled runs are pinned to them (FERN_GEMM_TILES), so their dispatch averages hold no tuner trials
 rm -f /tmp/shapes.csv
-FERN_PROF_DUMP=/tmp/shapes.csv timeout 600 python3 $R/bench.py --no-cpu-baseline --headline-only --lanes 1 --steps 10 --save-tiles $O/${TAG}_gemm_tiles.txt > /dev/null 2>&1
+FERN_PROF_DUMP=/tmp/shapes.csv timeout 600 python3 $R/bench.py --full --no-cpu-baseline --headline-only --lanes 1 --steps 10 --save-tiles $O/${TAG}_gemm_tiles.txt > /dev/null 2>&1
 python3 $R/tools/prof_shapes.py /tmp/shapes.csv > $O/${TAG}_shapes.txt
 for c in c3 c5; do      # per-shape tables of the other workloads (not pinned: their own tuner choices)
     rm -f /tmp/shapes_$c.csv
-    FERN_PROF_DUMP=/tmp/shapes_$c.csv timeout 600 python3 $R/bench.py --no-cpu-baseline --headline-only --lanes 1 --steps 10 --config $c > /dev/null 2>&1
+    FERN_PROF_DUMP=/tmp/shapes_$c.csv timeout 600 python3 $R/bench.py --full --no-cpu-baseline --headline-only --lanes 1 --steps 10 --config $c > /dev/null 2>&1
     python3 $R/tools/prof_shapes.py /tmp/shapes_$c.csv > $O/${TAG}_shapes_$c.txt
 done
 export FERN_GEMM_TILES=$O/${TAG}_gemm_tiles.txt
@@ -61,7 +61,7 @@ python3 $R/tools/kstats.py /tmp/prof_sweep 16 $O/${TAG}_sweep_1M_kernel_stats.cs
 timeout 200 python3 $R/tools/attn_bench.py > $O/${TAG}_attn_bench.txt 2>&1
 cd $R
 # the driver's default command: it carries cpu_baseline, the harness / quality / PCIe legs and the c3 / c4 / c5 child runs (other_configs)
-timeout 1200 python3 bench.py --full-record $O/${TAG}_bench_c2_full.json > $O/${TAG}_bench_c2.json 2> $O/${TAG}_bench_c2.err
+timeout 1200 python3 bench.py --full --full-record $O/${TAG}_bench_c2_full.json > $O/${TAG}_bench_c2.json 2> $O/${TAG}_bench_c2.err
 # ranking stage: micro-benchmark of its three forms at the BASELINE shapes + kernel timelines of the forms the cost model picks
 timeout 300 python3 tools/rank_bench.py > $O/${TAG}_rank_bench.txt 2>&1
 cd /tmp
