@@ -2180,9 +2180,68 @@ extern "C" int fern_gather_scores(fern_ctx* c, const float* q, const float* gall
 
 extern "C" int fern_topk_merge(fern_ctx* c, const float* scores, const int32_t* idx, float* out_scores, int32_t* out_idx, int R, int B, int K,
                                void* stream) {
-    if (!c || R < 1 || B < 0 || K < 1 || K > 64 || (B && (!scores || !idx || !out_scores || !out_idx))) return fail(FERN_ERR_ARG, "fern_topk_merge: bad argument");
+    if (!c || R < 1 || B < 0 || K < 1 || K > 1024 || (B && (!scores || !idx || !out_scores || !out_idx))) return fail(FERN_ERR_ARG, "fern_topk_merge: bad argument");
+    if (K > 64 && (long)R * K > 16384) return fail(FERN_ERR_ARG, "fern_topk_merge: need R * K <= 16384 for K > 64");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(launch_topk_merge(scores, idx, out_scores, out_idx, R, B, K, (hipStream_t)stream));
+    if (K <= 64) HIP_TRY(launch_topk_merge(scores, idx, out_scores, out_idx, R, B, K, (hipStream_t)stream));
+    else HIP_TRY(launch_topk_merge_deep(scores, idx, out_scores, out_idx, R, B, K, (hipStream_t)stream));
+    return FERN_OK;
+}
+
+// Deep ranking (include/fern.h: fern_sim_topk_deep), per query chunk: scores of every row into a [m, ld] workspace (exact: the fp32 MFMA
+// chain; pre-filtered / bf16: the bf16 sweep's store form), one select kernel per query (topk_deep.hip), then the gated exact rows
+// (pre-filter only) and the gated radix-select fallback for the queries the select kernel had no room for.  Nothing is read back.
+extern "C" int fern_sim_topk_deep(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, const float* meta, int B,
+                                  int64_t N, int D, int K, float* out_scores, int32_t* out_idx, int64_t idx_offset, const int32_t* exclude_idx,
+                                  void* stream) {
+    if (K < 1 || K > 1024) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: need 1<=K<=1024");
+    if (B < 0 || N < 0 || D <= 0 || D % 32) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: need B >= 0, N >= 0, D % 32 == 0");
+    if (!gallery && !gallery_bf16) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: gallery and gallery_bf16 are both NULL");
+    if (B && (!q || !out_scores || !out_idx)) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: NULL argument");
+    if (gallery && gallery_bf16 && !meta) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: the pre-filtered form needs meta from fern_gallery_prepare");
+    const bool sweep_ok = D % 64 == 0 && D <= 768;      // the bf16 sweep's shapes
+    if (!gallery && !sweep_ok) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: a bf16-only gallery needs D % 64 == 0, D <= 768");
+    if (N > 0x7FFFFFF0LL) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: N too large for int32 indices");
+    const long ld = std::max<long>(4, (N + 3) & ~3L);
+    // queries per chunk: the [m, ld] fp32 score matrix stays within the dense form's budget (rank_strategy_for)
+    const long chunk = std::min<long>((long)kRankQueryChunk, (long)(1.1e9 / ((double)ld * 4)));
+    if (chunk < 1) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: one query's score row exceeds the 1.1 GB workspace budget");
+    if (!c) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: ctx is NULL");
+    enum { EXACT, PREFILTERED, BF16 } form = !gallery ? BF16 : (gallery_bf16 && sweep_ok && c->rank_strategy != FERN_RANK_PLAIN) ? PREFILTERED : EXACT;
+    if (N == 0) form = EXACT;                        // no scores to compute: the select kernel writes the -inf / -1 rows
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (B == 0) return FERN_OK;
+    for (long o = 0; o < B; o += chunk) {
+        const int m = (int)std::min<long>(chunk, B - o);
+        const int32_t* ex = exclude_idx ? exclude_idx + o : nullptr;
+        FERN_TRY(ws_begin(c, s));
+        float* S; int *flags, *state;
+        FERN_TRY(ws_get(c, (size_t)m * ld, &S));
+        FERN_TRY(ws_get(c, (size_t)4, &flags));
+        FERN_TRY(ws_get(c, (size_t)m, &state));
+        const float* qo = q + o * D;
+        StageTimer st(c, s);
+        st.sweep_begin();
+        if (form == EXACT) {
+            HIP_TRY(launch_deep_exact_scores(qo, gallery, m, N, D, S, ld, flags, state, 0, s));      // also zeroes flags
+            st.sweep_end((double)N * D * 4 + (double)m * D * 4 + (double)m * N * 4);
+        } else {
+            for (long b0 = 0; b0 < m; b0 += 64) {
+                const int mb = (int)std::min<long>(64, m - b0);
+                HIP_TRY(launch_sweep_bf16(qo + b0 * D, gallery_bf16, S + b0 * ld, ld, mb, N, D, N, 1, nullptr, nullptr, s, b0 == 0 ? flags : nullptr));
+                st.sweep_end((double)N * D * 2 + (double)mb * D * 4 + (double)mb * N * 4);
+            }
+        }
+        const bool pre = form == PREFILTERED;
+        HIP_TRY(launch_deep_select(S, ld, N, m, K, pre ? qo : nullptr, pre ? meta : nullptr, pre ? gallery : nullptr, D, ex, idx_offset,
+                                   out_scores + o * K, out_idx + o * K, flags, state, s));
+        if (N > 0) {
+            if (pre) HIP_TRY(launch_deep_exact_scores(qo, gallery, m, N, D, S, ld, flags, state, 1, s));
+            HIP_TRY(launch_deep_fallback(S, ld, N, m, K, ex, idx_offset, out_scores + o * K, out_idx + o * K, flags, state, s));
+        }
+        st.commit(m, (int)N, D);
+    }
     return FERN_OK;
 }
 

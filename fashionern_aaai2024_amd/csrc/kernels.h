@@ -433,5 +433,20 @@ hipError_t launch_topk_candidates(const TopkFilter& f, int B, int K, long idx_of
 // Merge R lists [R,B,K] (score, idx) -> [B,K]
 hipError_t launch_topk_merge(const float* scores, const int* idx, float* out_scores, int* out_idx, int R, int B, int K,
                              hipStream_t s);
+// ---- deep top-K (topk_deep.hip): 1 <= K <= 1024 on a stored score row per query ------------------------------------------------
+// S [B, ld] fp32 = exact chain scores of B queries against an fp32 gallery (deep_exact_scores_kernel: the MFMA sequence of
+// launch_rank_exact).  gated != 0: only if flags[0] is set, only the rows of queries with state[b] != 0; gated == 0 also zeroes flags[0..3].
+hipError_t launch_deep_exact_scores(const float* q, const float* gallery, int B, long N, int D, float* S, long ld, int* flags, const int* state,
+                                    int gated, hipStream_t s);
+// Per query the top-K keys of its score row S[b] (ld % 4 == 0): bound from row-group maxima, collection, bitonic sort in LDS.  q != null:
+// S holds bf16-sweep approximations, the certified margin (meta = fern_gallery_prepare's) selects survivors that are rescored exactly from
+// the fp32 `gallery` (D % 64 == 0, D <= 768).  A query without room sets state[b] = 1 and flags[0] = 1 (flags[0] zeroed before).
+hipError_t launch_deep_select(const float* S, long ld, long N, int B, int K, const float* q, const float* meta, const float* gallery, int D,
+                              const int* exclude, long idx_offset, float* out_scores, int* out_idx, int* flags, int* state, hipStream_t s);
+// Gated on flags[0] / state[b]: the exact top-K of S[b] by radix select (no capacity).
+hipError_t launch_deep_fallback(const float* S, long ld, long N, int B, int K, const int* exclude, long idx_offset, float* out_scores, int* out_idx,
+                                const int* flags, const int* state, hipStream_t s);
+// launch_topk_merge for 64 < K <= 1024, R * K <= 16 384.
+hipError_t launch_topk_merge_deep(const float* scores, const int* idx, float* out_scores, int* out_idx, int R, int B, int K, hipStream_t s);
 
 }  // namespace fern

@@ -13,6 +13,7 @@
 // reach a per-query bound to candidate lists; the two kernels here compute that bound from a row sample of the gallery
 // (topk_sample_bound_kernel) and select the exact top-K from the lists (topk_candidates_kernel).  kernels.h: TopkFilter.
 #include "kernels.h"
+#include "rescore.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -506,7 +507,6 @@ __global__ __launch_bounds__(256) void topk_candidates_kernel(TopkFilter f, int 
     }
 }
 
-typedef float f32x4e __attribute__((ext_vector_type(4)));
 // ---- certified pre-filter: select on the approximate keys, then rescore the survivors exactly ---------------------------------------
 // Final step of fern_sim_topk_prefiltered.  The candidate lists hold APPROXIMATE keys (bf16 sweep scores s~) of every row with
 // s~ >= (sample bound) - margin.  Per query (one workgroup): gather the lists as topk_candidates_kernel does, T~ = the K-th best
@@ -523,78 +523,8 @@ typedef float f32x4e __attribute__((ext_vector_type(4)));
 // exact K-th best too.
 constexpr int RESC_MAX = 1024;                  // survivors per query that are rescored here
 constexpr int RESC_PER = RESC_MAX / 256;
-constexpr int RESC_CH = 32;                     // k per step of the transposing tile
-constexpr int RESC_TLD = RESC_CH + 4;           // floats per tile row (+ 4: lane l's ds_read_b128 of row l starts 4 banks after lane l-1's)
-constexpr int RESC_ROWS = 32;                   // survivors per wave and round
 constexpr int RESC_TILE_FLOATS = 4 * 2 * RESC_ROWS * RESC_TLD;      // the four waves' tiles, double buffered
 
-// One wave, 32 survivors surv[s0 .. s0 + 32) (rows past ns redo survivor s0): their exact fp32 chains against qrow.  D = 32 nsteps k,
-// nsteps % RING == 0.  A step is four load instructions (8 rows x 32 floats each: whole 128-byte lines) whose registers go through
-// the wave's LDS tile so that lane l < 32 can continue survivor l's chain over those 32 k.  The loads of the next RING steps are always
-// in flight -- a register ring, a slot refilled right after its registers were written to the tile -- and the tile is double buffered:
-// step c + 1 is written while step c is read.  The loop body is BRANCH-FREE (loads past the row's end re-read its last step, the
-// tile write after the last step is never read): behind `if (c < nsteps)` guards the compiler waited for every load right after
-// issuing it (s_waitcnt vmcnt(0..3) in front of each tile write) and the ring was one deep.
-template <int RING>
-__device__ __forceinline__ float rescore_rows(const unsigned* surv, int s0, int ns, const float* qrow, const float* gallery, int D, float* tl) {
-    const int lane = threadIdx.x & 63;
-    const int lrow = lane >> 3, lcol = (lane & 7) * 4;       // loader role: row inside a group of 8, float offset inside a 32-float step
-    const int l31 = lane & 31;
-    const int nsteps = D / RESC_CH;
-    const float* src[4];
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-        const int r = s0 + rg * 8 + lrow;
-        src[rg] = gallery + (long)surv[r < ns ? r : s0] * D + lcol;
-    }
-    f32x4e reg[RING][4];
-#pragma unroll
-    for (int c = 0; c < RING; ++c)
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) reg[c][rg] = *reinterpret_cast<const f32x4e*>(src[rg] + c * RESC_CH);      // nsteps >= RING
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) *reinterpret_cast<f32x4e*>(tl + (rg * 8 + lrow) * RESC_TLD + lcol) = reg[0][rg];      // step 0's tile
-    {
-        const int cn = RING < nsteps ? RING : nsteps - 1;
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) reg[0][rg] = *reinterpret_cast<const f32x4e*>(src[rg] + cn * RESC_CH);
-    }
-    float acc = 0.0f;
-    for (int c0 = 0; c0 < nsteps; c0 += RING) {
-#pragma unroll
-        for (int cc = 0; cc < RING; ++cc) {
-            const int c = c0 + cc;
-            constexpr int TS = RESC_ROWS * RESC_TLD;
-            const int nslot = (cc + 1) % RING;
-            float* nt = tl + ((cc + 1) & 1) * TS;            // RING is even: step c + 1's buffer parity is static
-#pragma unroll
-            for (int rg = 0; rg < 4; ++rg) *reinterpret_cast<f32x4e*>(nt + (rg * 8 + lrow) * RESC_TLD + lcol) = reg[nslot][rg];
-            {
-                const int cn = c + 1 + RING < nsteps ? c + 1 + RING : nsteps - 1;
-#pragma unroll
-                for (int rg = 0; rg < 4; ++rg) reg[nslot][rg] = *reinterpret_cast<const f32x4e*>(src[rg] + cn * RESC_CH);
-            }
-            const float* mrow = tl + (cc & 1) * TS + l31 * RESC_TLD;
-            const float* qk = qrow + c * RESC_CH;
-            f32x4e gg[RESC_CH / 4], qq[RESC_CH / 4];
-#pragma unroll
-            for (int g4 = 0; g4 < RESC_CH / 4; ++g4) {
-                gg[g4] = *reinterpret_cast<const f32x4e*>(mrow + g4 * 4);
-                qq[g4] = *reinterpret_cast<const f32x4e*>(qk + g4 * 4);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // this step's reads (and the next step's tile writes) are done
-#pragma unroll
-            for (int g8 = 0; g8 < RESC_CH / 8; ++g8) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    acc = __builtin_fmaf(qq[2 * g8][e], gg[2 * g8][e], acc);
-                    acc = __builtin_fmaf(qq[2 * g8 + 1][e], gg[2 * g8 + 1][e], acc);
-                }
-            }
-        }
-    }
-    return acc;
-}
 
 // Exact scores of the survivors surv[0..ns) of query row `qrow` (LDS) and their ranking: the tail shared by the two rescoring
 // kernels.  Every thread of the 256-thread workgroup calls it.  A wave takes 32 survivors per round (rescore_rows).

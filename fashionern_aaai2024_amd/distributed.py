@@ -165,15 +165,18 @@ def build_gallery_from_shard(engine, shard_features: torch.Tensor, shard_local: 
 
 
 def rank_replicated(engine, queries: torch.Tensor, gallery: torch.Tensor, k: int, exclude_idx=None):
-    """Query-data-parallel ranking: this rank's queries against the replicated gallery.  No collective."""
+    """Query-data-parallel ranking: this rank's queries against the replicated gallery.  No collective.  k > 64: the deep ranking."""
+    if k > 64:
+        return engine.sim_topk_deep(queries, gallery, k, exclude_idx=exclude_idx)
     return engine.sim_topk(queries, gallery, k, exclude_idx=exclude_idx)
 
 
 def rank_sharded(engine, queries: torch.Tensor, gallery_shard: torch.Tensor, shard_start: int, k: int, exclude_idx=None):
     """Gallery-sharded ranking of the SAME query batch on every rank: local top-K with global indices, all-gather of
-    the [B, K] candidates, merge.  Returns the global (scores, idx) on every rank."""
+    the [B, K] candidates, merge.  Returns the global (scores, idx) on every rank.  k > 64: the deep ranking and the wide merge."""
     rank, world = world_info()
-    s, i = engine.sim_topk(queries, gallery_shard, k, idx_offset=shard_start, exclude_idx=exclude_idx)
+    rank_fn = engine.sim_topk_deep if k > 64 else engine.sim_topk
+    s, i = rank_fn(queries, gallery_shard, k, idx_offset=shard_start, exclude_idx=exclude_idx)
     if world == 1:
         return s, i
     b, kk = s.shape

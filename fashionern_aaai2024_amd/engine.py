@@ -378,6 +378,35 @@ class FernEngine:
                                                       _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_prefiltered")
         return scores, idx
 
+    def sim_topk_deep(self, q, gallery, k: int, idx_offset: int = 0, exclude_idx=None):
+        """Exact top-K for 1 <= k <= 1024 (include/fern.h: fern_sim_topk_deep); `sim_topk` stops at 64.  `gallery` is an fp32
+        tensor (exact fp32-chain scores), a `PreparedGallery` (the same bits through the certified bf16 pre-filter) or a bf16
+        tensor (the bf16 similarity of `sim_topk_bf16`).  For k' <= 64 the first k' columns equal those of the K <= 64 call."""
+        q = self._f32(q)
+        g32 = g16 = meta = None
+        if isinstance(gallery, PreparedGallery):
+            g32, g16, meta = gallery.f32, gallery.bf16, gallery.meta
+        elif isinstance(gallery, torch.Tensor) and gallery.dtype == torch.bfloat16:
+            if not gallery.is_cuda or not gallery.is_contiguous():
+                raise ValueError("a bf16 gallery must be a contiguous device tensor")
+            g16 = gallery
+        else:
+            g32 = self._f32(gallery)
+        g = g32 if g32 is not None else g16
+        if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+            raise ValueError(f"q [B,D] and gallery [N,D] must share D, got {tuple(q.shape)} and {tuple(g.shape)}")
+        b = q.shape[0]
+        scores = self._empty(b, k)
+        idx = self._empty(b, k, dtype=torch.int32)
+        ex = None
+        if exclude_idx is not None:
+            ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(ex.shape) != (b,):
+                raise ValueError("exclude_idx must be [B]")
+        _lib.check(self.lib.fern_sim_topk_deep(self._h, _ptr(q), _ptr(g32), _ptr(g16), _ptr(meta), b, g.shape[0], q.shape[1], int(k),
+                                               _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_deep")
+        return scores, idx
+
     def gallery_to_bf16(self, gallery) -> torch.Tensor:
         """fp32 [N,D] -> bf16 [N,D] (round to nearest even) for `sim_topk_bf16`."""
         g = self._f32(gallery)

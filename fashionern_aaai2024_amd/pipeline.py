@@ -185,7 +185,9 @@ class ComposedQueryPipeline:
             ref = eng.encode_image(images) if ref_feats is None else ref_feats
             tg, ts = eng.encode_text(tokens)
         fused = eng.dvr_fuse(ref, local, tg, ts)
-        if gallery.dtype == torch.bfloat16:
+        if k > 64:                                              # deep ranking: every gallery form (fp32, PreparedGallery, bf16)
+            scores, idx = eng.sim_topk_deep(fused, gallery, k, idx_offset=idx_offset, exclude_idx=exclude_idx)
+        elif gallery.dtype == torch.bfloat16:
             scores, idx = eng.sim_topk_bf16(fused, gallery, k, idx_offset=idx_offset, exclude_idx=exclude_idx)
         else:
             scores, idx = eng.sim_topk(fused, gallery, k, idx_offset=idx_offset, exclude_idx=exclude_idx)

@@ -323,12 +323,27 @@ FERN_API int fern_rank_set_strategy(fern_ctx* ctx, int strategy);
  * certificate (|exact - approximate| <= eps_b) and for callers that want the whole approximate score matrix. */
 FERN_API int fern_sweep_bf16_scores(fern_ctx* c, const float* q, const uint16_t* gallery_bf16, int B, int64_t N, int D, float* scores, int64_t ld,
                                     float* tile_max, int64_t ldt, void* stream);
+/* Deep ranking: the exact top-K for 1 <= K <= 1024 (the K <= 64 entry points above stop at 64).  Output contract of fern_sim_topk:
+ * score descending, then gallery index ascending; idx_offset / exclude_idx as there; unfilled slots -inf / -1 when K > N.  The gallery
+ * form follows from the pointers given:
+ *   gallery only                      exact: the fp32 fma-chain scores of fern_sim_topk (oracle/chain.c order), whatever fern_set_precision says;
+ *   gallery + gallery_bf16 + meta     exact through the certified bf16 pre-filter (fern_gallery_prepare): the same bits as the exact form.
+ *                                     Shapes the bf16 sweep does not cover (D % 64 != 0, D > 768) and FERN_RANK_PLAIN run the exact form;
+ *   gallery_bf16 only                 bf16 similarity (fern_sim_topk_bf16's contract): the scores fern_sweep_bf16_scores produces, ranked
+ *                                     exactly on those values.  Needs D % 64 == 0, D <= 768.
+ * For K' <= 64 the first K' columns equal what fern_sim_topk / _prefiltered / _bf16 return for K', bit for bit.  The stage stores the
+ * [m, N] scores of a query chunk (m queries within a 1.1 GB workspace), selects per query in LDS and rescores the pre-filter's survivors;
+ * a query without room (tie floods) is ranked by a capacity-free exact pass inside the same call, with nothing read back to the host. */
+FERN_API int fern_sim_topk_deep(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                                const uint16_t* gallery_bf16 /*[N,D] or NULL*/, const float* meta /*[4] device or NULL*/, int B, int64_t N,
+                                int D, int K, float* out_scores /*[B,K]*/, int32_t* out_idx /*[B,K]*/, int64_t idx_offset,
+                                const int32_t* exclude_idx, void* stream);
 /* scores of explicitly named gallery rows (CIRR subset ranking, run/test/test_cirr.py:64-66);
  * idx < 0 -> -inf */
 FERN_API int fern_gather_scores(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D]*/,
                        const int32_t* idx /*[B,m]*/, float* out /*[B,m]*/, int B, int m, int D,
                        void* stream);
-/* merge R per-shard top-K lists (gallery sharded over R GPUs; SURVEY.md 8e alternative) */
+/* merge R per-shard top-K lists (gallery sharded over R GPUs; SURVEY.md 8e alternative); 1 <= K <= 1024, R * K <= 16384 when K > 64 */
 FERN_API int fern_topk_merge(fern_ctx* ctx, const float* scores /*[R,B,K]*/, const int32_t* idx /*[R,B,K]*/,
                     float* out_scores /*[B,K]*/, int32_t* out_idx /*[B,K]*/, int R, int B, int K,
                     void* stream);

@@ -1,0 +1,115 @@
+"""Deep ranking without a GPU: the C ABI entry point fern_sim_topk_deep (header, library, ctypes table), its argument checks, and the
+k > 64 routing of distributed.rank_replicated / rank_sharded to sim_topk_deep and the wide topk_merge (world 2 over gloo)."""
+import os
+import re
+import socket
+import sys
+
+import numpy as np
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+
+
+def test_deep_entry_point_is_declared_exported_and_typed():
+    from fashionern_aaai2024_amd import _lib
+    header = open(os.path.join(ROOT, "include", "fern.h")).read()
+    assert re.search(r"FERN_API int fern_sim_topk_deep\(", header)
+    lib = _lib.load()
+    assert hasattr(lib, "fern_sim_topk_deep")
+    res, args = _lib.SIGNATURES["fern_sim_topk_deep"]
+    assert len(args) == 14
+    assert lib.fern_abi_version() == 3
+
+
+def test_deep_argument_errors_name_the_function():
+    from fashionern_aaai2024_amd import _lib
+    lib = _lib.load()
+    p = 0x1000                                           # never dereferenced: every call below is refused before any HIP call
+    calls = [
+        dict(K=0), dict(K=1025), dict(gallery=None, gallery_bf16=None), dict(out_scores=None), dict(out_idx=None), dict(q=None),
+        dict(meta=None, gallery_bf16=p), dict(gallery=None, gallery_bf16=p, D=96), dict(D=30),
+    ]
+    for bad in calls:
+        a = dict(ctx=None, q=p, gallery=p, gallery_bf16=None, meta=None, B=2, N=10, D=64, K=100, out_scores=p, out_idx=p)
+        a.update(bad)
+        rc = lib.fern_sim_topk_deep(a["ctx"], a["q"], a["gallery"], a["gallery_bf16"], a["meta"], a["B"], a["N"], a["D"], a["K"],
+                                    a["out_scores"], a["out_idx"], 0, None, None)
+        assert rc == -1, bad
+        assert b"fern_sim_topk_deep" in lib.fern_last_error(), bad
+    # K up to 1024 passes the argument checks (then the NULL context is refused)
+    assert lib.fern_sim_topk_deep(None, p, p, None, None, 2, 10, 64, 1024, p, p, 0, None, None) == -1
+    assert b"ctx is NULL" in lib.fern_last_error()
+    assert lib.fern_topk_merge(None, p, p, p, p, 2, 1, 1025, None) == -1
+    assert b"fern_topk_merge" in lib.fern_last_error()
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    return port
+
+
+def _worker(rank, world, port, out_dir):
+    sys.path.insert(0, HERE)
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    torch.set_num_threads(2)
+    from oracle_engine import OracleEngine
+    from fashionern_aaai2024_amd import distributed as fd
+
+    class DeepStub(OracleEngine):
+        """OracleEngine with the deep entry point and a record of what the ranking helpers called."""
+        def __init__(self):
+            super().__init__()
+            self.calls = []
+
+        def sim_topk(self, q, gallery, k, idx_offset=0, exclude_idx=None):
+            self.calls.append(("sim_topk", k))
+            return super().sim_topk(q, gallery, k, idx_offset, exclude_idx)
+
+        def sim_topk_deep(self, q, gallery, k, idx_offset=0, exclude_idx=None):
+            self.calls.append(("sim_topk_deep", k))
+            return super().sim_topk(q, gallery, k, idx_offset, exclude_idx)
+
+        def topk_merge(self, scores, idx):
+            self.calls.append(("topk_merge", scores.shape[2]))
+            return super().topk_merge(scores, idx)
+
+    fd.init_from_env("gloo")
+    n, d = 701, 32
+    g = torch.Generator().manual_seed(5)
+    gallery = torch.nn.functional.normalize(torch.randn(n, d, generator=g), dim=-1)
+    q = torch.nn.functional.normalize(torch.randn(6, d, generator=g), dim=-1)
+    eng = DeepStub()
+    s_rep, i_rep = fd.rank_replicated(eng, q, gallery, 200)
+    start, stop, _ = fd.shard_rows(n, rank, world)
+    ex = torch.tensor([3, -1, n - 1, 0, 5, 400], dtype=torch.int32)
+    s_sh, i_sh = fd.rank_sharded(eng, q, gallery[start:stop], start, 200, exclude_idx=ex)
+    small = fd.rank_replicated(eng, q, gallery, 7)
+    np.savez(os.path.join(out_dir, f"r{rank}.npz"), s_rep=s_rep.numpy(), i_rep=i_rep.numpy(), s_sh=s_sh.numpy(), i_sh=i_sh.numpy(),
+             calls=np.array([f"{a}:{b}" for a, b in eng.calls]), small=small[1].numpy())
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_distributed_ranking_routes_deep_k(tmp_path):
+    from oracle import rank as orank
+    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    n, d = 701, 32
+    g = torch.Generator().manual_seed(5)
+    gallery = torch.nn.functional.normalize(torch.randn(n, d, generator=g), dim=-1)
+    q = torch.nn.functional.normalize(torch.randn(6, d, generator=g), dim=-1)
+    ex = torch.tensor([3, -1, n - 1, 0, 5, 400], dtype=torch.int32)
+    rs, ri = orank.cosine_topk(q, gallery, 200)
+    ss, si = orank.cosine_topk(q, gallery, 200, 0, ex)
+    for rank in range(2):
+        got = np.load(tmp_path / f"r{rank}.npz")
+        assert list(got["calls"]) == ["sim_topk_deep:200", "sim_topk_deep:200", "topk_merge:200", "sim_topk:7"]
+        assert np.array_equal(got["i_rep"], ri.numpy()) and np.array_equal(got["s_rep"], rs.numpy())
+        assert np.array_equal(got["i_sh"], si.numpy()) and np.array_equal(got["s_sh"], ss.numpy())
