@@ -93,6 +93,11 @@ SIGNATURES = {
                                c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "fern_attention_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                     c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "fern_layernorm_q": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_i64, c_i64,
+                                 c_int, c_float, c_void_p]),
+    "fern_attention_mx8": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
+                                   c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "fern_im2col_q": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p]),
     "fern_prof_enable": (c_int, [c_void_p, c_int]),
     "fern_prof_collect": (c_int, [c_void_p, C.POINTER(ProfStats)]),
     "fern_tuner_export": (c_i64, [C.c_char_p, c_i64]),

@@ -2413,6 +2413,83 @@ extern "C" int fern_attention_bf16(fern_ctx* c, const uint16_t* q, int64_t ldq, 
     return run_attention(c, a, (hipStream_t)stream);
 }
 
+// ---- the fused producers of the towers' operands (kernel-level parity tests): the launchers the blocks call, nothing else ----
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+extern "C" int fern_layernorm_q(fern_ctx* c, const void* x, int x_is_bf16, int64_t ldx, const float* gamma, const float* beta, int out_form,
+                                void* y, int64_t ldy, void* scales, int64_t scale_rows, int64_t rows, int d, float eps, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_layernorm_q: ctx is NULL");
+    if (rows < 0 || (out_form != FERN_QFORM_BF16 && out_form != FERN_QFORM_FP8 && out_form != FERN_QFORM_MX8))
+        return fail(FERN_ERR_ARG, "fern_layernorm_q: bad argument");
+    if (rows == 0) return FERN_OK;
+    if (!x || !gamma || !beta || !y || (out_form != FERN_QFORM_BF16 && !scales)) return fail(FERN_ERR_ARG, "fern_layernorm_q: NULL argument");
+    if (d <= 0 || d % 4 || d > 1280 || ldx < d || ldy < d || ldx % 4 || ldy % 4)
+        return fail(FERN_ERR_ARG, "fern_layernorm_q: need d % 4 == 0, d <= 1280, ld % 4 == 0, ld >= d");
+    if (misaligned16(x) || misaligned16(gamma) || misaligned16(beta) || misaligned16(y) || (scales && misaligned16(scales)))
+        return fail(FERN_ERR_ARG, "fern_layernorm_q: pointers must be 16-byte aligned");
+    if (out_form == FERN_QFORM_MX8 && (d % 128 || scale_rows < rows))
+        return fail(FERN_ERR_ARG, "fern_layernorm_q: the MX form needs d % 128 == 0 and scale_rows >= rows");
+    if (out_form != FERN_QFORM_MX8 && x_is_bf16) return fail(FERN_ERR_ARG, "fern_layernorm_q: bf16 rows are read by the MX form only");
+    HIP_TRY(hipSetDevice(c->device));
+    const hipStream_t s = (hipStream_t)stream;
+    if (out_form == FERN_QFORM_BF16)
+        HIP_TRY(launch_layernorm_bf16(static_cast<const float*>(x), gamma, beta, static_cast<unsigned short*>(y), rows, d, ldx, ldy, eps, s));
+    else if (out_form == FERN_QFORM_FP8)
+        HIP_TRY(launch_layernorm_fp8(static_cast<const float*>(x), gamma, beta, static_cast<unsigned char*>(y), static_cast<float*>(scales), rows, d,
+                                     ldx, ldy, eps, s));
+    else if (x_is_bf16)
+        HIP_TRY(launch_layernorm_mx8(nullptr, gamma, beta, static_cast<unsigned char*>(y), static_cast<unsigned char*>(scales), scale_rows, rows, d,
+                                     ldx, ldy, eps, s, static_cast<const unsigned short*>(x)));
+    else
+        HIP_TRY(launch_layernorm_mx8(static_cast<const float*>(x), gamma, beta, static_cast<unsigned char*>(y), static_cast<unsigned char*>(scales),
+                                     scale_rows, rows, d, ldx, ldy, eps, s));
+    return FERN_OK;
+}
+
+extern "C" int fern_attention_mx8(fern_ctx* c, const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v, int64_t ldv,
+                                  uint8_t* out, int64_t ldo, uint8_t* scales, int64_t scale_rows, int batch, int heads, int head_dim, int s_q,
+                                  int s_k, int causal, float scale, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_attention_mx8: ctx is NULL");
+    if (batch <= 0 || heads <= 0 || s_q <= 0 || s_k <= 0 || (causal && s_q != s_k) || s_k > (causal ? 96 : 224))
+        return fail(FERN_ERR_ARG, "fern_attention_mx8: bad shape");
+    const int64_t w = (int64_t)heads * head_dim;
+    if (head_dim <= 0 || head_dim % 32 || head_dim > 96 || w % 128)
+        return fail(FERN_ERR_ARG, "fern_attention_mx8: need head_dim % 32 == 0, head_dim <= 96, heads * head_dim % 128 == 0");
+    if (!q || !k || !v || !out || !scales) return fail(FERN_ERR_ARG, "fern_attention_mx8: NULL argument");
+    if (ldq % 8 || ldk % 8 || ldv % 8 || ldq < w || ldk < w || ldv < w || ldo % 16 || ldo < w || scale_rows < (int64_t)batch * s_q)
+        return fail(FERN_ERR_ARG, "fern_attention_mx8: need ldq / ldk / ldv % 8 == 0, ldo % 16 == 0, ld >= heads * head_dim, scale_rows >= batch * s_q");
+    if (misaligned16(q) || misaligned16(k) || misaligned16(v) || misaligned16(out))
+        return fail(FERN_ERR_ARG, "fern_attention_mx8: pointers must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    AttnParams a{nullptr, nullptr, nullptr, nullptr, (long)ldq, (long)ldk, (long)ldv, (long)ldo, batch, heads, head_dim, s_q, s_k, causal, scale,
+                 nullptr, q, k, v};
+    a.out_q8 = out; a.out_scales = scales; a.out_srows = scale_rows;
+    return run_attention(c, a, (hipStream_t)stream);
+}
+
+extern "C" int fern_im2col_q(fern_ctx* c, const float* images, int b, int img, int patch, int out_form, void* y, void* scales, int64_t scale_rows,
+                             void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_im2col_q: ctx is NULL");
+    if (b < 0 || (out_form != FERN_QFORM_BF16 && out_form != FERN_QFORM_MX8)) return fail(FERN_ERR_ARG, "fern_im2col_q: bad argument");
+    if (b == 0) return FERN_OK;
+    if (!images || !y || (out_form == FERN_QFORM_MX8 && !scales)) return fail(FERN_ERR_ARG, "fern_im2col_q: NULL argument");
+    const int d = 3 * patch * patch;
+    if (patch <= 0 || patch % 4 || img <= 0 || img % patch || d > 1280 || d % (out_form == FERN_QFORM_MX8 ? 128 : 32))
+        return fail(FERN_ERR_ARG, "fern_im2col_q: need patch % 4 == 0, img % patch == 0, 3 * patch^2 <= 1280 and % 32 (BF16) / % 128 (MX8) == 0");
+    const int grid = img / patch;
+    const int64_t rows = (int64_t)b * grid * grid;
+    if (out_form == FERN_QFORM_MX8 && scale_rows < rows) return fail(FERN_ERR_ARG, "fern_im2col_q: scale_rows >= rows");
+    if (misaligned16(images) || misaligned16(y) || (scales && misaligned16(scales)))
+        return fail(FERN_ERR_ARG, "fern_im2col_q: pointers must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    if (out_form == FERN_QFORM_BF16)
+        HIP_TRY(launch_im2col_bf16(images, static_cast<unsigned short*>(y), b, img, patch, grid, (hipStream_t)stream));
+    else
+        HIP_TRY(launch_im2col_mx8(images, static_cast<unsigned char*>(y), static_cast<unsigned char*>(scales), scale_rows, b, img, patch, grid,
+                                  (hipStream_t)stream));
+    return FERN_OK;
+}
+
 // The tuner's per-shape tile choices of this process (every context shares them), as text: one line per shape,
 // "f32|bf16|fp8 M N K epilogue loader|outflags cfg".  Returns the number of bytes the full text needs (excluding the
 // terminator); writes at most cap - 1 bytes + NUL.  A file of these lines, named by FERN_GEMM_TILES, pins the choices.

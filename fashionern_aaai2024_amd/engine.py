@@ -22,6 +22,7 @@ SR_TARGET, SR_DVR = 0, 1
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RELU, EPI_BIAS_RESIDUAL = 0, 1, 2, 3
 PART_DVR, PART_TARGET_SR, PART_TARGET_COMBINER, PART_ALL = 1, 2, 4, 7
 PREC_FP32, PREC_BF16, PREC_FP8, PREC_MX8, PREC_F32X3, PREC_MX8_MLP, PREC_MX8_IMG = 0, 1, 2, 3, 4, 5, 6
+QFORM_BF16, QFORM_FP8, QFORM_MX8 = 0, 1, 2
 _PREC_NAMES = {"fp32": PREC_FP32, "bf16": PREC_BF16, "fp8": PREC_FP8, "mx8": PREC_MX8, "f32x3": PREC_F32X3, "mx8mlp": PREC_MX8_MLP, "mx8img": PREC_MX8_IMG}
 PATCH_NUM = 13
 
@@ -504,21 +505,38 @@ class FernEngine:
                                           m, n, k, int(epilogue), int(bool(out_bf16)), _stream()), "fern_gemm_fp8")
         return out
 
-    def quantize_mx8(self, x):
-        """[R,C] fp32 or bf16 (C % 128 == 0) -> (e4m3fn bytes [R,C] as uint8, E8M0 block scales as uint8 [C/128, R, 4]):
-        scale byte of (row r, 32-k block b) = scales[b // 4, r, b % 4] (include/fern.h: fern_quantize_mx8)."""
+    def _mx_scales(self, d, rows, scale_rows=None, scales=None) -> torch.Tensor:
+        """The uint8 [d/128, scale_rows, 4] array an MX producer writes its E8M0 bytes into: `scales` when given (written in place;
+        bytes of rows >= `rows` are left as they are), else a new one with scale_rows (default: rows) rows."""
+        if scales is None:
+            return torch.empty(d // 128, rows if scale_rows is None else int(scale_rows), 4, dtype=torch.uint8, device=self.device)
+        if (scales.dtype != torch.uint8 or scales.device != self.device or not scales.is_contiguous() or scales.dim() != 3 or
+                scales.shape[0] != d // 128 or scales.shape[2] != 4 or (scale_rows is not None and scales.shape[1] != scale_rows)):
+            raise ValueError(f"scales must be a contiguous uint8 [{d // 128}, scale_rows, 4] tensor on {self.device}")
+        return scales
+
+    def quantize_mx8(self, x, scale_rows=None, scales=None):
+        """[R,C] fp32 or bf16 (C % 128 == 0) -> (e4m3fn bytes [R,C] as uint8, E8M0 block scales as uint8 [C/128, scale_rows, 4]):
+        scale byte of (row r, 32-k block b) = scales[b // 4, r, b % 4] (include/fern.h: fern_quantize_mx8).  scale_rows >= R (default
+        R); `scales`: an existing array to write into."""
         x = x.to(self.device).contiguous() if x.dtype == torch.bfloat16 else self._f32(x)
         rows, d = x.shape
         y = torch.empty(rows, d, dtype=torch.uint8, device=self.device)
-        sc = torch.empty(d // 128, rows, 4, dtype=torch.uint8, device=self.device)
-        _lib.check(self.lib.fern_quantize_mx8(self._h, _ptr(x), int(x.dtype == torch.bfloat16), d, _ptr(y), d, _ptr(sc), rows, rows, d,
+        sc = self._mx_scales(d, rows, scale_rows, scales)
+        _lib.check(self.lib.fern_quantize_mx8(self._h, _ptr(x), int(x.dtype == torch.bfloat16), d, _ptr(y), d, _ptr(sc), sc.shape[1], rows, d,
                                               _stream()), "fern_quantize_mx8")
         return y, sc
 
-    def gemm_mx8(self, a8, sa, w8, sw, bias=None, residual=None, epilogue=EPI_BIAS, out_bf16=False) -> torch.Tensor:
-        """Block-scaled fp8 GEMM on v_mfma_scale_f32_32x32x64_f8f6f4; operands and scales as quantize_mx8 returns them."""
+    def gemm_mx8(self, a8, sa, w8, sw, bias=None, residual=None, epilogue=EPI_BIAS, out_bf16=False, scale_rows_a=None,
+                 scale_rows_w=None) -> torch.Tensor:
+        """Block-scaled fp8 GEMM on v_mfma_scale_f32_32x32x64_f8f6f4; operands and scales as quantize_mx8 returns them.  The scale
+        layouts' row counts default to the arrays' middle dimension; a smaller count (>= M / N) reads a prefix of the array."""
         m, k = a8.shape
         n = w8.shape[0]
+        scale_rows_a = sa.shape[1] if scale_rows_a is None else int(scale_rows_a)
+        scale_rows_w = sw.shape[1] if scale_rows_w is None else int(scale_rows_w)
+        if sa.numel() < k // 128 * scale_rows_a * 4 or sw.numel() < k // 128 * scale_rows_w * 4:
+            raise ValueError("a scale array is smaller than its scale_rows layout")
         bias = None if bias is None else self._f32(bias, (n,))
         if residual is not None and out_bf16:      # the bf16 residual-stream form (include/fern.h: fern_gemm_mx8)
             if residual.dtype != torch.bfloat16 or tuple(residual.shape) != (m, n):
@@ -527,7 +545,7 @@ class FernEngine:
         else:
             residual = None if residual is None else self._f32(residual, (m, n))
         out = torch.empty(m, n, dtype=torch.bfloat16 if out_bf16 else torch.float32, device=self.device)
-        _lib.check(self.lib.fern_gemm_mx8(self._h, _ptr(a8), k, _ptr(sa), sa.shape[1], _ptr(w8), k, _ptr(sw), sw.shape[1], _ptr(bias),
+        _lib.check(self.lib.fern_gemm_mx8(self._h, _ptr(a8), k, _ptr(sa), scale_rows_a, _ptr(w8), k, _ptr(sw), scale_rows_w, _ptr(bias),
                                           _ptr(residual), _ptr(out), n, m, n, k, int(epilogue), int(bool(out_bf16)), _stream()), "fern_gemm_mx8")
         return out
 
@@ -580,6 +598,71 @@ class FernEngine:
         _lib.check(self.lib.fern_attention_bf16(self._h, _ptr(q), w, _ptr(k), w, _ptr(v), w, _ptr(out), w, b, heads, hd, sq, sk,
                                                 int(bool(causal)), sc, _stream()), "fern_attention_bf16")
         return out
+
+    def layernorm_q(self, x, gamma, beta, eps: float, out_form=QFORM_MX8, scale_rows=None, scales=None):
+        """LayerNorm written in a GEMM operand form through the towers' own launchers (include/fern.h: fern_layernorm_q).  x: [R, d]
+        fp32 (or bf16, MX form only) on the device; a view with a row stride (x.stride(0) % 4 == 0) is read in place.  Returns the bf16
+        [R, d] tensor (QFORM_BF16), (e4m3fn bytes [R, d] as uint8, fp32 row scales [R]) (QFORM_FP8) or (e4m3fn bytes, E8M0 scales
+        [d/128, scale_rows, 4]) (QFORM_MX8; `scales`: an existing array to write into, see quantize_mx8)."""
+        if not (isinstance(x, torch.Tensor) and x.device == self.device and x.dtype in (torch.float32, torch.bfloat16) and x.dim() == 2 and
+                x.stride(1) == 1):
+            x = self._f32(x)
+        rows, d = x.shape
+        gamma, beta = self._f32(gamma, (d,)), self._f32(beta, (d,))
+        bf16_in = x.dtype == torch.bfloat16
+        if out_form == QFORM_BF16:
+            y, sc, srows = torch.empty(rows, d, dtype=torch.bfloat16, device=self.device), None, 0
+        elif out_form == QFORM_FP8:
+            y, sc, srows = torch.empty(rows, d, dtype=torch.uint8, device=self.device), self._empty(rows), 0
+        elif out_form == QFORM_MX8:
+            y = torch.empty(rows, d, dtype=torch.uint8, device=self.device)
+            sc = self._mx_scales(d, rows, scale_rows, scales)
+            srows = sc.shape[1]
+        else:
+            raise ValueError(f"unknown operand form {out_form}")
+        _lib.check(self.lib.fern_layernorm_q(self._h, _ptr(x), int(bf16_in), x.stride(0), _ptr(gamma), _ptr(beta), int(out_form), _ptr(y), d,
+                                             _ptr(sc), srows, rows, d, float(eps), _stream()), "fern_layernorm_q")
+        return y if out_form == QFORM_BF16 else (y, sc)
+
+    def attention_mx8(self, q, k, v, heads: int, causal=False, scale=None, out=None, scale_rows=None, scales=None):
+        """attention_bf16 with the block-scaled output of FERN_PREC_MX8 / _MX8_IMG (include/fern.h: fern_attention_mx8): q/k/v bf16
+        [B,S,W] (fp32 inputs are rounded first) -> (e4m3fn bytes [B*Sq, ldo] as uint8, E8M0 scales [W/128, scale_rows, 4]).  `out`: an
+        existing uint8 [B*Sq, ldo] array to write into (columns >= W are not written), `scales` as in quantize_mx8."""
+        def b16(x):
+            if x.dtype != torch.bfloat16:
+                x3 = self._f32(x)
+                return self.to_bf16(x3.reshape(-1, x3.shape[-1])).reshape(x3.shape)
+            return x.to(self.device).contiguous()
+        q, k, v = b16(q), b16(k), b16(v)
+        b, sq, w = q.shape
+        sk = k.shape[1]
+        hd = w // heads
+        if out is None:
+            out = torch.empty(b * sq, w, dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or out.device != self.device or out.dim() != 2 or out.shape[0] != b * sq or out.shape[1] < w or out.stride(1) != 1:
+            raise ValueError(f"out must be a uint8 [{b * sq}, ldo >= {w}] tensor on {self.device}")
+        sc = self._mx_scales(w, b * sq, scale_rows, scales)
+        scl = float(scale) if scale is not None else hd ** -0.5
+        _lib.check(self.lib.fern_attention_mx8(self._h, _ptr(q), w, _ptr(k), w, _ptr(v), w, _ptr(out), out.stride(0), _ptr(sc), sc.shape[1],
+                                               b, heads, hd, sq, sk, int(bool(causal)), scl, _stream()), "fern_attention_mx8")
+        return out, sc
+
+    def im2col_q(self, images, patch: int, out_form=QFORM_MX8, scale_rows=None, scales=None):
+        """Patch rows of [b, 3, img, img] fp32 images in the patch embedding's operand form (include/fern.h: fern_im2col_q): the bf16
+        [b * (img/patch)^2, 3 * patch^2] tensor (QFORM_BF16) or (e4m3fn bytes as uint8, E8M0 scales [d/128, scale_rows, 4]) (QFORM_MX8)."""
+        x = self._f32(images)
+        b, _, img, _ = x.shape
+        rows, d = b * (img // patch) ** 2, 3 * patch * patch
+        if out_form == QFORM_BF16:
+            y, sc, srows = torch.empty(rows, d, dtype=torch.bfloat16, device=self.device), None, 0
+        elif out_form == QFORM_MX8:
+            y = torch.empty(rows, d, dtype=torch.uint8, device=self.device)
+            sc = self._mx_scales(d, rows, scale_rows, scales)
+            srows = sc.shape[1]
+        else:
+            raise ValueError(f"unknown operand form {out_form}")
+        _lib.check(self.lib.fern_im2col_q(self._h, _ptr(x), b, img, patch, int(out_form), _ptr(y), _ptr(sc), srows, _stream()), "fern_im2col_q")
+        return y if out_form == QFORM_BF16 else (y, sc)
 
     # ---- profiling ----------------------------------------------------------------------------
     def prof_enable(self, on: bool) -> None:

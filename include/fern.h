@@ -139,6 +139,13 @@ typedef enum {
     FERN_EPI_BIAS_RESIDUAL = 3  /* C = A W^T + bias + R  (R has leading dim ldc)  */
 } fern_epilogue;
 
+/* Operand forms the towers' producers write (fern_layernorm_q, fern_im2col_q) */
+typedef enum {
+    FERN_QFORM_BF16 = 0,        /* bf16, round to nearest even                                          */
+    FERN_QFORM_FP8 = 1,         /* e4m3fn with one fp32 scale per row (fern_quantize_rows_fp8's form)   */
+    FERN_QFORM_MX8 = 2          /* e4m3fn with one E8M0 byte per 32-element block (fern_quantize_mx8's) */
+} fern_qform;
+
 /* kernel-time accounting for bench.py's roofline block */
 typedef struct {
     double gemm_ms;        /* every fp32-MFMA GEMM launch: sum over its kernel dispatches of the dispatch's own begin -> end timestamps
@@ -403,6 +410,27 @@ FERN_API int fern_attention(fern_ctx* ctx, const float* q, int64_t ldq, const fl
 FERN_API int fern_attention_bf16(fern_ctx* ctx, const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v,
                         int64_t ldv, uint16_t* out, int64_t ldo, int batch, int heads, int head_dim, int s_q, int s_k,
                         int causal, float scale, void* stream);
+/* The producers that fuse a quantiser into another kernel, reached through the launchers the towers call, so that the dispatch under
+ * test is the production dispatch.  Arguments are validated before any HIP call.
+ * fern_layernorm_q: LayerNorm (eps, fp32 statistics) of rows [rows, d] read with stride ldx, written in `out_form` with stride ldy.
+ *   FERN_QFORM_BF16 / _FP8: x is fp32 (x_is_bf16 == 0), d % 4 == 0, d <= 1280; FP8: `scales` is float [rows] (max|y| / 448).
+ *   FERN_QFORM_MX8: x is fp32 or bf16 (x_is_bf16), d % 128 == 0, d <= 1280, `scales` uint8 in fern_quantize_mx8's layout with
+ *   scale_rows >= rows rows (bytes of rows >= `rows` are not written).  ldx / ldy % 4 == 0, >= d; x, gamma, beta, y and scales
+ *   16-byte aligned.  The launcher picks the kernel from the width, the strides and the alignment, as in the towers.
+ * fern_attention_mx8: fern_attention_bf16 whose output is e4m3fn bytes [batch * s_q, ldo] + E8M0 scales per 32 output columns
+ *   (fern_quantize_mx8's layout, scale_rows >= batch * s_q rows), quantised from the kernel's fp32 output values -- the MX operand of
+ *   the out-projection in FERN_PREC_MX8 / _MX8_IMG.  head_dim % 32 == 0, heads * head_dim % 128 == 0, ldo % 16 == 0.
+ * fern_im2col_q: the patch rows of [b, 3, img, img] fp32 images, row (image, gy, gx) = 3 x patch x patch pixels in (channel, y, x)
+ *   order, as FERN_QFORM_BF16 ([rows, d] uint16) or FERN_QFORM_MX8 ([rows, d] bytes + scales with scale_rows >= rows rows), with
+ *   rows = b * (img / patch)^2 and d = 3 * patch^2: the patch embedding's A operand.  patch % 4 == 0, img % patch == 0, d <= 1280;
+ *   d % 32 == 0 (BF16) or d % 128 == 0 (MX8). */
+FERN_API int fern_layernorm_q(fern_ctx* ctx, const void* x, int x_is_bf16, int64_t ldx, const float* gamma, const float* beta, int out_form,
+                     void* y, int64_t ldy, void* scales, int64_t scale_rows, int64_t rows, int d, float eps, void* stream);
+FERN_API int fern_attention_mx8(fern_ctx* ctx, const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v,
+                       int64_t ldv, uint8_t* out, int64_t ldo, uint8_t* scales, int64_t scale_rows, int batch, int heads,
+                       int head_dim, int s_q, int s_k, int causal, float scale, void* stream);
+FERN_API int fern_im2col_q(fern_ctx* ctx, const float* images, int b, int img, int patch, int out_form, void* y, void* scales,
+                  int64_t scale_rows, void* stream);
 
 /* The GEMM launchers time their tile candidates once per new shape (all candidates are bit-identical).  This
  * returns the choices made so far in this process as text, one line per shape ("f32|bf16|fp8 M N K epilogue loader cfg");

@@ -140,6 +140,20 @@ def _block(sd, prefix, x, heads, causal, prec=None):
     return _r(x + _linear(_r(h, reduced and prec != "mx8"), sd[prefix + ".mlp.c_proj.weight"], sd[prefix + ".mlp.c_proj.bias"], prec), stream_bf16)
 
 
+def _block_mixed(sd, prefix, x, heads, causal, attn_mx):
+    """The mixed blocks (csrc/api.hip: clip_block_mxmlp) over the fp32 residual stream.  FERN_PREC_MX8_MLP (attn_mx False): the
+    attention half in the bf16 form (LayerNorm-1 -> bf16, bf16 QKV stored as bf16, bf16 attention, bf16 out-proj), the MLP half
+    block-scaled (LayerNorm-2 -> e4m3fn + E8M0, c_fc, its GELU output quantised from fp32 with no bf16 round trip, c_proj).
+    FERN_PREC_MX8_IMG (attn_mx True): the attention half block-scaled too when head_dim % 32 == 0 (LayerNorm-1 -> MX, MX QKV
+    stored as bf16, bf16-operand attention whose fp32 output is block-quantised by the kernel, MX out-proj); any other head_dim
+    keeps the bf16 attention half, as the product does (qkv_mx)."""
+    hd = x.shape[-1] // heads
+    aprec = "mx8" if attn_mx and hd % 32 == 0 else "bf16"
+    x = x + _attention(sd, prefix + ".attn", _ln(sd, prefix + ".ln_1", x), heads, causal, aprec)
+    h = F.gelu(_linear(_ln(sd, prefix + ".ln_2", x), sd[prefix + ".mlp.c_fc.weight"], sd[prefix + ".mlp.c_fc.bias"], "mx8"))
+    return x + _linear(h, sd[prefix + ".mlp.c_proj.weight"], sd[prefix + ".mlp.c_proj.bias"], "mx8")
+
+
 def _block_cls(sd, prefix, x, heads, prec):
     """The last ViT block as the product evaluates it under a reduced precision: same arithmetic as ``_block`` restricted
     to the class row (the only row ln_post reads, modeling_clip.py:876-877) with fp32 operands, except the K/V projection
@@ -197,11 +211,14 @@ def encode_image(sd, cfg, images, precision="fp32"):
 
     ``precision="bf16"`` / ``"fp8"`` / ``"mx8"`` restate the product's reduced-precision modes (no reference counterpart;
     include/fern.h:fern_precision): the same arithmetic with the operands of the token-level block GEMMs rounded to
-    bfloat16, quantised to e4m3fn with per-token / per-channel scales, or to e4m3fn with one E8M0 scale per 32-element block."""
-    if precision not in ("fp32", "bf16", "fp8", "mx8"):
+    bfloat16, quantised to e4m3fn with per-token / per-channel scales, or to e4m3fn with one E8M0 scale per 32-element block.
+    ``"mx8mlp"`` / ``"mx8img"``: the mixed modes (``_block_mixed``) behind the bf16 modes' patch embedding and over their fp32
+    stream; the last block's K/V branch takes bf16 operands, as in the bf16 mode."""
+    if precision not in ("fp32", "bf16", "fp8", "mx8", "mx8mlp", "mx8img"):
         raise ValueError(precision)
     bf16 = precision != "fp32"
-    prec = None if precision == "fp32" else precision
+    mixed = precision in ("mx8mlp", "mx8img")
+    prec = None if precision == "fp32" else "bf16" if mixed else precision
     if getattr(cfg, "v_arch", "vit") == "resnet":
         if bf16:
             raise ValueError("reduced precisions are defined for the transformer towers only")
@@ -211,7 +228,7 @@ def encode_image(sd, cfg, images, precision="fp32"):
         # the block-scaled mode runs conv1 as a linear layer over patch rows ((channel, y, x) order) with block-scaled operands
         patches = F.unfold(images, kernel_size=cfg.patch_size, stride=cfg.patch_size).transpose(1, 2)    # [b, g*g, 3*P*P]
         x = _linear(patches, w.flatten(1), None, "mx8")
-    elif precision == "bf16" and w[0].numel() % 32 == 0 and w[0].numel() <= 1280:
+    elif precision in ("bf16", "mx8mlp", "mx8img") and w[0].numel() % 32 == 0 and w[0].numel() <= 1280:
         # the bf16-operand modes (round 6) run conv1 as a linear layer over bf16-rounded patch rows and the bf16 copy of its weight
         patches = F.unfold(images, kernel_size=cfg.patch_size, stride=cfg.patch_size).transpose(1, 2)    # [b, g*g, 3*P*P]
         x = _linear(patches, w.flatten(1), None, "bf16")
@@ -224,7 +241,10 @@ def encode_image(sd, cfg, images, precision="fp32"):
     if precision == "mx8" and cfg.v_layers > 1:
         x = _r(x, True)                                                 # ln_pre writes the mode's bf16 residual stream
     for i in range(cfg.v_layers - (1 if bf16 else 0)):
-        x = _block(sd, f"visual.transformer.resblocks.{i}", x, cfg.v_heads, causal=False, prec=prec)
+        if mixed:
+            x = _block_mixed(sd, f"visual.transformer.resblocks.{i}", x, cfg.v_heads, False, precision == "mx8img")
+        else:
+            x = _block(sd, f"visual.transformer.resblocks.{i}", x, cfg.v_heads, causal=False, prec=prec)
     if bf16:
         x = _block_cls(sd, f"visual.transformer.resblocks.{cfg.v_layers - 1}", x, cfg.v_heads, prec)
     pooled = _ln(sd, "visual.ln_post", x[:, 0])                         # :876-877
@@ -232,6 +252,10 @@ def encode_image(sd, cfg, images, precision="fp32"):
 
 
 def text_hidden(sd, cfg, text, precision="fp32"):
+    if precision not in ("fp32", "bf16", "fp8", "mx8", "mx8mlp", "mx8img"):
+        raise ValueError(precision)
+    if precision in ("mx8mlp", "mx8img"):
+        precision = "bf16"                                              # the mixed modes run the text tower on the bf16 block
     x = sd["token_embedding.weight"][text] + sd["positional_embedding"][: text.shape[1]]   # :204-232
     if precision == "mx8":
         x = _r(x, True)                                                 # the block-scaled mode's bf16 residual stream

@@ -21,8 +21,10 @@ class OracleEngine:
         self.precision = "fp32"
 
     def set_precision(self, precision):
+        # every name here is restated by oracle.clip (mx8mlp / mx8img: _block_mixed and the bf16 text tower); anything else is refused,
+        # never computed in another mode
         if precision not in ("fp32", "f32x3", "bf16", "fp8", "mx8", "mx8mlp", "mx8img"):
-            raise ValueError(precision)
+            raise ValueError(f"the oracle does not restate precision {precision!r}")
         self.precision = "fp32" if precision == "f32x3" else precision      # f32x3 is fp32-accurate: the fp32 oracle is its checker
 
     def close(self):

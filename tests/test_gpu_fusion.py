@@ -334,6 +334,61 @@ def test_clip_towers_mx8_precision(name, n):
     eng.close()
 
 
+# Cosine-error bounds of the mixed modes against their own restatement.  Measured on an MI355X (tiny-w256 / tiny-hd48 / ViT-B-16):
+# mx8img 2.7e-4 / 4.7e-7 / 8.1e-4, mx8mlp 7.7e-5 / 4.7e-7 / 4.0e-4 -- e4m3 rounding flips compounding over the layers, as in the
+# mx8 and fp8 modes.  The bounds keep a margin of about 2.5x over the largest value.
+MIXED_BOUNDS = {"mx8img": 2e-3, "mx8mlp": 1e-3}
+
+
+@pytest.mark.parametrize("name,n", [("tiny-w256", 4), ("tiny-hd48", 4), ("ViT-B-16", 3)])
+def test_clip_towers_mx8img_and_mx8mlp_precision(name, n):
+    """The mixed modes (FERN_PREC_MX8_MLP; FERN_PREC_MX8_IMG, the c5 default) against oracle.clip's restatement of their own rounding
+    points (_block_mixed: MX MLP half -- and for mx8img the MX attention half when head_dim % 32 == 0; tiny-hd48's head_dim 48 takes
+    the bf16 attention half -- over the fp32 stream, the bf16 text tower).  (1) close to the restatement, closer than to fp32 and to
+    the bf16 restatement; (2) the text features are the bf16 mode's; (3) batch invariance and a clean return to fp32."""
+    cfg = synth.CLIP_CONFIGS[name]
+    sd_np = synth.clip_state_dict(cfg, seed=11)
+    sd = ofusion.as_torch(sd_np)
+    eng = FernEngine("cuda:0")
+    eng.load_tensors(sd_np)
+    eng.finalize_clip(cfg)
+    imgs = _t(synth.images(n, cfg))
+    toks = _t(synth.captions(n, cfg))
+    fp32_img = eng.encode_image(imgs)
+    got, txt = {}, {}
+    for mode in ("mx8img", "mx8mlp"):
+        eng.set_precision(mode)
+        assert eng.precision == mode
+        got[mode] = eng.encode_image(imgs)
+        txt[mode] = eng.encode_text(toks)
+        assert torch.equal(eng.encode_image(imgs[1:2]), got[mode][1:2])      # block scales are per token: batch-invariant
+        assert torch.equal(eng.encode_text(toks[2:3])[0], txt[mode][0][2:3])
+    eng.set_precision("fp32")
+    assert torch.equal(eng.encode_image(imgs), fp32_img)
+    eng.close()
+
+    ref = {m: oclip.encode_image(sd, cfg, imgs, precision=m) for m in ("mx8img", "mx8mlp", "bf16", "fp32")}
+    rg_b, rs_b = oclip.encode_text(sd, cfg, toks, precision="bf16")
+
+    def cos_err(a, b):
+        return (1 - F.cosine_similarity(a.cpu().double().flatten(-1 if a.dim() == 2 else 1), b.double().flatten(-1 if b.dim() == 2 else 1), dim=-1)).abs().max().item()
+
+    for mode, other in (("mx8img", "mx8mlp"), ("mx8mlp", "mx8img")):
+        g, s = txt[mode]
+        e_own, e_other = cos_err(got[mode], ref[mode]), cos_err(got[mode], ref[other])
+        e_f, e_b = cos_err(got[mode], ref["fp32"]), cos_err(got[mode], ref["bf16"])
+        print(f"{mode} {name}: vs own restatement {e_own:.2e}, vs {other} {e_other:.2e}, vs bf16 {e_b:.2e}, vs fp32 {e_f:.2e}; "
+              f"text vs bf16 {cos_err(g, rg_b):.2e} / {cos_err(s, rs_b):.2e}")
+        assert e_own < MIXED_BOUNDS[mode]
+        assert e_own < e_f and e_own < e_b
+        # e_other is reported, not asserted: on tiny-hd48 (head_dim 48) the two modes are the same computation, so there is no
+        # separation to require; on the other towers it measured 2.4x - 16x
+        # the text tower is the bf16 block: the bf16 test's bounds
+        assert cos_err(g, rg_b) < 2e-5 and cos_err(s, rs_b) < 2e-5
+        assert _maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
+    assert not torch.equal(got["mx8img"], fp32_img) and not torch.equal(got["mx8mlp"], fp32_img)
+
+
 def test_mx8_precision_needs_widths_that_are_multiples_of_128():
     cfg = synth.CLIP_CONFIGS["tiny-hd64"]                              # ViT width 192
     eng = FernEngine("cuda:0")
@@ -413,14 +468,15 @@ def test_encoders_chunk_large_batches_without_changing_rows(precision):
     eng.close()
 
 
-@pytest.mark.parametrize("precision", ["fp32", "f32x3", "bf16", "mx8img"])
-@pytest.mark.parametrize("cfg_name,b", [("ViT-B-16", 64), ("ViT-B-16", 5), ("tiny", 7)])
+@pytest.mark.parametrize("cfg_name,b,precision", [(c, b, p) for c, b in [("ViT-B-16", 64), ("ViT-B-16", 5), ("tiny", 7)]
+                                                    for p in ["fp32", "f32x3", "bf16", "mx8img"]] +
+                         [("ViT-B-16", b, p) for b in (65, 130) for p in ("fp32", "mx8img")])
 def test_encode_pair_is_bit_identical_to_the_two_encoder_calls(cfg_name, b, precision):
     """fern_encode_pair (round 6): both towers of a query batch walked layer by layer, the text layer's GEMMs riding in the image layer's
     launches (gemm.hip: gemm_f32_pair_kernel, once the image GEMM's tuned plan is a mixed plan -- the second call of a shape).  Same tiles,
     same k order: image features, text global and text seq equal fern_vit_encode_image + fern_text_encode BIT FOR BIT, on the first call
     (two launches per pair while the shapes are tuned), on later calls (one launch), with pairing switched off by a forced tile, and in a
-    mode the library does not pair (bf16: the two calls)."""
+    mode the library does not pair (bf16: the two calls).  b = 65 / 130: the pair path cuts batches above 64 into chunks of 64."""
     from fashionern_aaai2024_amd.engine import FernEngine
     cfg = synth.CLIP_CONFIGS[cfg_name]
     eng = FernEngine("cuda:0")

@@ -38,6 +38,15 @@ def test_ctypes_loader_and_error_reporting_without_gpu():
     assert lib.fern_gemm_mx8(None, None, 0, None, 0, None, 0, None, 0, None, None, None, 0, 1, 1, 128, 0, 0, None) == -1
     assert lib.fern_gemm_mx8_quant(None, None, 0, None, 0, None, 0, None, 0, None, None, 0, None, 0, 1, 128, 128, 0, None) == -1
     assert b"fern_gemm_mx8_quant" in lib.fern_last_error()
+    # so do the producer entry points of the kernel-level parity tests
+    for name in ("fern_layernorm_q", "fern_attention_mx8", "fern_im2col_q"):
+        assert name in _lib.SIGNATURES
+    assert lib.fern_layernorm_q(None, None, 0, 128, None, None, 2, None, 128, None, 1, 1, 128, 1e-5, None) == -1
+    assert b"fern_layernorm_q: ctx is NULL" in lib.fern_last_error()
+    assert lib.fern_attention_mx8(None, None, 192, None, 192, None, 192, None, 64, None, 77, 1, 1, 64, 77, 77, 1, 0.125, None) == -1
+    assert b"fern_attention_mx8: ctx is NULL" in lib.fern_last_error()
+    assert lib.fern_im2col_q(None, None, 1, 224, 16, 2, None, None, 196, None) == -1
+    assert b"fern_im2col_q: ctx is NULL" in lib.fern_last_error()
 
 
 def test_code_object_targets_gfx950_only():
