@@ -95,6 +95,8 @@ struct ClipW {
     ResNetW res;
     fern_clip_config cfg{};
     const float *conv_w = nullptr, *cls = nullptr, *vpos = nullptr, *vproj_t = nullptr;
+    const float* conv_wp = nullptr;  // patch sides outside the 16-byte patch loaders (patch % 4 or 3 * patch^2 % 32, e.g. 14): conv1 as [width, conv_kp], zero padded
+    int conv_kp = 0;                 // 3 * patch^2 rounded up to 32 (588 -> 608); 0 = the im2col loaders take this patch
     LinearW conv_mx;                 // conv1 as a [width, 3 * patch * patch] linear layer: its block-scaled copy (FERN_PREC_MX8 patch embedding) and its bf16 copy (bf16-operand modes)
     LNW ln_pre, ln_post, ln_final;
     std::vector<ClipBlockW> vblocks, tblocks;
@@ -814,14 +816,23 @@ extern "C" int fern_finalize_clip(fern_ctx* c, const fern_clip_config* cfg) {
         FERN_TRY(finalize_resnet(c, cfg));
     } else if (cfg->v_layers > 0) {
         const int g = cfg->patch_size > 0 ? cfg->image_size / cfg->patch_size : 0;
-        if (bad(cfg->v_width, cfg->v_heads) || cfg->v_mlp % 32 || cfg->patch_size % 4 || g * cfg->patch_size != cfg->image_size ||
-            (3 * cfg->patch_size * cfg->patch_size) % 32 || g * g + 1 > 224)
+        if (bad(cfg->v_width, cfg->v_heads) || cfg->v_mlp % 32 || g <= 0 || g * cfg->patch_size != cfg->image_size || g * g + 1 > ATTN_MAX_KEYS)
             return fail(FERN_ERR_ARG, "clip: unsupported image tower shape");
         const int vw = cfg->v_width, P = cfg->patch_size, tokens = g * g + 1;
         FERN_TRY(up_key(c, "visual.conv1.weight", {vw, 3, P, P}, &W.conv_w));
         W.conv_mx = LinearW{W.conv_w, nullptr, vw, 3 * P * P};
-        FERN_TRY(make_mx8(c, &W.conv_mx));
-        FERN_TRY(make_bf16(c, &W.conv_mx));
+        if (P % 4 || (3 * P * P) % 32) {      // e.g. patch 14: fp32 patch rows + this padded copy, in every precision mode (vit_front): no bf16 / MX copy
+            const HostTensor* hw;
+            FERN_TRY(need(c, "visual.conv1.weight", {vw, 3, P, P}, &hw));
+            const int K = 3 * P * P, Kp = (K + 31) / 32 * 32;
+            std::vector<float> wp((size_t)vw * Kp, 0.f);
+            for (int o = 0; o < vw; ++o) std::copy(hw->f.data() + (size_t)o * K, hw->f.data() + (size_t)(o + 1) * K, wp.begin() + (size_t)o * Kp);
+            FERN_TRY(upload(c, wp.data(), wp.size(), &W.conv_wp));
+            W.conv_kp = Kp;
+        } else {
+            FERN_TRY(make_mx8(c, &W.conv_mx));
+            FERN_TRY(make_bf16(c, &W.conv_mx));
+        }
         FERN_TRY(up_key(c, "visual.class_embedding", {vw}, &W.cls));
         FERN_TRY(up_key(c, "visual.positional_embedding", {tokens, vw}, &W.vpos));
         FERN_TRY(up_ln(c, "visual.ln_pre", vw, &W.ln_pre));
@@ -1414,7 +1425,19 @@ static int vit_front(fern_ctx* c, const float* images, float* X, float* H, int b
     const ClipW& W = c->clip;
     const fern_clip_config& cf = W.cfg;
     const int vw = cf.v_width, g = cf.image_size / cf.patch_size, g2 = g * g, S = g2 + 1;
-    if (c->precision == FERN_PREC_MX8 && W.conv_mx.wm && (3 * cf.patch_size * cf.patch_size) <= 1280) {
+    if (W.conv_kp) {
+        // patch sides the 16-byte patch loaders do not take (14): fp32 patch rows zero-padded to conv_kp columns, then the plain-loader fp32
+        // GEMM against the padded weight; same epilogue.  Every precision mode: the reduced modes define no patch embedding for these shapes
+        const long rows = (long)b * g2;
+        float* P = H;
+        // H is [b * S, v_mlp] FLOATS in all three walkers (vit_chunk, pair_chunk, pair_chunk_mximg): element counts are compared
+        if ((size_t)rows * W.conv_kp > (size_t)b * S * cf.v_mlp) FERN_TRY(ws_get(c, (size_t)rows * W.conv_kp, &P));      // narrow MLPs (test towers)
+        HIP_TRY(launch_patch_rows_f32(images, P, b, cf.image_size, cf.patch_size, g, W.conv_kp, s));
+        LinearW conv{W.conv_wp, nullptr, vw, W.conv_kp};
+        GemmParams pp = gemm_desc(P, W.conv_kp, conv, X, vw, (int)rows, EPI_PATCH_EMBED);
+        pp.aux0 = W.vpos; pp.grid = g;
+        FERN_TRY(run_gemm(c, pp, s));
+    } else if (c->precision == FERN_PREC_MX8 && W.conv_mx.wm && (3 * cf.patch_size * cf.patch_size) <= 1280) {
         // block-scaled mode: patch rows are quantised once (H is free until the first block) and conv1 runs on the scaled MFMA;
         // same epilogue (positional embedding added, class slot skipped)
         const int kd = 3 * cf.patch_size * cf.patch_size;
@@ -1479,6 +1502,14 @@ static int text_tail(fern_ctx* c, const float* X, float* XN, const int* eot, flo
         FERN_TRY(run_gemm(c, gemm_desc(pooled, tw, proj, out_global, E, B, EPI_BIAS), s));
     }
     return FERN_OK;
+}
+
+// Images per chunk of the ViT walkers (vit_chunk, pair_chunk, pair_chunk_mximg): 64 up to 197 tokens -- what every tower before ViT-L/14 ran
+// with -- and beyond that as many as keep a chunk at those 64 x 197 = 12 608 token rows (257 tokens: 49 images, 577: 21), so the workspace
+// grows with the tower's width only.  Rows are batch-invariant: where a chunk ends changes no result.
+static int vit_chunk_images(const fern_clip_config& cf) {
+    const int g = cf.image_size / cf.patch_size, S = g * g + 1;
+    return std::max(1, std::min(64, 64 * 197 / S));
 }
 
 static int vit_chunk(fern_ctx* c, const float* images, float* out, int b, hipStream_t s) {
@@ -1618,7 +1649,7 @@ extern "C" int fern_vit_encode_image(fern_ctx* c, const float* images, float* ou
     const fern_clip_config& cf = c->clip.cfg;
     const long img_sz = 3L * cf.image_size * cf.image_size;
     const bool resnet = cf.v_arch == 1;
-    const int CH = resnet ? 128 : 64;      // the ResNet's late stages have few pixels per image: larger chunks fill the chip (M = 128 x 81 rows)
+    const int CH = resnet ? 128 : vit_chunk_images(cf);      // the ResNet's late stages have few pixels per image: larger chunks fill the chip (M = 128 x 81 rows)
     for (int o = 0; o < b; o += CH) {
         const int m = std::min(CH, b - o);
         FERN_TRY(ws_begin(c, s));
@@ -1701,14 +1732,8 @@ static int pair_chunk(fern_ctx* c, const float* images, float* out_img, const in
     FERN_TRY(ws_get(c, (size_t)Rt * tw, &ATTt));
     FERN_TRY(ws_get(c, (size_t)Rt * cf.t_mlp, &Ht));
     FERN_TRY(ws_get(c, (size_t)b, &eot));
-    // image tower front: conv1 as an im2col-free GEMM (epilogue adds the positional embedding), class token, ln_pre -- as vit_chunk
-    GemmParams pe{};
-    pe.A = images; pe.W = W.conv_w; pe.ldw = 3L * cf.patch_size * cf.patch_size; pe.C = X; pe.ldc = vw;
-    pe.M = b * g2; pe.N = vw; pe.K = 3 * cf.patch_size * cf.patch_size;
-    pe.epi = EPI_PATCH_EMBED; pe.aload = ALOAD_IM2COL; pe.aux0 = W.vpos;
-    pe.img = cf.image_size; pe.patch = cf.patch_size; pe.grid = g;
-    FERN_TRY(run_gemm(c, pe, s));
-    HIP_TRY(launch_vit_cls(W.cls, W.vpos, X, b, S, vw, s));
+    // image tower front: conv1 (epilogue adds the positional embedding), class token, ln_pre -- as vit_chunk
+    FERN_TRY(vit_front(c, images, X, H, b, s));
     HIP_TRY(launch_layernorm(X, nullptr, W.ln_pre.g, W.ln_pre.b, X, R, vw, vw, vw, 1e-5f, s));
     // text tower front -- as text_chunk
     HIP_TRY(launch_text_embed(tokens, W.tok_emb, W.tpos, Xt, eot, b, T, tw, cf.vocab_size, c->tok_flag, s));
@@ -1878,7 +1903,7 @@ extern "C" int fern_encode_pair(fern_ctx* c, const float* images, const int64_t*
     FERN_TRY(check_token_flag(c, "fern_encode_pair"));
     hipStream_t s = (hipStream_t)stream;
     const long img_sz = 3L * cf.image_size * cf.image_size;
-    const int CH = 64;                                      // vit_chunk's chunk: the pairing keeps the image tower's launch shapes
+    const int CH = vit_chunk_images(cf);                    // vit_chunk's chunk: the pairing keeps the image tower's launch shapes
     for (int o = 0; o < B; o += CH) {
         const int m = std::min(CH, B - o);
         FERN_TRY(ws_begin(c, s));
@@ -2450,7 +2475,7 @@ extern "C" int fern_attention_mx8(fern_ctx* c, const uint16_t* q, int64_t ldq, c
                                   uint8_t* out, int64_t ldo, uint8_t* scales, int64_t scale_rows, int batch, int heads, int head_dim, int s_q,
                                   int s_k, int causal, float scale, void* stream) {
     if (!c) return fail(FERN_ERR_ARG, "fern_attention_mx8: ctx is NULL");
-    if (batch <= 0 || heads <= 0 || s_q <= 0 || s_k <= 0 || (causal && s_q != s_k) || s_k > (causal ? 96 : 224))
+    if (batch <= 0 || heads <= 0 || s_q <= 0 || s_k <= 0 || (causal && s_q != s_k) || s_k > (causal ? 96 : ATTN_MAX_KEYS))
         return fail(FERN_ERR_ARG, "fern_attention_mx8: bad shape");
     const int64_t w = (int64_t)heads * head_dim;
     if (head_dim <= 0 || head_dim % 32 || head_dim > 96 || w % 128)

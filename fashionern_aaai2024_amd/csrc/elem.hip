@@ -533,6 +533,28 @@ __global__ __launch_bounds__(256) void im2col_bf16_kernel(const float* images, u
     }
 }
 
+// Patch sides the 16-byte patch loaders do not take (14: a patch row is 14 floats, K = 588 is not a multiple of 32): the patch rows as
+// fp32 in the same (channel, y, x) order, zero padded to kp columns (588 -> 608), for the plain-loader fp32 GEMM against the equally
+// padded conv1 weight.  Scalar reads: a patch row starts on no 16-byte boundary.
+__global__ __launch_bounds__(256) void patch_rows_f32_kernel(const float* images, float* y, long rows, int img, int patch, int grid, int kp) {
+    const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const int pp = patch * patch, d = 3 * pp, g2 = grid * grid;
+    const long b = row / g2;
+    const int gy = (int)(row % g2) / grid, gx = (int)(row % g2) % grid;
+    const float* src = images + b * 3L * img * img + (long)(gy * patch) * img + gx * patch;
+    float* yr = y + row * kp;
+    for (int k = lane; k < kp; k += 64) {
+        float v = 0.0f;
+        if (k < d) {
+            const int ch = k / pp, rem = k % pp;
+            v = src[((long)ch * img + rem / patch) * img + rem % patch];
+        }
+        yr[k] = v;
+    }
+}
+
 // bf16 or fp32 rows up to 4096 wide (a lane holds 8 consecutive elements: a 32-block is 4 lanes)
 __global__ __launch_bounds__(256) void quantize_mx8_kernel(const unsigned short* xb, const float* xf, long ldx, unsigned char* y, long ldy,
                                                            unsigned char* scales, long srows, long rows, int d) {
@@ -1022,6 +1044,13 @@ hipError_t launch_im2col_bf16(const float* images, unsigned short* y, int b, int
     const int d = 3 * patch * patch;
     if (d % 32 || d > 256 * MAXV || (patch & 3) || (img & 3) || grid * patch != img) return hipErrorInvalidValue;
     hipLaunchKernelGGL(im2col_bf16_kernel, row_grid(rows), dim3(256), 0, s, images, y, rows, img, patch, grid);
+    return hipGetLastError();
+}
+hipError_t launch_patch_rows_f32(const float* images, float* y, int b, int img, int patch, int grid, int kp, hipStream_t s) {
+    const long rows = (long)b * grid * grid;
+    if (rows <= 0) return hipSuccess;
+    if (patch <= 0 || grid * patch != img || kp < 3 * patch * patch || (kp & 3)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(patch_rows_f32_kernel, row_grid(rows), dim3(256), 0, s, images, y, rows, img, patch, grid, kp);
     return hipGetLastError();
 }
 hipError_t launch_quantize_mx8(const unsigned short* x_bf16, const float* x_f32, long ldx, unsigned char* y, long ldy, unsigned char* scales,

@@ -297,6 +297,7 @@ struct AttnParams {
     unsigned char* out_scales;
     long out_srows;
 };
+constexpr int ATTN_MAX_KEYS = 4096;      // validation bound of the non-causal forms (causal: 96, the text context)
 hipError_t launch_attention(const AttnParams& p, hipStream_t s);   // hipErrorInvalidValue for unsupported shapes
 
 // ---- row-wise / element-wise kernels (elem.hip) -------------------------------------------------
@@ -320,6 +321,8 @@ hipError_t launch_quantize_mx8(const unsigned short* x_bf16, const float* x_f32,
                                long srows, long rows, int d, hipStream_t s);
 // patch rows [b * grid * grid, 3 * patch * patch] of an image batch ((channel, y, x) order = conv1's weight layout), MX-quantised
 hipError_t launch_im2col_bf16(const float* images, unsigned short* y, int b, int img, int patch, int grid, hipStream_t s);
+// fp32 patch rows [b * grid * grid, kp], (channel, y, x) order, columns 3 * patch^2 .. kp zero: any patch side (the 16-byte loaders need patch % 4 == 0)
+hipError_t launch_patch_rows_f32(const float* images, float* y, int b, int img, int patch, int grid, int kp, hipStream_t s);
 hipError_t launch_im2col_mx8(const float* images, unsigned char* y, unsigned char* scales, long srows, int b, int img, int patch, int grid,
                              hipStream_t s);
 // mode 0: x / max(||x||, eps) (F.normalize); mode 1: x / (||x|| + eps) (VisualSR.l2norm)

@@ -111,8 +111,8 @@ def file_splits(kind, args, clip_model):
 def main(kind: str) -> None:
     p = ArgumentParser()
     p.add_argument("--dataset", default={"fiq": "fashionIQ", "val": "fashionIQ", "cirr": "CIRR", "shoes": "shoes", "200k": "fashion200k"}[kind], type=str)
-    p.add_argument("--input-dim", default=224, type=int, help="224 for ViT, 288 for RN50x4")
-    p.add_argument("--feature-dim", default=512, type=int, help="512 for ViT, 640 for RN50x4")
+    p.add_argument("--input-dim", default=224, type=int, help="the tower's image side: 224 for ViT-B-16 / ViT-B-32 / ViT-L-14, 336 for ViT-L-14-336, 288 for RN50x4")
+    p.add_argument("--feature-dim", default=512, type=int, help="the tower's embed_dim: 512 for ViT-B-16 / ViT-B-32, 768 for ViT-L-14 / ViT-L-14-336, 640 for RN50x4")
     p.add_argument("--patch-num", default=13, type=int)
     p.add_argument("--num-workers", type=int, default=0)
     p.add_argument("--batch-size", default=32, type=int)

@@ -178,6 +178,10 @@ class ClipConfig:
 CLIP_CONFIGS = {
     # open_clip "ViT-B-16" (run/test/test_fiq.py:134 default --clip-model-name)
     "ViT-B-16": ClipConfig("ViT-B-16", 512, 224, 16, 768, 12, 12, 3072, 77, 49408, 512, 8, 12, 2048),
+    # open_clip "ViT-L-14" / "ViT-L-14-336" (257 / 577 tokens, 14-pixel patches: K = 588) and "ViT-B-32"
+    "ViT-L-14": ClipConfig("ViT-L-14", 768, 224, 14, 1024, 24, 16, 4096, 77, 49408, 768, 12, 12, 3072),
+    "ViT-L-14-336": ClipConfig("ViT-L-14-336", 768, 336, 14, 1024, 24, 16, 4096, 77, 49408, 768, 12, 12, 3072),
+    "ViT-B-32": ClipConfig("ViT-B-32", 512, 224, 32, 768, 12, 12, 3072, 77, 49408, 512, 8, 12, 2048),
     # open_clip "RN50x4" (run/test/test_cirr.py:149 default): ModifiedResNet (4,6,10,6) width 80 @288 px, attention pool 40 heads
     "RN50x4": ClipConfig("RN50x4", 640, 288, 32, 0, 1, 0, 0, 77, 49408, 640, 10, 12, 2560, "resnet", (4, 6, 10, 6), 80, 40),
     "RN50x4-text": ClipConfig("RN50x4-text", 640, 288, 16, 768, 0, 12, 3072, 77, 49408, 640, 10, 12, 2560),
@@ -187,6 +191,10 @@ CLIP_CONFIGS = {
     "tiny-hd64": ClipConfig("tiny-hd64", 64, 48, 16, 192, 2, 3, 384, 77, 600, 128, 2, 2, 256),
     "tiny-w256": ClipConfig("tiny-w256", 64, 48, 16, 256, 3, 4, 512, 77, 600, 128, 2, 2, 256),     # widths % 128 == 0 (block-scaled fp8 mode)
     "tiny-hd48": ClipConfig("tiny-hd48", 64, 48, 16, 384, 2, 8, 768, 77, 600, 128, 2, 2, 256),     # head_dim 48: not a multiple of an MX block
+    # more than 224 tokens (streaming attention) and / or 14-pixel patches (padded fp32 patch embedding)
+    "tiny-p14": ClipConfig("tiny-p14", 64, 238, 14, 128, 2, 4, 512, 77, 600, 128, 2, 2, 256),          # 290 tokens, head_dim 32
+    "tiny-long": ClipConfig("tiny-long", 64, 272, 16, 256, 3, 4, 512, 77, 600, 128, 2, 2, 256),        # 290 tokens, head_dim 64, widths % 128 == 0
+    "tiny-p14-short": ClipConfig("tiny-p14-short", 64, 112, 14, 128, 2, 4, 512, 77, 600, 128, 2, 2, 256),   # 65 tokens: the patch path alone
 }
 
 

@@ -400,13 +400,16 @@ FERN_API int fern_gemm_mx8_quant(fern_ctx* ctx, const uint8_t* A, int64_t lda, c
 /* y = LayerNorm(x (+ residual)) * gamma + beta, rows of width d */
 FERN_API int fern_layernorm(fern_ctx* ctx, const float* x, const float* residual, const float* gamma,
                    const float* beta, float* y, int64_t rows, int d, float eps, void* stream);
-/* softmax(scale * Q K^T (+causal)) V per (batch, head); q/k/v row strides in floats */
+/* softmax(scale * Q K^T (+causal)) V per (batch, head); q/k/v row strides in floats.  head_dim % 4 == 0, <= 96; s_q and s_k are
+ * independent when not causal, s_k <= 4096 (up to 224 keys K / V stay resident in LDS, beyond that they stream through it in chunks of 128
+ * keys: the same arithmetic per (query, key) in the same order); causal: s_q == s_k <= 96. */
 FERN_API int fern_attention(fern_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
                    int64_t ldv, float* out, int64_t ldo, int batch, int heads, int head_dim, int s_q,
                    int s_k, int causal, float scale, void* stream);
 /* bf16 operand form (perf mode of the CLIP towers): q/k/v/out hold bf16 bit patterns (strides in elements, % 8 == 0);
  * QK^T and PV on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, `scale` applied to the fp32 scores, softmax statistics
- * in fp32, the un-normalised weights rounded to bf16 for the PV product.  head_dim % 8 == 0, <= 96; s_k <= 224. */
+ * in fp32, the un-normalised weights rounded to bf16 for the PV product.  head_dim % 8 == 0, <= 96; s_k <= 4096 (causal: <= 96),
+ * resident up to 224 keys and key-streaming beyond, as fern_attention. */
 FERN_API int fern_attention_bf16(fern_ctx* ctx, const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v,
                         int64_t ldv, uint16_t* out, int64_t ldo, int batch, int heads, int head_dim, int s_q, int s_k,
                         int causal, float scale, void* stream);
@@ -420,6 +423,7 @@ FERN_API int fern_attention_bf16(fern_ctx* ctx, const uint16_t* q, int64_t ldq, 
  * fern_attention_mx8: fern_attention_bf16 whose output is e4m3fn bytes [batch * s_q, ldo] + E8M0 scales per 32 output columns
  *   (fern_quantize_mx8's layout, scale_rows >= batch * s_q rows), quantised from the kernel's fp32 output values -- the MX operand of
  *   the out-projection in FERN_PREC_MX8 / _MX8_IMG.  head_dim % 32 == 0, heads * head_dim % 128 == 0, ldo % 16 == 0.
+ *   s_k <= 4096 (causal: <= 96); the key-streaming form past 224 keys stores the same way.
  * fern_im2col_q: the patch rows of [b, 3, img, img] fp32 images, row (image, gy, gx) = 3 x patch x patch pixels in (channel, y, x)
  *   order, as FERN_QFORM_BF16 ([rows, d] uint16) or FERN_QFORM_MX8 ([rows, d] bytes + scales with scale_rows >= rows rows), with
  *   rows = b * (img / patch)^2 and d = 3 * patch^2: the patch embedding's A operand.  patch % 4 == 0, img % patch == 0, d <= 1280;

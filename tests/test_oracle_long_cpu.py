@@ -1,0 +1,44 @@
+"""CPU: the oracle on the towers past 224 tokens / with 14-pixel patches against tests/golden/clip_long.npz (outputs of the in-tree
+CLIP statement, tools/make_goldens.py:clip_long_goldens).  Bounds: test_clip_oracle_matches_in_tree_statement's (2e-5 tiny, 2e-4 full
+size); measured 1.2e-6 on the tiny towers, 1.3e-6 on ViT-L-14."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from fashionern_aaai2024_amd import synth
+from oracle import clip as oclip, fusion as ofusion
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+CLIP_SEED, INPUT_SEED = 5, 42
+
+
+def t(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def test_long_tower_shapes():
+    assert synth.CLIP_CONFIGS["ViT-L-14"].v_tokens == 257
+    assert synth.CLIP_CONFIGS["ViT-L-14-336"].v_tokens == 577
+    assert synth.CLIP_CONFIGS["tiny-p14"].v_tokens == 290 and synth.CLIP_CONFIGS["tiny-long"].v_tokens == 290
+    assert synth.CLIP_CONFIGS["tiny-p14-short"].v_tokens == 65
+    assert synth.CLIP_CONFIGS["ViT-B-32"].v_tokens == 50
+
+
+@pytest.mark.parametrize("name,n_img,n_txt,tol", [("tiny-p14", 5, 0, 2e-5), ("tiny-long", 5, 0, 2e-5), ("ViT-L-14", 2, 2, 2e-4)])
+def test_clip_oracle_matches_in_tree_statement_long(name, n_img, n_txt, tol):
+    gold = np.load(os.path.join(GOLD, "clip_long.npz"))
+    cfg = synth.CLIP_CONFIGS[name]
+    sd = ofusion.as_torch(synth.clip_state_dict(cfg, seed=CLIP_SEED))
+    with torch.no_grad():
+        img = oclip.encode_image(sd, cfg, t(synth.images(n_img, cfg, INPUT_SEED)))
+        err = np.abs(img.numpy() - gold[f"{name}_image"]).max()
+        print(f"{name}: image max |d| {err:.2e}")
+        assert err < tol
+        for tag, full in (("full", True), ("ragged", False)) if n_txt else ():
+            toks = t(synth.captions(n_txt, cfg, INPUT_SEED, full_length=full))
+            g, s = oclip.encode_text(sd, cfg, toks)
+            es, eg = np.abs(s.numpy() - gold[f"{name}_text_{tag}_seq"]).max(), np.abs(g.numpy() - gold[f"{name}_text_{tag}_global"]).max()
+            print(f"{name}: text {tag} max |d| seq {es:.2e} global {eg:.2e}")
+            assert es < tol and eg < tol

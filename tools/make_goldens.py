@@ -9,6 +9,7 @@ the HIP path.
   fusion.npz   <- models.model.ERN (mode="test"/"index") and its sub-modules, D in {128, 512, 640}
   clip.npz     <- models/others/modeling_clip.py (the in-tree statement of CLIP arithmetic), executed
                   under the installed transformers package so its relative imports resolve
+  clip_long.npz <- the same for tiny-p14 / tiny-long / ViT-L-14 (patch 14, more than 224 tokens)
   loss.npz     <- losses.loss.BatchBasedClassificationLoss and ERN mode="train" (forward values only)
   harness.json/.npz <- run/test/test_{fiq,cirr,200k,shoes,val}.py compute_*_val_metrics and
                   utils.utils.extract_index_features on in-memory synthetic datasets with a stub CLIP
@@ -150,11 +151,12 @@ def to_hf_names(sd, cfg):
     return {k: t(np.ascontiguousarray(val)) for k, val in out.items()}
 
 
-def clip_goldens():
+def _clip_outputs(towers):
+    """Image (and, n_txt > 0, text) outputs of the in-tree CLIP statement for (name, images, captions) towers with synth weights."""
     mod = load_reference_clip_module()
     from transformers import CLIPConfig
     out = {}
-    for name, n_img, n_txt in (("tiny", 5, 6), ("tiny-hd64", 5, 6), ("ViT-B-16", 2, 2)):
+    for name, n_img, n_txt in towers:
         cfg = synth.CLIP_CONFIGS[name]
         hf = CLIPConfig(
             text_config=dict(vocab_size=cfg.vocab_size, hidden_size=cfg.t_width, intermediate_size=cfg.t_mlp,
@@ -174,14 +176,27 @@ def clip_goldens():
         imgs = t(synth.images(n_img, cfg, INPUT_SEED))
         with torch.no_grad():
             out[f"{name}_image"] = model.get_image_features(pixel_values=imgs).numpy()
-            for tag, full in (("full", True), ("ragged", False)):
+            for tag, full in (("full", True), ("ragged", False)) if n_txt else ():
                 toks = t(synth.captions(n_txt, cfg, INPUT_SEED, full_length=full))
                 tm = model.text_model(input_ids=toks)
                 hidden = tm[0]                       # final_layer_norm applied, modeling_clip.py:750
                 out[f"{name}_text_{tag}_seq"] = model.text_projection(hidden).numpy()
                 out[f"{name}_text_{tag}_global"] = model.get_text_features(input_ids=toks).numpy()
+    return out
+
+
+def clip_goldens():
+    out = _clip_outputs((("tiny", 5, 6), ("tiny-hd64", 5, 6), ("ViT-B-16", 2, 2)))
     np.savez_compressed(os.path.join(OUT, "clip.npz"), **out)
     print("clip.npz", {k: v.shape for k, v in out.items()})
+
+
+def clip_long_goldens():
+    """Towers past 224 tokens / with 14-pixel patches (the same recipe): tiny-p14, tiny-long (290 tokens) and ViT-L-14 (257 tokens; its
+    768-wide text tower is the only one no other fixture covers, so text outputs are kept for it alone)."""
+    out = _clip_outputs((("tiny-p14", 5, 0), ("tiny-long", 5, 0), ("ViT-L-14", 2, 2)))
+    np.savez_compressed(os.path.join(OUT, "clip_long.npz"), **out)
+    print("clip_long.npz", {k: v.shape for k, v in out.items()})
 
 
 # ------------------------------------------------------------------------------------------------
@@ -299,6 +314,6 @@ if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     only = sys.argv[1:]
-    for name, fn in (("fusion", fusion_goldens), ("clip", clip_goldens), ("harness", harness_goldens), ("loss", loss_goldens)):
+    for name, fn in (("fusion", fusion_goldens), ("clip", clip_goldens), ("clip_long", clip_long_goldens), ("harness", harness_goldens), ("loss", loss_goldens)):
         if not only or name in only:
             fn()
