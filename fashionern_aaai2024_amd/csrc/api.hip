@@ -2270,6 +2270,125 @@ extern "C" int fern_sim_topk_deep(fern_ctx* c, const float* q, const float* gall
     return FERN_OK;
 }
 
+// Exact target ranks (include/fern.h: fern_rank_keys, fern_rank_count).  A rank is the number of rows whose key is greater than the
+// target's, so the stage is one more sweep with a counting epilogue: no list, no capacity, no fallback, nothing read back.
+//   fp32 form   keys: the fma chain on the gathered rows (rank.hip); counts: the fp32 sweep with EPI_RANK_COUNT through run_gemm -- the
+//               tuner and the profiling hooks apply, the f32x3 split never does (PROF_SWEEP, and split_ok() does not list the epilogue)
+//   bf16 form   keys: the targets' rows as a small gallery through the bf16 sweep's store form; counts: the sweep's store form per query
+//               chunk (the deep stage's 1.1 GB budget) + a kernel that reads each stored score row once per RANKC_T targets
+static int rank_shape_check(const char* fn, fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                            int m) {
+    const std::string f(fn);
+    if (!c) return fail(FERN_ERR_ARG, f + ": ctx is NULL");
+    if (B < 0 || N < 0 || m < 1 || D <= 0) return fail(FERN_ERR_ARG, f + ": need B >= 0, N >= 0, m >= 1, D > 0");
+    if (N > 0 && !gallery && !gallery_bf16) return fail(FERN_ERR_ARG, f + ": gallery and gallery_bf16 are both NULL");
+    if (gallery || N == 0) {
+        if (D % 32) return fail(FERN_ERR_ARG, f + ": the fp32 form needs D % 32 == 0");
+    } else if (D % 64 || D > 768) {
+        return fail(FERN_ERR_ARG, f + ": a bf16-only gallery needs D % 64 == 0, D <= 768");
+    }
+    if (B && !q) return fail(FERN_ERR_ARG, f + ": NULL argument");
+    if (N > 0x7FFFFFF0LL) return fail(FERN_ERR_ARG, f + ": N too large for int32 indices");
+    return FERN_OK;
+}
+
+extern "C" int fern_rank_keys(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                              const int32_t* targets, int m, int64_t idx_offset, uint64_t* out_keys, void* stream) {
+    FERN_TRY(rank_shape_check("fern_rank_keys", c, q, gallery, gallery_bf16, B, N, D, m));
+    if (B && (!targets || !out_keys)) return fail(FERN_ERR_ARG, "fern_rank_keys: NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (B == 0) return FERN_OK;
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(out_keys);
+    if (gallery || N == 0) {
+        int stage;
+        FERN_TRY(prof_open(c, PROF_STAGE, 0, s, &stage));
+        HIP_TRY(launch_rank_keys(q, gallery, targets, B, N, D, m, idx_offset, keys, s));
+        return prof_close(c, stage, s);
+    }
+    // bf16 form: 64-query blocks, each against the 64 m gathered rows of its own targets
+    const long ld = ((long)64 * m + 3) & ~3L;
+    const long chunk = std::max<long>(64, std::min<long>((long)kRankQueryChunk, ((long)(256e6 / ((double)m * D * 2))) & ~63L));
+    for (long o = 0; o < B; o += chunk) {
+        const int mq = (int)std::min<long>(chunk, B - o);
+        FERN_TRY(ws_begin(c, s));
+        unsigned short* rows; float* S;
+        FERN_TRY(ws_get(c, (size_t)mq * m * D, &rows));
+        FERN_TRY(ws_get(c, (size_t)mq * ld, &S));
+        StageTimer st(c, s);
+        HIP_TRY(launch_rank_gather_bf16(gallery_bf16, targets + o * m, (long)mq * m, N, D, idx_offset, rows, s));
+        st.sweep_begin();
+        for (long b0 = 0; b0 < mq; b0 += 64) {
+            const int mb = (int)std::min<long>(64, mq - b0);
+            HIP_TRY(launch_sweep_bf16(q + (o + b0) * D, rows + b0 * m * D, S + b0 * ld, ld, mb, (long)mb * m, D, (long)mb * m, 1, nullptr, nullptr, s));
+            st.sweep_end((double)mb * m * D * 2 + (double)mb * D * 4 + (double)mb * mb * m * 4);
+        }
+        HIP_TRY(launch_rank_keys_from_scores(S, ld, targets + o * m, mq, N, m, idx_offset, keys + o * m, s));
+        st.commit(mq, (int)N, D);
+    }
+    return FERN_OK;
+}
+
+extern "C" int fern_rank_count(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                               const uint64_t* keys_in, int m, int64_t idx_offset, const int32_t* exclude_idx, int32_t* out_count, void* stream) {
+    FERN_TRY(rank_shape_check("fern_rank_count", c, q, gallery, gallery_bf16, B, N, D, m));
+    if (B && (!keys_in || !out_count)) return fail(FERN_ERR_ARG, "fern_rank_count: NULL argument");
+    const bool bf16_form = !gallery && N > 0;
+    const long ld = std::max<long>(4, (N + 3) & ~3L);
+    long chunk = (long)kRankQueryChunk;
+    if (bf16_form) {      // queries per chunk: the [m, ld] fp32 score matrix stays within the dense form's budget, whole 64-query sweep blocks
+        chunk = std::min<long>(chunk, (long)(1.1e9 / ((double)ld * 4)));
+        if (chunk < 1) return fail(FERN_ERR_ARG, "fern_rank_count: one query's score row exceeds the 1.1 GB workspace budget");
+        if (chunk > 64) chunk &= ~63L;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (B == 0) return FERN_OK;
+    const unsigned long long* keys = reinterpret_cast<const unsigned long long*>(keys_in);
+    for (long o = 0; o < B; o += chunk) {
+        const int mq = (int)std::min<long>(chunk, B - o);
+        const int32_t* ex = exclude_idx ? exclude_idx + o : nullptr;
+        FERN_TRY(ws_begin(c, s));
+        int* partial;
+        FERN_TRY(ws_get(c, (size_t)RANKC_P * mq * RANKC_T, &partial));
+        const size_t partial_bytes = (size_t)RANKC_P * mq * RANKC_T * sizeof(int);
+        auto pass = [&](int t0) {
+            return RankCount{keys + o * m + t0, partial, ex, (long)idx_offset, (long)idx_offset, m, std::min(RANKC_T, m - t0)};
+        };
+        if (!bf16_form) {
+            int stage;
+            FERN_TRY(prof_open(c, PROF_STAGE, 0, s, &stage));
+            for (int t0 = 0; t0 < m; t0 += RANKC_T) {
+                GemmParams p{};
+                p.A = q + o * D; p.lda = D; p.W = gallery; p.ldw = D; p.ldc = 4;
+                p.M = mq; p.N = (int)N; p.K = D; p.epi = EPI_RANK_COUNT; p.aload = ALOAD_PLAIN; p.rankc = pass(t0);
+                HIP_TRY(hipMemsetAsync(partial, 0, partial_bytes, s));
+                if (N > 0) FERN_TRY(run_gemm(c, p, s, PROF_SWEEP, (double)N * D * 4 + (double)mq * D * 4 + (double)mq * p.rankc.nt * 12));
+                HIP_TRY(launch_rank_finalize(p.rankc, mq, out_count + o * m + t0, m, s));
+            }
+            FERN_TRY(prof_close(c, stage, s));
+            continue;
+        }
+        float* S;
+        FERN_TRY(ws_get(c, (size_t)mq * ld, &S));
+        StageTimer st(c, s);
+        st.sweep_begin();
+        for (long b0 = 0; b0 < mq; b0 += 64) {
+            const int mb = (int)std::min<long>(64, mq - b0);
+            HIP_TRY(launch_sweep_bf16(q + (o + b0) * D, gallery_bf16, S + b0 * ld, ld, mb, N, D, N, 1, nullptr, nullptr, s));
+            st.sweep_end((double)N * D * 2 + (double)mb * D * 4 + (double)mb * N * 4);
+        }
+        for (int t0 = 0; t0 < m; t0 += RANKC_T) {
+            const RankCount rc = pass(t0);
+            HIP_TRY(hipMemsetAsync(partial, 0, partial_bytes, s));
+            HIP_TRY(launch_rank_count_rows(S, ld, mq, N, rc, s));
+            HIP_TRY(launch_rank_finalize(rc, mq, out_count + o * m + t0, m, s));
+        }
+        st.commit(mq, (int)N, D);
+    }
+    return FERN_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // image side: PIL-exact 8-bit resampling + ToTensor/Normalize
 // ------------------------------------------------------------------------------------------------

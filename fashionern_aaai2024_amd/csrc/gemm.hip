@@ -183,7 +183,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_f32_kernel(Ge
 // SPLIT = 3: the "f32x3" arithmetic (FERN_PREC_F32X3) -- fp32 operands split into three bf16 planes in registers, six
 // v_mfma_f32_32x32x16_bf16 per k pair of fp32 MFMAs (see the compute step below).
 template <int BM, int BN, int WM, int WN, int BKT, bool CONV = false, int SYNC = 0 /* 0: wait+barrier free to sink below the tail MFMAs (fastest), 1: drain copy first, 2: pinned after all MFMAs */,
-          bool FILT = false, int SPLIT = 0>
+          int FILT = 0 /* 1: EPI_TOPK_FILTER epilogue, 2: EPI_RANK_COUNT epilogue */, int SPLIT = 0>
 __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* smem) {
     constexpr int WAVES_N = BN / WN;
     constexpr int WAVES_M = BM / WM;
@@ -427,7 +427,8 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
         FERN_TRACE_MARK();
     }
     __builtin_amdgcn_s_setprio(0);
-    if (FILT) filter_epilogue<BM, BN, WM, WN, TM, TN>(p, acc, bm, bn, wm, wn, l31, lh);
+    if (FILT == 2) rank_count_epilogue<BM, BN, WM, WN, TM, TN>(p, acc, bm, bn, wm, wn, l31, lh, smem);
+    else if (FILT) filter_epilogue<BM, BN, WM, WN, TM, TN>(p, acc, bm, bn, wm, wn, l31, lh);
     else gemm_epilogue<BM, BN, WM, WN, TM, TN, WAVES_N>(p, acc, bm, bn, nbn, wm, wn, l31, lh, tid);
 #ifdef FERN_GEMM_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -438,7 +439,7 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
 
 // ONE __shared__ object per kernel: with a second LDS object next to the DMA destination hipcc drains the DMA (s_waitcnt vmcnt(0))
 // before the first ds_read of every k step, which serialises the copy and the MFMAs of a wave.
-template <int BM, int BN, int WM, int WN, int BKT, int MINW, bool CONV = false, int SYNC = 0, bool FILT = false, int SPLIT = 0>
+template <int BM, int BN, int WM, int WN, int BKT, int MINW, bool CONV = false, int SYNC = 0, int FILT = 0, int SPLIT = 0>
 __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, MINW) void gemm_f32_glds_kernel(GemmParams p) {
     __shared__ __attribute__((aligned(1024))) float smem[2 * (BM + BN) * BKT];
     if (p.gate && *p.gate == 0) return;
@@ -628,12 +629,12 @@ __global__ __launch_bounds__(SPLIT ? 256 : 512, SPLIT ? 2 : 4) void gemm_f32_mix
     constexpr int WMA = SPLIT ? BMA / 2 : 64, WNA = SPLIT ? BNA / 2 : 64;      // 2 x 2 fat waves, or 8 waves of 64x64
     if (bid < n_a8) {
         const int tiles = (ra / BMA) * ((p.N + BNA - 1) / BNA);
-        if (bid < tiles) glds_tile<BMA, BNA, WMA, WNA, 16, false, 0, false, SPLIT>(band(0, ra), bid, smem);
+        if (bid < tiles) glds_tile<BMA, BNA, WMA, WNA, 16, false, 0, 0, SPLIT>(band(0, ra), bid, smem);
     } else if (bid < n_a8 + n_b8) {
         const int tiles = ((rb - ra + 127) / 128) * ((p.N + 127) / 128);
-        if (bid - n_a8 < tiles) glds_tile<128, 128, 64, SPLIT ? 64 : 32, 16, false, 0, false, SPLIT>(band(ra, rb - ra), bid - n_a8, smem);
+        if (bid - n_a8 < tiles) glds_tile<128, 128, 64, SPLIT ? 64 : 32, 16, false, 0, 0, SPLIT>(band(ra, rb - ra), bid - n_a8, smem);
     } else {
-        glds_tile<64, 128, 32, SPLIT ? 64 : 32, 16, false, 0, false, SPLIT>(band(rb, p.M - rb), bid - n_a8 - n_b8, smem);
+        glds_tile<64, 128, 32, SPLIT ? 64 : 32, 16, false, 0, 0, SPLIT>(band(rb, p.M - rb), bid - n_a8 - n_b8, smem);
     }
 }
 
@@ -668,20 +669,20 @@ __global__ __launch_bounds__(SPLIT ? 256 : 512, SPLIT ? 2 : 4) void gemm_f32_pai
     const int n2 = n_d8 + n_e8;
     if (bid < n_d8) {
         const int tiles = (rb2 / 128) * ((p2.N + 127) / 128);
-        if (bid < tiles) glds_tile<128, 128, 64, WNS, 16, false, 0, false, SPLIT>(band(p2, 0, rb2), bid, smem);
+        if (bid < tiles) glds_tile<128, 128, 64, WNS, 16, false, 0, 0, SPLIT>(band(p2, 0, rb2), bid, smem);
     } else if (bid < n2) {
         const int tiles = ((p2.M - rb2 + 63) / 64) * ((p2.N + 127) / 128);
-        if (bid - n_d8 < tiles) glds_tile<64, 128, 32, WNS, 16, false, 0, false, SPLIT>(band(p2, rb2, p2.M - rb2), bid - n_d8, smem);
+        if (bid - n_d8 < tiles) glds_tile<64, 128, 32, WNS, 16, false, 0, 0, SPLIT>(band(p2, rb2, p2.M - rb2), bid - n_d8, smem);
     } else if (bid - n2 < n_a8) {
         const int b1 = bid - n2;
         const int tiles = (ra / BMA) * ((p.N + BNA - 1) / BNA);
-        if (b1 < tiles) glds_tile<BMA, BNA, WMA, WNA, 16, false, 0, false, SPLIT>(band(p, 0, ra), b1, smem);
+        if (b1 < tiles) glds_tile<BMA, BNA, WMA, WNA, 16, false, 0, 0, SPLIT>(band(p, 0, ra), b1, smem);
     } else if (bid - n2 < n_a8 + n_b8) {
         const int b1 = bid - n2 - n_a8;
         const int tiles = ((rb - ra + 127) / 128) * ((p.N + 127) / 128);
-        if (b1 < tiles) glds_tile<128, 128, 64, WNS, 16, false, 0, false, SPLIT>(band(p, ra, rb - ra), b1, smem);
+        if (b1 < tiles) glds_tile<128, 128, 64, WNS, 16, false, 0, 0, SPLIT>(band(p, ra, rb - ra), b1, smem);
     } else {
-        glds_tile<64, 128, 32, WNS, 16, false, 0, false, SPLIT>(band(p, rb, p.M - rb), bid - n2 - n_a8 - n_b8, smem);
+        glds_tile<64, 128, 32, WNS, 16, false, 0, 0, SPLIT>(band(p, rb, p.M - rb), bid - n2 - n_a8 - n_b8, smem);
     }
     (void)n_c8;
 }
@@ -887,6 +888,8 @@ bool gemm_force_cfg(int family, int cfg) {      // family 0: fp32 tiles, 1: f32x
     return true;
 }
 
+static bool epi_is_sweep(int e) { return e == EPI_TOPK_FILTER || e == EPI_RANK_COUNT; }      // nothing stored: the four LDS-DMA tiles with their own epilogues
+
 static int best_of(int M, int N, int first, int last) {
     int best = first;
     double best_cost = 1e300;
@@ -920,10 +923,21 @@ static hipError_t launch_cfg(int c, const GemmParams& p, hipStream_t s) {
     if (p.epi == EPI_TOPK_FILTER) {      // the filtered sweep: LDS-DMA family, own instantiations
         if (p.aload != ALOAD_PLAIN) return hipErrorInvalidValue;
         switch (c) {
-            case 8: FERN_LAUNCH((gemm_f32_glds_kernel<128, 128, 64, 64, 16, 2, false, 0, true>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 9: FERN_LAUNCH((gemm_f32_glds_kernel<64, 128, 32, 64, 16, 2, false, 0, true>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 10: FERN_LAUNCH((gemm_f32_glds_kernel<128, 64, 64, 32, 16, 2, false, 0, true>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 11: FERN_LAUNCH((gemm_f32_glds_kernel<64, 64, 32, 32, 16, 2, false, 0, true>), dim3(nb, ks), dim3(256), 0, s, p); break;
+            case 8: FERN_LAUNCH((gemm_f32_glds_kernel<128, 128, 64, 64, 16, 2, false, 0, 1>), dim3(nb, ks), dim3(256), 0, s, p); break;
+            case 9: FERN_LAUNCH((gemm_f32_glds_kernel<64, 128, 32, 64, 16, 2, false, 0, 1>), dim3(nb, ks), dim3(256), 0, s, p); break;
+            case 10: FERN_LAUNCH((gemm_f32_glds_kernel<128, 64, 64, 32, 16, 2, false, 0, 1>), dim3(nb, ks), dim3(256), 0, s, p); break;
+            case 11: FERN_LAUNCH((gemm_f32_glds_kernel<64, 64, 32, 32, 16, 2, false, 0, 1>), dim3(nb, ks), dim3(256), 0, s, p); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    if (p.epi == EPI_RANK_COUNT) {      // the counting sweep of the exact target ranks: the same four tiles, counting epilogue
+        if (p.aload != ALOAD_PLAIN || ks != 1) return hipErrorInvalidValue;
+        switch (c) {
+            case 8: FERN_LAUNCH((gemm_f32_glds_kernel<128, 128, 64, 64, 16, 2, false, 0, 2>), dim3(nb, ks), dim3(256), 0, s, p); break;
+            case 9: FERN_LAUNCH((gemm_f32_glds_kernel<64, 128, 32, 64, 16, 2, false, 0, 2>), dim3(nb, ks), dim3(256), 0, s, p); break;
+            case 10: FERN_LAUNCH((gemm_f32_glds_kernel<128, 64, 64, 32, 16, 2, false, 0, 2>), dim3(nb, ks), dim3(256), 0, s, p); break;
+            case 11: FERN_LAUNCH((gemm_f32_glds_kernel<64, 64, 32, 32, 16, 2, false, 0, 2>), dim3(nb, ks), dim3(256), 0, s, p); break;
             default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
@@ -960,7 +974,7 @@ static hipError_t launch_cfg(int c, const GemmParams& p, hipStream_t s) {
 }
 
 static bool skinny_form_ok(const GemmParams& p) {      // forms the 16x16 small-M kernel covers ...
-    return (p.K % 64) == 0 && p.aload == ALOAD_PLAIN && p.epi != EPI_SR_LOCAL && p.epi != EPI_PATCH_EMBED && p.epi != EPI_TOPK_FILTER;
+    return (p.K % 64) == 0 && p.aload == ALOAD_PLAIN && p.epi != EPI_SR_LOCAL && p.epi != EPI_PATCH_EMBED && !epi_is_sweep(p.epi);
 }
 static bool skinny_ok(const GemmParams& p) { return p.M <= 128 && skinny_form_ok(p); }      // ... and the shapes it is a candidate for on its own
 
@@ -1171,7 +1185,8 @@ static Plan tune_shape(const GemmParams& p, hipStream_t s, bool& tuned) {
     long out_rows = p.M;
     if (p.epi == EPI_PATCH_EMBED) out_rows = p.M + p.M / (p.grid * p.grid) + 2;
     const bool reduce = epi_is_reduce(p.epi);
-    const size_t scratch_floats = reduce ? (size_t)p.M * ((p.N + 31) / 32) : p.epi == EPI_TOPK_FILTER ? 4 : (size_t)out_rows * p.ldc;
+    const size_t scratch_floats = reduce ? (size_t)p.M * ((p.N + 31) / 32) : p.epi == EPI_TOPK_FILTER ? 4 :
+                                  p.epi == EPI_RANK_COUNT ? (size_t)RANKC_P * p.M * RANKC_T : (size_t)out_rows * p.ldc;
     float* scratch = nullptr;
     if (hipMalloc(&scratch, scratch_floats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fallback; }
     hipEvent_t e0, e1;
@@ -1182,6 +1197,7 @@ static Plan tune_shape(const GemmParams& p, hipStream_t s, bool& tuned) {
     if (reduce) q.partial = scratch;
     else q.C = scratch;       // residual input (p.R) is only read: tuning has no side effects on the caller's buffers
     if (p.epi == EPI_TOPK_FILTER) q.filt.thr_key = nullptr;      // trial launches reject every score: nothing is appended
+    if (p.epi == EPI_RANK_COUNT) q.rankc.partial = reinterpret_cast<int*>(scratch);      // trial launches count (atomics and all) into scratch sets
     // Every candidate is timed in two rounds and keeps its faster time: the first launches after an idle spell run while the
     // clocks are still ramping, which would otherwise favour whichever candidates happen to be tried last.
     auto timed = [&](auto&& launch) -> float {
@@ -1211,12 +1227,12 @@ static Plan tune_shape(const GemmParams& p, hipStream_t s, bool& tuned) {
         for (int i = 0; i < NC; ++i) {
             const int c = cands[i];
             if (c == 6 && !skinny_ok(p)) continue;
-            if ((c == 12 || c == 13) && (p.epi == EPI_TOPK_FILTER || p.aload != ALOAD_PLAIN || p.M < 2048)) continue;      // macro-tiles: plain loader, stored outputs, deep matrices
+            if ((c == 12 || c == 13) && (epi_is_sweep(p.epi) || p.aload != ALOAD_PLAIN || p.M < 2048)) continue;      // macro-tiles: plain loader, stored outputs, deep matrices
             if (c >= 14) {      // odd-width tiles: only where they pad fewer columns than the 64-wide tiles do (N = 80: 96 < 128) or as many with a wider tile (N = 160, 320)
                 const int pad64 = (p.N + 63) / 64 * 64, padc = (p.N + kCfgs[c].bn - 1) / kCfgs[c].bn * kCfgs[c].bn;
-                if (p.epi == EPI_TOPK_FILTER || epi_is_reduce(p.epi) || p.M < 1024 || (c == 14 ? padc >= pad64 : padc > pad64)) continue;
+                if (epi_is_sweep(p.epi) || epi_is_reduce(p.epi) || p.M < 1024 || (c == 14 ? padc >= pad64 : padc > pad64)) continue;
             }
-            if (c < 8 && p.epi == EPI_TOPK_FILTER) continue;
+            if (c < 8 && epi_is_sweep(p.epi)) continue;
             if (c >= 8 && p.aload == ALOAD_IM2COL) continue;
             if (c < 8 && p.aload == ALOAD_CONV3) continue;
             if (p.K % kCfgs[c].bk) continue;
@@ -1394,7 +1410,7 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
     }
     if (c == 6 && !skinny_ok(p)) c = (p.K & 31) ? best_of(p.M, p.N, 8, 12) : best_of(p.M, p.N, 0, kNumAuto);   // forced but not applicable
     if (c != 6 && forced_cfg() < 0 && !tunable && p.M <= 64 && p.N >= 256 && skinny_ok(p)) c = 6;     // untuned small-M GEMMs
-    if (p.epi == EPI_TOPK_FILTER && (c < 8 || c > 11)) c = 8 + (c & 3);     // filtered sweep: the four LDS-DMA tiles only
+    if (epi_is_sweep(p.epi) && (c < 8 || c > 11)) c = 8 + (c & 3);     // filtered / counting sweep: the four LDS-DMA tiles only
     if (p.aload == ALOAD_CONV3 && (c < 8 || c == 12 || c == 13)) c = 8 + (c & 3);     // 3x3 window: LDS-DMA family without the macro-tiles
     if (c >= 8 && p.aload == ALOAD_IM2COL) c &= 3;                        // patch loader: register-staged family only
     return launch_cfg(c, p, s);

@@ -246,6 +246,78 @@ __device__ __forceinline__ void filter_epilogue(const GemmParams& p, f32x16 (&ac
     }
 }
 
+// The counting sweep of the exact target ranks (kernels.h: RankCount; rows = queries, columns = gallery rows): no score is stored.
+// The workgroup first stages its BM queries' target keys and excluded rows in `lds` (the GEMM's tile buffers, free after the k loop:
+// BM * (RANKC_T * 8 + 4) bytes <= the 128 (BM + BN) bytes of the two buffers).  Per accumulator register r -- query q0 + (r & 3) +
+// 8 (r >> 2) + 4 lh, lane l31 = gallery row -- and target, ONE 64-lane ballot of "this row's key is greater" gives two popcounts: the
+// counts of the lh = 0 and lh = 1 queries.  They stay in SGPRs over the wave's TN tiles; lanes 0..15 then add the (2 queries x 8
+// targets) counts of the register with one vector atomic.  Rows >= N and the excluded row carry key 0, which is greater than nothing.
+template <int BM, int BN, int WM, int WN, int TM, int TN>
+__device__ __forceinline__ void rank_count_epilogue(const GemmParams& p, f32x16 (&acc)[TM][TN], int bm, int bn, int wm, int wn, int l31, int lh,
+                                                    float* lds) {
+    const RankCount& rc = p.rankc;
+    if (!rc.partial) return;                                  // (kernel-uniform)
+    unsigned long long* skey = reinterpret_cast<unsigned long long*>(lds);      // [BM][RANKC_T]
+    int* sex = reinterpret_cast<int*>(skey + BM * RANKC_T);                     // [BM] local excluded row, -1: none
+    for (int i = threadIdx.x; i < BM * RANKC_T; i += blockDim.x) {
+        const int qi = bm * BM + i / RANKC_T, t = i % RANKC_T;
+        skey[i] = (qi < p.M && t < rc.nt) ? rc.keys[(long)qi * rc.kstride + t] : ~0ull;
+    }
+    for (int i = threadIdx.x; i < BM; i += blockDim.x) {
+        const int qi = bm * BM + i;
+        const long ex = (rc.exclude && qi < p.M) ? (long)rc.exclude[qi] - rc.exclude_off : -1;
+        sex[i] = (ex >= 0 && ex < p.N) ? (int)ex : -1;
+    }
+    __syncthreads();
+    const int row_w = bm * BM + wm * WM;
+    const int col_w = bn * BN + wn * WN;
+    if (col_w >= p.N) return;                                 // (wave-uniform, after the barrier)
+    const int lane = l31 + 32 * lh;
+    int* part = rc.partial + (long)((col_w >> 5) & (RANKC_P - 1)) * p.M * RANKC_T;
+    int nrow[TN];
+    unsigned klo[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int n = col_w + j * 32 + l31;
+        nrow[j] = n < p.N ? n : -2;                           // -2: matches no excluded row, and the key is forced to 0 below
+        klo[j] = 0xFFFFFFFFu - (unsigned)((long)n + rc.idx_offset);
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int q0 = row_w + i * 32;
+        if (q0 >= p.M) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int ru = (r & 3) + 8 * (r >> 2);
+            const int ql = wm * WM + i * 32 + ru + 4 * lh;    // this lane half's query inside the workgroup's BM
+            const int ex = sex[ql];
+            unsigned long long key[TN];
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+                key[j] = (nrow[j] >= 0 && nrow[j] != ex) ? (((unsigned long long)orderable(acc[i][j][r]) << 32) | klo[j]) : 0ull;
+            int mine = 0;
+#pragma unroll
+            for (int t = 0; t < RANKC_T; ++t) {
+                if (t < rc.nt) {                              // (kernel-uniform)
+                    const unsigned long long tk = skey[ql * RANKC_T + t];
+                    int clo = 0, chi = 0;
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const unsigned long long b = __ballot(key[j] > tk);
+                        clo += __popc((unsigned)b);
+                        chi += __popc((unsigned)(b >> 32));
+                    }
+                    mine = lane == t ? clo : lane == RANKC_T + t ? chi : mine;
+                }
+            }
+            const int qa = q0 + ru + 4 * (lane >> 3);         // lanes 0..7: the lh = 0 query's targets, 8..15: the lh = 1 query's
+            if (lane < 2 * RANKC_T && (lane & (RANKC_T - 1)) < rc.nt && qa < p.M && mine != 0)
+                atomicAdd(&part[(long)qa * RANKC_T + (lane & (RANKC_T - 1))], mine);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // Shared epilogue of the fp32 and bf16 GEMM kernels (ALLOW_BF16_OUT: only the bf16 kernel stores bf16 outputs).
 template <int BM, int BN, int WM, int WN, int TM, int TN, int WAVES_N, bool ALLOW_BF16_OUT = false, int RGELU = 1 /* GELU of the reduced-precision families: 1 fast, 2 tanh */,
           bool ALLOW_SCALED = true /* per-row / per-channel fp8 scales folded back here (p.scale_a); the block-scaled family has none and leaves the code out */>

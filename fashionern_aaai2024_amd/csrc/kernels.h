@@ -73,6 +73,21 @@ struct TopkFilter {
     long exclude_off;                     // ... as a global index: the local row is exclude[q] - exclude_off
     int cap;                              // entries per list (<= 64: the select kernel reads a list with one wave load)
 };
+// ---- exact target ranks: counting sweep (EPI_RANK_COUNT of the fp32 GEMM, rank.hip for the bf16 form) -----------------------------
+// A rank is a count: rows whose key (make_key: score descending, index ascending) is greater than the target's key.  One gallery pass
+// serves RANKC_T target keys per query; every wave adds its tile counts to one of RANKC_P partial counter sets (chosen by its column
+// tile, so the ~N / 64 adds per (query, target) do not queue on one address), launch_rank_finalize sums the sets.  Integer adds
+// commute: the result does not depend on the tile configuration or on the order the waves arrive in.
+constexpr int RANKC_T = 8;
+constexpr int RANKC_P = 64;
+struct RankCount {
+    const unsigned long long* keys;       // target keys of this pass: query q's are keys[q * kstride + 0 .. nt) (0 = no target: counted, reported as -1)
+    int* partial;                         // [RANKC_P][B][RANKC_T], zero before the sweep (null: nothing is counted)
+    const int* exclude;                   // [B] gallery index that is not counted per query, or null ...
+    long exclude_off;                     // ... as a global index: the local row is exclude[q] - exclude_off
+    long idx_offset;                      // key index of local row n is n + idx_offset
+    int kstride, nt;                      // 1 <= nt <= RANKC_T
+};
 // sample column c -> gallery row: one row out of every run of R consecutive rows, at a hashed offset inside the run (a fixed
 // stride would alias with periodic structure in the gallery order); monotonic in c, so sample order = gallery order
 __host__ __device__ inline long sample_row(long c, int R) {
@@ -94,7 +109,8 @@ enum GemmEpi : int {
     EPI_SR_LOCAL = 7,        // p = row % 13: v = tanh((acc + bias[col] - aux1[p]) * aux2[p] + aux3[p]);
                              // partial[row][nb] = sum_col v * G[(row/13)*ldg + col] * aux0[col]     (VisualSR local branch)
     EPI_BIAS_RESIDUAL_RELU = 8, // C = relu(acc + bias + R[row*ldc + col])   (ResNet bottleneck tail: conv3 + BN folded + identity)
-    EPI_TOPK_FILTER = 9         // rows = queries, columns = gallery rows: nothing is stored; acc >= the query's bound is appended to p.filt
+    EPI_TOPK_FILTER = 9,        // rows = queries, columns = gallery rows: nothing is stored; acc >= the query's bound is appended to p.filt
+    EPI_RANK_COUNT = 10         // same sweep, nothing stored: per (query, target key) the number of gallery rows whose key is greater -> p.rankc
 };
 __host__ __device__ inline bool epi_is_reduce(int e) { return e == EPI_RELU_DOT || e == EPI_SR_LOCAL; }
 // ALOAD_IM2COL: non-overlapping patches of an NCHW image (ViT conv1); ALOAD_CONV3: 3x3 / stride 1 / pad 1 window over an
@@ -128,6 +144,7 @@ struct GemmParams {
     float* kpart;
     int w_sample;                 // > 1: W row r is gallery row sample_row(r, w_sample) (the sample pass of the fused top-K sweep)
     TopkFilter filt;              // EPI_TOPK_FILTER
+    RankCount rankc;              // EPI_RANK_COUNT
     const int* gate;              // when set: the launch does nothing unless *gate != 0 (retry pass of the fused top-K sweep)
     // split == 3: "f32x3" arithmetic (FERN_PREC_F32X3): fp32 operands split into three bf16 planes in registers, six bf16 MFMAs per
     // pair of fp32 ones -- fp32-accurate (error vs exact arithmetic = the fp32 kernel's), not the fp32 fma chain.  Plain loader,
@@ -436,6 +453,23 @@ hipError_t launch_topk_candidates(const TopkFilter& f, int B, int K, long idx_of
 // Merge R lists [R,B,K] (score, idx) -> [B,K]
 hipError_t launch_topk_merge(const float* scores, const int* idx, float* out_scores, int* out_idx, int R, int B, int K,
                              hipStream_t s);
+// ---- exact target ranks (rank.hip) -------------------------------------------------------------------------------------------------
+// keys[b][j] = make_key(chain score of q[b] and gallery row targets[b][j] - idx_offset, targets[b][j]); 0 for a target < 0 or outside
+// [idx_offset, idx_offset + N).  The score is the sweep's fp32 fma chain (oracle/chain.c order), bit for bit.  D % 8 == 0.
+hipError_t launch_rank_keys(const float* q, const float* gallery, const int* targets, int B, long N, int D, int m, long idx_offset,
+                            unsigned long long* keys, hipStream_t s);
+// bf16 form, step 1: rows[b * m + j] = gallery row of target (b, j) (row 0 for an invalid target) -- a small gallery that
+// launch_sweep_bf16 scores in its store form, 64 queries against their own 64 m rows (the sweep's MFMA sequence and k order);
+// step 2: keys[b][j] = make_key(S[b][(b % 64) * m + j], targets[b][j]) or 0.
+hipError_t launch_rank_gather_bf16(const unsigned short* gallery, const int* targets, long count, long N, int D, long idx_offset,
+                                   unsigned short* rows, hipStream_t s);
+hipError_t launch_rank_keys_from_scores(const float* S, long ld, const int* targets, int B, long N, int m, long idx_offset,
+                                        unsigned long long* keys, hipStream_t s);
+// counting over stored score rows S [B, ld] (the bf16 sweep's store form): adds into rc.partial like the fp32 sweep's epilogue
+hipError_t launch_rank_count_rows(const float* S, long ld, int B, long N, const RankCount& rc, hipStream_t s);
+// count[b * cstride + t] = keys[b * kstride + t] ? sum over the RANKC_P sets of partial[.][b][t] : -1, t < nt
+hipError_t launch_rank_finalize(const RankCount& rc, int B, int* count, int cstride, hipStream_t s);
+
 // ---- deep top-K (topk_deep.hip): 1 <= K <= 1024 on a stored score row per query ------------------------------------------------
 // S [B, ld] fp32 = exact chain scores of B queries against an fp32 gallery (deep_exact_scores_kernel: the MFMA sequence of
 // launch_rank_exact).  gated != 0: only if flags[0] is set, only the rows of queries with state[b] != 0; gated == 0 also zeroes flags[0..3].

@@ -187,6 +187,41 @@ def rank_sharded(engine, queries: torch.Tensor, gallery_shard: torch.Tensor, sha
     return engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
 
 
+def _all_reduce_sum(x: torch.Tensor) -> torch.Tensor:
+    """In-place SUM all-reduce of an integer tensor (through the host under the gloo debug backend with device tensors)."""
+    if dist.get_backend() == "gloo" and x.is_cuda:
+        h = x.cpu()
+        dist.all_reduce(h, op=dist.ReduceOp.SUM)
+        x.copy_(h)
+    else:
+        dist.all_reduce(x, op=dist.ReduceOp.SUM)
+    return x
+
+
+def rank_of_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: int, targets, exclude_idx=None):
+    """Gallery-sharded exact target ranks of the SAME query batch on every rank (`FernEngine.rank_of` on the whole gallery): the key of
+    a target comes from the shard that owns its row -- every other rank contributes 0, so the int64 SUM all-reduce is exact, wrap-around
+    included -- then every rank counts the rows of its shard that outrank the keys and the counts are SUM-reduced.  Two small
+    collectives of [B, m] integers; world 1 makes none.  Returns int32 shaped like `targets` on every rank; -1 for a target < 0,
+    outside the gallery, or equal to the query's excluded row."""
+    rank, world = world_info()
+    t = torch.as_tensor(targets)
+    flat = t.dim() == 1
+    t2 = (t[:, None] if flat else t).to(dtype=torch.int32)
+    keys = engine.rank_keys(queries, gallery_shard, t2, idx_offset=shard_start)
+    if world > 1:
+        _all_reduce_sum(keys)
+    if exclude_idx is not None:
+        ex = torch.as_tensor(exclude_idx).to(device=keys.device, dtype=torch.int32)
+        keys = torch.where(t2.to(keys.device) == ex[:, None], torch.zeros_like(keys), keys)
+    counts = engine.rank_count(queries, gallery_shard, keys, idx_offset=shard_start, exclude_idx=exclude_idx)
+    if world > 1:
+        counts = counts.clamp(min=0)                 # a keyless target is -1 on every rank: summed as 0, restored below
+        _all_reduce_sum(counts)
+        counts = torch.where(keys == 0, torch.full_like(counts, -1), counts)
+    return counts[:, 0] if flat else counts
+
+
 def share_gemm_tiles(engine, src: int = 0) -> None:
     """Every rank adopts rank `src`'s GEMM tile choices (the per-shape tuner runs independently in each process; all choices
     give bit-identical results, but different tiles run at slightly different speeds and a multi-GPU step is as slow as its

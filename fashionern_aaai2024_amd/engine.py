@@ -408,6 +408,74 @@ class FernEngine:
                                                _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_deep")
         return scores, idx
 
+    # ---- exact target ranks ---------------------------------------------------------------------
+    def _rank_forms(self, q, gallery):
+        """(q, fp32 gallery or None, bf16 gallery or None): the gallery forms of `sim_topk_deep`; a PreparedGallery ranks on its
+        fp32 rows (its bf16 copy is not read)."""
+        q = self._f32(q)
+        g32 = g16 = None
+        if isinstance(gallery, PreparedGallery):
+            g32 = gallery.f32
+        elif isinstance(gallery, torch.Tensor) and gallery.dtype == torch.bfloat16:
+            if not gallery.is_cuda or not gallery.is_contiguous():
+                raise ValueError("a bf16 gallery must be a contiguous device tensor")
+            g16 = gallery
+        else:
+            g32 = self._f32(gallery)
+        g = g32 if g32 is not None else g16
+        if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+            raise ValueError(f"q [B,D] and gallery [N,D] must share D, got {tuple(q.shape)} and {tuple(g.shape)}")
+        return q, g32, g16
+
+    def _per_query(self, t, b: int, dtype, what: str) -> torch.Tensor:
+        t = torch.as_tensor(t).to(device=self.device, dtype=dtype)
+        if t.dim() == 1:
+            t = t[:, None]
+        if t.dim() != 2 or t.shape[0] != b or t.shape[1] < 1:
+            raise ValueError(f"{what} must be [B] or [B,m] with m >= 1, got {tuple(t.shape)}")
+        return t.contiguous()
+
+    def rank_keys(self, q, gallery, targets, idx_offset: int = 0) -> torch.Tensor:
+        """int64 [B,m]: the bits of the 64-bit ranking keys (include/fern.h: fern_rank_keys) of the gallery rows `targets` (global
+        indices, [B] or [B,m]); 0 for a target < 0 or outside [idx_offset, idx_offset + N)."""
+        q, g32, g16 = self._rank_forms(q, gallery)
+        g = g32 if g32 is not None else g16
+        tg = self._per_query(targets, q.shape[0], torch.int32, "targets")
+        keys = self._empty(*tg.shape, dtype=torch.int64)
+        _lib.check(self.lib.fern_rank_keys(self._h, _ptr(q), _ptr(g32), _ptr(g16), q.shape[0], g.shape[0], q.shape[1], _ptr(tg), tg.shape[1],
+                                           int(idx_offset), _ptr(keys), _stream()), "fern_rank_keys")
+        return keys
+
+    def rank_count(self, q, gallery, keys, idx_offset: int = 0, exclude_idx=None) -> torch.Tensor:
+        """int32 [B,m]: per key the number of rows of `gallery` whose ranking key is greater (include/fern.h: fern_rank_count); the
+        row `exclude_idx[b]` (global index) is not counted; -1 for a key of 0.  Counts of gallery shards add up."""
+        q, g32, g16 = self._rank_forms(q, gallery)
+        g = g32 if g32 is not None else g16
+        b = q.shape[0]
+        ky = self._per_query(keys, b, torch.int64, "keys")
+        ex = None
+        if exclude_idx is not None:
+            ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(ex.shape) != (b,):
+                raise ValueError("exclude_idx must be [B]")
+        count = self._empty(*ky.shape, dtype=torch.int32)
+        _lib.check(self.lib.fern_rank_count(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, g.shape[0], q.shape[1], _ptr(ky), ky.shape[1],
+                                            int(idx_offset), _ptr(ex), _ptr(count), _stream()), "fern_rank_count")
+        return count
+
+    def rank_of(self, q, gallery, targets, idx_offset: int = 0, exclude_idx=None) -> torch.Tensor:
+        """int32, shaped like `targets` ([B] or [B,m]): the 0-based position of each target row in the ordering `sim_topk` defines
+        (score descending, gallery index ascending) -- what the reference reads off its full argsort (run/test/test_fiq.py:49-60) --
+        at any depth.  -1 for a target that is < 0, outside the gallery, or the query's excluded row."""
+        flat = torch.as_tensor(targets).dim() == 1
+        keys = self.rank_keys(q, gallery, targets, idx_offset)
+        if exclude_idx is not None:
+            ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32)
+            tg = self._per_query(targets, keys.shape[0], torch.int32, "targets")
+            keys = torch.where(tg == ex[:, None], torch.zeros_like(keys), keys)
+        ranks = self.rank_count(q, gallery, keys, idx_offset, exclude_idx)
+        return ranks[:, 0] if flat else ranks
+
     def gallery_to_bf16(self, gallery) -> torch.Tensor:
         """fp32 [N,D] -> bf16 [N,D] (round to nearest even) for `sim_topk_bf16`."""
         g = self._f32(gallery)

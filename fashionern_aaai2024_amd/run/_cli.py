@@ -128,6 +128,8 @@ def main(kind: str) -> None:
     p.add_argument("--precision", default="fp32", choices=["fp32", "f32x3", "bf16", "fp8", "mx8"],
                    help="encoder operand precision: fp32 = the reference's arithmetic (bit-exact fma chains); f32x3 = fp32-accurate GEMMs from "
                         "three bf16 planes per operand (~1.4x faster); bf16 / fp8 / mx8 = perf modes (ViT / text towers)")
+    p.add_argument("--rank-metrics", action="store_true",
+                   help="fiq / cirr / 200k: after the recalls also print where the targets landed in the full ranking (Recall@K, median / mean rank, MRR)")
     args = p.parse_args()
     setup_seed(args.seed)
     rank, world, local = fd.init_from_env()                 # torchrun: one process per GPU; a lone process is (0, 1, 0)
@@ -167,6 +169,14 @@ def main(kind: str) -> None:
                  args.clip_model_name)
         say(split, "recalls:", res)
         results.append(res)
+        if args.rank_metrics:
+            from . import rank_metrics
+            rank_fn = {"fiq": rank_metrics.compute_fiq_rank_metrics, "cirr": rank_metrics.compute_cirr_rank_metrics,
+                       "200k": rank_metrics.compute_200k_rank_metrics}.get(kind)
+            if rank_fn is None:
+                raise SystemExit(f"--rank-metrics is not available for {kind}")
+            say(split, "rank metrics:", rank_fn(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size,
+                                               args.num_workers, args.clip_model_name))
     avg = [mean(r[j] for r in results) for j in range(len(results[0]))]
     if kind == "cirr":
         say("Average: ", (avg[4] + avg[0]) / 2)        # (R@5 + R_subset@1) / 2, test_cirr.py:198

@@ -318,3 +318,45 @@ def recalls_cirr(model, predicted, index_fused, index_names, reference_names, ta
         ranks[i] = int(np.where(member_rows[i][order] == tgt[i])[0][0])
     grp = tuple(_pct((ranks < k).sum(), q) for k in (1, 2, 3))
     return grp + glob                                          # (G@1,G@2,G@3,R@1,R@5,R@10,R@50) test_cirr.py:80
+
+
+def target_ranks(model, predicted, index_fused, rows, exclude=None) -> np.ndarray:
+    """The 0-based place of gallery rows `rows` ([Q] or [Q, m]; -1 = no target) in every query's full ranking -- what the reference
+    reads off its argsort (test_fiq.py:49-60) -- as a host int32 array [Q, m]; -1 where there is no target or the target is the
+    query's excluded row.  No depth limit: the engine counts the rows that outrank each target (FernEngine.rank_of).  Query slices go
+    per rank and the rows are gathered, as in `_ranked`."""
+    eng = _engine_of(model)
+    rows = np.asarray(rows)
+    rows = (rows[:, None] if rows.ndim == 1 else rows).astype(np.int32)
+    q, m = rows.shape
+    start, stop, per = _my_rows(q)
+    ex = None if exclude is None else torch.as_tensor(np.asarray(exclude)[start:stop], dtype=torch.int32)
+    if stop > start:
+        ranks = eng.rank_of(predicted[start:stop], index_fused, torch.as_tensor(rows[start:stop]), exclude_idx=ex)
+    else:
+        ranks = torch.empty((0, m), dtype=torch.int32, device=predicted.device)
+    if hasattr(eng, "sync"):
+        eng.sync()
+    if fd.world_info()[1] > 1:
+        block = torch.full((per, m), -1, dtype=torch.int32, device=ranks.device)
+        block[: stop - start] = ranks
+        ranks = fd.all_gather_shards(block, q)
+    return ranks.cpu().numpy()
+
+
+def retrieval_metrics(ranks, ks) -> Dict[str, float]:
+    """{"recall@k" ..., "median_rank", "mean_rank", "mrr"} of target ranks [Q] or [Q, m] (0-based, -1 = no target).  A query's rank is
+    the best (minimum) of its valid targets -- Fashion200k's any-hit (test_200k.py:59-60); a query without a valid target is a miss
+    everywhere.  Recalls are `_pct` of the queries ranked < k, i.e. bit for bit the tuples of the recall functions above.  median_rank
+    and mean_rank count places from 1 over the queries that have a target; mrr is the mean of 1 / place over ALL queries."""
+    r = np.asarray(ranks)
+    r = (r[:, None] if r.ndim == 1 else r).astype(np.int64)
+    q = r.shape[0]
+    best = np.where(r >= 0, r, np.iinfo(np.int64).max).min(axis=1) if q else np.zeros(0, dtype=np.int64)
+    found = best != np.iinfo(np.int64).max
+    out = {f"recall@{k}": _pct(int((found & (best < k)).sum()), q) for k in ks}
+    place = best[found].astype(np.float64) + 1.0
+    out["median_rank"] = float(np.median(place)) if place.size else float("nan")
+    out["mean_rank"] = float(place.mean()) if place.size else float("nan")
+    out["mrr"] = float((1.0 / place).sum() / q) if q else float("nan")
+    return out

@@ -345,6 +345,27 @@ FERN_API int fern_sim_topk_deep(fern_ctx* ctx, const float* q /*[B,D]*/, const f
                                 const uint16_t* gallery_bf16 /*[N,D] or NULL*/, const float* meta /*[4] device or NULL*/, int B, int64_t N,
                                 int D, int K, float* out_scores /*[B,K]*/, int32_t* out_idx /*[B,K]*/, int64_t idx_offset,
                                 const int32_t* exclude_idx, void* stream);
+/* Exact target ranks.  The reference ranks with a full argsort of 1 - q @ g.T and looks the target up in it (run/test/test_fiq.py:49-60),
+ * so it knows the place of every gallery row; the top-K entry points above know the first K <= 1024 places.  A place is a COUNT -- the
+ * number of rows whose ranking key is greater than the target's -- and these two entry points compute it with one more gallery pass and
+ * no list: any depth, no capacity, no fallback, nothing read back; asynchronous on `stream` and graph-capturable after one warm-up call.
+ * The ranking key is the one the top-K kernels sort, orderable(score) << 32 | ~global_index (score descending, index ascending as one
+ * unsigned compare), so a count is the 0-based position of the target in the ordering fern_sim_topk / fern_sim_topk_deep define.
+ * Counts are additive over gallery shards: take each target's key from the shard that owns it, count on every shard, add.
+ * The gallery form follows from the pointers given, as for fern_sim_topk_deep:
+ *   gallery (gallery_bf16 ignored)    the exact fp32 fma-chain scores of fern_sim_topk, whatever fern_set_precision says; D % 32 == 0;
+ *   gallery_bf16 only                 the bf16 similarity: the values fern_sweep_bf16_scores produces; D % 64 == 0, D <= 768.
+ * fern_rank_keys: out_keys[b][j] = the key of gallery row targets[b][j] - idx_offset for query b, its score bit for bit what the sweep of
+ * the same form gives that row; 0 when the target is < 0 or not a row of this gallery (shard). */
+FERN_API int fern_rank_keys(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                            const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const int32_t* targets /*[B,m] global indices*/,
+                            int m, int64_t idx_offset, uint64_t* out_keys /*[B,m]*/, void* stream);
+/* fern_rank_count: out_count[b][j] = the number of rows n < N with key(score(b, n), n + idx_offset) > keys[b][j]; the row exclude_idx[b]
+ * (a global index, may be NULL; CIRR's reference removal, run/test/test_cirr.py) is not counted; a key of 0 gives -1.  Any m >= 1: a
+ * gallery pass serves 8 targets per query.  Queries are processed in chunks of 1024 (bf16 form: within a 1.1 GB score workspace). */
+FERN_API int fern_rank_count(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                             const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const uint64_t* keys /*[B,m]*/, int m,
+                             int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/, int32_t* out_count /*[B,m]*/, void* stream);
 /* scores of explicitly named gallery rows (CIRR subset ranking, run/test/test_cirr.py:64-66);
  * idx < 0 -> -inf */
 FERN_API int fern_gather_scores(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D]*/,

@@ -1,0 +1,232 @@
+"""Exact target ranks (include/fern.h: fern_rank_keys / fern_rank_count; FernEngine.rank_keys / rank_count / rank_of): the 0-based place
+of named gallery rows in the ordering the top-K stages define, at any depth, on every gallery form.
+
+Oracle: oracle/chain.c scores ranked by a stable argsort (score descending, gallery index ascending).  Finite inputs only."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import chain
+
+pytestmark = pytest.mark.gpu
+
+
+def _rand(n, d, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(n, d, generator=g) * scale
+
+
+def _int_unit(n, d, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(-1, 2, (n, d), generator=g).float() / 8.0
+
+
+def _places(scores):
+    """[B,N] int64: the place of every row in the stable ranking of `scores` (numpy [B,N])."""
+    order = np.argsort(-scores, axis=1, kind="stable")
+    place = np.empty_like(order)
+    np.put_along_axis(place, order, np.broadcast_to(np.arange(scores.shape[1]), order.shape), axis=1)
+    return place
+
+
+def _expected(place, targets, idx_offset=0, exclude=None):
+    """Ranks of global `targets` [B,m] given the places of the local rows; the excluded row (global) leaves the ranking."""
+    b, n = place.shape
+    local = targets.astype(np.int64) - idx_offset
+    ok = (targets >= 0) & (local >= 0) & (local < n)
+    safe = np.where(ok, local, 0)
+    out = np.take_along_axis(place, safe, axis=1)
+    if exclude is not None:
+        exl = exclude.astype(np.int64) - idx_offset
+        has = (exclude >= 0) & (exl >= 0) & (exl < n)
+        exp = np.take_along_axis(place, np.where(has, exl, 0)[:, None], axis=1)
+        out = out - (has[:, None] & (exp < out))
+        ok &= ~(has[:, None] & (local == exl[:, None]))
+    return np.where(ok, out, -1).astype(np.int32)
+
+
+def _targets(b, n, m, seed, place=None, idx_offset=0, exclude=None):
+    """[B,m] global indices over the whole depth: rows at evenly spread places plus random rows, then -1, an index past the gallery,
+    a duplicate and the excluded row written over some of them."""
+    rng = np.random.default_rng(seed)
+    t = rng.integers(0, n, size=(b, m))
+    if place is not None:
+        order = np.argsort(place, axis=1)
+        depth = np.linspace(0, n - 1, m).astype(np.int64)
+        spread = order[:, depth]
+        t = np.where(rng.random((b, m)) < 0.6, spread, t)
+    t = t.astype(np.int64) + idx_offset
+    for r in range(b):
+        if r % 4 == 1:
+            t[r, rng.integers(m)] = -1
+        if r % 4 == 2:
+            t[r, rng.integers(m)] = idx_offset + n + rng.integers(0, 5)
+        if r % 4 == 3 and m > 1:
+            t[r, m - 1] = t[r, 0]
+        if exclude is not None and r % 2 == 0:
+            t[r, rng.integers(m)] = exclude[r]
+    return t.astype(np.int32)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from fashionern_aaai2024_amd.engine import FernEngine
+    e = FernEngine("cuda:0")
+    yield e
+    e.close()
+
+
+SHAPES = [(1, 1, 128), (64, 63, 128), (64, 46_000, 512), (3, 46_000, 768), (1025, 1000, 640), (2, 200_000, 640)]
+
+
+@pytest.mark.parametrize("B,N,D", SHAPES)
+def test_fp32_ranks_equal_the_chain_oracle(eng, B, N, D):
+    q, g = _rand(B, D, seed=B + N), _rand(N, D, seed=N + D, scale=D ** -0.5)
+    place = _places(chain.chain_scores(q.numpy(), g.numpy()))
+    qd, gd = q.cuda(), g.cuda()
+    ex = np.array([(7 * r) % N if r % 3 else -1 for r in range(B)], dtype=np.int32)
+    for m in (1, 3, 8, 13):
+        t = _targets(B, N, m, seed=m, place=place)
+        got = eng.rank_of(qd, gd, torch.from_numpy(t))
+        assert np.array_equal(got.cpu().numpy(), _expected(place, t)), m
+        t = _targets(B, N, m, seed=100 + m, place=place, exclude=ex)
+        got = eng.rank_of(qd, gd, torch.from_numpy(t), exclude_idx=torch.from_numpy(ex))
+        assert np.array_equal(got.cpu().numpy(), _expected(place, t, exclude=ex)), m
+    flat = _targets(B, N, 1, seed=5, place=place)
+    assert np.array_equal(eng.rank_of(qd, gd, torch.from_numpy(flat[:, 0])).cpu().numpy(), _expected(place, flat)[:, 0])
+
+
+@pytest.mark.parametrize("B,N,D", [(8, 46_000, 512), (5, 3000, 128), (3, 1000, 64)])
+def test_tie_heavy_galleries(eng, B, N, D):
+    q, g = _int_unit(B, D, seed=41), _int_unit(N, D, seed=42)
+    s = chain.chain_scores(q.numpy(), g.numpy())
+    place = _places(s)
+    t = _targets(B, N, 13, seed=3, place=place)
+    valid = (t >= 0) & (t < N)
+    ts = np.take_along_axis(s, np.where(valid, t, 0), axis=1)
+    shared = np.array([[(s[b] == ts[b, j]).sum() > 1 for j in range(t.shape[1])] for b in range(B)])
+    assert (shared & valid).sum() * 2 >= valid.sum()          # the data is what the test is about: most targets tie with another row
+    for gal in (g.cuda(), eng.prepare_gallery(g)):
+        got = eng.rank_of(q.cuda(), gal, torch.from_numpy(t))
+        assert np.array_equal(got.cpu().numpy(), _expected(place, t))
+
+
+def _forms(eng, g):
+    pg = eng.prepare_gallery(g)
+    return [("fp32", g.cuda(), None), ("prepared-auto", pg, "auto"), ("prepared-plain", pg, "plain"), ("prepared-lists", pg, "lists"),
+            ("prepared-dense", pg, "dense"), ("bf16", pg.bf16, None)]
+
+
+@pytest.mark.parametrize("B,N,D", [(64, 46_000, 512), (5, 3000, 640)])
+def test_every_place_of_the_list_stages_is_its_own_rank(eng, B, N, D):
+    q, g = _rand(B, D, seed=71 + N).cuda(), _rand(N, D, seed=72 + N, scale=D ** -0.5)
+    off = 1_000
+    ex = torch.tensor([off + (11 * r) % N for r in range(B)], dtype=torch.int32)
+    try:
+        for label, gal, strategy in _forms(eng, g):
+            if strategy:
+                eng.set_rank_strategy(strategy)
+            for idx_offset, exclude in ((0, None), (off, None), (off, ex)):
+                if label == "bf16":
+                    i50 = eng.sim_topk_bf16(q, gal, 50, idx_offset=idx_offset, exclude_idx=exclude)[1]
+                else:
+                    i50 = eng.sim_topk(q, gal, 50, idx_offset=idx_offset, exclude_idx=exclude)[1]
+                i1024 = eng.sim_topk_deep(q, gal, 1024, idx_offset=idx_offset, exclude_idx=exclude)[1]
+                for idx in (i50, i1024):
+                    k = idx.shape[1]
+                    want = torch.arange(k, dtype=torch.int32, device=idx.device).expand(B, k)
+                    got = eng.rank_of(q, gal, idx, idx_offset=idx_offset, exclude_idx=exclude)
+                    assert torch.equal(got, want), (label, idx_offset, exclude is not None, k)
+    finally:
+        eng.set_rank_strategy("auto")
+
+
+@pytest.mark.parametrize("B,N,D", [(64, 46_000, 512), (3, 1000, 128), (70, 20_000, 768)])
+def test_bf16_form_ranks_the_sweep_scores(eng, B, N, D):
+    q, g = _rand(B, D, seed=21 + N), _rand(N, D, seed=22 + N, scale=D ** -0.5)
+    pg = eng.prepare_gallery(g)
+    place = _places(eng.sweep_bf16_scores(q, pg, tile_max=False).cpu().numpy())
+    ex = np.array([(5 * r) % N if r % 2 else -1 for r in range(B)], dtype=np.int32)
+    for m in (1, 8, 13):
+        t = _targets(B, N, m, seed=m, place=place, exclude=ex)
+        got = eng.rank_of(q.cuda(), pg.bf16, torch.from_numpy(t), exclude_idx=torch.from_numpy(ex))
+        assert np.array_equal(got.cpu().numpy(), _expected(place, t, exclude=ex)), m
+
+
+@pytest.mark.parametrize("form", ["fp32", "bf16"])
+def test_counts_add_up_over_ragged_shards(eng, form):
+    B, N, D, m = 16, 46_000, 512, 5
+    q, g = _rand(B, D, seed=51).cuda(), _rand(N, D, seed=52, scale=D ** -0.5)
+    gal = g.cuda() if form == "fp32" else eng.gallery_to_bf16(g)
+    t = torch.from_numpy(_targets(B, N, m, seed=9))
+    ex = torch.tensor([(13 * r) % N for r in range(B)], dtype=torch.int32)
+    whole = eng.rank_of(q, gal, t, exclude_idx=ex)
+    bounds = [0, 7_001, 30_033, N]
+    shards = [(a, gal[a:b].contiguous()) for a, b in zip(bounds[:-1], bounds[1:])]
+    keys = torch.zeros(B, m, dtype=torch.int64, device=q.device)
+    for a, sh in shards:
+        k = eng.rank_keys(q, sh, t, idx_offset=a)
+        assert ((k == 0) | (keys == 0)).all()                 # exactly one shard owns a target
+        keys += k
+    keys = torch.where(t.cuda() == ex.cuda()[:, None], torch.zeros_like(keys), keys)
+    counts = sum(eng.rank_count(q, sh, keys, idx_offset=a, exclude_idx=ex).clamp(min=0) for a, sh in shards)
+    counts = torch.where(keys == 0, torch.full_like(counts, -1), counts)
+    assert torch.equal(counts, whole)
+
+
+@pytest.mark.parametrize("prec", ["f32x3", "mx8img"])
+def test_encoder_precision_does_not_move_the_ranks(eng, prec):
+    B, N, D = 300, 46_000, 512                                 # M >= 256: a plain GEMM of this shape would run the f32x3 split
+    q, g = _rand(B, D, seed=7).cuda(), _rand(N, D, seed=8, scale=D ** -0.5).cuda()
+    t = torch.from_numpy(_targets(B, N, 8, seed=1))
+    ref = eng.rank_of(q, g, t)
+    before = eng.precision
+    eng.set_precision(prec)
+    try:
+        assert torch.equal(eng.rank_of(q, g, t), ref)
+    finally:
+        eng.set_precision(before)
+
+
+def test_graph_capture_replays_on_new_inputs(eng):
+    B, N, D, m = 64, 46_000, 512, 8
+    g = _rand(N, D, seed=62, scale=D ** -0.5).cuda()
+    q, t = _rand(B, D, seed=61).cuda(), torch.from_numpy(_targets(B, N, m, seed=2)).cuda()
+    ex = torch.tensor([(3 * r) % N for r in range(B)], dtype=torch.int32).cuda()
+    eng.rank_of(q, g, t, exclude_idx=ex)                       # one eager call: tile choice and workspace exist
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        out = eng.rank_of(q, g, t, exclude_idx=ex)
+    for seed in (63, 64):
+        q.copy_(_rand(B, D, seed=seed))
+        t.copy_(torch.from_numpy(_targets(B, N, m, seed=seed)))
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, eng.rank_of(q, g, t, exclude_idx=ex))
+
+
+def test_null_context_and_bad_shapes_are_refused(eng):
+    lib = eng.lib
+    assert lib.fern_rank_keys(None, None, None, None, 1, 1, 32, None, 1, 0, None, None) == -1
+    assert b"fern_rank_keys" in lib.fern_last_error()
+    assert lib.fern_rank_count(None, None, None, None, 1, 1, 32, None, 1, 0, None, None, None) == -1
+    assert b"fern_rank_count" in lib.fern_last_error()
+    q, g = _rand(2, 48, seed=1).cuda(), _rand(10, 48, seed=2).cuda()
+    with pytest.raises(Exception, match="fern_rank_keys"):
+        eng.rank_keys(q, g, torch.zeros(2, 1, dtype=torch.int32))
+
+
+@pytest.mark.parametrize("kind", ["fiq", "cirr", "200k"])
+def test_harness_rank_metrics_return_the_golden_recalls(kind):
+    from test_gpu_harness import DEV, META, build
+    from fashionern_aaai2024_amd.run import rank_metrics
+    fn = {"fiq": rank_metrics.compute_fiq_rank_metrics, "cirr": rank_metrics.compute_cirr_rank_metrics,
+          "200k": rank_metrics.compute_200k_rank_metrics}[kind]
+    clip, model, rel, feats, names, local, d = build(kind)
+    ks = (1, 5, 10, 50) if kind == "cirr" else (10, 50)
+    res = fn(rel, clip, feats, local, names, model, DEV, d, META["batch_size"], 0, "stub", ks=ks)
+    golden = META["recalls"][kind][3:] if kind == "cirr" else META["recalls"][kind]      # cirr: (G@1, G@2, G@3, R@1, R@5, R@10, R@50)
+    assert [res[f"recall@{k}"] for k in ks] == golden, (res, golden)
+    assert 1.0 <= res["median_rank"] <= META["n"] and 0.0 < res["mrr"] <= 1.0
