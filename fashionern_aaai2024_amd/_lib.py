@@ -45,6 +45,7 @@ SIGNATURES = {
     "fern_load_tensor": (c_int, [c_void_p, C.c_char_p, c_void_p, c_int, c_int, C.POINTER(c_i64)]),
     "fern_finalize_fusion": (c_int, [c_void_p, c_int, c_int]),
     "fern_finalize_clip": (c_int, [c_void_p, C.POINTER(ClipConfigC)]),
+    "fern_clip_set_activation": (c_int, [c_void_p, c_int]),
     "fern_vit_encode_image": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "fern_text_encode": (c_int, [c_void_p, c_void_p, c_void_p, C.POINTER(c_i64), c_void_p, c_void_p, c_int, c_void_p]),
     "fern_encode_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -26,11 +26,14 @@ from .synth import CLIP_CONFIGS, ClipConfig
 class FernCLIP:
     """CLIP ViT image tower + text tower running as HIP kernels on one MI355X."""
 
-    def __init__(self, model_name: Union[str, ClipConfig] = "ViT-B-16", device="cuda:0", engine=None, precision: str = "fp32"):
-        cfg = model_name if isinstance(model_name, ClipConfig) else CLIP_CONFIGS.get(model_name)
-        if cfg is None:
+    def __init__(self, model_name: Union[str, ClipConfig] = "ViT-B-16", device="cuda:0", engine=None, precision: str = "fp32",
+                 force_quick_gelu: bool = False):
+        """``force_quick_gelu`` mirrors open_clip's argument of the same name: both towers' MLPs use QuickGELU, x * sigmoid(1.702 x),
+        instead of exact-erf GELU.  open_clip sets it for ``pretrained="openai"``; pass it (or a ``*-quickgelu`` config name) whenever
+        the weights that follow through ``load_state_dict`` are OpenAI's -- RN50x4's only public weights are."""
+        if not isinstance(model_name, ClipConfig) and model_name not in CLIP_CONFIGS:
             raise ValueError(f"unknown CLIP model {model_name!r}; known: {sorted(CLIP_CONFIGS)}")
-        self.cfg = cfg
+        self.cfg = synth.resolve_clip_config(model_name, force_quick_gelu)
         self.engine = engine if engine is not None else FernEngine(device)
         self.device = self.engine.device
         self._state: Dict[str, np.ndarray] = {}
@@ -123,10 +126,13 @@ class FernCLIP:
         return s if mode == "seq" else (g, s)
 
 
-def create_model(model_name="ViT-B-16", device="cuda:0", seed: Optional[int] = None, engine=None, precision: str = "fp32") -> FernCLIP:
+def create_model(model_name="ViT-B-16", device="cuda:0", seed: Optional[int] = None, engine=None, precision: str = "fp32",
+                 force_quick_gelu: bool = False) -> FernCLIP:
     """Counterpart of ``open_clip.create_model_and_transforms(name, device=)`` (test_fiq.py:141): random-init when
-    ``seed`` is given, otherwise weights must follow through ``load_state_dict(saved["CLIP"])``."""
-    m = FernCLIP(model_name, device, engine=engine, precision=precision)
+    ``seed`` is given, otherwise weights must follow through ``load_state_dict(saved["CLIP"])``.  ``force_quick_gelu`` is
+    open_clip's argument: what ``pretrained="openai"`` turns on there (QuickGELU in both towers) is requested here with
+    ``force_quick_gelu=True`` or a ``*-quickgelu`` model name."""
+    m = FernCLIP(model_name, device, engine=engine, precision=precision, force_quick_gelu=force_quick_gelu)
     if seed is not None:
         m.init_random(seed)
     return m

@@ -101,6 +101,7 @@ struct ClipW {
     LNW ln_pre, ln_post, ln_final;
     std::vector<ClipBlockW> vblocks, tblocks;
     const float *tok_emb = nullptr, *tpos = nullptr, *tproj_t = nullptr;
+    int act = FERN_ACT_GELU;         // MLP activation of BOTH towers (fern_clip_set_activation); lives with the weights: forks read the root's
 };
 
 enum ProfKind { PROF_GEMM = 0, PROF_ATTN = 1, PROF_TOPK = 2, PROF_SWEEP = 3, PROF_STAGE = 4 };
@@ -157,6 +158,12 @@ struct fern_ctx {
     std::vector<hipEvent_t> ev_pool;
     LaunchTimer timer;
 };
+
+// c_fc epilogue of the CLIP towers' MLPs, every walker and precision mode (the fusion BERT keeps exact-erf GELU)
+static int clip_mlp_epi(const fern_ctx* c) {
+    const fern_ctx* root = c->parent ? c->parent : c;
+    return root->clip.act == FERN_ACT_QUICK_GELU ? EPI_BIAS_QUICKGELU : EPI_BIAS_GELU;
+}
 
 static int ws_begin(fern_ctx* c, hipStream_t s) {
     if (c->blocks.size() > 1) {      // grew during the previous op: merge into one block (outside capture only)
@@ -880,6 +887,16 @@ extern "C" int fern_set_precision(fern_ctx* c, int precision) {
     c->f32x3 = split;
     return FERN_OK;
 }
+// The MLP activation of the CLIP towers (open_clip's quick_gelu / force_quick_gelu, HF's hidden_act): a property of the weights, so it
+// is set on the context that owns them and its forks follow it (clip_mlp_epi reads the root's value at every launch).
+extern "C" int fern_clip_set_activation(fern_ctx* c, int act) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_clip_set_activation: ctx is NULL");
+    if (act != FERN_ACT_GELU && act != FERN_ACT_QUICK_GELU)
+        return fail(FERN_ERR_ARG, "fern_clip_set_activation: unknown activation " + std::to_string(act) + " (FERN_ACT_GELU = 0, FERN_ACT_QUICK_GELU = 1)");
+    if (c->parent) return fail(FERN_ERR_ARG, "fern_clip_set_activation: set it on the root context, its forks follow");
+    c->clip.act = act;
+    return FERN_OK;
+}
 extern "C" int fern_get_precision(fern_ctx* c) { return !c ? FERN_ERR_ARG : c->f32x3 ? FERN_PREC_F32X3 : c->precision; }
 
 // ------------------------------------------------------------------------------------------------
@@ -1208,7 +1225,7 @@ static int clip_block(fern_ctx* c, const ClipBlockW& Bk, float* X, float* XN, fl
     po.R = X;
     FERN_TRY(run_gemm(c, po, s));
     HIP_TRY(launch_layernorm(X, nullptr, Bk.ln2.g, Bk.ln2.b, XN, R, width, width, width, 1e-5f, s));
-    FERN_TRY(run_gemm(c, gemm_desc(XN, width, Bk.fc, H, Bk.fc.out, (int)R, EPI_BIAS_GELU), s));
+    FERN_TRY(run_gemm(c, gemm_desc(XN, width, Bk.fc, H, Bk.fc.out, (int)R, clip_mlp_epi(c)), s));
     GemmParams p2 = gemm_desc(H, Bk.fc.out, Bk.proj, X, width, (int)R, EPI_BIAS_RESIDUAL);
     p2.R = X;
     return run_gemm(c, p2, s);
@@ -1230,7 +1247,7 @@ static int clip_block_bf16(fern_ctx* c, const ClipBlockW& Bk, float* X, unsigned
     po.R = X;
     FERN_TRY(run_gemm_b(c, po, s));
     HIP_TRY(launch_layernorm_bf16(X, Bk.ln2.g, Bk.ln2.b, XNb, R, width, width, width, 1e-5f, s));
-    FERN_TRY(run_gemm_b(c, gemm_desc_b(XNb, width, Bk.fc, Hb, Bk.fc.out, (int)R, EPI_BIAS_GELU, true), s));
+    FERN_TRY(run_gemm_b(c, gemm_desc_b(XNb, width, Bk.fc, Hb, Bk.fc.out, (int)R, clip_mlp_epi(c), true), s));
     GemmParams p2 = gemm_desc_b(Hb, Bk.fc.out, Bk.proj, X, width, (int)R, EPI_BIAS_RESIDUAL, false);
     p2.R = X;
     return run_gemm_b(c, p2, s);
@@ -1255,7 +1272,7 @@ static int clip_block_fp8(fern_ctx* c, const ClipBlockW& Bk, float* X, unsigned 
     po.R = X;
     FERN_TRY(run_gemm_b(c, po, s));
     HIP_TRY(launch_layernorm_fp8(X, Bk.ln2.g, Bk.ln2.b, XN8, SA, R, width, width, width, 1e-5f, s));
-    FERN_TRY(run_gemm_b(c, gemm_desc_f8(XN8, SA, width, Bk.fc, Hb, mlp, (int)R, EPI_BIAS_GELU, true), s));
+    FERN_TRY(run_gemm_b(c, gemm_desc_f8(XN8, SA, width, Bk.fc, Hb, mlp, (int)R, clip_mlp_epi(c), true), s));
     HIP_TRY(launch_quantize_rows_fp8(Hb, nullptr, mlp, H8, mlp, SA, R, mlp, s));
     GemmParams p2 = gemm_desc_f8(H8, SA, mlp, Bk.proj, X, width, (int)R, EPI_BIAS_RESIDUAL, false);
     p2.R = X;
@@ -1290,7 +1307,7 @@ static int clip_block_mx8(fern_ctx* c, const ClipBlockW& Bk, unsigned short* Xb,
     HIP_TRY(launch_layernorm_mx8(nullptr, Bk.ln2.g, Bk.ln2.b, XN8, SM, R, R, width, width, width, 1e-5f, s, Xb));
     // c_fc quantises its GELU output where it is produced (fp32 values -> e4m3fn + block scales): no bf16 round trip, no extra pass
     unsigned char* SH = SM + ((size_t)R * (width / 32) + 255) / 256 * 256;      // H's scales, behind the LayerNorm output's
-    GemmParams pf = gemm_desc_mx(XN8, SM, R, width, Bk.fc, H8, mlp, (int)R, EPI_BIAS_GELU, false);
+    GemmParams pf = gemm_desc_mx(XN8, SM, R, width, Bk.fc, H8, mlp, (int)R, clip_mlp_epi(c), false);
     pf.out_mx8 = 1; pf.mxc = SH; pf.mxc_rows = R;
     FERN_TRY(run_gemm_b(c, pf, s));
     GemmParams p2 = gemm_desc_mx(H8, SH, R, mlp, Bk.proj, Xb, width, (int)R, EPI_BIAS_RESIDUAL, true);
@@ -1337,7 +1354,7 @@ static int clip_block_mxmlp(fern_ctx* c, const ClipBlockW& Bk, float* X, float* 
     }
     HIP_TRY(launch_layernorm_mx8(X, Bk.ln2.g, Bk.ln2.b, XN8, SM, R, R, width, width, width, 1e-5f, s));
     unsigned char* SH = SM + ((size_t)R * (width / 32) + 255) / 256 * 256;      // H's scales, behind the LayerNorm output's
-    GemmParams pf = gemm_desc_mx(XN8, SM, R, width, Bk.fc, H8, mlp, (int)R, EPI_BIAS_GELU, false);
+    GemmParams pf = gemm_desc_mx(XN8, SM, R, width, Bk.fc, H8, mlp, (int)R, clip_mlp_epi(c), false);
     pf.out_mx8 = 1; pf.mxc = SH; pf.mxc_rows = R;
     FERN_TRY(run_gemm_b(c, pf, s));
     GemmParams p2 = gemm_desc_mx(H8, SH, R, mlp, Bk.proj, X, width, (int)R, EPI_BIAS_RESIDUAL, false);
@@ -1401,7 +1418,7 @@ static int clip_block_cls_only(fern_ctx* c, const ClipBlockW& Bk, const float* X
     po.R = CLS;
     FERN_TRY(run_gemm(c, po, s));
     HIP_TRY(launch_layernorm(CLS, nullptr, Bk.ln2.g, Bk.ln2.b, T0, batch, width, width, width, 1e-5f, s));
-    FERN_TRY(run_gemm(c, gemm_desc(T0, width, Bk.fc, H, Bk.fc.out, batch, EPI_BIAS_GELU), s));
+    FERN_TRY(run_gemm(c, gemm_desc(T0, width, Bk.fc, H, Bk.fc.out, batch, clip_mlp_epi(c)), s));
     GemmParams p2 = gemm_desc(H, Bk.fc.out, Bk.proj, CLS, width, batch, EPI_BIAS_RESIDUAL);
     p2.R = CLS;
     // The class rows' c_proj is M = batch with an unsplit k chain of 3072 (ViT-B): 24 workgroups walking 48 k tiles each, 58 us.  Like
@@ -1754,7 +1771,7 @@ static int pair_chunk(fern_ctx* c, const float* images, float* out_img, const in
         FERN_TRY(run_gemm_pair(c, pov, pot, s));
         HIP_TRY(launch_layernorm(X, nullptr, Bv.ln2.g, Bv.ln2.b, XN, R, vw, vw, vw, 1e-5f, s));
         HIP_TRY(launch_layernorm(Xt, nullptr, Bt.ln2.g, Bt.ln2.b, XNt, Rt, tw, tw, tw, 1e-5f, s));
-        FERN_TRY(run_gemm_pair(c, gemm_desc(XN, vw, Bv.fc, H, Bv.fc.out, (int)R, EPI_BIAS_GELU), gemm_desc(XNt, tw, Bt.fc, Ht, Bt.fc.out, (int)Rt, EPI_BIAS_GELU), s));
+        FERN_TRY(run_gemm_pair(c, gemm_desc(XN, vw, Bv.fc, H, Bv.fc.out, (int)R, clip_mlp_epi(c)), gemm_desc(XNt, tw, Bt.fc, Ht, Bt.fc.out, (int)Rt, clip_mlp_epi(c)), s));
         GemmParams ppv = gemm_desc(H, Bv.fc.out, Bv.proj, X, vw, (int)R, EPI_BIAS_RESIDUAL), ppt = gemm_desc(Ht, Bt.fc.out, Bt.proj, Xt, tw, (int)Rt, EPI_BIAS_RESIDUAL);
         ppv.R = X; ppt.R = Xt;
         FERN_TRY(run_gemm_pair(c, ppv, ppt, s));
@@ -1823,9 +1840,9 @@ static int pair_chunk_mximg(fern_ctx* c, const float* images, float* out_img, co
         FERN_TRY(run_gemm_b_pair(c, pov, pot, s));
         HIP_TRY(launch_layernorm_mx8(X, Bv.ln2.g, Bv.ln2.b, XN8, SM, R, R, vw, vw, vw, 1e-5f, s));
         HIP_TRY(launch_layernorm_bf16(Xt, Bt.ln2.g, Bt.ln2.b, XNtb, Rt, tw, tw, tw, 1e-5f, s));
-        GemmParams pfv = gemm_desc_mx(XN8, SM, R, vw, Bv.fc, H8, mlp, (int)R, EPI_BIAS_GELU, false);
+        GemmParams pfv = gemm_desc_mx(XN8, SM, R, vw, Bv.fc, H8, mlp, (int)R, clip_mlp_epi(c), false);
         pfv.out_mx8 = 1; pfv.mxc = SH; pfv.mxc_rows = R;
-        FERN_TRY(run_gemm_b_pair(c, pfv, gemm_desc_b(XNtb, tw, Bt.fc, Htb, Bt.fc.out, (int)Rt, EPI_BIAS_GELU, true), s));
+        FERN_TRY(run_gemm_b_pair(c, pfv, gemm_desc_b(XNtb, tw, Bt.fc, Htb, Bt.fc.out, (int)Rt, clip_mlp_epi(c), true), s));
         GemmParams ppv = gemm_desc_mx(H8, SH, R, mlp, Bv.proj, X, vw, (int)R, EPI_BIAS_RESIDUAL, false);
         GemmParams ppt = gemm_desc_b(Htb, Bt.fc.out, Bt.proj, Xt, tw, (int)Rt, EPI_BIAS_RESIDUAL, false);
         ppv.R = X; ppt.R = Xt;
@@ -2417,18 +2434,21 @@ extern "C" int fern_u8_to_normalized_chw(fern_ctx* c, const uint8_t* src, int64_
 // ------------------------------------------------------------------------------------------------
 // building blocks
 // ------------------------------------------------------------------------------------------------
+// fern_epilogue -> GemmEpi: the first four values coincide, FERN_EPI_BIAS_QUICKGELU has its own (kernels.h)
+static bool public_epi_ok(int e) { return (e >= FERN_EPI_BIAS && e <= FERN_EPI_BIAS_RESIDUAL) || e == FERN_EPI_BIAS_QUICKGELU; }
+static int gemm_epi_of(int e) { return e == FERN_EPI_BIAS_QUICKGELU ? (int)EPI_BIAS_QUICKGELU : e; }
 extern "C" int fern_gemm(fern_ctx* c, const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* residual,
                          float* C, int64_t ldc, int M, int N, int K, int epilogue, void* stream) {
     if (!c || M < 0 || N < 0 || K <= 0) return fail(FERN_ERR_ARG, "fern_gemm: bad argument");
     if (M == 0 || N == 0) return FERN_OK;
     if (!A || !W || !C) return fail(FERN_ERR_ARG, "fern_gemm: NULL argument");
-    if (epilogue < FERN_EPI_BIAS || epilogue > FERN_EPI_BIAS_RESIDUAL) return fail(FERN_ERR_ARG, "fern_gemm: unknown epilogue");
+    if (!public_epi_ok(epilogue)) return fail(FERN_ERR_ARG, "fern_gemm: unknown epilogue");
     if (epilogue == FERN_EPI_BIAS_RESIDUAL && !residual) return fail(FERN_ERR_ARG, "fern_gemm: residual is NULL");
     if (K % 32) return fail(FERN_ERR_ARG, "fern_gemm: K must be a multiple of 32");
     HIP_TRY(hipSetDevice(c->device));
     GemmParams p{};
     p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.bias = bias; p.R = residual; p.C = C; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K; p.epi = epilogue; p.aload = ALOAD_PLAIN;
+    p.M = M; p.N = N; p.K = K; p.epi = gemm_epi_of(epilogue); p.aload = ALOAD_PLAIN;
     return run_gemm(c, p, (hipStream_t)stream);
 }
 
@@ -2437,15 +2457,15 @@ extern "C" int fern_gemm_bf16(fern_ctx* c, const uint16_t* A, int64_t lda, const
     if (!c || M < 0 || N < 0 || K <= 0) return fail(FERN_ERR_ARG, "fern_gemm_bf16: bad argument");
     if (M == 0 || N == 0) return FERN_OK;
     if (!A || !W || !C) return fail(FERN_ERR_ARG, "fern_gemm_bf16: NULL argument");
-    if (epilogue < FERN_EPI_BIAS || epilogue > FERN_EPI_BIAS_RESIDUAL) return fail(FERN_ERR_ARG, "fern_gemm_bf16: unknown epilogue");
+    if (!public_epi_ok(epilogue)) return fail(FERN_ERR_ARG, "fern_gemm_bf16: unknown epilogue");
     if (epilogue == FERN_EPI_BIAS_RESIDUAL && (!residual || out_bf16)) return fail(FERN_ERR_ARG, "fern_gemm_bf16: the residual epilogue needs a residual and fp32 output");
     if (K % 32 || lda % 8 || ldw % 8) return fail(FERN_ERR_ARG, "fern_gemm_bf16: K % 32, lda % 8 and ldw % 8 must be 0");
     HIP_TRY(hipSetDevice(c->device));
     GemmParams p{};
     p.Ab = A; p.lda = lda; p.Wb = W; p.ldw = ldw; p.bias = bias; p.R = residual; p.C = reinterpret_cast<float*>(C); p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K; p.epi = epilogue; p.aload = ALOAD_PLAIN; p.out_bf16 = out_bf16 ? 1 : 0;
+    p.M = M; p.N = N; p.K = K; p.epi = gemm_epi_of(epilogue); p.aload = ALOAD_PLAIN; p.out_bf16 = out_bf16 ? 1 : 0;
     int slot;
-    FERN_TRY(prof_open(c, PROF_GEMM, 2.0 * M * (double)N * K, (hipStream_t)stream, &slot, M, N, K, 100 + epilogue));
+    FERN_TRY(prof_open(c, PROF_GEMM, 2.0 * M * (double)N * K, (hipStream_t)stream, &slot, M, N, K, 100 + p.epi));
     const hipError_t le = launch_gemm_bf16(p, (hipStream_t)stream);
     HIP_TRY_PROF(le, c, slot);
     return prof_close(c, slot, (hipStream_t)stream);
@@ -2467,14 +2487,14 @@ extern "C" int fern_gemm_fp8(fern_ctx* c, const uint8_t* A, int64_t lda, const f
     if (!c || M < 0 || N < 0 || K <= 0) return fail(FERN_ERR_ARG, "fern_gemm_fp8: bad argument");
     if (M == 0 || N == 0) return FERN_OK;
     if (!A || !W || !C || !scale_a || !scale_w) return fail(FERN_ERR_ARG, "fern_gemm_fp8: NULL argument");
-    if (epilogue != FERN_EPI_BIAS && epilogue != FERN_EPI_BIAS_GELU && epilogue != FERN_EPI_BIAS_RESIDUAL)
-        return fail(FERN_ERR_ARG, "fern_gemm_fp8: epilogue must be BIAS, BIAS_GELU or BIAS_RESIDUAL");
+    if (epilogue != FERN_EPI_BIAS && epilogue != FERN_EPI_BIAS_GELU && epilogue != FERN_EPI_BIAS_QUICKGELU && epilogue != FERN_EPI_BIAS_RESIDUAL)
+        return fail(FERN_ERR_ARG, "fern_gemm_fp8: epilogue must be BIAS, BIAS_GELU, BIAS_QUICKGELU or BIAS_RESIDUAL");
     if (epilogue == FERN_EPI_BIAS_RESIDUAL && (!residual || out_bf16)) return fail(FERN_ERR_ARG, "fern_gemm_fp8: the residual epilogue needs a residual and fp32 output");
     if (K % 64 || lda % 16 || ldw % 16) return fail(FERN_ERR_ARG, "fern_gemm_fp8: K % 64, lda % 16 and ldw % 16 must be 0");
     HIP_TRY(hipSetDevice(c->device));
     GemmParams p{};
     p.Ab = reinterpret_cast<const unsigned short*>(A); p.lda = lda; p.Wb = reinterpret_cast<const unsigned short*>(W); p.ldw = ldw;
-    p.bias = bias; p.R = residual; p.C = reinterpret_cast<float*>(C); p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = epilogue;
+    p.bias = bias; p.R = residual; p.C = reinterpret_cast<float*>(C); p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = gemm_epi_of(epilogue);
     p.aload = ALOAD_PLAIN; p.out_bf16 = out_bf16 ? 1 : 0; p.fp8 = 1; p.scale_a = scale_a; p.scale_w = scale_w;
     return run_gemm_b(c, p, (hipStream_t)stream);
 }
@@ -2496,15 +2516,15 @@ extern "C" int fern_gemm_mx8(fern_ctx* c, const uint8_t* A, int64_t lda, const u
     if (!c || M < 0 || N < 0 || K <= 0) return fail(FERN_ERR_ARG, "fern_gemm_mx8: bad argument");
     if (M == 0 || N == 0) return FERN_OK;
     if (!A || !W || !C || !scales_a || !scales_w) return fail(FERN_ERR_ARG, "fern_gemm_mx8: NULL argument");
-    if (epilogue != FERN_EPI_BIAS && epilogue != FERN_EPI_BIAS_GELU && epilogue != FERN_EPI_BIAS_RESIDUAL)
-        return fail(FERN_ERR_ARG, "fern_gemm_mx8: epilogue must be BIAS, BIAS_GELU or BIAS_RESIDUAL");
+    if (epilogue != FERN_EPI_BIAS && epilogue != FERN_EPI_BIAS_GELU && epilogue != FERN_EPI_BIAS_QUICKGELU && epilogue != FERN_EPI_BIAS_RESIDUAL)
+        return fail(FERN_ERR_ARG, "fern_gemm_mx8: epilogue must be BIAS, BIAS_GELU, BIAS_QUICKGELU or BIAS_RESIDUAL");
     if (epilogue == FERN_EPI_BIAS_RESIDUAL && !residual) return fail(FERN_ERR_ARG, "fern_gemm_mx8: the residual epilogue needs a residual");
     if (K % 128 || lda % 16 || ldw % 16 || scale_rows_a < M || scale_rows_w < N)
         return fail(FERN_ERR_ARG, "fern_gemm_mx8: K % 128, lda % 16 and ldw % 16 must be 0, scale_rows >= rows");
     HIP_TRY(hipSetDevice(c->device));
     GemmParams p{};
     p.Ab = reinterpret_cast<const unsigned short*>(A); p.lda = lda; p.Wb = reinterpret_cast<const unsigned short*>(W); p.ldw = ldw;
-    p.bias = bias; p.R = residual; p.C = reinterpret_cast<float*>(C); p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = epilogue;
+    p.bias = bias; p.R = residual; p.C = reinterpret_cast<float*>(C); p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = gemm_epi_of(epilogue);
     p.aload = ALOAD_PLAIN; p.out_bf16 = out_bf16 ? 1 : 0; p.fp8 = 2; p.mxa = scales_a; p.mxa_rows = scale_rows_a; p.mxw = scales_w; p.mxw_rows = scale_rows_w;
     if (out_bf16 && epilogue == FERN_EPI_BIAS_RESIDUAL) { p.Rb = reinterpret_cast<const unsigned short*>(residual); p.R = nullptr; }      // bf16 residual stream
     return run_gemm_b(c, p, (hipStream_t)stream);
@@ -2516,13 +2536,14 @@ extern "C" int fern_gemm_mx8_quant(fern_ctx* c, const uint8_t* A, int64_t lda, c
     if (!c || M < 0 || N < 0 || K <= 0) return fail(FERN_ERR_ARG, "fern_gemm_mx8_quant: bad argument");
     if (M == 0 || N == 0) return FERN_OK;
     if (!A || !W || !C8 || !scales_a || !scales_w || !scales_c) return fail(FERN_ERR_ARG, "fern_gemm_mx8_quant: NULL argument");
-    if (epilogue != FERN_EPI_BIAS && epilogue != FERN_EPI_BIAS_GELU) return fail(FERN_ERR_ARG, "fern_gemm_mx8_quant: epilogue must be BIAS or BIAS_GELU");
+    if (epilogue != FERN_EPI_BIAS && epilogue != FERN_EPI_BIAS_GELU && epilogue != FERN_EPI_BIAS_QUICKGELU)
+        return fail(FERN_ERR_ARG, "fern_gemm_mx8_quant: epilogue must be BIAS, BIAS_GELU or BIAS_QUICKGELU");
     if (K % 128 || N % 128 || lda % 16 || ldw % 16 || ldc % 16 || scale_rows_a < M || scale_rows_w < N || scale_rows_c < M)
         return fail(FERN_ERR_ARG, "fern_gemm_mx8_quant: K % 128, N % 128, lda / ldw / ldc % 16 must be 0, scale_rows >= rows");
     HIP_TRY(hipSetDevice(c->device));
     GemmParams p{};
     p.Ab = reinterpret_cast<const unsigned short*>(A); p.lda = lda; p.Wb = reinterpret_cast<const unsigned short*>(W); p.ldw = ldw;
-    p.bias = bias; p.C = reinterpret_cast<float*>(C8); p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = epilogue;
+    p.bias = bias; p.C = reinterpret_cast<float*>(C8); p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = gemm_epi_of(epilogue);
     p.aload = ALOAD_PLAIN; p.fp8 = 2; p.mxa = scales_a; p.mxa_rows = scale_rows_a; p.mxw = scales_w; p.mxw_rows = scale_rows_w;
     p.out_mx8 = 1; p.mxc = scales_c; p.mxc_rows = scale_rows_c;
     return run_gemm_b(c, p, (hipStream_t)stream);

@@ -834,6 +834,7 @@ __global__ __launch_bounds__(256) void gemm_f32_skinny_kernel(GemmParams p) {
             float v = acc[t][r] + bia;
             switch (p.epi) {
                 case EPI_BIAS_GELU: v = gelu_erf2(f32x2{v, v})[0]; break;      // the 32x32 kernels' arithmetic, bit for bit
+                case EPI_BIAS_QUICKGELU: v = quick_gelu2(f32x2{v, v})[0]; break;
                 case EPI_BIAS_RELU: v = fmaxf(v, 0.0f); break;
                 case EPI_BIAS_RESIDUAL: v += add[r]; break;
                 case EPI_BIAS_RESIDUAL_RELU: v = fmaxf(v + add[r], 0.0f); break;
@@ -1102,7 +1103,7 @@ static bool tuning_enabled() {
 
 static bool split_ok(const GemmParams& p) {      // row-independent epilogue and loader: the rows can be cut anywhere
     return p.aload == ALOAD_PLAIN && p.w_sample <= 1 && p.ksplit <= 1 &&
-           (p.epi == EPI_BIAS || p.epi == EPI_BIAS_GELU || p.epi == EPI_BIAS_RELU || p.epi == EPI_BIAS_RESIDUAL ||
+           (p.epi == EPI_BIAS || p.epi == EPI_BIAS_GELU || p.epi == EPI_BIAS_QUICKGELU || p.epi == EPI_BIAS_RELU || p.epi == EPI_BIAS_RESIDUAL ||
             p.epi == EPI_BIAS_RESIDUAL_RELU || p.epi == EPI_COLAFFINE_TANH);
 }
 // the rows [rows_a, M) of a plain-epilogue GEMM as a GEMM of their own

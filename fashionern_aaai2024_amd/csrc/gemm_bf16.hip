@@ -362,6 +362,7 @@ __device__ __forceinline__ void mx8_tile_body(const GemmParams& p, const int bid
             for (int r = 0; r < 16; r += 2) {
                 f32x2 v2 = {acc[i][j][r] + bia, acc[i][j][r + 1] + bia};
                 if (p.epi == EPI_BIAS_GELU) v2 = gelu_tanh2(v2);      // the family's GELU (gemm_epilogue.h): same values as the stored epilogues
+                else if (p.epi == EPI_BIAS_QUICKGELU) v2 = quick_gelu2(v2);
                 patch[((r & 3) + 8 * (r >> 2) + 4 * lh) * PS + l31] = v2[0];
                 patch[(((r + 1) & 3) + 8 * ((r + 1) >> 2) + 4 * lh) * PS + l31] = v2[1];
                 __builtin_amdgcn_sched_barrier(0);      // one pair at a time (register budget of the 128-VGPR configurations)
@@ -688,7 +689,7 @@ static bool rp_args_ok(const GemmParams& p) {
     if (p.fp8 == 2) {
         if (!p.mxa || !p.mxw || p.scale_a || ((uintptr_t)p.mxa & 3) || ((uintptr_t)p.mxw & 3) || p.mxa_rows < p.M || p.mxw_rows < p.N) return false;
         if (p.epi == EPI_BIAS_RESIDUAL && (p.out_bf16 ? !p.Rb : !p.R)) return false;
-        if (p.out_mx8 && (!p.mxc || p.mxc_rows < p.M || (p.N & 31) || (p.ldc & 15) || ((uintptr_t)p.C & 15) || (p.epi != EPI_BIAS && p.epi != EPI_BIAS_GELU)))
+        if (p.out_mx8 && (!p.mxc || p.mxc_rows < p.M || (p.N & 31) || (p.ldc & 15) || ((uintptr_t)p.C & 15) || (p.epi != EPI_BIAS && p.epi != EPI_BIAS_GELU && p.epi != EPI_BIAS_QUICKGELU)))
             return false;
     }
     return true;

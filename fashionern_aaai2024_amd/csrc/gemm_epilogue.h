@@ -72,10 +72,25 @@ __device__ __forceinline__ f32x2 gelu_tanh2(f32x2 x) {
     const f32x2 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
     return x * r;
 }
+// QuickGELU, x * sigmoid(1.702 x): the MLP activation of OpenAI's CLIP checkpoints (EPI_BIAS_QUICKGELU).  It is its own definition, not
+// an approximation of the erf form, so ONE function serves every family: a given fp32 input yields the same bits in the fp32, f32x3,
+// bf16, fp8 and block-scaled kernels.  One multiply, one v_exp_f32 on the pre-scaled argument, one add, the 1-ulp v_rcp_f32 and one
+// multiply: ~4.5 issue slots per element (the two transcendentals are quarter rate), fewer than any of the three GELU forms above.
+// |quick_gelu2 - float64 x sigmoid(1.702 x)| <= 1.5e-6 over [-30, 30] (fp32; tests/test_quickgelu_cpu.py restates it operation for
+// operation).  exp2 overflow (x << 0) gives rcp(inf) = 0 and underflow x * 1: both limits.
+__device__ __forceinline__ f32x2 quick_gelu2(f32x2 x) {
+    const f32x2 w = x * (-1.702f * 1.4426950408889634f);      // -1.702 x log2(e)
+    const f32x2 e = {__builtin_amdgcn_exp2f(w[0]), __builtin_amdgcn_exp2f(w[1])};
+    const f32x2 d = e + 1.0f;
+    const f32x2 r = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+    return x * r;
+}
 // FAST (template parameter of the epilogues below): 0 = gelu_erf2 (fp32 parity mode), 1 = gelu_fast2 (bf16 / per-row fp8 families),
-// 2 = gelu_tanh2 (block-scaled fp8 family)
+// 2 = gelu_tanh2 (block-scaled fp8 family), 3 = quick_gelu2 (EPI_BIAS_QUICKGELU: instantiated as EPI_BIAS_GELU with FAST = 3 in every family)
+constexpr int QUICK = 3;
 template <int FAST>
 __device__ __forceinline__ f32x2 gelu_of(f32x2 x) {
+    if (FAST == QUICK) return quick_gelu2(x);
     if (FAST == 2) return gelu_tanh2(x);
     if (FAST == 1) return gelu_fast2(x);
     return gelu_erf2(x);
@@ -329,10 +344,12 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
         if (ALLOW_BF16_OUT && ALLOW_SCALED && p.scale_a) {      // fp8 operands: scales folded back here; bias / GELU / residual forms
             if (p.out_bf16) {
                 if (p.epi == EPI_BIAS_GELU) plain_epilogue<EPI_BIAS_GELU, true, true, RGELU>(p, acc, row_w, col_w, l31, lh);
+                else if (p.epi == EPI_BIAS_QUICKGELU) plain_epilogue<EPI_BIAS_GELU, true, true, QUICK>(p, acc, row_w, col_w, l31, lh);
                 else plain_epilogue<EPI_BIAS, true, true>(p, acc, row_w, col_w, l31, lh);
             } else {
                 if (p.epi == EPI_BIAS_RESIDUAL) plain_epilogue<EPI_BIAS_RESIDUAL, false, true>(p, acc, row_w, col_w, l31, lh);
                 else if (p.epi == EPI_BIAS_GELU) plain_epilogue<EPI_BIAS_GELU, false, true, RGELU>(p, acc, row_w, col_w, l31, lh);
+                else if (p.epi == EPI_BIAS_QUICKGELU) plain_epilogue<EPI_BIAS_GELU, false, true, QUICK>(p, acc, row_w, col_w, l31, lh);
                 else plain_epilogue<EPI_BIAS, false, true>(p, acc, row_w, col_w, l31, lh);
             }
             return;
@@ -344,6 +361,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
             }
             switch (p.epi) {      // bf16 outputs feed the next bf16 GEMM: bias (+ GELU / ReLU) only
                 case EPI_BIAS_GELU: plain_epilogue<EPI_BIAS_GELU, true, false, RGELU>(p, acc, row_w, col_w, l31, lh); break;
+                case EPI_BIAS_QUICKGELU: plain_epilogue<EPI_BIAS_GELU, true, false, QUICK>(p, acc, row_w, col_w, l31, lh); break;
                 case EPI_BIAS_RELU: plain_epilogue<EPI_BIAS_RELU, true, false>(p, acc, row_w, col_w, l31, lh); break;
                 default: plain_epilogue<EPI_BIAS, true, false>(p, acc, row_w, col_w, l31, lh); break;
             }
@@ -351,6 +369,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x16 (&acc)
         }
         switch (p.epi) {
             case EPI_BIAS_GELU: plain_epilogue<EPI_BIAS_GELU, false, false, ALLOW_BF16_OUT ? RGELU : 0>(p, acc, row_w, col_w, l31, lh); break;
+            case EPI_BIAS_QUICKGELU: plain_epilogue<EPI_BIAS_GELU, false, false, QUICK>(p, acc, row_w, col_w, l31, lh); break;
             case EPI_BIAS_RELU: plain_epilogue<EPI_BIAS_RELU, false, false>(p, acc, row_w, col_w, l31, lh); break;
             case EPI_BIAS_RESIDUAL: plain_epilogue<EPI_BIAS_RESIDUAL, false, false>(p, acc, row_w, col_w, l31, lh); break;
             case EPI_BIAS_RESIDUAL_RELU: plain_epilogue<EPI_BIAS_RESIDUAL_RELU, false, false>(p, acc, row_w, col_w, l31, lh); break;

@@ -93,6 +93,7 @@ __device__ __forceinline__ void pp_quant_epilogue(const GemmParams& p, f32x16 (&
             for (int r = 0; r < 16; r += 2) {
                 f32x2 v2 = {acc[i][j][r] + bia, acc[i][j][r + 1] + bia};
                 if (p.epi == EPI_BIAS_GELU) v2 = gelu_tanh2(v2);
+                else if (p.epi == EPI_BIAS_QUICKGELU) v2 = quick_gelu2(v2);
                 patch[((r & 3) + 8 * (r >> 2) + 4 * lh) * PS + l31] = v2[0];
                 patch[(((r + 1) & 3) + 8 * ((r + 1) >> 2) + 4 * lh) * PS + l31] = v2[1];
             }

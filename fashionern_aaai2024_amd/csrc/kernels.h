@@ -110,7 +110,8 @@ enum GemmEpi : int {
                              // partial[row][nb] = sum_col v * G[(row/13)*ldg + col] * aux0[col]     (VisualSR local branch)
     EPI_BIAS_RESIDUAL_RELU = 8, // C = relu(acc + bias + R[row*ldc + col])   (ResNet bottleneck tail: conv3 + BN folded + identity)
     EPI_TOPK_FILTER = 9,        // rows = queries, columns = gallery rows: nothing is stored; acc >= the query's bound is appended to p.filt
-    EPI_RANK_COUNT = 10         // same sweep, nothing stored: per (query, target key) the number of gallery rows whose key is greater -> p.rankc
+    EPI_RANK_COUNT = 10,        // same sweep, nothing stored: per (query, target key) the number of gallery rows whose key is greater -> p.rankc
+    EPI_BIAS_QUICKGELU = 11     // C = v * sigmoid(1.702 v), v = acc + bias (OpenAI CLIP's MLP activation); accepted wherever EPI_BIAS_GELU is
 };
 __host__ __device__ inline bool epi_is_reduce(int e) { return e == EPI_RELU_DOT || e == EPI_SR_LOCAL; }
 // ALOAD_IM2COL: non-overlapping patches of an NCHW image (ViT conv1); ALOAD_CONV3: 3x3 / stride 1 / pad 1 window over an
@@ -167,7 +168,7 @@ struct GemmParams {
     const unsigned char* mxa;     // A's scales, mxa_rows >= M rows per 128-k tile
     const unsigned char* mxw;     // W's scales, mxw_rows >= N
     long mxa_rows, mxw_rows;
-    // out_mx8 (fp8 == 2, EPI_BIAS / EPI_BIAS_GELU, N % 32 == 0): the output is quantised where it is produced -- C holds e4m3fn
+    // out_mx8 (fp8 == 2, EPI_BIAS / EPI_BIAS_GELU / EPI_BIAS_QUICKGELU, N % 32 == 0): the output is quantised where it is produced -- C holds e4m3fn
     // bytes (ldc in bytes), mxc the E8M0 scales of its 32-column blocks (mx_scale_offset layout, mxc_rows rows): the next
     // GEMM's A operand, with the same rounding as launch_quantize_mx8 applied to the fp32 values.
     int out_mx8;

@@ -20,6 +20,8 @@ from .synth import ClipConfig
 COMBINER_TARGET, COMBINER_DVR_GLOBAL, COMBINER_DVR_LOCAL, COMBINER_DVR_FINAL = 0, 1, 2, 3
 SR_TARGET, SR_DVR = 0, 1
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RELU, EPI_BIAS_RESIDUAL = 0, 1, 2, 3
+EPI_BIAS_QUICKGELU = 4      # x * sigmoid(1.702 x): accepted wherever EPI_BIAS_GELU is (include/fern.h: fern_epilogue)
+ACT_GELU, ACT_QUICK_GELU = 0, 1
 PART_DVR, PART_TARGET_SR, PART_TARGET_COMBINER, PART_ALL = 1, 2, 4, 7
 PREC_FP32, PREC_BF16, PREC_FP8, PREC_MX8, PREC_F32X3, PREC_MX8_MLP, PREC_MX8_IMG = 0, 1, 2, 3, 4, 5, 6
 QFORM_BF16, QFORM_FP8, QFORM_MX8 = 0, 1, 2
@@ -169,7 +171,12 @@ class FernEngine:
                               cfg.v_mlp, cfg.context_length, cfg.vocab_size, cfg.t_width, cfg.t_heads, cfg.t_layers, cfg.t_mlp,
                               1 if cfg.v_arch == "resnet" else 0, (C.c_int * 4)(*cfg.r_layers), cfg.r_width, cfg.r_heads)
         _lib.check(self.lib.fern_finalize_clip(self._h, C.byref(cc)), "fern_finalize_clip")
+        self.set_clip_activation(ACT_QUICK_GELU if getattr(cfg, "quick_gelu", False) else ACT_GELU)
         self.clip_cfg = cfg
+
+    def set_clip_activation(self, act: int) -> None:
+        """MLP activation of both CLIP towers (ACT_GELU / ACT_QUICK_GELU); `finalize_clip` sets it from `cfg.quick_gelu`.  Forks follow."""
+        _lib.check(self.lib.fern_clip_set_activation(self._h, int(act)), "fern_clip_set_activation")
 
     # ---- encoders -----------------------------------------------------------------------------
     def encode_image(self, images: torch.Tensor) -> torch.Tensor:

@@ -108,7 +108,7 @@ def file_splits(kind, args, clip_model):
              Fashion200kTestQueryDataset(root, "val", pre, local_dir=local_dir))]
 
 
-def main(kind: str) -> None:
+def build_parser(kind: str) -> ArgumentParser:
     p = ArgumentParser()
     p.add_argument("--dataset", default={"fiq": "fashionIQ", "val": "fashionIQ", "cirr": "CIRR", "shoes": "shoes", "200k": "fashion200k"}[kind], type=str)
     p.add_argument("--input-dim", default=224, type=int, help="the tower's image side: 224 for ViT-B-16 / ViT-B-32 / ViT-L-14, 336 for ViT-L-14-336, 288 for RN50x4")
@@ -130,7 +130,15 @@ def main(kind: str) -> None:
                         "three bf16 planes per operand (~1.4x faster); bf16 / fp8 / mx8 = perf modes (ViT / text towers)")
     p.add_argument("--rank-metrics", action="store_true",
                    help="fiq / cirr / 200k: after the recalls also print where the targets landed in the full ranking (Recall@K, median / mean rank, MRR)")
-    args = p.parse_args()
+    p.add_argument("--force-quick-gelu", action="store_true",
+                   help="QuickGELU, x * sigmoid(1.702 x), in both CLIP towers' MLPs: open_clip's force_quick_gelu, what it turns on for "
+                        "pretrained='openai' -- needed for OpenAI's checkpoints (RN50x4's only public weights); default: the config's own "
+                        "setting (exact-erf GELU, QuickGELU for the *-quickgelu names)")
+    return p
+
+
+def main(kind: str) -> None:
+    args = build_parser(kind).parse_args()
     setup_seed(args.seed)
     rank, world, local = fd.init_from_env()                 # torchrun: one process per GPU; a lone process is (0, 1, 0)
     if world > 1 and os.environ.get("FERN_BENCH_SHARE_GPU"):  # debug only: several ranks on the one GPU of a dev box (gloo)
@@ -139,7 +147,8 @@ def main(kind: str) -> None:
     if world > 1:
         torch.cuda.set_device(device)
     say = print if rank == 0 else (lambda *a, **k: None)
-    clip_model = create_model(args.clip_model_name, device=device, seed=None if args.clip_path else args.seed, precision=args.precision)
+    clip_model = create_model(args.clip_model_name, device=device, seed=None if args.clip_path else args.seed, precision=args.precision,
+                              force_quick_gelu=args.force_quick_gelu)
     if args.clip_path:
         clip_model.load_state_dict(torch.load(args.clip_path, map_location="cpu")["CLIP"])
     cfg = clip_model.cfg

@@ -35,7 +35,7 @@ def extract_directory(clip_model, image_paths, out_path_of, dim=None, overwrite=
     return done
 
 
-def main() -> None:
+def build_parser() -> ArgumentParser:
     p = ArgumentParser()
     p.add_argument("--images", required=True, help="directory that is searched recursively for images")
     p.add_argument("--out", required=True, help="output directory; the relative path of an image is kept, with '.pth' in place of the extension")
@@ -45,8 +45,15 @@ def main() -> None:
     p.add_argument("--clip-path", type=str, help="checkpoint with key 'CLIP' (open_clip state dict); default: seeded random init")
     p.add_argument("--seed", default=42, type=int)
     p.add_argument("--overwrite", action="store_true")
-    args = p.parse_args()
-    clip_model = create_model(args.clip_model_name, device=torch.device("cuda"), seed=None if args.clip_path else args.seed)
+    p.add_argument("--force-quick-gelu", action="store_true",
+                   help="QuickGELU in both CLIP towers' MLPs (open_clip's force_quick_gelu; what pretrained='openai' turns on)")
+    return p
+
+
+def main() -> None:
+    args = build_parser().parse_args()
+    clip_model = create_model(args.clip_model_name, device=torch.device("cuda"), seed=None if args.clip_path else args.seed,
+                              force_quick_gelu=args.force_quick_gelu)
     if args.clip_path:
         clip_model.load_state_dict(torch.load(args.clip_path, map_location="cpu")["CLIP"])
     paths = sorted({q for pat in args.pattern.split(",") for q in glob.glob(os.path.join(args.images, "**", pat.strip()), recursive=True)})

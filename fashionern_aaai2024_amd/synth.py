@@ -17,8 +17,8 @@ CLS token are non-trivial so that a wrong axis or a dropped term shows up in par
 from __future__ import annotations
 
 import zlib
-from dataclasses import dataclass
-from typing import Dict
+from dataclasses import dataclass, replace
+from typing import Dict, Union
 
 import numpy as np
 
@@ -165,6 +165,10 @@ class ClipConfig:
     r_layers: tuple = (0, 0, 0, 0)
     r_width: int = 0
     r_heads: int = 0
+    # MLP activation of BOTH towers: False = exact-erf GELU (open_clip configs built without weights), True = QuickGELU,
+    # x * sigmoid(1.702 x) (OpenAI's checkpoints: open_clip's "*-quickgelu" configs, force_quick_gelu, pretrained="openai").
+    # Not a shape: clip_state_dict() does not depend on it.
+    quick_gelu: bool = False
 
     @property
     def grid(self) -> int:
@@ -196,6 +200,29 @@ CLIP_CONFIGS = {
     "tiny-long": ClipConfig("tiny-long", 64, 272, 16, 256, 3, 4, 512, 77, 600, 128, 2, 2, 256),        # 290 tokens, head_dim 64, widths % 128 == 0
     "tiny-p14-short": ClipConfig("tiny-p14-short", 64, 112, 14, 128, 2, 4, 512, 77, 600, 128, 2, 2, 256),   # 65 tokens: the patch path alone
 }
+
+# open_clip's "*-quickgelu" configs: the same shapes with "quick_gelu": true (what pretrained="openai" resolves to)
+for _base in ("ViT-B-32", "ViT-B-16", "ViT-L-14", "ViT-L-14-336"):
+    CLIP_CONFIGS[_base + "-quickgelu"] = replace(CLIP_CONFIGS[_base], name=_base + "-quickgelu", quick_gelu=True)
+del _base
+
+
+def resolve_clip_config(name_or_cfg: Union[str, ClipConfig], force_quick_gelu: bool = False) -> ClipConfig:
+    """A config name or instance -> the ClipConfig to build, with open_clip's ``force_quick_gelu`` applied.
+
+    ``force_quick_gelu=True`` turns QuickGELU on whatever the config says (open_clip does this for ``pretrained="openai"``);
+    ``False`` leaves the config's own setting alone, so a ``*-quickgelu`` name stays QuickGELU.  Everything else is unchanged."""
+    if isinstance(name_or_cfg, ClipConfig):
+        cfg = name_or_cfg
+    else:
+        try:
+            cfg = CLIP_CONFIGS[name_or_cfg]
+        except KeyError:
+            raise KeyError(f"unknown CLIP config {name_or_cfg!r}; known: {sorted(CLIP_CONFIGS)}") from None
+    if force_quick_gelu and not cfg.quick_gelu:
+        cfg = replace(cfg, quick_gelu=True)
+    return cfg
+
 
 
 def _conv_bn(sd, seed, conv, bn, cout, cin, k, gamma=1.0):

@@ -136,8 +136,17 @@ typedef enum {
     FERN_EPI_BIAS = 0,          /* C = A W^T + bias (bias may be NULL)            */
     FERN_EPI_BIAS_GELU = 1,     /* exact erf GELU                                 */
     FERN_EPI_BIAS_RELU = 2,
-    FERN_EPI_BIAS_RESIDUAL = 3  /* C = A W^T + bias + R  (R has leading dim ldc)  */
+    FERN_EPI_BIAS_RESIDUAL = 3, /* C = A W^T + bias + R  (R has leading dim ldc)  */
+    FERN_EPI_BIAS_QUICKGELU = 4 /* v * sigmoid(1.702 v), v = A W^T + bias: accepted wherever FERN_EPI_BIAS_GELU is, the quantising
+                                   fern_gemm_mx8_quant included.  One arithmetic for every operand family (each GELU family has its own form) */
 } fern_epilogue;
+
+/* MLP activation of the CLIP towers (fern_clip_set_activation) */
+typedef enum {
+    FERN_ACT_GELU = 0,          /* exact-erf GELU: open_clip's configs built without pretrained weights (the default)                 */
+    FERN_ACT_QUICK_GELU = 1     /* x * sigmoid(1.702 x): OpenAI's checkpoints -- open_clip's pretrained="openai", force_quick_gelu and
+                                   "*-quickgelu" configs, HF CLIPConfig's default hidden_act="quick_gelu"                              */
+} fern_clip_activation;
 
 /* Operand forms the towers' producers write (fern_layernorm_q, fern_im2col_q) */
 typedef enum {
@@ -200,6 +209,11 @@ FERN_API int fern_load_tensor(fern_ctx* ctx, const char* key, const void* host_p
 /* repack for the kernels (packed QKV, folded BatchNorm, transposed projections) and upload */
 FERN_API int fern_finalize_fusion(fern_ctx* ctx, int feature_dim, int parts); /* ERN(clip, feature_dim, device) model.py:8; parts = FERN_PART_* mask */
 FERN_API int fern_finalize_clip(fern_ctx* ctx, const fern_clip_config* cfg); /* open_clip.create_model_and_transforms test_fiq.py:141 */
+/* The activation of BOTH towers' MLPs, in every precision mode and every encoder entry point (the fusion BERT keeps exact-erf GELU).
+ * It belongs to the CLIP weights: fern_finalize_clip returns it to FERN_ACT_GELU, so call this after finalising; contexts forked from
+ * `ctx` follow it (call it on the root context, FERN_ERR_ARG on a fork).  FERN_ERR_ARG for any other value and for a NULL ctx.
+ * Additive: no field of fern_clip_config changes and FERN_ABI_VERSION stays 3. */
+FERN_API int fern_clip_set_activation(fern_ctx* ctx, int act /* fern_clip_activation */);
 
 /* encoders ------------------------------------------------------------------------------ */
 /* clip_model.encode_image(images) -- call site utils/utils.py:64, models/clip_model.py:13-15.

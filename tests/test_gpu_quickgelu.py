@@ -1,0 +1,582 @@
+"""GPU: QuickGELU (EPI_BIAS_QUICKGELU, fern_clip_set_activation) from the GEMM epilogue up to the CLIP towers, every mode.
+
+Bounds are the project's own, unchanged: fp32 GEMMs 2e-5 relative (test_gpu_kernels.py:_close); the bf16 / fp8 / block-scaled
+families the tolerances their GELU cases have in test_gpu_kernels.py; fp32 / f32x3 towers DESIGN section 2's 2e-4 (tiny) and
+1e-3 (full size) of the feature scale; the reduced modes the constants of test_gpu_fusion.py / test_gpu_towers_long.py
+(MIXED_BOUNDS included) against the patched oracle's restatement (tests/quickgelu_oracle.py).
+"""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from fashionern_aaai2024_amd import synth
+from fashionern_aaai2024_amd._lib import FernError
+from fashionern_aaai2024_amd.engine import ACT_GELU, ACT_QUICK_GELU, EPI_BIAS_GELU, EPI_BIAS_QUICKGELU, FernEngine
+from oracle import clip as oclip
+from oracle import fusion as ofusion
+
+import quickgelu_oracle as qo
+
+pytestmark = pytest.mark.gpu
+
+MIXED_BOUNDS = {"mx8img": 2e-3, "mx8mlp": 1e-3}      # test_gpu_fusion.py
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def _rand(*shape, seed=0, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(*shape, generator=g) * scale
+
+
+def _quick64(x):
+    x = x.double()
+    return x * torch.sigmoid(1.702 * x)
+
+
+def _maxerr(got, ref):
+    return (got.detach().cpu().double() - ref.double()).abs().max().item()
+
+
+def _close(got, ref, rel=2e-5):
+    got, ref = got.detach().cpu().double(), ref.double()
+    err = (got - ref).abs().max().item()
+    print(f"max abs err {err:.3e} vs scale {ref.abs().max().item():.3e}")
+    assert err <= rel * max(ref.abs().max().item(), 1e-6), f"max abs err {err} vs scale {ref.abs().max().item()}"
+
+
+def _cos_err(a, b):
+    a, b = a.cpu().double(), b.double()
+    return (1 - F.cosine_similarity(a.flatten(-1 if a.dim() == 2 else 1), b.flatten(-1 if b.dim() == 2 else 1), dim=-1)).abs().max().item()
+
+
+def _quick_engine(cfg, seed, quick=True):
+    cfg = synth.resolve_clip_config(cfg, force_quick_gelu=quick)
+    eng = FernEngine("cuda:0")
+    eng.load_tensors(synth.clip_state_dict(cfg, seed=seed))
+    eng.finalize_clip(cfg)
+    return eng, cfg
+
+
+# ==== a. GEMM level =================================================================================================================
+@pytest.mark.parametrize("M,N,K", [(2304, 3072, 768), (12608, 3072, 768), (1000, 520, 256), (129, 513, 128), (257, 129, 32), (64, 3072, 768),
+                                    (1, 32, 32), (37, 200, 96)])
+def test_gemm_quickgelu_matches_float64(engine, M, N, K):
+    """fp32 family: deep, ragged-edge and skinny (M <= 128: the 16x16 kernel) shapes, with and without a bias."""
+    a, w, b = _rand(M, K, seed=1), _rand(N, K, seed=2, scale=K ** -0.5), _rand(N, seed=3)
+    ref = a.double() @ w.double().T
+    _close(engine.gemm(a, w, b, epilogue=EPI_BIAS_QUICKGELU), _quick64(ref + b.double()))
+    if M <= 1000:
+        _close(engine.gemm(a, w, None, epilogue=EPI_BIAS_QUICKGELU), _quick64(ref))
+
+
+def test_gemm_quickgelu_saturates_cleanly(engine):
+    """x << 0: exp2 overflows, rcp(inf) = 0 and the output is (minus) zero; x >> 0: the output is x.  No NaN / inf anywhere."""
+    a = torch.zeros(64, 32)
+    w = torch.zeros(96, 32)
+    b = torch.cat([torch.full((32,), -200.0), torch.full((32,), 150.0), torch.linspace(-60, 60, 32)])
+    got = engine.gemm(a, w, b, epilogue=EPI_BIAS_QUICKGELU).cpu()
+    assert torch.isfinite(got).all()
+    assert (got[:, :32] == 0).all() and torch.equal(got[:, 32:64], b[32:64].expand(64, 32))
+    _close(got[:, 64:], _quick64(b[64:].expand(64, 32)))
+
+
+@pytest.mark.parametrize("m,n,k", [(1000, 520, 256), (4096, 768, 768), (300, 96, 64)])
+def test_gemm_quickgelu_f32x3(m, n, k):
+    """f32x3 family (M >= 256): fp32-accurate (test_gemm_f32x3_is_fp32_accurate_and_configuration_independent's rule), all eight tile
+    configurations and the mixed plans bit-identical, batch-invariant."""
+    eng = FernEngine("cuda:0")
+    a, w, b = _rand(m, k, seed=31), _rand(n, k, seed=32, scale=k ** -0.5), _rand(n, seed=33)
+    epi = EPI_BIAS_QUICKGELU
+    ref = _quick64(a.double() @ w.double().T + b.double())
+    run = lambda: eng.gemm(a, w, b, epilogue=epi).cpu()  # noqa: E731
+    exact = run()
+    eng.set_precision("f32x3")
+    kepi = 11      # the tuner's lines carry the kernels' own epilogue number (csrc/kernels.h: EPI_BIAS_QUICKGELU)
+    outs = []
+    for cfg in range(8):
+        eng.tuner_import(f"f32x3 {m} {n} {k} {kepi} {cfg}\n")
+        assert f"f32x3 {m} {n} {k} {kepi} {cfg} " in eng.tuner_export(), "the line did not round-trip"
+        outs.append(run())
+    if m >= 2048:
+        for cfg, ra, rb in ((20, 2048, m), (20, 3840, 3840), (21, 1920, 3072), (21, 4096, 4096)):
+            eng.tuner_import(f"f32x3 {m} {n} {k} {kepi} {cfg} {ra} {rb}\n")
+            assert f"f32x3 {m} {n} {k} {kepi} {cfg} {ra} {rb}" in eng.tuner_export(), "the plan was refused"
+            outs.append(run())
+    for o in outs[1:]:
+        assert torch.equal(o, outs[0]), "f32x3 tile configurations must be bit-identical"
+    _close(outs[0], ref)
+    rms = ref.pow(2).mean().sqrt().item()
+    err_x3, err_f32 = (outs[0].double() - ref).abs().max().item(), (exact.double() - ref).abs().max().item()
+    print(f"f32x3 {err_x3:.3e} fp32 {err_f32:.3e} rms {rms:.3e}")
+    assert err_x3 <= max(2.0 * err_f32, 2e-6 * rms) and err_x3 < 1e-5 * rms
+    assert torch.equal(eng.gemm(a[17:17 + 256], w, b, epilogue=epi).cpu(), outs[0][17:17 + 256]), "batch invariance"
+    assert torch.equal(eng.gemm(a[:100], w, b, epilogue=epi).cpu(), exact[:100]), "fewer than 256 rows: the exact fp32 kernels"
+    eng.close()
+
+
+def test_gemm_quickgelu_every_fp32_tile_configuration_is_bit_identical(engine):
+    """The family invariant: every forced tile configuration, mixed plan and bulk + remainder plan gives the same bits, and a row's bits do not
+    depend on the batch it travels in (M = 64 rides the 16x16 kernel)."""
+    m, n, k = 3000, 768, 768
+    a, w, b = _rand(m, k, seed=21), _rand(n, k, seed=22, scale=k ** -0.5), _rand(n, seed=23)
+    epi, kepi = EPI_BIAS_QUICKGELU, 11
+    run = lambda x=a: engine.gemm(x, w, b, epilogue=epi).cpu()  # noqa: E731
+    base = run()
+    _close(base, _quick64(a.double() @ w.double().T + b.double()))
+    try:
+        for cfg in (0, 1, 2, 3, 8, 9, 10, 11, 12, 13, 14, 15):
+            engine.tuner_force_config("f32", cfg)
+            assert torch.equal(run(), base), cfg
+        engine.tuner_force_config("f32", 6)              # the 16x16 small-M kernel
+        assert torch.equal(run(a[:64]), base[:64]) and torch.equal(run(a[100:228]), base[100:228])
+    finally:
+        engine.tuner_force_config("f32", -1)
+    hi = (m // 256) * 256
+    for cfg, ra, rb in [(20, hi, m), (20, 1024, 2560), (21, (m // 128) * 128, m), (21, 1152, 2048), (8, 1024, 11), (12, 2048, 8), (11, 2048, 6), (9, 1984, 6)]:
+        engine.tuner_import(f"f32 {m} {n} {k} {kepi} 0 {cfg} {ra} {rb}\n")
+        assert f"f32 {m} {n} {k} {kepi} 0 {cfg} {ra} {rb}" in engine.tuner_export(), "the plan was refused"
+        assert torch.equal(run(), base), (cfg, ra, rb)
+    engine.tuner_import(f"f32 {m} {n} {k} {kepi} 0 8 0 8\n")
+    for lo, hi_ in ((0, 1), (0, 64), (100, 1124), (2990, 3000)):
+        assert torch.equal(run(a[lo:hi_]), base[lo:hi_]), (lo, hi_)
+
+
+def test_tuner_lines_round_trip_the_new_epilogue(engine):
+    """`f32` / `f32x3` / `pair` lines of fern_tuner_export / fern_tuner_import carry the epilogue in their key: the new value gets plans of
+    its own, next to -- not instead of -- the GELU key's."""
+    lines = ["f32 5000 640 256 11 0 9 0 9", "f32 5000 640 256 1 0 10 0 10", "f32x3 5000 640 256 11 3 0 3", "f32x3 5000 640 256 1 2 0 2",
+             "pair 5000 640 256 11 0 1232 640 128 11 0 1", "pair 5000 640 256 1 0 1232 640 128 1 0 0",
+             "pairb 5000 640 256 11 13 1232 640 128 11 1 2", "pairb 5000 640 256 1 13 1232 640 128 1 1 0",
+             "bf16 5000 640 256 11 1 3", "mx8 5000 640 256 11 13 4"]
+    engine.tuner_import("\n".join(lines) + "\n")
+    out = engine.tuner_export().splitlines()
+    for ln in lines:
+        assert any(o.startswith(ln) for o in out), ln
+
+
+@pytest.mark.parametrize("m,n,k", [(64, 128, 64), (197, 384, 96), (1000, 520, 256), (4096, 768, 768)])
+@pytest.mark.parametrize("out_bf16", [False, True])
+def test_gemm_bf16_quickgelu(engine, m, n, k, out_bf16):
+    """test_gemm_bf16's GELU case with QuickGELU: fp64 math on the SAME rounded operands, the same tolerances."""
+    g = torch.Generator().manual_seed(m * 7 + n + k + 4)
+    a, w, b = torch.randn(m, k, generator=g), torch.randn(n, k, generator=g) * k ** -0.5, torch.randn(n, generator=g)
+    ab, wb = a.bfloat16(), w.bfloat16()
+    ref = _quick64(ab.double() @ wb.double().T + b.double())
+    got = engine.gemm_bf16(ab.cuda(), wb.cuda(), b, epilogue=EPI_BIAS_QUICKGELU, out_bf16=out_bf16)
+    assert got.dtype == (torch.bfloat16 if out_bf16 else torch.float32)
+    print(f"max abs err {_maxerr(got.float(), ref):.3e}")
+    if out_bf16:
+        assert torch.allclose(got.float().cpu().double(), ref, rtol=2 ** -7, atol=1e-3)
+    else:
+        assert torch.allclose(got.cpu().double(), ref, rtol=1e-5, atol=2e-5)
+
+
+@pytest.mark.parametrize("m,n,k", [(64, 128, 64), (197, 384, 192), (1000, 520, 256), (4096, 768, 768)])
+@pytest.mark.parametrize("out_bf16", [True, False])
+def test_gemm_fp8_quickgelu(engine, m, n, k, out_bf16):
+    """test_gemm_fp8's cases: bf16 output at rtol 2^-7 / atol 1e-3 (its GELU case), fp32 output at the family's 1e-4 relative."""
+    g = torch.Generator().manual_seed(m + n + k + 4)
+    a, w, b = torch.randn(m, k, generator=g), torch.randn(n, k, generator=g) * k ** -0.5, torch.randn(n, generator=g)
+    a8, sa = engine.quantize_rows_fp8(a)
+    w8, sw = engine.quantize_rows_fp8(w)
+    qa, qw = a8.cpu().view(torch.float8_e4m3fn).double(), w8.cpu().view(torch.float8_e4m3fn).double()
+    ref = _quick64((qa @ qw.T) * (sa.cpu().double().unsqueeze(1) * sw.cpu().double().unsqueeze(0)) + b.double())
+    got = engine.gemm_fp8(a8, sa, w8, sw, b, epilogue=EPI_BIAS_QUICKGELU, out_bf16=out_bf16)
+    print(f"max abs err {_maxerr(got.float(), ref):.3e}")
+    if out_bf16:
+        assert got.dtype == torch.bfloat16 and torch.allclose(got.float().cpu().double(), ref, rtol=2 ** -7, atol=1e-3)
+    else:
+        assert (got.cpu().double() - ref).abs().max().item() < 1e-4 * max(1.0, ref.abs().max().item())
+
+
+def _mx_scales_by_block(sc):
+    return sc.permute(1, 0, 2).reshape(sc.shape[1], -1)
+
+
+@pytest.mark.parametrize("m,n,k", [(64, 128, 128), (197, 384, 256), (1000, 520, 640), (4096, 768, 768), (333, 2304, 768)])
+@pytest.mark.parametrize("out_bf16", [True, False])
+def test_gemm_mx8_quickgelu(engine, m, n, k, out_bf16):
+    """test_gemm_mx8's cases: fp64 math on the SAME quantised operands and scales."""
+    from oracle.clip import mx8_dequantize
+    g = torch.Generator().manual_seed(m + n + k + 4)
+    a = torch.randn(m, k, generator=g) * torch.logspace(-1, 1, k // 32).repeat_interleave(32)
+    w, b = torch.randn(n, k, generator=g) * k ** -0.5, torch.randn(n, generator=g)
+    a8, sa = engine.quantize_mx8(a)
+    w8, sw = engine.quantize_mx8(w)
+    qa = mx8_dequantize(a8.cpu().view(torch.float8_e4m3fn), _mx_scales_by_block(sa.cpu()), torch.float64)
+    qw = mx8_dequantize(w8.cpu().view(torch.float8_e4m3fn), _mx_scales_by_block(sw.cpu()), torch.float64)
+    ref = _quick64(qa @ qw.T + b.double())
+    got = engine.gemm_mx8(a8, sa, w8, sw, b, epilogue=EPI_BIAS_QUICKGELU, out_bf16=out_bf16)
+    print(f"max abs err {_maxerr(got.float(), ref):.3e}")
+    if out_bf16:
+        assert got.dtype == torch.bfloat16 and torch.allclose(got.float().cpu().double(), ref, rtol=2 ** -7, atol=1e-3)
+    else:
+        assert (got.cpu().double() - ref).abs().max().item() < 1e-4 * max(1.0, ref.abs().max().item())
+
+
+def test_quickgelu_is_one_arithmetic_for_every_family(engine):
+    """One function serves all families: integer operands make every accumulator exact in every family, so the fp32, bf16 and block-scaled
+    kernels hand the epilogue the same fp32 input -- and must return the same bits (the three GELU forms differ here)."""
+    g = torch.Generator().manual_seed(3)
+    m, n, k = 300, 256, 128
+    a = torch.randint(-3, 4, (m, k), generator=g).float()
+    w = torch.randint(-2, 3, (n, k), generator=g).float() * 0.125
+    b = torch.randint(-8, 9, (n,), generator=g).float() * 0.25
+    f32 = engine.gemm(a, w, b, epilogue=EPI_BIAS_QUICKGELU).cpu()
+    bf = engine.gemm_bf16(a.bfloat16().cuda(), w.bfloat16().cuda(), b, epilogue=EPI_BIAS_QUICKGELU).cpu()
+    a8, sa = engine.quantize_mx8(a)
+    w8, sw = engine.quantize_mx8(w)
+    mx = engine.gemm_mx8(a8, sa, w8, sw, b, epilogue=EPI_BIAS_QUICKGELU).cpu()
+    assert torch.equal(engine.gemm(a, w, b).cpu(), a @ w.T + b)      # the premise: exact accumulators
+    assert torch.equal(f32, bf) and torch.equal(f32, mx)
+    assert not torch.equal(engine.gemm(a, w, b, epilogue=EPI_BIAS_GELU).cpu(), f32)
+
+
+@pytest.mark.parametrize("m,n,k", [(64, 128, 128), (197, 384, 256), (1000, 512, 640), (4097, 3072, 768), (12608, 768, 768)])
+def test_gemm_mx8_quant_quickgelu_is_the_quantiser_applied_to_the_fp32_output(engine, m, n, k):
+    """fern_gemm_mx8_quant(QUICKGELU) == fern_quantize_mx8(fern_gemm_mx8(QUICKGELU, fp32 out)): bytes and scales, bit for bit, on the tuned
+    configuration, on configuration 0 and on the ping-pong tile (configuration 11)."""
+    g = torch.Generator().manual_seed(m + n + k + 4)
+    a, w, b = torch.randn(m, k, generator=g), torch.randn(n, k, generator=g) * k ** -0.5, torch.randn(n, generator=g)
+    a8, sa = engine.quantize_mx8(a)
+    w8, sw = engine.quantize_mx8(w)
+    epi = EPI_BIAS_QUICKGELU
+    q_ref, s_ref = engine.quantize_mx8(engine.gemm_mx8(a8, sa, w8, sw, b, epilogue=epi))
+    q, sc = engine.gemm_mx8_quant(a8, sa, w8, sw, b, epilogue=epi)
+    assert torch.equal(sc, s_ref) and torch.equal(q, q_ref)
+    qg, _ = engine.gemm_mx8_quant(a8, sa, w8, sw, b, epilogue=EPI_BIAS_GELU)
+    assert not torch.equal(qg, q)
+    try:
+        for cfg in (0, 11):
+            engine.tuner_force_config("mx8", cfg)
+            q2, sc2 = engine.gemm_mx8_quant(a8, sa, w8, sw, b, epilogue=epi)
+            f2 = engine.gemm_mx8(a8, sa, w8, sw, b, epilogue=epi, out_bf16=True)
+            torch.cuda.synchronize()
+            assert torch.equal(sc2, s_ref) and torch.equal(q2, q_ref), cfg
+            assert torch.equal(f2.view(torch.int16), engine.gemm_mx8(a8, sa, w8, sw, b, epilogue=epi).bfloat16().view(torch.int16)), cfg
+    finally:
+        engine.tuner_force_config("mx8", -1)
+
+
+@pytest.mark.parametrize("family,cfgs", [("bf16", range(10)), ("mx8", range(12)), ("fp8", range(6))])
+def test_reduced_families_quickgelu_tile_configurations_are_bit_identical(engine, family, cfgs):
+    m, n, k = 2049, 640, 768
+    g = torch.Generator().manual_seed(17)
+    a, w, b = torch.randn(m, k, generator=g), torch.randn(n, k, generator=g) * k ** -0.5, torch.randn(n, generator=g)
+    if family == "bf16":
+        ab, wb = engine.to_bf16(a), engine.to_bf16(w)
+        run = lambda: [engine.gemm_bf16(ab, wb, b, epilogue=EPI_BIAS_QUICKGELU, out_bf16=ob) for ob in (True, False)]  # noqa: E731
+    elif family == "fp8":
+        (a8, sa), (w8, sw) = engine.quantize_rows_fp8(a), engine.quantize_rows_fp8(w)
+        run = lambda: [engine.gemm_fp8(a8, sa, w8, sw, b, epilogue=EPI_BIAS_QUICKGELU, out_bf16=ob) for ob in (True, False)]  # noqa: E731
+    else:
+        (a8, sa), (w8, sw) = engine.quantize_mx8(a), engine.quantize_mx8(w)
+        run = lambda: ([engine.gemm_mx8(a8, sa, w8, sw, b, epilogue=EPI_BIAS_QUICKGELU, out_bf16=ob) for ob in (True, False)] +  # noqa: E731
+                       list(engine.gemm_mx8_quant(a8, sa, w8, sw, b, epilogue=EPI_BIAS_QUICKGELU)))
+    as_bytes = lambda outs: [o.cpu().contiguous().view(torch.uint8) for o in outs]  # noqa: E731
+    base = as_bytes(run())
+    try:
+        for cfg in cfgs:
+            engine.tuner_force_config(family, cfg)
+            got = as_bytes(run())
+            for i, (x, y) in enumerate(zip(base, got)):
+                assert torch.equal(x, y), (family, cfg, i)
+    finally:
+        engine.tuner_force_config(family, -1)
+
+
+def test_bad_activation_and_epilogue_values_are_refused(engine):
+    eng = FernEngine("cuda:0")
+    for bad in (-1, 2, 11):
+        with pytest.raises(FernError, match="unknown activation"):
+            eng.set_clip_activation(bad)
+    a, w = _rand(8, 32), _rand(8, 32)
+    for bad in (5, 11, -1):
+        with pytest.raises(FernError, match="unknown epilogue"):
+            eng.gemm(a, w, None, epilogue=bad)
+    eng.close()
+
+
+# ==== b. fp32 / f32x3 towers against the golden: FAILS without the feature ==========================================================
+@pytest.mark.parametrize("precision", ["fp32", "f32x3"])
+@pytest.mark.parametrize("name,n_img,n_txt,tol", [("tiny", 5, 6, 2e-4), ("tiny-hd64", 5, 6, 2e-4), ("ViT-B-16", 2, 2, 1e-3)])
+def test_quickgelu_towers_match_the_in_tree_statement(name, n_img, n_txt, tol, precision):
+    gold = qo.load_goldens()
+    eng, cfg = _quick_engine(name, seed=5)
+    assert cfg.quick_gelu and eng.clip_cfg is cfg
+    eng.set_precision(precision)
+    imgs = _t(synth.images(n_img, cfg, 42))
+    got = eng.encode_image(imgs)
+    ref = _t(gold[f"{name}_image"])
+    print(f"{name} {precision}: image max |d| {_maxerr(got, ref):.3e} scale {ref.abs().max().item():.2f}")
+    assert _maxerr(got, ref) < tol * max(1.0, ref.abs().max().item())
+    if precision == "fp32":      # (f32x3 serves M >= 256 only: one image's 197 rows run the exact fp32 kernels, by design)
+        assert torch.equal(eng.encode_image(imgs[1:2]), got[1:2])
+    for tag, full in (("full", True), ("ragged", False)):
+        toks = _t(synth.captions(n_txt, cfg, 42, full_length=full))
+        g, s = eng.encode_text(toks)
+        rs, rg = _t(gold[f"{name}_text_{tag}_seq"]), _t(gold[f"{name}_text_{tag}_global"])
+        scale = max(1.0, rs.abs().max().item())
+        print(f"{name} {precision}: text {tag} max |d| seq {_maxerr(s, rs):.3e} global {_maxerr(g, rg):.3e} scale {scale:.2f}")
+        assert _maxerr(s, rs) < tol * scale and _maxerr(g, rg) < tol * scale
+    eng.close()
+
+
+@pytest.mark.parametrize("name", ["ViT-B-16-quickgelu", "tiny"])
+def test_create_model_surface(name):
+    """The public surface: a *-quickgelu name, force_quick_gelu= on FernCLIP / create_model; against the golden at the tower bounds."""
+    from fashionern_aaai2024_amd.clip_model import FernCLIP, create_model
+    gold = qo.load_goldens()
+    base = name.replace("-quickgelu", "")
+    tol = 1e-3 if base == "ViT-B-16" else 2e-4
+    m = create_model(name, device="cuda:0", force_quick_gelu=(name == "tiny"))
+    assert m.cfg.quick_gelu
+    m.load_state_dict(synth.clip_state_dict(synth.CLIP_CONFIGS[base], seed=5))
+    n_img = gold[f"{base}_image"].shape[0]
+    ref = _t(gold[f"{base}_image"])
+    got = m.encode_image(_t(synth.images(n_img, m.cfg, 42)))
+    assert _maxerr(got, ref) < tol * max(1.0, ref.abs().max().item())
+    plain = FernCLIP(base, "cuda:0").init_random(5)
+    assert not plain.cfg.quick_gelu and not torch.equal(plain.encode_image(_t(synth.images(n_img, m.cfg, 42))), got)
+    m.engine.close()
+    plain.engine.close()
+
+
+# ==== c. reduced modes against the patched oracle's restatement =====================================================================
+@pytest.mark.parametrize("name,n", [("tiny", 5), ("tiny-hd64", 4), ("ViT-B-16", 3)])
+def test_quickgelu_towers_bf16_precision(name, n):
+    """test_clip_towers_bf16_precision's constants."""
+    eng, cfg = _quick_engine(name, seed=11)
+    sd = ofusion.as_torch(synth.clip_state_dict(cfg, seed=11))
+    imgs, toks = _t(synth.images(n, cfg)), _t(synth.captions(n, cfg))
+    fp32_img = eng.encode_image(imgs)
+    eng.set_precision("bf16")
+    got = eng.encode_image(imgs)
+    g, s = eng.encode_text(toks)
+    assert torch.equal(eng.encode_image(imgs[1:2]), got[1:2])
+    child = eng.fork()
+    assert torch.equal(child.encode_image(imgs), got)      # forks follow their parent's activation
+    child.close()
+    eng.set_precision("fp32")
+    assert torch.equal(eng.encode_image(imgs), fp32_img)
+    eng.close()
+    with torch.no_grad(), qo.quick_gelu() as oc:
+        ref_b, ref_f = oc.encode_image(sd, cfg, imgs, precision="bf16"), oc.encode_image(sd, cfg, imgs)
+        rg_b, rs_b = oc.encode_text(sd, cfg, toks, precision="bf16")
+        rg_f, _ = oc.encode_text(sd, cfg, toks)
+    print(f"bf16 {name}: image cos {_cos_err(got, ref_b):.2e} max {_maxerr(got, ref_b):.2e}; text cos {_cos_err(g, rg_b):.2e} seq max {_maxerr(s, rs_b):.2e}; "
+          f"vs fp32 {_cos_err(got, ref_f):.2e} / {_cos_err(g, rg_f):.2e}")
+    assert _cos_err(got, ref_b) < 2e-5 and _cos_err(g, rg_b) < 2e-5
+    assert _maxerr(got, ref_b) < 5e-3 * max(1.0, ref_b.abs().max().item())
+    assert _maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
+    assert _cos_err(got, ref_f) < 1e-3 and _cos_err(g, rg_f) < 1e-3
+    assert _cos_err(got, ref_f) > 0 and not torch.equal(got, fp32_img)
+
+
+@pytest.mark.parametrize("mode,name,n", [("fp8", "tiny-hd64", 4), ("fp8", "ViT-B-16", 3), ("mx8", "tiny-w256", 4), ("mx8", "tiny-hd48", 4), ("mx8", "ViT-B-16", 3)])
+def test_quickgelu_towers_fp8_and_mx8_precision(mode, name, n):
+    """test_clip_towers_fp8_precision's / test_clip_towers_mx8_precision's constants."""
+    eng, cfg = _quick_engine(name, seed=11)
+    sd = ofusion.as_torch(synth.clip_state_dict(cfg, seed=11))
+    imgs, toks = _t(synth.images(n, cfg)), _t(synth.captions(n, cfg))
+    fp32_img = eng.encode_image(imgs)
+    eng.set_precision(mode)
+    got = eng.encode_image(imgs)
+    g, s = eng.encode_text(toks)
+    assert torch.equal(eng.encode_image(imgs[1:2]), got[1:2])
+    assert torch.equal(eng.encode_text(toks[2:3])[0], g[2:3])
+    eng.set_precision("fp32")
+    assert torch.equal(eng.encode_image(imgs), fp32_img)
+    eng.close()
+    with torch.no_grad(), qo.quick_gelu() as oc:
+        ref_q, ref_f = oc.encode_image(sd, cfg, imgs, precision=mode), oc.encode_image(sd, cfg, imgs)
+        rg_q, _ = oc.encode_text(sd, cfg, toks, precision=mode)
+        rg_f, _ = oc.encode_text(sd, cfg, toks)
+    print(f"{mode} {name}: vs restatement {_cos_err(got, ref_q):.2e} / {_cos_err(g, rg_q):.2e}, vs fp32 {_cos_err(got, ref_f):.2e} / {_cos_err(g, rg_f):.2e}")
+    assert _cos_err(got, ref_q) < 2e-3 and _cos_err(g, rg_q) < 2e-3
+    assert _cos_err(got, ref_q) < _cos_err(got, ref_f) and _cos_err(g, rg_q) < _cos_err(g, rg_f)
+    assert _cos_err(got, ref_f) < 1e-2 and _cos_err(g, rg_f) < 1e-2
+    assert _cos_err(got, ref_f) > 1e-5
+
+
+@pytest.mark.parametrize("name,n", [("tiny-w256", 4), ("tiny-hd48", 4), ("ViT-B-16", 3)])
+def test_quickgelu_towers_mx8img_and_mx8mlp_precision(name, n):
+    """test_clip_towers_mx8img_and_mx8mlp_precision's constants (MIXED_BOUNDS; the text tower is the bf16 block)."""
+    eng, cfg = _quick_engine(name, seed=11)
+    sd = ofusion.as_torch(synth.clip_state_dict(cfg, seed=11))
+    imgs, toks = _t(synth.images(n, cfg)), _t(synth.captions(n, cfg))
+    fp32_img = eng.encode_image(imgs)
+    got, txt = {}, {}
+    for mode in ("mx8img", "mx8mlp"):
+        eng.set_precision(mode)
+        got[mode] = eng.encode_image(imgs)
+        txt[mode] = eng.encode_text(toks)
+        assert torch.equal(eng.encode_image(imgs[1:2]), got[mode][1:2])
+        assert torch.equal(eng.encode_text(toks[2:3])[0], txt[mode][0][2:3])
+    eng.set_precision("fp32")
+    assert torch.equal(eng.encode_image(imgs), fp32_img)
+    eng.close()
+    with torch.no_grad(), qo.quick_gelu() as oc:
+        ref = {m: oc.encode_image(sd, cfg, imgs, precision=m) for m in ("mx8img", "mx8mlp", "bf16", "fp32")}
+        rg_b, rs_b = oc.encode_text(sd, cfg, toks, precision="bf16")
+    for mode in ("mx8img", "mx8mlp"):
+        g, s = txt[mode]
+        e_own, e_f, e_b = _cos_err(got[mode], ref[mode]), _cos_err(got[mode], ref["fp32"]), _cos_err(got[mode], ref["bf16"])
+        print(f"{mode} {name}: vs own restatement {e_own:.2e}, vs bf16 {e_b:.2e}, vs fp32 {e_f:.2e}; text vs bf16 {_cos_err(g, rg_b):.2e} / {_cos_err(s, rs_b):.2e}")
+        assert e_own < MIXED_BOUNDS[mode]
+        assert e_own < e_f and e_own < e_b
+        assert _cos_err(g, rg_b) < 2e-5 and _cos_err(s, rs_b) < 2e-5
+        assert _maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
+    assert not torch.equal(got["mx8img"], fp32_img) and not torch.equal(got["mx8mlp"], fp32_img)
+
+
+# ==== d. remaining cases ============================================================================================================
+@pytest.mark.parametrize("cfg_name,b,precision", [("ViT-B-16", 64, "fp32"), ("ViT-B-16", 5, "fp32"), ("tiny", 7, "fp32"), ("ViT-B-16", 64, "mx8img"),
+                                                  ("ViT-B-16", 65, "mx8img"), ("ViT-B-16", 64, "f32x3")])
+def test_encode_pair_quickgelu_is_bit_identical_to_the_two_encoder_calls(cfg_name, b, precision):
+    eng, cfg = _quick_engine(cfg_name, seed=4)
+    eng.set_precision(precision)
+    imgs = _t(synth.images(b, cfg, 11)).cuda()
+    toks = _t(synth.captions(b, cfg, 11)).cuda()
+    ref_i = eng.encode_image(imgs)
+    ref_g, ref_s = eng.encode_text(toks)
+    for rep in range(3):      # 1st call: shapes new to the pair launcher (two launches); later calls: tuned plans, one launch where it wins
+        pi, pg, ps = eng.encode_pair(imgs, toks)
+        assert torch.equal(pi, ref_i) and torch.equal(pg, ref_g) and torch.equal(ps, ref_s), (cfg_name, b, precision, rep)
+    if precision in ("fp32", "f32x3") and cfg_name == "ViT-B-16" and b == 64:
+        pairs = [ln for ln in eng.tuner_export().splitlines() if ln.startswith("pair ")]
+        quick = [ln for ln in pairs if ln.split()[4] == "11"]
+        assert quick, pairs      # the c_fc pair of the two towers carries the new epilogue in its key
+        flipped = "\n".join(ln[:-1] + ("0" if ln.endswith("1") else "1") for ln in pairs) + "\n"
+        eng.tuner_import(flipped)
+        assert all(ln in eng.tuner_export() for ln in flipped.splitlines())
+        pi, pg, ps = eng.encode_pair(imgs, toks)
+        assert torch.equal(pi, ref_i) and torch.equal(pg, ref_g) and torch.equal(ps, ref_s)
+    gelu, _ = _quick_engine(cfg_name, seed=4, quick=False)
+    gelu.set_precision(precision)
+    assert not torch.equal(gelu.encode_image(imgs), ref_i) and not torch.equal(gelu.encode_text(toks)[0], ref_g)
+    gelu.close()
+    eng.close()
+
+
+def test_vit_l14_quickgelu_fp32():
+    """The long tower (257 tokens, streaming attention, 14-pixel patches) on 2 images / captions at test_clip_full_size_long's 1e-3."""
+    cfg = synth.resolve_clip_config("ViT-L-14-quickgelu")
+    assert cfg.quick_gelu
+    sd_np = synth.clip_state_dict(cfg, seed=5)
+    sd = ofusion.as_torch(sd_np)
+    eng = FernEngine("cuda:0")
+    eng.load_tensors(sd_np)
+    eng.finalize_clip(cfg)
+    imgs, toks = _t(synth.images(2, cfg, 42)), _t(synth.captions(2, cfg, 42))
+    got = eng.encode_image(imgs)
+    g, s = eng.encode_text(toks)
+    eng.close()
+    with torch.no_grad(), qo.quick_gelu() as oc:
+        ref = oc.encode_image(sd, cfg, imgs)
+        rg, rs = oc.encode_text(sd, cfg, toks)
+    cos = F.cosine_similarity(got.cpu(), ref, dim=-1)
+    print(f"ViT-L-14-quickgelu: image max |d| {_maxerr(got, ref):.3e} scale {ref.abs().max().item():.2f}; seq {_maxerr(s, rs):.3e}")
+    assert _maxerr(got, ref) < 1e-3 * max(1.0, ref.abs().max().item()) and (1 - cos).abs().max().item() < 1e-5
+    assert _maxerr(s, rs) < 1e-3 * max(1.0, rs.abs().max().item())
+    assert (1 - F.cosine_similarity(g.cpu(), rg, dim=-1)).abs().max().item() < 1e-5
+
+
+@pytest.mark.parametrize("name,n,tol", [("tiny-resnet", 5, 2e-4), ("RN50x4-text", 3, 1e-3)])
+def test_resnet_and_rn50x4_text_with_force_quick_gelu(name, n, tol):
+    """force_quick_gelu on the towers CLIP4Cir fine-tunes from: the text tower follows the patched oracle (test_modified_resnet_tower_tiny_and_rn50x4's
+    bounds); the ModifiedResNet image tower has no GELU, so its output is the GELU config's, bit for bit."""
+    quick, cfg = _quick_engine(name, seed=8)
+    gelu, gcfg = _quick_engine(name, seed=8, quick=False)
+    assert cfg.quick_gelu and not gcfg.quick_gelu
+    sd = ofusion.as_torch(synth.clip_state_dict(cfg, seed=8))
+    toks = _t(synth.captions(n, cfg))
+    g, s = quick.encode_text(toks)
+    with torch.no_grad(), qo.quick_gelu() as oc:
+        rg, rs = oc.encode_text(sd, cfg, toks)
+    scale = max(1.0, rs.abs().max().item())
+    print(f"{name}: text max |d| seq {_maxerr(s, rs):.3e} global {_maxerr(g, rg):.3e} scale {scale:.2f}")
+    assert _maxerr(s, rs) < tol * scale and _maxerr(g, rg) < tol * scale
+    assert not torch.equal(gelu.encode_text(toks)[1], s)
+    if cfg.v_arch == "resnet":
+        imgs = _t(synth.images(n, cfg))
+        assert torch.equal(quick.encode_image(imgs), gelu.encode_image(imgs))
+    quick.close()
+    gelu.close()
+
+
+def test_the_setting_is_isolated_to_the_clip_towers():
+    """dvr_fuse (the fusion BERT keeps exact-erf GELU) does not see the CLIP activation; an explicit FERN_ACT_GELU is the default; the setter
+    switches an engine back and forth; forks follow their parent and refuse a setting of their own."""
+    cfg = synth.CLIP_CONFIGS["tiny"]
+    d = cfg.embed_dim
+    engs = {}
+    for quick in (False, True):
+        eng, _ = _quick_engine("tiny", seed=3, quick=quick)
+        eng.load_tensors(synth.fusion_state_dict(d, seed=4))
+        eng.finalize_fusion(d)
+        engs[quick] = eng
+    b = 9
+    rg, rl = _t(synth.global_feats(b, d, tag="rg")), _t(synth.local_feats(b, d, tag="rl"))
+    tg, ts = _t(synth.global_feats(b, d, tag="tg")), _t(synth._normal(42, f"tseq/{d}", (b, 77, d)))
+    for prec in ("fp32", "bf16"):
+        for e in engs.values():
+            e.set_precision(prec)
+        assert torch.equal(engs[True].dvr_fuse(rg, rl, tg, ts), engs[False].dvr_fuse(rg, rl, tg, ts)), prec
+    for e in engs.values():
+        e.set_precision("fp32")
+    imgs, toks = _t(synth.images(4, cfg, 7)), _t(synth.captions(4, cfg, 7))
+    gelu_i, quick_i = engs[False].encode_image(imgs), engs[True].encode_image(imgs)
+    gelu_t, quick_t = engs[False].encode_text(toks)[1], engs[True].encode_text(toks)[1]
+    assert not torch.equal(gelu_i, quick_i) and not torch.equal(gelu_t, quick_t)
+    eng = engs[False]
+    eng.set_clip_activation(ACT_GELU)                       # explicit == default
+    assert torch.equal(eng.encode_image(imgs), gelu_i) and torch.equal(eng.encode_text(toks)[1], gelu_t)
+    child = eng.fork()
+    eng.set_clip_activation(ACT_QUICK_GELU)                 # the parent's setting reaches an existing fork
+    assert torch.equal(eng.encode_image(imgs), quick_i) and torch.equal(eng.encode_text(toks)[1], quick_t)
+    assert torch.equal(child.encode_image(imgs), quick_i) and torch.equal(child.encode_text(toks)[1], quick_t)
+    with pytest.raises(FernError, match="root context"):
+        child.set_clip_activation(ACT_GELU)
+    eng.set_clip_activation(ACT_GELU)
+    assert torch.equal(child.encode_image(imgs), gelu_i) and torch.equal(eng.encode_image(imgs), gelu_i)
+    child.close()
+    for e in engs.values():
+        e.close()
+
+
+def test_pipeline_lanes_follow_the_quickgelu_parent():
+    """A ComposedQueryPipeline with several lanes (forked contexts) over a QuickGELU model: the bits of serial calls, and not a GELU model's."""
+    from fashionern_aaai2024_amd.clip_model import create_model
+    from fashionern_aaai2024_amd.model import ERN
+    from fashionern_aaai2024_amd.pipeline import ComposedQueryPipeline
+    cfg = synth.resolve_clip_config("tiny", force_quick_gelu=True)
+    d = cfg.embed_dim
+    clip = create_model("tiny", device="cuda:0", seed=3, force_quick_gelu=True)
+    assert clip.cfg == cfg
+    model = ERN(clip, d, "cuda:0", engine=clip.engine).init_random(4)
+    eng = model.engine
+    gal = eng.index_fuse(_t(synth.global_feats(3000, d, tag="pg")), _t(synth.local_feats(3000, d, tag="pgl")), True)
+    batches = [(_t(synth.images(9, cfg, 100 + j)).cuda(), _t(synth.captions(9, cfg, 100 + j)).cuda(), _t(synth.local_feats(9, d, 100 + j)).cuda())
+               for j in range(6)]
+    serial, feats = [], []
+    for im, tk, lc in batches:
+        fi = eng.encode_image(im)
+        feats.append(fi)
+        serial.append(eng.sim_topk(eng.dvr_fuse(fi, lc, *eng.encode_text(tk)), gal, 20))
+    plain = create_model("tiny", device="cuda:0", seed=3)
+    assert not torch.equal(plain.encode_image(batches[0][0]), feats[0])
+    plain.engine.close()
+    pipe = ComposedQueryPipeline(eng, lanes=3)
+    for _ in range(2):
+        futures = [pipe.submit(im, tk, lc, gal, 20) for im, tk, lc in batches]
+        for (rs, ri), fut in zip(serial, futures):
+            s, i = fut.wait()
+            torch.cuda.current_stream().synchronize()
+            assert torch.equal(i, ri) and torch.equal(s, rs)
+    pipe.close()
+    clip.engine.close()

@@ -10,6 +10,8 @@ the HIP path.
   clip.npz     <- models/others/modeling_clip.py (the in-tree statement of CLIP arithmetic), executed
                   under the installed transformers package so its relative imports resolve
   clip_long.npz <- the same for tiny-p14 / tiny-long / ViT-L-14 (patch 14, more than 224 tokens)
+  clip_quickgelu.npz, clip_quickgelu_vitb16.npz <- clip.npz's recipe with hidden_act="quick_gelu" in both sub-configs
+                  (OpenAI's activation); two files because one would pass the 1 MiB limit of a committed file
   loss.npz     <- losses.loss.BatchBasedClassificationLoss and ERN mode="train" (forward values only)
   harness.json/.npz <- run/test/test_{fiq,cirr,200k,shoes,val}.py compute_*_val_metrics and
                   utils.utils.extract_index_features on in-memory synthetic datasets with a stub CLIP
@@ -151,8 +153,9 @@ def to_hf_names(sd, cfg):
     return {k: t(np.ascontiguousarray(val)) for k, val in out.items()}
 
 
-def _clip_outputs(towers):
-    """Image (and, n_txt > 0, text) outputs of the in-tree CLIP statement for (name, images, captions) towers with synth weights."""
+def _clip_outputs(towers, hidden_act="gelu"):
+    """Image (and, n_txt > 0, text) outputs of the in-tree CLIP statement for (name, images, captions) towers with synth weights;
+    `hidden_act` ("gelu" / "quick_gelu") goes to both sub-configs (modeling_clip.py:343, ACT2FN[config.hidden_act])."""
     mod = load_reference_clip_module()
     from transformers import CLIPConfig
     out = {}
@@ -161,12 +164,12 @@ def _clip_outputs(towers):
         hf = CLIPConfig(
             text_config=dict(vocab_size=cfg.vocab_size, hidden_size=cfg.t_width, intermediate_size=cfg.t_mlp,
                              num_hidden_layers=cfg.t_layers, num_attention_heads=cfg.t_heads,
-                             max_position_embeddings=cfg.context_length, hidden_act="gelu", layer_norm_eps=1e-5,
+                             max_position_embeddings=cfg.context_length, hidden_act=hidden_act, layer_norm_eps=1e-5,
                              attention_dropout=0.0, projection_dim=cfg.embed_dim, eos_token_id=cfg.vocab_size - 1,
                              bos_token_id=cfg.vocab_size - 2, pad_token_id=0),
             vision_config=dict(hidden_size=cfg.v_width, intermediate_size=cfg.v_mlp, num_hidden_layers=cfg.v_layers,
                                num_attention_heads=cfg.v_heads, image_size=cfg.image_size, patch_size=cfg.patch_size,
-                               hidden_act="gelu", layer_norm_eps=1e-5, attention_dropout=0.0, projection_dim=cfg.embed_dim),
+                               hidden_act=hidden_act, layer_norm_eps=1e-5, attention_dropout=0.0, projection_dim=cfg.embed_dim),
             projection_dim=cfg.embed_dim)
         model = mod.CLIPModel(hf).eval().float()
         sd = to_hf_names(synth.clip_state_dict(cfg, seed=CLIP_SEED), cfg)
@@ -189,6 +192,20 @@ def clip_goldens():
     out = _clip_outputs((("tiny", 5, 6), ("tiny-hd64", 5, 6), ("ViT-B-16", 2, 2)))
     np.savez_compressed(os.path.join(OUT, "clip.npz"), **out)
     print("clip.npz", {k: v.shape for k, v in out.items()})
+
+
+def clip_quickgelu_goldens():
+    """clip_goldens() with QuickGELU, x * sigmoid(1.702 x), in both towers' MLPs: the activation of OpenAI's checkpoints and HF's
+    default.  Same weights (synth.clip_state_dict does not depend on the activation), same inputs, same keys: outputs only."""
+    out = _clip_outputs((("tiny", 5, 6), ("tiny-hd64", 5, 6), ("ViT-B-16", 2, 2)), hidden_act="quick_gelu")
+    # fp32 outputs do not compress: the fifteen arrays together are 1.2 MiB, over the 1 MiB a committed file may have, so the ViT-B-16
+    # arrays (same keys as in clip.npz) go to a file of their own -- tests/quickgelu_oracle.py:load_goldens() reads the two as one
+    big = {k: v for k, v in out.items() if k.startswith("ViT-B-16_")}
+    small = {k: v for k, v in out.items() if k not in big}
+    np.savez_compressed(os.path.join(OUT, "clip_quickgelu.npz"), **small)
+    np.savez_compressed(os.path.join(OUT, "clip_quickgelu_vitb16.npz"), **big)
+    print("clip_quickgelu.npz", {k: v.shape for k, v in small.items()})
+    print("clip_quickgelu_vitb16.npz", {k: v.shape for k, v in big.items()})
 
 
 def clip_long_goldens():
@@ -314,6 +331,7 @@ if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     only = sys.argv[1:]
-    for name, fn in (("fusion", fusion_goldens), ("clip", clip_goldens), ("clip_long", clip_long_goldens), ("harness", harness_goldens), ("loss", loss_goldens)):
+    for name, fn in (("fusion", fusion_goldens), ("clip", clip_goldens), ("clip_long", clip_long_goldens), ("clip_quickgelu", clip_quickgelu_goldens),
+                     ("harness", harness_goldens), ("loss", loss_goldens)):
         if not only or name in only:
             fn()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Images/s (and captions/s) of a CLIP tower configuration on one GPU, with a per-shape GEMM breakdown.
-Usage: python tools/tower_bench.py RN50x4 [--batch 64]"""
+Usage: python tools/tower_bench.py RN50x4 [--batch 64] [--precision mx8img] [--force-quick-gelu]"""
 import argparse
 import os
 import sys
@@ -16,9 +16,11 @@ ap = argparse.ArgumentParser()
 ap.add_argument("name")
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--iters", type=int, default=5)
+ap.add_argument("--precision", default="fp32", choices=["fp32", "f32x3", "bf16", "fp8", "mx8", "mx8mlp", "mx8img"])
+ap.add_argument("--force-quick-gelu", action="store_true", help="QuickGELU in both towers' MLPs (OpenAI's checkpoints); *-quickgelu names have it on")
 a = ap.parse_args()
-cfg = synth.CLIP_CONFIGS[a.name]
-clip = create_model(cfg, device="cuda:0", seed=0)
+cfg = synth.resolve_clip_config(a.name, a.force_quick_gelu)
+clip = create_model(cfg, device="cuda:0", seed=0, precision=a.precision)
 eng = clip.engine
 imgs = torch.from_numpy(synth.images(a.batch, cfg)).cuda()
 toks = torch.from_numpy(synth.captions(a.batch, cfg)).cuda()
@@ -35,5 +37,5 @@ for fn, label, arg in ((eng.encode_image, "images", imgs), (eng.encode_text, "ca
     fn(arg)
     st = eng.prof_collect()
     eng.prof_enable(False)
-    print(f"{a.name} {label}: {a.batch / dt:9.1f} /s  ({dt * 1e3:.2f} ms per batch of {a.batch}); GEMM {st['gemm_flops'] / 1e9:.0f} GFLOP "
+    print(f"{a.name} {a.precision} {'quick_gelu' if cfg.quick_gelu else 'gelu'} {label}: {a.batch / dt:9.1f} /s  ({dt * 1e3:.2f} ms per batch of {a.batch}); GEMM {st['gemm_flops'] / 1e9:.0f} GFLOP "
           f"at {st['gemm_flops'] / max(st['gemm_ms'], 1e-9) / 1e9:.1f} TFLOP/s ({st['gemm_ms']:.2f} ms), attention {st['attn_ms']:.2f} ms")
