@@ -1211,200 +1211,219 @@ extern "C" int fern_dvr_fuse(fern_ctx* c, const float* ref_global, const float* 
 // ------------------------------------------------------------------------------------------------
 // CLIP towers
 // ------------------------------------------------------------------------------------------------
-// pre-LN residual block (modeling_clip.py:354-401): x += attn(ln_1(x)); x += mlp(ln_2(x))
-static int clip_block(fern_ctx* c, const ClipBlockW& Bk, float* X, float* XN, float* QKV, float* ATT, float* H, int batch, int S,
-                      int width, int heads, int causal, hipStream_t s) {
-    const long R = (long)batch * S;
-    const int hd = width / heads;
-    HIP_TRY(launch_layernorm(X, nullptr, Bk.ln1.g, Bk.ln1.b, XN, R, width, width, width, 1e-5f, s));
-    FERN_TRY(run_gemm(c, gemm_desc(XN, width, Bk.qkv, QKV, 3 * width, (int)R, EPI_BIAS), s));
-    AttnParams a{QKV, QKV + width, QKV + 2 * width, ATT, 3L * width, 3L * width, 3L * width, (long)width,
-                 batch, heads, hd, S, S, causal, 1.0f / std::sqrt((float)hd)};
-    FERN_TRY(run_attention(c, a, s));
-    GemmParams po = gemm_desc(ATT, width, Bk.out, X, width, (int)R, EPI_BIAS_RESIDUAL);
-    po.R = X;
-    FERN_TRY(run_gemm(c, po, s));
-    HIP_TRY(launch_layernorm(X, nullptr, Bk.ln2.g, Bk.ln2.b, XN, R, width, width, width, 1e-5f, s));
-    FERN_TRY(run_gemm(c, gemm_desc(XN, width, Bk.fc, H, Bk.fc.out, (int)R, clip_mlp_epi(c)), s));
-    GemmParams p2 = gemm_desc(H, Bk.fc.out, Bk.proj, X, width, (int)R, EPI_BIAS_RESIDUAL);
-    p2.R = X;
-    return run_gemm(c, p2, s);
+// A pre-LN residual block (modeling_clip.py:354-401) is two halves -- x += attn(ln_1(x)); x += mlp(ln_2(x)) -- and each half runs its two
+// token-level GEMMs in one operand form.  Accumulation, the LayerNorm statistics and the attention softmax are fp32 in every form.
+//   F32   fp32 operands (the parity mode; under f32x3 the GEMMs run split, run_gemm).
+//   BF16  perf mode: LayerNorm / attention / GELU outputs are rounded to bf16 as they are written, weights are the bf16 copies.
+//   FP8   (BASELINE config 5: "fp8 MFMA encoder path") e4m3fn operands with per-token activation scales and per-output-channel weight
+//         scales, folded back in the fp32 epilogue.  LayerNorm quantises as it writes; the attention and GELU outputs are written as bf16
+//         (a row's maximum is not known inside those kernels) and quantised by a row pass.  Attention itself runs on bf16 operands.
+//   MX    FP8 with block-scaled operands -- one E8M0 scale per (token, 32 channels) and per (output channel, 32 inputs), applied inside
+//         v_mfma_scale_f32_32x32x64_f8f6f4 (twice the MFMA rate of the plain fp8 form, and an outlier channel costs its own 32-block
+//         precision, not the whole token row).  The attention kernel (head dim a multiple of 32) and c_fc quantise their outputs where
+//         they are produced (fp32 values -> e4m3fn + block scales): no bf16 round trip, no extra pass.
+enum Form { F32, BF16, FP8, MX };
+
+// One tower's chunk: weights, shape, the form of each half and the workspace.  The reduced forms keep their operands inside the fp32-sized
+// buffers; the accessors below are the only place those offsets are written.
+struct Tower {
+    const ClipBlockW* blocks;
+    int batch, S, width, heads, mlp, causal;
+    Form attn, mlpf;
+    bool bf16_stream;      // the mode's residual stream is bf16: the walker allocates Xb where full blocks run
+    float *X, *XN, *QKV, *ATT, *H;
+    unsigned short* Xb;    // the bf16 residual stream (X is then not read by the blocks); null: the stream is the fp32 X
+
+    long R() const { return (long)batch * S; }
+    void* stream() const { return Xb ? (void*)Xb : (void*)X; }
+    // XN / QKV / ATT / H double as the bf16 operand buffers (half filled)
+    unsigned short* XNb() const { return reinterpret_cast<unsigned short*>(XN); }
+    unsigned short* QKVb() const { return reinterpret_cast<unsigned short*>(QKV); }
+    unsigned short* ATTb() const { return reinterpret_cast<unsigned short*>(ATT); }
+    unsigned short* Hb() const { return reinterpret_cast<unsigned short*>(H); }
+    // XN: fp8 rows, the scales of the operand in flight behind them (FP8: one float per row; MX: the same area holds E8M0 bytes)
+    unsigned char* XN8() const { return reinterpret_cast<unsigned char*>(XN); }
+    float* SA() const { return XN + ((size_t)R() * width / 4 + 63) / 64 * 64; }
+    unsigned char* SM() const { return reinterpret_cast<unsigned char*>(SA()); }
+    unsigned char* SH() const { return SM() + ((size_t)R() * (width / 32) + 255) / 256 * 256; }      // H's MX scales, behind the LayerNorm output's
+    // ATT / H: bf16 output in the first half, its fp8 copy behind it; c_fc in the MX form writes fp8 directly, at H
+    unsigned char* ATT8() const { return reinterpret_cast<unsigned char*>(ATT) + (size_t)R() * width * 2; }
+    unsigned char* H8(Form f) const { return reinterpret_cast<unsigned char*>(H) + (f == MX ? 0 : (size_t)R() * mlp * 2); }
+};
+
+// precision mode -> the forms of a tower's halves and its residual stream.
+//   mx8     (FERN_PREC_MX8) both halves MX over a BF16 residual stream (round 4): the two residual GEMMs of a block read and write it in
+//           place (C = bf16(acc + bias + Xb): one rounding per residual add) and the LayerNorms read it -- out-proj / c_proj were HBM-bound
+//           on their 2 x 39 MB of fp32 residual traffic per launch (M = 12608), the LayerNorm + quantise passes on their 39 MB reads.
+//   mx8mlp  (FERN_PREC_MX8_MLP) the attention half BF16, the MLP half -- two thirds of a block's GEMM flops -- MX, over the fp32 stream:
+//           half of the fp8 rounding points of mx8 (and its bf16 residual stream) are gone; bench.py's `reduced_modes` table has what
+//           that buys.
+//   mx8img  (FERN_PREC_MX8_IMG, round 6) the attention half MX too where the attention kernel can quantise its own output (head dim a
+//           multiple of 32), still over the FP32 stream: all four GEMMs at the fp8 rate without mx8's bf16 stream, whose 24 extra
+//           roundings per tower cost more Recall than the four GEMMs' operands do.
+//   The TEXT tower runs BF16 throughout under mx8mlp / mx8img (round 6): its GEMMs (M = 77 B rows, K = 512) are the ones the block-scaled
+//   kernels run worst (0.07-0.12 of their peak) and its rounding points sit directly on the query: e4m3 there cost 0.9 pp of Recall@50
+//   (bench.py `reduced_modes`: mx8mlp -1.03 -> -0.15 pp) for ~0.1 ms of a 4 ms step.
+static void tower_forms(const fern_ctx* c, bool text, Tower* T) {
+    T->attn = T->mlpf = F32;
+    T->bf16_stream = false;
+    switch (c->precision) {
+    case FERN_PREC_BF16: T->attn = T->mlpf = BF16; break;
+    case FERN_PREC_FP8: T->attn = T->mlpf = FP8; break;
+    case FERN_PREC_MX8: T->attn = T->mlpf = MX; T->bf16_stream = true; break;
+    case FERN_PREC_MX8_MLP:
+    case FERN_PREC_MX8_IMG:
+        T->attn = !text && c->precision == FERN_PREC_MX8_IMG && (T->width / T->heads) % 32 == 0 ? MX : BF16;
+        T->mlpf = text ? BF16 : MX;
+        break;
+    default: break;
+    }
 }
 
-// Perf-mode block: the four token-level GEMMs take bf16 operands (LayerNorm / attention / GELU outputs are rounded to bf16
-// as they are written, weights are the bf16 copies) and accumulate in fp32; the residual stream X, the LayerNorm
-// statistics and the attention softmax stay fp32.
-static int clip_block_bf16(fern_ctx* c, const ClipBlockW& Bk, float* X, unsigned short* XNb, unsigned short* QKVb, unsigned short* ATTb,
-                           unsigned short* Hb, int batch, int S, int width, int heads, int causal, hipStream_t s) {
-    const long R = (long)batch * S;
-    const int hd = width / heads;
-    HIP_TRY(launch_layernorm_bf16(X, Bk.ln1.g, Bk.ln1.b, XNb, R, width, width, width, 1e-5f, s));
-    FERN_TRY(run_gemm_b(c, gemm_desc_b(XNb, width, Bk.qkv, QKVb, 3 * width, (int)R, EPI_BIAS, true), s));
-    AttnParams a{nullptr, nullptr, nullptr, nullptr, 3L * width, 3L * width, 3L * width, (long)width,
-                 batch, heads, hd, S, S, causal, 1.0f / std::sqrt((float)hd), ATTb, QKVb, QKVb + width, QKVb + 2 * width};
-    FERN_TRY(run_attention(c, a, s));
-    GemmParams po = gemm_desc_b(ATTb, width, Bk.out, X, width, (int)R, EPI_BIAS_RESIDUAL, false);
-    po.R = X;
-    FERN_TRY(run_gemm_b(c, po, s));
-    HIP_TRY(launch_layernorm_bf16(X, Bk.ln2.g, Bk.ln2.b, XNb, R, width, width, width, 1e-5f, s));
-    FERN_TRY(run_gemm_b(c, gemm_desc_b(XNb, width, Bk.fc, Hb, Bk.fc.out, (int)R, clip_mlp_epi(c), true), s));
-    GemmParams p2 = gemm_desc_b(Hb, Bk.fc.out, Bk.proj, X, width, (int)R, EPI_BIAS_RESIDUAL, false);
-    p2.R = X;
-    return run_gemm_b(c, p2, s);
+// Shape, weights and forms of one tower for a chunk of `batch` samples, and its five buffers (fp32-sized in every mode).
+static int tower_open(fern_ctx* c, bool text, int batch, Tower* T) {
+    const ClipW& W = c->clip;
+    const fern_clip_config& cf = W.cfg;
+    const int g = cf.image_size / cf.patch_size;
+    if (text) *T = Tower{W.tblocks.data(), batch, cf.context_length, cf.t_width, cf.t_heads, cf.t_mlp, 1};
+    else *T = Tower{W.vblocks.data(), batch, g * g + 1, cf.v_width, cf.v_heads, cf.v_mlp, 0};
+    tower_forms(c, text, T);
+    const size_t R = (size_t)T->R();
+    FERN_TRY(ws_get(c, R * T->width, &T->X));
+    FERN_TRY(ws_get(c, R * T->width, &T->XN));
+    FERN_TRY(ws_get(c, R * 3 * T->width, &T->QKV));
+    FERN_TRY(ws_get(c, R * T->width, &T->ATT));
+    return ws_get(c, R * T->mlp, &T->H);
 }
 
-// fp8 block (BASELINE config 5: "fp8 MFMA encoder path"): the four token-level GEMMs take e4m3fn operands with per-token
-// activation scales and per-output-channel weight scales, folded back in the fp32 epilogue.  LayerNorm quantises as it
-// writes; the attention and GELU outputs are written as bf16 (a row's maximum is not known inside those kernels) and
-// quantised by a row pass.  Attention itself runs in the bf16 operand form; everything else as in the bf16 block.
-static int clip_block_fp8(fern_ctx* c, const ClipBlockW& Bk, float* X, unsigned char* XN8, float* SA, unsigned short* QKVb,
-                          unsigned short* ATTb, unsigned char* ATT8, unsigned short* Hb, unsigned char* H8, int batch, int S, int width,
-                          int heads, int causal, hipStream_t s) {
-    const long R = (long)batch * S;
-    const int hd = width / heads, mlp = Bk.fc.out;
-    HIP_TRY(launch_layernorm_fp8(X, Bk.ln1.g, Bk.ln1.b, XN8, SA, R, width, width, width, 1e-5f, s));
-    FERN_TRY(run_gemm_b(c, gemm_desc_f8(XN8, SA, width, Bk.qkv, QKVb, 3 * width, (int)R, EPI_BIAS, true), s));
-    AttnParams a{nullptr, nullptr, nullptr, nullptr, 3L * width, 3L * width, 3L * width, (long)width,
-                 batch, heads, hd, S, S, causal, 1.0f / std::sqrt((float)hd), ATTb, QKVb, QKVb + width, QKVb + 2 * width};
-    FERN_TRY(run_attention(c, a, s));
-    HIP_TRY(launch_quantize_rows_fp8(ATTb, nullptr, width, ATT8, width, SA, R, width, s));
-    GemmParams po = gemm_desc_f8(ATT8, SA, width, Bk.out, X, width, (int)R, EPI_BIAS_RESIDUAL, false);
-    po.R = X;
-    FERN_TRY(run_gemm_b(c, po, s));
-    HIP_TRY(launch_layernorm_fp8(X, Bk.ln2.g, Bk.ln2.b, XN8, SA, R, width, width, width, 1e-5f, s));
-    FERN_TRY(run_gemm_b(c, gemm_desc_f8(XN8, SA, width, Bk.fc, Hb, mlp, (int)R, clip_mlp_epi(c), true), s));
-    HIP_TRY(launch_quantize_rows_fp8(Hb, nullptr, mlp, H8, mlp, SA, R, mlp, s));
-    GemmParams p2 = gemm_desc_f8(H8, SA, mlp, Bk.proj, X, width, (int)R, EPI_BIAS_RESIDUAL, false);
-    p2.R = X;
-    return run_gemm_b(c, p2, s);
+static int run_gemm_form(fern_ctx* c, Form f, const GemmParams& p, hipStream_t s) { return f == F32 ? run_gemm(c, p, s) : run_gemm_b(c, p, s); }
+
+// LayerNorm of the residual stream into XN in operand form f, and the descriptor of the GEMM that reads it.
+static int ln_gemm(const Tower& T, Form f, const LNW& ln, const LinearW& L, void* C, long ldc, int epi, bool out_bf16, hipStream_t s, GemmParams* p) {
+    const long R = T.R();
+    const int w = T.width;
+    switch (f) {
+    case F32:
+        HIP_TRY(launch_layernorm(T.X, nullptr, ln.g, ln.b, T.XN, R, w, w, w, 1e-5f, s));
+        *p = gemm_desc(T.XN, w, L, reinterpret_cast<float*>(C), ldc, (int)R, epi);
+        break;
+    case BF16:
+        HIP_TRY(launch_layernorm_bf16(T.X, ln.g, ln.b, T.XNb(), R, w, w, w, 1e-5f, s));
+        *p = gemm_desc_b(T.XNb(), w, L, C, ldc, (int)R, epi, out_bf16);
+        break;
+    case FP8:
+        HIP_TRY(launch_layernorm_fp8(T.X, ln.g, ln.b, T.XN8(), T.SA(), R, w, w, w, 1e-5f, s));
+        *p = gemm_desc_f8(T.XN8(), T.SA(), w, L, C, ldc, (int)R, epi, out_bf16);
+        break;
+    case MX:
+        HIP_TRY(launch_layernorm_mx8(T.Xb ? nullptr : T.X, ln.g, ln.b, T.XN8(), T.SM(), R, R, w, w, w, 1e-5f, s, T.Xb));
+        *p = gemm_desc_mx(T.XN8(), T.SM(), R, w, L, C, ldc, (int)R, epi, out_bf16);
+        break;
+    }
+    return FERN_OK;
+}
+// out-proj / c_proj write the residual stream in place.  Only the MX form runs over the bf16 stream (tower_forms).
+static void residual_in_place(const Tower& T, GemmParams* p) {
+    if (T.Xb) p->Rb = T.Xb;
+    else p->R = T.X;
 }
 
-// MX block (FERN_PREC_MX8): clip_block_fp8 with block-scaled operands -- one E8M0 scale per (token, 32 channels) and per (output
-// channel, 32 inputs), applied inside v_mfma_scale_f32_32x32x64_f8f6f4 (twice the MFMA rate of the plain fp8 form, and an outlier
-// channel costs its own 32-block precision, not the whole token row).  SM: the activation scales of the operand in flight.
-// The residual stream of this mode is BF16 (Xb, round 4): the two residual GEMMs of a block read and write it in place
-// (C = bf16(acc + bias + Xb): one rounding per residual add) and the LayerNorms read it -- out-proj / c_proj were HBM-bound on their
-// 2 x 39 MB of fp32 residual traffic per launch (M = 12608), the LayerNorm + quantise passes on their 39 MB reads.
-static int clip_block_mx8(fern_ctx* c, const ClipBlockW& Bk, unsigned short* Xb, unsigned char* XN8, unsigned char* SM, unsigned short* QKVb,
-                          unsigned short* ATTb, unsigned char* ATT8, unsigned char* H8, int batch, int S, int width,
-                          int heads, int causal, hipStream_t s) {
-    const long R = (long)batch * S;
-    const int hd = width / heads, mlp = Bk.fc.out;
-    HIP_TRY(launch_layernorm_mx8(nullptr, Bk.ln1.g, Bk.ln1.b, XN8, SM, R, R, width, width, width, 1e-5f, s, Xb));
-    FERN_TRY(run_gemm_b(c, gemm_desc_mx(XN8, SM, R, width, Bk.qkv, QKVb, 3 * width, (int)R, EPI_BIAS, true), s));
-    AttnParams a{nullptr, nullptr, nullptr, nullptr, 3L * width, 3L * width, 3L * width, (long)width,
-                 batch, heads, hd, S, S, causal, 1.0f / std::sqrt((float)hd), ATTb, QKVb, QKVb + width, QKVb + 2 * width};
-    if (hd % 32 == 0) {      // the attention kernel quantises its fp32 output itself (the QKV GEMM is done with SM by now)
-        a.out_b = nullptr; a.out_q8 = ATT8; a.out_scales = SM; a.out_srows = R;
+// The four steps of a block: each launches what precedes its GEMM and fills the GEMM's descriptor.
+static int prep_qkv(fern_ctx*, const Tower& T, const ClipBlockW& Bk, hipStream_t s, GemmParams* p) {
+    return ln_gemm(T, T.attn, Bk.ln1, Bk.qkv, T.QKV, 3 * T.width, EPI_BIAS, true, s, p);
+}
+static int prep_out(fern_ctx* c, const Tower& T, const ClipBlockW& Bk, hipStream_t s, GemmParams* p) {
+    const long R = T.R();
+    const int w = T.width, hd = w / T.heads;
+    const bool fused = T.attn == MX && hd % 32 == 0;      // the attention kernel quantises its fp32 output itself (the QKV GEMM is done with SM by now)
+    if (T.attn == F32) {
+        AttnParams a{T.QKV, T.QKV + w, T.QKV + 2 * w, T.ATT, 3L * w, 3L * w, 3L * w, (long)w,
+                     T.batch, T.heads, hd, T.S, T.S, T.causal, 1.0f / std::sqrt((float)hd)};
         FERN_TRY(run_attention(c, a, s));
     } else {
+        AttnParams a{nullptr, nullptr, nullptr, nullptr, 3L * w, 3L * w, 3L * w, (long)w,
+                     T.batch, T.heads, hd, T.S, T.S, T.causal, 1.0f / std::sqrt((float)hd), T.ATTb(), T.QKVb(), T.QKVb() + w, T.QKVb() + 2 * w};
+        if (fused) { a.out_b = nullptr; a.out_q8 = T.ATT8(); a.out_scales = T.SM(); a.out_srows = R; }
         FERN_TRY(run_attention(c, a, s));
-        HIP_TRY(launch_quantize_mx8(ATTb, nullptr, width, ATT8, width, SM, R, R, width, s));
     }
-    GemmParams po = gemm_desc_mx(ATT8, SM, R, width, Bk.out, Xb, width, (int)R, EPI_BIAS_RESIDUAL, true);
-    po.Rb = Xb;
-    FERN_TRY(run_gemm_b(c, po, s));
-    HIP_TRY(launch_layernorm_mx8(nullptr, Bk.ln2.g, Bk.ln2.b, XN8, SM, R, R, width, width, width, 1e-5f, s, Xb));
-    // c_fc quantises its GELU output where it is produced (fp32 values -> e4m3fn + block scales): no bf16 round trip, no extra pass
-    unsigned char* SH = SM + ((size_t)R * (width / 32) + 255) / 256 * 256;      // H's scales, behind the LayerNorm output's
-    GemmParams pf = gemm_desc_mx(XN8, SM, R, width, Bk.fc, H8, mlp, (int)R, clip_mlp_epi(c), false);
-    pf.out_mx8 = 1; pf.mxc = SH; pf.mxc_rows = R;
-    FERN_TRY(run_gemm_b(c, pf, s));
-    GemmParams p2 = gemm_desc_mx(H8, SH, R, mlp, Bk.proj, Xb, width, (int)R, EPI_BIAS_RESIDUAL, true);
-    p2.Rb = Xb;
-    return run_gemm_b(c, p2, s);
+    switch (T.attn) {
+    case F32: *p = gemm_desc(T.ATT, w, Bk.out, T.X, w, (int)R, EPI_BIAS_RESIDUAL); break;
+    case BF16: *p = gemm_desc_b(T.ATTb(), w, Bk.out, T.X, w, (int)R, EPI_BIAS_RESIDUAL, false); break;
+    case FP8:
+        HIP_TRY(launch_quantize_rows_fp8(T.ATTb(), nullptr, w, T.ATT8(), w, T.SA(), R, w, s));
+        *p = gemm_desc_f8(T.ATT8(), T.SA(), w, Bk.out, T.X, w, (int)R, EPI_BIAS_RESIDUAL, false);
+        break;
+    case MX:
+        if (!fused) HIP_TRY(launch_quantize_mx8(T.ATTb(), nullptr, w, T.ATT8(), w, T.SM(), R, R, w, s));
+        *p = gemm_desc_mx(T.ATT8(), T.SM(), R, w, Bk.out, T.stream(), w, (int)R, EPI_BIAS_RESIDUAL, T.Xb != nullptr);
+        break;
+    }
+    residual_in_place(T, p);
+    return FERN_OK;
+}
+static int prep_fc(fern_ctx* c, const Tower& T, const ClipBlockW& Bk, hipStream_t s, GemmParams* p) {
+    FERN_TRY(ln_gemm(T, T.mlpf, Bk.ln2, Bk.fc, T.H, T.mlp, clip_mlp_epi(c), T.mlpf != MX, s, p));
+    if (T.mlpf == MX) { p->out_mx8 = 1; p->mxc = T.SH(); p->mxc_rows = T.R(); }
+    return FERN_OK;
+}
+static int prep_proj(fern_ctx*, const Tower& T, const ClipBlockW& Bk, hipStream_t s, GemmParams* p) {
+    const long R = T.R();
+    const int w = T.width, mlp = T.mlp;
+    switch (T.mlpf) {
+    case F32: *p = gemm_desc(T.H, mlp, Bk.proj, T.X, w, (int)R, EPI_BIAS_RESIDUAL); break;
+    case BF16: *p = gemm_desc_b(T.Hb(), mlp, Bk.proj, T.X, w, (int)R, EPI_BIAS_RESIDUAL, false); break;
+    case FP8:
+        HIP_TRY(launch_quantize_rows_fp8(T.Hb(), nullptr, mlp, T.H8(FP8), mlp, T.SA(), R, mlp, s));
+        *p = gemm_desc_f8(T.H8(FP8), T.SA(), mlp, Bk.proj, T.X, w, (int)R, EPI_BIAS_RESIDUAL, false);
+        break;
+    case MX:
+        *p = gemm_desc_mx(T.H8(MX), T.SH(), R, mlp, Bk.proj, T.stream(), w, (int)R, EPI_BIAS_RESIDUAL, T.Xb != nullptr);
+        break;
+    }
+    residual_in_place(T, p);
+    return FERN_OK;
 }
 
-// Mixed block (FERN_PREC_MX8_MLP): the attention half as in the bf16 block (LayerNorm -> bf16, QKV and out-proj on the bf16 MFMA, bf16
-// attention), the MLP half -- two thirds of a block's GEMM flops -- as in the block-scaled block (LayerNorm -> e4m3fn + E8M0 scales,
-// c_fc quantising its GELU output where it is produced, c_proj), over the fp32 residual stream of the bf16 / fp8 modes.  Half of the
-// fp8 rounding points of the MX8 mode (and its bf16 residual stream) are gone; bench.py's `reduced_modes` table has what that buys.
-// attn_mx (FERN_PREC_MX8_IMG, round 6): the attention half block-scaled too -- LayerNorm-1 writes e4m3fn + scales, the attention kernel
-// quantises its own output, QKV and out-proj run on the scaled MFMA -- still over the FP32 residual stream: all four GEMMs at the fp8
-// rate without FERN_PREC_MX8's bf16 stream, whose 24 extra roundings per tower cost more Recall than the four GEMMs' operands do.
-static int clip_block_mxmlp(fern_ctx* c, const ClipBlockW& Bk, float* X, float* XN, unsigned short* QKVb, unsigned short* ATTb, unsigned char* H8,
-                            int batch, int S, int width, int heads, int causal, hipStream_t s, bool attn_mx = false) {
-    const long R = (long)batch * S;
-    const int hd = width / heads, mlp = Bk.fc.out;
-    unsigned short* XNb = reinterpret_cast<unsigned short*>(XN);
-    unsigned char* XN8 = reinterpret_cast<unsigned char*>(XN);
-    unsigned char* SM = reinterpret_cast<unsigned char*>(XN + ((size_t)R * width / 4 + 63) / 64 * 64);
-    const bool qkv_mx = attn_mx && hd % 32 == 0;
-    if (qkv_mx) {
-        HIP_TRY(launch_layernorm_mx8(X, Bk.ln1.g, Bk.ln1.b, XN8, SM, R, R, width, width, width, 1e-5f, s));
-        FERN_TRY(run_gemm_b(c, gemm_desc_mx(XN8, SM, R, width, Bk.qkv, QKVb, 3 * width, (int)R, EPI_BIAS, true), s));
-    } else {
-        HIP_TRY(launch_layernorm_bf16(X, Bk.ln1.g, Bk.ln1.b, XNb, R, width, width, width, 1e-5f, s));
-        FERN_TRY(run_gemm_b(c, gemm_desc_b(XNb, width, Bk.qkv, QKVb, 3 * width, (int)R, EPI_BIAS, true), s));
-    }
-    AttnParams a{nullptr, nullptr, nullptr, nullptr, 3L * width, 3L * width, 3L * width, (long)width,
-                 batch, heads, hd, S, S, causal, 1.0f / std::sqrt((float)hd), ATTb, QKVb, QKVb + width, QKVb + 2 * width};
-    if (qkv_mx) {      // the attention kernel quantises its output itself (the QKV GEMM is done with SM by now)
-        unsigned char* ATT8 = reinterpret_cast<unsigned char*>(ATTb) + (size_t)R * width * 2;
-        a.out_b = nullptr; a.out_q8 = ATT8; a.out_scales = SM; a.out_srows = R;
-        FERN_TRY(run_attention(c, a, s));
-        GemmParams po = gemm_desc_mx(ATT8, SM, R, width, Bk.out, X, width, (int)R, EPI_BIAS_RESIDUAL, false);
-        po.R = X;
-        FERN_TRY(run_gemm_b(c, po, s));
-    } else {
-        FERN_TRY(run_attention(c, a, s));
-        GemmParams po = gemm_desc_b(ATTb, width, Bk.out, X, width, (int)R, EPI_BIAS_RESIDUAL, false);
-        po.R = X;
-        FERN_TRY(run_gemm_b(c, po, s));
-    }
-    HIP_TRY(launch_layernorm_mx8(X, Bk.ln2.g, Bk.ln2.b, XN8, SM, R, R, width, width, width, 1e-5f, s));
-    unsigned char* SH = SM + ((size_t)R * (width / 32) + 255) / 256 * 256;      // H's scales, behind the LayerNorm output's
-    GemmParams pf = gemm_desc_mx(XN8, SM, R, width, Bk.fc, H8, mlp, (int)R, clip_mlp_epi(c), false);
-    pf.out_mx8 = 1; pf.mxc = SH; pf.mxc_rows = R;
-    FERN_TRY(run_gemm_b(c, pf, s));
-    GemmParams p2 = gemm_desc_mx(H8, SH, R, mlp, Bk.proj, X, width, (int)R, EPI_BIAS_RESIDUAL, false);
-    p2.R = X;
-    return run_gemm_b(c, p2, s);
+static int tower_block(fern_ctx* c, const Tower& T, int l, hipStream_t s) {
+    const ClipBlockW& Bk = T.blocks[l];
+    GemmParams p;
+    FERN_TRY(prep_qkv(c, T, Bk, s, &p));
+    FERN_TRY(run_gemm_form(c, T.attn, p, s));
+    FERN_TRY(prep_out(c, T, Bk, s, &p));
+    FERN_TRY(run_gemm_form(c, T.attn, p, s));
+    FERN_TRY(prep_fc(c, T, Bk, s, &p));
+    FERN_TRY(run_gemm_form(c, T.mlpf, p, s));
+    FERN_TRY(prep_proj(c, T, Bk, s, &p));
+    return run_gemm_form(c, T.mlpf, p, s);
 }
 
 // Last ViT block: only the class token is consumed afterwards (ln_post on token 0, modeling_clip.py:876-877), so
 // K/V are projected for every token but Q, the attention output, out_proj and the MLP run for the class rows only.
 // Equal to the full block on the rows that are read only to TOLERANCE since round 5: the single-query attention kernel and the
 // 512-wide split-K c_proj add their products in another order than the full block's kernels (fp32 parity mode included).
-// Xb (FERN_PREC_MX8 with its bf16 residual stream): the stream itself -- the token-level LayerNorm reads it as the full blocks do and
+// V.Xb (FERN_PREC_MX8 with its bf16 residual stream): the stream itself -- the token-level LayerNorm reads it as the full blocks do and
 // only the class rows are widened to fp32 (X is then not read: round 5 dropped the 58 MB bf16 -> fp32 pass over the whole stream).
-static int clip_block_cls_only(fern_ctx* c, const ClipBlockW& Bk, const float* X, float* XN, float* QKV, float* CLS /*[b,width] out*/,
-                               float* T0 /*[b,width]*/, float* T1 /*[b,width]*/, float* H /*[b,mlp]*/, int batch, int S, int width,
-                               int heads, hipStream_t s, const unsigned short* Xb = nullptr) {
-    const long R = (long)batch * S;
-    const int hd = width / heads;
+static int clip_block_cls_only(fern_ctx* c, const Tower& V, const ClipBlockW& Bk, float* CLS /*[b,width] out*/, float* T0 /*[b,width]*/,
+                               float* T1 /*[b,width]*/, float* H /*[b,mlp]*/, hipStream_t s) {
+    const int batch = V.batch, S = V.S, width = V.width, heads = V.heads, hd = width / heads;
+    const float* X = V.X;
+    const unsigned short* Xb = V.Xb;
+    float* QKV = V.QKV;
     LinearW kv{Bk.qkv.w + (size_t)width * width, Bk.qkv.b + width, 2 * width, width, Bk.qkv.wb + (size_t)width * width,
                Bk.qkv.w8 ? Bk.qkv.w8 + (size_t)width * width : nullptr, Bk.qkv.sw ? Bk.qkv.sw + width : nullptr,
                Bk.qkv.wm ? Bk.qkv.wm + (size_t)width * width : nullptr, Bk.qkv.swm ? Bk.qkv.swm + (size_t)width * 4 : nullptr, Bk.qkv.swm_rows};
-    if (c->precision == FERN_PREC_MX8) {
-        // MX mode: block-scaled K/V projection of all tokens (fp32 output); the class-row chain below stays fp32
-        unsigned char* XN8 = reinterpret_cast<unsigned char*>(XN);
-        unsigned char* SM = reinterpret_cast<unsigned char*>(XN + ((size_t)R * width / 4 + 63) / 64 * 64);
-        if (Xb) HIP_TRY(launch_layernorm_mx8(nullptr, Bk.ln1.g, Bk.ln1.b, XN8, SM, R, R, width, width, width, 1e-5f, s, Xb));
-        else HIP_TRY(launch_layernorm_mx8(X, Bk.ln1.g, Bk.ln1.b, XN8, SM, R, R, width, width, width, 1e-5f, s));
-        FERN_TRY(run_gemm_b(c, gemm_desc_mx(XN8, SM, R, width, kv, QKV + width, 3 * width, (int)R, EPI_BIAS, false), s));
+    // token-level ln_1 and the K/V projection of all tokens (fp32 output) in the attention half's form; this block stays BF16 under
+    // FERN_PREC_MX8_IMG as under FERN_PREC_MX8_MLP
+    const Form f = c->precision == FERN_PREC_MX8_IMG ? BF16 : V.attn;
+    GemmParams pk;
+    FERN_TRY(ln_gemm(V, f, Bk.ln1, kv, QKV + width, 3 * width, EPI_BIAS, false, s, &pk));
+    FERN_TRY(run_gemm_form(c, f, pk, s));                                                              // K, V for all tokens
+    if (f == F32) {
+        HIP_TRY(launch_gather_rows(V.XN, width, T0, width, batch, width, 1, S, 0, nullptr, s));        // ln_1(x)[:, 0]
+    } else {      // the class-row chain below stays fp32 in every form
         if (Xb) HIP_TRY(launch_gather_rows_bf16(Xb, width, T1, width, batch, width, S, s));
-        else HIP_TRY(launch_gather_rows(X, width, T1, width, batch, width, 1, S, 0, nullptr, s));
-        HIP_TRY(launch_layernorm(T1, nullptr, Bk.ln1.g, Bk.ln1.b, T0, batch, width, width, width, 1e-5f, s));
-    } else if (c->precision == FERN_PREC_FP8) {
-        // fp8 mode: quantised K/V projection of all tokens (fp32 output); the class-row chain below stays fp32
-        unsigned char* XN8 = reinterpret_cast<unsigned char*>(XN);
-        float* SA = XN + ((size_t)R * width / 4 + 63) / 64 * 64;       // scales live behind the fp8 rows inside XN
-        HIP_TRY(launch_layernorm_fp8(X, Bk.ln1.g, Bk.ln1.b, XN8, SA, R, width, width, width, 1e-5f, s));
-        FERN_TRY(run_gemm_b(c, gemm_desc_f8(XN8, SA, width, kv, QKV + width, 3 * width, (int)R, EPI_BIAS, false), s));
-        HIP_TRY(launch_gather_rows(X, width, T1, width, batch, width, 1, S, 0, nullptr, s));
-        HIP_TRY(launch_layernorm(T1, nullptr, Bk.ln1.g, Bk.ln1.b, T0, batch, width, width, width, 1e-5f, s));
-    } else if (c->precision == FERN_PREC_BF16 || c->precision == FERN_PREC_MX8_MLP || c->precision == FERN_PREC_MX8_IMG) {
-        // perf mode: the token-level K/V projection takes bf16 operands; the class-row chain below stays fp32
-        unsigned short* XNb = reinterpret_cast<unsigned short*>(XN);
-        HIP_TRY(launch_layernorm_bf16(X, Bk.ln1.g, Bk.ln1.b, XNb, R, width, width, width, 1e-5f, s));
-        FERN_TRY(run_gemm_b(c, gemm_desc_b(XNb, width, kv, QKV + width, 3 * width, (int)R, EPI_BIAS, false), s));
-        HIP_TRY(launch_gather_rows(X, width, T1, width, batch, width, 1, S, 0, nullptr, s));           // x[:, 0]
+        else HIP_TRY(launch_gather_rows(X, width, T1, width, batch, width, 1, S, 0, nullptr, s));      // x[:, 0]
         HIP_TRY(launch_layernorm(T1, nullptr, Bk.ln1.g, Bk.ln1.b, T0, batch, width, width, width, 1e-5f, s));   // ln_1(x)[:, 0]
-    } else {
-        HIP_TRY(launch_layernorm(X, nullptr, Bk.ln1.g, Bk.ln1.b, XN, R, width, width, width, 1e-5f, s));
-        FERN_TRY(run_gemm(c, gemm_desc(XN, width, kv, QKV + width, 3 * width, (int)R, EPI_BIAS), s));  // K, V for all tokens
-        HIP_TRY(launch_gather_rows(XN, width, T0, width, batch, width, 1, S, 0, nullptr, s));          // ln_1(x)[:, 0]
     }
     LinearW qw{Bk.qkv.w, Bk.qkv.b, width, width};
     FERN_TRY(run_gemm(c, gemm_desc(T0, width, qw, T1, width, batch, EPI_BIAS), s));                    // Q for the class rows
@@ -1447,7 +1466,7 @@ static int vit_front(fern_ctx* c, const float* images, float* X, float* H, int b
         // GEMM against the padded weight; same epilogue.  Every precision mode: the reduced modes define no patch embedding for these shapes
         const long rows = (long)b * g2;
         float* P = H;
-        // H is [b * S, v_mlp] FLOATS in all three walkers (vit_chunk, pair_chunk, pair_chunk_mximg): element counts are compared
+        // H is [b * S, v_mlp] FLOATS in both walkers (vit_chunk, pair_chunk: tower_open): element counts are compared
         if ((size_t)rows * W.conv_kp > (size_t)b * S * cf.v_mlp) FERN_TRY(ws_get(c, (size_t)rows * W.conv_kp, &P));      // narrow MLPs (test towers)
         HIP_TRY(launch_patch_rows_f32(images, P, b, cf.image_size, cf.patch_size, g, W.conv_kp, s));
         LinearW conv{W.conv_wp, nullptr, vw, W.conv_kp};
@@ -1489,13 +1508,12 @@ static int vit_front(fern_ctx* c, const float* images, float* X, float* H, int b
 }
 
 // Tail of the ViT tower: the last block for the class rows only, ln_post, the visual projection (modeling_clip.py:876-887).  ATT / H are
-// free after the last full block: their heads are the [b, width] / [b, mlp] temporaries.  Xb: the bf16 residual stream of FERN_PREC_MX8.
-static int vit_tail(fern_ctx* c, float* X, float* XN, float* QKV, float* ATT, float* H, float* CLS, float* out, int b, hipStream_t s,
-                    const unsigned short* Xb = nullptr) {
+// free after the last full block: their heads are the [b, width] / [b, mlp] temporaries.
+static int vit_tail(fern_ctx* c, const Tower& V, float* CLS, float* out, hipStream_t s) {
     const ClipW& W = c->clip;
     const fern_clip_config& cf = W.cfg;
-    const int vw = cf.v_width, g = cf.image_size / cf.patch_size, S = g * g + 1;
-    FERN_TRY(clip_block_cls_only(c, W.vblocks[cf.v_layers - 1], X, XN, QKV, CLS, ATT, ATT + (size_t)b * vw, H, b, S, vw, cf.v_heads, s, Xb));
+    const int vw = V.width, b = V.batch;
+    FERN_TRY(clip_block_cls_only(c, V, W.vblocks[cf.v_layers - 1], CLS, V.ATT, V.ATT + (size_t)b * vw, V.H, s));
     HIP_TRY(launch_layernorm(CLS, nullptr, W.ln_post.g, W.ln_post.b, CLS, b, vw, vw, vw, 1e-5f, s));
     LinearW proj{W.vproj_t, nullptr, cf.embed_dim, vw};
     return run_gemm(c, gemm_desc(CLS, vw, proj, out, cf.embed_dim, b, EPI_BIAS), s);
@@ -1521,7 +1539,7 @@ static int text_tail(fern_ctx* c, const float* X, float* XN, const int* eot, flo
     return FERN_OK;
 }
 
-// Images per chunk of the ViT walkers (vit_chunk, pair_chunk, pair_chunk_mximg): 64 up to 197 tokens -- what every tower before ViT-L/14 ran
+// Images per chunk of the ViT walkers (vit_chunk, pair_chunk): 64 up to 197 tokens -- what every tower before ViT-L/14 ran
 // with -- and beyond that as many as keep a chunk at those 64 x 197 = 12 608 token rows (257 tokens: 49 images, 577: 21), so the workspace
 // grows with the tower's width only.  Rows are batch-invariant: where a chunk ends changes no result.
 static int vit_chunk_images(const fern_clip_config& cf) {
@@ -1531,50 +1549,22 @@ static int vit_chunk_images(const fern_clip_config& cf) {
 
 static int vit_chunk(fern_ctx* c, const float* images, float* out, int b, hipStream_t s) {
     const ClipW& W = c->clip;
-    const fern_clip_config& cf = W.cfg;
-    const int vw = cf.v_width, g = cf.image_size / cf.patch_size, g2 = g * g, S = g2 + 1;
-    const long R = (long)b * S;
-    float *X, *XN, *QKV, *ATT, *H, *CLS;
-    FERN_TRY(ws_get(c, (size_t)R * vw, &X));
-    FERN_TRY(ws_get(c, (size_t)R * vw, &XN));
-    FERN_TRY(ws_get(c, (size_t)R * 3 * vw, &QKV));
-    FERN_TRY(ws_get(c, (size_t)R * vw, &ATT));
-    FERN_TRY(ws_get(c, (size_t)R * cf.v_mlp, &H));
-    FERN_TRY(ws_get(c, (size_t)b * vw, &CLS));
-    FERN_TRY(vit_front(c, images, X, H, b, s));
-    unsigned short* Xb = nullptr;              // FERN_PREC_MX8: the bf16 residual stream of the full blocks
-    const bool mx_stream = c->precision == FERN_PREC_MX8 && cf.v_layers > 1;
-    if (mx_stream) {
-        FERN_TRY(ws_get(c, (size_t)R * vw, &Xb));
-        HIP_TRY(launch_layernorm_bf16(X, W.ln_pre.g, W.ln_pre.b, Xb, R, vw, vw, vw, 1e-5f, s));      // ln_pre writes the stream (rounded once)
+    Tower V;
+    float* CLS;
+    FERN_TRY(tower_open(c, false, b, &V));
+    FERN_TRY(ws_get(c, (size_t)b * V.width, &CLS));
+    FERN_TRY(vit_front(c, images, V.X, V.H, b, s));
+    const long R = V.R();
+    const int vw = V.width;
+    if (V.bf16_stream && W.cfg.v_layers > 1) {
+        FERN_TRY(ws_get(c, (size_t)R * vw, &V.Xb));
+        HIP_TRY(launch_layernorm_bf16(V.X, W.ln_pre.g, W.ln_pre.b, V.Xb, R, vw, vw, vw, 1e-5f, s));      // ln_pre writes the stream (rounded once)
     } else {
-        HIP_TRY(launch_layernorm(X, nullptr, W.ln_pre.g, W.ln_pre.b, X, R, vw, vw, vw, 1e-5f, s));
+        HIP_TRY(launch_layernorm(V.X, nullptr, W.ln_pre.g, W.ln_pre.b, V.X, R, vw, vw, vw, 1e-5f, s));
     }
-    for (int l = 0; l + 1 < cf.v_layers; ++l) {
-        if (c->precision == FERN_PREC_MX8) {    // same buffer plan as fp8 below; the scale area holds E8M0 bytes
-            unsigned char* XN8 = reinterpret_cast<unsigned char*>(XN);
-            FERN_TRY(clip_block_mx8(c, W.vblocks[l], Xb, XN8, reinterpret_cast<unsigned char*>(XN + ((size_t)R * vw / 4 + 63) / 64 * 64),
-                                    reinterpret_cast<unsigned short*>(QKV), reinterpret_cast<unsigned short*>(ATT),
-                                    reinterpret_cast<unsigned char*>(ATT) + (size_t)R * vw * 2, reinterpret_cast<unsigned char*>(H),
-                                    b, S, vw, cf.v_heads, 0, s));
-        } else if (c->precision == FERN_PREC_FP8) {    // XN: fp8 rows + scales; ATT / H: bf16 output in the first half, its fp8 copy behind it
-            unsigned char* XN8 = reinterpret_cast<unsigned char*>(XN);
-            FERN_TRY(clip_block_fp8(c, W.vblocks[l], X, XN8, XN + ((size_t)R * vw / 4 + 63) / 64 * 64, reinterpret_cast<unsigned short*>(QKV),
-                                    reinterpret_cast<unsigned short*>(ATT), reinterpret_cast<unsigned char*>(ATT) + (size_t)R * vw * 2,
-                                    reinterpret_cast<unsigned short*>(H), reinterpret_cast<unsigned char*>(H) + (size_t)R * cf.v_mlp * 2,
-                                    b, S, vw, cf.v_heads, 0, s));
-        } else if (c->precision == FERN_PREC_MX8_MLP || c->precision == FERN_PREC_MX8_IMG) {
-            FERN_TRY(clip_block_mxmlp(c, W.vblocks[l], X, XN, reinterpret_cast<unsigned short*>(QKV), reinterpret_cast<unsigned short*>(ATT),
-                                      reinterpret_cast<unsigned char*>(H), b, S, vw, cf.v_heads, 0, s, c->precision == FERN_PREC_MX8_IMG));
-        } else if (c->precision == FERN_PREC_BF16)     // XN / ATT / H double as the bf16 operand buffers (half filled)
-            FERN_TRY(clip_block_bf16(c, W.vblocks[l], X, reinterpret_cast<unsigned short*>(XN), reinterpret_cast<unsigned short*>(QKV),
-                                     reinterpret_cast<unsigned short*>(ATT),
-                                     reinterpret_cast<unsigned short*>(H), b, S, vw, cf.v_heads, 0, s));
-        else
-            FERN_TRY(clip_block(c, W.vblocks[l], X, XN, QKV, ATT, H, b, S, vw, cf.v_heads, 0, s));
-    }
+    for (int l = 0; l + 1 < W.cfg.v_layers; ++l) FERN_TRY(tower_block(c, V, l, s));
     // the class-row chain of the last block is fp32; with the bf16 stream only the class rows are widened (exactly), inside the block
-    return vit_tail(c, X, XN, QKV, ATT, H, CLS, out, b, s, mx_stream ? Xb : nullptr);
+    return vit_tail(c, V, CLS, out, s);
 }
 
 // ---- open_clip ModifiedResNet (RN50x4).  Activations are NHWC, so every 1x1 convolution is a plain GEMM over the pixel
@@ -1679,180 +1669,66 @@ extern "C" int fern_vit_encode_image(fern_ctx* c, const float* images, float* ou
 static int text_chunk(fern_ctx* c, const int64_t* tokens, float* out_global, float* out_seq, int B, hipStream_t s) {
     const ClipW& W = c->clip;
     const fern_clip_config& cf = W.cfg;
-    const int tw = cf.t_width, T = cf.context_length;
-    const long R = (long)B * T;
-    float *X, *XN, *QKV, *ATT, *H;
+    Tower T;
     int* eot;
-    FERN_TRY(ws_get(c, (size_t)R * tw, &X));
-    FERN_TRY(ws_get(c, (size_t)R * tw, &XN));
-    FERN_TRY(ws_get(c, (size_t)R * 3 * tw, &QKV));
-    FERN_TRY(ws_get(c, (size_t)R * tw, &ATT));
-    FERN_TRY(ws_get(c, (size_t)R * cf.t_mlp, &H));
+    FERN_TRY(tower_open(c, true, B, &T));
     FERN_TRY(ws_get(c, (size_t)B, &eot));
-    HIP_TRY(launch_text_embed(tokens, W.tok_emb, W.tpos, X, eot, B, T, tw, cf.vocab_size, c->tok_flag, s));
-    const bool text_mx = c->precision == FERN_PREC_MX8;
-    unsigned short* Xb = nullptr;              // FERN_PREC_MX8: the bf16 residual stream of the blocks (clip_block_mx8)
-    if (text_mx) {
-        FERN_TRY(ws_get(c, (size_t)R * tw, &Xb));
-        HIP_TRY(launch_f32_to_bf16(X, Xb, R * tw, s));
+    HIP_TRY(launch_text_embed(tokens, W.tok_emb, W.tpos, T.X, eot, B, T.S, T.width, cf.vocab_size, c->tok_flag, s));
+    if (T.bf16_stream) {
+        FERN_TRY(ws_get(c, (size_t)T.R() * T.width, &T.Xb));
+        HIP_TRY(launch_f32_to_bf16(T.X, T.Xb, T.R() * T.width, s));
     }
-    for (int l = 0; l < cf.t_layers; ++l) {
-        if (text_mx) {
-            unsigned char* XN8 = reinterpret_cast<unsigned char*>(XN);
-            FERN_TRY(clip_block_mx8(c, W.tblocks[l], Xb, XN8, reinterpret_cast<unsigned char*>(XN + ((size_t)R * tw / 4 + 63) / 64 * 64),
-                                    reinterpret_cast<unsigned short*>(QKV), reinterpret_cast<unsigned short*>(ATT),
-                                    reinterpret_cast<unsigned char*>(ATT) + (size_t)R * tw * 2, reinterpret_cast<unsigned char*>(H),
-                                    B, T, tw, cf.t_heads, 1, s));
-        } else if (c->precision == FERN_PREC_FP8) {
-            unsigned char* XN8 = reinterpret_cast<unsigned char*>(XN);
-            FERN_TRY(clip_block_fp8(c, W.tblocks[l], X, XN8, XN + ((size_t)R * tw / 4 + 63) / 64 * 64, reinterpret_cast<unsigned short*>(QKV),
-                                    reinterpret_cast<unsigned short*>(ATT), reinterpret_cast<unsigned char*>(ATT) + (size_t)R * tw * 2,
-                                    reinterpret_cast<unsigned short*>(H), reinterpret_cast<unsigned char*>(H) + (size_t)R * cf.t_mlp * 2,
-                                    B, T, tw, cf.t_heads, 1, s));
-        } else if (c->precision == FERN_PREC_BF16 || c->precision == FERN_PREC_MX8_MLP || c->precision == FERN_PREC_MX8_IMG)
-            // FERN_PREC_MX8_MLP / _IMG (round 6): the TEXT tower runs the bf16 block throughout -- its GEMMs (M = 77 B rows, K = 512) are
-            // the ones the block-scaled kernels run worst (0.07-0.12 of their peak) and its rounding points sit directly on the query:
-            // e4m3 there cost 0.9 pp of Recall@50 (bench.py `reduced_modes`: mx8mlp -1.03 -> -0.15 pp) for ~0.1 ms of a 4 ms step
-            FERN_TRY(clip_block_bf16(c, W.tblocks[l], X, reinterpret_cast<unsigned short*>(XN), reinterpret_cast<unsigned short*>(QKV),
-                                     reinterpret_cast<unsigned short*>(ATT),
-                                     reinterpret_cast<unsigned short*>(H), B, T, tw, cf.t_heads, 1, s));
-        else
-            FERN_TRY(clip_block(c, W.tblocks[l], X, XN, QKV, ATT, H, B, T, tw, cf.t_heads, 1, s));
-    }
-    if (Xb) HIP_TRY(launch_bf16_to_f32(Xb, X, R * tw, s));
-    return text_tail(c, X, XN, eot, out_global, out_seq, B, s);
+    for (int l = 0; l < cf.t_layers; ++l) FERN_TRY(tower_block(c, T, l, s));
+    if (T.Xb) HIP_TRY(launch_bf16_to_f32(T.Xb, T.X, T.R() * T.width, s));
+    return text_tail(c, T.X, T.XN, eot, out_global, out_seq, B, s);
 }
 
-// Both towers of a composed query in one pass (round 6), fp32 data flow only (FERN_PREC_FP32, also under f32x3): the
-// image tower's full blocks and the text tower's blocks are walked LAYER BY LAYER and the four GEMMs of a layer -- QKV, out-proj, c_fc,
-// c_proj -- are issued as image + text PAIRS (run_gemm_pair): the text layer's few hundred tiles ride in the image layer's launch and
-// back-fill its tail instead of running as under-filled launches of their own.  Everything else (LayerNorms, attention, the class-row
-// block, the projections) is issued exactly as vit_chunk / text_chunk issue it, and every GEMM computes the same tiles in the same k
-// order: the features are bit-identical to fern_vit_encode_image + fern_text_encode.
+// Both towers of a composed query in one pass (round 6): the image tower's full blocks and the text tower's blocks are
+// walked LAYER BY LAYER and the four GEMMs of a layer -- QKV, out-proj, c_fc, c_proj -- are issued as image + text PAIRS: the text layer's
+// few hundred tiles ride in the image layer's launch and back-fill its tail instead of running as under-filled launches of their own.
+// Two data flows pair (fern_encode_pair): fp32 (FERN_PREC_FP32, also under f32x3: run_gemm_pair) and FERN_PREC_MX8_IMG (the c5 default)
+// with both image halves MX and the text tower BF16 (run_gemm_b_pair).  Everything else (LayerNorms, attention, the class-row block, the
+// projections) is issued exactly as vit_chunk / text_chunk issue it, and every GEMM computes the same tiles in the same k order: the
+// features are bit-identical to fern_vit_encode_image + fern_text_encode.
 static int pair_chunk(fern_ctx* c, const float* images, float* out_img, const int64_t* tokens, float* out_global, float* out_seq, int b, hipStream_t s) {
     const ClipW& W = c->clip;
     const fern_clip_config& cf = W.cfg;
-    const int vw = cf.v_width, g = cf.image_size / cf.patch_size, g2 = g * g, S = g2 + 1;
-    const int tw = cf.t_width, T = cf.context_length;
-    const long R = (long)b * S, Rt = (long)b * T;
-    float *X, *XN, *QKV, *ATT, *H, *CLS, *Xt, *XNt, *QKVt, *ATTt, *Ht;
+    Tower V, T;
+    float* CLS;
     int* eot;
-    FERN_TRY(ws_get(c, (size_t)R * vw, &X));
-    FERN_TRY(ws_get(c, (size_t)R * vw, &XN));
-    FERN_TRY(ws_get(c, (size_t)R * 3 * vw, &QKV));
-    FERN_TRY(ws_get(c, (size_t)R * vw, &ATT));
-    FERN_TRY(ws_get(c, (size_t)R * cf.v_mlp, &H));
-    FERN_TRY(ws_get(c, (size_t)b * vw, &CLS));
-    FERN_TRY(ws_get(c, (size_t)Rt * tw, &Xt));
-    FERN_TRY(ws_get(c, (size_t)Rt * tw, &XNt));
-    FERN_TRY(ws_get(c, (size_t)Rt * 3 * tw, &QKVt));
-    FERN_TRY(ws_get(c, (size_t)Rt * tw, &ATTt));
-    FERN_TRY(ws_get(c, (size_t)Rt * cf.t_mlp, &Ht));
+    FERN_TRY(tower_open(c, false, b, &V));
+    FERN_TRY(ws_get(c, (size_t)b * V.width, &CLS));
+    FERN_TRY(tower_open(c, true, b, &T));
     FERN_TRY(ws_get(c, (size_t)b, &eot));
     // image tower front: conv1 (epilogue adds the positional embedding), class token, ln_pre -- as vit_chunk
-    FERN_TRY(vit_front(c, images, X, H, b, s));
-    HIP_TRY(launch_layernorm(X, nullptr, W.ln_pre.g, W.ln_pre.b, X, R, vw, vw, vw, 1e-5f, s));
+    FERN_TRY(vit_front(c, images, V.X, V.H, b, s));
+    HIP_TRY(launch_layernorm(V.X, nullptr, W.ln_pre.g, W.ln_pre.b, V.X, V.R(), V.width, V.width, V.width, 1e-5f, s));
     // text tower front -- as text_chunk
-    HIP_TRY(launch_text_embed(tokens, W.tok_emb, W.tpos, Xt, eot, b, T, tw, cf.vocab_size, c->tok_flag, s));
+    HIP_TRY(launch_text_embed(tokens, W.tok_emb, W.tpos, T.X, eot, b, T.S, T.width, cf.vocab_size, c->tok_flag, s));
     const int vfull = cf.v_layers - 1;                     // the image tower's last block runs for the class rows only
     const int paired = vfull < cf.t_layers ? vfull : cf.t_layers;
-    const int vhd = vw / cf.v_heads, thd = tw / cf.t_heads;
+    const bool mx = V.attn == MX;
+    auto run_pair = [&](const GemmParams& pv, const GemmParams& pt) { return mx ? run_gemm_b_pair(c, pv, pt, s) : run_gemm_pair(c, pv, pt, s); };
     for (int l = 0; l < paired; ++l) {
-        const ClipBlockW &Bv = W.vblocks[l], &Bt = W.tblocks[l];
-        HIP_TRY(launch_layernorm(X, nullptr, Bv.ln1.g, Bv.ln1.b, XN, R, vw, vw, vw, 1e-5f, s));
-        HIP_TRY(launch_layernorm(Xt, nullptr, Bt.ln1.g, Bt.ln1.b, XNt, Rt, tw, tw, tw, 1e-5f, s));
-        FERN_TRY(run_gemm_pair(c, gemm_desc(XN, vw, Bv.qkv, QKV, 3 * vw, (int)R, EPI_BIAS), gemm_desc(XNt, tw, Bt.qkv, QKVt, 3 * tw, (int)Rt, EPI_BIAS), s));
-        AttnParams av{QKV, QKV + vw, QKV + 2 * vw, ATT, 3L * vw, 3L * vw, 3L * vw, (long)vw, b, cf.v_heads, vhd, S, S, 0, 1.0f / std::sqrt((float)vhd)};
-        FERN_TRY(run_attention(c, av, s));
-        AttnParams at{QKVt, QKVt + tw, QKVt + 2 * tw, ATTt, 3L * tw, 3L * tw, 3L * tw, (long)tw, b, cf.t_heads, thd, T, T, 1, 1.0f / std::sqrt((float)thd)};
-        FERN_TRY(run_attention(c, at, s));
-        GemmParams pov = gemm_desc(ATT, vw, Bv.out, X, vw, (int)R, EPI_BIAS_RESIDUAL), pot = gemm_desc(ATTt, tw, Bt.out, Xt, tw, (int)Rt, EPI_BIAS_RESIDUAL);
-        pov.R = X; pot.R = Xt;
-        FERN_TRY(run_gemm_pair(c, pov, pot, s));
-        HIP_TRY(launch_layernorm(X, nullptr, Bv.ln2.g, Bv.ln2.b, XN, R, vw, vw, vw, 1e-5f, s));
-        HIP_TRY(launch_layernorm(Xt, nullptr, Bt.ln2.g, Bt.ln2.b, XNt, Rt, tw, tw, tw, 1e-5f, s));
-        FERN_TRY(run_gemm_pair(c, gemm_desc(XN, vw, Bv.fc, H, Bv.fc.out, (int)R, clip_mlp_epi(c)), gemm_desc(XNt, tw, Bt.fc, Ht, Bt.fc.out, (int)Rt, clip_mlp_epi(c)), s));
-        GemmParams ppv = gemm_desc(H, Bv.fc.out, Bv.proj, X, vw, (int)R, EPI_BIAS_RESIDUAL), ppt = gemm_desc(Ht, Bt.fc.out, Bt.proj, Xt, tw, (int)Rt, EPI_BIAS_RESIDUAL);
-        ppv.R = X; ppt.R = Xt;
-        FERN_TRY(run_gemm_pair(c, ppv, ppt, s));
+        const ClipBlockW &Bv = V.blocks[l], &Bt = T.blocks[l];
+        GemmParams pv, pt;
+        FERN_TRY(prep_qkv(c, V, Bv, s, &pv));
+        FERN_TRY(prep_qkv(c, T, Bt, s, &pt));
+        FERN_TRY(run_pair(pv, pt));
+        FERN_TRY(prep_out(c, V, Bv, s, &pv));
+        FERN_TRY(prep_out(c, T, Bt, s, &pt));
+        FERN_TRY(run_pair(pv, pt));
+        FERN_TRY(prep_fc(c, V, Bv, s, &pv));
+        FERN_TRY(prep_fc(c, T, Bt, s, &pt));
+        FERN_TRY(run_pair(pv, pt));
+        FERN_TRY(prep_proj(c, V, Bv, s, &pv));
+        FERN_TRY(prep_proj(c, T, Bt, s, &pt));
+        FERN_TRY(run_pair(pv, pt));
     }
-    for (int l = paired; l < vfull; ++l) FERN_TRY(clip_block(c, W.vblocks[l], X, XN, QKV, ATT, H, b, S, vw, cf.v_heads, 0, s));
-    for (int l = paired; l < cf.t_layers; ++l) FERN_TRY(clip_block(c, W.tblocks[l], Xt, XNt, QKVt, ATTt, Ht, b, T, tw, cf.t_heads, 1, s));
-    FERN_TRY(vit_tail(c, X, XN, QKV, ATT, H, CLS, out_img, b, s));
-    return text_tail(c, Xt, XNt, eot, out_global, out_seq, b, s);
-}
-
-// The same walk for FERN_PREC_MX8_IMG (the c5 default): the image tower's block-scaled GEMM of a layer and the text tower's bf16 GEMM of the
-// same kind as one launch (run_gemm_b_pair).  Everything else as vit_chunk (clip_block_mxmlp with attn_mx) / text_chunk (clip_block_bf16)
-// issue it; bit-identical to the two entry points.
-static int pair_chunk_mximg(fern_ctx* c, const float* images, float* out_img, const int64_t* tokens, float* out_global, float* out_seq, int b, hipStream_t s) {
-    const ClipW& W = c->clip;
-    const fern_clip_config& cf = W.cfg;
-    const int vw = cf.v_width, g = cf.image_size / cf.patch_size, g2 = g * g, S = g2 + 1;
-    const int tw = cf.t_width, T = cf.context_length;
-    const long R = (long)b * S, Rt = (long)b * T;
-    float *X, *XN, *QKV, *ATT, *H, *CLS, *Xt, *XNt, *QKVt, *ATTt, *Ht;
-    int* eot;
-    FERN_TRY(ws_get(c, (size_t)R * vw, &X));
-    FERN_TRY(ws_get(c, (size_t)R * vw, &XN));
-    FERN_TRY(ws_get(c, (size_t)R * 3 * vw, &QKV));
-    FERN_TRY(ws_get(c, (size_t)R * vw, &ATT));
-    FERN_TRY(ws_get(c, (size_t)R * cf.v_mlp, &H));
-    FERN_TRY(ws_get(c, (size_t)b * vw, &CLS));
-    FERN_TRY(ws_get(c, (size_t)Rt * tw, &Xt));
-    FERN_TRY(ws_get(c, (size_t)Rt * tw, &XNt));
-    FERN_TRY(ws_get(c, (size_t)Rt * 3 * tw, &QKVt));
-    FERN_TRY(ws_get(c, (size_t)Rt * tw, &ATTt));
-    FERN_TRY(ws_get(c, (size_t)Rt * cf.t_mlp, &Ht));
-    FERN_TRY(ws_get(c, (size_t)b, &eot));
-    FERN_TRY(vit_front(c, images, X, H, b, s));
-    HIP_TRY(launch_layernorm(X, nullptr, W.ln_pre.g, W.ln_pre.b, X, R, vw, vw, vw, 1e-5f, s));
-    HIP_TRY(launch_text_embed(tokens, W.tok_emb, W.tpos, Xt, eot, b, T, tw, cf.vocab_size, c->tok_flag, s));
-    const int vfull = cf.v_layers - 1;
-    const int paired = vfull < cf.t_layers ? vfull : cf.t_layers;
-    const int vhd = vw / cf.v_heads, thd = tw / cf.t_heads, mlp = cf.v_mlp;
-    // operand views of the image tower's buffers (clip_block_mxmlp) and the text tower's (clip_block_bf16)
-    unsigned char* XN8 = reinterpret_cast<unsigned char*>(XN);
-    unsigned char* SM = reinterpret_cast<unsigned char*>(XN + ((size_t)R * vw / 4 + 63) / 64 * 64);
-    unsigned char* SH = SM + ((size_t)R * (vw / 32) + 255) / 256 * 256;
-    unsigned short* QKVb = reinterpret_cast<unsigned short*>(QKV);
-    unsigned short* ATTb = reinterpret_cast<unsigned short*>(ATT);
-    unsigned char* ATT8 = reinterpret_cast<unsigned char*>(ATT) + (size_t)R * vw * 2;
-    unsigned char* H8 = reinterpret_cast<unsigned char*>(H);
-    unsigned short *XNtb = reinterpret_cast<unsigned short*>(XNt), *QKVtb = reinterpret_cast<unsigned short*>(QKVt),
-                   *ATTtb = reinterpret_cast<unsigned short*>(ATTt), *Htb = reinterpret_cast<unsigned short*>(Ht);
-    for (int l = 0; l < paired; ++l) {
-        const ClipBlockW &Bv = W.vblocks[l], &Bt = W.tblocks[l];
-        HIP_TRY(launch_layernorm_mx8(X, Bv.ln1.g, Bv.ln1.b, XN8, SM, R, R, vw, vw, vw, 1e-5f, s));
-        HIP_TRY(launch_layernorm_bf16(Xt, Bt.ln1.g, Bt.ln1.b, XNtb, Rt, tw, tw, tw, 1e-5f, s));
-        FERN_TRY(run_gemm_b_pair(c, gemm_desc_mx(XN8, SM, R, vw, Bv.qkv, QKVb, 3 * vw, (int)R, EPI_BIAS, true),
-                                 gemm_desc_b(XNtb, tw, Bt.qkv, QKVtb, 3 * tw, (int)Rt, EPI_BIAS, true), s));
-        AttnParams av{nullptr, nullptr, nullptr, nullptr, 3L * vw, 3L * vw, 3L * vw, (long)vw,
-                      b, cf.v_heads, vhd, S, S, 0, 1.0f / std::sqrt((float)vhd), ATTb, QKVb, QKVb + vw, QKVb + 2 * vw};
-        av.out_b = nullptr; av.out_q8 = ATT8; av.out_scales = SM; av.out_srows = R;
-        FERN_TRY(run_attention(c, av, s));
-        AttnParams at{nullptr, nullptr, nullptr, nullptr, 3L * tw, 3L * tw, 3L * tw, (long)tw,
-                      b, cf.t_heads, thd, T, T, 1, 1.0f / std::sqrt((float)thd), ATTtb, QKVtb, QKVtb + tw, QKVtb + 2 * tw};
-        FERN_TRY(run_attention(c, at, s));
-        GemmParams pov = gemm_desc_mx(ATT8, SM, R, vw, Bv.out, X, vw, (int)R, EPI_BIAS_RESIDUAL, false);
-        GemmParams pot = gemm_desc_b(ATTtb, tw, Bt.out, Xt, tw, (int)Rt, EPI_BIAS_RESIDUAL, false);
-        pov.R = X; pot.R = Xt;
-        FERN_TRY(run_gemm_b_pair(c, pov, pot, s));
-        HIP_TRY(launch_layernorm_mx8(X, Bv.ln2.g, Bv.ln2.b, XN8, SM, R, R, vw, vw, vw, 1e-5f, s));
-        HIP_TRY(launch_layernorm_bf16(Xt, Bt.ln2.g, Bt.ln2.b, XNtb, Rt, tw, tw, tw, 1e-5f, s));
-        GemmParams pfv = gemm_desc_mx(XN8, SM, R, vw, Bv.fc, H8, mlp, (int)R, clip_mlp_epi(c), false);
-        pfv.out_mx8 = 1; pfv.mxc = SH; pfv.mxc_rows = R;
-        FERN_TRY(run_gemm_b_pair(c, pfv, gemm_desc_b(XNtb, tw, Bt.fc, Htb, Bt.fc.out, (int)Rt, clip_mlp_epi(c), true), s));
-        GemmParams ppv = gemm_desc_mx(H8, SH, R, mlp, Bv.proj, X, vw, (int)R, EPI_BIAS_RESIDUAL, false);
-        GemmParams ppt = gemm_desc_b(Htb, Bt.fc.out, Bt.proj, Xt, tw, (int)Rt, EPI_BIAS_RESIDUAL, false);
-        ppv.R = X; ppt.R = Xt;
-        FERN_TRY(run_gemm_b_pair(c, ppv, ppt, s));
-    }
-    for (int l = paired; l < vfull; ++l)
-        FERN_TRY(clip_block_mxmlp(c, W.vblocks[l], X, XN, QKVb, ATTb, H8, b, S, vw, cf.v_heads, 0, s, true));
-    for (int l = paired; l < cf.t_layers; ++l) FERN_TRY(clip_block_bf16(c, W.tblocks[l], Xt, XNtb, QKVtb, ATTtb, Htb, b, T, tw, cf.t_heads, 1, s));
-    FERN_TRY(vit_tail(c, X, XN, QKV, ATT, H, CLS, out_img, b, s));
-    return text_tail(c, Xt, XNt, eot, out_global, out_seq, b, s);
+    for (int l = paired; l < vfull; ++l) FERN_TRY(tower_block(c, V, l, s));
+    for (int l = paired; l < cf.t_layers; ++l) FERN_TRY(tower_block(c, T, l, s));
+    FERN_TRY(vit_tail(c, V, CLS, out_img, s));
+    return text_tail(c, T.X, T.XN, eot, out_global, out_seq, b, s);
 }
 
 // A token id outside the vocabulary cannot raise from inside a kernel (nn.Embedding does, in the reference): the embedding
@@ -1903,7 +1779,7 @@ extern "C" int fern_encode_pair(fern_ctx* c, const float* images, const int64_t*
     if (B < 0 || (B && (!images || !tokens || !out_image || (!out_global && !out_seq)))) return fail(FERN_ERR_ARG, "fern_encode_pair: bad argument");
     const fern_clip_config& cf = c->clip.cfg;
     const bool towers = cf.v_arch == 0 && cf.v_layers > 1 && cf.t_layers > 0;
-    // the mixed mode pairs when every image GEMM of a block is block-scaled (head dim a multiple of 32: clip_block_mxmlp) and the text GEMMs
+    // the mixed mode pairs when every image GEMM of a block is block-scaled (head dim a multiple of 32: tower_forms) and the text GEMMs
     // meet the bf16 family's k tiling
     const bool pair_mx = towers && c->precision == FERN_PREC_MX8_IMG && (cf.v_width / cf.v_heads) % 32 == 0 && cf.v_width % 128 == 0 &&
                          cf.v_mlp % 128 == 0 && cf.t_width % 32 == 0 && cf.t_mlp % 32 == 0;
@@ -1924,7 +1800,7 @@ extern "C" int fern_encode_pair(fern_ctx* c, const float* images, const int64_t*
     for (int o = 0; o < B; o += CH) {
         const int m = std::min(CH, B - o);
         FERN_TRY(ws_begin(c, s));
-        FERN_TRY((pair_mx ? pair_chunk_mximg : pair_chunk)(c, images + o * img_sz, out_image + (long)o * cf.embed_dim, tokens + (long)o * cf.context_length,
+        FERN_TRY(pair_chunk(c, images + o * img_sz, out_image + (long)o * cf.embed_dim, tokens + (long)o * cf.context_length,
                             out_global ? out_global + (long)o * cf.embed_dim : nullptr,
                             out_seq ? out_seq + (long)o * cf.context_length * cf.embed_dim : nullptr, m, s));
     }

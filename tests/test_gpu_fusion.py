@@ -527,3 +527,29 @@ def test_encode_pair_is_bit_identical_to_the_two_encoder_calls(cfg_name, b, prec
     with pytest.raises(ValueError):
         eng.encode_pair(imgs, toks[:-1])
     eng.close()
+
+
+@pytest.mark.parametrize("precision", ["fp32", "mx8img"])
+@pytest.mark.parametrize("v_layers,t_layers", [(4, 1), (2, 3)])
+def test_encode_pair_walks_the_unpaired_tail_layers(v_layers, t_layers, precision):
+    """Towers of unequal depth: fern_encode_pair pairs the layers both towers have and walks the deeper tower's remaining blocks alone
+    (4 + 1: three full image blocks, one paired, an image tail of two; 2 + 3: one paired, a text tail of two), in the fp32 data flow and in
+    the mixed mode (tiny-w256: widths that are multiples of 128, head_dim 64, so mx8img pairs).  Bit for bit the two encoder calls, on the
+    first call (which tunes) and the second (which may take the one-launch form), with and without the seq output."""
+    from dataclasses import replace
+    cfg = replace(synth.CLIP_CONFIGS["tiny-w256"], v_layers=v_layers, t_layers=t_layers)
+    eng = FernEngine("cuda:0")
+    eng.load_tensors(synth.clip_state_dict(cfg, seed=4))
+    eng.finalize_clip(cfg)
+    eng.set_precision(precision)
+    b = 3
+    imgs = torch.from_numpy(synth.images(b, cfg, 11)).cuda()
+    toks = torch.from_numpy(synth.captions(b, cfg, 11)).cuda()
+    ref_i = eng.encode_image(imgs)
+    ref_g, ref_s = eng.encode_text(toks)
+    for rep in range(2):
+        pi, pg, ps = eng.encode_pair(imgs, toks)
+        assert torch.equal(pi, ref_i) and torch.equal(pg, ref_g) and torch.equal(ps, ref_s), rep
+    pi, pg, ps = eng.encode_pair(imgs, toks, want_seq=False)
+    assert ps is None and torch.equal(pi, ref_i) and torch.equal(pg, eng.encode_text(toks, want_seq=False)[0])
+    eng.close()
