@@ -1997,6 +1997,49 @@ static int rank_strategy_for(const fern_ctx* c, int B, int64_t N, int D) {
     return best;
 }
 
+// One query chunk (m <= kRankQueryChunk) of the DENSE form: the bf16 sweep stores its [m, N] scores (and tile maxima), one kernel per query
+// selects, rescores and ranks.  rt != null (fern_sim_topk_filtered; mask / value at the chunk's first query): the sweep masks ineligible
+// (query, row) pairs to -inf, the exact fallbacks apply the same predicate -- the select kernels run as they are on the masked rows.
+static int rank_dense_chunk(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, const float* meta, int m, int64_t N,
+                            int D, int K, float* out_scores, int32_t* out_idx, int64_t idx_offset, const int32_t* ex, const RowTags* rt,
+                            hipStream_t s) {
+    const long QBLK2 = (D == 64 || D == 128 || D == 256 || D == 512) ? 128 : 64;
+    const long ld = (N + 31) & ~31L, ldt = (((N + 31) >> 5) + 3) & ~3L;      // whole 32-row tiles; one maximum per tile
+    // the sweep leaves tile maxima for the select kernel when it runs one 64-query block per launch; two-block sweeps (65..128
+    // queries, D a power of two) have no registers for it: kept below 131 072 rows, where walking the rows costs less than a second
+    // gallery pass
+    const long QBLK = (m > 64 && N < 131072) ? QBLK2 : 64;
+    const bool tiles = QBLK == 64 && N >= 16384;
+    const int groups = (int)std::min<long>(256, std::max<long>(1, (N + 4095) / 4096));
+    float *approx, *tmax; unsigned long long *thr, *partial; int *flags, *state;
+    FERN_TRY(ws_get(c, (size_t)m * ld, &approx));
+    FERN_TRY(ws_get(c, (size_t)m * ldt, &tmax));
+    FERN_TRY(ws_get(c, (size_t)m, &thr));
+    FERN_TRY(ws_get(c, (size_t)4, &flags));
+    FERN_TRY(ws_get(c, (size_t)2 * m, &state));
+    FERN_TRY(ws_get(c, (size_t)m * groups * 64, &partial));
+    StageTimer st(c, s);
+    st.sweep_begin();
+    for (long b0 = 0; b0 < m; b0 += QBLK) {
+        const int mb = (int)std::min<long>(QBLK, m - b0);
+        const RowTags rb = rt ? RowTags{rt->tags, rt->mask + b0, rt->value + b0} : RowTags{nullptr, nullptr, nullptr};
+        HIP_TRY(launch_sweep_bf16(q + b0 * D, gallery_bf16, approx + b0 * ld, ld, mb, N, D, N, 1, nullptr, nullptr, s,
+                                  b0 == 0 ? flags : nullptr, tiles ? tmax + b0 * ldt : nullptr, ldt, rt ? &rb : nullptr));
+        // bytes this kernel moves: the bf16 copy once, the queries, its [mb, N] fp32 scores out
+        st.sweep_end((double)N * D * 2 + (double)mb * D * 4 + (double)mb * N * 4);
+    }
+    // small galleries: a query without room is ranked by its own workgroup inside the kernel (one CU streams <= 128 MB of fp32 rows:
+    // <= ~2 ms in a case that almost never happens) and the gated exact-pass launch -- ~4.5 us of every call -- is not made
+    const bool inline_exact = (double)N * D * 4 <= 128e6;
+    HIP_TRY(launch_topk_dense_rescore(approx, ld, N, q, gallery, D, meta, m, K, ex, idx_offset, idx_offset, out_scores,
+                                      out_idx, thr, flags, state, state + m, s, inline_exact ? 1 : 0, tiles ? tmax : nullptr, ldt, rt));
+    if (!inline_exact)
+        HIP_TRY(launch_rank_exact(q, gallery, 0, m, N, D, K, state, thr, ex, idx_offset, idx_offset, partial, groups, state + m,
+                                  out_scores, out_idx, flags, s, rt));
+    st.commit(m, (int)N, D);
+    return FERN_OK;
+}
+
 extern "C" int fern_rank_set_strategy(fern_ctx* c, int strategy) {
     if (!c || strategy < FERN_RANK_AUTO || strategy > FERN_RANK_DENSE) return fail(FERN_ERR_ARG, "fern_rank_set_strategy: unknown strategy");
     c->rank_strategy = strategy;
@@ -2022,38 +2065,8 @@ extern "C" int fern_sim_topk_prefiltered(fern_ctx* c, const float* q, const floa
         const int32_t* ex = exclude_idx ? exclude_idx + o : nullptr;
         FERN_TRY(ws_begin(c, s));
         if (strategy == FERN_RANK_DENSE) {
-            const long ld = (N + 31) & ~31L, ldt = (((N + 31) >> 5) + 3) & ~3L;      // whole 32-row tiles; one maximum per tile
-            // the sweep leaves tile maxima for the select kernel when it runs one 64-query block per launch; two-block sweeps (65..128
-            // queries, D a power of two) have no registers for it: kept below 131 072 rows, where walking the rows costs less than a second
-            // gallery pass
-            const long QBLK = (m > 64 && N < 131072) ? QBLK2 : 64;
-            const bool tiles = QBLK == 64 && N >= 16384;
-            const int groups = (int)std::min<long>(256, std::max<long>(1, (N + 4095) / 4096));
-            float *approx, *tmax; unsigned long long *thr, *partial; int *flags, *state;
-            FERN_TRY(ws_get(c, (size_t)m * ld, &approx));
-            FERN_TRY(ws_get(c, (size_t)m * ldt, &tmax));
-            FERN_TRY(ws_get(c, (size_t)m, &thr));
-            FERN_TRY(ws_get(c, (size_t)4, &flags));
-            FERN_TRY(ws_get(c, (size_t)2 * m, &state));
-            FERN_TRY(ws_get(c, (size_t)m * groups * 64, &partial));
-            StageTimer st(c, s);
-            st.sweep_begin();
-            for (long b0 = 0; b0 < m; b0 += QBLK) {
-                const int mb = (int)std::min<long>(QBLK, m - b0);
-                HIP_TRY(launch_sweep_bf16(q + (o + b0) * D, gallery_bf16, approx + b0 * ld, ld, mb, N, D, N, 1, nullptr, nullptr, s,
-                                          b0 == 0 ? flags : nullptr, tiles ? tmax + b0 * ldt : nullptr, ldt));
-                // bytes this kernel moves: the bf16 copy once, the queries, its [mb, N] fp32 scores out
-                st.sweep_end((double)N * D * 2 + (double)mb * D * 4 + (double)mb * N * 4);
-            }
-            // small galleries: a query without room is ranked by its own workgroup inside the kernel (one CU streams <= 128 MB of fp32 rows:
-            // <= ~2 ms in a case that almost never happens) and the gated exact-pass launch -- ~4.5 us of every call -- is not made
-            const bool inline_exact = (double)N * D * 4 <= 128e6;
-            HIP_TRY(launch_topk_dense_rescore(approx, ld, N, q + o * D, gallery, D, meta, m, K, ex, idx_offset, idx_offset, out_scores + o * K,
-                                              out_idx + o * K, thr, flags, state, state + m, s, inline_exact ? 1 : 0, tiles ? tmax : nullptr, ldt));
-            if (!inline_exact)
-                HIP_TRY(launch_rank_exact(q + o * D, gallery, 0, m, N, D, K, state, thr, ex, idx_offset, idx_offset, partial, groups, state + m,
-                                          out_scores + o * K, out_idx + o * K, flags, s));
-            st.commit(m, (int)N, D);
+            FERN_TRY(rank_dense_chunk(c, q + o * D, gallery, gallery_bf16, meta, m, N, D, K, out_scores + o * K, out_idx + o * K, idx_offset, ex,
+                                      nullptr, s));
             continue;
         }
         RankPlan P;
@@ -2109,22 +2122,25 @@ extern "C" int fern_topk_merge(fern_ctx* c, const float* scores, const int32_t* 
 // Deep ranking (include/fern.h: fern_sim_topk_deep), per query chunk: scores of every row into a [m, ld] workspace (exact: the fp32 MFMA
 // chain; pre-filtered / bf16: the bf16 sweep's store form), one select kernel per query (topk_deep.hip), then the gated exact rows
 // (pre-filter only) and the gated radix-select fallback for the queries the select kernel had no room for.  Nothing is read back.
-extern "C" int fern_sim_topk_deep(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, const float* meta, int B,
-                                  int64_t N, int D, int K, float* out_scores, int32_t* out_idx, int64_t idx_offset, const int32_t* exclude_idx,
-                                  void* stream) {
-    if (K < 1 || K > 1024) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: need 1<=K<=1024");
-    if (B < 0 || N < 0 || D <= 0 || D % 32) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: need B >= 0, N >= 0, D % 32 == 0");
-    if (!gallery && !gallery_bf16) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: gallery and gallery_bf16 are both NULL");
-    if (B && (!q || !out_scores || !out_idx)) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: NULL argument");
-    if (gallery && gallery_bf16 && !meta) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: the pre-filtered form needs meta from fern_gallery_prepare");
+// rt != null (fern_sim_topk_filtered): both score producers store -inf for ineligible (query, row) pairs -- the gated rewrite of flagged
+// rows too -- and rows scoring -inf take no place in the select kernel (never collected, so never rescored) or in the radix fallback.
+static int sim_topk_deep_impl(const char* fn_name, fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, const float* meta,
+                              int B, int64_t N, int D, int K, float* out_scores, int32_t* out_idx, int64_t idx_offset, const int32_t* exclude_idx,
+                              const RowTags* rt, void* stream) {
+    const std::string fn(fn_name);
+    if (K < 1 || K > 1024) return fail(FERN_ERR_ARG, fn + ": need 1<=K<=1024");
+    if (B < 0 || N < 0 || D <= 0 || D % 32) return fail(FERN_ERR_ARG, fn + ": need B >= 0, N >= 0, D % 32 == 0");
+    if (!gallery && !gallery_bf16) return fail(FERN_ERR_ARG, fn + ": gallery and gallery_bf16 are both NULL");
+    if (B && (!q || !out_scores || !out_idx)) return fail(FERN_ERR_ARG, fn + ": NULL argument");
+    if (gallery && gallery_bf16 && !meta) return fail(FERN_ERR_ARG, fn + ": the pre-filtered form needs meta from fern_gallery_prepare");
     const bool sweep_ok = D % 64 == 0 && D <= 768;      // the bf16 sweep's shapes
-    if (!gallery && !sweep_ok) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: a bf16-only gallery needs D % 64 == 0, D <= 768");
-    if (N > 0x7FFFFFF0LL) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: N too large for int32 indices");
+    if (!gallery && !sweep_ok) return fail(FERN_ERR_ARG, fn + ": a bf16-only gallery needs D % 64 == 0, D <= 768");
+    if (N > 0x7FFFFFF0LL) return fail(FERN_ERR_ARG, fn + ": N too large for int32 indices");
     const long ld = std::max<long>(4, (N + 3) & ~3L);
     // queries per chunk: the [m, ld] fp32 score matrix stays within the dense form's budget (rank_strategy_for)
     const long chunk = std::min<long>((long)kRankQueryChunk, (long)(1.1e9 / ((double)ld * 4)));
-    if (chunk < 1) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: one query's score row exceeds the 1.1 GB workspace budget");
-    if (!c) return fail(FERN_ERR_ARG, "fern_sim_topk_deep: ctx is NULL");
+    if (chunk < 1) return fail(FERN_ERR_ARG, fn + ": one query's score row exceeds the 1.1 GB workspace budget");
+    if (!c) return fail(FERN_ERR_ARG, fn + ": ctx is NULL");
     enum { EXACT, PREFILTERED, BF16 } form = !gallery ? BF16 : (gallery_bf16 && sweep_ok && c->rank_strategy != FERN_RANK_PLAIN) ? PREFILTERED : EXACT;
     if (N == 0) form = EXACT;                        // no scores to compute: the select kernel writes the -inf / -1 rows
     HIP_TRY(hipSetDevice(c->device));
@@ -2139,15 +2155,18 @@ extern "C" int fern_sim_topk_deep(fern_ctx* c, const float* q, const float* gall
         FERN_TRY(ws_get(c, (size_t)4, &flags));
         FERN_TRY(ws_get(c, (size_t)m, &state));
         const float* qo = q + o * D;
+        const RowTags ro = rt ? RowTags{rt->tags, rt->mask + o, rt->value + o} : RowTags{nullptr, nullptr, nullptr};
         StageTimer st(c, s);
         st.sweep_begin();
         if (form == EXACT) {
-            HIP_TRY(launch_deep_exact_scores(qo, gallery, m, N, D, S, ld, flags, state, 0, s));      // also zeroes flags
+            HIP_TRY(launch_deep_exact_scores(qo, gallery, m, N, D, S, ld, flags, state, 0, s, &ro));      // also zeroes flags
             st.sweep_end((double)N * D * 4 + (double)m * D * 4 + (double)m * N * 4);
         } else {
             for (long b0 = 0; b0 < m; b0 += 64) {
                 const int mb = (int)std::min<long>(64, m - b0);
-                HIP_TRY(launch_sweep_bf16(qo + b0 * D, gallery_bf16, S + b0 * ld, ld, mb, N, D, N, 1, nullptr, nullptr, s, b0 == 0 ? flags : nullptr));
+                const RowTags rb{ro.tags, ro.tags ? ro.mask + b0 : nullptr, ro.tags ? ro.value + b0 : nullptr};
+                HIP_TRY(launch_sweep_bf16(qo + b0 * D, gallery_bf16, S + b0 * ld, ld, mb, N, D, N, 1, nullptr, nullptr, s, b0 == 0 ? flags : nullptr, nullptr, 0,
+                                          &rb));
                 st.sweep_end((double)N * D * 2 + (double)mb * D * 4 + (double)mb * N * 4);
             }
         }
@@ -2155,10 +2174,48 @@ extern "C" int fern_sim_topk_deep(fern_ctx* c, const float* q, const float* gall
         HIP_TRY(launch_deep_select(S, ld, N, m, K, pre ? qo : nullptr, pre ? meta : nullptr, pre ? gallery : nullptr, D, ex, idx_offset,
                                    out_scores + o * K, out_idx + o * K, flags, state, s));
         if (N > 0) {
-            if (pre) HIP_TRY(launch_deep_exact_scores(qo, gallery, m, N, D, S, ld, flags, state, 1, s));
+            if (pre) HIP_TRY(launch_deep_exact_scores(qo, gallery, m, N, D, S, ld, flags, state, 1, s, &ro));
             HIP_TRY(launch_deep_fallback(S, ld, N, m, K, ex, idx_offset, out_scores + o * K, out_idx + o * K, flags, state, s));
         }
         st.commit(m, (int)N, D);
+    }
+    return FERN_OK;
+}
+
+extern "C" int fern_sim_topk_deep(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, const float* meta, int B,
+                                  int64_t N, int D, int K, float* out_scores, int32_t* out_idx, int64_t idx_offset, const int32_t* exclude_idx,
+                                  void* stream) {
+    return sim_topk_deep_impl("fern_sim_topk_deep", c, q, gallery, gallery_bf16, meta, B, N, D, K, out_scores, out_idx, idx_offset, exclude_idx, nullptr,
+                              stream);
+}
+
+// Filtered ranking (include/fern.h: fern_sim_topk_filtered): the exact ranking of the rows that are eligible for each query.  Two forms,
+// the same bits from both:
+//   masked dense form   K <= 64, a prepared gallery (fp32 + bf16 copy + meta), a shape the bf16 sweep takes, the dense form's score budget,
+//                       strategy not PLAIN: rank_dense_chunk with the row filter -- the masked store-form sweep + the tiles / dense select kernels;
+//   deep stage          everything else: sim_topk_deep_impl on masked rows (exact, pre-filtered or bf16 by the pointers given).
+extern "C" int fern_sim_topk_filtered(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, const float* meta, int B,
+                                      int64_t N, int D, int K, float* out_scores, int32_t* out_idx, int64_t idx_offset, const int32_t* exclude_idx,
+                                      const uint32_t* tags, const uint32_t* mask, const uint32_t* value, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_sim_topk_filtered: ctx is NULL");
+    if (K < 1 || K > 1024) return fail(FERN_ERR_ARG, "fern_sim_topk_filtered: need 1<=K<=1024");
+    if (!tags) return fail(FERN_ERR_ARG, "fern_sim_topk_filtered: tags is NULL (unfiltered callers use fern_sim_topk_deep and its siblings)");
+    if (B > 0 && (!mask || !value)) return fail(FERN_ERR_ARG, "fern_sim_topk_filtered: mask or value is NULL");
+    const RowTags rt{tags, mask, value};
+    const bool sweep_ok = D > 0 && D % 64 == 0 && D <= 768;
+    const bool dense = K <= 64 && B > 0 && N > 0 && N <= 0x7FFFFFF0LL && gallery && gallery_bf16 && meta && q && out_scores && out_idx && sweep_ok &&
+                       c->rank_strategy != FERN_RANK_PLAIN && (double)std::min<long>(B, (long)kRankQueryChunk) * N * 4 <= 1.1e9;
+    if (!dense)
+        return sim_topk_deep_impl("fern_sim_topk_filtered", c, q, gallery, gallery_bf16, meta, B, N, D, K, out_scores, out_idx, idx_offset, exclude_idx,
+                                  &rt, stream);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    for (long o = 0; o < B; o += (long)kRankQueryChunk) {
+        const int m = (int)std::min<long>((long)kRankQueryChunk, B - o);
+        const RowTags ro{tags, mask + o, value + o};
+        FERN_TRY(ws_begin(c, s));
+        FERN_TRY(rank_dense_chunk(c, q + o * D, gallery, gallery_bf16, meta, m, N, D, K, out_scores + o * K, out_idx + o * K, idx_offset,
+                                  exclude_idx ? exclude_idx + o : nullptr, &ro, s));
     }
     return FERN_OK;
 }
@@ -2222,16 +2279,19 @@ extern "C" int fern_rank_keys(fern_ctx* c, const float* q, const float* gallery,
     return FERN_OK;
 }
 
-extern "C" int fern_rank_count(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
-                               const uint64_t* keys_in, int m, int64_t idx_offset, const int32_t* exclude_idx, int32_t* out_count, void* stream) {
-    FERN_TRY(rank_shape_check("fern_rank_count", c, q, gallery, gallery_bf16, B, N, D, m));
-    if (B && (!keys_in || !out_count)) return fail(FERN_ERR_ARG, "fern_rank_count: NULL argument");
+// rt != null (fern_rank_count_filtered): a row that is ineligible for a query carries key 0 for it, like the excluded row.
+static int rank_count_impl(const char* fn_name, fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                           const uint64_t* keys_in, int m, int64_t idx_offset, const int32_t* exclude_idx, int32_t* out_count, const RowTags* rt,
+                           void* stream) {
+    const std::string fn(fn_name);
+    FERN_TRY(rank_shape_check(fn_name, c, q, gallery, gallery_bf16, B, N, D, m));
+    if (B && (!keys_in || !out_count)) return fail(FERN_ERR_ARG, fn + ": NULL argument");
     const bool bf16_form = !gallery && N > 0;
     const long ld = std::max<long>(4, (N + 3) & ~3L);
     long chunk = (long)kRankQueryChunk;
     if (bf16_form) {      // queries per chunk: the [m, ld] fp32 score matrix stays within the dense form's budget, whole 64-query sweep blocks
         chunk = std::min<long>(chunk, (long)(1.1e9 / ((double)ld * 4)));
-        if (chunk < 1) return fail(FERN_ERR_ARG, "fern_rank_count: one query's score row exceeds the 1.1 GB workspace budget");
+        if (chunk < 1) return fail(FERN_ERR_ARG, fn + ": one query's score row exceeds the 1.1 GB workspace budget");
         if (chunk > 64) chunk &= ~63L;
     }
     HIP_TRY(hipSetDevice(c->device));
@@ -2246,7 +2306,8 @@ extern "C" int fern_rank_count(fern_ctx* c, const float* q, const float* gallery
         FERN_TRY(ws_get(c, (size_t)RANKC_P * mq * RANKC_T, &partial));
         const size_t partial_bytes = (size_t)RANKC_P * mq * RANKC_T * sizeof(int);
         auto pass = [&](int t0) {
-            return RankCount{keys + o * m + t0, partial, ex, (long)idx_offset, (long)idx_offset, m, std::min(RANKC_T, m - t0)};
+            return RankCount{keys + o * m + t0, partial, ex, (long)idx_offset, (long)idx_offset, m, std::min(RANKC_T, m - t0),
+                             rt ? RowTags{rt->tags, rt->mask + o, rt->value + o} : RowTags{nullptr, nullptr, nullptr}};
         };
         if (!bf16_form) {
             int stage;
@@ -2268,7 +2329,9 @@ extern "C" int fern_rank_count(fern_ctx* c, const float* q, const float* gallery
         st.sweep_begin();
         for (long b0 = 0; b0 < mq; b0 += 64) {
             const int mb = (int)std::min<long>(64, mq - b0);
-            HIP_TRY(launch_sweep_bf16(q + (o + b0) * D, gallery_bf16, S + b0 * ld, ld, mb, N, D, N, 1, nullptr, nullptr, s));
+            const RowTags rb = rt ? RowTags{rt->tags, rt->mask + o + b0, rt->value + o + b0} : RowTags{nullptr, nullptr, nullptr};
+            HIP_TRY(launch_sweep_bf16(q + (o + b0) * D, gallery_bf16, S + b0 * ld, ld, mb, N, D, N, 1, nullptr, nullptr, s, nullptr, nullptr, 0,
+                                      rt ? &rb : nullptr));
             st.sweep_end((double)N * D * 2 + (double)mb * D * 4 + (double)mb * N * 4);
         }
         for (int t0 = 0; t0 < m; t0 += RANKC_T) {
@@ -2280,6 +2343,21 @@ extern "C" int fern_rank_count(fern_ctx* c, const float* q, const float* gallery
         st.commit(mq, (int)N, D);
     }
     return FERN_OK;
+}
+
+extern "C" int fern_rank_count(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                               const uint64_t* keys_in, int m, int64_t idx_offset, const int32_t* exclude_idx, int32_t* out_count, void* stream) {
+    return rank_count_impl("fern_rank_count", c, q, gallery, gallery_bf16, B, N, D, keys_in, m, idx_offset, exclude_idx, out_count, nullptr, stream);
+}
+
+extern "C" int fern_rank_count_filtered(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                                        const uint64_t* keys_in, int m, int64_t idx_offset, const int32_t* exclude_idx, int32_t* out_count,
+                                        const uint32_t* tags, const uint32_t* mask, const uint32_t* value, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_rank_count_filtered: ctx is NULL");
+    if (!tags) return fail(FERN_ERR_ARG, "fern_rank_count_filtered: tags is NULL (unfiltered callers use fern_rank_count)");
+    if (B > 0 && (!mask || !value)) return fail(FERN_ERR_ARG, "fern_rank_count_filtered: mask or value is NULL");
+    const RowTags rt{tags, mask, value};
+    return rank_count_impl("fern_rank_count_filtered", c, q, gallery, gallery_bf16, B, N, D, keys_in, m, idx_offset, exclude_idx, out_count, &rt, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

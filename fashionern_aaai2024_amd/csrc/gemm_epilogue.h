@@ -267,6 +267,9 @@ __device__ __forceinline__ void filter_epilogue(const GemmParams& p, f32x16 (&ac
 // 8 (r >> 2) + 4 lh, lane l31 = gallery row -- and target, ONE 64-lane ballot of "this row's key is greater" gives two popcounts: the
 // counts of the lh = 0 and lh = 1 queries.  They stay in SGPRs over the wave's TN tiles; lanes 0..15 then add the (2 queries x 8
 // targets) counts of the register with one vector atomic.  Rows >= N and the excluded row carry key 0, which is greater than nothing.
+// A per-query row filter (rc.rt.tags != null, kernels.h: RowTags; a kernel-uniform branch): the workgroup also stages the tags of its
+// BN gallery rows and its BM queries' (mask, value) pairs next to the keys (4 BN + 8 BM bytes more: still inside the two buffers), and
+// a row that is ineligible for the register's query carries key 0 as well.
 template <int BM, int BN, int WM, int WN, int TM, int TN>
 __device__ __forceinline__ void rank_count_epilogue(const GemmParams& p, f32x16 (&acc)[TM][TN], int bm, int bn, int wm, int wn, int l31, int lh,
                                                     float* lds) {
@@ -283,6 +286,22 @@ __device__ __forceinline__ void rank_count_epilogue(const GemmParams& p, f32x16 
         const long ex = (rc.exclude && qi < p.M) ? (long)rc.exclude[qi] - rc.exclude_off : -1;
         sex[i] = (ex >= 0 && ex < p.N) ? (int)ex : -1;
     }
+    const bool tagged = rc.rt.tags != nullptr;                // (kernel-uniform)
+    unsigned* smask = reinterpret_cast<unsigned*>(sex + BM);  // [BM] masks, [BM] values, [BN] tags
+    unsigned* svalue = smask + BM;
+    unsigned* stag = svalue + BM;
+    static_assert(BM * (RANKC_T * 8 + 4 + 8) + BN * 4 <= 128 * (BM + BN), "the staged keys, filters and tags overlay the tile buffers");
+    if (tagged) {
+        for (int i = threadIdx.x; i < BM; i += blockDim.x) {
+            const int qi = bm * BM + i;
+            smask[i] = qi < p.M ? rc.rt.mask[qi] : 0u;
+            svalue[i] = qi < p.M ? rc.rt.value[qi] : 1u;
+        }
+        for (int i = threadIdx.x; i < BN; i += blockDim.x) {
+            const long n = (long)bn * BN + i;
+            stag[i] = rc.rt.tags[n < p.N ? n : p.N - 1];
+        }
+    }
     __syncthreads();
     const int row_w = bm * BM + wm * WM;
     const int col_w = bn * BN + wn * WN;
@@ -290,10 +309,11 @@ __device__ __forceinline__ void rank_count_epilogue(const GemmParams& p, f32x16 
     const int lane = l31 + 32 * lh;
     int* part = rc.partial + (long)((col_w >> 5) & (RANKC_P - 1)) * p.M * RANKC_T;
     int nrow[TN];
-    unsigned klo[TN];
+    unsigned klo[TN], tag[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int n = col_w + j * 32 + l31;
+        tag[j] = tagged ? stag[wn * WN + j * 32 + l31] : 0u;
         nrow[j] = n < p.N ? n : -2;                           // -2: matches no excluded row, and the key is forced to 0 below
         klo[j] = 0xFFFFFFFFu - (unsigned)((long)n + rc.idx_offset);
     }
@@ -306,10 +326,11 @@ __device__ __forceinline__ void rank_count_epilogue(const GemmParams& p, f32x16 
             const int ru = (r & 3) + 8 * (r >> 2);
             const int ql = wm * WM + i * 32 + ru + 4 * lh;    // this lane half's query inside the workgroup's BM
             const int ex = sex[ql];
+            const unsigned fm = tagged ? smask[ql] : 0u, fv = tagged ? svalue[ql] : 0u;      // untagged: every row passes (0 & 0 == 0)
             unsigned long long key[TN];
 #pragma unroll
             for (int j = 0; j < TN; ++j)
-                key[j] = (nrow[j] >= 0 && nrow[j] != ex) ? (((unsigned long long)orderable(acc[i][j][r]) << 32) | klo[j]) : 0ull;
+                key[j] = (nrow[j] >= 0 && nrow[j] != ex && row_eligible(tag[j], fm, fv)) ? (((unsigned long long)orderable(acc[i][j][r]) << 32) | klo[j]) : 0ull;
             int mine = 0;
 #pragma unroll
             for (int t = 0; t < RANKC_T; ++t) {

@@ -73,6 +73,18 @@ struct TopkFilter {
     long exclude_off;                     // ... as a global index: the local row is exclude[q] - exclude_off
     int cap;                              // entries per list (<= 64: the select kernel reads a list with one wave load)
 };
+// ---- per-query gallery row filter (include/fern.h: fern_sim_topk_filtered, fern_rank_count_filtered) -------------------------------
+// Gallery row n is eligible for query b iff (tags[n] & mask[b]) == value[b].  tags == null: no filter, every row is eligible.
+// INVARIANT of every kernel that takes one: an ineligible (query, row) pair is scored -inf where scores are stored and carries key 0
+// where keys are compared, so it is never collected, never reaches rescore.h and never leaves a fallback.
+struct RowTags {
+    const unsigned* tags;                 // [N] one tag per gallery row (null: unfiltered)
+    const unsigned* mask;                 // [B]
+    const unsigned* value;                // [B]
+};
+#ifdef __HIPCC__
+__device__ __forceinline__ bool row_eligible(unsigned tag, unsigned mask, unsigned value) { return (tag & mask) == value; }
+#endif
 // ---- exact target ranks: counting sweep (EPI_RANK_COUNT of the fp32 GEMM, rank.hip for the bf16 form) -----------------------------
 // A rank is a count: rows whose key (make_key: score descending, index ascending) is greater than the target's key.  One gallery pass
 // serves RANKC_T target keys per query; every wave adds its tile counts to one of RANKC_P partial counter sets (chosen by its column
@@ -87,6 +99,7 @@ struct RankCount {
     long exclude_off;                     // ... as a global index: the local row is exclude[q] - exclude_off
     long idx_offset;                      // key index of local row n is n + idx_offset
     int kstride, nt;                      // 1 <= nt <= RANKC_T
+    RowTags rt;                           // rows that are ineligible for a query are not counted for it (rt.tags null: every row counts)
 };
 // sample column c -> gallery row: one row out of every run of R consecutive rows, at a hashed offset inside the run (a fixed
 // stride would alias with periodic structure in the gallery order); monotonic in c, so sample order = gallery order
@@ -409,7 +422,10 @@ hipError_t launch_gallery_prepare(const float* x, unsigned short* y, long n, int
 // zero_flags (sample form only, may be null): two ints the first workgroup zeroes (the ranking stage's overflow flags, when no bound
 // kernel runs before the selection).
 hipError_t launch_sweep_bf16(const float* q, const unsigned short* g, float* scores, long ld, int B, long N, int D, long S, int R,
-                             const TopkFilter* filt, const int* gate, hipStream_t s, int* zero_flags = nullptr, float* tmax = nullptr, long ldt = 0);
+                             const TopkFilter* filt, const int* gate, hipStream_t s, int* zero_flags = nullptr, float* tmax = nullptr, long ldt = 0,
+                             const RowTags* rt = nullptr);
+// rt (store-all form only: S = N, R = 1): the stored score of an ineligible (query, row) pair is -inf, and a tile maximum is the maximum
+// over the query's eligible rows (-inf: none).  rt->mask / rt->value point at the FIRST query of this launch.
 
 // ---- top-K (topk.hip) ------------------------------------------------------------------------
 // Fused sweep, step 2: per query the K-th best key of the sample scores [B, ld] (S valid columns; column c is gallery row
@@ -434,7 +450,9 @@ hipError_t launch_topk_sample_bound(const float* scores, long ld, int B, long S,
 hipError_t launch_topk_dense_rescore(const float* approx, long ld, long N, const float* q, const float* gallery, int D, const float* meta,
                                      int B, int K, const int* exclude, long exclude_off, long idx_offset, float* out_scores,
                                      int* out_idx, unsigned long long* thr_key, int* flags, int* state, int* done, hipStream_t s, int inline_exact = 0,
-                                     const float* tmax = nullptr, long ldt = 0);
+                                     const float* tmax = nullptr, long ldt = 0, const RowTags* rt = nullptr);
+// rt (approx holds the masked sweep's scores): the inline exact ranking skips ineligible rows, and a margin that is not finite sends the
+// query to the exact ranking instead of accepting every row.
 hipError_t launch_topk_rescore(const TopkFilter& f, const float* q, const float* gallery, int D, const float* margin, int B, int K, long idx_offset,
                                float* out_scores, int* out_idx, int* flags, int* state, hipStream_t s);
 // Fused sweep, final step: exact top-K of each query's candidate list -> out (idx = row + idx_offset; unfilled: -inf / -1).
@@ -448,7 +466,7 @@ hipError_t launch_topk_rescore(const TopkFilter& f, const float* q, const float*
 hipError_t launch_rank_exact(const float* q, const void* gallery, int gallery_bf16, int B, long N, int D, int K, const int* state,
                              const unsigned long long* thr_key, const int* exclude, long exclude_off, long idx_offset,
                              unsigned long long* partial, int groups, int* done, float* out_scores, int* out_idx, const int* gate,
-                             hipStream_t s);
+                             hipStream_t s, const RowTags* rt = nullptr);
 hipError_t launch_topk_candidates(const TopkFilter& f, int B, int K, long idx_offset, float* out_scores, int* out_idx, int* flags,
                                   int* state, hipStream_t s);
 // Merge R lists [R,B,K] (score, idx) -> [B,K]
@@ -474,8 +492,9 @@ hipError_t launch_rank_finalize(const RankCount& rc, int B, int* count, int cstr
 // ---- deep top-K (topk_deep.hip): 1 <= K <= 1024 on a stored score row per query ------------------------------------------------
 // S [B, ld] fp32 = exact chain scores of B queries against an fp32 gallery (deep_exact_scores_kernel: the MFMA sequence of
 // launch_rank_exact).  gated != 0: only if flags[0] is set, only the rows of queries with state[b] != 0; gated == 0 also zeroes flags[0..3].
+// rt: the stored score of an ineligible (query, row) pair is -inf -- in the gated rewrite too -- and such rows take no place below.
 hipError_t launch_deep_exact_scores(const float* q, const float* gallery, int B, long N, int D, float* S, long ld, int* flags, const int* state,
-                                    int gated, hipStream_t s);
+                                    int gated, hipStream_t s, const RowTags* rt = nullptr);
 // Per query the top-K keys of its score row S[b] (ld % 4 == 0): bound from row-group maxima, collection, bitonic sort in LDS.  q != null:
 // S holds bf16-sweep approximations, the certified margin (meta = fern_gallery_prepare's) selects survivors that are rescored exactly from
 // the fp32 `gallery` (D % 64 == 0, D <= 768).  A query without room sets state[b] = 1 and flags[0] = 1 (flags[0] zeroed before).

@@ -101,12 +101,16 @@ __global__ __launch_bounds__(256) void rank_count_rows_kernel(const float* S, lo
 #pragma unroll
     for (int t = 0; t < RANKC_T; ++t) tk[t] = t < rc.nt ? rc.keys[(long)b * rc.kstride + t] : ~0ull;
     const long ex = rc.exclude ? (long)rc.exclude[b] - rc.exclude_off : -1;
+    // a per-query row filter (kernels.h: RowTags): the sweep stored its ineligible rows as -inf; they carry key 0 here like the excluded row
+    const bool tagged = rc.rt.tags != nullptr;
+    const unsigned fm = tagged ? rc.rt.mask[b] : 0u, fv = tagged ? rc.rt.value[b] : 0u;
     int cnt[RANKC_T];
 #pragma unroll
     for (int t = 0; t < RANKC_T; ++t) cnt[t] = 0;
     const float* row = S + (long)b * ld;
     for (long n = (long)blockIdx.x * 256 + tid; n < N; n += (long)gridDim.x * 256) {
-        const u64 key = n != ex ? make_key(row[n], (unsigned)(n + rc.idx_offset)) : 0ull;
+        const bool ok = n != ex && (!tagged || row_eligible(rc.rt.tags[n], fm, fv));
+        const u64 key = ok ? make_key(row[n], (unsigned)(n + rc.idx_offset)) : 0ull;
 #pragma unroll
         for (int t = 0; t < RANKC_T; ++t) cnt[t] += key > tk[t] ? 1 : 0;
     }

@@ -80,6 +80,15 @@ constexpr int STAGE_BYTES = ROWS_T * KSTAGE * 2;   // 4096
 // a RETURNING global atomic (~1-2 us round trip); one per finished tile stalled the wave's DMA ring and cost 40 % of the stream
 constexpr int QCAP = 128;                          // queue entries per wave (a register can add up to 64 at once)
 constexpr int QUEUE_BYTES = 4 * QCAP * 12 + 128 * 8 + 128 * 4;     // 4 waves x (key 8 B + query 4 B) + the (<= 128) bounds as keys and as floats
+// Masked store form (MASK: a per-query row filter, kernels.h: RowTags).  The filter form's queue is unused then and its place holds
+// the block's (mask, value) image -- [128] + [128] dwords -- and a TAG RING: per wave and ring slot the 64 dwords one
+// global_load_lds_dword brings (lane l31 = the tag of the tile's row l31; the upper half wave repeats it).
+constexpr int TAG_SLOT_BYTES = 256;
+constexpr int tail_bytes(int stages, bool mask) {
+    return mask && 1024 + 4 * stages * TAG_SLOT_BYTES > QUEUE_BYTES ? 1024 + 4 * stages * TAG_SLOT_BYTES : QUEUE_BYTES;
+}
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // FILTER = false: the sample pass -- tile rows are the gallery rows sample_row(c, R) of S sample columns, scores are stored
 // ([B, ld], 128-byte coalesced).  FILTER = true: the full sweep -- nothing is stored; every finished 32x32 score tile is
@@ -134,10 +143,17 @@ __device__ __forceinline__ int tile_row_max_query(int lane) {
     return (i >> 4) * 32 + (i & 3) + 8 * ((i & 15) >> 2) + 4 * (lane >> 5);
 }
 
-template <int STAGES, bool FILTER, int KCH, int QB = 1>
+// MASK (store-all form only: S = N, R = 1): an ineligible (query, row) pair becomes -inf in the accumulators BEFORE the tile maximum
+// and the score store, so everything that selects on this kernel's output sees the filtered gallery.  It is a template parameter, not
+// a run-time branch: the unfiltered instantiations keep their code and their register counts (D = 640 holds 320 fragment VGPRs), and
+// the counted s_waitcnt of the ring changes with it -- a tile's tag load travels WITH the tile's first ring stage (one more
+// global_load_lds, issued in front of that stage's four), so it is older than the stage and has landed when the stage has; the wait
+// immediate grows by the number of tag loads that are newer than the stage being consumed, and the ring depth stays what it was.
+template <int STAGES, bool FILTER, int KCH, int QB = 1, bool MASK = false>
 __global__ __launch_bounds__(256) void sweep_bf16_kernel(const float* q, const u16* g, float* scores, long ld, int B, long N, int D, long S, int R,
-                                                         TopkFilter filt, const int* gate, int* zero_flags, float* tmax, long ldt) {
+                                                         TopkFilter filt, const int* gate, int* zero_flags, float* tmax, long ldt, RowTags rt) {
     static_assert(QB == 1 || KCH > 0, "two query blocks need the register-resident form");
+    static_assert(!(MASK && FILTER), "the row filter masks stored scores: store form only");
     if (gate && *gate == 0) return;
     if (!FILTER && zero_flags && blockIdx.x == 0 && threadIdx.x == 0) { zero_flags[0] = 0; zero_flags[1] = 0; }
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
@@ -148,7 +164,8 @@ __global__ __launch_bounds__(256) void sweep_bf16_kernel(const float* q, const u
     // (their HBM round trip, ~2-4 us at C2's 33 MB burst, used to begin only after the ~4 us of query staging).
     constexpr bool OVERLAY = KCH > 0 && QB == 1;
     constexpr int QIMG = OVERLAY ? ((64 * (128 * KCH + 16) + 1023) & ~1023) : 0;
-    constexpr int EARLY_ROOM = OVERLAY ? (4 * STAGES * STAGE_BYTES + QUEUE_BYTES - QIMG) / (4 * STAGE_BYTES) : 0;
+    // (MASK: the tail behind the ring is written from the start -- tag ring -- so the image must end inside the ring)
+    constexpr int EARLY_ROOM = OVERLAY ? (4 * STAGES * STAGE_BYTES + (MASK ? 0 : QUEUE_BYTES) - QIMG) / (4 * STAGE_BYTES) : 0;
     constexpr int EARLY = !OVERLAY ? STAGES - 1 : EARLY_ROOM > STAGES - 1 ? STAGES - 1 : EARLY_ROOM;      // (ring next to the image: every slot is free)
     unsigned char* img = smem + (OVERLAY ? EARLY * 4 * STAGE_BYTES : 0);
     unsigned char* ring_base = OVERLAY ? smem : smem + ((64 * q_stride + 1023) & ~1023);
@@ -187,6 +204,12 @@ __global__ __launch_bounds__(256) void sweep_bf16_kernel(const float* q, const u
     unsigned long long* qkey = reinterpret_cast<unsigned long long*>(qbase + wave * QCAP * 12);
     int* qq = reinterpret_cast<int*>(qbase + wave * QCAP * 12 + QCAP * 8);
     int qlen = 0;                                                  // wave-uniform
+    // MASK: the same bytes hold the block's masks and values ([128] dwords each: four consecutive queries are one 16-byte read) and
+    // the waves' tag rings
+    unsigned* mk_lds = reinterpret_cast<unsigned*>(qbase);
+    unsigned* vl_lds = mk_lds + 128;
+    unsigned char* tagring = qbase + 1024 + wave * (STAGES * TAG_SLOT_BYTES);
+    int tslot_issue = 0, tslot_read = 0;                           // wave-uniform
     // append the queued survivors to their lists: one batch of returning atomics per <= 64 entries
     auto flush = [&]() {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the queue writes of every lane have landed
@@ -252,6 +275,12 @@ __global__ __launch_bounds__(256) void sweep_bf16_kernel(const float* q, const u
     }
     auto issue_next = [&]() {
         unsigned char* dst = ring + slot_issue * SLOT_BYTES;
+        if (MASK && kc_issue == 0) {      // the tile's tags, in front of its first stage (rows past the end read the last row's tag: masked by n < N)
+            const long n = t_issue * ROWS_T + l31;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rt.tags + (n < N ? n : N - 1)),
+                                             (__attribute__((address_space(3))) void*)(tagring + tslot_issue * TAG_SLOT_BYTES), 4, 0, 0);
+            tslot_issue = tslot_issue + 1 == STAGES ? 0 : tslot_issue + 1;
+        }
         if ((FILTER || R == 1) && (t_issue + 1) * ROWS_T <= (FILTER ? N : S)) {      // whole tile of consecutive rows (the full sweep; the store-all form S = N, R = 1)
             const unsigned char* base = reinterpret_cast<const unsigned char*>(g) + (t_issue * ROWS_T * D + (long)kc_issue * KSTAGE) * 2;
 #pragma unroll
@@ -320,6 +349,10 @@ __global__ __launch_bounds__(256) void sweep_bf16_kernel(const float* q, const u
             __syncthreads();
         }
     }
+    if (MASK) {      // (the tail is not under the image in this form: no barrier needed before; queries >= B match nothing)
+        if (tid < 128) { mk_lds[tid] = tid < B ? rt.mask[tid] : 0u; vl_lds[tid] = tid < B ? rt.value[tid] : 1u; }
+        __syncthreads();
+    }
     if (FILTER) {
         if (tid < 64 * QB) thr_lds[tid] = tid < B ? filt.thr_key[tid] : ~0ull;
         if (QB == 2 && tid < 128) thr_f[tid] = filter_bound(tid < B ? filt.thr_key[tid] : ~0ull);
@@ -339,7 +372,21 @@ __global__ __launch_bounds__(256) void sweep_bf16_kernel(const float* q, const u
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the slot about to be refilled has been read
         if (issued < nstages) {
             issue_next();
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (STAGES - 1)) : "memory");   // this stage landed; newer ones stay in flight
+            // this stage landed; newer ones stay in flight.  MASK with a compile-time kc: the newer loads include one tag load per tile
+            // whose first stage is among the STAGES - 1 newer stages (run-time kc: the plain count, which waits for a few loads more)
+            constexpr int W0 = 4 * (STAGES - 1);
+            const int extra = (MASK && KCH > 0) ? (kc + STAGES - 1) / (KCH > 0 ? KCH : 1) : 0;
+            switch (extra) {
+                case 1: wait_vmcnt<W0 + 1>(); break;
+                case 2: wait_vmcnt<W0 + 2>(); break;
+                case 3: wait_vmcnt<W0 + 3>(); break;
+                case 4: wait_vmcnt<W0 + 4>(); break;
+                case 5: wait_vmcnt<W0 + 5>(); break;
+                case 6: wait_vmcnt<W0 + 6>(); break;
+                case 7: wait_vmcnt<W0 + 7>(); break;
+                case 8: wait_vmcnt<W0 + 8>(); break;
+                default: wait_vmcnt<W0>(); break;
+            }
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -362,6 +409,34 @@ __global__ __launch_bounds__(256) void sweep_bf16_kernel(const float* q, const u
     const int my_q = tile_row_max_query(lane);
     auto tile_done = [&](long t) {
         const long n = t * ROWS_T + l31;
+        if (MASK) {      // ineligible (query, row) pairs -> -inf, before the tile maximum and the store
+            const unsigned tag = *reinterpret_cast<const unsigned*>(tagring + tslot_read * TAG_SLOT_BYTES + l31 * 4);
+            tslot_read = tslot_read + 1 == STAGES ? 0 : tslot_read + 1;
+            // Two steps, for registers (D = 640 has 16 to spare): a ROLLED loop turns the block's filters into one eligibility bit per
+            // accumulator register (four consecutive queries = one 16-byte read of masks, one of values: group gq holds queries
+            // 8 gq + 4 lh .. + 3, i.e. registers 4 (gq & 3) .. + 3 of accumulator gq >> 2), then the bits select.  Unrolled, the compiler
+            // kept all 2 x 8 QB reads live at once (50 VGPRs, spills in the two-block forms).
+            unsigned elig[QB];
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb) elig[qb] = 0u;
+#pragma unroll
+            for (int qb = 0; qb < QB; ++qb) {
+#pragma unroll 1
+                for (int gq = 0; gq < 8; ++gq) {
+                    const uint4 m4 = *reinterpret_cast<const uint4*>(mk_lds + qb * 64 + 8 * gq + 4 * lh);
+                    const uint4 v4 = *reinterpret_cast<const uint4*>(vl_lds + qb * 64 + 8 * gq + 4 * lh);
+                    const unsigned b4 = (row_eligible(tag, m4.x, v4.x) ? 1u : 0u) | (row_eligible(tag, m4.y, v4.y) ? 2u : 0u) |
+                                        (row_eligible(tag, m4.z, v4.z) ? 4u : 0u) | (row_eligible(tag, m4.w, v4.w) ? 8u : 0u);
+                    elig[qb] |= b4 << (4 * gq);
+                }
+                elig[qb] = n < N ? elig[qb] : 0u;
+            }
+#pragma unroll
+            for (int tm = 0; tm < 2 * QB; ++tm)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    acc[tm][r] = ((elig[tm >> 1] >> ((tm & 1) * 16 + r)) & 1u) ? acc[tm][r] : -__builtin_inff();
+        }
         if (!FILTER && QB == 1 && tmax) {                            // (rows past the gallery's end were loaded as its last row: the maximum is unchanged;
                                                                      //  QB = 2 has no registers left for the reduction: the launcher refuses it)
 #pragma unroll
@@ -438,14 +513,15 @@ hipError_t launch_bf16_to_f32(const unsigned short* x, float* y, long n, hipStre
     return hipGetLastError();
 }
 
-template <int STAGES, bool FILTER, int KCH, int QB = 1>
-static hipError_t launch_sweep_inst(const float* q, const unsigned short* g, float* scores, long ld, int B, long N, int D, long S, int R,
-                                    const TopkFilter& filt, const int* gate, hipStream_t s, int* zf, float* tmax, long ldt) {
+template <int STAGES, bool FILTER, int KCH, int QB = 1, bool MASK = false>
+static hipError_t launch_sweep_go(const float* q, const unsigned short* g, float* scores, long ld, int B, long N, int D, long S, int R,
+                                  const TopkFilter& filt, const int* gate, hipStream_t s, int* zf, float* tmax, long ldt, const RowTags& rt) {
     const size_t qbytes = ((size_t)64 * (D * 2 + 16) + 1023) / 1024 * 1024;
-    const size_t ringq = (size_t)4 * STAGES * STAGE_BYTES + QUEUE_BYTES;
+    const size_t ringq = (size_t)4 * STAGES * STAGE_BYTES + tail_bytes(STAGES, MASK);
     const size_t lds = (KCH > 0 && QB == 1) ? std::max(qbytes, ringq) : qbytes + ringq;
+    if (lds > (size_t)160 * 1024) return hipErrorInvalidValue;
     static size_t attr_set = 0;
-    auto kern = sweep_bf16_kernel<STAGES, FILTER, KCH, QB>;
+    auto kern = sweep_bf16_kernel<STAGES, FILTER, KCH, QB, MASK>;
     if (lds > attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -454,51 +530,71 @@ static hipError_t launch_sweep_inst(const float* q, const unsigned short* g, flo
     const long ntiles = ((FILTER ? N : S) + ROWS_T - 1) / ROWS_T;
     long blocks = (ntiles + 3) / 4;
     if (blocks > 256) blocks = 256;                                // one persistent workgroup per CU
-    FERN_LAUNCH(kern, dim3((unsigned)blocks), dim3(256), lds, s, q, g, scores, ld, B, N, D, S, R, filt, gate, zf, tmax, ldt);
+    FERN_LAUNCH(kern, dim3((unsigned)blocks), dim3(256), lds, s, q, g, scores, ld, B, N, D, S, R, filt, gate, zf, tmax, ldt, rt);
     return hipGetLastError();
+}
+// the row filter is part of the instantiation (store form only)
+template <int STAGES, bool FILTER, int KCH, int QB = 1>
+static hipError_t launch_sweep_inst(const float* q, const unsigned short* g, float* scores, long ld, int B, long N, int D, long S, int R,
+                                    const TopkFilter& filt, const int* gate, hipStream_t s, int* zf, float* tmax, long ldt, const RowTags* rt) {
+    // (the two-block form at D = 512 has 12 registers to spare, the masking needs more: launch_sweep_bf16 runs two one-block launches)
+    if constexpr (QB == 2 && KCH == 8) {
+        if (rt) return hipErrorInvalidValue;
+    } else if constexpr (!FILTER) {
+        if (rt) return launch_sweep_go<STAGES, FILTER, KCH, QB, true>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, *rt);
+    }
+    return launch_sweep_go<STAGES, FILTER, KCH, QB, false>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, RowTags{nullptr, nullptr, nullptr});
 }
 
 template <bool FILTER>
 static hipError_t launch_sweep_mode(const float* q, const unsigned short* g, float* scores, long ld, int B, long N, int D, long S, int R,
-                                    const TopkFilter& filt, const int* gate, hipStream_t s, int* zf, float* tmax, long ldt) {
+                                    const TopkFilter& filt, const int* gate, hipStream_t s, int* zf, float* tmax, long ldt, const RowTags* rt) {
     static const bool regq = [] { const char* e = getenv("FERN_SWEEP_REGQ"); return !(e && e[0] == '0'); }();      // A/B switch
     if (B > 64) {    // 65..128 queries per gallery pass: second query block in LDS, 5-stage ring
         switch (D) {
-            case 64: return launch_sweep_inst<5, FILTER, 1, 2>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
-            case 128: return launch_sweep_inst<5, FILTER, 2, 2>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
-            case 256: return launch_sweep_inst<5, FILTER, 4, 2>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
-            case 512: return launch_sweep_inst<5, FILTER, 8, 2>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
+            case 64: return launch_sweep_inst<5, FILTER, 1, 2>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
+            case 128: return launch_sweep_inst<5, FILTER, 2, 2>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
+            case 256: return launch_sweep_inst<5, FILTER, 4, 2>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
+            case 512: return launch_sweep_inst<5, FILTER, 8, 2>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
             default: return hipErrorInvalidValue;
         }
     }
     if (regq) {      // register-resident queries, 9-stage ring
         switch (D) {
-            case 64: return launch_sweep_inst<9, FILTER, 1>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
-            case 128: return launch_sweep_inst<9, FILTER, 2>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
-            case 256: return launch_sweep_inst<9, FILTER, 4>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
-            case 512: return launch_sweep_inst<9, FILTER, 8>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
-            case 640: return launch_sweep_inst<9, FILTER, 10>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);      // RN50x4 (C3): 320 fragment VGPRs of the 512
+            case 64: return launch_sweep_inst<9, FILTER, 1>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
+            case 128: return launch_sweep_inst<9, FILTER, 2>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
+            case 256: return launch_sweep_inst<9, FILTER, 4>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
+            case 512: return launch_sweep_inst<9, FILTER, 8>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
+            case 640: return launch_sweep_inst<9, FILTER, 10>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);      // RN50x4 (C3): 320 fragment VGPRs of the 512
             default: break;
         }
     }
     const size_t qbytes = ((size_t)64 * (D * 2 + 16) + 1023) / 1024 * 1024;
-    const size_t room = (size_t)160 * 1024 - qbytes - QUEUE_BYTES;
+    const size_t room = (size_t)160 * 1024 - qbytes - QUEUE_BYTES;      // (<= 5 stages: the masked form's tail is no larger)
     const int stages = (int)(room / (4 * STAGE_BYTES));
-    if (stages >= 5) return launch_sweep_inst<5, FILTER, 0>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
-    if (stages >= 4) return launch_sweep_inst<4, FILTER, 0>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
-    if (stages >= 3) return launch_sweep_inst<3, FILTER, 0>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt);
+    if (stages >= 5) return launch_sweep_inst<5, FILTER, 0>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
+    if (stages >= 4) return launch_sweep_inst<4, FILTER, 0>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
+    if (stages >= 3) return launch_sweep_inst<3, FILTER, 0>(q, g, scores, ld, B, N, D, S, R, filt, gate, s, zf, tmax, ldt, rt);
     return hipErrorInvalidValue;
 }
 
 hipError_t launch_sweep_bf16(const float* q, const unsigned short* g, float* scores, long ld, int B, long N, int D, long S, int R,
-                             const TopkFilter* filt, const int* gate, hipStream_t s, int* zero_flags, float* tmax, long ldt) {
+                             const TopkFilter* filt, const int* gate, hipStream_t s, int* zero_flags, float* tmax, long ldt, const RowTags* rt) {
     if (B <= 0 || N <= 0) return hipSuccess;
+    if (rt && !rt->tags) rt = nullptr;
+    if (rt && (filt || S != N || R != 1 || !rt->mask || !rt->value)) return hipErrorInvalidValue;      // row filter: the store-all form
     if (B > 128 || (B > 64 && D != 64 && D != 128 && D != 256 && D != 512) || D % 64 || D > 1024 || R < 1) return hipErrorInvalidValue;
-    if (filt) return launch_sweep_mode<true>(q, g, nullptr, 0, B, N, D, 0, 1, *filt, gate, s, nullptr, nullptr, 0);
+    if (filt) return launch_sweep_mode<true>(q, g, nullptr, 0, B, N, D, 0, 1, *filt, gate, s, nullptr, nullptr, 0, nullptr);
     if (S <= 0) return hipSuccess;
     if (!scores || (S - 1) * (long)R >= N) return hipErrorInvalidValue;      // every sample run must start inside the gallery
     if (tmax && (S != N || R != 1 || B > 64 || ldt < (N + ROWS_T - 1) / ROWS_T)) return hipErrorInvalidValue;      // tile maxima: store-all form, one query block
-    return launch_sweep_mode<false>(q, g, scores, ld, B, N, D, S, R, TopkFilter{}, gate, s, zero_flags, tmax, ldt);
+    if (rt && B > 64 && D == 512) {      // masked, two query blocks, D = 512: no registers for it in one pass -- one pass per block
+        const RowTags r1{rt->tags, rt->mask + 64, rt->value + 64};
+        const hipError_t e = launch_sweep_mode<false>(q, g, scores, ld, 64, N, D, S, R, TopkFilter{}, gate, s, zero_flags, nullptr, 0, rt);
+        if (e != hipSuccess) return e;
+        return launch_sweep_mode<false>(q + 64L * D, g, scores + 64 * ld, ld, B - 64, N, D, S, R, TopkFilter{}, gate, s, nullptr, nullptr, 0, &r1);
+    }
+    return launch_sweep_mode<false>(q, g, scores, ld, B, N, D, S, R, TopkFilter{}, gate, s, zero_flags, tmax, ldt, rt);
 }
 
 }  // namespace fern

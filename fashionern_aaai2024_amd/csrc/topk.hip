@@ -656,15 +656,17 @@ __global__ __launch_bounds__(256) void topk_rescore_kernel(TopkFilter f, const f
 // for (near-tie floods, galleries smaller than ~K, NaN scores) is ranked right here -- every row's exact chain, streamed through the
 // waves' sorted lists (wave_offer: no capacity) -- instead of by the gated exact-pass launch, whose ~4.5 us of launch boundary every call
 // paid for a case that almost never happens.  One CU streams the whole fp32 gallery (~60 GB/s): the launcher allows it up to 128 MB.
+// tags != null: rows that are ineligible for this query ((tags[n] & mask) != value) are skipped like the excluded row.
 __device__ __forceinline__ void exact_topk_inline(const float* qrow, const float* gallery, long N, int D, long drop, int K, long idx_offset,
-                                                  float* os, int* oi, u64 (*wl)[64]) {
+                                                  float* os, int* oi, u64 (*wl)[64], const unsigned* tags = nullptr, unsigned mask = 0u,
+                                                  unsigned value = 0u) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     u64 best = 0;
 #pragma unroll 1
     for (long n0 = (long)wave * 64; n0 < N; n0 += 256) {
         const long n = n0 + lane;
         u64 key = 0;
-        if (n < N && n != drop) {
+        if (n < N && n != drop && (!tags || row_eligible(tags[n], mask, value))) {
             const float* g = gallery + n * D;
             float acc = 0.0f;
             for (int k8 = 0; k8 < D; k8 += 8) {
@@ -705,7 +707,10 @@ constexpr int DENSE_BATCH = 1024 * DENSE_UB;    // floats the workgroup covers p
 template <int NB>
 __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* approx, long ld, long N, const float* q, const float* gallery, int D,
                                                                  BoundMargin mg, int K, const int* exclude, long exclude_off, long idx_offset,
-                                                                 float* out_scores, int* out_idx, u64* thr_key, int* flags, int* state, int* done, int stop, int inline_exact) {
+                                                                 float* out_scores, int* out_idx, u64* thr_key, int* flags, int* state, int* done, int stop, int inline_exact,
+                                                                 RowTags rt) {
+    // rt.tags != null: `approx` holds the MASKED sweep's scores (ineligible rows are -inf, so no walk collects them while the cut is a
+    // number); the only places that look at the gallery itself again are the exact fallbacks, which apply the predicate.
     __shared__ u64 wlists[4][64];                                            // inline exact ranking: the waves' sorted lists
     __shared__ __attribute__((aligned(16))) u64 ckey[4][DENSE_SEG + 2];      // per wave: collected approximate keys (+ zero padding)
     __shared__ __attribute__((aligned(16))) float tiles[RESC_TILE_FLOATS];
@@ -814,6 +819,7 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     u64 fallback_thr = 0;
     do {
     if (l0 == 0) break;      // (uniform) no bound -- tiny galleries, or NaN scores
+    if (rt.tags && !(margin < INFINITY)) break;      // (uniform) filtered: a cut that is no number would collect the masked rows too
     const float cut0 = unorderable(l0) - margin;
     if (stop == 2) { if (cut0 == 0.12345f) out_idx[0] = 1; return; }
     // (This kernel runs ONCE per CU on a cold instruction cache: its time follows the bytes of code it executes.  A second, never-taken
@@ -921,7 +927,8 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     return;
     } while (0);
     if (inline_exact) {      // small galleries: ranked exactly right here
-        exact_topk_inline(qrow, gallery, N, D, drop, K, idx_offset, out_scores + (long)b * K, out_idx + (long)b * K, wlists);
+        exact_topk_inline(qrow, gallery, N, D, drop, K, idx_offset, out_scores + (long)b * K, out_idx + (long)b * K, wlists, rt.tags,
+                          rt.tags ? rt.mask[b] : 0u, rt.tags ? rt.value[b] : 0u);
     } else if (tid == 0) {   // flagged for the gated exact pass
         state[b] = 1;
         flags[0] = 1;
@@ -949,7 +956,9 @@ template <bool HOLD>
 __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* approx, long ld, const float* tmax, long ldt, long N, const float* q,
                                                                  const float* gallery, int D, BoundMargin mg, int K, const int* exclude, long exclude_off,
                                                                  long idx_offset, float* out_scores, int* out_idx, u64* thr_key, int* flags, int* state,
-                                                                 int* done, int inline_exact) {
+                                                                 int* done, int inline_exact, RowTags rt) {
+    // (rt: as in topk_dense_rescore_kernel -- tile maxima and scores come from the masked sweep; a tile whose rows are all ineligible
+    //  has maximum -inf = "no tile")
     __shared__ u64 wlists[4][64];
     __shared__ __attribute__((aligned(16))) u64 ckey[4][DENSE_SEG + 2];
     __shared__ __attribute__((aligned(16))) float tiles[RESC_TILE_FLOATS];
@@ -1132,7 +1141,8 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
     return;
     } while (0);
     if (inline_exact) {
-        exact_topk_inline(qrow, gallery, N, D, drop, K, idx_offset, out_scores + (long)b * K, out_idx + (long)b * K, wlists);
+        exact_topk_inline(qrow, gallery, N, D, drop, K, idx_offset, out_scores + (long)b * K, out_idx + (long)b * K, wlists, rt.tags,
+                          rt.tags ? rt.mask[b] : 0u, rt.tags ? rt.value[b] : 0u);
     } else if (tid == 0) {
         state[b] = 1;
         flags[0] = 1;
@@ -1158,8 +1168,9 @@ constexpr int EXACT_QB = 32;                    // flagged queries per gallery p
 template <bool BF16>
 __global__ __launch_bounds__(256) void rank_exact_kernel(const float* q, const void* gallery, int B, long N, int D, int K, const int* state,
                                                          const u64* thr_key, const int* exclude, long exclude_off, long idx_offset,
-                                                         u64* partial, int* done, float* out_scores, int* out_idx, const int* gate) {
+                                                         u64* partial, int* done, float* out_scores, int* out_idx, const int* gate, RowTags rt) {
     if (*gate == 0) return;
+    __shared__ unsigned mk_s[EXACT_QB], vl_s[EXACT_QB];      // rt.tags != null: the chunk's row filters (ineligible rows are never offered)
     __shared__ u64 lists[4][EXACT_QB][64];      // 64 KiB: every wave's sorted list of every query of the chunk
     __shared__ int flagged[1024];               // the flagged queries in query order (a plan holds <= 1024 queries: api.hip kRankQueryChunk)
     __shared__ u64 thr_s[EXACT_QB];
@@ -1192,6 +1203,8 @@ __global__ __launch_bounds__(256) void rank_exact_kernel(const float* q, const v
             const int b = flagged[c0 + (tid < nq ? tid : 0)];
             thr_s[tid] = tid < nq ? thr_key[b] : ~0ull;
             ex_s[tid] = (tid < nq && exclude) ? (long)exclude[b] - exclude_off : -1;
+            mk_s[tid] = (tid < nq && rt.tags) ? rt.mask[b] : 0u;
+            vl_s[tid] = (tid < nq && rt.tags) ? rt.value[b] : 0u;
         }
         for (int i = tid; i < 4 * EXACT_QB * 64; i += 256) (&lists[0][0][0])[i] = 0;
         __syncthreads();
@@ -1202,6 +1215,7 @@ __global__ __launch_bounds__(256) void rank_exact_kernel(const float* q, const v
         for (long t = (long)g * 4 + wave; t < ntiles; t += (long)G * 4) {
             const long n = t * 32 + l31;
             const long nc = n < N ? n : N - 1;
+            const unsigned tag = rt.tags ? rt.tags[nc] : 0u;
             f32x16e acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
@@ -1243,7 +1257,7 @@ __global__ __launch_bounds__(256) void rank_exact_kernel(const float* q, const v
 #pragma unroll
                 for (int r = 1; r < 16; ++r) v = rsel == r ? acc[r] : v;
                 u64 cand = 0;
-                if (lh == hsel && n < N && n != ex_s[qi]) {
+                if (lh == hsel && n < N && n != ex_s[qi] && row_eligible(tag, mk_s[qi], vl_s[qi])) {
                     const u64 key = make_key(v, (unsigned)n);
                     cand = key >= thr_s[qi] ? key : 0;
                 }
@@ -1323,18 +1337,20 @@ hipError_t launch_topk_rescore(const TopkFilter& f, const float* q, const float*
 hipError_t launch_topk_dense_rescore(const float* approx, long ld, long N, const float* q, const float* gallery, int D, const float* meta,
                                      int B, int K, const int* exclude, long exclude_off, long idx_offset, float* out_scores,
                                      int* out_idx, unsigned long long* thr_key, int* flags, int* state, int* done, hipStream_t s, int inline_exact,
-                                     const float* tmax, long ldt) {
+                                     const float* tmax, long ldt, const RowTags* rtp) {
     if (B <= 0) return hipSuccess;
+    const RowTags rt = (rtp && rtp->tags) ? *rtp : RowTags{nullptr, nullptr, nullptr};
+    if (rt.tags && (!rt.mask || !rt.value)) return hipErrorInvalidValue;
     if (K < 1 || K > 64 || D < 64 || D % 64 || D > 1024 || N < 1 || (ld & 3) || !meta) return hipErrorInvalidValue;
     const BoundMargin mg{q, D, meta, nullptr};
     if (tmax && N >= TILES_MIN_N) {                  // selection on the sweep's tile maxima
         if (ld < ((N + 31) & ~31L) || ldt < (N + 31) / 32) return hipErrorInvalidValue;
         if ((N + 31) / 32 <= 256L * TILES_TB)
             FERN_LAUNCH(topk_tiles_rescore_kernel<true>, dim3(B), dim3(256), 0, s, approx, ld, tmax, ldt, N, q, gallery, D, mg, K, exclude, exclude_off,
-                        idx_offset, out_scores, out_idx, thr_key, flags, state, done, inline_exact);
+                        idx_offset, out_scores, out_idx, thr_key, flags, state, done, inline_exact, rt);
         else
             FERN_LAUNCH(topk_tiles_rescore_kernel<false>, dim3(B), dim3(256), 0, s, approx, ld, tmax, ldt, N, q, gallery, D, mg, K, exclude, exclude_off,
-                        idx_offset, out_scores, out_idx, thr_key, flags, state, done, inline_exact);
+                        idx_offset, out_scores, out_idx, thr_key, flags, state, done, inline_exact, rt);
         return hipGetLastError();
     }
     // lab switch (tools/rank_bench.py): FERN_DENSE_STOP=k ends the kernel after phase k (results are then garbage) to attribute its time
@@ -1342,7 +1358,7 @@ hipError_t launch_topk_dense_rescore(const float* approx, long ld, long N, const
     const long n4 = N & ~3L;
 #define FERN_DENSE_GO(NB)                                                                                                                       \
     FERN_LAUNCH(topk_dense_rescore_kernel<NB>, dim3(B), dim3(256), 0, s, approx, ld, N, q, gallery, D, mg, K, exclude, exclude_off, idx_offset, \
-                out_scores, out_idx, thr_key, flags, state, done, stop, inline_exact)
+                out_scores, out_idx, thr_key, flags, state, done, stop, inline_exact, rt)
     if (n4 <= 1L * DENSE_BATCH) FERN_DENSE_GO(1);
     else if (n4 <= 2L * DENSE_BATCH) FERN_DENSE_GO(2);
     else if (n4 <= 3L * DENSE_BATCH) FERN_DENSE_GO(3);
@@ -1354,15 +1370,17 @@ hipError_t launch_topk_dense_rescore(const float* approx, long ld, long N, const
 hipError_t launch_rank_exact(const float* q, const void* gallery, int gallery_bf16, int B, long N, int D, int K, const int* state,
                              const unsigned long long* thr_key, const int* exclude, long exclude_off, long idx_offset,
                              unsigned long long* partial, int groups, int* done, float* out_scores, int* out_idx, const int* gate,
-                             hipStream_t s) {
+                             hipStream_t s, const RowTags* rtp) {
     if (B <= 0 || N <= 0) return hipSuccess;
+    const RowTags rt = (rtp && rtp->tags) ? *rtp : RowTags{nullptr, nullptr, nullptr};
+    if (rt.tags && (!rt.mask || !rt.value)) return hipErrorInvalidValue;
     if (K < 1 || K > 64 || groups < 1 || B > 1024 || D % (gallery_bf16 ? 16 : 8)) return hipErrorInvalidValue;
     if (gallery_bf16)
         FERN_LAUNCH(rank_exact_kernel<true>, dim3(groups), dim3(256), 0, s, q, gallery, B, N, D, K, state, thr_key, exclude, exclude_off,
-                    idx_offset, partial, done, out_scores, out_idx, gate);
+                    idx_offset, partial, done, out_scores, out_idx, gate, rt);
     else
         FERN_LAUNCH(rank_exact_kernel<false>, dim3(groups), dim3(256), 0, s, q, gallery, B, N, D, K, state, thr_key, exclude, exclude_off,
-                    idx_offset, partial, done, out_scores, out_idx, gate);
+                    idx_offset, partial, done, out_scores, out_idx, gate, rt);
     return hipGetLastError();
 }
 

@@ -107,10 +107,14 @@ __device__ __forceinline__ void write_key(u64 key, long idx_offset, float* os, i
 // h: k = 8 g8 + 4 h + e), i.e. the oracle/chain.c order.  Workgroup (x, y): queries 32 y .. 32 y + 31, wave w the 32-row tiles
 // 4 x + w + j * 4 gridDim.x.  GATED: runs only if flags[0] is set and writes only the rows of flagged queries (state[b] != 0);
 // otherwise it also zeroes flags[0..3] for the selection that follows.
+// rt.tags != null (a per-query row filter, kernels.h: RowTags; kernel-uniform branch -- this kernel is MFMA-bound on fp32 operands, the
+// predicate is 16 VALU compares per 32 x 32 tile): an ineligible (query, row) pair is stored as -inf, in the GATED rewrite as well, so
+// neither the selection nor the radix fallback ever sees it.
 template <bool GATED>
 __global__ __launch_bounds__(256) void deep_exact_scores_kernel(const float* q, const float* gallery, int B, long N, int D, float* S, long ld,
-                                                                int* flags, const int* state) {
+                                                                int* flags, const int* state, RowTags rt) {
     __shared__ int qflag[32];
+    __shared__ unsigned qmask[32], qvalue[32];
     __shared__ int any;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lh = lane >> 5;
     const int q0 = blockIdx.y * 32, nq = B - q0 < 32 ? B - q0 : 32;
@@ -129,11 +133,17 @@ __global__ __launch_bounds__(256) void deep_exact_scores_kernel(const float* q, 
         if (tid < 32) qflag[tid] = tid < nq;
         __syncthreads();
     }
+    const bool tagged = rt.tags != nullptr;
+    if (tagged) {
+        if (tid < 32) { qmask[tid] = tid < nq ? rt.mask[q0 + tid] : 0u; qvalue[tid] = tid < nq ? rt.value[q0 + tid] : 1u; }
+        __syncthreads();
+    }
     const float* qrow = q + (long)(q0 + (l31 < nq ? l31 : 0)) * D;      // this lane's A row
     const long ntiles = (N + 31) / 32;
     for (long t = (long)blockIdx.x * 4 + wave; t < ntiles; t += (long)gridDim.x * 4) {
         const long n = t * 32 + l31;
         const float* grow = gallery + (n < N ? n : N - 1) * D;
+        const unsigned tag = tagged ? rt.tags[n < N ? n : N - 1] : 0u;      // issued in front of the row's loads
         f32x16d acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
@@ -147,7 +157,7 @@ __global__ __launch_bounds__(256) void deep_exact_scores_kernel(const float* q, 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int qi = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (qflag[qi]) S[(long)(q0 + qi) * ld + n] = acc[r];
+                if (qflag[qi]) S[(long)(q0 + qi) * ld + n] = (!tagged || row_eligible(tag, qmask[qi], qvalue[qi])) ? acc[r] : -INFINITY;
             }
         }
     }
@@ -445,16 +455,18 @@ __global__ __launch_bounds__(MERGE_NT) void topk_merge_deep_kernel(const float* 
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------
 hipError_t launch_deep_exact_scores(const float* q, const float* gallery, int B, long N, int D, float* S, long ld, int* flags, const int* state,
-                                    int gated, hipStream_t s) {
+                                    int gated, hipStream_t s, const RowTags* rt) {
     if (B <= 0 || N <= 0) return hipSuccess;
     if (D <= 0 || D % 8 || ld < N || (gated && !state)) return hipErrorInvalidValue;
     const long ntiles = (N + 31) / 32;
     const int gy = (B + 31) / 32;
     const int gx = (int)std::min<long>((ntiles + 3) / 4, std::max(1, 2048 / gy));
+    const RowTags tags = (rt && rt->tags) ? *rt : RowTags{nullptr, nullptr, nullptr};
+    if (tags.tags && (!tags.mask || !tags.value)) return hipErrorInvalidValue;
     if (gated)
-        FERN_LAUNCH(deep_exact_scores_kernel<true>, dim3(gx, gy), dim3(256), 0, s, q, gallery, B, N, D, S, ld, flags, state);
+        FERN_LAUNCH(deep_exact_scores_kernel<true>, dim3(gx, gy), dim3(256), 0, s, q, gallery, B, N, D, S, ld, flags, state, tags);
     else
-        FERN_LAUNCH(deep_exact_scores_kernel<false>, dim3(gx, gy), dim3(256), 0, s, q, gallery, B, N, D, S, ld, flags, state);
+        FERN_LAUNCH(deep_exact_scores_kernel<false>, dim3(gx, gy), dim3(256), 0, s, q, gallery, B, N, D, S, ld, flags, state, tags);
     return hipGetLastError();
 }
 

@@ -171,12 +171,15 @@ def rank_replicated(engine, queries: torch.Tensor, gallery: torch.Tensor, k: int
     return engine.sim_topk(queries, gallery, k, exclude_idx=exclude_idx)
 
 
-def rank_sharded(engine, queries: torch.Tensor, gallery_shard: torch.Tensor, shard_start: int, k: int, exclude_idx=None):
+def rank_sharded(engine, queries: torch.Tensor, gallery_shard: torch.Tensor, shard_start: int, k: int, exclude_idx=None, row_filter=None):
     """Gallery-sharded ranking of the SAME query batch on every rank: local top-K with global indices, all-gather of
-    the [B, K] candidates, merge.  Returns the global (scores, idx) on every rank.  k > 64: the deep ranking and the wide merge."""
+    the [B, K] candidates, merge.  Returns the global (scores, idx) on every rank.  k > 64: the deep ranking and the wide merge.
+    `row_filter`: the SHARD's `RowFilter` -- tags shard with the rows, mask / value are the same on every rank; the filtered lists
+    merge exactly like the unfiltered ones."""
     rank, world = world_info()
     rank_fn = engine.sim_topk_deep if k > 64 else engine.sim_topk
-    s, i = rank_fn(queries, gallery_shard, k, idx_offset=shard_start, exclude_idx=exclude_idx)
+    kw = {} if row_filter is None else {"row_filter": row_filter}
+    s, i = rank_fn(queries, gallery_shard, k, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
     if world == 1:
         return s, i
     b, kk = s.shape
@@ -198,23 +201,33 @@ def _all_reduce_sum(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
-def rank_of_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: int, targets, exclude_idx=None):
+def rank_of_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: int, targets, exclude_idx=None, row_filter=None):
     """Gallery-sharded exact target ranks of the SAME query batch on every rank (`FernEngine.rank_of` on the whole gallery): the key of
     a target comes from the shard that owns its row -- every other rank contributes 0, so the int64 SUM all-reduce is exact, wrap-around
     included -- then every rank counts the rows of its shard that outrank the keys and the counts are SUM-reduced.  Two small
     collectives of [B, m] integers; world 1 makes none.  Returns int32 shaped like `targets` on every rank; -1 for a target < 0,
-    outside the gallery, or equal to the query's excluded row."""
+    outside the gallery, or equal to the query's excluded row.  `row_filter`: the SHARD's `RowFilter` (tags shard with the rows): only
+    eligible rows are counted, and the shard that owns a target drops its key when the target is not eligible (-1 on every rank)."""
     rank, world = world_info()
     t = torch.as_tensor(targets)
     flat = t.dim() == 1
     t2 = (t[:, None] if flat else t).to(dtype=torch.int32)
     keys = engine.rank_keys(queries, gallery_shard, t2, idx_offset=shard_start)
+    kw = {}
+    if row_filter is not None:
+        kw["row_filter"] = row_filter
+        n = gallery_shard.shape[0]
+        tags, mask, value = row_filter.resolve(keys.shape[0], n, keys.device)
+        local = t2.to(device=keys.device, dtype=torch.int64) - int(shard_start)
+        mine = (local >= 0) & (local < n)
+        ok = (tags[local.clamp(0, max(n - 1, 0))] & mask[:, None]) == value[:, None] if n else mine
+        keys = torch.where(mine & ~ok, torch.zeros_like(keys), keys)
     if world > 1:
         _all_reduce_sum(keys)
     if exclude_idx is not None:
         ex = torch.as_tensor(exclude_idx).to(device=keys.device, dtype=torch.int32)
         keys = torch.where(t2.to(keys.device) == ex[:, None], torch.zeros_like(keys), keys)
-    counts = engine.rank_count(queries, gallery_shard, keys, idx_offset=shard_start, exclude_idx=exclude_idx)
+    counts = engine.rank_count(queries, gallery_shard, keys, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
     if world > 1:
         counts = counts.clamp(min=0)                 # a keyless target is -1 on every rank: summed as 0, restored below
         _all_reduce_sum(counts)

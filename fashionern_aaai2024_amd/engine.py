@@ -67,6 +67,58 @@ class PreparedGallery:
         return True
 
 
+def _bits32(x, what: str) -> torch.Tensor:
+    """An integer tensor (or Python int) as int32 BITS: uint32 is reinterpreted, wider integers must fit 32 bits (signed or unsigned)."""
+    t = torch.as_tensor(x)
+    if t.dtype == torch.int32:
+        return t
+    if t.dtype == torch.uint32:
+        return t.view(torch.int32)
+    if t.dtype in (torch.int64, torch.int16, torch.int8, torch.uint8):
+        t = t.to(torch.int64)
+        if t.numel() and (int(t.min()) < -(1 << 31) or int(t.max()) >= (1 << 32)):
+            raise ValueError(f"{what} does not fit 32 bits")
+        return (((t & 0xFFFFFFFF) + (1 << 31)) % (1 << 32) - (1 << 31)).to(torch.int32)
+    raise ValueError(f"{what} must be an integer tensor (int32 or uint32 bits), got {t.dtype}")
+
+
+class RowFilter:
+    """Per-query gallery row filter (include/fern.h: fern_sim_topk_filtered): gallery row n is eligible for query b iff
+    ``(tags[n] & mask[b]) == value[b]``.  `tags` [N] is one 32-bit tag per gallery row (int32 or uint32, taken as bits); `mask` and
+    `value` are [B] tensors or scalars that apply to every query.  mask = value = 0 accepts every row; a value with bits outside the
+    mask matches nothing.  The reference's per-category FashionIQ indexes (run/test/test_fiq.py:157-177) are tag = category,
+    mask = all ones, value = the query's category; CIRR's img_set (run/test/test_cirr.py:63-66) is a group id field."""
+
+    __slots__ = ("tags", "mask", "value")
+
+    def __init__(self, tags, mask=0, value=0):
+        self.tags = _bits32(tags, "tags")
+        if self.tags.dim() != 1:
+            raise ValueError(f"tags must be [N], got {tuple(self.tags.shape)}")
+        self.mask, self.value = _bits32(mask, "mask"), _bits32(value, "value")
+        for name, t in (("mask", self.mask), ("value", self.value)):
+            if t.dim() > 1:
+                raise ValueError(f"{name} must be a scalar or [B], got {tuple(t.shape)}")
+        if self.mask.dim() == 1 and self.value.dim() == 1 and self.mask.shape != self.value.shape:
+            raise ValueError(f"mask {tuple(self.mask.shape)} and value {tuple(self.value.shape)} must have the same length")
+
+    def rows(self, start: int, stop: int) -> "RowFilter":
+        """The filter of the query slice [start, stop): per-query masks / values are sliced, scalars and the tags stay."""
+        cut = lambda t: t[start:stop] if t.dim() == 1 else t      # noqa: E731
+        return RowFilter(self.tags, cut(self.mask), cut(self.value))
+
+    def resolve(self, b: int, n: int, device):
+        """(tags [n], mask [b], value [b]) as contiguous int32 tensors on `device`; raises when the shapes do not fit the call."""
+        if self.tags.shape[0] != n:
+            raise ValueError(f"row_filter.tags has {self.tags.shape[0]} entries, the gallery has {n} rows")
+        out = [self.tags.to(device).contiguous()]
+        for name, t in (("mask", self.mask), ("value", self.value)):
+            if t.dim() == 1 and t.shape[0] != b:
+                raise ValueError(f"row_filter.{name} must be a scalar or [B = {b}], got {tuple(t.shape)}")
+            out.append((t.to(device).expand(b) if t.dim() == 0 else t.to(device)).contiguous())
+        return tuple(out)
+
+
 class FernEngine:
     """One native context on one GPU.  Not thread-safe (one per device per process)."""
 
@@ -330,9 +382,48 @@ class FernEngine:
         _lib.check(self.lib.fern_gallery_prepare(self._h, _ptr(g), g.shape[0], g.shape[1], _ptr(b16), _ptr(meta), _stream()), "fern_gallery_prepare")
         return PreparedGallery(g, b16, meta)
 
-    def sim_topk(self, q, gallery, k: int, idx_offset: int = 0, exclude_idx=None):
+    def _exclude(self, exclude_idx, b: int):
+        if exclude_idx is None:
+            return None
+        ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(ex.shape) != (b,):
+            raise ValueError("exclude_idx must be [B]")
+        return ex
+
+    def _sim_topk_filtered(self, q, gallery, k: int, idx_offset, exclude_idx, row_filter: RowFilter):
+        """The filtered form of `sim_topk` / `sim_topk_deep` / `sim_topk_bf16` (include/fern.h: fern_sim_topk_filtered): the exact
+        ranking of the rows that are eligible for each query, 1 <= k <= 1024, any gallery form."""
+        if not isinstance(row_filter, RowFilter):
+            raise TypeError("row_filter must be a RowFilter")
+        q = self._f32(q)
+        g32 = g16 = meta = None
+        if isinstance(gallery, PreparedGallery):
+            g32, g16, meta = gallery.f32, gallery.bf16, gallery.meta
+        elif isinstance(gallery, torch.Tensor) and gallery.dtype == torch.bfloat16:
+            if not gallery.is_cuda or not gallery.is_contiguous():
+                raise ValueError("a bf16 gallery must be a contiguous device tensor")
+            g16 = gallery
+        else:
+            g32 = self._f32(gallery)
+        g = g32 if g32 is not None else g16
+        if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+            raise ValueError(f"q [B,D] and gallery [N,D] must share D, got {tuple(q.shape)} and {tuple(g.shape)}")
+        b = q.shape[0]
+        tags, mask, value = row_filter.resolve(b, g.shape[0], self.device)
+        scores = self._empty(b, k)
+        idx = self._empty(b, k, dtype=torch.int32)
+        ex = self._exclude(exclude_idx, b)
+        _lib.check(self.lib.fern_sim_topk_filtered(self._h, _ptr(q), _ptr(g32), _ptr(g16), _ptr(meta), b, g.shape[0], q.shape[1], int(k),
+                                                   _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask), _ptr(value),
+                                                   _stream()), "fern_sim_topk_filtered")
+        return scores, idx
+
+    def sim_topk(self, q, gallery, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
         """Exact cosine top-K of q [B,D] against an fp32 gallery [N,D] (run/test/test_fiq.py:49-50).  `gallery` is a tensor -- the
-        fp32-MFMA sweep -- or a `PreparedGallery` -- bf16 pre-filter + exact rescoring, same scores and ordering bit for bit."""
+        fp32-MFMA sweep -- or a `PreparedGallery` -- bf16 pre-filter + exact rescoring, same scores and ordering bit for bit.
+        `row_filter`: rank only the rows that are eligible for each query (`RowFilter`)."""
+        if row_filter is not None:
+            return self._sim_topk_filtered(q, gallery, k, idx_offset, exclude_idx, row_filter)
         if isinstance(gallery, PreparedGallery):
             return self._sim_topk_prefiltered(q, gallery, k, idx_offset, exclude_idx)
         q, g = self._f32(q), self._f32(gallery)
@@ -386,10 +477,13 @@ class FernEngine:
                                                       _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_prefiltered")
         return scores, idx
 
-    def sim_topk_deep(self, q, gallery, k: int, idx_offset: int = 0, exclude_idx=None):
+    def sim_topk_deep(self, q, gallery, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
         """Exact top-K for 1 <= k <= 1024 (include/fern.h: fern_sim_topk_deep); `sim_topk` stops at 64.  `gallery` is an fp32
         tensor (exact fp32-chain scores), a `PreparedGallery` (the same bits through the certified bf16 pre-filter) or a bf16
-        tensor (the bf16 similarity of `sim_topk_bf16`).  For k' <= 64 the first k' columns equal those of the K <= 64 call."""
+        tensor (the bf16 similarity of `sim_topk_bf16`).  For k' <= 64 the first k' columns equal those of the K <= 64 call.
+        `row_filter`: rank only the rows that are eligible for each query (`RowFilter`)."""
+        if row_filter is not None:
+            return self._sim_topk_filtered(q, gallery, k, idx_offset, exclude_idx, row_filter)
         q = self._f32(q)
         g32 = g16 = meta = None
         if isinstance(gallery, PreparedGallery):
@@ -453,9 +547,10 @@ class FernEngine:
                                            int(idx_offset), _ptr(keys), _stream()), "fern_rank_keys")
         return keys
 
-    def rank_count(self, q, gallery, keys, idx_offset: int = 0, exclude_idx=None) -> torch.Tensor:
+    def rank_count(self, q, gallery, keys, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None) -> torch.Tensor:
         """int32 [B,m]: per key the number of rows of `gallery` whose ranking key is greater (include/fern.h: fern_rank_count); the
-        row `exclude_idx[b]` (global index) is not counted; -1 for a key of 0.  Counts of gallery shards add up."""
+        row `exclude_idx[b]` (global index) is not counted; -1 for a key of 0.  Counts of gallery shards add up.  `row_filter`: only
+        the rows that are eligible for the query are counted (fern_rank_count_filtered)."""
         q, g32, g16 = self._rank_forms(q, gallery)
         g = g32 if g32 is not None else g16
         b = q.shape[0]
@@ -466,21 +561,37 @@ class FernEngine:
             if tuple(ex.shape) != (b,):
                 raise ValueError("exclude_idx must be [B]")
         count = self._empty(*ky.shape, dtype=torch.int32)
+        if row_filter is not None:
+            if not isinstance(row_filter, RowFilter):
+                raise TypeError("row_filter must be a RowFilter")
+            tags, mask, value = row_filter.resolve(b, g.shape[0], self.device)
+            _lib.check(self.lib.fern_rank_count_filtered(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, g.shape[0], q.shape[1], _ptr(ky), ky.shape[1],
+                                                         int(idx_offset), _ptr(ex), _ptr(count), _ptr(tags), _ptr(mask), _ptr(value), _stream()),
+                       "fern_rank_count_filtered")
+            return count
         _lib.check(self.lib.fern_rank_count(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, g.shape[0], q.shape[1], _ptr(ky), ky.shape[1],
                                             int(idx_offset), _ptr(ex), _ptr(count), _stream()), "fern_rank_count")
         return count
 
-    def rank_of(self, q, gallery, targets, idx_offset: int = 0, exclude_idx=None) -> torch.Tensor:
+    def rank_of(self, q, gallery, targets, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None) -> torch.Tensor:
         """int32, shaped like `targets` ([B] or [B,m]): the 0-based position of each target row in the ordering `sim_topk` defines
         (score descending, gallery index ascending) -- what the reference reads off its full argsort (run/test/test_fiq.py:49-60) --
-        at any depth.  -1 for a target that is < 0, outside the gallery, or the query's excluded row."""
+        at any depth.  -1 for a target that is < 0, outside the gallery, or the query's excluded row.  `row_filter`: the position
+        among the rows that are eligible for the query; -1 for a target that is not eligible itself."""
         flat = torch.as_tensor(targets).dim() == 1
         keys = self.rank_keys(q, gallery, targets, idx_offset)
         if exclude_idx is not None:
             ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32)
             tg = self._per_query(targets, keys.shape[0], torch.int32, "targets")
             keys = torch.where(tg == ex[:, None], torch.zeros_like(keys), keys)
-        ranks = self.rank_count(q, gallery, keys, idx_offset, exclude_idx)
+        if row_filter is not None:      # ineligible targets lose their key on the device, like the excluded row
+            tg = self._per_query(targets, keys.shape[0], torch.int32, "targets")
+            n = gallery.shape[0]
+            tags, mask, value = row_filter.resolve(keys.shape[0], n, self.device)
+            local = (tg.to(torch.int64) - int(idx_offset)).clamp(0, max(n - 1, 0))
+            ok = (tags[local] & mask[:, None]) == value[:, None] if n else torch.zeros_like(tg, dtype=torch.bool)
+            keys = torch.where(ok, keys, torch.zeros_like(keys))
+        ranks = self.rank_count(q, gallery, keys, idx_offset, exclude_idx, row_filter)
         return ranks[:, 0] if flat else ranks
 
     def gallery_to_bf16(self, gallery) -> torch.Tensor:
@@ -490,7 +601,9 @@ class FernEngine:
         _lib.check(self.lib.fern_gallery_to_bf16(self._h, _ptr(g), _ptr(out), g.shape[0], g.shape[1], _stream()), "fern_gallery_to_bf16")
         return out
 
-    def sim_topk_bf16(self, q, gallery_bf16: torch.Tensor, k: int, idx_offset: int = 0, exclude_idx=None):
+    def sim_topk_bf16(self, q, gallery_bf16: torch.Tensor, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
+        if row_filter is not None:
+            return self._sim_topk_filtered(q, gallery_bf16, k, idx_offset, exclude_idx, row_filter)
         q = self._f32(q)
         g = gallery_bf16
         if g.dtype != torch.bfloat16 or g.dim() != 2 or not g.is_cuda or not g.is_contiguous() or g.shape[1] != q.shape[1]:

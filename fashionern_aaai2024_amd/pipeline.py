@@ -12,7 +12,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .engine import FernEngine
+from .engine import FernEngine, RowFilter
 
 
 class QueryResult:
@@ -71,6 +71,7 @@ class _LaneGraph:
         self.graph = None
         self.inputs = None
         self.outputs = None
+        self.tags = None
         self.ws_generation = None      # the lane engine's workspace generation the graph's baked-in addresses belong to
 
 
@@ -114,14 +115,17 @@ class ComposedQueryPipeline:
         return True
 
     def submit(self, images: Optional[torch.Tensor], tokens: torch.Tensor, local: torch.Tensor, gallery: torch.Tensor, k: int,
-               exclude_idx=None, members=None, idx_offset: int = 0, ref_feats: Optional[torch.Tensor] = None) -> QueryResult:
+               exclude_idx=None, members=None, idx_offset: int = 0, ref_feats: Optional[torch.Tensor] = None,
+               row_filter: Optional[RowFilter] = None) -> QueryResult:
         """images [B,3,S,S], tokens [B,77] int64, local [B,13,D] (device tensors), fused gallery [N,D] fp32 -- or a `PreparedGallery`
         of it (engine.prepare_gallery: the same exact fp32 ranking through the certified bf16 pre-filter, the form a serving process
         keeps), or bf16, which selects the bf16 sweep -- -> QueryResult.  `exclude_idx` [B] drops one gallery index per query and `members` [B,m]
         (fp32 gallery) also returns the scores of those rows: CIRR's reference removal and subset ranking
         (run/test/test_cirr.py:55-66).  `ref_feats` [B,D] (with `images=None`) is the reference harness's own query form: the
         reference image's RAW feature is looked up in the gallery index instead of being encoded again (test_fiq.py:104-107), so
-        the step is text tower + fusion + rank."""
+        the step is text tower + fusion + rank.  `row_filter` (`RowFilter`): each query ranks only the gallery rows that are eligible
+        for it -- one store for several categories, withdrawn rows hidden without re-preparing the gallery; its tags are a static
+        pointer of a captured graph, its per-query mask / value travel through the lane's static buffers like `exclude_idx`."""
         if (images is None) == (ref_feats is None):
             raise ValueError("give either images (encoded per query) or ref_feats (looked up in the index), not both / neither")
         if members is not None and gallery.dtype != torch.float32:
@@ -132,16 +136,19 @@ class ComposedQueryPipeline:
         self._next = (self._next + 1) % len(self.engines)
         eng, stream = self.engines[lane], self.streams[lane]
         stream.wait_stream(torch.cuda.current_stream())          # inputs produced on the caller's stream
-        args = (images, tokens, local, exclude_idx, members, ref_feats)
+        tags = mask = value = None
+        if row_filter is not None:
+            tags, mask, value = row_filter.resolve(tokens.shape[0], gallery.shape[0], eng.device)
+        args = (images, tokens, local, exclude_idx, members, ref_feats, mask, value)
         with torch.cuda.stream(stream):
             ev0 = None
             if self.timing:
                 ev0 = torch.cuda.Event(enable_timing=True)
                 ev0.record(stream)
             if self.graphs:
-                outs = self._replay(lane, eng, stream, args, gallery, k, idx_offset)
+                outs = self._replay(lane, eng, stream, args, gallery, k, idx_offset, tags)
             else:
-                outs = self._step(eng, args, gallery, k, idx_offset)
+                outs = self._step(eng, args, gallery, k, idx_offset, tags)
             ev = torch.cuda.Event(enable_timing=self.timing)
             ev.record(stream)
         if alone:
@@ -177,15 +184,17 @@ class ComposedQueryPipeline:
         return FusedResult(fused, ev, keep)
 
     @staticmethod
-    def _step(eng, args, gallery, k, idx_offset):
-        images, tokens, local, exclude_idx, members, ref_feats = args
+    def _step(eng, args, gallery, k, idx_offset, tags=None):
+        images, tokens, local, exclude_idx, members, ref_feats, mask, value = args
         if ref_feats is None and images.shape[0] == tokens.shape[0]:
             ref, tg, ts = eng.encode_pair(images, tokens)      # both towers in one pass: the text layers' GEMMs ride in the image layers' launches (fp32 / f32x3 / mx8img)
         else:
             ref = eng.encode_image(images) if ref_feats is None else ref_feats
             tg, ts = eng.encode_text(tokens)
         fused = eng.dvr_fuse(ref, local, tg, ts)
-        if k > 64:                                              # deep ranking: every gallery form (fp32, PreparedGallery, bf16)
+        if tags is not None:                                    # filtered ranking: every k <= 1024, every gallery form
+            scores, idx = eng.sim_topk(fused, gallery, k, idx_offset=idx_offset, exclude_idx=exclude_idx, row_filter=RowFilter(tags, mask, value))
+        elif k > 64:                                            # deep ranking: every gallery form (fp32, PreparedGallery, bf16)
             scores, idx = eng.sim_topk_deep(fused, gallery, k, idx_offset=idx_offset, exclude_idx=exclude_idx)
         elif gallery.dtype == torch.bfloat16:
             scores, idx = eng.sim_topk_bf16(fused, gallery, k, idx_offset=idx_offset, exclude_idx=exclude_idx)
@@ -194,9 +203,10 @@ class ComposedQueryPipeline:
         member_scores = eng.gather_scores(fused, gallery, members) if members is not None else None
         return fused, scores, idx, member_scores
 
-    def _replay(self, lane, eng, stream, args, gallery, k, idx_offset):
+    def _replay(self, lane, eng, stream, args, gallery, k, idx_offset, tags=None):
         key = tuple((tuple(a.shape), a.dtype) if a is not None else None for a in args) + (
-            gallery.data_ptr(), tuple(gallery.shape), gallery.dtype, int(k), int(idx_offset), eng.precision)
+            gallery.data_ptr(), tuple(gallery.shape), gallery.dtype, int(k), int(idx_offset), eng.precision,
+            None if tags is None else tags.data_ptr())
         lg = self._lane_graphs[lane].setdefault(key, _LaneGraph())
         if lg.graph is not None and lg.ws_generation != eng.ws_generation():
             stream.synchronize()                                 # the workspace the graph points into was freed: start over
@@ -204,13 +214,14 @@ class ComposedQueryPipeline:
         lg.calls += 1
         if lg.graph is None:
             if lg.calls <= 2:                                    # eager: sizes the workspaces, lets the tile tuner see every shape
-                return self._step(eng, args, gallery, k, idx_offset)
+                return self._step(eng, args, gallery, k, idx_offset, tags)
             lg.inputs = tuple(None if a is None else a.clone() for a in args)
             stream.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=stream):
-                lg.outputs = self._step(eng, lg.inputs, gallery, k, idx_offset)
+                lg.outputs = self._step(eng, lg.inputs, gallery, k, idx_offset, tags)
             lg.graph, lg.ws_generation = graph, eng.ws_generation()
+            lg.tags = tags                                       # the graph reads the filter's tags through their address: keep them alive
         for dst, src in zip(lg.inputs, args):
             if dst is not None:
                 dst.copy_(src, non_blocking=True)

@@ -134,7 +134,30 @@ def build_parser(kind: str) -> ArgumentParser:
                    help="QuickGELU, x * sigmoid(1.702 x), in both CLIP towers' MLPs: open_clip's force_quick_gelu, what it turns on for "
                         "pretrained='openai' -- needed for OpenAI's checkpoints (RN50x4's only public weights); default: the config's own "
                         "setting (exact-erf GELU, QuickGELU for the *-quickgelu names)")
+    if kind in ("fiq", "val"):
+        p.add_argument("--merged-gallery", action="store_true",
+                       help="keep the three categories in ONE gallery (concatenated in category order, tag = category ordinal), fused and prepared "
+                            "once, and rank all queries against it with a per-query row filter -- the same recalls as the three separate indexes")
     return p
+
+
+def merged_category_metrics(kind: str, triples, clip_model, model, device, args):
+    """--merged-gallery: [(recalls of a category)] from one merged, filtered gallery (run/_common.recalls_merged).  Every category's queries
+    are still built against that category's own index features -- the reference image's raw feature is a lookup in them
+    (test_fiq.py:104-107) -- only the ranking sees the merged store."""
+    from . import _common, test_fiq, test_val
+    mod = test_fiq if kind == "fiq" else test_val
+    ks = (10, 50) if kind == "fiq" else test_val.KS
+    feats, locals_, names, predicted, targets = [], [], [], [], []
+    for _, classic, relative in triples:
+        f, n, l = fd.extract_index_features_sharded(classic, clip_model, args.patch_num, device, args.feature_dim,
+                                                    num_workers=0 if args.data_root else args.num_workers)
+        p, t = mod.generate_fiq_val_predictions(clip_model, relative, model, n, f, device, args.feature_dim, args.batch_size, args.num_workers,
+                                                args.clip_model_name)
+        feats.append(f); locals_.append(l); names.append(n); predicted.append(p); targets.append(t)
+    all_feats, all_local, tags, starts = _common.merge_galleries(feats, locals_)
+    index_fused = _common.fuse_index(model, all_feats, all_local, prepared=True)
+    return _common.recalls_merged(model, predicted, index_fused, tags, starts, names, targets, ks)
 
 
 def main(kind: str) -> None:
@@ -171,6 +194,13 @@ def main(kind: str) -> None:
         triples = [(split,) + synthetic_split(kind, cfg, args.feature_dim, args.synthetic_gallery, args.synthetic_queries, args.seed + i)
                    for i, split in enumerate(splits)]
     results = []
+    if getattr(args, "merged_gallery", False):
+        if args.rank_metrics:
+            raise SystemExit("--rank-metrics is not available with --merged-gallery")
+        results = merged_category_metrics(kind, triples, clip_model, model, device, args)
+        for (split, _, _), res in zip(triples, results):
+            say(split, "recalls:", res)
+        triples = []
     for split, classic, relative in triples:
         feats, names, local = fd.extract_index_features_sharded(classic, clip_model, args.patch_num, device, args.feature_dim,
                                                                 num_workers=0 if args.data_root else args.num_workers)

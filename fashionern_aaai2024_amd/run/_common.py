@@ -236,10 +236,17 @@ def _my_rows(q: int):
     return fd.shard_rows(q, rank, world)
 
 
-def _ranked(model, predicted, index_fused, k, exclude=None) -> np.ndarray:
+def _filter_kw(row_filter, start: int, stop: int) -> dict:
+    """The engine keyword of a query slice's row filter -- nothing at all when there is none, so engines that do not know the keyword
+    keep working."""
+    return {} if row_filter is None else {"row_filter": row_filter.rows(start, stop)}
+
+
+def _ranked(model, predicted, index_fused, k, exclude=None, row_filter=None) -> np.ndarray:
     """Top-k gallery rows of every query as a host array [Q, k]: this rank ranks its slice of the queries, the index rows are
     gathered (rank order == query order).  The engine is synchronised before the result is read, so a ranking error the
-    kernels can only flag (fern_sync) raises here instead of being counted as misses."""
+    kernels can only flag (fern_sync) raises here instead of being counted as misses.  `row_filter` (`engine.RowFilter`, mask / value
+    per query or scalar): every query ranks only the rows that are eligible for it."""
     eng = _engine_of(model)
     q = predicted.shape[0]
     start, stop, per = _my_rows(q)
@@ -248,7 +255,7 @@ def _ranked(model, predicted, index_fused, k, exclude=None) -> np.ndarray:
         # the gallery is ranked against once per evaluation, like the reference builds its index once (test_fiq.py:45-46): the
         # prepared form (bf16 pre-filter copy + its certificate) lets the engine pick the cheapest exact form of the stage
         prepared = eng.prepare_gallery(index_fused) if hasattr(eng, "prepare_gallery") and torch.is_tensor(index_fused) else index_fused
-        _, idx = eng.sim_topk(predicted[start:stop], prepared, k, exclude_idx=ex)
+        _, idx = eng.sim_topk(predicted[start:stop], prepared, k, exclude_idx=ex, **_filter_kw(row_filter, start, stop))
     else:
         idx = torch.empty((0, k), dtype=torch.int32, device=predicted.device)
     if hasattr(eng, "sync"):
@@ -273,12 +280,39 @@ def _unique_rows(index_names: Sequence[str], wanted: Sequence[str], what: str) -
     return np.array([row[n] for n in wanted], dtype=np.int64)
 
 
-def recalls_unique(model, predicted, index_fused, index_names, target_names, ks):
-    """FashionIQ / Shoes / VAL: R@k = % of queries whose (unique) target is ranked < k."""
+def recalls_unique(model, predicted, index_fused, index_names, target_names, ks, row_filter=None):
+    """FashionIQ / Shoes / VAL: R@k = % of queries whose (unique) target is ranked < k (`row_filter`: among the eligible rows)."""
     q = len(target_names)
     tgt = _unique_rows(index_names, target_names, "target")
-    hit = _ranked(model, predicted, index_fused, max(ks)) == tgt[:, None]
+    hit = _ranked(model, predicted, index_fused, max(ks), row_filter=row_filter) == tgt[:, None]
     return tuple(_pct(hit[:, :k].sum(), q) for k in ks)
+
+
+def merge_galleries(index_features: Sequence[torch.Tensor], index_local_features: Sequence[torch.Tensor]):
+    """Several galleries (FashionIQ's three categories, run/test/test_fiq.py:157-177) as ONE store: features and local features
+    concatenated in the order given, tag of a row = the ordinal of its gallery, and the row each segment starts at."""
+    sizes = [int(f.shape[0]) for f in index_features]
+    starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    tags = torch.cat([torch.full((n,), c, dtype=torch.int32) for c, n in enumerate(sizes)]) if sizes else torch.zeros(0, dtype=torch.int32)
+    return torch.cat(list(index_features)), torch.cat(list(index_local_features)), tags, starts
+
+
+def recalls_merged(model, predicted: Sequence[torch.Tensor], index_fused, tags: torch.Tensor, starts, index_names: Sequence[Sequence[str]],
+                   target_names: Sequence[Sequence[str]], ks):
+    """`recalls_unique` of every category against the MERGED, fused gallery of `merge_galleries`: all queries are ranked in one
+    call, each only among the rows of its own category (tag == ordinal) -- the per-category rankings of test_fiq.py:157-177, bit for
+    bit.  A target is looked up inside its category's segment, so a name may repeat across categories.  One recall tuple per category."""
+    from ..engine import RowFilter
+    sizes = [int(p.shape[0]) for p in predicted]
+    tgt = np.concatenate([starts[c] + _unique_rows(index_names[c], target_names[c], "target") for c in range(len(sizes))]) if sizes else np.zeros(0, np.int64)
+    value = torch.cat([torch.full((n,), c, dtype=torch.int32) for c, n in enumerate(sizes)])
+    flt = RowFilter(tags.to(predicted[0].device), -1, value.to(predicted[0].device))      # mask: all 32 bits
+    hit = _ranked(model, torch.cat(list(predicted)), index_fused, max(ks), row_filter=flt) == tgt[:, None]
+    out, o = [], 0
+    for n in sizes:
+        out.append(tuple(_pct(hit[o:o + n, :k].sum(), n) for k in ks))
+        o += n
+    return out
 
 
 def recalls_anyhit(model, predicted, index_fused, index_names, target_names, ks):
@@ -320,11 +354,12 @@ def recalls_cirr(model, predicted, index_fused, index_names, reference_names, ta
     return grp + glob                                          # (G@1,G@2,G@3,R@1,R@5,R@10,R@50) test_cirr.py:80
 
 
-def target_ranks(model, predicted, index_fused, rows, exclude=None) -> np.ndarray:
+def target_ranks(model, predicted, index_fused, rows, exclude=None, row_filter=None) -> np.ndarray:
     """The 0-based place of gallery rows `rows` ([Q] or [Q, m]; -1 = no target) in every query's full ranking -- what the reference
     reads off its argsort (test_fiq.py:49-60) -- as a host int32 array [Q, m]; -1 where there is no target or the target is the
     query's excluded row.  No depth limit: the engine counts the rows that outrank each target (FernEngine.rank_of).  Query slices go
-    per rank and the rows are gathered, as in `_ranked`."""
+    per rank and the rows are gathered, as in `_ranked`.  `row_filter`: the place among the rows that are eligible for the query, -1 for
+    a target that is not eligible itself."""
     eng = _engine_of(model)
     rows = np.asarray(rows)
     rows = (rows[:, None] if rows.ndim == 1 else rows).astype(np.int32)
@@ -332,7 +367,7 @@ def target_ranks(model, predicted, index_fused, rows, exclude=None) -> np.ndarra
     start, stop, per = _my_rows(q)
     ex = None if exclude is None else torch.as_tensor(np.asarray(exclude)[start:stop], dtype=torch.int32)
     if stop > start:
-        ranks = eng.rank_of(predicted[start:stop], index_fused, torch.as_tensor(rows[start:stop]), exclude_idx=ex)
+        ranks = eng.rank_of(predicted[start:stop], index_fused, torch.as_tensor(rows[start:stop]), exclude_idx=ex, **_filter_kw(row_filter, start, stop))
     else:
         ranks = torch.empty((0, m), dtype=torch.int32, device=predicted.device)
     if hasattr(eng, "sync"):

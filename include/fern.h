@@ -380,6 +380,38 @@ FERN_API int fern_rank_keys(fern_ctx* ctx, const float* q /*[B,D]*/, const float
 FERN_API int fern_rank_count(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
                              const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const uint64_t* keys /*[B,m]*/, int m,
                              int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/, int32_t* out_count /*[B,m]*/, void* stream);
+/* Filtered ranking: per-query gallery row filters.  The reference never ranks against everything it has encoded: it builds one index
+ * per FashionIQ category and ranks each query inside its own (run/test/test_fiq.py:157-177), and ranks CIRR's target inside the query's
+ * six-member img_set (run/test/test_cirr.py:63-66).  Here the gallery carries one 32-bit tag per row, tags[N] (device), a query carries
+ * mask[b] and value[b], and row n is ELIGIBLE for query b iff
+ *     (tags[n] & mask[b]) == value[b]
+ * mask = value = 0 accepts every row; bit fields give equality on several attributes at once (a live bit, a category field, a group id);
+ * a value with bits outside mask matches nothing, which is a valid, empty filter.  The result is the unfiltered exact ranking with the
+ * ineligible rows removed: the same score bits, the same order (score descending, global index ascending), idx_offset / exclude_idx as
+ * for the unfiltered entry points, unfilled places -inf / -1.  The predicate is applied where scores are produced (ineligible pairs are
+ * stored as -inf) and again wherever exact scores are recomputed from the gallery, so an ineligible row is never rescored and never
+ * leaves a fallback.  Asynchronous on `stream`, nothing read back, graph-capturable after one warm-up call.
+ * fern_sim_topk_filtered: the arguments of fern_sim_topk_deep + the filter; 1 <= K <= 1024; the gallery form follows from the pointers as
+ * there (fp32 only, fp32 + bf16 copy + meta, bf16 only), with the same constraints on D.  tags == NULL is an argument error: unfiltered
+ * callers keep the entry points above.  Routing (every route returns the same bits):
+ *   masked dense form   K <= 64, a prepared gallery (all three pointers), D % 64 == 0, D <= 768, min(B, 1024) * N * 4 bytes of scores
+ *                       <= 1.1e9: the bf16 sweep stores masked scores (and masked tile maxima), the dense form's select kernels run on them;
+ *   deep stage          everything else: fern_sim_topk_deep's stage on masked score rows.
+ * fern_rank_set_strategy: FERN_RANK_PLAIN forces exact fp32 scores (the bf16 copy is not read); FERN_RANK_DENSE forces the masked dense
+ * form wherever it is offered (which is also what FERN_RANK_AUTO does); FERN_RANK_LISTS has no filtered form and behaves as AUTO. */
+FERN_API int fern_sim_topk_filtered(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                                    const uint16_t* gallery_bf16 /*[N,D] or NULL*/, const float* meta /*[4] device or NULL*/, int B, int64_t N,
+                                    int D, int K, float* out_scores /*[B,K]*/, int32_t* out_idx /*[B,K]*/, int64_t idx_offset,
+                                    const int32_t* exclude_idx, const uint32_t* tags /*[N]*/, const uint32_t* mask /*[B]*/,
+                                    const uint32_t* value /*[B]*/, void* stream);
+/* fern_rank_count_filtered: fern_rank_count over the rows that are eligible for each query (the per-category ranks of
+ * run/test/test_fiq.py:157-177, the img_set ranks of run/test/test_cirr.py:63-66): the arguments of fern_rank_count + the filter, same
+ * predicate; an ineligible row is not counted.  fern_rank_keys needs no filtered form: a row's key does not depend on a filter (whether a
+ * TARGET is eligible is the caller's question: a count is returned for any non-zero key). */
+FERN_API int fern_rank_count_filtered(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                                      const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const uint64_t* keys /*[B,m]*/,
+                                      int m, int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/, int32_t* out_count /*[B,m]*/,
+                                      const uint32_t* tags /*[N]*/, const uint32_t* mask /*[B]*/, const uint32_t* value /*[B]*/, void* stream);
 /* scores of explicitly named gallery rows (CIRR subset ranking, run/test/test_cirr.py:64-66);
  * idx < 0 -> -inf */
 FERN_API int fern_gather_scores(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D]*/,
