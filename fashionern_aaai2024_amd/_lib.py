@@ -76,6 +76,14 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fern_rank_count_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_i64, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fern_sim_topk_items": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fern_item_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_void_p, c_int, c_i64, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fern_item_keys": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_void_p, c_int, c_i64, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fern_item_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_void_p, c_int, c_i64, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fern_rank_set_strategy": (c_int, [c_void_p, c_int]),
     "fern_sweep_bf16_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
     "fern_gather_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -2189,6 +2189,149 @@ extern "C" int fern_sim_topk_deep(fern_ctx* c, const float* q, const float* gall
                               stream);
 }
 
+// Item-level ranking (include/fern.h: fern_sim_topk_items, fern_item_rank; items.hip), per query chunk: the deep stage's score rows S [m, ld]
+// (exact: the fp32 MFMA chain; bf16: the sweep's store form), the table best [m, G] of every item's greatest key, then
+//   top-K    every row but its item's representative becomes -inf and the deep stage's select + radix fallback run unchanged on the rows
+//            (margin 0: the stored scores are the ranking scores), out_item is gathered from out_idx;
+//   ranks    a count over the table per target.
+// A chunk keeps its score rows plus its table inside the deep stage's 1.1 GB budget.  Nothing is read back.
+struct ItemArgs {
+    const float* q; const float* gallery; const uint16_t* gallery_bf16;
+    int B; int64_t N; int D;
+    const int32_t* items; int G;
+    int64_t idx_offset; const int32_t* exclude_idx;
+    const uint32_t *tags, *mask, *value;
+};
+static int item_args_check(const std::string& fn, fern_ctx* c, const ItemArgs& a, long* ld, long* chunk) {
+    if (!c) return fail(FERN_ERR_ARG, fn + ": ctx is NULL");
+    if (a.B < 0 || a.N < 0 || a.D <= 0) return fail(FERN_ERR_ARG, fn + ": need B >= 0, N >= 0, D > 0");
+    if (a.G < 1) return fail(FERN_ERR_ARG, fn + ": need G >= 1");
+    if (!a.items) return fail(FERN_ERR_ARG, fn + ": items is NULL");
+    if (!a.gallery && !a.gallery_bf16) return fail(FERN_ERR_ARG, fn + ": gallery and gallery_bf16 are both NULL");
+    if (a.gallery) {
+        if (a.D % 32) return fail(FERN_ERR_ARG, fn + ": the fp32 form needs D % 32 == 0");
+    } else if (a.D % 64 || a.D > 768) {
+        return fail(FERN_ERR_ARG, fn + ": a bf16-only gallery needs D % 64 == 0, D <= 768");
+    }
+    if (a.B && !a.q) return fail(FERN_ERR_ARG, fn + ": NULL argument");
+    if (a.tags && a.B && (!a.mask || !a.value)) return fail(FERN_ERR_ARG, fn + ": mask or value is NULL");
+    if (a.N > 0x7FFFFFF0LL) return fail(FERN_ERR_ARG, fn + ": N too large for int32 indices");
+    *ld = std::max<long>(4, (a.N + 3) & ~3L);
+    // queries per chunk: the [m, ld] fp32 score rows and the [m, G] 64-bit table stay within the deep stage's budget (sim_topk_deep_impl)
+    *chunk = std::min<long>((long)kRankQueryChunk, (long)(1.1e9 / ((double)*ld * 4 + (double)a.G * 8)));
+    if (*chunk < 1) return fail(FERN_ERR_ARG, fn + ": one query's score row and item table exceed the 1.1 GB workspace budget");
+    return FERN_OK;
+}
+// score rows of queries o .. o + m and their table; *flags (4 ints) is zeroed on the stream for the selection that may follow
+static int item_chunk_table(fern_ctx* c, const ItemArgs& a, long o, int m, long ld, float** S_out, int** flags_out, int** state_out,
+                            unsigned long long** best_out, ItemRows* rows_out, StageTimer& st, hipStream_t s) {
+    float* S; int *flags, *state; unsigned long long* best;
+    FERN_TRY(ws_get(c, (size_t)m * ld, &S));
+    FERN_TRY(ws_get(c, (size_t)4, &flags));
+    FERN_TRY(ws_get(c, (size_t)m, &state));
+    FERN_TRY(ws_get(c, (size_t)m * a.G, &best));
+    const float* qo = a.q + o * a.D;
+    const RowTags ro = a.tags ? RowTags{a.tags, a.mask + o, a.value + o} : RowTags{nullptr, nullptr, nullptr};
+    st.sweep_begin();
+    if (a.N == 0) {
+        HIP_TRY(hipMemsetAsync(flags, 0, 4 * sizeof(int), s));
+    } else if (a.gallery) {
+        HIP_TRY(launch_deep_exact_scores(qo, a.gallery, m, a.N, a.D, S, ld, flags, state, 0, s, &ro));      // also zeroes flags
+        st.sweep_end((double)a.N * a.D * 4 + (double)m * a.D * 4 + (double)m * a.N * 4);
+    } else {
+        for (long b0 = 0; b0 < m; b0 += 64) {
+            const int mb = (int)std::min<long>(64, m - b0);
+            const RowTags rb{ro.tags, ro.tags ? ro.mask + b0 : nullptr, ro.tags ? ro.value + b0 : nullptr};
+            HIP_TRY(launch_sweep_bf16(qo + b0 * a.D, a.gallery_bf16, S + b0 * ld, ld, mb, a.N, a.D, a.N, 1, nullptr, nullptr, s, b0 == 0 ? flags : nullptr,
+                                      nullptr, 0, &rb));
+            st.sweep_end((double)a.N * a.D * 2 + (double)mb * a.D * 4 + (double)mb * a.N * 4);
+        }
+    }
+    const ItemRows rows{a.items, a.G, (long)a.N, (long)a.idx_offset, a.exclude_idx ? a.exclude_idx + o : nullptr, ro, 0};
+    HIP_TRY(hipMemsetAsync(best, 0, (size_t)m * a.G * sizeof(unsigned long long), s));      // on the stream, behind the score kernels: inside the timed stage, re-run by a replayed graph
+    HIP_TRY(launch_item_best(S, ld, m, rows, best, s));
+    *S_out = S; *flags_out = flags; *state_out = state; *best_out = best; *rows_out = rows;
+    return FERN_OK;
+}
+
+extern "C" int fern_sim_topk_items(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D, int K,
+                                   const int32_t* items, int G, float* out_scores, int32_t* out_idx, int32_t* out_item, int64_t idx_offset,
+                                   const int32_t* exclude_idx, const uint32_t* tags, const uint32_t* mask, const uint32_t* value, void* stream) {
+    const std::string fn("fern_sim_topk_items");
+    if (K < 1 || K > 1024) return fail(FERN_ERR_ARG, fn + ": need 1<=K<=1024");
+    const ItemArgs a{q, gallery, gallery_bf16, B, N, D, items, G, idx_offset, exclude_idx, tags, mask, value};
+    long ld, chunk;
+    FERN_TRY(item_args_check(fn, c, a, &ld, &chunk));
+    if (B && (!out_scores || !out_idx || !out_item)) return fail(FERN_ERR_ARG, fn + ": NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    for (long o = 0; o < B; o += chunk) {
+        const int m = (int)std::min<long>(chunk, B - o);
+        FERN_TRY(ws_begin(c, s));
+        float* S; int *flags, *state; unsigned long long* best; ItemRows rows;
+        StageTimer st(c, s);
+        FERN_TRY(item_chunk_table(c, a, o, m, ld, &S, &flags, &state, &best, &rows, st, s));
+        HIP_TRY(launch_item_keep_best(S, ld, m, rows, best, s));
+        HIP_TRY(launch_deep_select(S, ld, N, m, K, nullptr, nullptr, nullptr, D, rows.exclude, idx_offset, out_scores + o * K, out_idx + o * K, flags, state, s));
+        if (N > 0) HIP_TRY(launch_deep_fallback(S, ld, N, m, K, rows.exclude, idx_offset, out_scores + o * K, out_idx + o * K, flags, state, s));
+        HIP_TRY(launch_item_gather(out_idx + o * K, m, K, items, N, G, idx_offset, out_item + o * K, s));
+        st.commit(m, (int)N, D);
+    }
+    return FERN_OK;
+}
+
+// keys_in null: the targets' own keys (best[b][target_items[b][j]]); out_keys / out_rank may be null (fern_item_keys / fern_item_count)
+static int item_rank_impl(const std::string& fn, fern_ctx* c, const ItemArgs& a, const int32_t* target_items, const uint64_t* keys_in, int m,
+                          uint64_t* out_keys, int32_t* out_rank, void* stream) {
+    long ld, chunk;
+    FERN_TRY(item_args_check(fn, c, a, &ld, &chunk));
+    if (m < 1) return fail(FERN_ERR_ARG, fn + ": need m >= 1");
+    if (a.B && ((!target_items && !keys_in) || (!out_keys && !out_rank))) return fail(FERN_ERR_ARG, fn + ": NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    for (long o = 0; o < a.B; o += chunk) {
+        const int mq = (int)std::min<long>(chunk, a.B - o);
+        FERN_TRY(ws_begin(c, s));
+        float* S; int *flags, *state; unsigned long long *best, *keys; ItemRows rows;
+        StageTimer st(c, s);
+        FERN_TRY(item_chunk_table(c, a, o, mq, ld, &S, &flags, &state, &best, &rows, st, s));
+        if (keys_in) {
+            keys = const_cast<unsigned long long*>(reinterpret_cast<const unsigned long long*>(keys_in)) + o * m;
+        } else {
+            if (out_keys) keys = reinterpret_cast<unsigned long long*>(out_keys) + o * m;
+            else FERN_TRY(ws_get(c, (size_t)mq * m, &keys));
+            HIP_TRY(launch_item_keys(best, a.G, target_items + o * m, mq, m, keys, s));
+        }
+        if (out_rank) HIP_TRY(launch_item_count(best, a.G, keys, mq, m, out_rank + o * m, s));
+        st.commit(mq, (int)a.N, a.D);
+    }
+    return FERN_OK;
+}
+
+extern "C" int fern_item_rank(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                              const int32_t* items, int G, const int32_t* target_items, int m, int64_t idx_offset, const int32_t* exclude_idx,
+                              int32_t* out_rank, const uint32_t* tags, const uint32_t* mask, const uint32_t* value, void* stream) {
+    const ItemArgs a{q, gallery, gallery_bf16, B, N, D, items, G, idx_offset, exclude_idx, tags, mask, value};
+    if (B && (!target_items || !out_rank)) return fail(FERN_ERR_ARG, "fern_item_rank: NULL argument");
+    return item_rank_impl("fern_item_rank", c, a, target_items, nullptr, m, nullptr, out_rank, stream);
+}
+
+extern "C" int fern_item_keys(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                              const int32_t* items, int G, const int32_t* target_items, int m, int64_t idx_offset, const int32_t* exclude_idx,
+                              uint64_t* out_keys, const uint32_t* tags, const uint32_t* mask, const uint32_t* value, void* stream) {
+    const ItemArgs a{q, gallery, gallery_bf16, B, N, D, items, G, idx_offset, exclude_idx, tags, mask, value};
+    if (B && (!target_items || !out_keys)) return fail(FERN_ERR_ARG, "fern_item_keys: NULL argument");
+    return item_rank_impl("fern_item_keys", c, a, target_items, nullptr, m, out_keys, nullptr, stream);
+}
+
+extern "C" int fern_item_count(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                               const int32_t* items, int G, const uint64_t* keys, int m, int64_t idx_offset, const int32_t* exclude_idx,
+                               int32_t* out_count, const uint32_t* tags, const uint32_t* mask, const uint32_t* value, void* stream) {
+    const ItemArgs a{q, gallery, gallery_bf16, B, N, D, items, G, idx_offset, exclude_idx, tags, mask, value};
+    if (B && (!keys || !out_count)) return fail(FERN_ERR_ARG, "fern_item_count: NULL argument");
+    return item_rank_impl("fern_item_count", c, a, nullptr, keys, m, nullptr, out_count, stream);
+}
+
 // Filtered ranking (include/fern.h: fern_sim_topk_filtered): the exact ranking of the rows that are eligible for each query.  Two forms,
 // the same bits from both:
 //   masked dense form   K <= 64, a prepared gallery (fp32 + bf16 copy + meta), a shape the bf16 sweep takes, the dense form's score budget,

@@ -506,4 +506,28 @@ hipError_t launch_deep_fallback(const float* S, long ld, long N, int B, int K, c
 // launch_topk_merge for 64 < K <= 1024, R * K <= 16 384.
 hipError_t launch_topk_merge_deep(const float* scores, const int* idx, float* out_scores, int* out_idx, int R, int B, int K, hipStream_t s);
 
+// ---- item-level ranking (items.hip): galleries whose rows belong to items -------------------------------------------------------------
+// Which rows of a stored score matrix S [B, ld] can represent an item, and under which key: row n of query b carries
+// make_key(S[b][n], n + idx_offset) if n < N, n is not the query's excluded row (exclude[b] - idx_offset), the row is eligible under rt,
+// items[n] is inside [0, G) and the score is above -inf; 0 otherwise.
+struct ItemRows {
+    const int* items;                     // [N] item id per gallery row
+    int G;                                // number of items: ids outside [0, G) belong to no item
+    long N;
+    long idx_offset;                      // key index (and exclude's frame) of local row n is n + idx_offset
+    const int* exclude;                   // [B] global row index that represents nothing per query, or null
+    RowTags rt;                           // tags null: unfiltered; mask / value point at the first query of the launch
+    int aligned;                          // set by the launchers: items is 16-byte aligned
+};
+// best [B, G] (zero before): best[b][g] = the greatest key among the rows of item g, 0 when none can represent it.  ld % 4 == 0, ld >= N
+// rounded up to 4.
+hipError_t launch_item_best(const float* S, long ld, int B, const ItemRows& r, unsigned long long* best, hipStream_t s);
+// S[b][n] = -inf unless row n is the representative of its item (its key equals best[b][items[n]]): what launch_deep_select ranks.
+hipError_t launch_item_keep_best(float* S, long ld, int B, const ItemRows& r, const unsigned long long* best, hipStream_t s);
+// out_item[b][k] = items[idx[b][k] - idx_offset], -1 for idx < 0 (an unfilled place)
+hipError_t launch_item_gather(const int* idx, int B, int K, const int* items, long N, int G, long idx_offset, int* out_item, hipStream_t s);
+// keys[b][j] = best[b][targets[b][j]], 0 for an id outside [0, G); out[b][j] = #{g : best[b][g] > keys[b][j]}, -1 for a key of 0
+hipError_t launch_item_keys(const unsigned long long* best, int G, const int* targets, int B, int m, unsigned long long* keys, hipStream_t s);
+hipError_t launch_item_count(const unsigned long long* best, int G, const unsigned long long* keys, int B, int m, int* out, hipStream_t s);
+
 }  // namespace fern

@@ -235,6 +235,77 @@ def rank_of_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: i
     return counts[:, 0] if flat else counts
 
 
+def _require_unsplit_items(items) -> None:
+    """The item-level sharded helpers need every item's rows inside ONE shard.  Checked cheaply: the (min id, max id) of every shard's
+    rows (ids outside [0, n_items) belong to no item) are all-gathered and must be disjoint ranges -- which contiguous items sharded at
+    item boundaries give.  Every rank sees the same ranges, so every rank raises."""
+    rank, world = world_info()
+    if world == 1:
+        return
+    ids = items.items
+    ids = ids[(ids >= 0) & (ids < items.n_items)]
+    span = torch.tensor([int(ids.min()), int(ids.max())] if ids.numel() else [0, -1], dtype=torch.int64, device=items.items.device)
+    spans = torch.empty((world, 2), dtype=torch.int64, device=span.device)
+    _all_gather_into(spans, span)
+    held = sorted((lo, hi, r) for r, (lo, hi) in enumerate(spans.tolist()) if hi >= lo)
+    for (lo_a, hi_a, ra), (lo_b, hi_b, rb) in zip(held, held[1:]):
+        if lo_b <= hi_a:
+            raise ValueError(f"item ids of rank {ra} [{lo_a}, {hi_a}] and rank {rb} [{lo_b}, {hi_b}] overlap: item-level sharded ranking needs "
+                             "every item's rows inside one shard (shard the gallery at item boundaries)")
+
+
+def rank_items_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: int, items, k: int, exclude_idx=None, row_filter=None):
+    """Gallery-sharded item-level ranking of the SAME query batch on every rank (`FernEngine.sim_topk_items` on the whole gallery).
+    `items`: the SHARD's `ItemMap` (`ItemMap.rows(start, stop)`: global ids); NO ITEM MAY HAVE ROWS IN TWO SHARDS (ValueError otherwise,
+    `_require_unsplit_items`).  Then a shard's list holds the true representative of every item it lists, the lists share no item and
+    merge like row lists (`topk_merge`); the item ids travel beside the merge and are looked up by the merged global row index.
+    Returns (scores, idx, item) on every rank."""
+    rank, world = world_info()
+    _require_unsplit_items(items)
+    kw = {} if row_filter is None else {"row_filter": row_filter}
+    s, i, it = engine.sim_topk_items(queries, gallery_shard, items, k, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
+    if world == 1:
+        return s, i, it
+    b, kk = s.shape
+    all_s = torch.empty((world * b, kk), dtype=s.dtype, device=s.device)      # concatenated along dim 0 == [world, B, K]
+    all_i = torch.empty((world * b, kk), dtype=i.dtype, device=i.device)
+    all_t = torch.empty((world * b, kk), dtype=it.dtype, device=it.device)
+    _all_gather_into(all_s, s)
+    _all_gather_into(all_i, i)
+    _all_gather_into(all_t, it)
+    ms, mi = engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
+    # a global row index appears in one list only: sort each query's gathered indices once, look the merged ones up
+    cat_i = all_i.view(world, b, kk).permute(1, 0, 2).reshape(b, world * kk).to(torch.int64)
+    cat_t = all_t.view(world, b, kk).permute(1, 0, 2).reshape(b, world * kk)
+    sorted_i, perm = cat_i.sort(dim=1)
+    pos = torch.searchsorted(sorted_i, mi.to(torch.int64).contiguous()).clamp(max=world * kk - 1)
+    mt = cat_t.gather(1, perm.gather(1, pos))
+    return ms, mi, torch.where(mi >= 0, mt, torch.full_like(mt, -1))
+
+
+def item_rank_of_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: int, items, target_items, exclude_idx=None, row_filter=None):
+    """Gallery-sharded item-level target ranks (`FernEngine.item_rank_of` on the whole gallery), under the same requirement as
+    `rank_items_sharded`.  The key of a target item is its representative's, from the shard that owns the item -- every other rank
+    contributes 0, so the int64 SUM all-reduce is exact -- then every rank counts the items of its shard whose representative outranks
+    the key and the counts are SUM-reduced; a shard that does not own the target counts against the owner's key and so adds its items, never
+    a -1.  Returns int32 shaped like `target_items` on every rank; -1 for an id outside [0, n_items) or an item without an eligible row."""
+    rank, world = world_info()
+    _require_unsplit_items(items)
+    t = torch.as_tensor(target_items)
+    flat = t.dim() == 1
+    t2 = (t[:, None] if flat else t).to(dtype=torch.int32)
+    kw = {} if row_filter is None else {"row_filter": row_filter}
+    if world == 1:
+        ranks = engine.item_rank_of(queries, gallery_shard, items, t2, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
+        return ranks[:, 0] if flat else ranks
+    keys = engine.item_keys(queries, gallery_shard, items, t2, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
+    _all_reduce_sum(keys)
+    counts = engine.item_count(queries, gallery_shard, items, keys, idx_offset=shard_start, exclude_idx=exclude_idx, **kw).clamp(min=0)
+    _all_reduce_sum(counts)                              # an item without a key is -1 on every rank: summed as 0, restored here
+    counts = torch.where(keys == 0, torch.full_like(counts, -1), counts)
+    return counts[:, 0] if flat else counts
+
+
 def share_gemm_tiles(engine, src: int = 0) -> None:
     """Every rank adopts rank `src`'s GEMM tile choices (the per-shape tuner runs independently in each process; all choices
     give bit-identical results, but different tiles run at slightly different speeds and a multi-GPU step is as slow as its

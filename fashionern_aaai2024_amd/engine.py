@@ -119,6 +119,42 @@ class RowFilter:
         return tuple(out)
 
 
+class ItemMap:
+    """Which item every gallery row belongs to (include/fern.h: fern_sim_topk_items): `items` [N] holds one integer id per row, ids in
+    [0, n_items) -- Fashion200k's captions (many gallery rows share one, run/test/test_200k.py:52-60), a product's photographs.  A row
+    whose id is outside that range belongs to no item and is ignored by the item-level ranking.  `n_items` defaults to max id + 1,
+    computed once here (one read-back, at construction and never per call)."""
+
+    __slots__ = ("items", "n_items")
+
+    def __init__(self, items, n_items: Optional[int] = None):
+        t = torch.as_tensor(items)
+        if t.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+            raise ValueError(f"items must be an integer tensor, got {t.dtype}")
+        if t.dim() != 1:
+            raise ValueError(f"items must be [N], got {tuple(t.shape)}")
+        if t.dtype != torch.int32:
+            if t.numel() and (int(t.min()) < -(1 << 31) or int(t.max()) >= (1 << 31)):
+                raise ValueError("item ids do not fit int32")
+            t = t.to(torch.int32)
+        if n_items is None:
+            n_items = int(t.max()) + 1 if t.numel() else 1
+        n_items = int(n_items)
+        if n_items < 1:
+            raise ValueError(f"n_items must be >= 1, got {n_items}")
+        self.items, self.n_items = t.contiguous(), n_items
+
+    def rows(self, start: int, stop: int) -> "ItemMap":
+        """The map of the gallery rows [start, stop) (a shard): ids stay global, n_items stays."""
+        return ItemMap(self.items[start:stop], self.n_items)
+
+    def resolve(self, n: int, device) -> torch.Tensor:
+        """The ids as a contiguous int32 tensor on `device`; raises when the gallery has another number of rows."""
+        if self.items.shape[0] != n:
+            raise ValueError(f"items has {self.items.shape[0]} entries, the gallery has {n} rows")
+        return self.items.to(device).contiguous()
+
+
 class FernEngine:
     """One native context on one GPU.  Not thread-safe (one per device per process)."""
 
@@ -593,6 +629,72 @@ class FernEngine:
             keys = torch.where(ok, keys, torch.zeros_like(keys))
         ranks = self.rank_count(q, gallery, keys, idx_offset, exclude_idx, row_filter)
         return ranks[:, 0] if flat else ranks
+
+    # ---- item-level ranking -----------------------------------------------------------------------
+    def _item_call(self, q, gallery, items, exclude_idx, row_filter):
+        """Shared argument handling of the item entry points: (q, g32, g16, n, items, n_items, exclude, (tags, mask, value))."""
+        if not isinstance(items, ItemMap):
+            raise TypeError("items must be an ItemMap")
+        q, g32, g16 = self._rank_forms(q, gallery)
+        g = g32 if g32 is not None else g16
+        b, n = q.shape[0], g.shape[0]
+        it = items.resolve(n, self.device)
+        filt = (None, None, None)
+        if row_filter is not None:
+            if not isinstance(row_filter, RowFilter):
+                raise TypeError("row_filter must be a RowFilter")
+            filt = row_filter.resolve(b, n, self.device)
+        return q, g32, g16, n, it, items.n_items, self._exclude(exclude_idx, b), filt
+
+    def sim_topk_items(self, q, gallery, items: ItemMap, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
+        """Item-level exact top-K, 1 <= k <= 1024 (include/fern.h: fern_sim_topk_items): the row ranking of `sim_topk_deep` (exclude_idx
+        and `row_filter` applied first) with every row but the first of its item removed.  Returns (scores, idx, item) [B,k]: the
+        representative row's score, its global index and its item id; unfilled places -inf / -1 / -1.  `gallery`: an fp32 tensor or a
+        `PreparedGallery` (exact fp32-chain scores) or a bf16 tensor (the bf16 similarity)."""
+        q, g32, g16, n, it, g_items, ex, (tags, mask, value) = self._item_call(q, gallery, items, exclude_idx, row_filter)
+        b = q.shape[0]
+        scores = self._empty(b, k)
+        idx = self._empty(b, k, dtype=torch.int32)
+        item = self._empty(b, k, dtype=torch.int32)
+        _lib.check(self.lib.fern_sim_topk_items(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, n, q.shape[1], int(k), _ptr(it), g_items, _ptr(scores),
+                                                _ptr(idx), _ptr(item), int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask), _ptr(value), _stream()),
+                   "fern_sim_topk_items")
+        return scores, idx, item
+
+    def item_rank_of(self, q, gallery, items: ItemMap, target_items, idx_offset: int = 0, exclude_idx=None,
+                     row_filter: Optional[RowFilter] = None) -> torch.Tensor:
+        """int32, shaped like `target_items` ([B] or [B,m]): the number of items that come before each target item in the ranking
+        `sim_topk_items` defines, at any depth (include/fern.h: fern_item_rank); -1 for an id outside [0, n_items) or an item without
+        an eligible row for the query."""
+        flat = torch.as_tensor(target_items).dim() == 1
+        q, g32, g16, n, it, g_items, ex, (tags, mask, value) = self._item_call(q, gallery, items, exclude_idx, row_filter)
+        tg = self._per_query(target_items, q.shape[0], torch.int32, "target_items")
+        ranks = self._empty(*tg.shape, dtype=torch.int32)
+        _lib.check(self.lib.fern_item_rank(self._h, _ptr(q), _ptr(g32), _ptr(g16), q.shape[0], n, q.shape[1], _ptr(it), g_items, _ptr(tg), tg.shape[1],
+                                           int(idx_offset), _ptr(ex), _ptr(ranks), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_item_rank")
+        return ranks[:, 0] if flat else ranks
+
+    def item_keys(self, q, gallery, items: ItemMap, target_items, idx_offset: int = 0, exclude_idx=None,
+                  row_filter: Optional[RowFilter] = None) -> torch.Tensor:
+        """int64 [B,m]: the bits of the ranking key of each target item's representative row in this gallery (shard); 0 when the shard
+        holds no eligible row of the item (include/fern.h: fern_item_keys)."""
+        q, g32, g16, n, it, g_items, ex, (tags, mask, value) = self._item_call(q, gallery, items, exclude_idx, row_filter)
+        tg = self._per_query(target_items, q.shape[0], torch.int32, "target_items")
+        keys = self._empty(*tg.shape, dtype=torch.int64)
+        _lib.check(self.lib.fern_item_keys(self._h, _ptr(q), _ptr(g32), _ptr(g16), q.shape[0], n, q.shape[1], _ptr(it), g_items, _ptr(tg), tg.shape[1],
+                                           int(idx_offset), _ptr(ex), _ptr(keys), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_item_keys")
+        return keys
+
+    def item_count(self, q, gallery, items: ItemMap, keys, idx_offset: int = 0, exclude_idx=None,
+                   row_filter: Optional[RowFilter] = None) -> torch.Tensor:
+        """int32 [B,m]: per key the number of this gallery's (shard's) items whose representative's key is greater; -1 for a key of 0
+        (include/fern.h: fern_item_count).  Counts of shards that share no item add up."""
+        q, g32, g16, n, it, g_items, ex, (tags, mask, value) = self._item_call(q, gallery, items, exclude_idx, row_filter)
+        ky = self._per_query(keys, q.shape[0], torch.int64, "keys")
+        count = self._empty(*ky.shape, dtype=torch.int32)
+        _lib.check(self.lib.fern_item_count(self._h, _ptr(q), _ptr(g32), _ptr(g16), q.shape[0], n, q.shape[1], _ptr(it), g_items, _ptr(ky), ky.shape[1],
+                                            int(idx_offset), _ptr(ex), _ptr(count), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_item_count")
+        return count
 
     def gallery_to_bf16(self, gallery) -> torch.Tensor:
         """fp32 [N,D] -> bf16 [N,D] (round to nearest even) for `sim_topk_bf16`."""

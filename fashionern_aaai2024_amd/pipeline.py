@@ -12,16 +12,17 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .engine import FernEngine, RowFilter
+from .engine import FernEngine, ItemMap, RowFilter
 
 
 class QueryResult:
     """Top-K of one submitted batch; `scores` / `idx` are valid on the caller's stream after `wait()`."""
 
     def __init__(self, scores: torch.Tensor, idx: torch.Tensor, fused: torch.Tensor, event: torch.cuda.Event, member_scores=None,
-                 start_event: Optional[torch.cuda.Event] = None):
+                 start_event: Optional[torch.cuda.Event] = None, item: Optional[torch.Tensor] = None):
         self.scores, self.idx, self.fused, self._event, self.member_scores = scores, idx, fused, event, member_scores
         self._start = start_event
+        self.item = item      # submit(items=...): the item id of every place [B,k]; None for a row-level ranking
 
     @property
     def start_event(self) -> Optional[torch.cuda.Event]:
@@ -38,8 +39,9 @@ class QueryResult:
     def wait(self) -> Tuple[torch.Tensor, torch.Tensor]:
         cur = torch.cuda.current_stream()
         cur.wait_event(self._event)
-        for t in (self.scores, self.idx, self.fused):
-            t.record_stream(cur)
+        for t in (self.scores, self.idx, self.fused, self.item):
+            if t is not None:
+                t.record_stream(cur)
         return self.scores, self.idx
 
 
@@ -116,7 +118,7 @@ class ComposedQueryPipeline:
 
     def submit(self, images: Optional[torch.Tensor], tokens: torch.Tensor, local: torch.Tensor, gallery: torch.Tensor, k: int,
                exclude_idx=None, members=None, idx_offset: int = 0, ref_feats: Optional[torch.Tensor] = None,
-               row_filter: Optional[RowFilter] = None) -> QueryResult:
+               row_filter: Optional[RowFilter] = None, items: Optional[ItemMap] = None) -> QueryResult:
         """images [B,3,S,S], tokens [B,77] int64, local [B,13,D] (device tensors), fused gallery [N,D] fp32 -- or a `PreparedGallery`
         of it (engine.prepare_gallery: the same exact fp32 ranking through the certified bf16 pre-filter, the form a serving process
         keeps), or bf16, which selects the bf16 sweep -- -> QueryResult.  `exclude_idx` [B] drops one gallery index per query and `members` [B,m]
@@ -125,7 +127,9 @@ class ComposedQueryPipeline:
         reference image's RAW feature is looked up in the gallery index instead of being encoded again (test_fiq.py:104-107), so
         the step is text tower + fusion + rank.  `row_filter` (`RowFilter`): each query ranks only the gallery rows that are eligible
         for it -- one store for several categories, withdrawn rows hidden without re-preparing the gallery; its tags are a static
-        pointer of a captured graph, its per-query mask / value travel through the lane's static buffers like `exclude_idx`."""
+        pointer of a captured graph, its per-query mask / value travel through the lane's static buffers like `exclude_idx`.  `items`
+        (`ItemMap`): the ranking is item-level (engine.sim_topk_items: one place per item, represented by its best eligible row) and
+        `QueryResult.item` holds the item id of every place; the ids are a static pointer of a captured graph, like the tags."""
         if (images is None) == (ref_feats is None):
             raise ValueError("give either images (encoded per query) or ref_feats (looked up in the index), not both / neither")
         if members is not None and gallery.dtype != torch.float32:
@@ -139,6 +143,11 @@ class ComposedQueryPipeline:
         tags = mask = value = None
         if row_filter is not None:
             tags, mask, value = row_filter.resolve(tokens.shape[0], gallery.shape[0], eng.device)
+        item_ids = None
+        if items is not None:
+            if not isinstance(items, ItemMap):
+                raise TypeError("items must be an ItemMap")
+            item_ids = ItemMap(items.resolve(gallery.shape[0], eng.device), items.n_items)
         args = (images, tokens, local, exclude_idx, members, ref_feats, mask, value)
         with torch.cuda.stream(stream):
             ev0 = None
@@ -146,15 +155,15 @@ class ComposedQueryPipeline:
                 ev0 = torch.cuda.Event(enable_timing=True)
                 ev0.record(stream)
             if self.graphs:
-                outs = self._replay(lane, eng, stream, args, gallery, k, idx_offset, tags)
+                outs = self._replay(lane, eng, stream, args, gallery, k, idx_offset, tags, item_ids)
             else:
-                outs = self._step(eng, args, gallery, k, idx_offset, tags)
+                outs = self._step(eng, args, gallery, k, idx_offset, tags, item_ids)
             ev = torch.cuda.Event(enable_timing=self.timing)
             ev.record(stream)
         if alone:
             stream.synchronize()
-        fused, scores, idx, member_scores = outs
-        return QueryResult(scores, idx, fused, ev, member_scores, ev0)
+        fused, scores, idx, member_scores, item = outs
+        return QueryResult(scores, idx, fused, ev, member_scores, ev0, item)
 
     def submit_fuse(self, tokens: torch.Tensor, local: torch.Tensor, ref_rows: torch.Tensor, index_features: torch.Tensor) -> "FusedResult":
         """The query loop of the reference harness as ONE lane job (run/test/test_fiq.py:98-118): tokens [B,77] int64 and local
@@ -184,7 +193,7 @@ class ComposedQueryPipeline:
         return FusedResult(fused, ev, keep)
 
     @staticmethod
-    def _step(eng, args, gallery, k, idx_offset, tags=None):
+    def _step(eng, args, gallery, k, idx_offset, tags=None, items=None):
         images, tokens, local, exclude_idx, members, ref_feats, mask, value = args
         if ref_feats is None and images.shape[0] == tokens.shape[0]:
             ref, tg, ts = eng.encode_pair(images, tokens)      # both towers in one pass: the text layers' GEMMs ride in the image layers' launches (fp32 / f32x3 / mx8img)
@@ -192,7 +201,11 @@ class ComposedQueryPipeline:
             ref = eng.encode_image(images) if ref_feats is None else ref_feats
             tg, ts = eng.encode_text(tokens)
         fused = eng.dvr_fuse(ref, local, tg, ts)
-        if tags is not None:                                    # filtered ranking: every k <= 1024, every gallery form
+        item = None
+        if items is not None:                                   # item-level ranking: every k <= 1024, filtered or not
+            scores, idx, item = eng.sim_topk_items(fused, gallery, items, k, idx_offset=idx_offset, exclude_idx=exclude_idx,
+                                                   row_filter=None if tags is None else RowFilter(tags, mask, value))
+        elif tags is not None:                                  # filtered ranking: every k <= 1024, every gallery form
             scores, idx = eng.sim_topk(fused, gallery, k, idx_offset=idx_offset, exclude_idx=exclude_idx, row_filter=RowFilter(tags, mask, value))
         elif k > 64:                                            # deep ranking: every gallery form (fp32, PreparedGallery, bf16)
             scores, idx = eng.sim_topk_deep(fused, gallery, k, idx_offset=idx_offset, exclude_idx=exclude_idx)
@@ -201,12 +214,12 @@ class ComposedQueryPipeline:
         else:
             scores, idx = eng.sim_topk(fused, gallery, k, idx_offset=idx_offset, exclude_idx=exclude_idx)
         member_scores = eng.gather_scores(fused, gallery, members) if members is not None else None
-        return fused, scores, idx, member_scores
+        return fused, scores, idx, member_scores, item
 
-    def _replay(self, lane, eng, stream, args, gallery, k, idx_offset, tags=None):
+    def _replay(self, lane, eng, stream, args, gallery, k, idx_offset, tags=None, items=None):
         key = tuple((tuple(a.shape), a.dtype) if a is not None else None for a in args) + (
             gallery.data_ptr(), tuple(gallery.shape), gallery.dtype, int(k), int(idx_offset), eng.precision,
-            None if tags is None else tags.data_ptr())
+            None if tags is None else tags.data_ptr(), None if items is None else (items.items.data_ptr(), items.n_items))
         lg = self._lane_graphs[lane].setdefault(key, _LaneGraph())
         if lg.graph is not None and lg.ws_generation != eng.ws_generation():
             stream.synchronize()                                 # the workspace the graph points into was freed: start over
@@ -214,14 +227,14 @@ class ComposedQueryPipeline:
         lg.calls += 1
         if lg.graph is None:
             if lg.calls <= 2:                                    # eager: sizes the workspaces, lets the tile tuner see every shape
-                return self._step(eng, args, gallery, k, idx_offset, tags)
+                return self._step(eng, args, gallery, k, idx_offset, tags, items)
             lg.inputs = tuple(None if a is None else a.clone() for a in args)
             stream.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=stream):
-                lg.outputs = self._step(eng, lg.inputs, gallery, k, idx_offset, tags)
+                lg.outputs = self._step(eng, lg.inputs, gallery, k, idx_offset, tags, items)
             lg.graph, lg.ws_generation = graph, eng.ws_generation()
-            lg.tags = tags                                       # the graph reads the filter's tags through their address: keep them alive
+            lg.tags = (tags, items)                              # the graph reads the filter's tags and the item ids through their addresses: keep them alive
         for dst, src in zip(lg.inputs, args):
             if dst is not None:
                 dst.copy_(src, non_blocking=True)

@@ -138,6 +138,10 @@ def build_parser(kind: str) -> ArgumentParser:
         p.add_argument("--merged-gallery", action="store_true",
                        help="keep the three categories in ONE gallery (concatenated in category order, tag = category ordinal), fused and prepared "
                             "once, and rank all queries against it with a per-query row filter -- the same recalls as the three separate indexes")
+    if kind == "200k":
+        p.add_argument("--item-level", action="store_true",
+                       help="after the recalls also print the ITEM-level numbers: the items are the distinct gallery names, every item takes one "
+                            "place in a ranking (its best row), and Recall@10 / Recall@50 / the median place are those of the target item")
     return p
 
 
@@ -216,6 +220,11 @@ def main(kind: str) -> None:
                 raise SystemExit(f"--rank-metrics is not available for {kind}")
             say(split, "rank metrics:", rank_fn(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size,
                                                args.num_workers, args.clip_model_name))
+        if getattr(args, "item_level", False):
+            from . import rank_metrics as _rm
+            res_items = _rm.compute_200k_item_metrics(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size,
+                                                            args.num_workers, args.clip_model_name)
+            say(split, "item-level: R@10 %.4f  R@50 %.4f  median place %.1f" % (res_items["recall@10"], res_items["recall@50"], res_items["median_rank"]))
     avg = [mean(r[j] for r in results) for j in range(len(results[0]))]
     if kind == "cirr":
         say("Average: ", (avg[4] + avg[0]) / 2)        # (R@5 + R_subset@1) / 2, test_cirr.py:198

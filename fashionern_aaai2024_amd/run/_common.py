@@ -324,6 +324,40 @@ def recalls_anyhit(model, predicted, index_fused, index_names, target_names, ks)
     return tuple(_pct((hit[:, :k].sum(1) > 0).sum(), q) for k in ks)
 
 
+def items_of_names(index_names: Sequence[str]):
+    """Gallery rows that share a name are one item: (int32 item id per row, the distinct names in order of first appearance)."""
+    ids: Dict[str, int] = {}
+    rows = np.fromiter((ids.setdefault(n, len(ids)) for n in index_names), dtype=np.int32, count=len(index_names))
+    return rows, list(ids)
+
+
+def recalls_items(model, predicted, index_fused, index_names, target_names, ks) -> Dict[str, float]:
+    """Fashion200k at ITEM level: the items are the distinct `index_names` (many rows share a caption, test_200k.py:52-60), a query's
+    ranking holds every item once, represented by its best row (FernEngine.item_rank_of), and the target item's 0-based place in it is the
+    number of ITEMS in front -- not the number of rows, which `recalls_anyhit` and `target_ranks` count.  `retrieval_metrics` of those
+    places: {"recall@k" ..., "median_rank", "mean_rank", "mrr"}; a target name that is not in the gallery is a miss.  Query slices go per
+    rank and the places are gathered, as in `target_ranks`."""
+    from ..engine import ItemMap
+    eng = _engine_of(model)
+    rows, names = items_of_names(index_names)
+    item_of = {n: i for i, n in enumerate(names)}
+    tgt = np.array([item_of.get(n, -1) for n in target_names], dtype=np.int32)
+    q = len(target_names)
+    start, stop, per = _my_rows(q)
+    if stop > start:
+        items = ItemMap(torch.from_numpy(rows).to(predicted.device), max(len(names), 1))
+        places = eng.item_rank_of(predicted[start:stop], index_fused, items, torch.from_numpy(tgt[start:stop, None]))
+    else:
+        places = torch.empty((0, 1), dtype=torch.int32, device=predicted.device)
+    if hasattr(eng, "sync"):
+        eng.sync()
+    if fd.world_info()[1] > 1:
+        block = torch.full((per, 1), -1, dtype=torch.int32, device=places.device)
+        block[: stop - start] = places
+        places = fd.all_gather_shards(block, q)
+    return retrieval_metrics(places.cpu().numpy(), ks)
+
+
 def recalls_cirr(model, predicted, index_fused, index_names, reference_names, target_names, group_members):
     """CIRR: reference image removed from each ranking; global R@1/5/10/50 + subset R@1/2/3 (test_cirr.py:55-80)."""
     q = len(target_names)

@@ -49,3 +49,14 @@ def compute_200k_rank_metrics(relative_val_dataset, clip_model, index_features, 
     for i, r in enumerate(per_query):
         rows[i, :len(r)] = r
     return _common.retrieval_metrics(_common.target_ranks(model, predicted, index_fused, rows), ks)
+
+
+def compute_200k_item_metrics(relative_val_dataset, clip_model, index_features, index_local_features, index_names, model, device,
+                              feature_dim, batch_size, num_workers, clip_model_name, ks=(10, 50)):
+    """--item-level: the gallery's items are its distinct names, every item takes one place in a query's ranking, and the metrics are
+    those of the target ITEM's place (`_common.recalls_items`): item-level Recall@10 / Recall@50 and the median place, next to the
+    row-level numbers of `compute_200k_val_metrics`, which stay what the reference prints."""
+    predicted, target_names = test_200k.generate_200k_val_predictions(clip_model, relative_val_dataset, model, index_names, index_features,
+                                                                      device, feature_dim, batch_size, num_workers, clip_model_name)
+    index_fused = _common.fuse_index(model, index_features, index_local_features, prepared=True)
+    return _common.recalls_items(model, predicted, index_fused, index_names, target_names, ks)

@@ -412,6 +412,50 @@ FERN_API int fern_rank_count_filtered(fern_ctx* ctx, const float* q /*[B,D]*/, c
                                       const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const uint64_t* keys /*[B,m]*/,
                                       int m, int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/, int32_t* out_count /*[B,m]*/,
                                       const uint32_t* tags /*[N]*/, const uint32_t* mask /*[B]*/, const uint32_t* value /*[B]*/, void* stream);
+/* Item-level ranking: galleries whose rows belong to items.  The reference's galleries are not all made of distinct rows: in Fashion200k
+ * the gallery name of an image is its caption (dataloader/fashion200k_patch.py:282-290), index_names holds many duplicates and
+ * run/test/test_200k.py:52-60 scores "any row with the target's name"; a product with several photographs is the same case.  Here the
+ * gallery carries one int32 item id per row, items[N] (device), and the caller gives the number of items G.  The item-level ranking of
+ * query b is the exact row ranking the entry points above define -- score descending, global row index ascending, exclude_idx and the row
+ * filter applied first -- with every row that is not the FIRST row of its item removed.  So an item is represented by its best eligible
+ * row, an item without an eligible row takes no place, ties between items break by the representatives' global row index (item ids play no
+ * part), and a row whose id is outside [0, G) belongs to no item and is ignored.  Exact for any grouping: the stage stores the score rows
+ * of a query chunk, reduces them into a [B, G] table of the items' best ranking keys and ranks the representatives with the deep stage.
+ * The gallery form follows from the pointers, as for fern_rank_count: `gallery` given: the exact fp32 fma-chain scores (gallery_bf16 is
+ * ignored), D % 32 == 0; gallery_bf16 only: the values fern_sweep_bf16_scores produces, D % 64 == 0, D <= 768.  There is no certified
+ * pre-filtered form: a group maximum over approximate scores certifies nothing.  tags == NULL: unfiltered (mask / value ignored);
+ * otherwise fern_sim_topk_filtered's predicate.  Asynchronous on `stream`, nothing read back, graph-capturable after one warm-up call.
+ * Queries are processed in chunks whose [m, N] fp32 score rows plus [m, G] 64-bit table stay inside the deep stage's 1.1 GB workspace;
+ * a single query that does not fit is an argument error.
+ * fern_sim_topk_items: 1 <= K <= 1024; out_idx = the representative row's global index, out_item = its item id, unfilled places
+ * -inf / -1 / -1. */
+FERN_API int fern_sim_topk_items(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                                 const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, int K, const int32_t* items /*[N]*/, int G,
+                                 float* out_scores /*[B,K]*/, int32_t* out_idx /*[B,K]*/, int32_t* out_item /*[B,K]*/, int64_t idx_offset,
+                                 const int32_t* exclude_idx /*[B] or NULL*/, const uint32_t* tags /*[N] or NULL*/, const uint32_t* mask /*[B]*/,
+                                 const uint32_t* value /*[B]*/, void* stream);
+/* fern_item_rank: out_rank[b][j] = the number of items that come before item target_items[b][j] in the ranking above (its 0-based place,
+ * any depth: a count over the table, no selection); -1 when the id is outside [0, G) or the item has no eligible row for query b. */
+FERN_API int fern_item_rank(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                            const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const int32_t* items /*[N]*/, int G,
+                            const int32_t* target_items /*[B,m]*/, int m, int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/,
+                            int32_t* out_rank /*[B,m]*/, const uint32_t* tags /*[N] or NULL*/, const uint32_t* mask /*[B]*/,
+                            const uint32_t* value /*[B]*/, void* stream);
+/* The two halves of fern_item_rank, for galleries sharded so that no item has rows in two shards (fern_rank_keys / fern_rank_count's
+ * scheme): fern_item_keys: out_keys[b][j] = the ranking key of item target_items[b][j]'s representative row in this shard (the key holds
+ * the GLOBAL row index), 0 when the id is outside [0, G) or no row of this shard can represent it; fern_item_count: out_count[b][j] = the
+ * number of this shard's items whose representative's key is greater than keys[b][j], -1 for a key of 0.  Take each target's key from
+ * the shard that owns the item (the maximum over the shards), count on every shard, add. */
+FERN_API int fern_item_keys(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                            const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const int32_t* items /*[N]*/, int G,
+                            const int32_t* target_items /*[B,m]*/, int m, int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/,
+                            uint64_t* out_keys /*[B,m]*/, const uint32_t* tags /*[N] or NULL*/, const uint32_t* mask /*[B]*/,
+                            const uint32_t* value /*[B]*/, void* stream);
+FERN_API int fern_item_count(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                             const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const int32_t* items /*[N]*/, int G,
+                             const uint64_t* keys /*[B,m]*/, int m, int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/,
+                             int32_t* out_count /*[B,m]*/, const uint32_t* tags /*[N] or NULL*/, const uint32_t* mask /*[B]*/,
+                             const uint32_t* value /*[B]*/, void* stream);
 /* scores of explicitly named gallery rows (CIRR subset ranking, run/test/test_cirr.py:64-66);
  * idx < 0 -> -inf */
 FERN_API int fern_gather_scores(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D]*/,
