@@ -2542,6 +2542,7 @@ extern "C" int fern_gemm(fern_ctx* c, const float* A, int64_t lda, const float* 
     if (!public_epi_ok(epilogue)) return fail(FERN_ERR_ARG, "fern_gemm: unknown epilogue");
     if (epilogue == FERN_EPI_BIAS_RESIDUAL && !residual) return fail(FERN_ERR_ARG, "fern_gemm: residual is NULL");
     if (K % 32) return fail(FERN_ERR_ARG, "fern_gemm: K must be a multiple of 32");
+    if (lda < K || ldw < K || ldc < N) return fail(FERN_ERR_ARG, "fern_gemm: need lda >= K, ldw >= K, ldc >= N (rows must not overlap)");
     HIP_TRY(hipSetDevice(c->device));
     GemmParams p{};
     p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.bias = bias; p.R = residual; p.C = C; p.ldc = ldc;
@@ -2557,6 +2558,7 @@ extern "C" int fern_gemm_bf16(fern_ctx* c, const uint16_t* A, int64_t lda, const
     if (!public_epi_ok(epilogue)) return fail(FERN_ERR_ARG, "fern_gemm_bf16: unknown epilogue");
     if (epilogue == FERN_EPI_BIAS_RESIDUAL && (!residual || out_bf16)) return fail(FERN_ERR_ARG, "fern_gemm_bf16: the residual epilogue needs a residual and fp32 output");
     if (K % 32 || lda % 8 || ldw % 8) return fail(FERN_ERR_ARG, "fern_gemm_bf16: K % 32, lda % 8 and ldw % 8 must be 0");
+    if (lda < K || ldw < K || ldc < N) return fail(FERN_ERR_ARG, "fern_gemm_bf16: need lda >= K, ldw >= K, ldc >= N (rows must not overlap)");
     HIP_TRY(hipSetDevice(c->device));
     GemmParams p{};
     p.Ab = A; p.lda = lda; p.Wb = W; p.ldw = ldw; p.bias = bias; p.R = residual; p.C = reinterpret_cast<float*>(C); p.ldc = ldc;
@@ -2572,6 +2574,7 @@ extern "C" int fern_quantize_rows_fp8(fern_ctx* c, const void* x, int x_is_bf16,
                                       int d, void* stream) {
     if (!c || rows < 0 || (rows && (!x || !y || !scale))) return fail(FERN_ERR_ARG, "fern_quantize_rows_fp8: bad argument");
     if (d <= 0 || d % 8 || d > 4096 || ldx % 8 || ldy % 8) return fail(FERN_ERR_ARG, "fern_quantize_rows_fp8: need d % 8 == 0, d <= 4096, ld % 8 == 0");
+    if (ldx < d || ldy < d) return fail(FERN_ERR_ARG, "fern_quantize_rows_fp8: need ldx >= d and ldy >= d (rows must not overlap)");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_quantize_rows_fp8(x_is_bf16 ? static_cast<const unsigned short*>(x) : nullptr, x_is_bf16 ? nullptr : static_cast<const float*>(x),
                                      ldx, y, ldy, scale, rows, d, (hipStream_t)stream));
@@ -2588,6 +2591,7 @@ extern "C" int fern_gemm_fp8(fern_ctx* c, const uint8_t* A, int64_t lda, const f
         return fail(FERN_ERR_ARG, "fern_gemm_fp8: epilogue must be BIAS, BIAS_GELU, BIAS_QUICKGELU or BIAS_RESIDUAL");
     if (epilogue == FERN_EPI_BIAS_RESIDUAL && (!residual || out_bf16)) return fail(FERN_ERR_ARG, "fern_gemm_fp8: the residual epilogue needs a residual and fp32 output");
     if (K % 64 || lda % 16 || ldw % 16) return fail(FERN_ERR_ARG, "fern_gemm_fp8: K % 64, lda % 16 and ldw % 16 must be 0");
+    if (lda < K || ldw < K || ldc < N) return fail(FERN_ERR_ARG, "fern_gemm_fp8: need lda >= K, ldw >= K, ldc >= N (rows must not overlap)");
     HIP_TRY(hipSetDevice(c->device));
     GemmParams p{};
     p.Ab = reinterpret_cast<const unsigned short*>(A); p.lda = lda; p.Wb = reinterpret_cast<const unsigned short*>(W); p.ldw = ldw;
@@ -2601,6 +2605,7 @@ extern "C" int fern_quantize_mx8(fern_ctx* c, const void* x, int x_is_bf16, int6
     if (!c || rows < 0 || (rows && (!x || !y || !scales))) return fail(FERN_ERR_ARG, "fern_quantize_mx8: bad argument");
     if (d <= 0 || d % 128 || d > 4096 || ldx % 8 || ldy % 8 || scale_rows < rows)
         return fail(FERN_ERR_ARG, "fern_quantize_mx8: need d % 128 == 0, d <= 4096, ld % 8 == 0, scale_rows >= rows");
+    if (ldx < d || ldy < d) return fail(FERN_ERR_ARG, "fern_quantize_mx8: need ldx >= d and ldy >= d (rows must not overlap)");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_quantize_mx8(x_is_bf16 ? static_cast<const unsigned short*>(x) : nullptr, x_is_bf16 ? nullptr : static_cast<const float*>(x), ldx,
                                 y, ldy, scales, scale_rows, rows, d, (hipStream_t)stream));
@@ -2618,6 +2623,7 @@ extern "C" int fern_gemm_mx8(fern_ctx* c, const uint8_t* A, int64_t lda, const u
     if (epilogue == FERN_EPI_BIAS_RESIDUAL && !residual) return fail(FERN_ERR_ARG, "fern_gemm_mx8: the residual epilogue needs a residual");
     if (K % 128 || lda % 16 || ldw % 16 || scale_rows_a < M || scale_rows_w < N)
         return fail(FERN_ERR_ARG, "fern_gemm_mx8: K % 128, lda % 16 and ldw % 16 must be 0, scale_rows >= rows");
+    if (lda < K || ldw < K || ldc < N) return fail(FERN_ERR_ARG, "fern_gemm_mx8: need lda >= K, ldw >= K, ldc >= N (rows must not overlap)");
     HIP_TRY(hipSetDevice(c->device));
     GemmParams p{};
     p.Ab = reinterpret_cast<const unsigned short*>(A); p.lda = lda; p.Wb = reinterpret_cast<const unsigned short*>(W); p.ldw = ldw;
@@ -2637,6 +2643,7 @@ extern "C" int fern_gemm_mx8_quant(fern_ctx* c, const uint8_t* A, int64_t lda, c
         return fail(FERN_ERR_ARG, "fern_gemm_mx8_quant: epilogue must be BIAS, BIAS_GELU or BIAS_QUICKGELU");
     if (K % 128 || N % 128 || lda % 16 || ldw % 16 || ldc % 16 || scale_rows_a < M || scale_rows_w < N || scale_rows_c < M)
         return fail(FERN_ERR_ARG, "fern_gemm_mx8_quant: K % 128, N % 128, lda / ldw / ldc % 16 must be 0, scale_rows >= rows");
+    if (lda < K || ldw < K || ldc < N) return fail(FERN_ERR_ARG, "fern_gemm_mx8_quant: need lda >= K, ldw >= K, ldc >= N (rows must not overlap)");
     HIP_TRY(hipSetDevice(c->device));
     GemmParams p{};
     p.Ab = reinterpret_cast<const unsigned short*>(A); p.lda = lda; p.Wb = reinterpret_cast<const unsigned short*>(W); p.ldw = ldw;
@@ -2657,6 +2664,10 @@ extern "C" int fern_layernorm(fern_ctx* c, const float* x, const float* residual
 extern "C" int fern_attention(fern_ctx* c, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, float* out,
                               int64_t ldo, int batch, int heads, int head_dim, int s_q, int s_k, int causal, float scale, void* stream) {
     if (!c || !q || !k || !v || !out) return fail(FERN_ERR_ARG, "fern_attention: NULL argument");
+    if (heads > 0 && head_dim > 0) {
+        const int64_t w = (int64_t)heads * head_dim;
+        if (ldq < w || ldk < w || ldv < w || ldo < w) return fail(FERN_ERR_ARG, "fern_attention: need ldq, ldk, ldv, ldo >= heads * head_dim (rows must not overlap)");
+    }
     HIP_TRY(hipSetDevice(c->device));
     AttnParams a{q, k, v, out, (long)ldq, (long)ldk, (long)ldv, (long)ldo, batch, heads, head_dim, s_q, s_k, causal, scale};
     return run_attention(c, a, (hipStream_t)stream);
@@ -2669,6 +2680,10 @@ extern "C" int fern_attention_bf16(fern_ctx* c, const uint16_t* q, int64_t ldq, 
                                    uint16_t* out, int64_t ldo, int batch, int heads, int head_dim, int s_q, int s_k, int causal, float scale,
                                    void* stream) {
     if (!c || !q || !k || !v || !out) return fail(FERN_ERR_ARG, "fern_attention_bf16: NULL argument");
+    if (heads > 0 && head_dim > 0) {
+        const int64_t w = (int64_t)heads * head_dim;
+        if (ldq < w || ldk < w || ldv < w || ldo < w) return fail(FERN_ERR_ARG, "fern_attention_bf16: need ldq, ldk, ldv, ldo >= heads * head_dim (rows must not overlap)");
+    }
     HIP_TRY(hipSetDevice(c->device));
     AttnParams a{nullptr, nullptr, nullptr, nullptr, (long)ldq, (long)ldk, (long)ldv, (long)ldo, batch, heads, head_dim, s_q, s_k, causal, scale,
                  out, q, k, v};

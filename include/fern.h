@@ -340,7 +340,8 @@ FERN_API int fern_rank_set_strategy(fern_ctx* ctx, int strategy);
 /* The bf16 sweep on its own: scores[b * ld + n] = the fp32-accumulated dot product of bf16(q[b]) and gallery_bf16[n] (v_mfma_f32_32x32x16_bf16,
  * k ascending) for every n < N -- the APPROXIMATE score the pre-filter selects on; tile_max (may be NULL) [B, ldt]: per 32 consecutive
  * gallery rows the largest of those scores (one wave tile of the sweep, reduced across its lanes), which is what the dense form of
- * fern_sim_topk_prefiltered reads instead of the rows.  ld >= N, ldt >= ceil(N / 32); D % 64 == 0, D <= 768.  For tests of the
+ * fern_sim_topk_prefiltered reads instead of the rows.  ld >= N, ldt >= ceil(N / 32) (any such value; elements outside [B, N] /
+ * [B, ceil(N / 32)] are not written); D % 64 == 0, D <= 768.  For tests of the
  * certificate (|exact - approximate| <= eps_b) and for callers that want the whole approximate score matrix. */
 FERN_API int fern_sweep_bf16_scores(fern_ctx* c, const float* q, const uint16_t* gallery_bf16, int B, int64_t N, int D, float* scores, int64_t ld,
                                     float* tile_max, int64_t ldt, void* stream);
@@ -467,14 +468,21 @@ FERN_API int fern_topk_merge(fern_ctx* ctx, const float* scores /*[R,B,K]*/, con
                     void* stream);
 
 /* building blocks (exported for kernel-level parity tests) -------------------------------- */
-/* C[M,N] = A[M,K] W[N,K]^T (+ epilogue); fp32 MFMA.  K % 32 == 0, lda/ldw % 4 == 0. */
+/* Leading dimensions, for every entry point of this section that takes one (pinned by tests/test_gpu_frames.py): ld >= width
+ * (lda, ldw >= K; ldc >= N; ldq, ldk, ldv, ldo >= heads * head_dim; ldx, ldy >= d; FERN_ERR_ARG otherwise: rows would overlap and
+ * stores race), and elements outside [rows, width] are neither read into the result nor written -- the gap columns width .. ld of
+ * every row, the rows before the first and after the last, bias / scale entries past N or M, scale bytes of rows >= `rows`.  The
+ * same holds for the [B, K] outputs of the ranking entry points above: nothing before row 0 or after row B - 1 is written.
+ * C[M,N] = A[M,K] W[N,K]^T (+ epilogue); fp32 MFMA.  K % 32 == 0, lda/ldw % 4 == 0, lda >= K, ldw >= K, ldc >= N (any ldc >= N;
+ * `residual` shares ldc and may be C itself). */
 FERN_API int fern_gemm(fern_ctx* ctx, const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
               const float* residual, float* C, int64_t ldc, int M, int N, int K, int epilogue,
               void* stream);
 /* bf16 operand form of fern_gemm ("perf mode" of the encoder GEMMs): A [M,lda] and W [N,ldw] hold bf16
  * bit patterns (fern_gallery_to_bf16 converts any fp32 buffer, round to nearest even), products accumulate in fp32 on
  * v_mfma_f32_32x32x16_bf16; C is fp32, or bf16 when out_bf16 != 0 (not with the residual epilogue).  K % 32 == 0,
- * lda/ldw % 8 == 0. */
+ * lda/ldw % 8 == 0, lda >= K, ldw >= K, ldc >= N (any ldc >= N, odd ones included: bf16 rows may be 2-byte aligned); elements outside
+ * [rows, width] are neither read into the result nor written. */
 FERN_API int fern_gemm_bf16(fern_ctx* ctx, const uint16_t* A, int64_t lda, const uint16_t* W, int64_t ldw, const float* bias,
                    const float* residual, void* C, int64_t ldc, int M, int N, int K, int epilogue, int out_bf16,
                    void* stream);
@@ -482,7 +490,8 @@ FERN_API int fern_gemm_bf16(fern_ctx* ctx, const uint16_t* A, int64_t lda, const
  * scale[r] = max|row r| / 448, or 1 for a zero row; y = fp8(x / scale[r]), round to nearest even);
  * C = (sum_k A8 W8) * scale_a[row] * scale_w[col] + bias (+ GELU | + residual), fp32 accumulation on
  * v_mfma_f32_32x32x16_fp8_fp8.  K % 64 == 0, lda/ldw % 16 == 0; `x` of the quantiser is bf16 when x_is_bf16 else fp32,
- * d % 8 == 0, d <= 4096. */
+ * d % 8 == 0, d <= 4096, ldx / ldy % 8 == 0.  lda >= K, ldw >= K, ldc >= N, ldx >= d, ldy >= d; elements outside [rows, width] --
+ * scale_a[row >= M] and scale_w[col >= N] included -- are neither read into the result nor written. */
 FERN_API int fern_quantize_rows_fp8(fern_ctx* ctx, const void* x, int x_is_bf16, int64_t ldx, uint8_t* y, int64_t ldy, float* scale,
                            int64_t rows, int d, void* stream);
 FERN_API int fern_gemm_fp8(fern_ctx* ctx, const uint8_t* A, int64_t lda, const float* scale_a, const uint8_t* W, int64_t ldw,
@@ -496,7 +505,9 @@ FERN_API int fern_gemm_fp8(fern_ctx* ctx, const uint8_t* A, int64_t lda, const f
  * scale_rows >= rows.  fern_gemm_mx8: C = sum over blocks of 2^(ea-127) 2^(ew-127) (A8 . W8) + bias (+ GELU | + residual), fp32
  * accumulation, scales applied inside the MFMA.  K % 128 == 0, d % 128 == 0, d <= 4096, lda / ldw % 16 == 0, ldx / ldy % 8 == 0.
  * FERN_EPI_BIAS_RESIDUAL with out_bf16 != 0 is the bf16 RESIDUAL-STREAM form (FERN_PREC_MX8's token stream): `residual` then points
- * at bf16 [M, ldc] (may alias C) and C = bf16(sum + bias + float(residual)), one round-to-nearest-even per element. */
+ * at bf16 [M, ldc] (may alias C) and C = bf16(sum + bias + float(residual)), one round-to-nearest-even per element.
+ * lda >= K, ldw >= K, ldc >= N, ldx >= d, ldy >= d; elements outside [rows, width] -- scale bytes of rows >= `rows` included -- are
+ * neither read into the result nor written. */
 FERN_API int fern_quantize_mx8(fern_ctx* ctx, const void* x, int x_is_bf16, int64_t ldx, uint8_t* y, int64_t ldy, uint8_t* scales,
                       int64_t scale_rows, int64_t rows, int d, void* stream);
 FERN_API int fern_gemm_mx8(fern_ctx* ctx, const uint8_t* A, int64_t lda, const uint8_t* scales_a, int64_t scale_rows_a, const uint8_t* W,
@@ -504,7 +515,8 @@ FERN_API int fern_gemm_mx8(fern_ctx* ctx, const uint8_t* A, int64_t lda, const u
                   int64_t ldc, int M, int N, int K, int epilogue, int out_bf16, void* stream);
 /* fern_gemm_mx8 whose output is quantised where it is produced: C8 [M, ldc] e4m3fn bytes + scales_c (the layout above, scale_rows_c
  * rows) = fern_quantize_mx8 applied to the fp32 values bias + sum (+ GELU), bit for bit -- the A operand of the next
- * fern_gemm_mx8.  N % 128 == 0, ldc % 16 == 0; epilogue BIAS or BIAS_GELU. */
+ * fern_gemm_mx8.  N % 128 == 0, ldc % 16 == 0, ldc >= N (lda, ldw >= K); epilogue BIAS, BIAS_GELU or BIAS_QUICKGELU.  Bytes of C8 outside
+ * [M, N] and scale bytes of rows >= M are not written. */
 FERN_API int fern_gemm_mx8_quant(fern_ctx* ctx, const uint8_t* A, int64_t lda, const uint8_t* scales_a, int64_t scale_rows_a, const uint8_t* W,
                         int64_t ldw, const uint8_t* scales_w, int64_t scale_rows_w, const float* bias, uint8_t* C8, int64_t ldc,
                         uint8_t* scales_c, int64_t scale_rows_c, int M, int N, int K, int epilogue, void* stream);
@@ -513,14 +525,17 @@ FERN_API int fern_layernorm(fern_ctx* ctx, const float* x, const float* residual
                    const float* beta, float* y, int64_t rows, int d, float eps, void* stream);
 /* softmax(scale * Q K^T (+causal)) V per (batch, head); q/k/v row strides in floats.  head_dim % 4 == 0, <= 96; s_q and s_k are
  * independent when not causal, s_k <= 4096 (up to 224 keys K / V stay resident in LDS, beyond that they stream through it in chunks of 128
- * keys: the same arithmetic per (query, key) in the same order); causal: s_q == s_k <= 96. */
+ * keys: the same arithmetic per (query, key) in the same order); causal: s_q == s_k <= 96.  ldq, ldk, ldv, ldo % 4 == 0 and
+ * >= heads * head_dim (q, k, v may be column slices of one packed [rows, 3 W] buffer); elements outside [rows, heads * head_dim] --
+ * K / V rows past s_k of the last batch included -- are neither read into the result nor written. */
 FERN_API int fern_attention(fern_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
                    int64_t ldv, float* out, int64_t ldo, int batch, int heads, int head_dim, int s_q,
                    int s_k, int causal, float scale, void* stream);
 /* bf16 operand form (perf mode of the CLIP towers): q/k/v/out hold bf16 bit patterns (strides in elements, % 8 == 0);
  * QK^T and PV on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, `scale` applied to the fp32 scores, softmax statistics
  * in fp32, the un-normalised weights rounded to bf16 for the PV product.  head_dim % 8 == 0, <= 96; s_k <= 4096 (causal: <= 96),
- * resident up to 224 keys and key-streaming beyond, as fern_attention. */
+ * resident up to 224 keys and key-streaming beyond, as fern_attention.  Every ld >= heads * head_dim; elements outside
+ * [rows, heads * head_dim] are neither read into the result nor written. */
 FERN_API int fern_attention_bf16(fern_ctx* ctx, const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v,
                         int64_t ldv, uint16_t* out, int64_t ldo, int batch, int heads, int head_dim, int s_q, int s_k,
                         int causal, float scale, void* stream);

@@ -8,20 +8,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gemm_refs
+from gemm_refs import attn_ref as _attn_ref, close as _close, mx_scales_by_block as _mx_scales_by_block, rand as _rand
 from oracle import rank as orank
 
 pytestmark = pytest.mark.gpu
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def _close(got, ref, rel=2e-5):
-    got, ref = got.detach().cpu().double(), ref.double()
-    err = (got - ref).abs().max().item()
-    assert err <= rel * max(ref.abs().max().item(), 1e-6), f"max abs err {err} vs scale {ref.abs().max().item()}"
 
 
 GEMM_SHAPES = [(64, 64, 32), (1, 32, 32), (100, 130, 64), (37, 200, 96), (300, 768, 768), (129, 513, 128),
@@ -31,17 +22,9 @@ GEMM_SHAPES = [(64, 64, 32), (1, 32, 32), (100, 130, 64), (37, 200, 96), (300, 7
 @pytest.mark.parametrize("M,N,K", GEMM_SHAPES)
 @pytest.mark.parametrize("epi", [0, 1, 2, 3])
 def test_gemm_matches_torch(engine, M, N, K, epi):
-    a, w, b = _rand(M, K, seed=1), _rand(N, K, seed=2, scale=K ** -0.5), _rand(N, seed=3)
-    r = _rand(M, N, seed=4)
-    ref = a.double() @ w.double().T + b.double()
-    if epi == 1:
-        ref = F.gelu(ref)
-    elif epi == 2:
-        ref = F.relu(ref)
-    elif epi == 3:
-        ref = ref + r.double()
+    a, w, b, r, base = gemm_refs.f32_case(M, N, K)
     got = engine.gemm(a, w, b, residual=r if epi == 3 else None, epilogue=epi)
-    _close(got, ref)
+    _close(got, gemm_refs.epi_ref(base, epi, r))
 
 
 def test_gemm_exact_on_integer_data(engine):
@@ -68,18 +51,6 @@ def test_layernorm(engine, rows, d):
     for eps in (1e-5, 1e-12):
         _close(engine.layernorm(x, g, b, eps), F.layer_norm(x.double(), (d,), g.double(), b.double(), eps), rel=1e-5)
     _close(engine.layernorm(x, g, b, 1e-12, residual=r), F.layer_norm((x + r).double(), (d,), g.double(), b.double(), 1e-12), rel=1e-5)
-
-
-def _attn_ref(q, k, v, heads, causal, scale):
-    b, sq, w = q.shape
-    sk, hd = k.shape[1], w // heads
-    qh = q.double().view(b, sq, heads, hd).transpose(1, 2) * scale
-    kh = k.double().view(b, sk, heads, hd).transpose(1, 2)
-    vh = v.double().view(b, sk, heads, hd).transpose(1, 2)
-    att = qh @ kh.transpose(-1, -2)
-    if causal:
-        att = att + torch.full((sq, sk), float("-inf"), dtype=torch.float64).triu(1)
-    return (torch.softmax(att, -1) @ vh).transpose(1, 2).reshape(b, sq, w)
 
 
 ATTN_CASES = [  # batch, heads, hd, s_q, s_k, causal
@@ -210,6 +181,50 @@ def test_bad_arguments_are_reported_not_executed(engine):
         engine.gemm(torch.zeros(4, 48), torch.zeros(4, 48))
     with pytest.raises(ValueError):
         engine.sim_topk(_int_unit(2, 64, 1), _int_unit(10, 32, 2), 5)
+    # ld < width makes rows overlap and stores race: FERN_ERR_ARG before any launch, and the framed output stays untouched
+    import ctypes as C
+    from framed import SENTINEL, Framed
+    from fashionern_aaai2024_amd.engine import _stream
+    lib, h, st = engine.lib, engine._h, _stream()
+    M, N = 8, 32
+    out = Framed(M, N, N, torch.float32, SENTINEL, "cuda")
+    out.view.fill_(7.0)
+    before = out.flat.clone()
+    z = torch.zeros(64 * 512, dtype=torch.float32, device="cuda")      # operands large enough for any of the shapes below
+    one = torch.ones(64, dtype=torch.float32, device="cuda")
+    po, pz, p1 = C.c_void_p(out.data_ptr()), C.c_void_p(z.data_ptr()), C.c_void_p(one.data_ptr())
+
+    def refused(code, what):
+        torch.cuda.synchronize()
+        assert code == -1, f"{what}: expected FERN_ERR_ARG, got {code}"
+        assert "ld" in lib.fern_last_error().decode(), what
+        assert torch.equal(out.flat.view(torch.int32), before.view(torch.int32)), f"{what}: the refused call wrote to its output"
+
+    for fam, K, step in (("f32", 32, 4), ("bf16", 32, 8), ("fp8", 64, 16), ("mx8", 128, 16), ("mx8q", 128, 16)):
+        n = 128 if fam == "mx8q" else N
+        for lda, ldw, ldc in ((K - step, K, n), (K, K - step, n), (K, K, n - (16 if fam == "mx8q" else 1))):
+            if fam == "f32":
+                code = lib.fern_gemm(h, pz, lda, pz, ldw, None, None, po, ldc, M, n, K, 0, st)
+            elif fam == "bf16":
+                code = lib.fern_gemm_bf16(h, pz, lda, pz, ldw, None, None, po, ldc, M, n, K, 0, 0, st)
+            elif fam == "fp8":
+                code = lib.fern_gemm_fp8(h, pz, lda, p1, pz, ldw, p1, None, None, po, ldc, M, n, K, 0, 0, st)
+            elif fam == "mx8":
+                code = lib.fern_gemm_mx8(h, pz, lda, pz, M, pz, ldw, pz, n, None, None, po, ldc, M, n, K, 0, 0, st)
+            else:
+                code = lib.fern_gemm_mx8_quant(h, pz, lda, pz, M, pz, ldw, pz, n, None, po, ldc, pz, M, M, n, K, 0, st)
+            refused(code, f"{fam} gemm lda={lda} ldw={ldw} ldc={ldc}")
+    heads, hd, s = 2, 16, 4
+    w = heads * hd
+    for name, entry, g in (("fern_attention", lib.fern_attention, 4), ("fern_attention_bf16", lib.fern_attention_bf16, 8)):
+        for bad in range(4):
+            lds = [w - g if i == bad else w for i in range(4)]
+            refused(entry(h, pz, lds[0], pz, lds[1], pz, lds[2], po, lds[3], 1, heads, hd, s, s, 0, 1.0, st), f"{name} ldq, ldk, ldv, ldo = {lds}")
+    for ldx, ldy in ((56, 64), (64, 56)):
+        refused(lib.fern_quantize_rows_fp8(h, pz, 0, ldx, po, ldy, pz, 4, 64, st), f"fern_quantize_rows_fp8 ldx={ldx} ldy={ldy}")
+    for ldx, ldy in ((120, 128), (128, 120)):
+        refused(lib.fern_quantize_mx8(h, pz, 0, ldx, po, ldy, pz, 4, 4, 128, st), f"fern_quantize_mx8 ldx={ldx} ldy={ldy}")
+    out.assert_intact("the output frame of the refused calls")
 
 
 def test_topk_large_gallery_many_segments(engine):
@@ -353,28 +368,12 @@ def test_gemm_bf16(engine, m, n, k, epi, out_bf16):
     """bf16-operand GEMM against fp64 math on the SAME rounded operands: only the fp32 accumulation order differs."""
     if epi == 3 and out_bf16:
         pytest.skip("the residual epilogue keeps the fp32 residual stream")
-    g = torch.Generator().manual_seed(m * 7 + n + k + epi)
-    a = torch.randn(m, k, generator=g)
-    w = torch.randn(n, k, generator=g) * k ** -0.5
-    b = torch.randn(n, generator=g)
-    r = torch.randn(m, n, generator=g)
-    ab, wb = a.bfloat16(), w.bfloat16()
-    ref = ab.double() @ wb.double().T + b.double()
-    if epi == 1:
-        ref = torch.nn.functional.gelu(ref)
-    elif epi == 2:
-        ref = torch.relu(ref)
-    elif epi == 3:
-        ref = ref + r.double()
+    a, ab, wb, b, r, base = gemm_refs.bf16_case(m, n, k, epi)
+    ref = gemm_refs.epi_ref(base, epi, r)
     got = engine.gemm_bf16(ab.cuda(), wb.cuda(), b, residual=r if epi == 3 else None, epilogue=epi, out_bf16=out_bf16)
-    assert got.dtype == (torch.bfloat16 if out_bf16 else torch.float32)
     # the engine's own fp32 -> bf16 conversion is RNE, i.e. torch's
     assert torch.equal(engine.to_bf16(a).cpu().view(torch.int16), ab.view(torch.int16))
-    if out_bf16:
-        # one bf16 rounding of a value the fp32 accumulation may have moved across a rounding boundary: <= 1 bf16 ulp
-        assert torch.allclose(got.float().cpu().double(), ref, rtol=2 ** -7, atol=1e-3)
-    else:
-        assert torch.allclose(got.cpu().double(), ref, rtol=1e-5, atol=2e-5)
+    gemm_refs.check_bf16_family(got, ref, out_bf16)
 
 
 @pytest.mark.gpu
@@ -425,26 +424,10 @@ def test_quantize_rows_fp8_is_bit_exact(engine, rows, d, bf16):
 @pytest.mark.parametrize("epi,out_bf16", [(0, False), (0, True), (1, True), (3, False)])
 def test_gemm_fp8(engine, m, n, k, epi, out_bf16):
     """fp8-operand GEMM against fp64 math on the SAME quantised operands and scales."""
-    g = torch.Generator().manual_seed(m + n + k + epi)
-    a = torch.randn(m, k, generator=g)
-    w = torch.randn(n, k, generator=g) * k ** -0.5
-    b = torch.randn(n, generator=g)
-    r = torch.randn(m, n, generator=g)
-    a8, sa = engine.quantize_rows_fp8(a)
-    w8, sw = engine.quantize_rows_fp8(w)
-    qa, qw = a8.cpu().view(torch.float8_e4m3fn).double(), w8.cpu().view(torch.float8_e4m3fn).double()
-    ref = (qa @ qw.T) * (sa.cpu().double().unsqueeze(1) * sw.cpu().double().unsqueeze(0)) + b.double()
-    if epi == 1:
-        ref = torch.nn.functional.gelu(ref)
-    elif epi == 3:
-        ref = ref + r.double()
+    a8, sa, w8, sw, b, r, base, g = gemm_refs.fp8_case(engine, m, n, k, epi)
+    ref = gemm_refs.epi_ref(base, epi, r)
     got = engine.gemm_fp8(a8, sa, w8, sw, b, residual=r if epi == 3 else None, epilogue=epi, out_bf16=out_bf16)
-    if out_bf16:
-        assert got.dtype == torch.bfloat16 and torch.allclose(got.float().cpu().double(), ref, rtol=2 ** -7, atol=1e-3)
-    else:
-        # v_mfma_f32_32x32x16_fp8_fp8 is exact on integer data (checked below) but does not sum its 16 products as a plain
-        # fp32 FMA chain: on random operands it sits ~1.4e-5 (rms, relative) from the exact sum, independent of K
-        assert (got.cpu().double() - ref).abs().max().item() < 1e-4 * max(1.0, ref.abs().max().item())
+    gemm_refs.check_fp8_family(got, ref, out_bf16)      # (the fp8 MFMA is exact on integer data: checked below)
     if epi == 0 and not out_bf16:
         ai = torch.randint(-4, 5, (m, k), generator=g).float()
         wi = torch.randint(-4, 5, (n, k), generator=g).float()
@@ -469,11 +452,6 @@ def test_gemm_mx8_quantising_epilogue_is_the_quantiser_applied_to_the_fp32_outpu
     q, sc = engine.gemm_mx8_quant(a8, sa, w8, sw, b, epilogue=epi)
     assert torch.equal(sc, s_ref)
     assert torch.equal(q, q_ref)
-
-
-def _mx_scales_by_block(sc):
-    """engine.quantize_mx8's [D/128, R, 4] scale array -> [R, D/32] (block b = k // 32)."""
-    return sc.permute(1, 0, 2).reshape(sc.shape[1], -1)
 
 
 @pytest.mark.gpu
@@ -508,24 +486,12 @@ def test_quantize_mx8_is_bit_exact(engine, rows, d, bf16):
 def test_gemm_mx8(engine, m, n, k, epi, out_bf16):
     """Block-scaled fp8 GEMM (v_mfma_scale_f32_32x32x64_f8f6f4) against fp64 math on the SAME quantised operands and scales."""
     from oracle.clip import mx8_dequantize
-    g = torch.Generator().manual_seed(m + n + k + epi)
-    a = torch.randn(m, k, generator=g) * torch.logspace(-1, 1, k // 32).repeat_interleave(32)     # blocks of different magnitude
-    w = torch.randn(n, k, generator=g) * k ** -0.5
-    b = torch.randn(n, generator=g)
-    r = torch.randn(m, n, generator=g)
-    a8, sa = engine.quantize_mx8(a)
-    w8, sw = engine.quantize_mx8(w)
-    qa = mx8_dequantize(a8.cpu().view(torch.float8_e4m3fn), _mx_scales_by_block(sa.cpu()), torch.float64)
-    qw = mx8_dequantize(w8.cpu().view(torch.float8_e4m3fn), _mx_scales_by_block(sw.cpu()), torch.float64)
-    ref = qa @ qw.T + b.double()
-    if epi == 1:
-        ref = torch.nn.functional.gelu(ref)
-    elif epi == 3:
-        ref = ref + r.double()
+    a8, sa, w8, sw, b, r, base, g = gemm_refs.mx8_case(engine, m, n, k, epi)
+    ref = gemm_refs.epi_ref(base, epi, r)
     if epi == 3 and out_bf16:
         # the bf16 residual-stream form (FERN_PREC_MX8's token stream): bf16 residual in, C = bf16(acc + bias + residual) -- ONE rounding
         rb = r.bfloat16()
-        ref = qa @ qw.T + b.double() + rb.double()
+        ref = gemm_refs.epi_ref(base, 3, rb)
         got = engine.gemm_mx8(a8, sa, w8, sw, b, residual=rb, epilogue=3, out_bf16=True)
         f32 = engine.gemm_mx8(a8, sa, w8, sw, b, residual=rb.float(), epilogue=3, out_bf16=False)
         assert got.dtype == torch.bfloat16 and torch.equal(got.cpu(), f32.cpu().bfloat16())      # exactly the fp32 epilogue's value, rounded once
@@ -539,10 +505,7 @@ def test_gemm_mx8(engine, m, n, k, epi, out_bf16):
         assert torch.equal(inplace.cpu(), got.cpu())
         return
     got = engine.gemm_mx8(a8, sa, w8, sw, b, residual=r if epi == 3 else None, epilogue=epi, out_bf16=out_bf16)
-    if out_bf16:
-        assert got.dtype == torch.bfloat16 and torch.allclose(got.float().cpu().double(), ref, rtol=2 ** -7, atol=1e-3)
-    else:
-        assert (got.cpu().double() - ref).abs().max().item() < 1e-4 * max(1.0, ref.abs().max().item())
+    gemm_refs.check_fp8_family(got, ref, out_bf16)
     if epi == 0 and not out_bf16:
         # integer data, power-of-two block scales: every product and partial sum is exact in fp32
         ai = torch.randint(-4, 5, (m, k), generator=g).float()

@@ -237,6 +237,26 @@ def test_attention_mx8_output(engine, b, heads, hd, s, causal):
     out = torch.full((rows, ldo), SENTINEL, dtype=torch.uint8, device="cuda")
     y8, sc = engine.attention_mx8(q.cuda(), k.cuda(), v.cuda(), heads, causal=causal, out=out, scales=_scales(w, rows + 3))
     yb = engine.attention_bf16(q.cuda(), k.cuda(), v.cuda(), heads, causal=causal).cpu().reshape(rows, w)
+    # The towers' input layout: q, k, v as column slices of ONE packed [rows, 3 W + 8] buffer (ldq = ldk = ldv = 3 W + 8) with NaN in its
+    # gap columns and around it, the outputs inside 0xA5 frames (tests/framed.py): the same bytes and scales, nothing else written.
+    import ctypes as C
+    from framed import NAN, Framed
+    from fashionern_aaai2024_amd import _lib
+    from fashionern_aaai2024_amd.engine import _stream
+    ldp = 3 * w + 8
+    packed = Framed(rows, 3 * w, ldp, torch.bfloat16, NAN, "cuda").load(torch.cat([q, k, v], -1))
+    fo = Framed(rows, w, ldo, torch.uint8, SENTINEL, "cuda")
+    fsc = Framed(w // 128, rows * 4, (rows + 3) * 4, torch.uint8, SENTINEL, "cuda")
+    p0 = packed.data_ptr()
+    _lib.check(engine.lib.fern_attention_mx8(engine._h, C.c_void_p(p0), ldp, C.c_void_p(p0 + 2 * w), ldp, C.c_void_p(p0 + 4 * w), ldp,
+                                             C.c_void_p(fo.data_ptr()), ldo, C.c_void_p(fsc.data_ptr()), rows + 3, b, heads, hd, s, s,
+                                             int(causal), hd ** -0.5, _stream()), "fern_attention_mx8")
+    torch.cuda.synchronize()
+    fo.assert_intact("attention_mx8 out (packed QKV)")
+    fsc.assert_intact("attention_mx8 scales (packed QKV)")
+    packed.assert_intact("packed QKV (input)")
+    assert torch.equal(fo.view, y8[:, :w]), "packed q / k / v: the e4m3fn bytes differ from the contiguous call"
+    assert torch.equal(fsc.view.reshape(w // 128, rows, 4), sc[:, :rows]), "packed q / k / v: the scale bytes differ from the contiguous call"
     y8 = y8.cpu()
     assert (y8[:, w:] == SENTINEL).all(), "bytes beyond the width were written"
     y8 = y8[:, :w].int()
