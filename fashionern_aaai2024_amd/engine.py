@@ -426,16 +426,15 @@ class FernEngine:
             raise ValueError("exclude_idx must be [B]")
         return ex
 
-    def _sim_topk_filtered(self, q, gallery, k: int, idx_offset, exclude_idx, row_filter: RowFilter):
-        """The filtered form of `sim_topk` / `sim_topk_deep` / `sim_topk_bf16` (include/fern.h: fern_sim_topk_filtered): the exact
-        ranking of the rows that are eligible for each query, 1 <= k <= 1024, any gallery form."""
-        if not isinstance(row_filter, RowFilter):
-            raise TypeError("row_filter must be a RowFilter")
+    def _gallery_forms(self, q, gallery, bf16_ok: bool = True):
+        """(q, g32, g16, meta): the queries as fp32 [B,D] and the forms of `gallery` -- a `PreparedGallery` gives all three, a bf16
+        device tensor g16 alone (`bf16_ok`; without it a bf16 tensor is converted like any other), anything else g32 alone.  q and
+        the gallery share D."""
         q = self._f32(q)
         g32 = g16 = meta = None
         if isinstance(gallery, PreparedGallery):
             g32, g16, meta = gallery.f32, gallery.bf16, gallery.meta
-        elif isinstance(gallery, torch.Tensor) and gallery.dtype == torch.bfloat16:
+        elif bf16_ok and isinstance(gallery, torch.Tensor) and gallery.dtype == torch.bfloat16:
             if not gallery.is_cuda or not gallery.is_contiguous():
                 raise ValueError("a bf16 gallery must be a contiguous device tensor")
             g16 = gallery
@@ -444,10 +443,22 @@ class FernEngine:
         g = g32 if g32 is not None else g16
         if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
             raise ValueError(f"q [B,D] and gallery [N,D] must share D, got {tuple(q.shape)} and {tuple(g.shape)}")
+        return q, g32, g16, meta
+
+    def _topk_out(self, b: int, k: int):
+        """The (scores fp32, idx int32) [B,k] outputs of a top-K call."""
+        return self._empty(b, k), self._empty(b, k, dtype=torch.int32)
+
+    def _sim_topk_filtered(self, q, gallery, k: int, idx_offset, exclude_idx, row_filter: RowFilter):
+        """The filtered form of `sim_topk` / `sim_topk_deep` / `sim_topk_bf16` (include/fern.h: fern_sim_topk_filtered): the exact
+        ranking of the rows that are eligible for each query, 1 <= k <= 1024, any gallery form."""
+        if not isinstance(row_filter, RowFilter):
+            raise TypeError("row_filter must be a RowFilter")
+        q, g32, g16, meta = self._gallery_forms(q, gallery)
+        g = g32 if g32 is not None else g16
         b = q.shape[0]
         tags, mask, value = row_filter.resolve(b, g.shape[0], self.device)
-        scores = self._empty(b, k)
-        idx = self._empty(b, k, dtype=torch.int32)
+        scores, idx = self._topk_out(b, k)
         ex = self._exclude(exclude_idx, b)
         _lib.check(self.lib.fern_sim_topk_filtered(self._h, _ptr(q), _ptr(g32), _ptr(g16), _ptr(meta), b, g.shape[0], q.shape[1], int(k),
                                                    _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask), _ptr(value),
@@ -462,17 +473,10 @@ class FernEngine:
             return self._sim_topk_filtered(q, gallery, k, idx_offset, exclude_idx, row_filter)
         if isinstance(gallery, PreparedGallery):
             return self._sim_topk_prefiltered(q, gallery, k, idx_offset, exclude_idx)
-        q, g = self._f32(q), self._f32(gallery)
-        if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
-            raise ValueError(f"q [B,D] and gallery [N,D] must share D, got {tuple(q.shape)} and {tuple(g.shape)}")
+        q, g, _, _ = self._gallery_forms(q, gallery, bf16_ok=False)
         b = q.shape[0]
-        scores = self._empty(b, k)
-        idx = self._empty(b, k, dtype=torch.int32)
-        ex = None
-        if exclude_idx is not None:
-            ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(ex.shape) != (b,):
-                raise ValueError("exclude_idx must be [B]")
+        scores, idx = self._topk_out(b, k)
+        ex = self._exclude(exclude_idx, b)
         _lib.check(self.lib.fern_sim_topk(self._h, _ptr(q), _ptr(g), b, g.shape[0], q.shape[1], int(k), _ptr(scores), _ptr(idx),
                                           int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk")
         return scores, idx
@@ -498,17 +502,10 @@ class FernEngine:
         _lib.check(self.lib.fern_rank_set_strategy(self._h, code), "fern_rank_set_strategy")
 
     def _sim_topk_prefiltered(self, q, pg: PreparedGallery, k: int, idx_offset: int = 0, exclude_idx=None):
-        q, g = self._f32(q), pg.f32
-        if q.dim() != 2 or q.shape[1] != g.shape[1]:
-            raise ValueError(f"q [B,D] and gallery [N,D] must share D, got {tuple(q.shape)} and {tuple(g.shape)}")
+        q, g, _, _ = self._gallery_forms(q, pg)
         b = q.shape[0]
-        scores = self._empty(b, k)
-        idx = self._empty(b, k, dtype=torch.int32)
-        ex = None
-        if exclude_idx is not None:
-            ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(ex.shape) != (b,):
-                raise ValueError("exclude_idx must be [B]")
+        scores, idx = self._topk_out(b, k)
+        ex = self._exclude(exclude_idx, b)
         _lib.check(self.lib.fern_sim_topk_prefiltered(self._h, _ptr(q), _ptr(g), _ptr(pg.bf16), _ptr(pg.meta), b, g.shape[0], q.shape[1], int(k),
                                                       _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_prefiltered")
         return scores, idx
@@ -520,27 +517,11 @@ class FernEngine:
         `row_filter`: rank only the rows that are eligible for each query (`RowFilter`)."""
         if row_filter is not None:
             return self._sim_topk_filtered(q, gallery, k, idx_offset, exclude_idx, row_filter)
-        q = self._f32(q)
-        g32 = g16 = meta = None
-        if isinstance(gallery, PreparedGallery):
-            g32, g16, meta = gallery.f32, gallery.bf16, gallery.meta
-        elif isinstance(gallery, torch.Tensor) and gallery.dtype == torch.bfloat16:
-            if not gallery.is_cuda or not gallery.is_contiguous():
-                raise ValueError("a bf16 gallery must be a contiguous device tensor")
-            g16 = gallery
-        else:
-            g32 = self._f32(gallery)
+        q, g32, g16, meta = self._gallery_forms(q, gallery)
         g = g32 if g32 is not None else g16
-        if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
-            raise ValueError(f"q [B,D] and gallery [N,D] must share D, got {tuple(q.shape)} and {tuple(g.shape)}")
         b = q.shape[0]
-        scores = self._empty(b, k)
-        idx = self._empty(b, k, dtype=torch.int32)
-        ex = None
-        if exclude_idx is not None:
-            ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(ex.shape) != (b,):
-                raise ValueError("exclude_idx must be [B]")
+        scores, idx = self._topk_out(b, k)
+        ex = self._exclude(exclude_idx, b)
         _lib.check(self.lib.fern_sim_topk_deep(self._h, _ptr(q), _ptr(g32), _ptr(g16), _ptr(meta), b, g.shape[0], q.shape[1], int(k),
                                                _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_deep")
         return scores, idx
@@ -549,20 +530,8 @@ class FernEngine:
     def _rank_forms(self, q, gallery):
         """(q, fp32 gallery or None, bf16 gallery or None): the gallery forms of `sim_topk_deep`; a PreparedGallery ranks on its
         fp32 rows (its bf16 copy is not read)."""
-        q = self._f32(q)
-        g32 = g16 = None
-        if isinstance(gallery, PreparedGallery):
-            g32 = gallery.f32
-        elif isinstance(gallery, torch.Tensor) and gallery.dtype == torch.bfloat16:
-            if not gallery.is_cuda or not gallery.is_contiguous():
-                raise ValueError("a bf16 gallery must be a contiguous device tensor")
-            g16 = gallery
-        else:
-            g32 = self._f32(gallery)
-        g = g32 if g32 is not None else g16
-        if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
-            raise ValueError(f"q [B,D] and gallery [N,D] must share D, got {tuple(q.shape)} and {tuple(g.shape)}")
-        return q, g32, g16
+        q, g32, g16, _ = self._gallery_forms(q, gallery)
+        return q, g32, (g16 if g32 is None else None)
 
     def _per_query(self, t, b: int, dtype, what: str) -> torch.Tensor:
         t = torch.as_tensor(t).to(device=self.device, dtype=dtype)
@@ -591,11 +560,7 @@ class FernEngine:
         g = g32 if g32 is not None else g16
         b = q.shape[0]
         ky = self._per_query(keys, b, torch.int64, "keys")
-        ex = None
-        if exclude_idx is not None:
-            ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(ex.shape) != (b,):
-                raise ValueError("exclude_idx must be [B]")
+        ex = self._exclude(exclude_idx, b)
         count = self._empty(*ky.shape, dtype=torch.int32)
         if row_filter is not None:
             if not isinstance(row_filter, RowFilter):
@@ -617,7 +582,7 @@ class FernEngine:
         flat = torch.as_tensor(targets).dim() == 1
         keys = self.rank_keys(q, gallery, targets, idx_offset)
         if exclude_idx is not None:
-            ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32)
+            ex = self._exclude(exclude_idx, keys.shape[0])
             tg = self._per_query(targets, keys.shape[0], torch.int32, "targets")
             keys = torch.where(tg == ex[:, None], torch.zeros_like(keys), keys)
         if row_filter is not None:      # ineligible targets lose their key on the device, like the excluded row
@@ -653,8 +618,7 @@ class FernEngine:
         `PreparedGallery` (exact fp32-chain scores) or a bf16 tensor (the bf16 similarity)."""
         q, g32, g16, n, it, g_items, ex, (tags, mask, value) = self._item_call(q, gallery, items, exclude_idx, row_filter)
         b = q.shape[0]
-        scores = self._empty(b, k)
-        idx = self._empty(b, k, dtype=torch.int32)
+        scores, idx = self._topk_out(b, k)
         item = self._empty(b, k, dtype=torch.int32)
         _lib.check(self.lib.fern_sim_topk_items(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, n, q.shape[1], int(k), _ptr(it), g_items, _ptr(scores),
                                                 _ptr(idx), _ptr(item), int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask), _ptr(value), _stream()),
@@ -706,16 +670,12 @@ class FernEngine:
     def sim_topk_bf16(self, q, gallery_bf16: torch.Tensor, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
         if row_filter is not None:
             return self._sim_topk_filtered(q, gallery_bf16, k, idx_offset, exclude_idx, row_filter)
-        q = self._f32(q)
-        g = gallery_bf16
-        if g.dtype != torch.bfloat16 or g.dim() != 2 or not g.is_cuda or not g.is_contiguous() or g.shape[1] != q.shape[1]:
+        if not isinstance(gallery_bf16, torch.Tensor) or gallery_bf16.dtype != torch.bfloat16:
             raise ValueError("gallery must be a contiguous bf16 [N,D] device tensor sharing D with q")
+        q, _, g, _ = self._gallery_forms(q, gallery_bf16)
         b = q.shape[0]
-        scores = self._empty(b, k)
-        idx = self._empty(b, k, dtype=torch.int32)
-        ex = None
-        if exclude_idx is not None:
-            ex = torch.as_tensor(exclude_idx).to(device=self.device, dtype=torch.int32).contiguous()
+        scores, idx = self._topk_out(b, k)
+        ex = self._exclude(exclude_idx, b)
         _lib.check(self.lib.fern_sim_topk_bf16(self._h, _ptr(q), _ptr(g), b, g.shape[0], q.shape[1], int(k), _ptr(scores), _ptr(idx),
                                                int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_bf16")
         return scores, idx

@@ -53,6 +53,77 @@ def test_filtered_argument_errors_name_the_function():
     assert b"fern_rank_count_filtered: tags is NULL" in lib.fern_last_error()
 
 
+def test_every_ranking_entry_point_refuses_too_many_rows_and_a_bad_width_by_name():
+    """One argument check serves all twelve ranking entry points: each refuses N = 0x7FFFFFF1 (one row past the int32 index limit) and
+    a width its gallery form does not take (30 for fp32 rows, 96 for a bf16-only gallery) with FERN_ERR_ARG and its own name -- with a
+    NULL context, and with a context that is never dereferenced, where the message must be the row limit's or the width rule's own
+    (the width is judged first), not that of some earlier check."""
+    from fashionern_aaai2024_amd import _lib
+    lib = _lib.load()
+    p = 0x1000                                           # never dereferenced: every call below is refused before any HIP call
+    # name -> call(ctx, g32, g16, n, d); the forms each takes: "fp32", "bf16" (bf16-only gallery) or both
+    entry = {
+        "fern_sim_topk": (("fp32",), lambda c, g32, g16, n, d: lib.fern_sim_topk(c, p, g32, 2, n, d, 5, p, p, 0, None, None)),
+        "fern_sim_topk_bf16": (("bf16",), lambda c, g32, g16, n, d: lib.fern_sim_topk_bf16(c, p, g16, 2, n, d, 5, p, p, 0, None, None)),
+        "fern_sim_topk_prefiltered": (("fp32",), lambda c, g32, g16, n, d: lib.fern_sim_topk_prefiltered(c, p, g32, p, p, 2, n, d, 5, p, p, 0, None, None)),
+        "fern_sim_topk_deep": (("fp32", "bf16"), lambda c, g32, g16, n, d: lib.fern_sim_topk_deep(c, p, g32, g16, None, 2, n, d, 100, p, p, 0, None, None)),
+        "fern_sim_topk_filtered": (("fp32", "bf16"), lambda c, g32, g16, n, d: lib.fern_sim_topk_filtered(c, p, g32, g16, None, 2, n, d, 100, p, p, 0, None, p, p, p, None)),
+        "fern_sim_topk_items": (("fp32", "bf16"), lambda c, g32, g16, n, d: lib.fern_sim_topk_items(c, p, g32, g16, 2, n, d, 5, p, 5, p, p, p, 0, None, None, None, None, None)),
+        "fern_rank_keys": (("fp32", "bf16"), lambda c, g32, g16, n, d: lib.fern_rank_keys(c, p, g32, g16, 2, n, d, p, 1, 0, p, None)),
+        "fern_rank_count": (("fp32", "bf16"), lambda c, g32, g16, n, d: lib.fern_rank_count(c, p, g32, g16, 2, n, d, p, 1, 0, None, p, None)),
+        "fern_rank_count_filtered": (("fp32", "bf16"), lambda c, g32, g16, n, d: lib.fern_rank_count_filtered(c, p, g32, g16, 2, n, d, p, 1, 0, None, p, p, p, p, None)),
+    }
+    for name in ("fern_item_rank", "fern_item_keys", "fern_item_count"):
+        entry[name] = (("fp32", "bf16"), lambda c, g32, g16, n, d, fn=getattr(lib, name): fn(c, p, g32, g16, 2, n, d, p, 5, p, 1, 0, None, p, None, None, None, None))
+    assert len(entry) == 12
+    too_many = b"N too large for int32 indices"
+    for name, (forms, call) in entry.items():
+        for form in forms:
+            g32, g16, good, bad, width = (p, None, 64, 30, b"D % 32 == 0") if form == "fp32" else (None, p, 64, 96, b"D % 64 == 0")
+            for n, d, why in ((0x7FFFFFF1, good, too_many), (10, bad, width), (0x7FFFFFF1, bad, width)):
+                assert call(None, g32, g16, n, d) == -1, (name, form, n, d)
+                assert name.encode() + b":" in lib.fern_last_error(), (name, form, n, d, lib.fern_last_error())
+                assert call(p, g32, g16, n, d) == -1, (name, form, n, d)
+                assert name.encode() + b":" in lib.fern_last_error() and why in lib.fern_last_error(), (name, form, n, d, lib.fern_last_error())
+            assert call(None, g32, g16, 10, good) == -1 and name.encode() + b": ctx is NULL" in lib.fern_last_error()      # nothing else to refuse
+
+
+def test_a_mis_shaped_exclude_idx_is_refused_by_every_ranking_method():
+    """Every ranking method of FernEngine converts `exclude_idx` through `_exclude`: a [B + 1] tensor raises ValueError before the
+    library is reached -- `sim_topk_bf16` included, which used to hand it to the kernel unchecked."""
+    from fashionern_aaai2024_amd.engine import FernEngine, ItemMap
+
+    class Hostless(FernEngine):
+        """No context and no library: a call that gets past the argument handling fails with AttributeError, not ValueError."""
+        def __init__(self):
+            self.device = torch.device("cpu")
+
+        def _gallery_forms(self, q, gallery, bf16_ok=True):
+            if bf16_ok and isinstance(gallery, torch.Tensor) and gallery.dtype == torch.bfloat16:
+                return self._f32(q), None, gallery, None          # a host tensor stands in for the device tensor the engine asks for
+            return super()._gallery_forms(q, gallery, bf16_ok)
+
+    eng = Hostless()
+    b, n, d = 3, 7, 64
+    q, g = torch.zeros(b, d), torch.zeros(n, d)
+    assert eng._exclude(None, b) is None and eng._exclude([1, 2, 3], b).dtype == torch.int32
+    items, t = ItemMap(torch.zeros(n, dtype=torch.int32), 1), torch.zeros(b, dtype=torch.int32)
+    keys = torch.ones(b, 1, dtype=torch.int64)
+    for bad in (torch.zeros(b + 1, dtype=torch.int32), torch.zeros(b, 1, dtype=torch.int32)):
+        for call in (lambda: eng._exclude(bad, b),
+                     lambda: eng.sim_topk(q, g, 5, exclude_idx=bad),
+                     lambda: eng.sim_topk_bf16(q, g.bfloat16(), 5, exclude_idx=bad),
+                     lambda: eng.sim_topk_deep(q, g, 100, exclude_idx=bad),
+                     lambda: eng.sim_topk_deep(q, g.bfloat16(), 100, exclude_idx=bad),
+                     lambda: eng.rank_count(q, g, keys, exclude_idx=bad),
+                     lambda: eng.sim_topk_items(q, g, items, 5, exclude_idx=bad),
+                     lambda: eng.item_rank_of(q, g, items, t, exclude_idx=bad)):
+            with pytest.raises(ValueError, match=r"exclude_idx must be \[B\]"):
+                call()
+    with pytest.raises(AttributeError):                      # a well-shaped one goes on to the library
+        eng.sim_topk_bf16(q, g.bfloat16(), 5, exclude_idx=torch.zeros(b, dtype=torch.int32))
+
+
 # ---- RowFilter -------------------------------------------------------------------------------------------------------------------
 def test_row_filter_shape_checks_and_bit_forms():
     from fashionern_aaai2024_amd.engine import RowFilter
