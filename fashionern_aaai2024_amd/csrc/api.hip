@@ -377,7 +377,7 @@ static int run_gemm_b_pair(fern_ctx* c, const GemmParams& p1, const GemmParams& 
     const hipError_t le = launch_gemm_mxbf_pair(p1, p2, s);
     HIP_TRY_PROF(le, c, slot);
     if (slot >= 0) {
-        c->recs[slot].dispatches = gemm_bf16_last_dispatches();
+        c->recs[slot].dispatches = gemm_last_dispatches();
         c->recs[slot].extra_flops = 2.0 * p2.M * (double)p2.N * p2.K;
     }
     return prof_close(c, slot, s);
@@ -2735,13 +2735,15 @@ extern "C" int fern_im2col_q(fern_ctx* c, const float* images, int b, int img, i
     return FERN_OK;
 }
 
-// The tuner's per-shape tile choices of this process (every context shares them), as text: one line per shape,
-// "f32|bf16|fp8 M N K epilogue loader|outflags cfg".  Returns the number of bytes the full text needs (excluding the
-// terminator); writes at most cap - 1 bytes + NUL.  A file of these lines, named by FERN_GEMM_TILES, pins the choices.
+// The tuners' choices of this process (every context shares them), as text, one line per choice (gemm_tuner.hip has the fields):
+//   "f32 M N K epilogue loader cfg rows_a cfg_b" / "f32x3 M N K epilogue cfg rows_a cfg_b"      a shape's tile plan, fp32 / f32x3 family
+//   "bf16 | fp8 | mx8 M N K epilogue outflags cfg"                                               a shape's tile, reduced-precision families
+//   "pair <fp32 shape> <fp32 shape> one" / "pairb <mx8 shape> <bf16 shape> choice"               one launch or two for a pair of shapes
+// Returns the number of bytes the full text needs (excluding the terminator); writes at most cap - 1 bytes + NUL.  A file of these
+// lines, named by FERN_GEMM_TILES, pins the choices.
 extern "C" int64_t fern_tuner_export(char* buf, int64_t cap) {
     std::string text;
     gemm_tuner_export(text);
-    gemm_bf16_tuner_export(text);
     if (buf && cap > 0) {
         const size_t n = std::min<size_t>(text.size(), (size_t)cap - 1);
         std::memcpy(buf, text.data(), n);
@@ -2757,9 +2759,7 @@ extern "C" uint64_t fern_ws_generation(const fern_ctx* c) { return c ? c->ws_gen
 // inapplicable lines are skipped.  Every configuration is bit-identical, so this never changes a result.
 extern "C" int fern_tuner_import(const char* text) {
     if (!text) return fail(FERN_ERR_ARG, "fern_tuner_import: text is NULL");
-    const std::string t(text);
-    gemm_tuner_import(t);
-    gemm_bf16_tuner_import(t);
+    gemm_tuner_import(text);
     return FERN_OK;
 }
 
@@ -2768,7 +2768,7 @@ extern "C" int fern_tuner_import(const char* text) {
 // Set before the first launch of a shape; shapes already tuned keep their choice.  Never changes a result.
 extern "C" int fern_tuner_set_concurrency(int lanes) {
     if (lanes < 1) return fail(FERN_ERR_ARG, "fern_tuner_set_concurrency: lanes must be >= 1");
-    gemm_bf16_tuner_set_concurrency(lanes);
+    gemm_tuner_set_concurrency(lanes);
     return FERN_OK;
 }
 
@@ -2776,9 +2776,7 @@ extern "C" int fern_tuner_set_concurrency(int lanes) {
 // FERN_GEMM_BF16_CFG / FERN_GEMM_FP8_CFG / FERN_GEMM_MX8_CFG do from the environment, switchable at run time so that a test process can walk
 // every variant.  A configuration that cannot serve a call (k tile does not divide K, ...) falls back to the family's own choice.
 extern "C" int fern_tuner_force_config(const char* family, int cfg) {
-    static const char* names[] = {"f32", "f32x3", "bf16", "fp8", "mx8"};
-    for (int f = 0; family && f < 5; ++f)
-        if (!std::strcmp(family, names[f])) return (f < 2 ? gemm_force_cfg(f, cfg) : gemm_bf16_force_cfg(f, cfg)) ? FERN_OK : fail(FERN_ERR_ARG, "fern_tuner_force_config");
+    if (family && gemm_force_cfg(family, cfg)) return FERN_OK;
     return fail(FERN_ERR_ARG, "fern_tuner_force_config: family is one of f32, f32x3, bf16, fp8, mx8");
 }
 

@@ -15,17 +15,14 @@
 //     ds_read_b128 feeds four MFMAs; both operands use the same permutation, so the sum is unchanged;
 //   * workgroup ids are remapped so that each XCD (private L2) owns a contiguous run of tiles.
 #include "kernels.h"
-#include <atomic>
 #include "gemm_epilogue.h"
+#include "gemm_tuner.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <type_traits>
-#include <string>
 
 namespace fern {
 
@@ -846,49 +843,6 @@ __global__ __launch_bounds__(256) void gemm_f32_skinny_kernel(GemmParams p) {
     }
 }
 
-struct TileCfg { int bm, bn, bk; float eff; };
-// order matters only for ties; eff = relative main-loop efficiency used by the shape heuristic
-static const TileCfg kCfgs[] = {
-    {128, 128, 32, 1.00f},   // 0: register-staged, 4 waves of 64x64
-    {64, 128, 32, 0.93f},    // 1
-    {128, 64, 32, 0.93f},    // 2
-    {64, 64, 32, 0.86f},     // 3
-    {0, 0, 0, 0.f}, {0, 0, 0, 0.f},   // 4-5: unused (retired A/B variants of the register-staged kernel)
-    {64, 32, 64, 0.5f},      // 6: small-M kernel on the 16x16x4 MFMA (M <= 128, plain loader, no SR / patch epilogue)
-    {0, 0, 0, 0.f},          // 7: unused
-    {128, 128, 16, 1.00f},   // 8: LDS-DMA staging, 16-wide k tiles, double buffered
-    {64, 128, 16, 0.93f},    // 9
-    {128, 64, 16, 0.93f},    // 10
-    {64, 64, 16, 0.86f},     // 11
-    {256, 128, 16, 1.00f},   // 12: 8 waves, 256x128 macro-tile (0.75x the L2->LDS bytes per flop of 128x128), 2 workgroups per CU
-    {128, 256, 16, 1.00f},   // 13
-    // column counts that are not multiples of 64 (the ModifiedResNet's 80 / 160 / 320-channel layers: a 64- or 128-wide tile spends
-    // 37.5 % / 17 % of its MFMAs on padding columns): four waves stacked over the rows, each 32 rows x the whole tile width
-    {128, 96, 16, 1.00f},    // 14: wave tile 32x96
-    {128, 160, 16, 1.00f},   // 15: wave tile 32x160
-};
-constexpr int kNumAuto = 4;      // configs the heuristic may pick
-constexpr int kNumCfgs = 16;
-
-// A forced tile configuration per family: the environment's value (read on first use) unless gemm_force_cfg has set one at run time
-// (fern_tuner_force_config: the test suite walks every variant inside one process).  -2 = not read yet.
-static std::atomic<int> g_force_f32{-2}, g_force_split{-2};
-static int forced_value(std::atomic<int>& slot, const char* var) {
-    int v = slot.load(std::memory_order_relaxed);
-    if (v == -2) {
-        const char* e = getenv(var);
-        v = e ? atoi(e) : -1;
-        slot.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-static int forced_cfg() { return forced_value(g_force_f32, "FERN_GEMM_CFG"); }
-bool gemm_force_cfg(int family, int cfg) {      // family 0: fp32 tiles, 1: f32x3 tiles; cfg < 0: back to the environment's value
-    if (family != 0 && family != 1) return false;
-    (family == 0 ? g_force_f32 : g_force_split).store(cfg < 0 ? -2 : cfg, std::memory_order_relaxed);
-    return true;
-}
-
 static bool epi_is_sweep(int e) { return e == EPI_TOPK_FILTER || e == EPI_RANK_COUNT; }      // nothing stored: the four LDS-DMA tiles with their own epilogues
 
 static int best_of(int M, int N, int first, int last) {
@@ -906,8 +860,8 @@ static int best_of(int M, int N, int first, int last) {
 // with LDS-DMA (configs 8-11: more resident waves, no ds_write pass); small-M problems are latency-bound per block and
 // do better with the register-prefetched 32-wide k tiles (configs 0-3).
 static int choose_cfg(int M, int N, int K) {
-    const int f = forced_cfg();
-    if (f >= 0 && f < kNumCfgs && kCfgs[f].bk && K % kCfgs[f].bk == 0) return f;
+    const int f = forced_cfg(FAM_F32);
+    if (cfg_fits(FAM_F32, f, K)) return f;
     if (f >= 100) return best_of(M, N, 8, 12);
     return (M >= 1024 || (K & 31)) ? best_of(M, N, 8, 12) : best_of(M, N, 0, kNumAuto);   // K % 32 != 0: only the 16-wide k tiles fit
 }
@@ -918,57 +872,49 @@ int gemm_num_col_blocks(int M, int N, int K) {
     return (N + 31) / 32;
 }
 
+// configurations 8-11 (the four LDS-DMA tile geometries) of one variant of gemm_f32_glds_kernel; false: c is none of them
+template <int MINW, bool CONV, int FILT>
+static bool launch_glds_8_11(int c, dim3 grid, const GemmParams& p, hipStream_t s) {
+    switch (c) {
+        case 8: FERN_LAUNCH((gemm_f32_glds_kernel<128, 128, 64, 64, 16, MINW, CONV, 0, FILT>), grid, dim3(256), 0, s, p); return true;
+        case 9: FERN_LAUNCH((gemm_f32_glds_kernel<64, 128, 32, 64, 16, MINW, CONV, 0, FILT>), grid, dim3(256), 0, s, p); return true;
+        case 10: FERN_LAUNCH((gemm_f32_glds_kernel<128, 64, 64, 32, 16, MINW, CONV, 0, FILT>), grid, dim3(256), 0, s, p); return true;
+        case 11: FERN_LAUNCH((gemm_f32_glds_kernel<64, 64, 32, 32, 16, MINW, CONV, 0, FILT>), grid, dim3(256), 0, s, p); return true;
+        default: return false;
+    }
+}
 static hipError_t launch_cfg(int c, const GemmParams& p, hipStream_t s) {
     const int nb = ((p.M + kCfgs[c].bm - 1) / kCfgs[c].bm) * ((p.N + kCfgs[c].bn - 1) / kCfgs[c].bn);
     const int ks = p.ksplit > 1 ? p.ksplit : 1;
+    const dim3 grid(nb, ks);
     if (p.epi == EPI_TOPK_FILTER) {      // the filtered sweep: LDS-DMA family, own instantiations
-        if (p.aload != ALOAD_PLAIN) return hipErrorInvalidValue;
-        switch (c) {
-            case 8: FERN_LAUNCH((gemm_f32_glds_kernel<128, 128, 64, 64, 16, 2, false, 0, 1>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 9: FERN_LAUNCH((gemm_f32_glds_kernel<64, 128, 32, 64, 16, 2, false, 0, 1>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 10: FERN_LAUNCH((gemm_f32_glds_kernel<128, 64, 64, 32, 16, 2, false, 0, 1>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 11: FERN_LAUNCH((gemm_f32_glds_kernel<64, 64, 32, 32, 16, 2, false, 0, 1>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            default: return hipErrorInvalidValue;
-        }
+        if (p.aload != ALOAD_PLAIN || !launch_glds_8_11<2, false, 1>(c, grid, p, s)) return hipErrorInvalidValue;
         return hipGetLastError();
     }
     if (p.epi == EPI_RANK_COUNT) {      // the counting sweep of the exact target ranks: the same four tiles, counting epilogue
-        if (p.aload != ALOAD_PLAIN || ks != 1) return hipErrorInvalidValue;
-        switch (c) {
-            case 8: FERN_LAUNCH((gemm_f32_glds_kernel<128, 128, 64, 64, 16, 2, false, 0, 2>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 9: FERN_LAUNCH((gemm_f32_glds_kernel<64, 128, 32, 64, 16, 2, false, 0, 2>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 10: FERN_LAUNCH((gemm_f32_glds_kernel<128, 64, 64, 32, 16, 2, false, 0, 2>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 11: FERN_LAUNCH((gemm_f32_glds_kernel<64, 64, 32, 32, 16, 2, false, 0, 2>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            default: return hipErrorInvalidValue;
-        }
+        if (p.aload != ALOAD_PLAIN || ks != 1 || !launch_glds_8_11<2, false, 2>(c, grid, p, s)) return hipErrorInvalidValue;
         return hipGetLastError();
     }
     if (p.aload == ALOAD_CONV3) {      // 3x3 window loader exists for the LDS-DMA family only
+        if (launch_glds_8_11<4, true, 0>(c, grid, p, s)) return hipGetLastError();
         switch (c) {
-            case 8: FERN_LAUNCH((gemm_f32_glds_kernel<128, 128, 64, 64, 16, 4, true>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 9: FERN_LAUNCH((gemm_f32_glds_kernel<64, 128, 32, 64, 16, 4, true>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 10: FERN_LAUNCH((gemm_f32_glds_kernel<128, 64, 64, 32, 16, 4, true>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 11: FERN_LAUNCH((gemm_f32_glds_kernel<64, 64, 32, 32, 16, 4, true>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 14: FERN_LAUNCH((gemm_f32_glds_kernel<128, 96, 32, 96, 16, 4, true>), dim3(nb, ks), dim3(256), 0, s, p); break;
-            case 15: FERN_LAUNCH((gemm_f32_glds_kernel<128, 160, 32, 160, 16, 3, true>), dim3(nb, ks), dim3(256), 0, s, p); break;
+            case 14: FERN_LAUNCH((gemm_f32_glds_kernel<128, 96, 32, 96, 16, 4, true>), grid, dim3(256), 0, s, p); break;
+            case 15: FERN_LAUNCH((gemm_f32_glds_kernel<128, 160, 32, 160, 16, 3, true>), grid, dim3(256), 0, s, p); break;
             default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
     }
     switch (c) {
-        case 0: FERN_LAUNCH((gemm_f32_kernel<128, 128, 64, 64, 32, false>), dim3(nb, ks), dim3(256), 0, s, p); break;
-        case 1: FERN_LAUNCH((gemm_f32_kernel<64, 128, 32, 64, 32, false>), dim3(nb, ks), dim3(256), 0, s, p); break;
-        case 2: FERN_LAUNCH((gemm_f32_kernel<128, 64, 64, 32, 32, false>), dim3(nb, ks), dim3(256), 0, s, p); break;
-        case 3: FERN_LAUNCH((gemm_f32_kernel<64, 64, 32, 32, 32, false>), dim3(nb, ks), dim3(256), 0, s, p); break;
-        case 6: FERN_LAUNCH((gemm_f32_skinny_kernel<5, 64>), dim3(nb, ks), dim3(256), 0, s, p); break;
-        case 8: FERN_LAUNCH((gemm_f32_glds_kernel<128, 128, 64, 64, 16, 4>), dim3(nb, ks), dim3(256), 0, s, p); break;
-        case 9: FERN_LAUNCH((gemm_f32_glds_kernel<64, 128, 32, 64, 16, 4>), dim3(nb, ks), dim3(256), 0, s, p); break;
-        case 10: FERN_LAUNCH((gemm_f32_glds_kernel<128, 64, 64, 32, 16, 4>), dim3(nb, ks), dim3(256), 0, s, p); break;
-        case 11: FERN_LAUNCH((gemm_f32_glds_kernel<64, 64, 32, 32, 16, 4>), dim3(nb, ks), dim3(256), 0, s, p); break;
-        case 12: FERN_LAUNCH((gemm_f32_glds_kernel<256, 128, 64, 64, 16, 4>), dim3(nb, ks), dim3(512), 0, s, p); break;
-        case 13: FERN_LAUNCH((gemm_f32_glds_kernel<128, 256, 64, 64, 16, 4>), dim3(nb, ks), dim3(512), 0, s, p); break;
-        case 14: FERN_LAUNCH((gemm_f32_glds_kernel<128, 96, 32, 96, 16, 4>), dim3(nb, ks), dim3(256), 0, s, p); break;
-        case 15: FERN_LAUNCH((gemm_f32_glds_kernel<128, 160, 32, 160, 16, 4>), dim3(nb, ks), dim3(256), 0, s, p); break;
+        case 0: FERN_LAUNCH((gemm_f32_kernel<128, 128, 64, 64, 32, false>), grid, dim3(256), 0, s, p); break;
+        case 1: FERN_LAUNCH((gemm_f32_kernel<64, 128, 32, 64, 32, false>), grid, dim3(256), 0, s, p); break;
+        case 2: FERN_LAUNCH((gemm_f32_kernel<128, 64, 64, 32, 32, false>), grid, dim3(256), 0, s, p); break;
+        case 3: FERN_LAUNCH((gemm_f32_kernel<64, 64, 32, 32, 32, false>), grid, dim3(256), 0, s, p); break;
+        case 6: FERN_LAUNCH((gemm_f32_skinny_kernel<5, 64>), grid, dim3(256), 0, s, p); break;
+        case 8: case 9: case 10: case 11: launch_glds_8_11<4, false, 0>(c, grid, p, s); break;
+        case 12: FERN_LAUNCH((gemm_f32_glds_kernel<256, 128, 64, 64, 16, 4>), grid, dim3(512), 0, s, p); break;
+        case 13: FERN_LAUNCH((gemm_f32_glds_kernel<128, 256, 64, 64, 16, 4>), grid, dim3(512), 0, s, p); break;
+        case 14: FERN_LAUNCH((gemm_f32_glds_kernel<128, 96, 32, 96, 16, 4>), grid, dim3(256), 0, s, p); break;
+        case 15: FERN_LAUNCH((gemm_f32_glds_kernel<128, 160, 32, 160, 16, 4>), grid, dim3(256), 0, s, p); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -979,128 +925,9 @@ static bool skinny_form_ok(const GemmParams& p) {      // forms the 16x16 small-
 }
 static bool skinny_ok(const GemmParams& p) { return p.M <= 128 && skinny_form_ok(p); }      // ... and the shapes it is a candidate for on its own
 
-// ---- per-shape tile selection -------------------------------------------------------------------------------------
-// Every configuration accumulates each output element over k in the same order (k pairs (8g+e, 8g+4+e), g ascending),
-// so all of them produce bit-identical results: the choice is purely a speed choice.  Large problems are tuned once per
-// shape by timing the candidates on scratch outputs -- the reduce epilogues too: their partial sums are laid out per
-// 32-column group, independent of the tile configuration.
-struct ShapeKey {
-    int M, N, K, epi, aload;
-    bool operator<(const ShapeKey& o) const {
-        if (M != o.M) return M < o.M;
-        if (N != o.N) return N < o.N;
-        if (K != o.K) return K < o.K;
-        if (epi != o.epi) return epi < o.epi;
-        return aload < o.aload;
-    }
-};
-// What the tuner picks for a shape: one tile configuration for the whole matrix, or -- plain row-independent epilogues only -- a
-// BULK + REMAINDER pair: rows [0, rows_a) in configuration cfg, the rest in cfg_b.  rows_a is the largest row count whose tiles
-// fill whole rounds of the 256 CUs; the ragged last round (e.g. 72 of 2 376 tiles at 12608 x 3072: every CU waits for the
-// 72 that got a tenth tile) is recut into small tiles that spread over all CUs.  Every configuration produces bit-identical
-// results, so the split changes nothing but the time.
-// cfg 20 / 21: a MIXED plan (gemm_f32_mixed_kernel, macro-tile 256x128 / 128x256): rows [0, rows_a) in macro-tiles, [rows_a, cfg_b) in
-// 128x128 tiles, [cfg_b, M) in 64x128 tiles, one launch -- cfg_b then holds a ROW, not a configuration.
-struct Plan { int cfg, rows_a, cfg_b; };
-constexpr int kCfgMixed = 20;
-static bool mixed_plan_ok(const Plan& pl, int M) {
-    const int bma = pl.cfg == kCfgMixed + 1 ? 128 : 256;
-    return (pl.cfg == kCfgMixed || pl.cfg == kCfgMixed + 1) && pl.rows_a > 0 && pl.rows_a <= M && pl.rows_a % bma == 0 && pl.cfg_b >= pl.rows_a &&
-           pl.cfg_b <= M && (pl.cfg_b == M || (pl.cfg_b - pl.rows_a) % 128 == 0);
-}
-static std::map<ShapeKey, Plan> g_tuned;
-static std::mutex g_tuned_mu;
-static std::map<ShapeKey, Plan>& tuned_split_map();     // the f32x3 family's choices (defined with that family below)
-static std::map<std::pair<ShapeKey, ShapeKey>, bool>& pair_choice_map();      // launch_gemm_pair's one-launch / two-launch choices (defined with it, at the end)
-constexpr int kNumCfgsS = 8;                             // ... and its number of single configurations
-
-// FERN_GEMM_TILES=<file>: pin the per-shape choices (lines "f32 M N K epi aload cfg [rows_a cfg_b]", as written by gemm_tuner_export /
-// fern_tuner_export): listed shapes are never timed again, so a run's kernels -- and its HBM / L2 traffic -- are reproducible
-// from box to box.  Loaded once, before the first tuned launch.
-static void pin_tile_line(const char* line) {      // caller holds g_tuned_mu
-    {      // "pair M1 N1 K1 epi1 a1 M2 N2 K2 epi2 a2 one": launch_gemm_pair's choice for a pair of shapes (a = aload, 3000 for the f32x3 family)
-        int v[11];
-        if (sscanf(line, "pair %d %d %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &v[9], &v[10]) == 11) {
-            pair_choice_map()[{ShapeKey{v[0], v[1], v[2], v[3], v[4]}, ShapeKey{v[5], v[6], v[7], v[8], v[9]}}] = v[10] != 0;
-            return;
-        }
-    }
-    {
-        int M, N, K, epi, cfg, ra = 0, rb = 0;
-        const int got = sscanf(line, "f32x3 %d %d %d %d %d %d %d", &M, &N, &K, &epi, &cfg, &ra, &rb);
-        if (got >= 5) {
-            if (cfg >= 0 && cfg < kNumCfgsS) tuned_split_map()[ShapeKey{M, N, K, epi, 0}] = Plan{cfg, 0, cfg};
-            else if (got == 7 && mixed_plan_ok(Plan{cfg, ra, rb}, M)) tuned_split_map()[ShapeKey{M, N, K, epi, 0}] = Plan{cfg, ra, rb};
-            return;
-        }
-    }
-    char kind[16];
-    auto ok = [](int cfg, int K) { return cfg >= 0 && cfg < kNumCfgs && kCfgs[cfg].bk && K % kCfgs[cfg].bk == 0; };
-    int M, N, K, epi, aload, cfg, rows_a = 0, cfg_b = 0;
-    const int got = sscanf(line, "%15s %d %d %d %d %d %d %d %d", kind, &M, &N, &K, &epi, &aload, &cfg, &rows_a, &cfg_b);
-    if (got == 9 && !strcmp(kind, "f32") && cfg >= kCfgMixed) {
-        if (mixed_plan_ok(Plan{cfg, rows_a, cfg_b}, M) && K % 16 == 0) g_tuned[ShapeKey{M, N, K, epi, aload}] = Plan{cfg, rows_a, cfg_b};
-        return;
-    }
-    if (got < 7 || strcmp(kind, "f32") || !ok(cfg, K)) return;
-    if (got < 9 || rows_a <= 0 || rows_a >= M || !ok(cfg_b, K)) { rows_a = 0; cfg_b = cfg; }
-    g_tuned[ShapeKey{M, N, K, epi, aload}] = Plan{cfg, rows_a, cfg_b};
-}
-static void load_pinned_tiles() {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        const char* path = getenv("FERN_GEMM_TILES");
-        FILE* f = path ? fopen(path, "r") : nullptr;
-        if (!f) return;
-        char line[256];
-        std::lock_guard<std::mutex> lock(g_tuned_mu);
-        while (fgets(line, sizeof line, f)) pin_tile_line(line);
-        fclose(f);
-    });
-}
-// fern_tuner_import: the lines of another process's fern_tuner_export replace this process's choices for the listed shapes
-// (rank 0 tunes, every rank runs rank 0's kernels: no rank-to-rank tile skew in a max-over-ranks step time)
-void gemm_tuner_import(const std::string& text) {
-    load_pinned_tiles();
-    std::lock_guard<std::mutex> lock(g_tuned_mu);
-    size_t at = 0;
-    while (at < text.size()) {
-        size_t nl = text.find('\n', at);
-        if (nl == std::string::npos) nl = text.size();
-        pin_tile_line(text.substr(at, nl - at).c_str());
-        at = nl + 1;
-    }
-}
-void gemm_tuner_export(std::string& out) {
-    std::lock_guard<std::mutex> lock(g_tuned_mu);
-    for (const auto& kv : tuned_split_map()) {
-        char line[128];
-        snprintf(line, sizeof line, "f32x3 %d %d %d %d %d %d %d\n", kv.first.M, kv.first.N, kv.first.K, kv.first.epi, kv.second.cfg, kv.second.rows_a,
-                 kv.second.cfg_b);
-        out += line;
-    }
-    for (const auto& kv : g_tuned) {
-        char line[128];
-        snprintf(line, sizeof line, "f32 %d %d %d %d %d %d %d %d\n", kv.first.M, kv.first.N, kv.first.K, kv.first.epi, kv.first.aload, kv.second.cfg,
-                 kv.second.rows_a, kv.second.cfg_b);
-        out += line;
-    }
-    for (const auto& kv : pair_choice_map()) {
-        char line[192];
-        const ShapeKey &a = kv.first.first, &b = kv.first.second;
-        snprintf(line, sizeof line, "pair %d %d %d %d %d %d %d %d %d %d %d\n", a.M, a.N, a.K, a.epi, a.aload, b.M, b.N, b.K, b.epi, b.aload, kv.second ? 1 : 0);
-        out += line;
-    }
-}
-
-static bool tuning_enabled() {
-    static bool v = [] {
-        const char* e = getenv("FERN_GEMM_TUNE");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
+// ---- per-shape tile selection (gemm_tuner.h has the store and the plans) ---------------------------------------------------------------
+// The reduce epilogues are tuned like the stored ones: their partial sums are laid out per 32-column group, independent of the tile
+// configuration.
 static bool split_ok(const GemmParams& p) {      // row-independent epilogue and loader: the rows can be cut anywhere
     return p.aload == ALOAD_PLAIN && p.w_sample <= 1 && p.ksplit <= 1 &&
            (p.epi == EPI_BIAS || p.epi == EPI_BIAS_GELU || p.epi == EPI_BIAS_QUICKGELU || p.epi == EPI_BIAS_RELU || p.epi == EPI_BIAS_RESIDUAL ||
@@ -1115,22 +942,32 @@ static GemmParams tail_rows(const GemmParams& p, int rows_a) {
     t.M = p.M - rows_a;
     return t;
 }
-static thread_local int g_last_dispatches = 1;
-int gemm_last_dispatches() { return g_last_dispatches; }
 
+// The blocks of a mixed plan's three bands of rows over an M x N problem: macro-tiles on [0, rows_a), 128x128 tiles on [rows_a, cfg_b),
+// 64x128 tiles on [cfg_b, M).  Every band starts on a multiple of 8 blocks (block % 8 stays the XCD inside the band), so the counts are
+// rounded up to 8 -- but for the last band that has blocks at all in `blocks`, the grid of the plan on its own.
+struct MixedBands {
+    int n_a8, n_b8, n_c8, blocks;
+    MixedBands(const Plan& pl, int M, int N) {
+        const bool wide = pl.cfg == kCfgMixed + 1;
+        const int bma = wide ? 128 : 256, bna = wide ? 256 : 128, nbn = (N + 127) / 128;
+        const int n_a = (pl.rows_a / bma) * ((N + bna - 1) / bna), n_b = ((pl.cfg_b - pl.rows_a + 127) / 128) * nbn, n_c = ((M - pl.cfg_b + 63) / 64) * nbn;
+        n_a8 = (n_a + 7) & ~7;
+        n_b8 = (n_b + 7) & ~7;
+        n_c8 = (n_c + 7) & ~7;
+        blocks = n_c > 0 ? n_a8 + n_b8 + n_c : n_b > 0 ? n_a8 + n_b : n_a;
+    }
+};
 static hipError_t launch_mixed(const Plan& pl, const GemmParams& p, hipStream_t s) {
     if (!mixed_plan_ok(pl, p.M)) return hipErrorInvalidValue;
     const bool wide = pl.cfg == kCfgMixed + 1;
-    const int bma = wide ? 128 : 256, bna = wide ? 256 : 128;
-    const int ra = pl.rows_a, rb = pl.cfg_b, nbn = (p.N + 127) / 128;
-    const int n_a = (ra / bma) * ((p.N + bna - 1) / bna), n_b = ((rb - ra + 127) / 128) * nbn, n_c = ((p.M - rb + 63) / 64) * nbn;
-    const int n_a8 = (n_a + 7) & ~7, n_b8 = (n_b + 7) & ~7;      // every band starts on a multiple of 8 blocks: block % 8 stays the XCD inside the band
-    const int grid = n_c > 0 ? n_a8 + n_b8 + n_c : n_b > 0 ? n_a8 + n_b : n_a;
+    const int ra = pl.rows_a, rb = pl.cfg_b;
+    const MixedBands b(pl, p.M, p.N);
     if (p.split == 3) {
-        if (wide) FERN_LAUNCH((gemm_f32_mixed_kernel<true, 3>), dim3(grid), dim3(256), 0, s, p, ra, rb, n_a8, n_b8);
-        else FERN_LAUNCH((gemm_f32_mixed_kernel<false, 3>), dim3(grid), dim3(256), 0, s, p, ra, rb, n_a8, n_b8);
-    } else if (wide) FERN_LAUNCH(gemm_f32_mixed_kernel<true>, dim3(grid), dim3(512), 0, s, p, ra, rb, n_a8, n_b8);
-    else FERN_LAUNCH(gemm_f32_mixed_kernel<false>, dim3(grid), dim3(512), 0, s, p, ra, rb, n_a8, n_b8);
+        if (wide) FERN_LAUNCH((gemm_f32_mixed_kernel<true, 3>), dim3(b.blocks), dim3(256), 0, s, p, ra, rb, b.n_a8, b.n_b8);
+        else FERN_LAUNCH((gemm_f32_mixed_kernel<false, 3>), dim3(b.blocks), dim3(256), 0, s, p, ra, rb, b.n_a8, b.n_b8);
+    } else if (wide) FERN_LAUNCH(gemm_f32_mixed_kernel<true>, dim3(b.blocks), dim3(512), 0, s, p, ra, rb, b.n_a8, b.n_b8);
+    else FERN_LAUNCH(gemm_f32_mixed_kernel<false>, dim3(b.blocks), dim3(512), 0, s, p, ra, rb, b.n_a8, b.n_b8);
     return hipGetLastError();
 }
 
@@ -1174,44 +1011,28 @@ static hipError_t launch_plan(const Plan& pl, const GemmParams& p, hipStream_t s
     return launch_cfg(pl.cfg_b, tail_rows(p, pl.rows_a), s);
 }
 
-// `tuned` = false: nothing was timed (the stream is being captured, or no scratch memory) and the heuristic plan is returned --
-// the caller must NOT cache it, or the shape would stay on the untuned plan (and be exported as a tuned choice) for good.
+// The trials of a shape of the fp32 family (lookup_or_tune: `tuned`).  Rounds outermost: every candidate is timed in two rounds and
+// keeps its faster time -- the first launches after an idle spell run while the clocks are still ramping, which would otherwise favour
+// whichever candidates happen to be tried last.
 static Plan tune_shape(const GemmParams& p, hipStream_t s, bool& tuned) {
-    LaunchTimerPause pause;
     const int fallback_cfg = choose_cfg(p.M, p.N, p.K);
     const Plan fallback{fallback_cfg, 0, fallback_cfg};
     tuned = false;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return fallback;
     long out_rows = p.M;
     if (p.epi == EPI_PATCH_EMBED) out_rows = p.M + p.M / (p.grid * p.grid) + 2;
     const bool reduce = epi_is_reduce(p.epi);
     const size_t scratch_floats = reduce ? (size_t)p.M * ((p.N + 31) / 32) : p.epi == EPI_TOPK_FILTER ? 4 :
                                   p.epi == EPI_RANK_COUNT ? (size_t)RANKC_P * p.M * RANKC_T : (size_t)out_rows * p.ldc;
-    float* scratch = nullptr;
-    if (hipMalloc(&scratch, scratch_floats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fallback; }
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
+    TrialTimer timer(s);
+    float* scratch = static_cast<float*>(timer.scratch(scratch_floats * sizeof(float)));
+    if (!timer.ok()) return fallback;
     GemmParams q = p;      // split-K launches write only to kpart, which is scratch already
     q.gate = nullptr;
     if (reduce) q.partial = scratch;
     else q.C = scratch;       // residual input (p.R) is only read: tuning has no side effects on the caller's buffers
     if (p.epi == EPI_TOPK_FILTER) q.filt.thr_key = nullptr;      // trial launches reject every score: nothing is appended
     if (p.epi == EPI_RANK_COUNT) q.rankc.partial = reinterpret_cast<int*>(scratch);      // trial launches count (atomics and all) into scratch sets
-    // Every candidate is timed in two rounds and keeps its faster time: the first launches after an idle spell run while the
-    // clocks are still ramping, which would otherwise favour whichever candidates happen to be tried last.
-    auto timed = [&](auto&& launch) -> float {
-        if (launch() != hipSuccess) return 1e30f;                        // warm
-        (void)hipEventRecord(e0, s);
-        (void)launch();
-        (void)launch();
-        (void)hipEventRecord(e1, s);
-        if (hipEventSynchronize(e1) != hipSuccess) return 1e30f;
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        return ms;
-    };
+    auto timed = [&](auto&& launch) { return timer.best_ms(launch, 1, 2); };
     static const int cands[] = {0, 1, 2, 3, 6, 8, 9, 10, 11, 12, 13, 14, 15};
     // {bulk cfg, remainder cfg, tiles per round}: the bulk covers the rows whose tiles fill whole rounds of the chip -- 256 = one tile
     // per CU; the 8-wave macro-tiles keep two workgroups per CU, so a round of 512 gives every CU an even number of them
@@ -1267,25 +1088,11 @@ static Plan tune_shape(const GemmParams& p, hipStream_t s, bool& tuned) {
         if (t_pair[i] < best_ms * 0.99f) { best_ms = t_pair[i]; best = pair_plan[i]; }      // two launches must earn their keep
     for (int i = 0; i < nmixed; ++i)
         if (t_mixed[i] < best_ms) { best_ms = t_mixed[i]; best = mixed[i]; }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(scratch);
     tuned = best_ms < 1e29f;
     return best;
 }
 
-// ---- f32x3 family (GemmParams.split == 3) --------------------------------------------------------------------------------
-// The planes of a wave tile are 12 VGPRs per 32-row fragment, so the configurations trade occupancy for room: the 128x128 tile at
-// <= 170 VGPRs (three workgroups per CU), the macro-tiles on four fat waves (wave tile 128x64 / 64x128, two workgroups per CU),
-// and the small tiles at the usual 128.  All bit-identical to each other; tuned per shape like the fp32 family.
-// 6 (round 4): 256x256 on EIGHT fat waves (wave tile 128x64, one workgroup per CU).  The bf16 MFMAs of this family retire an fp32 k pair
-// in 6 x 32 cycles instead of 2 x 64, so the tile's L2 -> LDS bytes are due 2.67x sooner than in the fp32 kernel: the 256x128 tile on
-// four fat waves needs 32 B/clk per workgroup (two per CU: 64) of a path that delivers ~33 B/clk per CU -- copy-bound at about half the
-// MFMA rate, which is the 1.5x the family measured.  256x256 stages 32 KiB per 3 072 MFMA cycles per SIMD: 10.7 B/clk.
-static const TileCfg kCfgsS[kNumCfgsS] = {{128, 128, 16, 1.f}, {256, 128, 16, 1.f}, {128, 256, 16, 1.f}, {64, 128, 16, 1.f}, {128, 64, 16, 1.f}, {64, 64, 16, 1.f},
-                                          {256, 256, 16, 1.f},
-                                          // 7: operands split once per workgroup (gemm_f32x3_shared_kernel), 8 fat waves
-                                          {256, 256, 16, 1.f}};
+// ---- f32x3 family (GemmParams.split == 3; gemm_tuner.h: kCfgsS) -----------------------------------------------------------------------
 static bool split_family_ok(const GemmParams& p) {
     return p.split == 3 && split_ok(p) && p.M >= 256 && p.K % 16 == 0;
 }
@@ -1304,9 +1111,6 @@ static hipError_t launch_cfg_split(int c, const GemmParams& p, hipStream_t s) {
     }
     return hipGetLastError();
 }
-static std::map<ShapeKey, Plan> g_tuned_s;      // guarded by g_tuned_mu; Plan{cfg, 0, cfg} or a mixed plan {20|21, ra, rb}
-static std::map<ShapeKey, Plan>& tuned_split_map() { return g_tuned_s; }
-static int forced_cfg_split() { return forced_value(g_force_split, "FERN_GEMM_SPLIT_CFG"); }
 static int heuristic_split(const GemmParams& p) {
     const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
     return t128 >= 1024 ? 1 : t128 >= 384 ? 0 : 5;
@@ -1314,20 +1118,14 @@ static int heuristic_split(const GemmParams& p) {
 static hipError_t launch_plan_split(const Plan& pl, const GemmParams& p, hipStream_t s) {
     return pl.cfg >= kCfgMixed ? launch_mixed(pl, p, s) : launch_cfg_split(pl.cfg, p, s);
 }
-static Plan tune_shape_split(const GemmParams& p, hipStream_t s, bool& tuned) {
-    LaunchTimerPause pause;
+static Plan tune_shape_split(const GemmParams& p, hipStream_t s, bool& tuned) {      // rounds outermost, as tune_shape
     tuned = false;
     const int fb = heuristic_split(p);
     const Plan fallback{fb, 0, fb};
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (!tuning_enabled() || hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return fallback;
-    float* scratch = nullptr;
-    if (hipMalloc(&scratch, (size_t)p.M * p.ldc * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fallback; }
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
+    TrialTimer timer(s);
     GemmParams q = p;
-    q.C = scratch;      // the residual input is only read
+    q.C = static_cast<float*>(timer.scratch((size_t)p.M * p.ldc * sizeof(float)));      // the residual input is only read
+    if (!timer.ok()) return fallback;
     Plan cand[kNumCfgsS + 32];
     int nc = 0;
     for (int c = 0; c < kNumCfgsS; ++c) cand[nc++] = Plan{c, 0, c};
@@ -1339,44 +1137,22 @@ static Plan tune_shape_split(const GemmParams& p, hipStream_t s, bool& tuned) {
     float t[kNumCfgsS + 32];
     for (float& v : t) v = 1e30f;
     for (int round = 0; round < 2; ++round)
-        for (int c = 0; c < nc; ++c) {
-            if (launch_plan_split(cand[c], q, s) != hipSuccess) continue;
-            (void)hipEventRecord(e0, s);
-            (void)launch_plan_split(cand[c], q, s);
-            (void)launch_plan_split(cand[c], q, s);
-            (void)hipEventRecord(e1, s);
-            if (hipEventSynchronize(e1) != hipSuccess) continue;
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            t[c] = std::min(t[c], ms);
-        }
+        for (int c = 0; c < nc; ++c) t[c] = std::min(t[c], timer.best_ms([&] { return launch_plan_split(cand[c], q, s); }, 1, 2));
     Plan best = fallback;
     float best_ms = 1e30f;
     for (int c = 0; c < nc; ++c)
         if (t[c] < best_ms) { best_ms = t[c]; best = cand[c]; }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(scratch);
     tuned = best_ms < 1e29f;
     return best;
 }
 static hipError_t launch_gemm_split(const GemmParams& p, hipStream_t s) {
-    const int f = forced_cfg_split();
+    const int f = forced_cfg(FAM_F32X3);
     if (f >= 0 && f < kNumCfgsS) return launch_cfg_split(f, p, s);
     const double flops = 2.0 * p.M * (double)p.N * p.K;
     const int hb = heuristic_split(p);
     Plan pl{hb, 0, hb};
-    if (tuning_enabled() && flops >= 2.5e8 && flops <= 2e11) {
-        const ShapeKey key{p.M, p.N, p.K, p.epi, 0};
-        std::lock_guard<std::mutex> lock(g_tuned_mu);
-        auto it = g_tuned_s.find(key);
-        if (it != g_tuned_s.end()) pl = it->second;
-        else {
-            bool tuned = false;
-            pl = tune_shape_split(p, s, tuned);
-            if (tuned) g_tuned_s.emplace(key, pl);
-        }
-    }
+    if (tuning_enabled() && flops >= 2.5e8 && flops <= 2e11)
+        pl = lookup_or_tune(choice_store().f32x3, ShapeKey{p.M, p.N, p.K, p.epi, 0}, [&](bool& tuned) { return tune_shape_split(p, s, tuned); });
     return launch_plan_split(pl, p, s);
 }
 
@@ -1393,24 +1169,15 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
     // tuned: problems big enough to matter and small enough that ~30 trial launches are cheap (beyond ~0.2 TFLOP per launch
     // -- the gallery-side GEMMs over tens of thousands of rows -- every candidate fills the chip and the heuristic is used)
     const double flops = 2.0 * p.M * (double)p.N * p.K;
-    const bool tunable = forced_cfg() < 0 && tuning_enabled() && flops >= 2.5e8 && flops <= 2e11;
+    const bool tunable = forced_cfg(FAM_F32) < 0 && tuning_enabled() && flops >= 2.5e8 && flops <= 2e11;
     if (tunable) {
-        load_pinned_tiles();
         const ShapeKey key{p.M, p.N, p.K, p.epi, p.aload + 1000 * (p.ksplit > 1 ? p.ksplit : 0)};
-        std::lock_guard<std::mutex> lock(g_tuned_mu);
-        auto it = g_tuned.find(key);
-        Plan pl;
-        if (it != g_tuned.end()) pl = it->second;
-        else {
-            bool tuned = false;
-            pl = tune_shape(p, s, tuned);
-            if (tuned) g_tuned.emplace(key, pl);
-        }
+        const Plan pl = lookup_or_tune(choice_store().f32, key, [&](bool& tuned) { return tune_shape(p, s, tuned); });
         if (pl.rows_a > 0 && split_ok(p)) return launch_plan(pl, p, s);
         c = pl.cfg < kCfgMixed ? pl.cfg : choose_cfg(p.M, p.N, p.K);      // a pinned mixed plan on a call it cannot serve: heuristic tile
     }
     if (c == 6 && !skinny_ok(p)) c = (p.K & 31) ? best_of(p.M, p.N, 8, 12) : best_of(p.M, p.N, 0, kNumAuto);   // forced but not applicable
-    if (c != 6 && forced_cfg() < 0 && !tunable && p.M <= 64 && p.N >= 256 && skinny_ok(p)) c = 6;     // untuned small-M GEMMs
+    if (c != 6 && forced_cfg(FAM_F32) < 0 && !tunable && p.M <= 64 && p.N >= 256 && skinny_ok(p)) c = 6;     // untuned small-M GEMMs
     if (epi_is_sweep(p.epi) && (c < 8 || c > 11)) c = 8 + (c & 3);     // filtered / counting sweep: the four LDS-DMA tiles only
     if (p.aload == ALOAD_CONV3 && (c < 8 || c == 12 || c == 13)) c = 8 + (c & 3);     // 3x3 window: LDS-DMA family without the macro-tiles
     if (c >= 8 && p.aload == ALOAD_IM2COL) c &= 3;                        // patch loader: register-staged family only
@@ -1421,89 +1188,57 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
 // p1's tuned plan is a mixed plan and both calls are plain (row-independent epilogue, plain loader, same arithmetic family); two launches
 // otherwise -- also the first time a shape is seen (launch_gemm tunes it; the next call finds the plan) and for the pairs that the one-launch
 // form does not speed up (pair_wins, timed once per pair of shapes).  FERN_GEMM_PAIR=0 turns it off.
-static bool pair_enabled() {
-    static const bool on = [] { const char* e = getenv("FERN_GEMM_PAIR"); return !(e && e[0] == '0'); }();
-    return on;
+static hipError_t launch_pair_kernel(const Plan& pl, const GemmParams& p1, const GemmParams& p2, hipStream_t s) {
+    const bool wide = pl.cfg == kCfgMixed + 1;
+    const int ra = pl.rows_a, rb = pl.cfg_b, nbn2 = (p2.N + 127) / 128;
+    const MixedBands b(pl, p1.M, p1.N);
+    const int rb2 = (p2.M / 128) * 128;
+    const int n_d = (rb2 / 128) * nbn2, n_e = ((p2.M - rb2 + 63) / 64) * nbn2;
+    const int n_d8 = (n_d + 7) & ~7, n_e8 = (n_e + 7) & ~7;      // the second problem's bands start on a multiple of 8 blocks too
+    const int grid = n_d8 + n_e8 + b.blocks;
+    if (p1.split == 3) {
+        if (wide) FERN_LAUNCH((gemm_f32_pair_kernel<true, 3>), dim3(grid), dim3(256), 0, s, p1, ra, rb, b.n_a8, b.n_b8, b.n_c8, p2, rb2, n_d8);
+        else FERN_LAUNCH((gemm_f32_pair_kernel<false, 3>), dim3(grid), dim3(256), 0, s, p1, ra, rb, b.n_a8, b.n_b8, b.n_c8, p2, rb2, n_d8);
+    } else if (wide) FERN_LAUNCH(gemm_f32_pair_kernel<true>, dim3(grid), dim3(512), 0, s, p1, ra, rb, b.n_a8, b.n_b8, b.n_c8, p2, rb2, n_d8);
+    else FERN_LAUNCH(gemm_f32_pair_kernel<false>, dim3(grid), dim3(512), 0, s, p1, ra, rb, b.n_a8, b.n_b8, b.n_c8, p2, rb2, n_d8);
+    return hipGetLastError();
 }
-static hipError_t launch_pair_kernel(const Plan& pl, const GemmParams& p1, const GemmParams& p2, hipStream_t s);
 // per (first shape, second shape): does the ONE-launch form beat two launches?  Timed once on scratch outputs, like the tile tuners: the
 // second problem rides as 128x128 / 64x128 tiles, which is not every shape's best geometry (4928 x 512 x 2048 behind 12608 x 768 x 3072:
-// 117 TFLOP/s paired against 120 as two launches; the other three pairs of a ViT-B/16 + text layer gain 1-2 %)
-static std::map<std::pair<ShapeKey, ShapeKey>, bool> g_pair_choice;      // guarded by g_tuned_mu; exported / pinned / imported with the tile choices ("pair ..." lines)
-static std::map<std::pair<ShapeKey, ShapeKey>, bool>& pair_choice_map() { return g_pair_choice; }
-static bool pair_wins(const Plan& pl, const GemmParams& p1, const GemmParams& p2, hipStream_t s, bool& timed) {
-    LaunchTimerPause pause;
+// 117 TFLOP/s paired against 120 as two launches; the other three pairs of a ViT-B/16 + text layer gain 1-2 %).  Candidates outermost:
+// the two-launch form first, both of its rounds (its warm launches also tune the second shape), then the one-launch form.
+static int pair_wins(const Plan& pl, const GemmParams& p1, const GemmParams& p2, hipStream_t s, bool& timed) {
     timed = false;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return false;
-    float *c1 = nullptr, *c2 = nullptr;
-    if (hipMalloc(&c1, (size_t)p1.M * p1.ldc * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (hipMalloc(&c2, (size_t)p2.M * p2.ldc * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(c1); return false; }
-    GemmParams q1 = p1, q2 = p2;
-    q1.C = c1; q2.C = c2;                                  // the residual inputs are only read: no side effects on the caller's buffers
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    auto timed_ms = [&](auto&& fn) {
-        float best = 1e30f;
-        for (int round = 0; round < 2; ++round) {
-            if (fn() != hipSuccess) return 1e30f;          // warm (and, for the two-launch form, the second shape's own tuning)
-            (void)hipEventRecord(e0, s);
-            (void)fn();
-            (void)fn();
-            (void)hipEventRecord(e1, s);
-            if (hipEventSynchronize(e1) != hipSuccess) return 1e30f;
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            best = std::min(best, ms);
-        }
-        return best;
-    };
-    const float t_two = timed_ms([&] { const hipError_t e = launch_gemm(q1, s); return e != hipSuccess ? e : launch_gemm(q2, s); });
-    const float t_one = timed_ms([&] { return launch_pair_kernel(pl, q1, q2, s); });
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(c1);
-    (void)hipFree(c2);
+    TrialTimer timer(s);
+    GemmParams q1 = p1, q2 = p2;      // the residual inputs are only read: no side effects on the caller's buffers
+    q1.C = static_cast<float*>(timer.scratch((size_t)p1.M * p1.ldc * sizeof(float)));
+    q2.C = static_cast<float*>(timer.scratch((size_t)p2.M * p2.ldc * sizeof(float)));
+    if (!timer.ok()) return 0;
+    const float t_two = timer.best_ms([&] { const hipError_t e = launch_gemm(q1, s); return e != hipSuccess ? e : launch_gemm(q2, s); }, 2, 2);
+    const float t_one = timer.best_ms([&] { return launch_pair_kernel(pl, q1, q2, s); }, 2, 2);
     timed = t_two < 1e29f && t_one < 1e29f;
     return timed && t_one < t_two;
 }
 hipError_t launch_gemm_pair(const GemmParams& p1, const GemmParams& p2, hipStream_t s) {
     bool paired = false;
     Plan pl{-1, 0, 0};
-    const bool same_family = (p1.split == 3) == (p2.split == 3);
+    const bool sp = p1.split == 3, same_family = sp == (p2.split == 3);
     if (pair_enabled() && same_family && split_ok(p1) && split_ok(p2) && !p1.gate && !p2.gate && p1.K % 16 == 0 && p2.K % 16 == 0 && p1.M >= 256 && p2.M >= 64 &&
         p2.N >= 128 && !(p1.lda & 3) && !(p2.lda & 3) && !(p1.ldw & 3) && !(p2.ldw & 3) && !((uintptr_t)p1.A & 15) && !((uintptr_t)p2.A & 15) &&
-        !((uintptr_t)p1.W & 15) && !((uintptr_t)p2.W & 15) && forced_cfg() < 0 && forced_cfg_split() < 0 && tuning_enabled()) {
-        const bool sp = p1.split == 3;
-        if (!sp || (split_family_ok(p1) && split_family_ok(p2))) {
-            load_pinned_tiles();
-            const ShapeKey k1{p1.M, p1.N, p1.K, p1.epi, sp ? 3000 : p1.aload}, k2{p2.M, p2.N, p2.K, p2.epi, sp ? 3000 : p2.aload};
-            bool known = false;
-            {
-                std::lock_guard<std::mutex> lock(g_tuned_mu);
-                if (sp) {
-                    auto it = g_tuned_s.find(ShapeKey{p1.M, p1.N, p1.K, p1.epi, 0});
-                    if (it != g_tuned_s.end()) pl = it->second;
-                } else {
-                    auto it = g_tuned.find(ShapeKey{p1.M, p1.N, p1.K, p1.epi, p1.aload});
-                    if (it != g_tuned.end()) pl = it->second;
-                }
-                if (pl.cfg >= kCfgMixed && mixed_plan_ok(pl, p1.M)) {
-                    auto it = g_pair_choice.find({k1, k2});
-                    if (it != g_pair_choice.end()) { known = true; paired = it->second; }
-                } else {
-                    known = true;                           // no mixed plan (yet): two launches -- launch_gemm tunes the shape on first sight
-                }
-            }
-            if (!known) {                                   // (the trial launches call launch_gemm, which takes the mutex itself)
-                bool timed = false;
-                paired = pair_wins(pl, p1, p2, s, timed);
-                if (timed) {
-                    std::lock_guard<std::mutex> lock(g_tuned_mu);
-                    g_pair_choice[{k1, k2}] = paired;
-                }
-            }
+        !((uintptr_t)p1.W & 15) && !((uintptr_t)p2.W & 15) && forced_cfg(FAM_F32) < 0 && forced_cfg(FAM_F32X3) < 0 && tuning_enabled() &&
+        (!sp || (split_family_ok(p1) && split_family_ok(p2)))) {
+        load_pinned_tiles();
+        ChoiceStore& st = choice_store();
+        {
+            std::lock_guard<std::mutex> lock(st.mu);
+            const std::map<ShapeKey, Plan>& plans = sp ? st.f32x3 : st.f32;
+            const auto it = plans.find(ShapeKey{p1.M, p1.N, p1.K, p1.epi, sp ? 0 : p1.aload});
+            if (it != plans.end()) pl = it->second;
+        }
+        // no mixed plan (yet): two launches -- launch_gemm tunes the shape on first sight
+        if (pl.cfg >= kCfgMixed && mixed_plan_ok(pl, p1.M)) {
+            const PairKey key{ShapeKey{p1.M, p1.N, p1.K, p1.epi, sp ? 3000 : p1.aload}, ShapeKey{p2.M, p2.N, p2.K, p2.epi, sp ? 3000 : p2.aload}};
+            paired = lookup_or_tune_pair(st.pair, key, [&](bool& timed) { return pair_wins(pl, p1, p2, s, timed); }) != 0;
         }
     }
     if (!paired) {
@@ -1516,23 +1251,6 @@ hipError_t launch_gemm_pair(const GemmParams& p1, const GemmParams& p2, hipStrea
     }
     g_last_dispatches = 1;
     return launch_pair_kernel(pl, p1, p2, s);
-}
-static hipError_t launch_pair_kernel(const Plan& pl, const GemmParams& p1, const GemmParams& p2, hipStream_t s) {
-    const bool wide = pl.cfg == kCfgMixed + 1;
-    const int bma = wide ? 128 : 256, bna = wide ? 256 : 128;
-    const int ra = pl.rows_a, rb = pl.cfg_b, nbn = (p1.N + 127) / 128, nbn2 = (p2.N + 127) / 128;
-    const int n_a = (ra / bma) * ((p1.N + bna - 1) / bna), n_b = ((rb - ra + 127) / 128) * nbn, n_c = ((p1.M - rb + 63) / 64) * nbn;
-    const int rb2 = (p2.M / 128) * 128;
-    const int n_d = (rb2 / 128) * nbn2, n_e = ((p2.M - rb2 + 63) / 64) * nbn2;
-    const int n_a8 = (n_a + 7) & ~7, n_b8 = (n_b + 7) & ~7, n_c8 = (n_c + 7) & ~7, n_d8 = (n_d + 7) & ~7;      // every band starts on a multiple of 8 blocks
-    const int n_e8 = (n_e + 7) & ~7;
-    const int grid = n_d8 + n_e8 + (n_c > 0 ? n_a8 + n_b8 + n_c : n_b > 0 ? n_a8 + n_b : n_a);
-    if (p1.split == 3) {
-        if (wide) FERN_LAUNCH((gemm_f32_pair_kernel<true, 3>), dim3(grid), dim3(256), 0, s, p1, ra, rb, n_a8, n_b8, n_c8, p2, rb2, n_d8);
-        else FERN_LAUNCH((gemm_f32_pair_kernel<false, 3>), dim3(grid), dim3(256), 0, s, p1, ra, rb, n_a8, n_b8, n_c8, p2, rb2, n_d8);
-    } else if (wide) FERN_LAUNCH(gemm_f32_pair_kernel<true>, dim3(grid), dim3(512), 0, s, p1, ra, rb, n_a8, n_b8, n_c8, p2, rb2, n_d8);
-    else FERN_LAUNCH(gemm_f32_pair_kernel<false>, dim3(grid), dim3(512), 0, s, p1, ra, rb, n_a8, n_b8, n_c8, p2, rb2, n_d8);
-    return hipGetLastError();
 }
 
 }  // namespace fern

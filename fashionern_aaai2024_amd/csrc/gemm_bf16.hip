@@ -12,16 +12,11 @@
 // operands).  Every configuration adds the 16-wide k groups in ascending order, so all of them produce bit-identical
 // results and a row's result does not depend on the batch it is part of.
 #include "gemm_epilogue.h"
+#include "gemm_tuner.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <string>
 
 namespace fern {
 
@@ -398,26 +393,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, MINW) void gemm_mx8_ker
     mx8_tile_body<BM, BN, WM, WN, STAGES, RB>(p, blockIdx.x, smem);
 }
 
-struct TileCfgB { int bm, bn, bk, per_cu; };     // per_cu: workgroups of the configuration one CU holds (LDS / registers / waves)
-// The tuner's candidates.  Retired after A/B runs on MI355X: 3- and 4-stage rings of the 128x128 tile and
-// 128x64 / 128x128 per-wave tiles -- fewer resident workgroups cost more than the deeper prefetch or the saved LDS reads gain.
-static const TileCfgB kCfgsB[] = {
-    {128, 128, 32, 4},   // 0: 4 waves of 64x64, 64-byte rows, 2 stages, 4 workgroups per CU
-    {256, 128, 32, 2},   // 1: 8 waves of 64x64, 3 stages
-    {256, 256, 32, 1},   // 2: 16 waves of 64x64, 3 stages
-    {64, 128, 32, 4},    // 3: 4 waves of 32x64, 2 stages
-    {128, 64, 32, 4},    // 4: 4 waves of 64x32, 2 stages
-    {64, 64, 32, 8},     // 5: 4 waves of 32x32, 2 stages
-    {128, 128, 64, 2},   // 6: as 0 with 128-byte rows (64-element k tiles): whole 128-byte lines per request, half the barriers, 2 per CU
-    {256, 256, 32, 1},   // 7: round 6, gemm_pp.h: 8 waves of 128x64 in two groups half a phase apart, 4-slot ring of 64-byte-row k tiles (128 KiB)
-    // round 6, the short-K shapes of the text tower / fusion BERT (M = 4928 / 5824, K = 512): with 32-element k tiles and ONE tile in
-    // flight a 16-tile k loop is 16 L2 round trips -- every such GEMM took ~20 us whatever its size (129 TFLOP/s at N = 512).  128-byte
-    // rows halve the round trips, the third stage keeps two tiles in flight
-    {64, 64, 64, 3},     // 8: 4 waves of 32x32, 128-byte rows, 3 stages (48 KiB)
-    {64, 128, 64, 2},    // 9: 4 waves of 32x64, 128-byte rows, 3 stages (72 KiB)
-};
-constexpr int kNumCfgsB = 10;
-
+// ---- tile configurations of the three families (gemm_tuner.h: kCfgsB, kCfgsF8, kCfgsMx) -----------------------------------------------
 static hipError_t launch_cfg_b(int c, const GemmParams& p, hipStream_t s) {
     const int nb = ((p.M + kCfgsB[c].bm - 1) / kCfgsB[c].bm) * ((p.N + kCfgsB[c].bn - 1) / kCfgsB[c].bn);
     switch (c) {
@@ -435,10 +411,6 @@ static hipError_t launch_cfg_b(int c, const GemmParams& p, hipStream_t s) {
     }
     return hipGetLastError();
 }
-
-// fp8 tile family (k tile = 64 elements = 64-byte rows, 2 stages): same block shapes as the bf16 candidates
-static const TileCfgB kCfgsF8[] = {{128, 128, 64, 4}, {256, 128, 64, 2}, {256, 256, 64, 1}, {64, 128, 64, 4}, {128, 64, 64, 4}, {64, 64, 64, 8}};
-constexpr int kNumCfgsF8 = 6;
 static hipError_t launch_cfg_f8(int c, const GemmParams& p, hipStream_t s) {
     const int nb = ((p.M + kCfgsF8[c].bm - 1) / kCfgsF8[c].bm) * ((p.N + kCfgsF8[c].bn - 1) / kCfgsF8[c].bn);
     switch (c) {
@@ -452,23 +424,6 @@ static hipError_t launch_cfg_f8(int c, const GemmParams& p, hipStream_t s) {
     }
     return hipGetLastError();
 }
-
-// MX tile family (k tile = 128 bytes).  LDS per stage = (bm + bn) * 132 bytes.
-static const TileCfgB kCfgsMx[] = {
-    {128, 128, 128, 2},   // 0: 4 waves of 64x64, 2 stages (66 KiB: 2 workgroups per CU)
-    {256, 128, 128, 1},   // 1: 8 waves of 64x64, 2 stages (99 KiB)
-    {256, 128, 128, 1},   // 2: 4 waves of 128x64, 2 stages: 12 LDS reads per 8 MFMAs instead of 8 per 4
-    {128, 128, 128, 1},   // 3: as 0 with a 3-stage ring (99 KiB)
-    {64, 128, 128, 3},    // 4: 4 waves of 32x64
-    {128, 64, 128, 3},    // 5: 4 waves of 64x32
-    {64, 64, 128, 4},     // 6: 4 waves of 32x32
-    {256, 256, 128, 1},   // 7: 16 waves of 64x64, 2 stages (132 KiB)
-    {128, 128, 64, 3},    // 8: as 0 with 64-byte rows (one MFMA step per barrier), 3 stages: 50 KiB, 3 workgroups per CU
-    {256, 128, 64, 2},    // 9: as 1 with 64-byte rows, 3 stages: 75 KiB, 2 workgroups per CU (needs <= 128 VGPRs)
-    {256, 256, 64, 1},    // 10: 8 waves of 128x64, 64-byte rows, 4 stages (136 KiB): fewest staged bytes per FLOP, deep prefetch instead of occupancy
-    {256, 256, 64, 1},    // 11: round 6, gemm_pp.h: the ping-pong form of 10 (two wave groups half a phase apart, one 16 KiB unit staged per phase)
-};
-constexpr int kNumCfgsMx = 12;
 static hipError_t launch_cfg_mx(int c, const GemmParams& p, hipStream_t s) {
     const int nb = ((p.M + kCfgsMx[c].bm - 1) / kCfgsMx[c].bm) * ((p.N + kCfgsMx[c].bn - 1) / kCfgsMx[c].bn);
     switch (c) {
@@ -489,115 +444,6 @@ static hipError_t launch_cfg_mx(int c, const GemmParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-// forced tile configuration per family (gemm.hip: forced_value has the scheme): environment on first use, gemm_bf16_force_cfg at run time
-static std::atomic<int> g_force_b{-2}, g_force_f8{-2}, g_force_mx{-2};
-static int forced_value_b(std::atomic<int>& slot, const char* var) {
-    int v = slot.load(std::memory_order_relaxed);
-    if (v == -2) {
-        const char* e = getenv(var);
-        v = e ? atoi(e) : -1;
-        slot.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-static int forced_cfg_b() { return forced_value_b(g_force_b, "FERN_GEMM_BF16_CFG"); }
-bool gemm_bf16_force_cfg(int family, int cfg) {      // family 2: bf16, 3: fp8 (per-row scales), 4: block-scaled fp8; cfg < 0: environment
-    if (family < 2 || family > 4) return false;
-    (family == 2 ? g_force_b : family == 3 ? g_force_f8 : g_force_mx).store(cfg < 0 ? -2 : cfg, std::memory_order_relaxed);
-    return true;
-}
-
-// Per-shape tile selection, as in gemm.hip: every configuration produces bit-identical results, so the choice is purely a
-// speed choice; each new (M, N, K, epilogue) is timed once on scratch outputs (outside stream capture).
-struct ShapeKeyB {
-    int M, N, K, epi, ob;      // ob: bit 0 = bf16 output, bit 1 = fp8 operands, bit 2 = MX fp8 operands, bit 3 = MX fp8 output
-    bool operator<(const ShapeKeyB& o) const {
-        if (M != o.M) return M < o.M;
-        if (N != o.N) return N < o.N;
-        if (K != o.K) return K < o.K;
-        if (epi != o.epi) return epi < o.epi;
-        return ob < o.ob;
-    }
-};
-static std::map<ShapeKeyB, int> g_tuned_b;
-static std::mutex g_tuned_b_mu;
-struct PairKeyB {                                 // launch_gemm_mxbf_pair (end of this file): a (block-scaled shape, bf16 shape) pair
-    ShapeKeyB a, b;
-    bool operator<(const PairKeyB& o) const { return a < o.a || (!(o.a < a) && b < o.b); }
-};
-static std::map<PairKeyB, int>& pair_b_map();
-// Launches of other streams expected to run beside one of these GEMMs (fern_tuner_set_concurrency; the query pipeline sets its
-// lane count).  1: a trial's score is its duration.  > 1: duration x (share of the chip's workgroup slots the launch fills)^0.75 --
-// a launch that leaves CUs to its neighbours is worth more to the pipeline than its own latency says.  Measured on the c5 pipeline
-// (3 lanes, tools/c5_tiles_ab.sh): 256x256 tiles for the N = 768 block GEMMs (150 workgroups on 150 CUs) instead of the 1 200
-// small workgroups the latency score picks: 17.7 -> 18.9 k queries/s, although each of those launches takes longer.
-static int g_tune_concurrency = 1;
-void gemm_bf16_tuner_set_concurrency(int n) {
-    std::lock_guard<std::mutex> lock(g_tuned_b_mu);
-    g_tune_concurrency = n < 1 ? 1 : n;
-}
-
-// FERN_GEMM_TILES=<file>: lines "bf16 M N K epi ob cfg" / "fp8 M N K epi ob cfg" / "mx8 M N K epi ob cfg" pin the choices (see gemm.hip)
-static void pin_tile_line_b(const char* line) {      // caller holds g_tuned_b_mu
-    {      // "pairb M1 N1 K1 epi1 ob1 M2 N2 K2 epi2 ob2 choice": launch_gemm_mxbf_pair's choice for a (block-scaled, bf16) pair of shapes
-        int v[11];
-        if (sscanf(line, "pairb %d %d %d %d %d %d %d %d %d %d %d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &v[7], &v[8], &v[9], &v[10]) == 11) {
-            if (v[10] >= 0 && v[10] <= 2) pair_b_map()[PairKeyB{ShapeKeyB{v[0], v[1], v[2], v[3], v[4]}, ShapeKeyB{v[5], v[6], v[7], v[8], v[9]}}] = v[10];
-            return;
-        }
-    }
-    char kind[16];
-    int M, N, K, epi, ob, cfg;
-    if (sscanf(line, "%15s %d %d %d %d %d %d", kind, &M, &N, &K, &epi, &ob, &cfg) != 7) return;
-    // the LAUNCH family is selected by the `ob` bits of the key (bit 1: per-row fp8, bit 2: block-scaled fp8), so the family the
-    // configuration index is checked against comes from `ob`, and a line whose kind disagrees with it is dropped (an
-    // mx8 cfg pinned under a bf16 key would fail every launch of that shape)
-    const bool mx = (ob & 4) != 0, f8 = !mx && (ob & 2) != 0;
-    if (strcmp(kind, mx ? "mx8" : f8 ? "fp8" : "bf16") != 0) return;
-    if (cfg < 0 || cfg >= (mx ? kNumCfgsMx : f8 ? kNumCfgsF8 : kNumCfgsB) || M <= 0 || N <= 0 || K <= 0) return;
-    const int kq = mx ? 128 : f8 ? 64 : kCfgsB[cfg].bk;      // k granularity the family's kernels need (launch_gemm_bf16 checks the same)
-    if (K % kq) return;
-    g_tuned_b[ShapeKeyB{M, N, K, epi, ob}] = cfg;
-}
-static void load_pinned_tiles_b() {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        const char* path = getenv("FERN_GEMM_TILES");
-        FILE* f = path ? fopen(path, "r") : nullptr;
-        if (!f) return;
-        char line[256];
-        std::lock_guard<std::mutex> lock(g_tuned_b_mu);
-        while (fgets(line, sizeof line, f)) pin_tile_line_b(line);
-        fclose(f);
-    });
-}
-void gemm_bf16_tuner_import(const std::string& text) {      // see gemm_tuner_import (gemm.hip)
-    load_pinned_tiles_b();
-    std::lock_guard<std::mutex> lock(g_tuned_b_mu);
-    size_t at = 0;
-    while (at < text.size()) {
-        size_t nl = text.find('\n', at);
-        if (nl == std::string::npos) nl = text.size();
-        pin_tile_line_b(text.substr(at, nl - at).c_str());
-        at = nl + 1;
-    }
-}
-void gemm_bf16_tuner_export(std::string& out) {
-    std::lock_guard<std::mutex> lock(g_tuned_b_mu);
-    for (const auto& kv : g_tuned_b) {
-        char line[128];
-        snprintf(line, sizeof line, "%s %d %d %d %d %d %d\n", (kv.first.ob & 4) ? "mx8" : (kv.first.ob & 2) ? "fp8" : "bf16", kv.first.M, kv.first.N, kv.first.K, kv.first.epi,
-                 kv.first.ob, kv.second);
-        out += line;
-    }
-    for (const auto& kv : pair_b_map()) {
-        char line[192];
-        const ShapeKeyB &a = kv.first.a, &b = kv.first.b;
-        snprintf(line, sizeof line, "pairb %d %d %d %d %d %d %d %d %d %d %d\n", a.M, a.N, a.K, a.epi, a.ob, b.M, b.N, b.K, b.epi, b.ob, kv.second);
-        out += line;
-    }
-}
-
 static int heuristic_b(int M, int N) {
     static const int order[] = {2, 1, 0, 3, 5};       // largest tile that still gives every CU >= 2 workgroups' worth of work
     for (int c : order) {
@@ -607,77 +453,68 @@ static int heuristic_b(int M, int N) {
     }
     return 5;
 }
+static int heuristic_mx(int M, int N) { return (long)((M + 127) / 128) * ((N + 127) / 128) >= 256 ? 0 : 6; }
+static int first_cfg(int, int) { return 0; }
+
+// What tells the three families apart on the host.  Per-shape tile selection is as in gemm.hip: every configuration of a family
+// produces bit-identical results, so the choice is purely a speed choice; each new (M, N, K, epilogue, output form) inside the family's
+// flop window is timed once on scratch outputs.
+struct FamilyB {
+    int family;                                                        // FAM_*: the forced configuration and the k rule (gemm_tuner.h)
+    const TileCfgB* cfgs;
+    hipError_t (*launch)(int c, const GemmParams& p, hipStream_t s);
+    int key_bits;                                                      // the family's bits of its keys' tag
+    double max_flops;                                                  // the tuning window is [2.5e8, max_flops]
+    int (*untuned)(int M, int N);                                      // the configuration of a shape outside the window
+    int (*fallback)(int M, int N);                                     // ... and of a shape inside it whose trials cannot run
+};
+static const FamilyB kFamiliesB[3] = {{FAM_BF16, kCfgsB, launch_cfg_b, 0, 1.6e12, heuristic_b, heuristic_b},
+                                      {FAM_FP8, kCfgsF8, launch_cfg_f8, 2, HUGE_VAL, first_cfg, first_cfg},
+                                      {FAM_MX8, kCfgsMx, launch_cfg_mx, 4, HUGE_VAL, heuristic_mx, first_cfg}};
+static const FamilyB& family_of(const GemmParams& p) { return kFamiliesB[p.fp8 == 2 ? 2 : p.fp8 ? 1 : 0]; }
+static ShapeKey shape_key_b(const GemmParams& p) {
+    return ShapeKey{p.M, p.N, p.K, p.epi, p.out_bf16 | family_of(p).key_bits | (p.fp8 == 2 && p.out_mx8 ? 8 : 0)};
+}
 
 // With several batches in flight (fern_tuner_set_concurrency) a launch that leaves workgroup slots free is cheaper than its isolated time:
-// the other lanes' kernels run in them.  The tuners score a candidate as time x share^e, share = the fraction of the chip's slots it fills.
+// the other lanes' kernels run in them.  The tuner scores a candidate as time x share^e, share = the fraction of the chip's slots it fills.
 static double share_exponent() {
     static const double expo = [] { const char* e = getenv("FERN_TUNE_SHARE_EXP"); return e ? atof(e) : 0.75; }();      // A/B knob (tools/c5_exp_ab.sh: 0 = latency score 17.9-18.3 k queries/s on c5, 0.5 ... 1.5 all 19.2-19.5 k)
     return expo;
 }
 
-// `tuned` = false: nothing was timed (tuning off, stream capture, no scratch): the caller must not cache the fallback
-static int tune_shape_b(const GemmParams& p, hipStream_t s, bool& tuned) {
-    LaunchTimerPause pause;
+// The trials of a shape (lookup_or_tune: `tuned`, and the caller holds the store's lock).  Rounds outermost: two rounds, each candidate
+// keeps its faster time (the first launches after an idle spell run on ramping clocks).
+static int tune_shape_b(const FamilyB& fam, const GemmParams& p, hipStream_t s, bool& tuned) {
     tuned = false;
-    const bool f8 = p.fp8 != 0;
-    auto launch = p.fp8 == 2 ? launch_cfg_mx : f8 ? launch_cfg_f8 : launch_cfg_b;
-    const int fallback = f8 ? 0 : heuristic_b(p.M, p.N);
-    const char* e = getenv("FERN_GEMM_TUNE");
-    if (e && e[0] == '0') return fallback;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return fallback;
-    float* scratch = nullptr;
-    if (hipMalloc(&scratch, (size_t)p.M * p.ldc * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return fallback; }
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
+    const int fallback = fam.fallback(p.M, p.N);
+    if (!tuning_enabled()) return fallback;
+    TrialTimer timer(s);
     GemmParams q = p;
-    q.C = scratch;            // the residual input is only read: tuning has no side effects on the caller's buffers
-    if (p.out_mx8) { q.mxc = reinterpret_cast<unsigned char*>(scratch) + (size_t)p.M * p.ldc; q.mxc_rows = p.M; }   // bytes [M*ldc, M*ldc + M*N/32)
-    // two rounds, each candidate keeps its faster time (the first launches after an idle spell run on ramping clocks)
-    const int ncand = p.fp8 == 2 ? kNumCfgsMx : f8 ? kNumCfgsF8 : kNumCfgsB;
+    q.C = static_cast<float*>(timer.scratch((size_t)p.M * p.ldc * sizeof(float)));      // the residual input is only read: tuning has no side effects on the caller's buffers
+    if (!timer.ok()) return fallback;
+    if (p.out_mx8) { q.mxc = reinterpret_cast<unsigned char*>(q.C) + (size_t)p.M * p.ldc; q.mxc_rows = p.M; }   // bytes [M*ldc, M*ldc + M*N/32)
+    const int ncand = kFamilies[fam.family].ncfg;
     float t[16];
     for (float& v : t) v = 1e30f;
     for (int round = 0; round < 2; ++round)
-        for (int c = 0; c < ncand; ++c) {
-            if (!f8 && p.K % kCfgsB[c].bk) continue;
-            if (launch(c, q, s) != hipSuccess) continue;                       // warm
-            (void)hipEventRecord(e0, s);
-            (void)launch(c, q, s);
-            (void)launch(c, q, s);
-            (void)hipEventRecord(e1, s);
-            if (hipEventSynchronize(e1) != hipSuccess) continue;
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            t[c] = ms < t[c] ? ms : t[c];
-        }
+        for (int c = 0; c < ncand; ++c)
+            if (cfg_fits(fam.family, c, p.K)) t[c] = std::min(t[c], timer.best_ms([&] { return fam.launch(c, q, s); }, 1, 2));
+    const int conc = choice_store().concurrency;
     int best = fallback;
     float best_ms = 1e30f;
-    const TileCfgB* cfgs = p.fp8 == 2 ? kCfgsMx : f8 ? kCfgsF8 : kCfgsB;
     for (int c = 0; c < ncand; ++c) {
         if (t[c] > 1e29f) continue;
         float score = t[c];
-        if (g_tune_concurrency > 1) {      // caller holds g_tuned_b_mu
-            const double nwg = (double)((p.M + cfgs[c].bm - 1) / cfgs[c].bm) * ((p.N + cfgs[c].bn - 1) / cfgs[c].bn);
-            const double share = std::min(1.0, nwg / (256.0 * cfgs[c].per_cu));
+        if (conc > 1) {
+            const double nwg = (double)((p.M + fam.cfgs[c].bm - 1) / fam.cfgs[c].bm) * ((p.N + fam.cfgs[c].bn - 1) / fam.cfgs[c].bn);
+            const double share = std::min(1.0, nwg / (256.0 * fam.cfgs[c].per_cu));
             score *= (float)std::pow(share, share_exponent());
         }
         if (score < best_ms) { best_ms = score; best = c; }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(scratch);
     tuned = best_ms < 1e29f;
     return best;
-}
-static int tuned_cfg_b(const ShapeKeyB& key, const GemmParams& p, hipStream_t s) {
-    std::lock_guard<std::mutex> lock(g_tuned_b_mu);
-    auto it = g_tuned_b.find(key);
-    if (it != g_tuned_b.end()) return it->second;
-    bool tuned = false;
-    const int c = tune_shape_b(p, s, tuned);
-    if (tuned) g_tuned_b.emplace(key, c);
-    return c;
 }
 
 // the argument checks of the family (launch_gemm_bf16 and the pair launcher below)
@@ -695,53 +532,20 @@ static bool rp_args_ok(const GemmParams& p) {
     return true;
 }
 
-// the tile configuration launch_gemm_bf16 runs p with (forced / tuned per shape / heuristic); fam: 2 block-scaled, 1 per-row fp8, 0 bf16
-static int resolve_cfg_b(const GemmParams& p, hipStream_t s, int* fam) {
-    if (p.fp8 == 2) {
-        *fam = 2;
-        int c = forced_value_b(g_force_mx, "FERN_GEMM_MX8_CFG");
-        if (c < 0 || c >= kNumCfgsMx) {
-            c = (long)((p.M + 127) / 128) * ((p.N + 127) / 128) >= 256 ? 0 : 6;
-            if (2.0 * p.M * (double)p.N * p.K >= 2.5e8) {
-                const ShapeKeyB key{p.M, p.N, p.K, p.epi, p.out_bf16 | 4 | (p.out_mx8 ? 8 : 0)};
-                c = tuned_cfg_b(key, p, s);
-            }
-        }
-        return c;
-    }
-    if (p.fp8) {
-        *fam = 1;
-        int c = forced_value_b(g_force_f8, "FERN_GEMM_FP8_CFG");
-        if (c < 0 || c >= kNumCfgsF8) {
-            c = 0;
-            if (2.0 * p.M * (double)p.N * p.K >= 2.5e8) {
-                const ShapeKeyB key{p.M, p.N, p.K, p.epi, p.out_bf16 | 2};
-                c = tuned_cfg_b(key, p, s);
-            }
-        }
-        return c;
-    }
-    *fam = 0;
-    int c = forced_cfg_b();
-    if (c < 0 || c >= kNumCfgsB || p.K % kCfgsB[c].bk) {
-        const double flops = 2.0 * p.M * (double)p.N * p.K;
-        if (flops >= 2.5e8 && flops <= 1.6e12) {
-            const ShapeKeyB key{p.M, p.N, p.K, p.epi, p.out_bf16};
-            c = tuned_cfg_b(key, p, s);
-        } else {
-            c = heuristic_b(p.M, p.N);
-        }
-    }
-    return c;
-}
-
 hipError_t launch_gemm_bf16(const GemmParams& p, hipStream_t s) {
     if (p.M <= 0 || p.N <= 0) return hipSuccess;
-    load_pinned_tiles_b();
     if (!rp_args_ok(p)) return hipErrorInvalidValue;
-    int fam = 0;
-    const int c = resolve_cfg_b(p, s, &fam);
-    return fam == 2 ? launch_cfg_mx(c, p, s) : fam == 1 ? launch_cfg_f8(c, p, s) : launch_cfg_b(c, p, s);
+    const FamilyB& fam = family_of(p);
+    // the configuration: forced, else (inside the flop window) stored or tuned per shape, else the family's heuristic
+    int c = forced_cfg(fam.family);
+    if (!cfg_fits(fam.family, c, p.K)) {
+        const double flops = 2.0 * p.M * (double)p.N * p.K;
+        if (flops >= 2.5e8 && flops <= fam.max_flops)
+            c = lookup_or_tune(choice_store().rp, shape_key_b(p), [&](bool& tuned) { return tune_shape_b(fam, p, s, tuned); });
+        else
+            c = fam.untuned(p.M, p.N);
+    }
+    return fam.launch(c, p, s);
 }
 
 // ---- image + text GEMM pair of the mixed mode, ONE launch (round 6) -------------------------------------------------------------------
@@ -779,52 +583,22 @@ static hipError_t launch_mxbf_pair(int v, const GemmParams& p1, const GemmParams
     return hipGetLastError();
 }
 // per (block-scaled shape, bf16 shape): 0 = two launches (each with its own tuned tile), 1 / 2 = the pair kernel V = 0 / 1.  Timed once on
-// scratch outputs; exported / pinned / imported with the tile choices ("pairb ..." lines).
-static std::map<PairKeyB, int> g_pair_b;      // guarded by g_tuned_b_mu
-static std::map<PairKeyB, int>& pair_b_map() { return g_pair_b; }
-static thread_local int g_last_dispatches_b = 1;
-int gemm_bf16_last_dispatches() { return g_last_dispatches_b; }
+// scratch outputs; exported / pinned / imported with the tile choices ("pairb ..." lines).  Candidates outermost: the two-launch form
+// first, all of its rounds (its warm launches also tune the two shapes), then each pair form.
 static int tune_pair_b(const GemmParams& p1, const GemmParams& p2, hipStream_t s, bool& timed) {
-    LaunchTimerPause pause;
     timed = false;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return 0;
+    TrialTimer timer(s);
     // scratch outputs: the residual inputs are only read, so the trials have no side effects (a quantising first problem also writes scales)
-    const size_t b1 = (size_t)p1.M * p1.ldc * sizeof(float) + (p1.out_mx8 ? (size_t)p1.M * p1.N / 32 + 256 : 0), b2 = (size_t)p2.M * p2.ldc * sizeof(float);
-    char *c1 = nullptr, *c2 = nullptr;
-    if (hipMalloc(&c1, b1) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    if (hipMalloc(&c2, b2) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(c1); return 0; }
+    const size_t c1_bytes = (size_t)p1.M * p1.ldc * sizeof(float);
     GemmParams q1 = p1, q2 = p2;
-    q1.C = reinterpret_cast<float*>(c1);
-    q2.C = reinterpret_cast<float*>(c2);
-    if (p1.out_mx8) { q1.mxc = reinterpret_cast<unsigned char*>(c1) + (size_t)p1.M * p1.ldc * sizeof(float); q1.mxc_rows = p1.M; }
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    auto timed_ms = [&](auto&& fn) {
-        float best = 1e30f;
-        for (int round = 0; round < 3; ++round) {
-            if (fn() != hipSuccess) return 1e30f;
-            (void)hipEventRecord(e0, s);
-            (void)fn();
-            (void)fn();
-            (void)fn();
-            (void)hipEventRecord(e1, s);
-            if (hipEventSynchronize(e1) != hipSuccess) return 1e30f;
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            best = std::min(best, ms);
-        }
-        return best;
-    };
+    q1.C = static_cast<float*>(timer.scratch(c1_bytes + (p1.out_mx8 ? (size_t)p1.M * p1.N / 32 + 256 : 0)));
+    q2.C = static_cast<float*>(timer.scratch((size_t)p2.M * p2.ldc * sizeof(float)));
+    if (!timer.ok()) return 0;
+    if (p1.out_mx8) { q1.mxc = reinterpret_cast<unsigned char*>(q1.C) + c1_bytes; q1.mxc_rows = p1.M; }
     float t[3];
-    t[0] = timed_ms([&] { const hipError_t e = launch_gemm_bf16(q1, s); return e != hipSuccess ? e : launch_gemm_bf16(q2, s); });
-    t[1] = timed_ms([&] { return launch_mxbf_pair(0, q1, q2, s); });
-    t[2] = timed_ms([&] { return launch_mxbf_pair(1, q1, q2, s); });
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(c1);
-    (void)hipFree(c2);
+    t[0] = timer.best_ms([&] { const hipError_t e = launch_gemm_bf16(q1, s); return e != hipSuccess ? e : launch_gemm_bf16(q2, s); }, 3, 3);
+    t[1] = timer.best_ms([&] { return launch_mxbf_pair(0, q1, q2, s); }, 3, 3);
+    t[2] = timer.best_ms([&] { return launch_mxbf_pair(1, q1, q2, s); }, 3, 3);
     if (t[0] > 1e29f) return 0;
     timed = true;
     // Which pair form: alone the two are within a few per cent of each other on the ViT shapes (the choice flipped from run to run); with four
@@ -834,47 +608,19 @@ static int tune_pair_b(const GemmParams& p1, const GemmParams& p2, hipStream_t s
     // same fraction of their slots), so under concurrency the 8-wave form must win alone by 10 %.  Pair or two launches: plain times -- the
     // share score overrates what the other lanes make of a short text launch's free slots (it chose two launches for three of the four
     // pairs; measured 2-4 % below the pairs).
-    int conc;
-    {
-        std::lock_guard<std::mutex> lock(g_tuned_b_mu);
-        conc = g_tune_concurrency;
-    }
-    const float sc[2] = {t[1], conc > 1 ? t[2] * 1.10f : t[2]};
+    const float sc[2] = {t[1], tuner_concurrency() > 1 ? t[2] * 1.10f : t[2]};
     const int form = sc[1] < sc[0] ? 2 : 1;
     return t[form] < t[0] ? form : 0;
 }
-static bool pair_b_enabled() {
-    static const bool on = [] { const char* e = getenv("FERN_GEMM_PAIR"); return !(e && e[0] == '0'); }();
-    return on;
-}
 // p1: a block-scaled GEMM (fp8 == 2), p2: a bf16 GEMM (fp8 == 0); one launch where a one-off timing says it wins, two otherwise
 hipError_t launch_gemm_mxbf_pair(const GemmParams& p1, const GemmParams& p2, hipStream_t s) {
-    g_last_dispatches_b = 1;
+    g_last_dispatches = 1;
     int choice = 0;
-    if (pair_b_enabled() && p1.fp8 == 2 && p2.fp8 == 0 && p1.M >= 256 && p2.M >= 256 && p1.N >= 256 && p2.N >= 256 && rp_args_ok(p1) && rp_args_ok(p2) &&
-        forced_value_b(g_force_mx, "FERN_GEMM_MX8_CFG") < 0 && forced_cfg_b() < 0) {
-        const char* e = getenv("FERN_GEMM_TUNE");
-        if (!(e && e[0] == '0')) {
-            load_pinned_tiles_b();
-            const PairKeyB key{ShapeKeyB{p1.M, p1.N, p1.K, p1.epi, p1.out_bf16 | 4 | (p1.out_mx8 ? 8 : 0)}, ShapeKeyB{p2.M, p2.N, p2.K, p2.epi, p2.out_bf16}};
-            bool known = false;
-            {
-                std::lock_guard<std::mutex> lock(g_tuned_b_mu);
-                auto it = g_pair_b.find(key);
-                if (it != g_pair_b.end()) { known = true; choice = it->second; }
-            }
-            if (!known) {                                   // (the two-launch trial takes the mutex itself: tuned_cfg_b)
-                bool timed = false;
-                choice = tune_pair_b(p1, p2, s, timed);
-                if (timed) {
-                    std::lock_guard<std::mutex> lock(g_tuned_b_mu);
-                    g_pair_b[key] = choice;
-                }
-            }
-        }
-    }
+    if (pair_enabled() && p1.fp8 == 2 && p2.fp8 == 0 && p1.M >= 256 && p2.M >= 256 && p1.N >= 256 && p2.N >= 256 && rp_args_ok(p1) && rp_args_ok(p2) &&
+        forced_cfg(FAM_MX8) < 0 && forced_cfg(FAM_BF16) < 0 && tuning_enabled())
+        choice = lookup_or_tune_pair(choice_store().pairb, PairKey{shape_key_b(p1), shape_key_b(p2)}, [&](bool& timed) { return tune_pair_b(p1, p2, s, timed); });
     if (choice == 1 || choice == 2) return launch_mxbf_pair(choice - 1, p1, p2, s);
-    g_last_dispatches_b = 2;
+    g_last_dispatches = 2;
     const hipError_t e1 = launch_gemm_bf16(p1, s);
     return e1 != hipSuccess ? e1 : launch_gemm_bf16(p2, s);
 }

@@ -211,24 +211,21 @@ inline long mx_scale_offset(long r, long b, long srows) { return ((b >> 2) * sro
 int gemm_num_col_blocks(int M, int N, int K);
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s);
 hipError_t launch_gemm_pair(const GemmParams& p1, const GemmParams& p2, hipStream_t s);      // two plain GEMMs, ONE launch when p1's tuned plan is a mixed plan (gemm.hip)
-int gemm_last_dispatches();      // kernel dispatches of the calling thread's last launch_gemm (2 for a bulk + remainder plan)
+int gemm_last_dispatches();      // kernel dispatches of the calling thread's last launch_gemm / launch_gemm_pair / launch_gemm_mxbf_pair (2 for a bulk + remainder plan)
 // bf16 x bf16 -> fp32-accumulate GEMM (v_mfma_f32_32x32x16_bf16); plain epilogues only, K % 32 == 0, ALOAD_PLAIN
 hipError_t launch_gemm_bf16(const GemmParams& p, hipStream_t s);
 hipError_t launch_gemm_mxbf_pair(const GemmParams& p_mx8, const GemmParams& p_bf16, hipStream_t s);      // image (block-scaled) + text (bf16) GEMM of a layer, ONE launch where it wins
-int gemm_bf16_last_dispatches();
 hipError_t launch_gemm_pp(bool mx, const GemmParams& p, hipStream_t s);      // gemm_pp.hip: the ping-pong 256 x 256 tile (cfg 7 / 11 of the bf16 / block-scaled families)
-// the per-shape tile choices made so far, one text line per shape (the format FERN_GEMM_TILES=<file> reads back)
+// ---- the tuners' state (gemm_tuner.hip) ----
+// the per-shape choices of all GEMM families made so far, one text line per choice (the format FERN_GEMM_TILES=<file> reads back)
 void gemm_tuner_export(std::string& out);
-void gemm_bf16_tuner_export(std::string& out);
 // the reverse: lines of that format replace this process's choices for the listed shapes
 void gemm_tuner_import(const std::string& text);
-void gemm_bf16_tuner_import(const std::string& text);
-// reduced-precision families: score trials for a pipeline that keeps `n` batches in flight on separate streams (gemm_bf16.hip)
-void gemm_bf16_tuner_set_concurrency(int n);
-// Force one tile configuration of a family at run time (family 0 fp32, 1 f32x3: gemm.hip; 2 bf16, 3 fp8, 4 block-scaled fp8: gemm_bf16.hip);
-// cfg < 0 returns to the environment's value (FERN_GEMM_CFG, ...).  Every configuration of a family gives the same bits.
-bool gemm_force_cfg(int family, int cfg);
-bool gemm_bf16_force_cfg(int family, int cfg);
+// reduced-precision families: score trials for a pipeline that keeps `n` batches in flight on separate streams
+void gemm_tuner_set_concurrency(int n);
+// Force one tile configuration of a family ("f32", "f32x3", "bf16", "fp8", "mx8") at run time; cfg < 0 returns to the environment's value
+// (FERN_GEMM_CFG, ...).  Every configuration of a family gives the same bits.  false: no such family.
+bool gemm_force_cfg(const char* family, int cfg);
 
 #ifdef __HIPCC__
 // 64-bit ranking keys: orderable(score) << 32 | ~index, so "score descending, index ascending" is one unsigned compare

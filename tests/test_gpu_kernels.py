@@ -360,6 +360,59 @@ def test_gemm_variants_are_bit_identical(engine):
         assert torch.equal(engine.gemm(a[lo:hi], w, b, epilogue=1).cpu(), full[lo:hi])
 
 
+@pytest.mark.parametrize("family,m,n,k", [("f32", 320, 512, 1024), ("f32", 2112, 256, 256), ("f32x3", 320, 512, 1024), ("f32x3", 2112, 256, 256),
+                                          ("bf16", 320, 512, 1024), ("fp8", 320, 512, 1024), ("mx8", 320, 512, 1024)])
+def test_first_sight_of_a_shape_is_tuned_once_and_stored_as_one_line(engine, family, m, n, k):
+    """The first unforced call of a shape inside the tuning window times the family's candidates and stores ONE choice: one new export
+    line of the family's kind under the shape's key, which an import accepts back; the result has the bits of a forced configuration
+    (a forced call tunes nothing and stores nothing), and later calls neither add a line nor change a bit.  320 x 512 x 1024 (3.4e8 flop,
+    just over the 2.5e8 floor) is ragged against every tile height; 2112 x 256 x 256 (2.8e8 flop, M >= 2048) also brings the bulk +
+    remainder and mixed plans into the fp32 trials.  No other test uses these two shapes: the tuner's state is process-wide."""
+    from fashionern_aaai2024_amd.engine import FernEngine
+    eng = FernEngine("cuda:0") if family == "f32x3" else engine
+    try:
+        if family in ("f32", "f32x3"):
+            a, w, b, _, _ = gemm_refs.f32_case(m, n, k)
+            if family == "f32x3":
+                eng.set_precision("f32x3")
+            run = lambda: eng.gemm(a, w, b, epilogue=0).cpu()  # noqa: E731
+            key = f"f32 {m} {n} {k} 0 0 " if family == "f32" else f"f32x3 {m} {n} {k} 0 "
+        elif family == "bf16":
+            _, ab, wb, b, _, _ = gemm_refs.bf16_case(m, n, k, 0)
+            ab, wb = ab.cuda(), wb.cuda()
+            run = lambda: eng.gemm_bf16(ab, wb, b, epilogue=0, out_bf16=False).cpu()  # noqa: E731
+            key = f"bf16 {m} {n} {k} 0 0 "
+        elif family == "fp8":
+            a8, sa, w8, sw, b, _, _, _ = gemm_refs.fp8_case(eng, m, n, k, 0)
+            run = lambda: eng.gemm_fp8(a8, sa, w8, sw, b, epilogue=0, out_bf16=False).cpu()  # noqa: E731
+            key = f"fp8 {m} {n} {k} 0 2 "
+        else:
+            a8, sa, w8, sw, b, _, _, _ = gemm_refs.mx8_case(eng, m, n, k, 0)
+            run = lambda: eng.gemm_mx8(a8, sa, w8, sw, b, epilogue=0, out_bf16=False).cpu()  # noqa: E731
+            key = f"mx8 {m} {n} {k} 0 4 "
+        eng.tuner_force_config(family, 8 if family == "f32" else 0)
+        try:
+            forced = run()
+        finally:
+            eng.tuner_force_config(family, -1)
+        before = eng.tuner_export().splitlines()
+        assert not [ln for ln in before if ln.startswith(key)], "a forced call stored a choice"
+        first = run()
+        after = eng.tuner_export().splitlines()
+        new = [ln for ln in after if ln not in before]
+        assert len(new) == 1 and new[0].startswith(key), new
+        assert len(after) == len(before) + 1
+        eng.tuner_import(new[0] + "\n")
+        assert eng.tuner_export().splitlines() == after, "the exported line was not accepted back as it is"
+        assert torch.equal(first.view(torch.int32), forced.view(torch.int32))
+        again = run()
+        assert eng.tuner_export().splitlines() == after
+        assert torch.equal(again.view(torch.int32), forced.view(torch.int32))
+    finally:
+        if eng is not engine:
+            eng.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("m,n,k", [(64, 128, 64), (197, 384, 96), (1000, 520, 256), (4096, 768, 768)])
 @pytest.mark.parametrize("epi", [0, 1, 2, 3])
