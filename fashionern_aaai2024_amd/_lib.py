@@ -84,6 +84,9 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fern_item_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_void_p, c_int, c_i64, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fern_gallery_upsert": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p]),
+    "fern_gallery_move": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p]),
+    "fern_scatter_u32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
     "fern_rank_set_strategy": (c_int, [c_void_p, c_int]),
     "fern_sweep_bf16_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_i64, c_void_p, c_i64, c_void_p]),
     "fern_gather_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -14,6 +14,7 @@
 
 #include "../../include/fern.h"
 #include "kernels.h"
+#include "live.h"
 
 using namespace fern;
 
@@ -138,6 +139,7 @@ struct fern_ctx {
     const fern_ctx* parent = nullptr;
     unsigned parent_generation = 0;
     int* tok_flag = nullptr;         // host-mapped: set by the text embedding kernel when a token id is out of range
+    int* live_flag = nullptr;        // host-mapped [3]: set by the live-gallery kernels (upsert, move, scatter) when a slot is out of range
     FusionW fusion;
     ClipW clip;
     Clip4CirW c4c;
@@ -512,6 +514,7 @@ static int begin_group(fern_ctx* c, int group) {
     return FERN_OK;
 }
 static int check_token_flag(fern_ctx* c, const char* fn);
+static int check_live_flags(fern_ctx* c, const char* fn);
 // Weight-reading entry points call this first: a fork made before the parent's last re-finalisation must not run.
 static int check_fresh(fern_ctx* c, const char* fn) {
     if (c->parent && c->parent->generation != c->parent_generation)
@@ -563,6 +566,7 @@ extern "C" int fern_ctx_destroy(fern_ctx* c) {
     for (auto& grp : c->owned)
         for (void* p : grp) (void)hipFree(p);
     if (c->tok_flag) (void)hipHostFree(c->tok_flag);
+    if (c->live_flag) (void)hipHostFree(c->live_flag);
     for (auto& b : c->blocks) (void)hipFree(b.p);
     for (auto& r : c->recs) {
         if (r.a) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -575,7 +579,8 @@ extern "C" int fern_ctx_destroy(fern_ctx* c) {
 extern "C" int fern_sync(fern_ctx* c, void* stream) {
     if (!c) return fail(FERN_ERR_ARG, "fern_sync: ctx is NULL");
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    return check_token_flag(c, "fern_sync");
+    FERN_TRY(check_token_flag(c, "fern_sync"));
+    return check_live_flags(c, "fern_sync");
 }
 
 extern "C" int fern_load_tensor(fern_ctx* c, const char* key, const void* host_ptr, int dtype, int ndim, const int64_t* shape) {
@@ -2086,6 +2091,67 @@ extern "C" int fern_gallery_prepare(fern_ctx* c, const float* gallery, int64_t N
     if (D % 4) return fail(FERN_ERR_ARG, "fern_gallery_prepare: D must be a multiple of 4");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(launch_gallery_prepare(gallery, out_bf16, (long)N, D, out_meta, (hipStream_t)stream));
+    return FERN_OK;
+}
+
+// ---- live gallery (include/fern.h; kernels: live.hip) ---------------------------------------------------------------------------
+// A slot outside [0, capacity) cannot raise from inside a kernel: the wave writes nothing and stores 1 + its position in the entry's
+// host-mapped flag; it is turned into FERN_ERR_ARG here, at fern_sync and at the next call of one of the three entries -- the scheme of
+// check_token_flag, without a synchronisation on the launch path.
+enum { LIVE_UPSERT = 0, LIVE_MOVE = 1, LIVE_SCATTER = 2, LIVE_ENTRIES = 3 };
+static const char* const kLiveNames[LIVE_ENTRIES] = {"fern_gallery_upsert", "fern_gallery_move", "fern_scatter_u32"};
+static int check_live_flags(fern_ctx* c, const char* fn) {
+    if (!c->live_flag) return FERN_OK;
+    for (int e = 0; e < LIVE_ENTRIES; ++e) {
+        const int v = __atomic_load_n(c->live_flag + e, __ATOMIC_RELAXED);
+        if (v == 0) continue;
+        for (int k = 0; k < LIVE_ENTRIES; ++k) __atomic_store_n(c->live_flag + k, 0, __ATOMIC_RELAXED);
+        return fail(FERN_ERR_ARG, std::string(fn) + ": an earlier " + kLiveNames[e] + " on this context was given a slot outside [0, capacity) at position " +
+                                      std::to_string(v - 1) + " of its call: that row was not written, the other rows of the call were");
+    }
+    return FERN_OK;
+}
+// Common head of the three entries: device, the flags (allocated on first use), the error an earlier call left behind.
+static int live_begin(fern_ctx* c, const char* fn) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->live_flag) {
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->live_flag), LIVE_ENTRIES * sizeof(int), hipHostMallocMapped));
+        for (int e = 0; e < LIVE_ENTRIES; ++e) c->live_flag[e] = 0;
+    }
+    return check_live_flags(c, fn);
+}
+
+extern "C" int fern_gallery_upsert(fern_ctx* c, const float* rows, int64_t ld, const int32_t* slots, int m, float* gallery, uint16_t* gallery_bf16,
+                                   float* meta, int64_t capacity, int D, int normalize, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_gallery_upsert: ctx is NULL");
+    if (m < 0 || capacity < 0 || D <= 0 || (m && (!rows || !slots))) return fail(FERN_ERR_ARG, "fern_gallery_upsert: bad argument");
+    if (!gallery && !gallery_bf16) return fail(FERN_ERR_ARG, "fern_gallery_upsert: give gallery, gallery_bf16 or both");
+    if (meta && (!gallery || !gallery_bf16)) return fail(FERN_ERR_ARG, "fern_gallery_upsert: meta belongs to the prepared form (gallery + gallery_bf16 + meta)");
+    if (D % 4) return fail(FERN_ERR_ARG, "fern_gallery_upsert: D must be a multiple of 4");
+    if (ld < D || ld % 4) return fail(FERN_ERR_ARG, "fern_gallery_upsert: need ld >= D and ld % 4 == 0");
+    if (normalize && D > 1280) return fail(FERN_ERR_ARG, "fern_gallery_upsert: normalize needs D <= 1280 (fern_l2_normalize's limit)");
+    FERN_TRY(live_begin(c, "fern_gallery_upsert"));
+    HIP_TRY(launch_gallery_upsert(rows, (long)ld, slots, m, gallery, gallery_bf16, meta, (long)capacity, D, normalize != 0, c->live_flag + LIVE_UPSERT,
+                                  (hipStream_t)stream));
+    return FERN_OK;
+}
+
+extern "C" int fern_gallery_move(fern_ctx* c, const int32_t* src, const int32_t* dst, int m, float* gallery, uint16_t* gallery_bf16, uint32_t* tags,
+                                 int32_t* items, int64_t capacity, int D, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_gallery_move: ctx is NULL");
+    if (m < 0 || capacity < 0 || D <= 0 || (m && (!src || !dst))) return fail(FERN_ERR_ARG, "fern_gallery_move: bad argument");
+    if (!gallery && !gallery_bf16) return fail(FERN_ERR_ARG, "fern_gallery_move: give gallery, gallery_bf16 or both");
+    if (D % 4) return fail(FERN_ERR_ARG, "fern_gallery_move: D must be a multiple of 4");
+    FERN_TRY(live_begin(c, "fern_gallery_move"));
+    HIP_TRY(launch_gallery_move(src, dst, m, gallery, gallery_bf16, tags, items, (long)capacity, D, c->live_flag + LIVE_MOVE, (hipStream_t)stream));
+    return FERN_OK;
+}
+
+extern "C" int fern_scatter_u32(fern_ctx* c, const uint32_t* src, const int32_t* slots, int m, uint32_t* dst, int64_t capacity, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_scatter_u32: ctx is NULL");
+    if (m < 0 || capacity < 0 || (m && (!src || !slots || !dst))) return fail(FERN_ERR_ARG, "fern_scatter_u32: bad argument");
+    FERN_TRY(live_begin(c, "fern_scatter_u32"));
+    HIP_TRY(launch_scatter_u32(src, slots, m, dst, (long)capacity, c->live_flag + LIVE_SCATTER, (hipStream_t)stream));
     return FERN_OK;
 }
 

@@ -4,30 +4,10 @@
 // patch means, embedding gathers, and the scalar-gate / attention-pooling tails of
 // CombinerSimple (fusion_model.py:92-94) and VisualSR (fusion_model.py:149-154).
 #include "kernels.h"
+#include "row_ops.h"      // RowRegs, row_load / row_store / row_sumsq, wave_sum, row_l2_normalize: shared with live.hip
 
 namespace fern {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int ROWS_PER_BLOCK = 4;   // 4 waves per workgroup, one row each
-constexpr int MAXV = 5;             // row width <= 64 lanes * 4 floats * MAXV = 1280 (2 x 640 for the CLIP4Cir Combiner)
-
-// Wave-wide reductions on the DPP network (quad swaps, half-row and row mirrors: every lane then holds its 16-lane row's value) plus
-// four readlanes added in a fixed order -- ~10 issue slots, against six dependent ds_bpermute round trips (~100 cycles each) for the
-// __shfl_xor butterfly.  The row kernels are one wave per row with two or three reductions each: that latency, not the bytes, was
-// most of a LayerNorm launch.  Results are the same for every lane and depend only on the row (batch-invariant).
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float lane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }   // (readlane is an int builtin)
-__device__ __forceinline__ float wave_sum(float v) {
-    v += dpp_move<0xB1>(v);       // quad_perm [1,0,3,2]
-    v += dpp_move<0x4E>(v);       // quad_perm [2,3,0,1]
-    v += dpp_move<0x141>(v);      // row_half_mirror
-    v += dpp_move<0x140>(v);      // row_mirror
-    return (lane_f(v, 0) + lane_f(v, 16)) + (lane_f(v, 32) + lane_f(v, 48));
-}
 __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, dpp_move<0xB1>(v));
     v = fmaxf(v, dpp_move<0x4E>(v));
@@ -41,34 +21,6 @@ __device__ __forceinline__ float quad_max(float v) {
     return fmaxf(v, dpp_move<0x4E>(v));
 }
 __device__ __forceinline__ float oct_max(float v) { v = quad_max(v); return fmaxf(v, dpp_move<0x141>(v)); }
-
-// A row of width d (d % 4 == 0, d <= 1024) held as up to MAXV float4 per lane: element c = (i*64 + lane)*4.
-struct RowRegs {
-    f32x4 v[MAXV];
-};
-
-__device__ __forceinline__ void row_load(RowRegs& r, const float* x, int d, int lane) {
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        f32x4 t = {0.f, 0.f, 0.f, 0.f};
-        if (c < d) t = *reinterpret_cast<const f32x4*>(x + c);
-        r.v[i] = t;
-    }
-}
-__device__ __forceinline__ void row_store(const RowRegs& r, float* y, int d, int lane) {
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) *reinterpret_cast<f32x4*>(y + c) = r.v[i];
-    }
-}
-__device__ __forceinline__ float row_sumsq(const RowRegs& r) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) s += r.v[i][0] * r.v[i][0] + r.v[i][1] * r.v[i][1] + r.v[i][2] * r.v[i][2] + r.v[i][3] * r.v[i][3];
-    return wave_sum(s);
-}
 
 // y = (x - mean) / sqrt(var + eps) * gamma + beta with the two-pass variance torch uses
 __device__ __forceinline__ void row_layernorm(RowRegs& r, const float* gamma, const float* beta, int d, int lane, float eps) {
@@ -608,10 +560,7 @@ __global__ __launch_bounds__(256) void l2norm_kernel(const float* x, const float
 #pragma unroll
         for (int i = 0; i < MAXV; ++i) r.v[i] += q.v[i];
     }
-    const float nrm = sqrtf(row_sumsq(r));
-    const float den = mode == 0 ? fmaxf(nrm, eps) : nrm + eps;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) r.v[i] = r.v[i] / den;
+    row_l2_normalize(r, eps, mode);
     row_store(r, y + row * ldy, d, lane);
 }
 

@@ -14,6 +14,7 @@
 // lower bound of the K-th best score; the full pass compares each finished 32x32 score tile with the bounds in registers and
 // appends only the survivors (~K*R of N per query) to per-query candidate lists (kernels.h: TopkFilter, topk.hip).
 #include "kernels.h"
+#include "row_ops.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -52,25 +53,10 @@ __global__ __launch_bounds__(256) void gallery_prepare_kernel(const float* x, u1
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= n) return;
-    float e2 = 0.f, t2 = 0.f, g2 = 0.f;
-    for (int c = lane * 4; c < d; c += 256) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + row * d + c);
-        ushort4 o;
-        o.x = f32_to_bf16_rne(v[0]); o.y = f32_to_bf16_rne(v[1]); o.z = f32_to_bf16_rne(v[2]); o.w = f32_to_bf16_rne(v[3]);
-        *reinterpret_cast<ushort4*>(y + row * d + c) = o;
-        const float r0 = bf16_bits_to_f32(o.x), r1 = bf16_bits_to_f32(o.y), r2 = bf16_bits_to_f32(o.z), r3 = bf16_bits_to_f32(o.w);
-        const float d0 = v[0] - r0, d1 = v[1] - r1, d2 = v[2] - r2, d3 = v[3] - r3;
-        e2 += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-        t2 += r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3;
-        g2 += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { e2 += __shfl_xor(e2, m); t2 += __shfl_xor(t2, m); g2 += __shfl_xor(g2, m); }
-    if (lane == 0) {      // non-negative floats order like their bit patterns; NaN / inf rows poison the bound upwards (a NaN margin accepts every row)
-        atomicMax(reinterpret_cast<unsigned*>(meta + 0), __float_as_uint(sqrtf(e2)));
-        atomicMax(reinterpret_cast<unsigned*>(meta + 1), __float_as_uint(sqrtf(t2)));
-        atomicMax(reinterpret_cast<unsigned*>(meta + 2), __float_as_uint(sqrtf(g2)));
-    }
+    GalleryNorms s;      // row_ops.h: the per-row arithmetic is shared with live.hip's upsert, bit for bit
+    for (int c = lane * 4; c < d; c += 256)
+        *reinterpret_cast<ushort4*>(y + row * d + c) = gallery_chunk(*reinterpret_cast<const f32x4*>(x + row * d + c), s);
+    gallery_norms_fold(s, lane, meta);
 }
 
 constexpr int ROWS_T = 32;              // gallery rows per wave tile

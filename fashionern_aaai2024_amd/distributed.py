@@ -18,7 +18,9 @@ same code runs over RCCL on GPUs and over gloo in the CPU tests.
 from __future__ import annotations
 
 import os
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
+
+import numpy as np
 
 import torch
 import torch.distributed as dist
@@ -188,6 +190,22 @@ def rank_sharded(engine, queries: torch.Tensor, gallery_shard: torch.Tensor, sha
     _all_gather_into(all_s, s)
     _all_gather_into(all_i, i)
     return engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
+
+
+def route_rows(slots, bounds) -> List[np.ndarray]:
+    """Host-side partition of a gallery UPDATE by owning shard.  `slots` [m] are global gallery rows (the slots of a sharded
+    `live_gallery.LiveGallery`: shard r holds rows [bounds[r], bounds[r + 1]) and its store has ``slot_offset = bounds[r]``), `bounds`
+    the W + 1 ascending shard boundaries.  Returns W int64 arrays: for each rank the POSITIONS in `slots` (ascending, so the caller's
+    order is kept) of the rows it owns -- ``rows[idx[r]]`` / ``slots[idx[r]]`` is what rank r appends or replaces.  No collective: an
+    update is routed, each shard applies its part.  Raises on a slot outside [bounds[0], bounds[-1])."""
+    sl = np.asarray(slots).astype(np.int64).reshape(-1)
+    b = np.asarray(bounds, dtype=np.int64).reshape(-1)
+    if b.size < 2 or (np.diff(b) < 0).any():
+        raise ValueError("bounds must be W + 1 ascending shard boundaries")
+    if sl.size and (sl.min() < b[0] or sl.max() >= b[-1]):
+        raise IndexError(f"a slot lies outside [{int(b[0])}, {int(b[-1])})")
+    owner = np.searchsorted(b, sl, side="right") - 1
+    return [np.nonzero(owner == r)[0] for r in range(b.size - 1)]
 
 
 def _all_reduce_sum(x: torch.Tensor) -> torch.Tensor:

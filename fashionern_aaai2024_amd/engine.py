@@ -42,7 +42,8 @@ class PreparedGallery:
     `FernEngine.sim_topk` takes to run the ranking stage as one HBM-bound pass over the bf16 rows + exact fp32 rescoring of the few
     rows that can still be in the top-K.  Results are those of the fp32 gallery, bit for bit.  Build it once per gallery
     (`FernEngine.prepare_gallery`), like the reference builds its index once per evaluation (run/test/test_fiq.py:45-46); rebuild
-    it when the gallery's contents change."""
+    it when the gallery's contents change -- or keep the store in a `live_gallery.LiveGallery`, which changes rows in place and hands out
+    `PreparedGallery` views whose addresses never move."""
 
     __slots__ = ("f32", "bf16", "meta")
 
@@ -666,6 +667,62 @@ class FernEngine:
         out = torch.empty(g.shape, dtype=torch.bfloat16, device=self.device)
         _lib.check(self.lib.fern_gallery_to_bf16(self._h, _ptr(g), _ptr(out), g.shape[0], g.shape[1], _stream()), "fern_gallery_to_bf16")
         return out
+
+    # ---- live gallery: rows of a store change in place (include/fern.h: fern_gallery_upsert; live_gallery.LiveGallery owns the slots) ----
+    def _slots(self, slots, what: str = "slots") -> torch.Tensor:
+        t = torch.as_tensor(slots).to(device=self.device, dtype=torch.int32).contiguous()
+        if t.dim() != 1:
+            raise ValueError(f"{what} must be [m], got {tuple(t.shape)}")
+        return t
+
+    @staticmethod
+    def _store(f32, bf16):
+        """(capacity, D) of a store given as its fp32 rows, its bf16 rows or both; the arrays are written in place, so they must already
+        be contiguous device tensors of the right type."""
+        for t, dt in ((f32, torch.float32), (bf16, torch.bfloat16)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.dim() == 2 and t.is_contiguous()):
+                raise ValueError(f"a store array must be a contiguous [capacity, D] {dt} device tensor")
+        if f32 is None and bf16 is None:
+            raise ValueError("give the store's f32 rows, its bf16 rows or both")
+        if f32 is not None and bf16 is not None and f32.shape != bf16.shape:
+            raise ValueError(f"f32 {tuple(f32.shape)} and bf16 {tuple(bf16.shape)} must have one shape")
+        return tuple((f32 if f32 is not None else bf16).shape)
+
+    def gallery_upsert(self, rows, slots, f32=None, bf16=None, meta=None, normalize: bool = False) -> None:
+        """Write rows [m, D] into slots [m] of a store IN PLACE: `f32` [capacity, D] gets the row (after `normalize`: F.normalize), `bf16` its
+        round-to-nearest-even copy, and `meta` is raised to the rows' three norms (never reset) -- all forms in one launch, with the
+        arithmetic of `prepare_gallery`.  A device fp32 `rows` with unit column stride is read through its row stride (no copy)."""
+        cap, d = self._store(f32, bf16)
+        if not (isinstance(rows, torch.Tensor) and rows.device == self.device and rows.dtype == torch.float32 and rows.dim() == 2
+                and rows.stride(1) == 1 and rows.stride(0) >= rows.shape[1]):
+            rows = self._f32(rows)
+        if rows.dim() != 2 or rows.shape[1] != d:
+            raise ValueError(f"rows must be [m, {d}], got {tuple(rows.shape)}")
+        sl = self._slots(slots)
+        if sl.shape[0] != rows.shape[0]:
+            raise ValueError(f"{rows.shape[0]} rows for {sl.shape[0]} slots")
+        _lib.check(self.lib.fern_gallery_upsert(self._h, _ptr(rows), rows.stride(0), _ptr(sl),
+                                                sl.shape[0], _ptr(f32), _ptr(bf16), _ptr(meta), cap, d, int(bool(normalize)), _stream()),
+                   "fern_gallery_upsert")
+
+    def gallery_move(self, src, dst, f32=None, bf16=None, tags=None, items=None) -> None:
+        """Copy row src[p] onto row dst[p] of every array given (compaction); `src` and `dst` are disjoint sets of slots."""
+        cap, d = self._store(f32, bf16)
+        s, t = self._slots(src, "src"), self._slots(dst, "dst")
+        if s.shape != t.shape:
+            raise ValueError("src and dst must have one length")
+        _lib.check(self.lib.fern_gallery_move(self._h, _ptr(s), _ptr(t), s.shape[0], _ptr(f32), _ptr(bf16), _ptr(tags), _ptr(items), cap, d, _stream()),
+                   "fern_gallery_move")
+
+    def scatter_u32(self, src, slots, dst: torch.Tensor) -> None:
+        """dst[slots[p]] = src[p] on 32-bit words (tags; item ids as bits); `dst` is an int32 device tensor written in place."""
+        if not (isinstance(dst, torch.Tensor) and dst.is_cuda and dst.dtype == torch.int32 and dst.dim() == 1 and dst.is_contiguous()):
+            raise ValueError("dst must be a contiguous int32 [capacity] device tensor")
+        v = _bits32(src, "src").to(self.device).contiguous()
+        sl = self._slots(slots)
+        if v.shape != sl.shape:
+            raise ValueError(f"{v.numel()} values for {sl.shape[0]} slots")
+        _lib.check(self.lib.fern_scatter_u32(self._h, _ptr(v), _ptr(sl), sl.shape[0], _ptr(dst), dst.shape[0], _stream()), "fern_scatter_u32")
 
     def sim_topk_bf16(self, q, gallery_bf16: torch.Tensor, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
         if row_filter is not None:

@@ -129,7 +129,10 @@ class ComposedQueryPipeline:
         for it -- one store for several categories, withdrawn rows hidden without re-preparing the gallery; its tags are a static
         pointer of a captured graph, its per-query mask / value travel through the lane's static buffers like `exclude_idx`.  `items`
         (`ItemMap`): the ranking is item-level (engine.sim_topk_items: one place per item, represented by its best eligible row) and
-        `QueryResult.item` holds the item id of every place; the ids are a static pointer of a captured graph, like the tags."""
+        `QueryResult.item` holds the item id of every place; the ids are a static pointer of a captured graph, like the tags.
+        A gallery that CHANGES between submits (`live_gallery.LiveGallery`; its `full=True` views keep a captured graph valid) is updated
+        under a two-line protocol -- ``pipe.fence(); live.append(rows)`` on the caller's stream: `fence` orders the update behind every
+        lane still sweeping the store, and the next `submit` waits for the caller's stream, so it sees the update."""
         if (images is None) == (ref_feats is None):
             raise ValueError("give either images (encoded per query) or ref_feats (looked up in the index), not both / neither")
         if members is not None and gallery.dtype != torch.float32:
@@ -240,6 +243,14 @@ class ComposedQueryPipeline:
                 dst.copy_(src, non_blocking=True)
         lg.graph.replay()
         return tuple(None if o is None else o.clone() for o in lg.outputs)
+
+    def fence(self) -> None:
+        """Make the caller's current stream wait for everything enqueued on every lane so far (GPU-side waits, no host synchronisation):
+        work the caller enqueues next -- an in-place update of the gallery the lanes rank against -- cannot overtake a lane that is
+        still sweeping it.  The other direction needs nothing: `submit` makes its lane wait for the caller's stream."""
+        cur = torch.cuda.current_stream()
+        for s in self.streams:
+            cur.wait_stream(s)
 
     def set_precision(self, precision) -> None:
         """Encoder operand precision of every lane ("fp32" parity mode / "bf16" perf mode, FernEngine.set_precision)."""

@@ -130,6 +130,10 @@ def build_parser(kind: str) -> ArgumentParser:
                         "three bf16 planes per operand (~1.4x faster); bf16 / fp8 / mx8 = perf modes (ViT / text towers)")
     p.add_argument("--rank-metrics", action="store_true",
                    help="fiq / cirr / 200k: after the recalls also print where the targets landed in the full ranking (Recall@K, median / mean rank, MRR)")
+    p.add_argument("--incremental-index", type=int, default=0, metavar="ROWS",
+                   help="build every gallery the way a serving process grows one: fuse the index in chunks of ROWS rows and append each to a "
+                        "LiveGallery (in-place upserts into a store of capacity N) instead of fusing and preparing it in one piece -- the same "
+                        "gallery bytes, the same numbers; single process only")
     p.add_argument("--force-quick-gelu", action="store_true",
                    help="QuickGELU, x * sigmoid(1.702 x), in both CLIP towers' MLPs: open_clip's force_quick_gelu, what it turns on for "
                         "pretrained='openai' -- needed for OpenAI's checkpoints (RN50x4's only public weights); default: the config's own "
@@ -164,10 +168,47 @@ def merged_category_metrics(kind: str, triples, clip_model, model, device, args)
     return _common.recalls_merged(model, predicted, index_fused, tags, starts, names, targets, ks)
 
 
+def _evaluate(kind, args, triples, clip_model, model, device, fn, say):
+    """The per-split evaluation loop of `main`: the reference's summary lines per split; returns the recall tuples."""
+    results = []
+    if getattr(args, "merged_gallery", False):
+        if args.rank_metrics:
+            raise SystemExit("--rank-metrics is not available with --merged-gallery")
+        results = merged_category_metrics(kind, triples, clip_model, model, device, args)
+        for (split, _, _), res in zip(triples, results):
+            say(split, "recalls:", res)
+        triples = []
+    for split, classic, relative in triples:
+        feats, names, local = fd.extract_index_features_sharded(classic, clip_model, args.patch_num, device, args.feature_dim,
+                                                                num_workers=0 if args.data_root else args.num_workers)
+        res = fn(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size, args.num_workers,
+                 args.clip_model_name)
+        say(split, "recalls:", res)
+        results.append(res)
+        if args.rank_metrics:
+            from . import rank_metrics
+            rank_fn = {"fiq": rank_metrics.compute_fiq_rank_metrics, "cirr": rank_metrics.compute_cirr_rank_metrics,
+                       "200k": rank_metrics.compute_200k_rank_metrics}.get(kind)
+            if rank_fn is None:
+                raise SystemExit(f"--rank-metrics is not available for {kind}")
+            say(split, "rank metrics:", rank_fn(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size,
+                                               args.num_workers, args.clip_model_name))
+        if getattr(args, "item_level", False):
+            from . import rank_metrics as _rm
+            res_items = _rm.compute_200k_item_metrics(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size,
+                                                            args.num_workers, args.clip_model_name)
+            say(split, "item-level: R@10 %.4f  R@50 %.4f  median place %.1f" % (res_items["recall@10"], res_items["recall@50"], res_items["median_rank"]))
+    return results
+
+
 def main(kind: str) -> None:
     args = build_parser(kind).parse_args()
     setup_seed(args.seed)
     rank, world, local = fd.init_from_env()                 # torchrun: one process per GPU; a lone process is (0, 1, 0)
+    if args.incremental_index < 0:
+        raise SystemExit("--incremental-index needs ROWS >= 1")
+    if args.incremental_index and world > 1:                # a sharded store is updated shard by shard (distributed.route_rows), not by one loop
+        raise SystemExit("--incremental-index is not available under torch.distributed with world > 1")
     if world > 1 and os.environ.get("FERN_BENCH_SHARE_GPU"):  # debug only: several ranks on the one GPU of a dev box (gloo)
         local = local % torch.cuda.device_count()
     device = torch.device("cuda", local) if world > 1 else torch.device("cuda")
@@ -197,34 +238,9 @@ def main(kind: str) -> None:
     else:
         triples = [(split,) + synthetic_split(kind, cfg, args.feature_dim, args.synthetic_gallery, args.synthetic_queries, args.seed + i)
                    for i, split in enumerate(splits)]
-    results = []
-    if getattr(args, "merged_gallery", False):
-        if args.rank_metrics:
-            raise SystemExit("--rank-metrics is not available with --merged-gallery")
-        results = merged_category_metrics(kind, triples, clip_model, model, device, args)
-        for (split, _, _), res in zip(triples, results):
-            say(split, "recalls:", res)
-        triples = []
-    for split, classic, relative in triples:
-        feats, names, local = fd.extract_index_features_sharded(classic, clip_model, args.patch_num, device, args.feature_dim,
-                                                                num_workers=0 if args.data_root else args.num_workers)
-        res = fn(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size, args.num_workers,
-                 args.clip_model_name)
-        say(split, "recalls:", res)
-        results.append(res)
-        if args.rank_metrics:
-            from . import rank_metrics
-            rank_fn = {"fiq": rank_metrics.compute_fiq_rank_metrics, "cirr": rank_metrics.compute_cirr_rank_metrics,
-                       "200k": rank_metrics.compute_200k_rank_metrics}.get(kind)
-            if rank_fn is None:
-                raise SystemExit(f"--rank-metrics is not available for {kind}")
-            say(split, "rank metrics:", rank_fn(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size,
-                                               args.num_workers, args.clip_model_name))
-        if getattr(args, "item_level", False):
-            from . import rank_metrics as _rm
-            res_items = _rm.compute_200k_item_metrics(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size,
-                                                            args.num_workers, args.clip_model_name)
-            say(split, "item-level: R@10 %.4f  R@50 %.4f  median place %.1f" % (res_items["recall@10"], res_items["recall@50"], res_items["median_rank"]))
+    from . import _common
+    with _common.incremental_index(args.incremental_index):
+        results = _evaluate(kind, args, triples, clip_model, model, device, fn, say)
     avg = [mean(r[j] for r in results) for j in range(len(results[0]))]
     if kind == "cirr":
         say("Average: ", (avg[4] + avg[0]) / 2)        # (R@5 + R_subset@1) / 2, test_cirr.py:198

@@ -20,6 +20,7 @@ changes.
 """
 from __future__ import annotations
 
+import contextlib
 from collections import Counter
 from typing import Dict, List, Optional, Sequence
 
@@ -224,10 +225,46 @@ def _submit_fuse(pipe_box, clip_model, model, device, *args):
         return pipe_box[0].submit_fuse(*args)
 
 
+_incremental_rows: Optional[int] = None      # set by `incremental_index` (the drivers' --incremental-index ROWS)
+
+
+@contextlib.contextmanager
+def incremental_index(rows: Optional[int]):
+    """While active, `fuse_index` builds every gallery the way a serving process grows one: fused in chunks of `rows` index rows, each
+    chunk appended to a `live_gallery.LiveGallery` (`fuse_index_incremental`).  None / 0: nothing changes.  Refused under
+    torch.distributed with more than one rank -- a sharded store is updated shard by shard (distributed.route_rows), not by this loop."""
+    global _incremental_rows
+    if rows and fd.world_info()[1] > 1:
+        raise RuntimeError("--incremental-index builds the gallery in one process: it is not available under torch.distributed with world > 1")
+    if rows is not None and int(rows) < 0:
+        raise ValueError(f"incremental index chunk must be >= 1 rows, got {rows}")
+    saved, _incremental_rows = _incremental_rows, (int(rows) if rows else None)
+    try:
+        yield
+    finally:
+        _incremental_rows = saved
+
+
+def fuse_index_incremental(model, index_features, index_local_features, rows: int):
+    """The fused gallery of `fuse_index` built incrementally: chunks of `rows` index rows are fused (test_fiq.py:45-46 per chunk: the
+    fusion is batch-invariant) and appended to a `LiveGallery` of capacity N.  Returns the store; its `gallery()` -- a `PreparedGallery`
+    over the N rows -- holds the bytes of the one-shot `fuse_index` + `prepare_gallery`."""
+    from ..live_gallery import LiveGallery
+    eng = _engine_of(model)
+    n, d = index_features.shape
+    live = LiveGallery(eng, max(int(n), 1), int(d), form="prepared", tags=False)
+    for o in range(0, n, int(rows)):
+        live.append(eng.index_fuse(index_features[o:o + rows], index_local_features[o:o + rows], normalize_input=True))
+    return live
+
+
 def fuse_index(model, index_features, index_local_features, prepared: bool = False):
     """test_fiq.py:45-46.  N ranks: each fuses ceil(N/W) rows, ONE all-gather replicates the fused gallery.  ``prepared``: under
     torch.distributed the ranking form of the gallery (`PreparedGallery`) is gathered too -- every rank prepares only its shard --
-    and returned instead of the tensor (what `_ranked` would otherwise build from the whole gallery on every rank)."""
+    and returned instead of the tensor (what `_ranked` would otherwise build from the whole gallery on every rank).  Inside
+    `incremental_index(rows)` the gallery is grown chunk by chunk in a `LiveGallery` instead and its prepared view is returned."""
+    if _incremental_rows:
+        return fuse_index_incremental(model, index_features, index_local_features, _incremental_rows).gallery()
     return fd.build_gallery(_engine_of(model), index_features, index_local_features, normalize_input=True, prepared=prepared)
 
 

@@ -314,7 +314,8 @@ FERN_API int fern_sim_topk_bf16(fern_ctx* ctx, const float* q /*[B,D] f32*/, con
  * bf16 MFMA rate), and only the few rows that can still be in the top-K are scored in fp32.
  *   fern_gallery_prepare: once per gallery (the reference builds its index once per evaluation, run/test/test_fiq.py:45-46):
  *       out_bf16 [N, D] = bf16(gallery) (round to nearest even = fern_gallery_to_bf16) and out_meta (DEVICE, 4 floats) =
- *       {max_n ||g_n - bf16(g_n)||, max_n ||bf16(g_n)||, max_n ||g_n||, 0}.  D % 4 == 0.  Re-run after the gallery changes.
+ *       {max_n ||g_n - bf16(g_n)||, max_n ||bf16(g_n)||, max_n ||g_n||, 0}.  D % 4 == 0.  Re-run after the gallery changes -- or change
+ *       its rows in place with fern_gallery_upsert, which keeps out_bf16 and out_meta valid.
  *   fern_sim_topk_prefiltered: per query b, |exact score - bf16 score| <= eps_b = ||q_b|| meta[0] + ||q_b - bf16(q_b)|| meta[1] + slack
  *       for EVERY row (Cauchy-Schwarz; slack = fp32 accumulation of both dot products), so every row of the exact top-K has a bf16
  *       score within 2 eps_b of the K-th best bf16 score: those rows -- K plus the few inside the margin -- are rescored with the exact
@@ -457,6 +458,42 @@ FERN_API int fern_item_count(fern_ctx* ctx, const float* q /*[B,D]*/, const floa
                              const uint64_t* keys /*[B,m]*/, int m, int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/,
                              int32_t* out_count /*[B,m]*/, const uint32_t* tags /*[N] or NULL*/, const uint32_t* mask /*[B]*/,
                              const uint32_t* value /*[B]*/, void* stream);
+/* Live gallery: change rows of a gallery store in place.  The reference builds its index once per evaluation (run/test/test_fiq.py:45-46)
+ * and never changes it; a serving process keeps one [capacity, D] store for its lifetime -- fp32 rows, their bf16 copy and its three norms
+ * (fern_gallery_prepare), one tag and one item id per row -- while its catalogue changes a few hundred rows at a time.  These three entry
+ * points write chosen SLOTS (row indices in [0, capacity)) of that store without a pass over the rows that stay; the addresses and shapes
+ * of the store never change, so hipGraphs captured against it stay valid.  Which slots are in use is the caller's bookkeeping (the Python
+ * layer's SlotTable); a free or withdrawn slot is hidden from the ranking by a "live" bit in its tag (fern_sim_topk_filtered).
+ * fern_gallery_upsert, for each p < m: row = rows[p * ld .. + D), optionally x / max(||x||, 1e-12) (`normalize`: the F.normalize of
+ *     run/test/test_fiq.py:45, fern_l2_normalize's arithmetic bit for bit; needs D <= 1280 like it); then gallery[slots[p]] = row,
+ *     gallery_bf16[slots[p]] = bf16(row) (round to nearest even) and meta[0..2] = max(meta[0..2], {||row - bf16(row)||, ||bf16(row)||,
+ *     ||row||}).  A row's bits and norms are computed by the device code of fern_gallery_prepare, so upserting every row of a gallery into a
+ *     zeroed store with zeroed meta gives that function's output byte for byte, and normalize = 1 equals fern_l2_normalize followed by
+ *     normalize = 0.  meta is NOT reset: a maximum that is only ever raised remains an upper bound over the rows present, which is all the
+ *     certificate of fern_sim_topk_prefiltered needs (results stay exact; fern_gallery_prepare over the store makes the bound tight again
+ *     after many replacements).  NaN / inf rows poison meta upwards, as there.  The gallery form follows from the pointers, as everywhere:
+ *     gallery + gallery_bf16 + meta (prepared), gallery only, gallery_bf16 only (the bf16-similarity store).  FERN_ERR_ARG: meta without
+ *     both arrays, neither array, ld < D, ld % 4 != 0, D % 4 != 0.  m == 0 succeeds and launches nothing.
+ *     Duplicate slots within one call are the caller's error: the contents of a duplicated slot are then undefined (its forms may come from
+ *     different rows) and a prepared store must be re-prepared.
+ * fern_gallery_move: gallery[dst[p]] = gallery[src[p]], and the same for whichever of gallery_bf16, tags, items are given (at least one of
+ *     gallery / gallery_bf16) -- compaction.  The index sets src and dst must be DISJOINT and dst free of duplicates.  meta is untouched: a
+ *     move changes no norm.
+ * fern_scatter_u32: dst[slots[p]] = src[p] -- tags and, as bits, item ids of upserted rows.
+ * Slots (src / dst of a move included) outside [0, capacity): that position writes nothing, the other positions of the call are written,
+ *     and FERN_ERR_ARG naming the entry point and the position is reported by fern_sync and by the next call of one of these three entry
+ *     points on the context (a host-mapped flag, as for fern_text_encode's token ids: a bounds check, not a fault path).
+ * ORDERING CONTRACT.  All three are asynchronous on `stream`, read nothing back and are graph-capturable.  A ranking call that reads the
+ *     store must be stream-ordered AFTER the update that wrote it, and an update must be stream-ordered after every ranking call still
+ *     reading the store: a sweep that overlaps an upsert can see a new fp32 row next to its old bf16 copy, and no certificate covers that.
+ *     Updates racing with sweeps are forbidden, not made safe. */
+FERN_API int fern_gallery_upsert(fern_ctx* ctx, const float* rows /*[m, ld], ld >= D*/, int64_t ld, const int32_t* slots /*[m] device*/, int m,
+                                 float* gallery /*[capacity, D] or NULL*/, uint16_t* gallery_bf16 /*[capacity, D] or NULL*/,
+                                 float* meta /*[4] device or NULL*/, int64_t capacity, int D, int normalize, void* stream);
+FERN_API int fern_gallery_move(fern_ctx* ctx, const int32_t* src /*[m]*/, const int32_t* dst /*[m]*/, int m, float* gallery, uint16_t* gallery_bf16,
+                               uint32_t* tags /*[capacity] or NULL*/, int32_t* items /*[capacity] or NULL*/, int64_t capacity, int D, void* stream);
+FERN_API int fern_scatter_u32(fern_ctx* ctx, const uint32_t* src /*[m]*/, const int32_t* slots /*[m]*/, int m, uint32_t* dst /*[capacity]*/,
+                              int64_t capacity, void* stream);
 /* scores of explicitly named gallery rows (CIRR subset ranking, run/test/test_cirr.py:64-66);
  * idx < 0 -> -inf */
 FERN_API int fern_gather_scores(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D]*/,

@@ -1,0 +1,446 @@
+"""Live gallery (include/fern.h: fern_gallery_upsert / fern_gallery_move / fern_scatter_u32; live_gallery.LiveGallery): rows of a gallery
+store change in place, and every result is BIT FOR BIT what a freshly prepared gallery of the same contents gives.
+
+There are no new numerics to bound, so there are no tolerances here: bytes of the store are compared with `fern_gallery_prepare` /
+`fern_gallery_to_bf16` / `fern_l2_normalize` of the same rows, rankings with oracle/chain.c (`chain_topk`) or with the same engine call on
+a fresh `prepare_gallery` of the final contents under the equivalent filter.  Shapes are the smallest that reach every path: a partial
+last block of four rows, D below / at / above one 256-float chunk per wave and at the row-register limit, a leading dimension wider
+than D inside a NaN frame, slots out of range, and a gallery whose certificate has to grow for the result to stay exact."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from framed import NAN, framed_like
+from oracle import chain
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+LIVE = 1 << 31
+
+
+def _rand(n, d, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(n, d, generator=g) * scale
+
+
+def _bits(t):
+    """The tensor's bytes as a host integer array (bf16 -> int16, fp32 / int32 -> int32)."""
+    t = t.detach().cpu().contiguous()
+    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32).numpy()
+
+
+def _same(a, b):
+    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
+
+
+def _zero_store(n, d, form="prepared"):
+    f32 = torch.zeros(n, d, device=DEV) if form != "bf16" else None
+    b16 = torch.zeros(n, d, dtype=torch.bfloat16, device=DEV) if form != "f32" else None
+    meta = torch.zeros(4, device=DEV) if form == "prepared" else None
+    return f32, b16, meta
+
+
+# ---- 1. upsert of everything = prepare ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", [36, 64, 512, 640])
+def test_upserting_every_row_into_a_zeroed_store_reproduces_prepare(engine, D):
+    n = 1001                                               # the last block of four rows is partial
+    gen = torch.Generator().manual_seed(D)
+    rows = _rand(n, D, 100 + D) * 10.0 ** (torch.rand(n, 1, generator=gen) * 4 - 2)      # row lengths over four decades
+    perm = torch.randperm(n, generator=gen)
+    want = torch.empty_like(rows)
+    want[perm] = rows                                      # row p lands in slot perm[p]
+    rows_d, slots = rows.to(DEV), perm.to(torch.int32).to(DEV)
+    f32, b16, meta = _zero_store(n, D)
+    cut = 333                                              # two calls of unequal size
+    engine.gallery_upsert(rows_d[:cut], slots[:cut], f32, b16, meta)
+    engine.gallery_upsert(rows_d[cut:], slots[cut:], f32, b16, meta)
+    fresh = engine.prepare_gallery(want)
+    assert _same(f32, want)
+    assert _same(b16, fresh.bf16)
+    assert _same(meta, fresh.meta) and float(meta[3]) == 0.0 and float(meta[2]) > 0.0
+    _, b16_only, _ = _zero_store(n, D, "bf16")            # the bf16-similarity store alone
+    engine.gallery_upsert(rows_d, slots, None, b16_only, None)
+    assert _same(b16_only, engine.gallery_to_bf16(want))
+    f32_only, _, _ = _zero_store(n, D, "f32")
+    engine.gallery_upsert(rows_d, slots, f32_only, None, None)
+    assert _same(f32_only, want)
+    engine.sync()
+
+
+# ---- 2. frames ------------------------------------------------------------------------------------------------------------------------
+def test_rows_come_through_a_leading_dimension_and_only_the_destination_rows_change(engine):
+    n, d, m, ld = 300, 64, 37, 72
+    store = _rand(n, d, 1, 0.3)
+    pg = engine.prepare_gallery(store)
+    f32, b16, meta = pg.f32.clone(), pg.bf16.clone(), pg.meta.clone()
+    before = (f32.clone(), b16.clone())
+    new = _rand(m, d, 2, 0.3)
+    src = framed_like(new, ld, NAN, DEV)                   # gap columns and both bands are NaN: a read outside [m, d] poisons the store or meta
+    slots = torch.randperm(n, generator=torch.Generator().manual_seed(3))[:m].to(torch.int32)
+    engine.gallery_upsert(src.view, slots, f32, b16, meta)
+    engine.sync()
+    src.assert_intact("source frame")
+    want = store.clone()
+    want[slots.long()] = new
+    fresh = engine.prepare_gallery(want)
+    assert _same(f32, want) and _same(b16, fresh.bf16)
+    untouched = torch.ones(n, dtype=torch.bool)
+    untouched[slots.long()] = False
+    assert _same(f32[untouched.to(DEV)], before[0][untouched.to(DEV)]) and _same(b16[untouched.to(DEV)], before[1][untouched.to(DEV)])
+    assert torch.isfinite(meta).all() and (meta >= pg.meta).all()
+    lib, h, p = engine.lib, engine._h, lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    sl = slots.to(DEV)
+
+    def call(ld_=ld, d_=d, g=f32, gb=b16, mt=meta):
+        return lib.fern_gallery_upsert(h, src.data_ptr(), ld_, sl.data_ptr(), m, p(g), p(gb), p(mt), n, d_, 0, None)
+    for kw, why in ((dict(ld_=60), b"ld >= D"), (dict(d_=62), b"multiple of 4"), (dict(g=None), b"prepared form"), (dict(gb=None), b"prepared form"),
+                    (dict(g=None, gb=None, mt=None), b"gallery, gallery_bf16 or both")):
+        assert call(**kw) == -1 and b"fern_gallery_upsert" in lib.fern_last_error() and why in lib.fern_last_error(), kw
+    assert lib.fern_gallery_upsert(h, None, ld, None, 0, p(f32), p(b16), p(meta), n, d, 0, None) == 0      # m == 0: nothing to do
+    engine.sync()
+    assert _same(f32, want)
+
+
+# ---- 3. normalize = 1 -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("D", [36, 512, 1280])
+def test_normalize_equals_l2_normalize_followed_by_a_plain_upsert(engine, D):
+    m = 203
+    rows = _rand(m, D, 7 + D) * 10.0 ** (torch.rand(m, 1, generator=torch.Generator().manual_seed(D)) * 6 - 3)
+    rows[5] = 0.0                                          # F.normalize's eps: 0 / max(0, 1e-12) = 0
+    rows[9] = torch.nn.functional.normalize(rows[9], dim=0) * 1e-20      # norm 1e-20 < eps
+    slots = torch.randperm(m, generator=torch.Generator().manual_seed(1)).to(torch.int32)
+    a, b = _zero_store(m, D), _zero_store(m, D)
+    engine.gallery_upsert(rows, slots, *a, normalize=True)
+    unit = engine.l2_normalize(rows)
+    engine.gallery_upsert(unit, slots, *b, normalize=False)
+    engine.sync()
+    for x, y in zip(a, b):
+        assert _same(x, y)
+    assert _same(a[0][slots.long().to(DEV)], unit)
+    assert float(a[0][int(slots[5])].abs().max()) == 0.0 and torch.isfinite(a[0]).all() and torch.isfinite(a[2]).all()
+    norms = a[0].norm(dim=1).cpu()
+    assert abs(float(norms[int(slots[0])]) - 1.0) < 1e-5 and float(norms[int(slots[9])]) < 1e-6
+
+
+# ---- 4. the certificate survives a change that needs it -----------------------------------------------------------------------------------
+def test_folded_norms_keep_the_prefilter_exact_when_long_rows_replace_short_ones():
+    """The store starts as 4 096 unit rows / 64: its norms -- and so the certified margin -- are 64 times too small for what comes next.
+    400 slots are then replaced by unit rows within ~1e-4 of every query (test_rows_inside_the_margin_are_rescored_not_trusted's
+    construction): the bf16 ranking of those is scrambled, and with the OLD meta 135 rows of the exact top-50 lists fall outside the
+    margin (worked out on the CPU), so the result is exact only because the upsert raised meta."""
+    from fashionern_aaai2024_amd.engine import FernEngine
+    from fashionern_aaai2024_amd.live_gallery import LiveGallery
+    d, n, k, near = 512, 4096, 50, 400
+    norm = torch.nn.functional.normalize
+    base = norm(_rand(1, d, 77), dim=-1)
+    q = norm(base + 0.02 * _rand(8, d, 78) * d ** -0.5, dim=-1)
+    g = norm(_rand(n, d, 79), dim=-1) / 64.0
+    rows = torch.randperm(n, generator=torch.Generator().manual_seed(80))[:near]
+    new = norm(base + 0.03 * _rand(near, d, 81) * d ** -0.5, dim=-1)
+    eng = FernEngine(DEV)
+    try:
+        live = LiveGallery(eng, n, d)
+        slots = live.append(g)
+        assert slots.tolist() == list(range(n))
+        meta_before = live.meta.clone()
+        assert _same(meta_before, eng.prepare_gallery(g).meta)
+        live.replace(rows.numpy().astype(np.int32), new)
+        g[rows] = new
+        cs, ci = chain.chain_topk(q.numpy(), g.numpy(), k)
+        approx = (q.bfloat16().float() @ g.bfloat16().float().T).topk(k, dim=1).indices
+        scrambled = sum(set(a.tolist()) != set(b.tolist()) for a, b in zip(approx, torch.from_numpy(ci.astype(np.int64))))
+        assert scrambled >= 6, "the case must be one where the bf16 scores pick the wrong rows"
+        assert live.row_filter() is None                   # nothing withdrawn: the unfiltered fast path
+        for strategy in ("auto", "lists", "dense", "plain"):
+            eng.set_rank_strategy(strategy)
+            s, i = eng.sim_topk(q, live.gallery(), k)
+            assert np.array_equal(i.cpu().numpy(), ci) and np.array_equal(s.cpu().numpy().view(np.uint32), cs.view(np.uint32)), strategy
+        eng.set_rank_strategy("auto")
+        meta_new = eng.prepare_gallery(new).meta
+        assert _same(live.meta, torch.maximum(meta_before, meta_new))
+        assert (live.meta[:3] > 10 * meta_before[:3]).all()      # the change NEEDED the fold: the old bound is far too small
+        # the float64 check of test_prepare_reports_the_norms_that_certify_the_margin, for every live row
+        meta = live.meta.cpu()
+        gb, qb = g.bfloat16().float(), q.bfloat16().float()
+        err = (q.double() @ g.double().T - qb.double() @ gb.double().T).abs()
+        eps = q.double().norm(dim=1) * meta[0].double() + (q - qb).double().norm(dim=1) * meta[1].double()
+        assert (err.max(dim=1).values <= eps).all()
+        old = meta_before.cpu()
+        eps_old = q.double().norm(dim=1) * old[0].double() + (q - qb).double().norm(dim=1) * old[1].double()
+        assert (err.max(dim=1).values > eps_old).all()     # ... which the stale norms do not certify
+        eng.sync()
+    finally:
+        eng.close()
+
+
+# ---- 5. mixed churn equals a fresh store ------------------------------------------------------------------------------------------------
+class _Model:
+    """The host's picture of a store: what a fresh gallery of the same contents is built from."""
+
+    def __init__(self, capacity, d):
+        self.rows = torch.zeros(capacity, d)
+        self.tags = np.zeros(capacity, dtype=np.int64)     # user bits | LIVE
+        self.items = np.zeros(capacity, dtype=np.int32)
+
+    def put(self, slots, rows, tags=None, items=None):
+        s = np.asarray(slots, dtype=np.int64)
+        self.rows[torch.from_numpy(s)] = rows
+        if tags is not None:
+            self.tags[s] = np.asarray(tags, dtype=np.int64) | LIVE
+        if items is not None:
+            self.items[s] = items
+
+    def withdraw(self, slots):
+        self.tags[np.asarray(slots, dtype=np.int64)] &= ~LIVE
+
+
+def _assert_equals_fresh(eng, live, model, q, targets, n_items):
+    """Every ranking entry point on the live store (prefix and full view) against the same call on a fresh prepare_gallery of the
+    model's rows [0, n) under the equivalent filter."""
+    from fashionern_aaai2024_amd.engine import ItemMap, RowFilter
+    n, b = live.n, q.shape[0]
+    fresh = eng.prepare_gallery(model.rows[:n].to(DEV))
+    ftags = torch.from_numpy(model.tags[:n]).to(DEV)
+    fitems = ItemMap(torch.from_numpy(model.items[:n]).to(DEV), n_items)
+    umask, uvalue = torch.full((b,), 3), torch.arange(b) % 3
+    holes = bool(((model.tags[:n] & LIVE) == 0).any())
+    assert (live.row_filter() is None) == (not holes)
+    for user in (False, True):
+        mk, vl = (umask | LIVE, uvalue | LIVE) if user else (LIVE, LIVE)
+        fflt = RowFilter(ftags, mk, vl)
+        want = {
+            "topk": eng.sim_topk(q, fresh, 50, row_filter=fflt),
+            "deep": eng.sim_topk_deep(q, fresh, 200, row_filter=fflt),
+            "rank": (eng.rank_of(q, fresh, targets, row_filter=fflt),),
+            "items": eng.sim_topk_items(q, fresh, fitems, 50, row_filter=fflt),
+        }
+        for full in (False, True):
+            flt = live.row_filter(umask, uvalue, full=full) if user else live.row_filter(full=full)
+            gal, items = live.gallery(full=full), live.item_map(full=full)
+            assert gal.shape[0] == (live.capacity if full else n)
+            got = {
+                "topk": eng.sim_topk(q, gal, 50, row_filter=flt),
+                "deep": eng.sim_topk_deep(q, gal, 200, row_filter=flt),
+                "rank": (eng.rank_of(q, gal, targets, row_filter=flt),),
+                "items": eng.sim_topk_items(q, gal, items, 50, row_filter=flt),
+            }
+            for name in want:
+                for w, g in zip(want[name], got[name]):
+                    assert _same(w, g), (name, user, full)
+    eng.sync()
+    return want
+
+
+def test_mixed_churn_equals_a_fresh_store_of_the_final_contents(engine):
+    from fashionern_aaai2024_amd.live_gallery import LiveGallery
+    d, cap, n_items = 512, 3200, 300
+    r = np.random.default_rng(11)
+    live = LiveGallery(engine, cap, d, items=n_items)
+    model = _Model(cap, d)
+    g0 = _rand(3000, d, 21, d ** -0.5)
+    g0[17] *= 9.0                                          # one long row sets the maxima
+    tags0, items0 = np.arange(3000) % 3, r.integers(0, n_items, 3000).astype(np.int32)
+    for a, b in ((0, 1000), (1000, 2500), (2500, 3000)):   # three chunks
+        slots = live.append(g0[a:b], tags=tags0[a:b], items=items0[a:b])
+        assert slots.tolist() == list(range(a, b))
+        model.put(slots, g0[a:b], tags0[a:b], items0[a:b])
+    assert _same(live.meta, engine.prepare_gallery(g0).meta)
+    q = _rand(9, d, 22)
+    targets = torch.from_numpy(r.integers(0, 3000, (9, 3)).astype(np.int32))
+    rep = r.choice(3000, 257, replace=False).astype(np.int32)
+    rep = rep[rep != 17]
+    new = _rand(rep.size, d, 23, d ** -0.5)
+    live.replace(rep, new)                                 # tags and item ids stay
+    model.put(rep, new)
+    gone = np.sort(r.choice(3000, 50, replace=False)).astype(np.int32)
+    live.withdraw(gone)
+    model.withdraw(gone)
+    targets[0, 0], targets[1, 1] = int(gone[0]), int(gone[7])      # withdrawn targets have no place
+    assert live.n == 3000 and live.n_live == 2950
+    want = _assert_equals_fresh(engine, live, model, q, targets, n_items)
+    assert int(want["rank"][0][0, 0]) == -1 and not np.isin(want["topk"][1].cpu().numpy(), gone).any()
+    with pytest.raises(KeyError):
+        live.replace(gone[:1], new[:1])                    # a withdrawn slot is not live
+    with pytest.raises(ValueError, match="live bit"):
+        live.append(new[:1], tags=[LIVE], items=[0])
+    with pytest.raises(ValueError, match="live bit"):
+        live.row_filter(LIVE, 0)
+    add = _rand(100, d, 24, d ** -0.5)
+    tags1, items1 = np.arange(100) % 3, r.integers(0, n_items, 100).astype(np.int32)
+    slots = live.append(add, tags=tags1, items=items1)
+    assert slots[:50].tolist() == gone.tolist() and slots[50:].tolist() == list(range(3000, 3050))      # the lowest free slots first
+    model.put(slots, add, tags1, items1)
+    assert live.n == 3050 and live.n_live == 3050
+    _assert_equals_fresh(engine, live, model, q, targets, n_items)
+    with pytest.raises(RuntimeError, match="full"):
+        live.append(_rand(151, d, 25), tags=0, items=0)   # 150 slots are free
+    assert live.n == 3050
+    # replacing the longest row by a short one leaves meta as it is (an upper bound); refresh() makes it exact again
+    meta_before = live.meta.clone()
+    short = _rand(1, d, 26, 0.01 * d ** -0.5)
+    live.replace(np.array([17], dtype=np.int32), short)
+    model.put([17], short)
+    assert _same(live.meta, meta_before)
+    exact = engine.prepare_gallery(model.rows[:live.n].to(DEV))
+    assert float(exact.meta[2]) < 0.5 * float(meta_before[2])
+    _assert_equals_fresh(engine, live, model, q, targets, n_items)      # a loose bound costs nothing but rescoring
+    ptrs = (live.gallery().f32.data_ptr(), live.gallery().bf16.data_ptr(), live.meta.data_ptr())
+    live.refresh()
+    assert _same(live.meta, exact.meta) and _same(live.gallery().bf16, exact.bf16)
+    assert ptrs == (live.gallery(full=True).f32.data_ptr(), live.gallery(full=True).bf16.data_ptr(), live.meta.data_ptr())
+
+
+# ---- 6. compact -----------------------------------------------------------------------------------------------------------------------
+def test_compact_moves_the_highest_live_rows_into_the_holes(engine):
+    from fashionern_aaai2024_amd.live_gallery import LiveGallery
+    d, cap, n, n_items = 128, 700, 601, 40
+    r = np.random.default_rng(5)
+    live = LiveGallery(engine, cap, d, items=n_items)
+    model = _Model(cap, d)
+    g = _rand(n, d, 31, d ** -0.5)
+    tags, items = np.arange(n) % 3, r.integers(0, n_items, n).astype(np.int32)
+    model.put(live.append(g, tags=tags, items=items), g, tags, items)
+    gone = r.choice(n, 120, replace=False).astype(np.int32)
+    live.withdraw(gone)
+    model.withdraw(gone)
+    before = {k: getattr(live, k).clone() for k in ("f32", "bf16", "tags", "items")}
+    meta_before = live.meta.clone()
+    src, dst = live.compact()
+    n_live = n - 120
+    assert live.n == n_live and live.n_live == n_live and live.table.live_slots().tolist() == list(range(n_live))
+    assert src.size == dst.size and not set(src.tolist()) & set(dst.tolist()) and (src >= n_live).all() and (dst < n_live).all()
+    assert set(dst.tolist()) == set(gone[gone < n_live].tolist())
+    s, t = torch.from_numpy(src.astype(np.int64)).to(DEV), torch.from_numpy(dst.astype(np.int64)).to(DEV)
+    for k in ("f32", "bf16", "items"):
+        assert _same(getattr(live, k)[t], before[k][s]), k
+        keep = torch.ones(cap, dtype=torch.bool, device=DEV)
+        keep[t] = False
+        assert _same(getattr(live, k)[keep], before[k][keep]), k      # nothing but the destination rows changed
+    assert _same(live.tags[t], before["tags"][s])
+    assert ((live.tags[s] & -(1 << 31)) == 0).all() and _same(live.tags[s] & 0x7FFFFFFF, before["tags"][s] & 0x7FFFFFFF)      # the sources are free
+    assert _same(live.meta, meta_before)
+    assert live.row_filter() is None
+    model.rows[dst.astype(np.int64)] = model.rows[src.astype(np.int64)]
+    model.tags[dst], model.items[dst] = model.tags[src], model.items[src]
+    model.tags[src] &= ~LIVE
+    q = _rand(5, d, 32)
+    targets = torch.from_numpy(r.integers(0, n_live, (5, 2)).astype(np.int32))
+    _assert_equals_fresh(engine, live, model, q, targets, n_items)
+
+
+# ---- 7. slots out of range --------------------------------------------------------------------------------------------------------------
+def test_slots_outside_the_store_write_nothing_and_surface_at_sync():
+    from fashionern_aaai2024_amd._lib import FernError
+    from fashionern_aaai2024_amd.engine import FernEngine
+    eng = FernEngine(DEV)                                  # the flag belongs to the context: keep the session engine's clean
+    try:
+        cap, d = 50, 64
+        pg = eng.prepare_gallery(_rand(cap, d, 41))
+        f32, b16, meta = pg.f32.clone(), pg.bf16.clone(), pg.meta.clone()
+        before = (f32.clone(), b16.clone())
+        rows = _rand(5, d, 42)
+        slots = torch.tensor([3, -1, 7, cap, 9], dtype=torch.int32)
+        eng.gallery_upsert(rows, slots, f32, b16, meta)     # asynchronous: the launch itself succeeds
+        with pytest.raises(FernError, match=r"fern_sync.*fern_gallery_upsert.*position (1|3) "):
+            eng.sync()
+        want = before[0].clone()
+        want[[3, 7, 9]] = rows[[0, 2, 4]].to(DEV)
+        assert _same(f32, want)                            # the valid rows of the call were written, nothing else changed
+        want16 = before[1].clone()
+        want16[[3, 7, 9]] = eng.gallery_to_bf16(rows)[[0, 2, 4]]
+        assert _same(b16, want16)
+        eng.sync()                                         # reported once
+        tags = torch.zeros(cap, dtype=torch.int32, device=DEV)
+        eng.scatter_u32(torch.tensor([5, 6, 7], dtype=torch.int32), torch.tensor([2, cap + 3, 4], dtype=torch.int32), tags)
+        torch.cuda.current_stream().synchronize()
+        with pytest.raises(FernError, match=r"fern_gallery_move.*earlier fern_scatter_u32.*position 1 "):      # ... or at the next call of the three
+            eng.gallery_move(torch.tensor([0], dtype=torch.int32), torch.tensor([1], dtype=torch.int32), f32, b16)
+        assert tags.cpu().tolist()[:6] == [0, 0, 5, 0, 7, 0] and int(tags.abs().sum()) == 12
+        eng.gallery_move(torch.tensor([0, 60], dtype=torch.int32), torch.tensor([1, 2], dtype=torch.int32), f32, b16, tags)
+        with pytest.raises(FernError, match=r"fern_gallery_move.*position 1 "):
+            eng.sync()
+        assert _same(f32[1], f32[0]) and _same(b16[1], b16[0]) and _same(f32[2], want[2])
+        eng.gallery_upsert(rows, torch.tensor([10, 11, 12, 13, 14], dtype=torch.int32), f32, b16, meta)      # the next call works
+        eng.sync()
+        assert _same(f32[10:15], rows.to(DEV))
+    finally:
+        eng.close()
+
+
+# ---- 8. graph stability -----------------------------------------------------------------------------------------------------------------
+def test_a_captured_lane_graph_survives_an_append_to_the_full_view():
+    from fashionern_aaai2024_amd import synth
+    from fashionern_aaai2024_amd.clip_model import create_model
+    from fashionern_aaai2024_amd.live_gallery import LiveGallery
+    from fashionern_aaai2024_amd.model import ERN
+    from fashionern_aaai2024_amd.pipeline import ComposedQueryPipeline
+    cfg = synth.CLIP_CONFIGS["tiny"]
+    d = cfg.embed_dim
+    clip = create_model(cfg, device=DEV, seed=3)
+    model = ERN(clip, d, DEV, engine=clip.engine).init_random(4)
+    e = model.engine
+    n, b, k = 500, 9, 10
+    live = LiveGallery(e, 640, d)
+    fused_index = e.index_fuse(torch.from_numpy(synth.global_feats(n, d, tag="lg")), torch.from_numpy(synth.local_feats(n, d, tag="lgl")), True)
+    live.append(fused_index, normalize=True)               # unit rows: a query's own direction is then its best row by Cauchy-Schwarz
+    im, tk, lc = (torch.from_numpy(synth.images(b, cfg, 400)).cuda(), torch.from_numpy(synth.captions(b, cfg, 400)).cuda(),
+                  torch.from_numpy(synth.local_feats(b, d, 400)).cuda())
+    pipe = ComposedQueryPipeline(e, lanes=1, graphs=True)
+    try:
+        submit = lambda: pipe.submit(im, tk, lc, live.gallery(full=True), k, row_filter=live.row_filter(full=True))      # noqa: E731
+        results = [submit() for _ in range(4)]             # eager, eager, captured + replayed, replayed
+        first = results[0]
+        s0, i0 = first.wait()
+        graphs = {key: lg.graph for key, lg in pipe._lane_graphs[0].items()}
+        assert len(graphs) == 1 and all(g is not None for g in graphs.values())
+        assert int(i0.max()) < n                           # free slots of the full view are not eligible
+        for res in results[1:]:
+            s, i = res.wait()
+            assert _same(s, s0) and _same(i, i0)
+        pipe.fence()                                       # the update below must not overtake a lane still sweeping the store
+        slots = live.append(first.fused, normalize=True)
+        assert slots.tolist() == list(range(n, n + b))
+        s, i = submit().wait()
+        torch.cuda.current_stream().synchronize()
+        assert i[:, 0].cpu().tolist() == slots.tolist()    # every query's top-1 is its own appended slot
+        after = {key: lg.graph for key, lg in pipe._lane_graphs[0].items()}
+        assert list(after) == list(graphs) and all(after[key] is graphs[key] for key in graphs)      # nothing was recaptured
+        # direct calls on the lane's engine come last: they may move its workspace, which drops the lane's graphs by design
+        for rows, (gs, gi) in ((n, (s0, i0)), (n + b, (s, i))):
+            ws, wi = e.sim_topk(first.fused, e.prepare_gallery(live.gallery().f32[:rows].clone()), k)
+            assert _same(gs, ws) and _same(gi, wi), rows
+        e.sync()
+    finally:
+        pipe.close()
+
+
+# ---- 9. incremental harness ---------------------------------------------------------------------------------------------------------------
+def test_incremental_index_gives_the_recalls_and_the_gallery_bytes_of_the_one_shot_build():
+    import synthetic_data as sdata
+    from fashionern_aaai2024_amd import synth
+    from fashionern_aaai2024_amd.model import ERN
+    from fashionern_aaai2024_amd.run import _common, test_fiq
+    from fashionern_aaai2024_amd.tokenizer import register_tokenizer
+    from fashionern_aaai2024_amd.utils import extract_index_features
+    meta = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "harness.json")))
+    register_tokenizer("stub", sdata.stub_tokenizer)
+    d, n = meta["d"], meta["n"]
+    clip = sdata.StubCLIP(d).eval().to(DEV)
+    model = ERN(clip, d, DEV)
+    model.load_state_dict(synth.fusion_state_dict(d, seed=meta["fusion_seed"]))
+    gal = sdata.Gallery(n, d, seed=meta["gallery_seed"])
+    rel = sdata.RelativeDataset(gal, meta["q"], "fiq", seed=meta["relative_seed"])
+    feats, names, local = extract_index_features(sdata.ClassicDataset(gal), clip, 13, DEV, d, num_workers=0)
+    args = (rel, clip, feats, local, names, model, DEV, d, meta["batch_size"], 0, "stub")
+    plain = test_fiq.compute_fiq_val_metrics(*args)
+    with _common.incremental_index(64):
+        grown = test_fiq.compute_fiq_val_metrics(*args)
+        view = _common.fuse_index(model, feats, local, prepared=True)
+    assert tuple(grown) == tuple(plain) and list(plain) == meta["recalls"]["fiq"]
+    assert n % 64 and n > 64                               # several chunks and a ragged last one
+    fused = _common.fuse_index(model, feats, local)
+    fresh = model.engine.prepare_gallery(fused)
+    assert _same(view.f32, fused) and _same(view.bf16, fresh.bf16) and _same(view.meta, fresh.meta)
