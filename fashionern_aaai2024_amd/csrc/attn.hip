@@ -1,14 +1,21 @@
 // fp32 / bf16 MFMA attention: softmax(scale * Q K^T [+causal]) V.  Up to 224 keys K / V stay resident in LDS; longer
-// (non-causal, <= 4096 keys) sequences stream them through LDS in chunks (the key-streaming forms below).
+// (non-causal, <= 4096 keys) sequences stream them through LDS in chunks (the key-streaming kernels below).
 //
 // Replaces nn.MultiheadAttention / HF BertSelfAttention / CLIP attention on the hot path
 // (SURVEY.md 2.2 rows K2-K4): ViT-B/16 (197 tokens, 12 heads x 64), CLIP text (77, causal, 8 x 64),
 // the fusion BERT block (91 tokens, 8 heads x 64 or 80) and the 13 x 13 cross attention.
 //
-// One workgroup = one (batch, head).  K and V of the head live in LDS for the whole workgroup
-// (every sequence on this path fits), each wave owns 32-query tiles:
-//   * keys are walked in 32-key tiles with an online (running max / running sum) softmax, so only one
-//     score tile is live in registers at a time;
+// Every tiled kernel is one of two WALKERS over one of two operand FORMS:
+//   * a form (F32Form, Bf16Form) defines, once, the LDS image of a run of keys, the Q fragment load, the stager and the
+//     key-tile step: one 32-key tile of online (running max / running sum) softmax and P V, so only one score tile is live
+//     in registers at a time;
+//   * the resident walker keeps all keys of a (batch, head) in LDS and gives each wave 32-query tiles in turn (causal allowed);
+//     the chunk walker gives each wave one query tile, stages the keys in chunks and carries (m, sum, O) across them.
+// The five __global__ kernels pick a form, a walker and their constants, nothing else.  Arithmetic per (query, key) is therefore
+// the same code in every kernel of a form, applied to key tiles in ascending order: resident, chunked and streaming results are
+// bit-identical by construction (tests/test_gpu_attention_long.py still checks it).
+//
+// The tile step, fp32 form:
 //   * S^T = K Q^T on v_mfma_f32_32x32x2_f32 with K as the A operand: the accumulator then has the
 //     QUERY on the lane and the KEYS in registers, so the softmax row reduction is lane-local plus
 //     one cross-half shuffle, and
@@ -24,272 +31,117 @@ namespace fern {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef short bf16x8 __attribute__((ext_vector_type(8)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
-template <int HDP, int NT, bool CAUSAL, int NW>
-__global__ __launch_bounds__(NW * 64) void attn_f32_kernel(AttnParams p) {
-    constexpr int KS = HDP + 4;          // K row stride in LDS (floats)
-    constexpr int ROWS = NT * 32;        // padded key count
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Ks = smem;                    // [ROWS][KS]
-    float* Vs = smem + ROWS * KS;        // [ROWS][HDP]
+extern __shared__ __attribute__((aligned(16))) char attn_smem[];      // the K / V image of the form, ROWS padded keys
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int b = blockIdx.x / p.heads, h = blockIdx.x % p.heads;
-    const int hd = p.hd;
+// A lane's place in its wave: query l31 of the tile, half lh of the head dimension / key pairs; tr_off is the bf16 form's
+// transposing-read address inside a [4 keys][32 columns] block: lane 4q+p of a 16-lane group -> row q, columns 4p..4p+3
+struct LanePos { int l31, lh, tr_off; };
+__device__ __forceinline__ LanePos lane_pos() {
+    const int lane = threadIdx.x & 63, lh = lane >> 5;
+    return {lane & 31, lh, ((lane & 15) >> 2) * 64 + (((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2 + lh * 4 * 64};
+}
 
-    // ---- stage K and V of this (batch, head) into LDS, zero padded ----
-    {
+// ---- fp32 operand form -----------------------------------------------------------------------------------------------
+// Image: K [ROWS][HDP + 4] floats, then V [ROWS][HDP] floats.
+template <int HDP_>
+struct F32Form {
+    static constexpr int HDP = HDP_;
+    static constexpr bool BF16 = false;
+    static constexpr int KS = HDP + 4;          // K row stride in LDS (floats)
+    typedef f32x4 Q[HDP / 8];
+    static constexpr size_t image_bytes(int rows) { return (size_t)rows * (KS + HDP) * sizeof(float); }
+
+    // Q fragment (B operand): lane (query, half) holds d = 8*kk + 4*half + e, pre-scaled
+    static __device__ __forceinline__ void load_q(Q& qf, const AttnParams& p, int b, int h, int qrow, int lh, bool active) {
+        const float* qb = p.q + ((long)b * p.s_q + qrow) * p.ldq + (long)h * p.hd;
+#pragma unroll
+        for (int kk = 0; kk < HDP / 8; ++kk) {
+            const int d = kk * 8 + 4 * lh;
+            f32x4 t = {0.f, 0.f, 0.f, 0.f};
+            if (active && d < p.hd) t = *reinterpret_cast<const f32x4*>(qb + d);
+            qf[kk] = t * p.scale;
+        }
+    }
+
+    // keys [key0, key0 + rows) of (b, h) into image rows [0, rows), zero past s_k and past hd
+    template <int ROWS>
+    static __device__ __forceinline__ void stage(const AttnParams& p, int b, int h, int key0, int rows, int tid, int stride) {
         constexpr int C4 = HDP / 4;
-        const float* kb = p.k + (long)b * p.s_k * p.ldk + (long)h * hd;
-        const float* vb = p.v + (long)b * p.s_k * p.ldv + (long)h * hd;
-        for (int i = tid; i < ROWS * C4; i += NW * 64) {
-            const int row = i / C4, c = (i % C4) * 4;
+        float* Ks = reinterpret_cast<float*>(attn_smem);
+        float* Vs = Ks + ROWS * KS;
+        const float* kb = p.k + (long)b * p.s_k * p.ldk + (long)h * p.hd;
+        const float* vb = p.v + (long)b * p.s_k * p.ldv + (long)h * p.hd;
+        for (int i = tid; i < rows * C4; i += stride) {
+            const int row = i / C4, c = (i % C4) * 4, key = key0 + row;
             f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-            if (row < p.s_k && c < hd) {
-                kv = *reinterpret_cast<const f32x4*>(kb + (long)row * p.ldk + c);
-                vv = *reinterpret_cast<const f32x4*>(vb + (long)row * p.ldv + c);
+            if (key < p.s_k && c < p.hd) {
+                kv = *reinterpret_cast<const f32x4*>(kb + (long)key * p.ldk + c);
+                vv = *reinterpret_cast<const f32x4*>(vb + (long)key * p.ldv + c);
             }
             *reinterpret_cast<f32x4*>(&Ks[row * KS + c]) = kv;
             *reinterpret_cast<f32x4*>(&Vs[row * HDP + c]) = vv;
         }
     }
-    __syncthreads();
 
-    const int nqt = (p.s_q + 31) / 32;
-    for (int qt = wave; qt < nqt; qt += NW) {
-        const int qi = qt * 32 + l31;                 // this lane's query
-        const int qrow = qi < p.s_q ? qi : p.s_q - 1;
-        // ---- Q fragment (B operand): lane (query, half) holds d = 8*kk + 4*half + e, pre-scaled ----
-        f32x4 qf[HDP / 8];
-        {
-            const float* qb = p.q + ((long)b * p.s_q + qrow) * p.ldq + (long)h * hd;
+    // key tile t of the image = tile ta of the head: st[r] = score(key 32 ta + (r&3) + 8(r>>2) + 4*half, query qi)
+    template <bool CAUSAL, int ROWS>
+    static __device__ __forceinline__ void key_tile(int t, int ta, int qi, const LanePos& lp, const AttnParams& p, const Q& qf,
+                                                    float& m, float& sum, f32x16 (&o)[HDP / 32]) {
+        const float* Ks = reinterpret_cast<const float*>(attn_smem);
+        const float* Vs = Ks + ROWS * KS;
+        f32x16 st;
 #pragma unroll
-            for (int kk = 0; kk < HDP / 8; ++kk) {
-                const int d = kk * 8 + 4 * lh;
-                f32x4 t = {0.f, 0.f, 0.f, 0.f};
-                if (d < hd) t = *reinterpret_cast<const f32x4*>(qb + d);
-                qf[kk] = t * p.scale;
-            }
-        }
-        // ---- online softmax over 32-key tiles: only one S^T tile is live at a time ----
-        f32x16 o[HDP / 32];
-#pragma unroll
-        for (int db = 0; db < HDP / 32; ++db)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
-        float m = -INFINITY, sum = 0.0f;          // sum: this lane half's partial; halves share m
-        const int nt = CAUSAL ? (qt + 1 < NT ? qt + 1 : NT) : NT;   // causal: later tiles are all in the future
-#pragma unroll 1
-        for (int t = 0; t < nt; ++t) {
-            // S^T tile: st[r] = score(key 32t + (r&3) + 8(r>>2) + 4*half, query)
-            f32x16 st;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[r] = 0.0f;
-#pragma unroll
-            for (int kk = 0; kk < HDP / 8; ++kk) {
-                const f32x4 kf = *reinterpret_cast<const f32x4*>(&Ks[(t * 32 + l31) * KS + kk * 8 + 4 * lh]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    st = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qf[kk][e], st, 0, 0, 0);
-            }
-            float mt = -INFINITY;
-            if (CAUSAL || (t + 1) * 32 > p.s_k) {            // only the last key tile (or a causal one) has keys to mask: wave-uniform
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const bool ok = key < p.s_k && (!CAUSAL || key <= qi);
-                    st[r] = ok ? st[r] : -INFINITY;
-                    mt = fmaxf(mt, st[r]);
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mt = fmaxf(mt, st[r]);
-            }
-            mt = fmaxf(mt, __shfl_xor(mt, 32));
-            const float m_new = fmaxf(m, mt);      // finite from tile 0 on: key 0 is valid for every query
-            const float alpha = __expf(m - m_new);   // exp(-inf) = 0 on the first tile
-            float ps = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float e = __expf(st[r] - m_new);   // masked entries: exp(-inf) = 0
-                st[r] = e;
-                ps += e;
-            }
-            sum = sum * alpha + ps;
-            m = m_new;
-            // O^T = alpha * O^T + V_t^T P_t^T: A = V^T[d][key]; B = the P^T registers as they stand
-#pragma unroll
-            for (int db = 0; db < HDP / 32; ++db) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const float vf = Vs[key * HDP + db * 32 + l31];
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf, st[r], o[db], 0, 0, 0);
-                }
-            }
-        }
-        sum += __shfl_xor(sum, 32);
-        const float inv = 1.0f / sum;
-        // ---- store: lane (query, half) holds d = 32*db + 8*g + 4*half + {0..3} in registers 4g..4g+3 ----
-        if (qi < p.s_q && p.out_b) {
-            unsigned short* ob = p.out_b + ((long)b * p.s_q + qi) * p.ldo + (long)h * hd;
-#pragma unroll
-            for (int db = 0; db < HDP / 32; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = db * 32 + 8 * g + 4 * lh;
-                    if (d < hd) {
-                        ushort4 t;
-                        t.x = f32_to_bf16_bits(o[db][4 * g] * inv); t.y = f32_to_bf16_bits(o[db][4 * g + 1] * inv);
-                        t.z = f32_to_bf16_bits(o[db][4 * g + 2] * inv); t.w = f32_to_bf16_bits(o[db][4 * g + 3] * inv);
-                        *reinterpret_cast<ushort4*>(ob + d) = t;
-                    }
-                }
-        } else if (qi < p.s_q) {
-            float* ob = p.out + ((long)b * p.s_q + qi) * p.ldo + (long)h * hd;
-#pragma unroll
-            for (int db = 0; db < HDP / 32; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = db * 32 + 8 * g + 4 * lh;
-                    if (d < hd) {
-                        f32x4 t = {o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv};
-                        *reinterpret_cast<f32x4*>(ob + d) = t;
-                    }
-                }
-        }
-    }
-}
-
-// ---- key-chunked form (197-token ViT heads) -----------------------------------------------------------------------------
-// The kernel above keeps ALL keys of a head in LDS: 224 padded rows x (68 + 64) floats = 118 KB, so one workgroup fills a CU
-// (160 KB) and its phases -- staging (memory), S^T and P V (MFMA), softmax (VALU) -- run back to back with nothing beside them:
-// the phases of the 197 x 197 x 64 shape add up (32 + 42 + 34 + 13 us measured with parts switched off), and while an attention
-// workgroup is resident only one 32 KB GEMM workgroup of another stream fits next to it.  Here the keys are staged in KH chunks of
-// CT 32-key tiles (4 + 3 tiles for 197 keys: 68 KB), the online softmax simply carries (m, sum, O) across the chunk boundary, and
-// TWO workgroups (or one and two GEMM workgroups) share a CU: one's staging overlaps the other's MFMAs, four waves per SIMD cover
-// each other's softmax.  Each wave owns at most one 32-query tile (launch condition: s_q <= 32 NW).  Arithmetic per (query, key)
-// is the kernel above's, in the same order: bit-identical results.
-template <int HDP, int NT, int NW, int KH>
-__global__ __launch_bounds__(NW * 64, 2) void attn_f32_chunked_kernel(AttnParams p) {
-    constexpr int KS = HDP + 4;
-    constexpr int CT = (NT + KH - 1) / KH;      // key tiles per chunk
-    constexpr int ROWS = CT * 32;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Ks = smem;                    // [ROWS][KS]
-    float* Vs = smem + ROWS * KS;        // [ROWS][HDP]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int b = blockIdx.x / p.heads, h = blockIdx.x % p.heads;
-    const int hd = p.hd;
-    const bool active = wave * 32 < p.s_q;
-    const int qi = wave * 32 + l31;
-    const int qrow = qi < p.s_q ? qi : p.s_q - 1;
-    f32x4 qf[HDP / 8];
-    {
-        const float* qb = p.q + ((long)b * p.s_q + qrow) * p.ldq + (long)h * hd;
+        for (int r = 0; r < 16; ++r) st[r] = 0.0f;
 #pragma unroll
         for (int kk = 0; kk < HDP / 8; ++kk) {
-            const int d = kk * 8 + 4 * lh;
-            f32x4 t = {0.f, 0.f, 0.f, 0.f};
-            if (active && d < hd) t = *reinterpret_cast<const f32x4*>(qb + d);
-            qf[kk] = t * p.scale;
+            const f32x4 kf = *reinterpret_cast<const f32x4*>(&Ks[(t * 32 + lp.l31) * KS + kk * 8 + 4 * lp.lh]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                st = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qf[kk][e], st, 0, 0, 0);
         }
-    }
-    f32x16 o[HDP / 32];
-#pragma unroll
-    for (int db = 0; db < HDP / 32; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
-    float m = -INFINITY, sum = 0.0f;
-    const float* kb = p.k + (long)b * p.s_k * p.ldk + (long)h * hd;
-    const float* vb = p.v + (long)b * p.s_k * p.ldv + (long)h * hd;
-#pragma unroll 1
-    for (int c = 0; c < KH; ++c) {
-        if (c) __syncthreads();                                      // every wave is done with the previous chunk
-        {
-            constexpr int C4 = HDP / 4;
-            for (int i = tid; i < ROWS * C4; i += NW * 64) {
-                const int row = i / C4, cc = (i % C4) * 4, key = c * ROWS + row;
-                f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-                if (key < p.s_k && cc < hd) {
-                    kv = *reinterpret_cast<const f32x4*>(kb + (long)key * p.ldk + cc);
-                    vv = *reinterpret_cast<const f32x4*>(vb + (long)key * p.ldv + cc);
-                }
-                *reinterpret_cast<f32x4*>(&Ks[row * KS + cc]) = kv;
-                *reinterpret_cast<f32x4*>(&Vs[row * HDP + cc]) = vv;
-            }
-        }
-        __syncthreads();
-        if (!active) continue;
-        const int nt = (c + 1) * CT <= NT ? CT : NT - c * CT;
-#pragma unroll 1
-        for (int t = 0; t < nt; ++t) {
-            f32x16 st;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[r] = 0.0f;
-#pragma unroll
-            for (int kk = 0; kk < HDP / 8; ++kk) {
-                const f32x4 kf = *reinterpret_cast<const f32x4*>(&Ks[(t * 32 + l31) * KS + kk * 8 + 4 * lh]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    st = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qf[kk][e], st, 0, 0, 0);
-            }
-            float mt = -INFINITY;
-            if ((c * CT + t + 1) * 32 > p.s_k) {             // only the last key tile has keys to mask: wave-uniform
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = (c * CT + t) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    st[r] = key < p.s_k ? st[r] : -INFINITY;
-                    mt = fmaxf(mt, st[r]);
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mt = fmaxf(mt, st[r]);
-            }
-            mt = fmaxf(mt, __shfl_xor(mt, 32));
-            const float m_new = fmaxf(m, mt);
-            const float alpha = __expf(m - m_new);
-            float ps = 0.0f;
+        float mt = -INFINITY;
+        if (CAUSAL || (ta + 1) * 32 > p.s_k) {            // only the last key tile (or a causal one) has keys to mask: wave-uniform
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float e = __expf(st[r] - m_new);
-                st[r] = e;
-                ps += e;
+                const int key = ta * 32 + (r & 3) + 8 * (r >> 2) + 4 * lp.lh;
+                const bool ok = key < p.s_k && (!CAUSAL || key <= qi);
+                st[r] = ok ? st[r] : -INFINITY;
+                mt = fmaxf(mt, st[r]);
             }
-            sum = sum * alpha + ps;
-            m = m_new;
+        } else {
 #pragma unroll
-            for (int db = 0; db < HDP / 32; ++db) {
+            for (int r = 0; r < 16; ++r) mt = fmaxf(mt, st[r]);
+        }
+        mt = fmaxf(mt, __shfl_xor(mt, 32));
+        const float m_new = fmaxf(m, mt);      // finite from tile 0 on: key 0 is valid for every query
+        const float alpha = __expf(m - m_new);   // exp(-inf) = 0 on the first tile
+        float ps = 0.0f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
+        for (int r = 0; r < 16; ++r) {
+            const float e = __expf(st[r] - m_new);   // masked entries: exp(-inf) = 0
+            st[r] = e;
+            ps += e;
+        }
+        sum = sum * alpha + ps;                  // sum: this lane half's partial; halves share m
+        m = m_new;
+        // O^T = alpha * O^T + V_t^T P_t^T: A = V^T[d][key]; B = the P^T registers as they stand
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const float vf = Vs[row * HDP + db * 32 + l31];
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf, st[r], o[db], 0, 0, 0);
-                }
+        for (int db = 0; db < HDP / 32; ++db) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lp.lh;
+                const float vf = Vs[row * HDP + db * 32 + lp.l31];
+                o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf, st[r], o[db], 0, 0, 0);
             }
         }
     }
-    if (!active || qi >= p.s_q) return;
-    sum += __shfl_xor(sum, 32);
-    const float inv = 1.0f / sum;
-    float* ob = p.out + ((long)b * p.s_q + qi) * p.ldo + (long)h * hd;
-#pragma unroll
-    for (int db = 0; db < HDP / 32; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = db * 32 + 8 * g + 4 * lh;
-            if (d < hd) {
-                f32x4 t = {o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv};
-                *reinterpret_cast<f32x4*>(ob + d) = t;
-            }
-        }
-}
+};
 
 // ---- bf16 operand form ---------------------------------------------------------------------------------------------
 // Same structure on v_mfma_f32_32x32x16_bf16 (perf mode of the CLIP towers): S^T = K Q^T with K as the A operand, so the
@@ -297,180 +149,281 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_f32_chunked_kernel(AttnParams
 // of k-step s of O^T = V^T P^T -- with the k order permuted: element j of lane half h is key 16s + 8(j>>2) + 4h + (j&3).
 // The matching V^T fragment (d on the lane, those 8 keys in the elements) comes from two ds_read_b64_tr_b16 transposing
 // reads of the row-major V image.  K image: rows padded to HDP*2+16 bytes (conflict-free ds_read_b128); V image:
-// [HDP/32][key][32 columns] with 64-byte rows (the 4 x 64-byte block one half-wave transposes covers all 64 banks once).
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
+// [HDP/32][ROWS keys][32 columns] with 64-byte rows (the 4 x 64-byte block one half-wave transposes covers all 64 banks once).
+// Q is not scaled: the scores are, after the MFMA.
+template <int HDP_>
+struct Bf16Form {
+    static constexpr int HDP = HDP_;
+    static constexpr bool BF16 = true;
+    static constexpr int KSB = HDP * 2 + 16;    // K row stride in LDS (bytes)
+    typedef bf16x8 Q[HDP / 16];
+    static constexpr size_t image_bytes(int rows) { return (size_t)rows * (KSB + HDP * 2); }
 
-template <int HDP, int NT, bool CAUSAL, int NW>
-__global__ __launch_bounds__(NW * 64) void attn_bf16_kernel(AttnParams p) {
-    constexpr int KSB = HDP * 2 + 16;    // K row stride in LDS (bytes)
-    constexpr int ROWS = NT * 32;        // padded key count
-    extern __shared__ __attribute__((aligned(16))) char smem_b[];
-    char* Ks = smem_b;                   // [ROWS][KSB]
-    char* Vs = smem_b + ROWS * KSB;      // [HDP/32][ROWS][64 B]
+    static __device__ __forceinline__ void load_q(Q& qf, const AttnParams& p, int b, int h, int qrow, int lh, bool active) {
+        const unsigned short* qb = p.qb + ((long)b * p.s_q + qrow) * p.ldq + (long)h * p.hd;
+#pragma unroll
+        for (int kk = 0; kk < HDP / 16; ++kk) {
+            const int d = kk * 16 + 8 * lh;
+            bf16x8 t = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (active && d < p.hd) t = *reinterpret_cast<const bf16x8*>(qb + d);
+            qf[kk] = t;
+        }
+    }
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int b = blockIdx.x / p.heads, h = blockIdx.x % p.heads;
-    const int hd = p.hd;
-
-    {
-        constexpr int C8 = HDP / 8;      // 16-byte chunks per row
-        const unsigned short* kb = p.kb + (long)b * p.s_k * p.ldk + (long)h * hd;
-        const unsigned short* vb = p.vb + (long)b * p.s_k * p.ldv + (long)h * hd;
-        for (int i = tid; i < ROWS * C8; i += NW * 64) {
-            const int row = i / C8, c = i % C8;
+    template <int ROWS>
+    static __device__ __forceinline__ void stage(const AttnParams& p, int b, int h, int key0, int rows, int tid, int stride) {
+        constexpr int C8 = HDP / 8;      // 16-byte pieces per row
+        char* Ks = attn_smem;
+        char* Vs = attn_smem + ROWS * KSB;
+        const unsigned short* kb = p.kb + (long)b * p.s_k * p.ldk + (long)h * p.hd;
+        const unsigned short* vb = p.vb + (long)b * p.s_k * p.ldv + (long)h * p.hd;
+        for (int i = tid; i < rows * C8; i += stride) {
+            const int row = i / C8, c = i % C8, key = key0 + row;
             bf16x8 kv = {0, 0, 0, 0, 0, 0, 0, 0}, vv = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (row < p.s_k && c * 8 < hd) {
-                kv = *reinterpret_cast<const bf16x8*>(kb + (long)row * p.ldk + c * 8);
-                vv = *reinterpret_cast<const bf16x8*>(vb + (long)row * p.ldv + c * 8);
+            if (key < p.s_k && c * 8 < p.hd) {
+                kv = *reinterpret_cast<const bf16x8*>(kb + (long)key * p.ldk + c * 8);
+                vv = *reinterpret_cast<const bf16x8*>(vb + (long)key * p.ldv + c * 8);
             }
             *reinterpret_cast<bf16x8*>(Ks + row * KSB + c * 16) = kv;
             *reinterpret_cast<bf16x8*>(Vs + ((c >> 2) * ROWS + row) * 64 + (c & 3) * 16) = vv;
         }
     }
-    __syncthreads();
 
-    // transposing-read lane address inside a [4 keys][32 columns] block: lane 4q+p of a 16-lane group -> row q, columns 4p..4p+3
-    const int tr_off = ((lane & 15) >> 2) * 64 + (((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2 + lh * 4 * 64;
-
-    const int nqt = (p.s_q + 31) / 32;
-    for (int qt = wave; qt < nqt; qt += NW) {
-        const int qi = qt * 32 + l31;
-        const int qrow = qi < p.s_q ? qi : p.s_q - 1;
-        bf16x8 qf[HDP / 16];
+    template <bool CAUSAL, int ROWS>
+    static __device__ __forceinline__ void key_tile(int t, int ta, int qi, const LanePos& lp, const AttnParams& p, const Q& qf,
+                                                    float& m, float& sum, f32x16 (&o)[HDP / 32]) {
+        const char* Ks = attn_smem;
+        const char* Vs = attn_smem + ROWS * KSB;
+        f32x16 st;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[r] = 0.0f;
+#pragma unroll
+        for (int kk = 0; kk < HDP / 16; ++kk) {
+            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + (t * 32 + lp.l31) * KSB + (kk * 16 + 8 * lp.lh) * 2);
+            st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], st, 0, 0, 0);
+        }
+        float mt = -INFINITY;
+        if (CAUSAL || (ta + 1) * 32 > p.s_k) {            // only the last key tile (or a causal one) has keys to mask: wave-uniform
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = ta * 32 + (r & 3) + 8 * (r >> 2) + 4 * lp.lh;
+                const bool ok = key < p.s_k && (!CAUSAL || key <= qi);
+                st[r] = ok ? st[r] * p.scale : -INFINITY;
+                mt = fmaxf(mt, st[r]);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                st[r] *= p.scale;
+                mt = fmaxf(mt, st[r]);
+            }
+        }
+        mt = fmaxf(mt, __shfl_xor(mt, 32));
+        const float m_new = fmaxf(m, mt);
+        const float alpha = __expf(m - m_new);
+        float ps = 0.0f;
+        bf16x8 pf[2];
         {
-            const unsigned short* qb = p.qb + ((long)b * p.s_q + qrow) * p.ldq + (long)h * hd;
+            unsigned pw[8];
 #pragma unroll
-            for (int kk = 0; kk < HDP / 16; ++kk) {
-                const int d = kk * 16 + 8 * lh;
-                bf16x8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-                if (d < hd) t = *reinterpret_cast<const bf16x8*>(qb + d);
-                qf[kk] = t;
+            for (int r = 0; r < 16; r += 2) {
+                const float e0 = __expf(st[r] - m_new), e1 = __expf(st[r + 1] - m_new);
+                ps += e0;                              // the normaliser sums the un-rounded weights (same order as one by one)
+                ps += e1;
+                pw[r >> 1] = f32x2_to_bf16x2_bits(e0, e1);
+            }
+            pf[0] = __builtin_bit_cast(bf16x8, u32x4_t{pw[0], pw[1], pw[2], pw[3]});
+            pf[1] = __builtin_bit_cast(bf16x8, u32x4_t{pw[4], pw[5], pw[6], pw[7]});
+        }
+        sum = sum * alpha + ps;
+        m = m_new;
+#pragma unroll
+        for (int db = 0; db < HDP / 32; ++db) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const char* vblk = Vs + (db * ROWS + t * 32 + 16 * s) * 64 + lp.tr_off;
+                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vblk));
+                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vblk + 8 * 64));
+                const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[s], o[db], 0, 0, 0);
             }
         }
-        f32x16 o[HDP / 32];
+    }
+};
+
+// ---- stores: lane (query, half) holds d = 32*db + 8*g + 4*half + {0..3} in registers 4g..4g+3 of o[db] ----------------------
+template <int NB>
+__device__ __forceinline__ void store_f32(const f32x16 (&o)[NB], float inv, int b, int h, int qi, int lh, const AttnParams& p) {
+    if (qi >= p.s_q) return;
+    float* ob = p.out + ((long)b * p.s_q + qi) * p.ldo + (long)h * p.hd;
 #pragma unroll
-        for (int db = 0; db < HDP / 32; ++db)
+    for (int db = 0; db < NB; ++db)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
-        float m = -INFINITY, sum = 0.0f;
-        const int nt = CAUSAL ? (qt + 1 < NT ? qt + 1 : NT) : NT;
-#pragma unroll 1
-        for (int t = 0; t < nt; ++t) {
-            f32x16 st;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[r] = 0.0f;
-#pragma unroll
-            for (int kk = 0; kk < HDP / 16; ++kk) {
-                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + (t * 32 + l31) * KSB + (kk * 16 + 8 * lh) * 2);
-                st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], st, 0, 0, 0);
-            }
-            float mt = -INFINITY;
-            if (CAUSAL || (t + 1) * 32 > p.s_k) {            // only the last key tile (or a causal one) has keys to mask: wave-uniform
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const bool ok = key < p.s_k && (!CAUSAL || key <= qi);
-                    st[r] = ok ? st[r] * p.scale : -INFINITY;
-                    mt = fmaxf(mt, st[r]);
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    st[r] *= p.scale;
-                    mt = fmaxf(mt, st[r]);
-                }
-            }
-            mt = fmaxf(mt, __shfl_xor(mt, 32));
-            const float m_new = fmaxf(m, mt);
-            const float alpha = __expf(m - m_new);
-            float ps = 0.0f;
-            bf16x8 pf[2];
-            {
-                unsigned pw[8];
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const float e0 = __expf(st[r] - m_new), e1 = __expf(st[r + 1] - m_new);
-                    ps += e0;                              // the normaliser sums the un-rounded weights (same order as one by one)
-                    ps += e1;
-                    pw[r >> 1] = f32x2_to_bf16x2_bits(e0, e1);
-                }
-                typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-                pf[0] = __builtin_bit_cast(bf16x8, u32x4_t{pw[0], pw[1], pw[2], pw[3]});
-                pf[1] = __builtin_bit_cast(bf16x8, u32x4_t{pw[4], pw[5], pw[6], pw[7]});
-            }
-            sum = sum * alpha + ps;
-            m = m_new;
-#pragma unroll
-            for (int db = 0; db < HDP / 32; ++db) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const char* vblk = Vs + (db * ROWS + t * 32 + 16 * s) * 64 + tr_off;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vblk));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vblk + 8 * 64));
-                    const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[s], o[db], 0, 0, 0);
-                }
+        for (int g = 0; g < 4; ++g) {
+            const int d = db * 32 + 8 * g + 4 * lh;
+            if (d < p.hd) {
+                f32x4 t = {o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv};
+                *reinterpret_cast<f32x4*>(ob + d) = t;
             }
         }
-        sum += __shfl_xor(sum, 32);
-        const float inv = 1.0f / sum;
-        if (p.out_q8) {
-            // block-scaled fp8 output (the out-projection's MX operand): the two lanes of a query (halves 0 / 1) hold the 32 values
-            // of a d block between them -- block maximum, E8M0 byte, 16 e4m3fn bytes per lane (hd % 32 == 0 on this path)
-            const long orow = (long)b * p.s_q + qi;
+}
+
+template <int NB>
+__device__ __forceinline__ void store_bf16(const f32x16 (&o)[NB], float inv, int b, int h, int qi, int lh, const AttnParams& p) {
+    if (qi >= p.s_q) return;
+    unsigned short* ob = p.out_b + ((long)b * p.s_q + qi) * p.ldo + (long)h * p.hd;
 #pragma unroll
-            for (int db = 0; db < HDP / 32; ++db) {
-                float am = 0.f;
+    for (int db = 0; db < NB; ++db)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) am = fmaxf(am, fabsf(o[db][r] * inv));
-                am = fmaxf(am, __shfl_xor(am, 32));
-                const unsigned e8 = mx_scale_byte(am);
-                const float qs = mx_inv_scale(e8);
-                if (qi < p.s_q && db * 32 < hd) {
-                    unsigned char* o8 = p.out_q8 + orow * p.ldo + (long)h * hd + db * 32 + 4 * lh;
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        *reinterpret_cast<unsigned*>(o8 + 8 * g) = pack4_fp8(o[db][4 * g] * inv * qs, o[db][4 * g + 1] * inv * qs,
-                                                                             o[db][4 * g + 2] * inv * qs, o[db][4 * g + 3] * inv * qs);
-                    if (lh == 0) p.out_scales[mx_scale_offset(orow, (h * hd + db * 32) >> 5, p.out_srows)] = (unsigned char)e8;
-                }
+        for (int g = 0; g < 4; ++g) {
+            const int d = db * 32 + 8 * g + 4 * lh;
+            if (d < p.hd) {
+                ushort4 t;
+                t.x = f32_to_bf16_bits(o[db][4 * g] * inv); t.y = f32_to_bf16_bits(o[db][4 * g + 1] * inv);
+                t.z = f32_to_bf16_bits(o[db][4 * g + 2] * inv); t.w = f32_to_bf16_bits(o[db][4 * g + 3] * inv);
+                *reinterpret_cast<ushort4*>(ob + d) = t;
             }
-        } else if (qi < p.s_q) {
-            unsigned short* ob = p.out_b + ((long)b * p.s_q + qi) * p.ldo + (long)h * hd;
+        }
+}
+
+// block-scaled fp8 output (the out-projection's MX operand): the two lanes of a query (halves 0 / 1) hold the 32 values of a d block
+// between them -- block maximum, E8M0 byte, 16 e4m3fn bytes per lane (hd % 32 == 0 on this path).  Both lanes reach the shuffle,
+// whatever qi is: the bounds test comes after it.
+template <int NB>
+__device__ __forceinline__ void store_mx(const f32x16 (&o)[NB], float inv, int b, int h, int qi, int lh, const AttnParams& p) {
+    const long orow = (long)b * p.s_q + qi;
 #pragma unroll
-            for (int db = 0; db < HDP / 32; ++db)
+    for (int db = 0; db < NB; ++db) {
+        float am = 0.f;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int d = db * 32 + 8 * g + 4 * lh;
-                    if (d < hd) {
-                        ushort4 tt;
-                        tt.x = f32_to_bf16_bits(o[db][4 * g] * inv); tt.y = f32_to_bf16_bits(o[db][4 * g + 1] * inv);
-                        tt.z = f32_to_bf16_bits(o[db][4 * g + 2] * inv); tt.w = f32_to_bf16_bits(o[db][4 * g + 3] * inv);
-                        *reinterpret_cast<ushort4*>(ob + d) = tt;
-                    }
-                }
+        for (int r = 0; r < 16; ++r) am = fmaxf(am, fabsf(o[db][r] * inv));
+        am = fmaxf(am, __shfl_xor(am, 32));
+        const unsigned e8 = mx_scale_byte(am);
+        const float qs = mx_inv_scale(e8);
+        if (qi < p.s_q && db * 32 < p.hd) {
+            unsigned char* o8 = p.out_q8 + orow * p.ldo + (long)h * p.hd + db * 32 + 4 * lh;
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                *reinterpret_cast<unsigned*>(o8 + 8 * g) = pack4_fp8(o[db][4 * g] * inv * qs, o[db][4 * g + 1] * inv * qs,
+                                                                     o[db][4 * g + 2] * inv * qs, o[db][4 * g + 3] * inv * qs);
+            if (lh == 0) p.out_scales[mx_scale_offset(orow, (h * p.hd + db * 32) >> 5, p.out_srows)] = (unsigned char)e8;
         }
     }
 }
 
-// ---- key-streaming forms (any key count: ViT-L/14 has 257 tokens, 577 at 336 px) ----------------------------------------------
-// The kernels above keep every key of a head in LDS, which ends at 7 key tiles.  Here K / V are STAGED in chunks of STREAM_CT 32-key tiles
-// (fp32: 68 KB at head_dim 64, bf16: 35 KB -- sized so that two workgroups fit a CU by LDS and registers, the intent being that one's
-// staging overlaps the other's MFMAs; DESIGN.md 4 has what was measured) and the online
-// softmax carries (m, sum, O) across the chunk boundary, as attn_f32_chunked_kernel does for its two chunks.  One workgroup = one
-// (batch, head, GROUP of query tiles); each wave owns one 32-query tile, so a head's K / V are staged once per group.  Groups are
-// balanced: ceil(nqt / 8) groups whose sizes differ by at most one (9 query tiles = 5 + 4, 19 = 7 + 6 + 6).  s_q and s_k are independent.
-// Arithmetic per (query, key) is the resident kernels', in the same order -- key tiles ascending, the last tile masked, the same alpha
-// rescale, bf16 rounding points and final cross-half sum -- so the results are bit-identical to theirs on the shapes both take
-// (the resident kernels' all-padding tiles contribute alpha = 1, weights 0: nothing).
+// the form's outputs: fp32 operands store fp32; bf16 operands store bf16 or, when out_q8 is set, e4m3fn + E8M0 scales
+template <class F>
+__device__ __forceinline__ void store_out(const f32x16 (&o)[F::HDP / 32], float inv, int b, int h, int qi, int lh, const AttnParams& p) {
+    if constexpr (!F::BF16) store_f32(o, inv, b, h, qi, lh, p);
+    else if (p.out_q8) store_mx(o, inv, b, h, qi, lh, p);
+    else store_bf16(o, inv, b, h, qi, lh, p);
+}
+
+template <int NB>
+__device__ __forceinline__ void zero_acc(f32x16 (&o)[NB]) {
+#pragma unroll
+    for (int db = 0; db < NB; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
+}
+
+// ---- resident walker -----------------------------------------------------------------------------------------------
+// One workgroup = one (batch, head).  K and V of the head live in LDS for the whole workgroup (NT key tiles), each of the NW waves
+// owns 32-query tiles qt = wave, wave + NW, ...
+template <class F, int NT, bool CAUSAL, int NW>
+__device__ __forceinline__ void resident_walk(const AttnParams& p) {
+    constexpr int ROWS = NT * 32;        // padded key count
+    const int wave = threadIdx.x >> 6;
+    const int b = blockIdx.x / p.heads, h = blockIdx.x % p.heads;
+    F::template stage<ROWS>(p, b, h, 0, ROWS, threadIdx.x, NW * 64);
+    __syncthreads();
+    const LanePos lp = lane_pos();
+
+    const int nqt = (p.s_q + 31) / 32;
+    for (int qt = wave; qt < nqt; qt += NW) {
+        const int qi = qt * 32 + lp.l31;                 // this lane's query
+        typename F::Q qf;
+        F::load_q(qf, p, b, h, qi < p.s_q ? qi : p.s_q - 1, lp.lh, true);
+        f32x16 o[F::HDP / 32];
+        zero_acc(o);
+        float m = -INFINITY, sum = 0.0f;
+        const int nt = CAUSAL ? (qt + 1 < NT ? qt + 1 : NT) : NT;   // causal: later tiles are all in the future
+#pragma unroll 1
+        for (int t = 0; t < nt; ++t) F::template key_tile<CAUSAL, ROWS>(t, t, qi, lp, p, qf, m, sum, o);
+        sum += __shfl_xor(sum, 32);
+        store_out<F>(o, 1.0f / sum, b, h, qi, lp.lh, p);
+    }
+}
+
+// ---- chunk walker --------------------------------------------------------------------------------------------------
+// One workgroup = one (batch, head, GROUP of query tiles): wave w owns query tile sg.qt0 + w (waves beyond sg.gn only help
+// staging), so a head's K / V are staged once per group.  The nkt key tiles are staged in chunks of CT tiles, `stride` threads
+// copying; the online softmax simply carries (m, sum, O) across the chunk boundary.  whole_image: stage all CT tiles of every
+// chunk (zero rows past s_k), not only the tiles the chunk has.  Non-causal; s_q and s_k are independent.
+struct StreamGroup { int bh, qt0, gn; };
+
+template <class F, int CT>
+__device__ __forceinline__ void chunk_walk(const AttnParams& p, const StreamGroup sg, const int nkt, const int stride, const bool whole_image) {
+    constexpr int ROWS = CT * 32;
+    const LanePos lp = lane_pos();
+    const int wave = threadIdx.x >> 6;
+    const int b = sg.bh / p.heads, h = sg.bh % p.heads;
+    const bool active = wave < sg.gn;
+    const int qi = (sg.qt0 + (active ? wave : 0)) * 32 + lp.l31;
+    typename F::Q qf;
+    F::load_q(qf, p, b, h, qi < p.s_q ? qi : p.s_q - 1, lp.lh, active);
+    f32x16 o[F::HDP / 32];
+    zero_acc(o);
+    float m = -INFINITY, sum = 0.0f;
+#pragma unroll 1
+    for (int t0 = 0; t0 < nkt; t0 += CT) {
+        const int nt = nkt - t0 < CT ? nkt - t0 : CT;
+        if (t0) __syncthreads();                                     // every wave is done with the previous chunk
+        F::template stage<ROWS>(p, b, h, t0 * 32, whole_image ? ROWS : nt * 32, threadIdx.x, stride);
+        __syncthreads();                                             // (outside anything predicated on `active`)
+        if (!active) continue;
+#pragma unroll 1
+        for (int t = 0; t < nt; ++t) F::template key_tile<false, ROWS>(t, t0 + t, qi, lp, p, qf, m, sum, o);
+    }
+    if (!active) return;                                             // whole waves: both lanes of a query stay together
+    sum += __shfl_xor(sum, 32);
+    store_out<F>(o, 1.0f / sum, b, h, qi, lp.lh, p);
+}
+
+// ---- the kernels ---------------------------------------------------------------------------------------------------
+template <int HDP, int NT, bool CAUSAL, int NW>
+__global__ __launch_bounds__(NW * 64) void attn_f32_kernel(AttnParams p) {
+    resident_walk<F32Form<HDP>, NT, CAUSAL, NW>(p);
+}
+
+template <int HDP, int NT, bool CAUSAL, int NW>
+__global__ __launch_bounds__(NW * 64) void attn_bf16_kernel(AttnParams p) {
+    resident_walk<Bf16Form<HDP>, NT, CAUSAL, NW>(p);
+}
+
+// Key-chunked form (197-token ViT heads).  attn_f32_kernel keeps ALL keys of a head in LDS: 224 padded rows x (68 + 64) floats =
+// 118 KB, so one workgroup fills a CU (160 KB) and its phases -- staging (memory), S^T and P V (MFMA), softmax (VALU) -- run back
+// to back with nothing beside them: the phases of the 197 x 197 x 64 shape add up (32 + 42 + 34 + 13 us measured with parts
+// switched off), and while an attention workgroup is resident only one 32 KB GEMM workgroup of another stream fits next to it.
+// Here the NT key tiles are staged in KH chunks (4 + 3 tiles for 197 keys: 68 KB) and TWO workgroups (or one and two GEMM
+// workgroups) share a CU: one's staging overlaps the other's MFMAs, four waves per SIMD cover each other's softmax.  One group
+// per head: each wave owns at most one 32-query tile (launch condition: s_q <= 32 NW).
+template <int HDP, int NT, int NW, int KH>
+__global__ __launch_bounds__(NW * 64, 2) void attn_f32_chunked_kernel(AttnParams p) {
+    chunk_walk<F32Form<HDP>, (NT + KH - 1) / KH>(p, StreamGroup{(int)blockIdx.x, 0, (p.s_q + 31) / 32}, NT, NW * 64, true);
+}
+
+// Key-streaming forms (any key count: ViT-L/14 has 257 tokens, 577 at 336 px).  The resident kernels end at 7 key tiles; here
+// K / V are staged in chunks of STREAM_CT 32-key tiles (fp32: 68 KB at head_dim 64, bf16: 35 KB -- sized so that two workgroups
+// fit a CU by LDS and registers, the intent being that one's staging overlaps the other's MFMAs; DESIGN.md 4 has what was
+// measured).  Groups are balanced: ceil(nqt / 8) groups whose sizes differ by at most one (9 query tiles = 5 + 4, 19 = 7 + 6 + 6).
+// On the shapes both take, the results equal the resident kernels' bit for bit: the same tile step on the same tiles in the same
+// order (the resident kernels' all-padding tiles contribute alpha = 1, weights 0: nothing).
 constexpr int STREAM_CT = 4;           // key tiles per staged chunk
 constexpr int STREAM_MAX_WAVES = 8;    // query tiles per group at most
 
-struct StreamGroup { int bh, qt0, gn; };
 __device__ __forceinline__ StreamGroup stream_group(int s_q) {
     const int nqt = (s_q + 31) / 32, ng = (nqt + STREAM_MAX_WAVES - 1) / STREAM_MAX_WAVES;
     const int base = nqt / ng, rem = nqt % ng, grp = blockIdx.x % ng;
@@ -480,410 +433,82 @@ __device__ __forceinline__ StreamGroup stream_group(int s_q) {
 // (second launch bound = minimum waves per SIMD: 4 = two 8-wave workgroups per CU where the chunk's LDS allows two, head_dim <= 64)
 template <int HDP>
 __global__ __launch_bounds__(STREAM_MAX_WAVES * 64, HDP <= 64 ? 4 : 2) void attn_f32_stream_kernel(AttnParams p) {
-    constexpr int KS = HDP + 4;
-    constexpr int ROWS = STREAM_CT * 32;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* Ks = smem;                    // [ROWS][KS]
-    float* Vs = smem + ROWS * KS;        // [ROWS][HDP]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const StreamGroup sg = stream_group(p.s_q);
-    const int b = sg.bh / p.heads, h = sg.bh % p.heads;
-    const int hd = p.hd;
-    const bool active = wave < sg.gn;                     // waves beyond the group's tiles only help staging
-    const int qi = (sg.qt0 + (active ? wave : 0)) * 32 + l31;
-    const int qrow = qi < p.s_q ? qi : p.s_q - 1;
-    f32x4 qf[HDP / 8];
-    {
-        const float* qb = p.q + ((long)b * p.s_q + qrow) * p.ldq + (long)h * hd;
-#pragma unroll
-        for (int kk = 0; kk < HDP / 8; ++kk) {
-            const int d = kk * 8 + 4 * lh;
-            f32x4 t = {0.f, 0.f, 0.f, 0.f};
-            if (active && d < hd) t = *reinterpret_cast<const f32x4*>(qb + d);
-            qf[kk] = t * p.scale;
-        }
-    }
-    f32x16 o[HDP / 32];
-#pragma unroll
-    for (int db = 0; db < HDP / 32; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
-    float m = -INFINITY, sum = 0.0f;
-    const float* kb = p.k + (long)b * p.s_k * p.ldk + (long)h * hd;
-    const float* vb = p.v + (long)b * p.s_k * p.ldv + (long)h * hd;
-    const int nkt = (p.s_k + 31) / 32;
-#pragma unroll 1
-    for (int t0 = 0; t0 < nkt; t0 += STREAM_CT) {
-        const int nt = nkt - t0 < STREAM_CT ? nkt - t0 : STREAM_CT;
-        if (t0) __syncthreads();                                     // every wave is done with the previous chunk
-        {
-            constexpr int C4 = HDP / 4;
-            for (int i = tid; i < nt * 32 * C4; i += blockDim.x) {
-                const int row = i / C4, cc = (i % C4) * 4, key = t0 * 32 + row;
-                f32x4 kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-                if (key < p.s_k && cc < hd) {
-                    kv = *reinterpret_cast<const f32x4*>(kb + (long)key * p.ldk + cc);
-                    vv = *reinterpret_cast<const f32x4*>(vb + (long)key * p.ldv + cc);
-                }
-                *reinterpret_cast<f32x4*>(&Ks[row * KS + cc]) = kv;
-                *reinterpret_cast<f32x4*>(&Vs[row * HDP + cc]) = vv;
-            }
-        }
-        __syncthreads();
-        if (!active) continue;
-#pragma unroll 1
-        for (int t = 0; t < nt; ++t) {
-            f32x16 st;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[r] = 0.0f;
-#pragma unroll
-            for (int kk = 0; kk < HDP / 8; ++kk) {
-                const f32x4 kf = *reinterpret_cast<const f32x4*>(&Ks[(t * 32 + l31) * KS + kk * 8 + 4 * lh]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    st = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[e], qf[kk][e], st, 0, 0, 0);
-            }
-            float mt = -INFINITY;
-            if ((t0 + t + 1) * 32 > p.s_k) {                 // only the last key tile has keys to mask: wave-uniform
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = (t0 + t) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    st[r] = key < p.s_k ? st[r] : -INFINITY;
-                    mt = fmaxf(mt, st[r]);
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mt = fmaxf(mt, st[r]);
-            }
-            mt = fmaxf(mt, __shfl_xor(mt, 32));
-            const float m_new = fmaxf(m, mt);
-            const float alpha = __expf(m - m_new);
-            float ps = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float e = __expf(st[r] - m_new);
-                st[r] = e;
-                ps += e;
-            }
-            sum = sum * alpha + ps;
-            m = m_new;
-#pragma unroll
-            for (int db = 0; db < HDP / 32; ++db) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const float vf = Vs[row * HDP + db * 32 + l31];
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf, st[r], o[db], 0, 0, 0);
-                }
-            }
-        }
-    }
-    if (!active || qi >= p.s_q) return;                      // both lanes of a query leave together
-    sum += __shfl_xor(sum, 32);
-    const float inv = 1.0f / sum;
-    if (p.out_b) {
-        unsigned short* ob = p.out_b + ((long)b * p.s_q + qi) * p.ldo + (long)h * hd;
-#pragma unroll
-        for (int db = 0; db < HDP / 32; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = db * 32 + 8 * g + 4 * lh;
-                if (d < hd) {
-                    ushort4 t;
-                    t.x = f32_to_bf16_bits(o[db][4 * g] * inv); t.y = f32_to_bf16_bits(o[db][4 * g + 1] * inv);
-                    t.z = f32_to_bf16_bits(o[db][4 * g + 2] * inv); t.w = f32_to_bf16_bits(o[db][4 * g + 3] * inv);
-                    *reinterpret_cast<ushort4*>(ob + d) = t;
-                }
-            }
-        return;
-    }
-    float* ob = p.out + ((long)b * p.s_q + qi) * p.ldo + (long)h * hd;
-#pragma unroll
-    for (int db = 0; db < HDP / 32; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = db * 32 + 8 * g + 4 * lh;
-            if (d < hd) {
-                f32x4 t = {o[db][4 * g] * inv, o[db][4 * g + 1] * inv, o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv};
-                *reinterpret_cast<f32x4*>(ob + d) = t;
-            }
-        }
+    chunk_walk<F32Form<HDP>, STREAM_CT>(p, stream_group(p.s_q), (p.s_k + 31) / 32, blockDim.x, false);
 }
 
-// bf16 operands: the K chunk as rows of HDP * 2 + 16 bytes, the V chunk re-laid as [HDP/32][key][32 columns] for the transposing reads;
-// both stores of the resident kernel (bf16, or e4m3fn + E8M0 scales).
 template <int HDP>
 __global__ __launch_bounds__(STREAM_MAX_WAVES * 64, 4) void attn_bf16_stream_kernel(AttnParams p) {
-    constexpr int KSB = HDP * 2 + 16;
-    constexpr int ROWS = STREAM_CT * 32;
-    extern __shared__ __attribute__((aligned(16))) char smem_b[];
-    char* Ks = smem_b;                   // [ROWS][KSB]
-    char* Vs = smem_b + ROWS * KSB;      // [HDP/32][ROWS][64 B]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, lh = lane >> 5;
-    const StreamGroup sg = stream_group(p.s_q);
-    const int b = sg.bh / p.heads, h = sg.bh % p.heads;
-    const int hd = p.hd;
-    const bool active = wave < sg.gn;
-    const int qi = (sg.qt0 + (active ? wave : 0)) * 32 + l31;
-    const int qrow = qi < p.s_q ? qi : p.s_q - 1;
-    const int tr_off = ((lane & 15) >> 2) * 64 + (((lane >> 4) & 1) * 16 + (lane & 3) * 4) * 2 + lh * 4 * 64;
-    bf16x8 qf[HDP / 16];
-    {
-        const unsigned short* qb = p.qb + ((long)b * p.s_q + qrow) * p.ldq + (long)h * hd;
-#pragma unroll
-        for (int kk = 0; kk < HDP / 16; ++kk) {
-            const int d = kk * 16 + 8 * lh;
-            bf16x8 t = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (active && d < hd) t = *reinterpret_cast<const bf16x8*>(qb + d);
-            qf[kk] = t;
-        }
-    }
-    f32x16 o[HDP / 32];
-#pragma unroll
-    for (int db = 0; db < HDP / 32; ++db)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
-    float m = -INFINITY, sum = 0.0f;
-    const unsigned short* kb = p.kb + (long)b * p.s_k * p.ldk + (long)h * hd;
-    const unsigned short* vb = p.vb + (long)b * p.s_k * p.ldv + (long)h * hd;
-    const int nkt = (p.s_k + 31) / 32;
-#pragma unroll 1
-    for (int t0 = 0; t0 < nkt; t0 += STREAM_CT) {
-        const int nt = nkt - t0 < STREAM_CT ? nkt - t0 : STREAM_CT;
-        if (t0) __syncthreads();
-        {
-            constexpr int C8 = HDP / 8;      // 16-byte pieces per row
-            for (int i = tid; i < nt * 32 * C8; i += blockDim.x) {
-                const int row = i / C8, c = i % C8, key = t0 * 32 + row;
-                bf16x8 kv = {0, 0, 0, 0, 0, 0, 0, 0}, vv = {0, 0, 0, 0, 0, 0, 0, 0};
-                if (key < p.s_k && c * 8 < hd) {
-                    kv = *reinterpret_cast<const bf16x8*>(kb + (long)key * p.ldk + c * 8);
-                    vv = *reinterpret_cast<const bf16x8*>(vb + (long)key * p.ldv + c * 8);
-                }
-                *reinterpret_cast<bf16x8*>(Ks + row * KSB + c * 16) = kv;
-                *reinterpret_cast<bf16x8*>(Vs + ((c >> 2) * ROWS + row) * 64 + (c & 3) * 16) = vv;
-            }
-        }
-        __syncthreads();
-        if (!active) continue;
-#pragma unroll 1
-        for (int t = 0; t < nt; ++t) {
-            f32x16 st;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) st[r] = 0.0f;
-#pragma unroll
-            for (int kk = 0; kk < HDP / 16; ++kk) {
-                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + (t * 32 + l31) * KSB + (kk * 16 + 8 * lh) * 2);
-                st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], st, 0, 0, 0);
-            }
-            float mt = -INFINITY;
-            if ((t0 + t + 1) * 32 > p.s_k) {                 // only the last key tile has keys to mask: wave-uniform
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = (t0 + t) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    st[r] = key < p.s_k ? st[r] * p.scale : -INFINITY;
-                    mt = fmaxf(mt, st[r]);
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    st[r] *= p.scale;
-                    mt = fmaxf(mt, st[r]);
-                }
-            }
-            mt = fmaxf(mt, __shfl_xor(mt, 32));
-            const float m_new = fmaxf(m, mt);
-            const float alpha = __expf(m - m_new);
-            float ps = 0.0f;
-            bf16x8 pf[2];
-            {
-                unsigned pw[8];
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const float e0 = __expf(st[r] - m_new), e1 = __expf(st[r + 1] - m_new);
-                    ps += e0;                              // the normaliser sums the un-rounded weights
-                    ps += e1;
-                    pw[r >> 1] = f32x2_to_bf16x2_bits(e0, e1);
-                }
-                typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-                pf[0] = __builtin_bit_cast(bf16x8, u32x4_t{pw[0], pw[1], pw[2], pw[3]});
-                pf[1] = __builtin_bit_cast(bf16x8, u32x4_t{pw[4], pw[5], pw[6], pw[7]});
-            }
-            sum = sum * alpha + ps;
-            m = m_new;
-#pragma unroll
-            for (int db = 0; db < HDP / 32; ++db) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const char* vblk = Vs + (db * ROWS + t * 32 + 16 * s) * 64 + tr_off;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vblk));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vblk + 8 * 64));
-                    const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[s], o[db], 0, 0, 0);
-                }
-            }
-        }
-    }
-    if (!active) return;
-    sum += __shfl_xor(sum, 32);
-    const float inv = 1.0f / sum;
-    if (p.out_q8) {
-        // block-scaled fp8 output, as the resident kernel stores it: the two lanes of a query hold the 32 values of a d block between them
-        const long orow = (long)b * p.s_q + qi;
-#pragma unroll
-        for (int db = 0; db < HDP / 32; ++db) {
-            float am = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) am = fmaxf(am, fabsf(o[db][r] * inv));
-            am = fmaxf(am, __shfl_xor(am, 32));
-            const unsigned e8 = mx_scale_byte(am);
-            const float qs = mx_inv_scale(e8);
-            if (qi < p.s_q && db * 32 < hd) {
-                unsigned char* o8 = p.out_q8 + orow * p.ldo + (long)h * hd + db * 32 + 4 * lh;
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<unsigned*>(o8 + 8 * g) = pack4_fp8(o[db][4 * g] * inv * qs, o[db][4 * g + 1] * inv * qs,
-                                                                         o[db][4 * g + 2] * inv * qs, o[db][4 * g + 3] * inv * qs);
-                if (lh == 0) p.out_scales[mx_scale_offset(orow, (h * hd + db * 32) >> 5, p.out_srows)] = (unsigned char)e8;
-            }
-        }
-    } else if (qi < p.s_q) {
-        unsigned short* ob = p.out_b + ((long)b * p.s_q + qi) * p.ldo + (long)h * hd;
-#pragma unroll
-        for (int db = 0; db < HDP / 32; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d = db * 32 + 8 * g + 4 * lh;
-                if (d < hd) {
-                    ushort4 tt;
-                    tt.x = f32_to_bf16_bits(o[db][4 * g] * inv); tt.y = f32_to_bf16_bits(o[db][4 * g + 1] * inv);
-                    tt.z = f32_to_bf16_bits(o[db][4 * g + 2] * inv); tt.w = f32_to_bf16_bits(o[db][4 * g + 3] * inv);
-                    *reinterpret_cast<ushort4*>(ob + d) = tt;
-                }
-            }
-    }
+    chunk_walk<Bf16Form<HDP>, STREAM_CT>(p, stream_group(p.s_q), (p.s_k + 31) / 32, blockDim.x, false);
 }
 
-// A/B switch (tests, profiling): FERN_ATTN_STREAM=1 sends every non-causal tiled shape through the streaming form; read once per process
+// ---- host side -----------------------------------------------------------------------------------------------------
+// One launcher: opts the kernel in to its LDS size once (needed past 48 KB), then launches.  Keyed on the kernel POINTER: the
+// kernels all share one type, so a flag per type would be one flag for all of them.
+template <auto Kern>
+static hipError_t launch_kernel(const AttnParams& p, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set && lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    FERN_LAUNCH(Kern, grid, block, lds, s, p);
+    return hipGetLastError();
+}
+
+template <class F, int NT, bool CAUSAL>
+static hipError_t launch_resident(const AttnParams& p, hipStream_t s) {
+    // 197-token ViT heads: 7 query tiles -> 8 waves (two per SIMD) so one wave's softmax VALU work overlaps its partner's MFMAs
+    constexpr int NW = NT >= 7 ? 8 : 4;
+    const dim3 grid(p.batch * p.heads), block(NW * 64);
+    if constexpr (F::BF16) return launch_kernel<attn_bf16_kernel<F::HDP, NT, CAUSAL, NW>>(p, grid, block, F::image_bytes(NT * 32), s);
+    else return launch_kernel<attn_f32_kernel<F::HDP, NT, CAUSAL, NW>>(p, grid, block, F::image_bytes(NT * 32), s);
+}
+
+template <class F>
+static hipError_t launch_stream(const AttnParams& p, hipStream_t s) {
+    const int nqt = (p.s_q + 31) / 32, ng = (nqt + STREAM_MAX_WAVES - 1) / STREAM_MAX_WAVES;
+    const int gmax = nqt / ng + (nqt % ng ? 1 : 0);
+    const dim3 grid((unsigned)(p.batch * p.heads * ng)), block((gmax < 4 ? 4 : gmax) * 64);      // at least four waves stage a chunk
+    if constexpr (F::BF16) return launch_kernel<attn_bf16_stream_kernel<F::HDP>>(p, grid, block, F::image_bytes(STREAM_CT * 32), s);
+    else return launch_kernel<attn_f32_stream_kernel<F::HDP>>(p, grid, block, F::image_bytes(STREAM_CT * 32), s);
+}
+
+// A/B switches (tests, profiling), each read once per process: FERN_ATTN_STREAM=1 sends every non-causal tiled shape through the
+// streaming form; FERN_ATTN_CHUNKED=0 keeps the 197-token fp32 heads on the resident kernel
 static bool stream_forced() {
     static const bool on = [] { const char* e = getenv("FERN_ATTN_STREAM"); return e && e[0] == '1'; }();
     return on;
 }
-static void stream_launch_dims(const AttnParams& p, dim3* grid, dim3* block) {
-    const int nqt = (p.s_q + 31) / 32, ng = (nqt + STREAM_MAX_WAVES - 1) / STREAM_MAX_WAVES;
-    const int gmax = nqt / ng + (nqt % ng ? 1 : 0);
-    *grid = dim3((unsigned)(p.batch * p.heads * ng));
-    *block = dim3((gmax < 4 ? 4 : gmax) * 64);      // at least four waves stage a chunk
-}
-template <int HDP>
-static hipError_t launch_stream(const AttnParams& p, hipStream_t s) {
-    constexpr size_t lds = (size_t)STREAM_CT * 32 * (HDP + 4 + HDP) * sizeof(float);
-    static bool attr_set = false;
-    auto kern = attn_f32_stream_kernel<HDP>;
-    if (!attr_set && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    dim3 grid, block;
-    stream_launch_dims(p, &grid, &block);
-    FERN_LAUNCH(kern, grid, block, lds, s, p);
-    return hipGetLastError();
-}
-template <int HDP>
-static hipError_t launch_stream_b(const AttnParams& p, hipStream_t s) {
-    constexpr size_t lds = (size_t)STREAM_CT * 32 * (HDP * 2 + 16 + HDP * 2);      // <= 51 200 bytes (HDP = 96)
-    static bool attr_set = false;
-    auto kern = attn_bf16_stream_kernel<HDP>;
-    if (!attr_set && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    dim3 grid, block;
-    stream_launch_dims(p, &grid, &block);
-    FERN_LAUNCH(kern, grid, block, lds, s, p);
-    return hipGetLastError();
+static bool chunked_allowed() {
+    static const bool on = [] { const char* e = getenv("FERN_ATTN_CHUNKED"); return !(e && e[0] == '0'); }();
+    return on;
 }
 
-template <int HDP, int NT, bool CAUSAL>
-static hipError_t launch_inst_b(const AttnParams& p, hipStream_t s) {
-    constexpr size_t lds = (size_t)NT * 32 * (HDP * 2 + 16 + HDP * 2);
-    static bool attr_set = false;
-    constexpr int NW = NT >= 7 ? 8 : 4;
-    auto kern = attn_bf16_kernel<HDP, NT, CAUSAL, NW>;
-    if (!attr_set && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    FERN_LAUNCH(kern, dim3(p.batch * p.heads), dim3(NW * 64), lds, s, p);
-    return hipGetLastError();
-}
-
-template <int HDP>
-static hipError_t launch_hd_b(const AttnParams& p, hipStream_t s) {
+template <class F>
+static hipError_t launch_form(const AttnParams& p, hipStream_t s) {
     const int nt = (p.s_k + 31) / 32;
     if (p.causal) {
-        if (nt <= 1) return launch_inst_b<HDP, 1, true>(p, s);
-        if (nt <= 3) return launch_inst_b<HDP, 3, true>(p, s);
+        if (nt <= 1) return launch_resident<F, 1, true>(p, s);
+        if (nt <= 3) return launch_resident<F, 3, true>(p, s);
         return hipErrorInvalidValue;
     }
-    if (nt > 7 || stream_forced()) return launch_stream_b<HDP>(p, s);
-    if (nt <= 1) return launch_inst_b<HDP, 1, false>(p, s);
-    if (nt <= 3) return launch_inst_b<HDP, 3, false>(p, s);
-    return launch_inst_b<HDP, 7, false>(p, s);
-}
-
-template <int HDP, int NT, bool CAUSAL>
-static hipError_t launch_inst(const AttnParams& p, hipStream_t s) {
-    constexpr size_t lds = (size_t)NT * 32 * (HDP + 4 + HDP) * sizeof(float);
-    static bool attr_set = false;
-    // 197-token ViT heads: 7 query tiles -> 8 waves (two per SIMD) so one wave's softmax VALU work overlaps its partner's MFMAs
-    constexpr int NW = NT >= 7 ? 8 : 4;
-    auto kern = attn_f32_kernel<HDP, NT, CAUSAL, NW>;
-    if (!attr_set && lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
+    if (nt > 7 || stream_forced()) return launch_stream<F>(p, s);
+    if (nt <= 1) return launch_resident<F, 1, false>(p, s);
+    if (nt <= 3) return launch_resident<F, 3, false>(p, s);
+    if constexpr (!F::BF16) {
+        if (chunked_allowed() && nt > 4 && p.s_q <= 256)      // the key-chunked form: every wave owns one query tile
+            return launch_kernel<attn_f32_chunked_kernel<F::HDP, 7, 8, 2>>(p, dim3(p.batch * p.heads), dim3(8 * 64), F::image_bytes(4 * 32), s);
     }
-    FERN_LAUNCH(kern, dim3(p.batch * p.heads), dim3(NW * 64), lds, s, p);
-    return hipGetLastError();
+    return launch_resident<F, 7, false>(p, s);
 }
 
-template <int HDP>
+template <template <int> class Form>
 static hipError_t launch_hd(const AttnParams& p, hipStream_t s) {
-    const int nt = (p.s_k + 31) / 32;
-    if (p.causal) {
-        if (nt <= 1) return launch_inst<HDP, 1, true>(p, s);
-        if (nt <= 3) return launch_inst<HDP, 3, true>(p, s);
-        return hipErrorInvalidValue;
-    }
-    if (nt > 7 || stream_forced()) return launch_stream<HDP>(p, s);
-    if (nt <= 1) return launch_inst<HDP, 1, false>(p, s);
-    if (nt <= 3) return launch_inst<HDP, 3, false>(p, s);
-    {
-        static const bool chunked = [] { const char* e = getenv("FERN_ATTN_CHUNKED"); return !(e && e[0] == '0'); }();      // A/B switch
-        if (chunked && nt > 4 && p.s_q <= 256 && !p.out_b) {      // the key-chunked form: every wave owns one query tile
-            constexpr size_t lds = (size_t)4 * 32 * (HDP + 4 + HDP) * sizeof(float);
-            static bool attr_set = false;
-            auto kern = attn_f32_chunked_kernel<HDP, 7, 8, 2>;
-            if (!attr_set) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) return e;
-                attr_set = true;
-            }
-            FERN_LAUNCH(kern, dim3(p.batch * p.heads), dim3(8 * 64), lds, s, p);
-            return hipGetLastError();
-        }
-        return launch_inst<HDP, 7, false>(p, s);
-    }
+    if (p.hd <= 32) return launch_form<Form<32>>(p, s);
+    if (p.hd <= 64) return launch_form<Form<64>>(p, s);
+    if (p.hd <= 96) return launch_form<Form<96>>(p, s);
+    return hipErrorInvalidValue;
 }
 
 // ---- ONE query per (batch, head) (the class token of the last ViT block: clip_block_cls_only) ------------------------------------------
@@ -957,27 +582,20 @@ __global__ __launch_bounds__(256) void attn_f32_single_query_kernel(AttnParams p
     if (wave == 0 && lane < hd)
         p.out[(long)b * p.ldo + (long)h * hd + lane] = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) * (1.0f / sum);
 }
-
 hipError_t launch_attention(const AttnParams& p, hipStream_t s) {
     if (p.batch <= 0 || p.heads <= 0 || p.s_q <= 0 || p.s_k <= 0 || p.s_k > ATTN_MAX_KEYS) return hipErrorInvalidValue;
+    if (p.causal && p.s_q != p.s_k) return hipErrorInvalidValue;
     if (p.qb || p.kb || p.vb) {
         if (!p.qb || !p.kb || !p.vb || (!p.out_b && !p.out_q8) || (p.out_q8 && (!p.out_scales || (p.hd & 31))) || (p.hd & 7) || (p.ldq & 7) || (p.ldk & 7) || (p.ldv & 7) || (p.ldo & 3)) return hipErrorInvalidValue;
-        if (p.causal && p.s_q != p.s_k) return hipErrorInvalidValue;
-        if (p.hd <= 32) return launch_hd_b<32>(p, s);
-        if (p.hd <= 64) return launch_hd_b<64>(p, s);
-        if (p.hd <= 96) return launch_hd_b<96>(p, s);
-        return hipErrorInvalidValue;
+        return launch_hd<Bf16Form>(p, s);
     }
+    if (p.out_b || p.out_q8) return hipErrorInvalidValue;      // fp32 operands store fp32 only
     if ((p.hd & 3) || (p.ldq & 3) || (p.ldk & 3) || (p.ldv & 3) || (p.ldo & 3)) return hipErrorInvalidValue;
-    if (p.causal && p.s_q != p.s_k) return hipErrorInvalidValue;
-    if (p.s_q == 1 && !p.causal && p.hd <= 64 && p.s_k <= SQ1_MAX_KEYS && !p.out_b) {      // one query per head: no K / V image, no MFMA tile
+    if (p.s_q == 1 && !p.causal && p.hd <= 64 && p.s_k <= SQ1_MAX_KEYS) {      // one query per head: no K / V image, no MFMA tile
         FERN_LAUNCH(attn_f32_single_query_kernel<25>, dim3(p.batch * p.heads), dim3(256), 0, s, p);
         return hipGetLastError();
     }
-    if (p.hd <= 32) return launch_hd<32>(p, s);
-    if (p.hd <= 64) return launch_hd<64>(p, s);
-    if (p.hd <= 96) return launch_hd<96>(p, s);
-    return hipErrorInvalidValue;
+    return launch_hd<F32Form>(p, s);
 }
 
 }  // namespace fern

@@ -160,7 +160,8 @@ def test_streaming_kernels_are_bit_identical_to_the_resident_ones(engine, tmp_pa
     child, mine = np.load(path), dump.compute(engine)
     assert bool(child["stream_switch"][0]), "the child did not see FERN_ATTN_STREAM=1"
     assert sorted(f for f in child.files if f != "stream_switch") == sorted(mine)
-    assert len(mine) == len(dump.F32_SHAPES) + len(dump.BF16_SHAPES)
+    assert len(mine) == len(dump.F32_SHAPES) + len(dump.BF16_SHAPES) + 2 * len(dump.MX_SHAPES)      # MX: bytes and scale bytes
+    assert (len(dump.F32_SHAPES), len(dump.BF16_SHAPES), len(dump.MX_SHAPES)) == (7, 6, 3)
     for name, bits in mine.items():
         assert torch.equal(torch.from_numpy(child[name].astype(np.int64)), torch.from_numpy(bits.astype(np.int64))), name
 

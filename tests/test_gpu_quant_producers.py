@@ -222,7 +222,7 @@ ATTN_CASES = [(3, 12, 64, 197, False), (2, 8, 64, 77, True), (2, 4, 32, 50, Fals
 @pytest.mark.parametrize("b,heads,hd,s,causal", ATTN_CASES)
 def test_attention_mx8_output(engine, b, heads, hd, s, causal):
     """The attention kernel's block-scaled output (AttnParams.out_q8: attn_bf16_kernel's epilogue).  attn.hip launches the SAME
-    kernel instance for the bf16 and the MX output (launch_hd_b picks the template from head_dim / s_k / causal only; out_q8 is
+    kernel instance for the bf16 and the MX output (launch_form picks the template from head_dim / s_k / causal only; out_q8 is
     a run-time branch of the store), so both round one fp32 value o * (1/sum): (a) the scale byte equals the one of the bf16
     output's block maximum unless that maximum's bf16 rounding interval holds a 448 * 2^k boundary, and each element byte equals
     e4m3(bf16 value * 2^(127-e)) unless its bf16 rounding interval holds an e4m3 midpoint (excused mismatches < 5 %: a bf16 value
