@@ -4,7 +4,8 @@
 // patch means, embedding gathers, and the scalar-gate / attention-pooling tails of
 // CombinerSimple (fusion_model.py:92-94) and VisualSR (fusion_model.py:149-154).
 #include "kernels.h"
-#include "row_ops.h"      // RowRegs, row_load / row_store / row_sumsq, wave_sum, row_l2_normalize: shared with live.hip
+#include "row_ops.h"      // RowRegs, load4, row_load / row_store / row_sumsq, wave_sum, row_l2_normalize: shared with live.hip
+#include <type_traits>
 
 namespace fern {
 
@@ -22,101 +23,219 @@ __device__ __forceinline__ float quad_max(float v) {
 }
 __device__ __forceinline__ float oct_max(float v) { v = quad_max(v); return fmaxf(v, dpp_move<0x141>(v)); }
 
-// y = (x - mean) / sqrt(var + eps) * gamma + beta with the two-pass variance torch uses
-__device__ __forceinline__ void row_layernorm(RowRegs& r, const float* gamma, const float* beta, int d, int lane, float eps) {
+// ==== Row producers: the kernels that turn the residual stream, an activation or an image into the operand form of the next GEMM ====
+// A lane holds its part of a row as CHUNKS of W consecutive elements, x[i][e] = element e of chunk i: f32x4 chunks (W = 4: RowRegs and
+// the several-rows kernel, 64 lanes per row) or float[8] chunks (W = 8: the plain quantisers over 64 lanes, the half-wave LayerNorm over
+// 32).  Every load, the LayerNorm statement and every output form below is stated once over such chunks: in "LN -> fp8 equals
+// quantize_rows_fp8(layernorm(x)) byte for byte" (tests/test_gpu_quant_producers.py) both sides run the same text.  (Contraction is
+// still left to the compiler, as it always was here: which products of the variance become fmas depends on the code around the
+// call -- layernorm_rows_kernel below keeps its own copy for that reason.)
+template <class V>
+constexpr int chunk_width = sizeof(V) / sizeof(float);
+
+// ---- input forms (four elements: load4, row_ops.h) -----------------------------------------------------------------------------
+// Eight consecutive elements of a lane as fp32: two 16-byte loads of fp32, or one of bf16 (widened exactly).
+__device__ __forceinline__ void load8(float (&v)[8], const float* p) {
+    const f32x4 a = load4(p), b = load4(p + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
+}
+__device__ __forceinline__ void load8(float (&v)[8], const unsigned short* p) {
+    const uint4 t = *reinterpret_cast<const uint4*>(p);
+    const unsigned w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[2 * e] = __uint_as_float(w[e] << 16); v[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u); }
+}
+
+// ---- LayerNorm: y = (x - mean) / sqrt(var + eps) * gamma + beta with the two-pass variance torch uses -----------------------------
+// Over this lane's chunks of this row.  `sum` adds a value over the lanes that share the row (wave_sum, or the half-wave's sum);
+// live(i): chunk i lies inside the row (a chunk outside holds zeros: nothing for the sum, but (0 - mean)^2 for the variance).
+// A 4-element chunk enters the sum as one partial sum, the 8 elements of a half-wave chunk one by one: the orders these layouts have
+// always had, and the reason the half-wave kernel's values may differ from the one-row kernel's in the last bits.
+template <int CH, class V, class Sum>
+__device__ __forceinline__ float ln_mean(const V (&x)[CH], Sum sum, float d) {
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) s += r.v[i][0] + r.v[i][1] + r.v[i][2] + r.v[i][3];
-    const float mean = wave_sum(s) / (float)d;
+    for (int i = 0; i < CH; ++i) {
+        if constexpr (chunk_width<V> == 4) s += x[i][0] + x[i][1] + x[i][2] + x[i][3];
+        else
+#pragma unroll
+            for (int e = 0; e < chunk_width<V>; ++e) s += x[i][e];
+    }
+    return sum(s) / d;
+}
+template <int CH, class V, class Live, class Sum>
+__device__ __forceinline__ float ln_rstd(const V (&x)[CH], float mean, Live live, Sum sum, float d, float eps) {
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) {
+    for (int i = 0; i < CH; ++i)
+        if (live(i)) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { const float t = r.v[i][e] - mean; q += t * t; }
+            for (int e = 0; e < chunk_width<V>; ++e) { const float t = x[i][e] - mean; q += t * t; }
         }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)d + eps);
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) {
-            const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c);
-            const f32x4 bb = *reinterpret_cast<const f32x4*>(beta + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) r.v[i][e] = (r.v[i][e] - mean) * rstd * g[e] + bb[e];
-        }
-    }
+    return rsqrtf(sum(q) / d + eps);
 }
+__device__ __forceinline__ float ln_affine(float x, float mean, float rstd, float g, float b) { return (x - mean) * rstd * g + b; }
 
-__global__ __launch_bounds__(256) void layernorm_kernel(const float* x, const float* res, const float* gamma, const float* beta,
-                                                        float* y, long rows, int d, long ldx, long ldy, float eps) {
-    const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    RowRegs r;
-    row_load(r, x + row * ldx, d, lane);
-    if (res) {
-        RowRegs q;
-        row_load(q, res + row * ldx, d, lane);
-#pragma unroll
-        for (int i = 0; i < MAXV; ++i) r.v[i] += q.v[i];
-    }
-    row_layernorm(r, gamma, beta, d, lane, eps);
-    row_store(r, y + row * ldy, d, lane);
-}
-
-__global__ __launch_bounds__(256) void layernorm_bf16_kernel(const float* x, const float* gamma, const float* beta, unsigned short* y,
-                                                             long rows, int d, long ldx, long ldy, float eps) {
-    const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    RowRegs r;
-    row_load(r, x + row * ldx, d, lane);
-    row_layernorm(r, gamma, beta, d, lane, eps);
-    unsigned short* yr = y + row * ldy;
+// the RowRegs instance (one wave per row of any width d % 4 == 0): the one-row kernels below and bert_embed_kernel
+__device__ __forceinline__ void row_layernorm(RowRegs& r, const float* gamma, const float* beta, int d, int lane, float eps) {
+    const auto live = [&](int i) { return (i * 64 + lane) * 4 < d; };
+    const float mean = ln_mean(r.v, wave_sum, (float)d);
+    const float rstd = ln_rstd(r.v, mean, live, wave_sum, (float)d, eps);
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int c = (i * 64 + lane) * 4;
         if (c < d) {
-            ushort4 o;
-            o.x = f32_to_bf16_bits(r.v[i][0]); o.y = f32_to_bf16_bits(r.v[i][1]);
-            o.z = f32_to_bf16_bits(r.v[i][2]); o.w = f32_to_bf16_bits(r.v[i][3]);
-            *reinterpret_cast<ushort4*>(yr + c) = o;
+            const f32x4 g = load4(gamma + c), bb = load4(beta + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) r.v[i][e] = ln_affine(r.v[i][e], mean, rstd, g[e], bb[e]);
         }
     }
 }
 
-// LayerNorm fused with per-row fp8 (e4m3fn) quantisation: scale = max|y| / 448, y8 = fp8(y / scale)
-__global__ __launch_bounds__(256) void layernorm_fp8_kernel(const float* x, const float* gamma, const float* beta, unsigned char* y,
-                                                            float* scale, long rows, int d, long ldx, long ldy, float eps) {
-    const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    RowRegs r;
-    row_load(r, x + row * ldx, d, lane);
-    row_layernorm(r, gamma, beta, d, lane, eps);
-    float am = 0.f;
+// ---- output forms (the fp32 store of a row: row_store, row_ops.h) -----------------------------------------------------------------
+// four fp32 -> four bf16 (round to nearest even), one 8-byte store
+__device__ __forceinline__ void store4_bf16(unsigned short* p, const f32x4 v) {
+    ushort4 o;
+    o.x = f32_to_bf16_bits(v[0]); o.y = f32_to_bf16_bits(v[1]); o.z = f32_to_bf16_bits(v[2]); o.w = f32_to_bf16_bits(v[3]);
+    *reinterpret_cast<ushort4*>(p) = o;
+}
+// max(am, |v[e]|) over a chunk, and the same without a running maximum.  A maximum is exact, so the order cannot change a bit: a
+// 4-element chunk is reduced by pairs and an 8-element one in turn because those are the instructions each layout has always had.
+template <class V>
+__device__ __forceinline__ float chunk_amax(float am, const V& v) {
+    if constexpr (chunk_width<V> == 4) return fmaxf(am, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) am = fmaxf(am, fmaxf(fmaxf(fabsf(r.v[i][0]), fabsf(r.v[i][1])), fmaxf(fabsf(r.v[i][2]), fabsf(r.v[i][3]))));
+    for (int e = 0; e < chunk_width<V>; ++e) am = fmaxf(am, fabsf(v[e]));
+    return am;
+}
+template <class V>
+__device__ __forceinline__ float chunk_amax(const V& v) {
+    if constexpr (chunk_width<V> == 4) return fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+    return chunk_amax(0.f, v);
+}
+// a chunk times `inv` as e4m3fn bytes: one 4- or 8-byte store, or (NT) non-temporal dword stores
+template <bool NT = false, class V>
+__device__ __forceinline__ void store_fp8(unsigned char* p, const V& v, float inv) {
+    constexpr int NW = chunk_width<V> / 4;
+    unsigned w[NW];
+#pragma unroll
+    for (int h = 0; h < NW; ++h) w[h] = pack4_fp8(v[4 * h] * inv, v[4 * h + 1] * inv, v[4 * h + 2] * inv, v[4 * h + 3] * inv);
+    if constexpr (NT) {
+#pragma unroll
+        for (int h = 0; h < NW; ++h) __builtin_nontemporal_store(w[h], reinterpret_cast<unsigned*>(p) + h);
+    } else if constexpr (NW == 1) {
+        *reinterpret_cast<unsigned*>(p) = w[0];
+    } else {
+        *reinterpret_cast<uint2*>(p) = uint2{w[0], w[1]};
     }
+}
+// Per-row fp8 (e4m3fn) of a row held by the 64 lanes of a wave, chunk i at column (i * 64 + lane) * W: scale = max|x| / 448 (1 for an
+// all-zero row), bytes = fp8(x / scale).
+// `am`: max|x| over this lane's chunks (chunk_amax over the chunks inside the row) -- an argument, because a kernel that takes the
+// maximum where it loads a chunk has one guarded region per chunk, where a second loop is a second set of them: quantize_rows_fp8 at
+// 12608 x 3072 took 21.1 us with the second loop against 19.4 us.
+template <int CH, class V>
+__device__ __forceinline__ void row_store_fp8(const V (&x)[CH], float am, unsigned char* yr, float* scale, int d, int lane) {
+    constexpr int W = chunk_width<V>;
     am = wave_max(am);
     const float sc = am > 0.f ? am * (1.0f / 448.0f) : 1.0f;
     const float inv = 1.0f / sc;
-    if (lane == 0) scale[row] = sc;
-    unsigned char* yr = y + row * ldy;
+    if (lane == 0) *scale = sc;
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        if (c < d) *reinterpret_cast<unsigned*>(yr + c) = pack4_fp8(r.v[i][0] * inv, r.v[i][1] * inv, r.v[i][2] * inv, r.v[i][3] * inv);
+    for (int i = 0; i < CH; ++i) {
+        const int c = (i * 64 + lane) * W;
+        if (c < d) store_fp8(yr + c, x[i], inv);
+    }
+}
+// MX (block-scaled) e4m3fn: one E8M0 byte per 32 consecutive k, the operand form of v_mfma_scale_f32_32x32x64_f8f6f4 (gemm_bf16.hip:
+// gemm_mx8_kernel).  e = the smallest power of two that brings the block's maximum to <= 448, read off the maximum's exponent /
+// mantissa bits (448 = 1.75 * 2^8); the scaling x * 2^(127-e) is exact.
+// This lane's chunk at column c of `row` (bytes at yr + c); the 32 / W consecutive lanes that hold a 32-element block all call this
+// (the group maximum is a DPP exchange), live or not -- a chunk outside the row holds zeros and stores nothing.
+template <bool NT = false, class V>
+__device__ __forceinline__ void store_mx8(const V& v, bool live, unsigned char* yr, int c, unsigned char* scales, long srows, long row, int lane) {
+    constexpr int W = chunk_width<V>;
+    static_assert(W == 4 || W == 8, "a 32-element block is 8 or 4 lanes");
+    const float lm = chunk_amax(v);
+    const float am = W == 4 ? oct_max(lm) : quad_max(lm);
+    if (live) {
+        const unsigned e = mx_scale_byte(am);
+        const float inv = mx_inv_scale(e);
+        store_fp8<NT>(yr + c, v, inv);
+        if ((lane & (32 / W - 1)) == 0) scales[mx_scale_offset(row, c >> 5, srows)] = (unsigned char)e;
     }
 }
 
-// Per-row fp8 quantisation of a bf16 or fp32 matrix (one wave per row, rows up to 8 * 512 = 4096 wide, d % 8 == 0):
-// scale = max|x| / 448, y8 = fp8(x / scale).  Used for the attention / GELU outputs (bf16) and the weight matrices (fp32).
+// ---- one row per wave: LayerNorm of fp32 (or bf16) rows of any width, into any operand form ----------------------------------------
+// Out: where the normalised row goes.
+struct RowToF32 {
+    float* y; long ldy;
+    __device__ void operator()(const RowRegs& r, long row, int d, int lane) const { row_store(r, y + row * ldy, d, lane); }
+};
+struct RowToBf16 {
+    unsigned short* y; long ldy;
+    __device__ void operator()(const RowRegs& r, long row, int d, int lane) const {
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            if (c < d) store4_bf16(y + row * ldy + c, r.v[i]);
+        }
+    }
+};
+struct RowToFp8 {
+    unsigned char* y; long ldy; float* scale;
+    __device__ void operator()(const RowRegs& r, long row, int d, int lane) const {
+        float am = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i)
+            if ((i * 64 + lane) * 4 < d) am = chunk_amax(am, r.v[i]);
+        row_store_fp8(r.v, am, y + row * ldy, scale + row, d, lane);
+    }
+};
+struct RowToMx8 {      // a lane holds 4 consecutive elements: a 32-block is 8 lanes
+    unsigned char* y; long ldy; unsigned char* scales; long srows;
+    __device__ void operator()(const RowRegs& r, long row, int d, int lane) const {
+#pragma unroll
+        for (int i = 0; i < MAXV; ++i) {
+            const int c = (i * 64 + lane) * 4;
+            store_mx8(r.v[i], c < d, y + row * ldy, c, scales, srows, row, lane);
+        }
+    }
+};
+template <class T, class Out>
+__global__ __launch_bounds__(256) void layernorm_kernel(const T* x, const float* gamma, const float* beta, Out out, long rows, int d, long ldx,
+                                                        float eps, const float* res) {
+    // (res is the LAST argument: with it among the first, the quantising instances fetched gamma / beta / out from the argument
+    // segment only where the affine map needs them -- a scalar-load wait in the middle of every wave, where the four kernels this body
+    // replaces had all their arguments in the prologue; in a kernel trace LN -> fp8 at 16448 x 1024 took 17.7 us for 16.7, 17.3 for 17.4 now)
+    const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    RowRegs r;
+    row_load(r, x + row * ldx, d, lane);
+    if constexpr (std::is_same_v<Out, RowToF32>) {      // the fused residual (BERT): fp32 -> fp32 only
+        if (res) {
+            RowRegs q;
+            row_load(q, res + row * ldx, d, lane);
+#pragma unroll
+            for (int i = 0; i < MAXV; ++i) r.v[i] += q.v[i];
+        }
+    }
+    row_layernorm(r, gamma, beta, d, lane, eps);
+    out(r, row, d, lane);
+}
+
+// Per-row fp8 / MX quantisation of a bf16 or fp32 matrix: one wave per row, a lane holds 8 consecutive elements (a 32-block is 4
+// lanes), rows up to 8 * 512 = 4096 wide, d % 8 == 0.  Used for the attention / GELU outputs (bf16) and the weight matrices (fp32).
+__device__ __forceinline__ void row_load8(float (&v)[8], const unsigned short* xb, const float* xf, long at, bool live) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = 0.f;
+    if (live) {
+        if (xb) load8(v, xb + at);
+        else load8(v, xf + at);
+    }
+}
 __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const unsigned short* xb, const float* xf, long ldx, unsigned char* y, long ldy,
                                                                 float* scale, long rows, int d) {
     const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
@@ -127,94 +246,48 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const unsigned s
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int c = (i * 64 + lane) * 8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[i][e] = 0.f;
-        if (c < d) {
-            if (xb) {
-                const uint4 t = *reinterpret_cast<const uint4*>(xb + row * ldx + c);
-                const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[i][2 * e] = __uint_as_float(w[e] << 16); v[i][2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u); }
-            } else {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(xf + row * ldx + c), b = *reinterpret_cast<const f32x4*>(xf + row * ldx + c + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[i][e] = a[e]; v[i][4 + e] = b[e]; }
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(v[i][e]));
-        }
+        row_load8(v[i], xb, xf, row * ldx + c, c < d);
+        if (c < d) am = chunk_amax(am, v[i]);
     }
-    am = wave_max(am);
-    const float sc = am > 0.f ? am * (1.0f / 448.0f) : 1.0f;
-    const float inv = 1.0f / sc;
-    if (lane == 0) scale[row] = sc;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = (i * 64 + lane) * 8;
-        if (c < d) {
-            uint2 o;
-            o.x = pack4_fp8(v[i][0] * inv, v[i][1] * inv, v[i][2] * inv, v[i][3] * inv);
-            o.y = pack4_fp8(v[i][4] * inv, v[i][5] * inv, v[i][6] * inv, v[i][7] * inv);
-            *reinterpret_cast<uint2*>(y + row * ldy + c) = o;
-        }
-    }
+    row_store_fp8(v, am, y + row * ldy, scale + row, d, lane);
 }
-
-// ---- MX (block-scaled) e4m3fn quantisers: one E8M0 byte per 32 consecutive k, the operand form of
-// v_mfma_scale_f32_32x32x64_f8f6f4 (gemm_bf16.hip: gemm_mx8_kernel).  e = the smallest power of two that brings the block's
-// maximum to <= 448, read off the maximum's exponent / mantissa bits (448 = 1.75 * 2^8); the scaling x * 2^(127-e) is exact.
-
-// LayerNorm fused with the MX quantiser (a lane holds 4 consecutive elements: a 32-block is 8 lanes).  XB: the rows are bf16 (the
-// block-scaled mode's residual stream), 8-byte loads of the same 4 elements per lane.
-__device__ __forceinline__ void row_load_bf16(RowRegs& r, const unsigned short* x, int d, int lane) {
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        f32x4 t = {0.f, 0.f, 0.f, 0.f};
-        if (c < d) {
-            const uint2 w = *reinterpret_cast<const uint2*>(x + c);
-            t[0] = __uint_as_float(w.x << 16); t[1] = __uint_as_float(w.x & 0xffff0000u);
-            t[2] = __uint_as_float(w.y << 16); t[3] = __uint_as_float(w.y & 0xffff0000u);
-        }
-        r.v[i] = t;
-    }
-}
-template <bool XB>
-__global__ __launch_bounds__(256) void layernorm_mx8_kernel(const float* x, const unsigned short* xb, const float* gamma, const float* beta, unsigned char* y,
-                                                            unsigned char* scales, long srows, long rows, int d, long ldx, long ldy, float eps) {
+__global__ __launch_bounds__(256) void quantize_mx8_kernel(const unsigned short* xb, const float* xf, long ldx, unsigned char* y, long ldy,
+                                                           unsigned char* scales, long srows, long rows, int d) {
     const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
-    RowRegs r;
-    if (XB) row_load_bf16(r, xb + row * ldx, d, lane);
-    else row_load(r, x + row * ldx, d, lane);
-    row_layernorm(r, gamma, beta, d, lane, eps);
-    unsigned char* yr = y + row * ldy;
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = (i * 64 + lane) * 4;
-        float am = fmaxf(fmaxf(fabsf(r.v[i][0]), fabsf(r.v[i][1])), fmaxf(fabsf(r.v[i][2]), fabsf(r.v[i][3])));
-        am = oct_max(am);
-        if (c < d) {
-            const unsigned e = mx_scale_byte(am);
-            const float inv = mx_inv_scale(e);
-            *reinterpret_cast<unsigned*>(yr + c) = pack4_fp8(r.v[i][0] * inv, r.v[i][1] * inv, r.v[i][2] * inv, r.v[i][3] * inv);
-            if ((lane & 7) == 0) scales[mx_scale_offset(row, c >> 5, srows)] = (unsigned char)e;
-        }
+    for (int i = 0; i < 8; ++i) {
+        const int c = (i * 64 + lane) * 8;
+        float v[8];
+        row_load8(v, xb, xf, row * ldx + c, c < d);
+        store_mx8(v, c < d, y + row * ldy, c, scales, srows, row, lane);
     }
 }
 
-// ---- several rows per wave (round 4) ------------------------------------------------------------------------------------------
+// d = 256 * NV, NV = 1 .. 4 (the widths the two fixed-width LayerNorm kernels below cover): f(NV as a compile-time constant)
+template <class F>
+static void with_nv(int d, F f) {
+    switch (d / 256) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+
+// ---- several rows per wave (round 4), fp32 -> fp32 --------------------------------------------------------------------------------
 // One wave per row is one memory round trip, two dependent wave reductions and one store per row, back to back: at 12608 rows x
 // 768 columns the LayerNorm launches ran at 2.8 TB/s (bf16 rows in, fp8 out) -- latency, not bytes.  Here a wave owns RPW consecutive
 // rows: all their loads are issued before the first reduction (one round trip per RPW rows), the 2 x RPW reductions interleave, and
 // gamma / beta are fetched once per wave.  The width is a template parameter (d = 256 NV: no per-chunk bounds tests).  The per-row
-// arithmetic is the one-row kernels' statement for statement, and the kernel is used for EVERY row count of a width it covers, so a
-// row's bits still do not depend on the batch it travels in.
-// IN: 0 fp32 rows, 1 bf16 rows.  OUT: 0 fp32 (may alias the input), 1 e4m3fn + E8M0 block scales (the MX quantiser above).
-template <int NV, int RPW, int IN, int OUT>
-__global__ __launch_bounds__(256) void layernorm_rows_kernel(const void* xin, const float* gamma, const float* beta, void* yout, unsigned char* scales,
-                                                             long srows, long rows, long ldx, long ldy, float eps) {
+// arithmetic is the one-row kernel's statement for statement, and the kernel is used for EVERY row count of a width it covers,
+// so a row's bits still do not depend on the batch it travels in.  The output may alias the input.
+// (The bf16-input and MX-output forms this kernel once had lost to the half-wave kernel below in rounds 4 and 6 -- 15.1 and 14.0 us
+// against 9.1 at 12608 x 768 -- and are gone: rows the half-wave kernel does not take go to the one-row kernel, with the same bytes.)
+template <int NV, int RPW>
+__global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* x, const float* gamma, const float* beta, float* y, long rows, long ldx,
+                                                             long ldy, float eps) {
     constexpr int D = 256 * NV;
     const int lane = threadIdx.x & 63;
     const long row0 = ((long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6)) * RPW;
@@ -224,30 +297,20 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const void* xin, co
     for (int r = 0; r < RPW; ++r) {
         const long row = row0 + r < rows ? row0 + r : rows - 1;      // a short last group re-reads the last row (not stored)
 #pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = (i * 64 + lane) * 4;
-            if (IN == 1) {
-                const uint2 w = *reinterpret_cast<const uint2*>(static_cast<const unsigned short*>(xin) + row * ldx + c);
-                v[r][i] = f32x4{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u)};
-            } else {
-                v[r][i] = *reinterpret_cast<const f32x4*>(static_cast<const float*>(xin) + row * ldx + c);
-            }
-        }
+        for (int i = 0; i < NV; ++i) v[r][i] = load4(x + row * ldx + (i * 64 + lane) * 4);
     }
     f32x4 g[NV], bb[NV];
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        g[i] = *reinterpret_cast<const f32x4*>(gamma + (i * 64 + lane) * 4);
-        bb[i] = *reinterpret_cast<const f32x4*>(beta + (i * 64 + lane) * 4);
+        g[i] = load4(gamma + (i * 64 + lane) * 4);
+        bb[i] = load4(beta + (i * 64 + lane) * 4);
     }
     float mean[RPW], rstd[RPW];
 #pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) s += v[r][i][0] + v[r][i][1] + v[r][i][2] + v[r][i][3];
-        mean[r] = wave_sum(s) / (float)D;
-    }
+    for (int r = 0; r < RPW; ++r) mean[r] = ln_mean(v[r], wave_sum, (float)D);
+    // ln_rstd's statement, written out: called as a function (any of five ways of passing the rows tried) the compiler pairs the four
+    // rows' products differently and contracts other terms of q into fmas than it does here (at 768 columns 42 instead of 16; at 512
+    // and 1024, 12 and 46 instead of none), which moves the last bit of rstd.  These are the operations the kernel has always had.
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
         float q = 0.f;
@@ -257,90 +320,46 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const void* xin, co
             for (int e = 0; e < 4; ++e) { const float t = v[r][i][e] - mean[r]; q += t * t; }
         rstd[r] = rsqrtf(wave_sum(q) / (float)D + eps);
     }
-    unsigned e8s[RPW][NV];               // OUT == 1: the E8M0 byte of this lane's 32-block, per (row, chunk)
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
         const long row = row0 + r;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
-            const int c = (i * 64 + lane) * 4;
             f32x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (v[r][i][e] - mean[r]) * rstd[r] * g[i][e] + bb[i][e];
-            if (OUT == 0) {
-                if (row < rows) *reinterpret_cast<f32x4*>(static_cast<float*>(yout) + row * ldy + c) = o;
-            } else {
-                float am = fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3])));
-                am = oct_max(am);
-                const unsigned e8 = mx_scale_byte(am);
-                const float inv = mx_inv_scale(e8);
-                e8s[r][i] = e8;
-                if (row < rows)
-                    *reinterpret_cast<unsigned*>(static_cast<unsigned char*>(yout) + row * ldy + c) = pack4_fp8(o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv);
-            }
+            for (int e = 0; e < 4; ++e) o[e] = ln_affine(v[r][i][e], mean[r], rstd[r], g[i][e], bb[i][e]);
+            if (row < rows) *reinterpret_cast<f32x4*>(y + row * ldy + (i * 64 + lane) * 4) = o;
         }
-    }
-    if (OUT == 1) {
-        // Scales: the layout holds one dword per (128-k tile kt, row) = the bytes of blocks 4kt .. 4kt+3, i.e. of lanes 0, 8, 16, 24 (+ 32
-        // for the odd kt) of chunk kt / 2 -- gathered with v_readlane into ONE dword per (row, kt), and the RPW = 4 consecutive rows of the
-        // wave are 16 contiguous bytes per kt: one 16-byte store instead of 16 single-byte stores from 16 lanes of 4 instructions (a
-        // byte store is a write transaction of its own; 24 per row were as many transactions as all the data stores of the row).
-        static_assert(RPW == 4, "the scale gather writes the four rows of a wave as one uint4");
-        const bool whole = row0 + RPW <= rows && (srows & 3) == 0;      // row0 is a multiple of 4: the 16-byte stores are aligned
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                unsigned dw[RPW];
-#pragma unroll
-                for (int r = 0; r < RPW; ++r) {
-                    const int e = (int)e8s[r][i];
-                    dw[r] = (unsigned)__builtin_amdgcn_readlane(e, 32 * half) | ((unsigned)__builtin_amdgcn_readlane(e, 32 * half + 8) << 8) |
-                            ((unsigned)__builtin_amdgcn_readlane(e, 32 * half + 16) << 16) | ((unsigned)__builtin_amdgcn_readlane(e, 32 * half + 24) << 24);
-                }
-                const long kt = 2 * i + half;
-                unsigned* dst = reinterpret_cast<unsigned*>(scales + (kt * srows + row0) * 4);
-                if (lane == 0) {
-                    if (whole) *reinterpret_cast<uint4*>(dst) = uint4{dw[0], dw[1], dw[2], dw[3]};
-                    else
-#pragma unroll
-                        for (int r = 0; r < RPW; ++r)
-                            if (row0 + r < rows) dst[r] = dw[r];
-                }
-            }
     }
 }
 constexpr int LN_RPW = 4;
 // widths the several-rows kernel covers (256, 512, 768, 1024): launch it and return true
-template <int IN, int OUT>
-static bool launch_ln_rows(const void* x, const float* gamma, const float* beta, void* y, unsigned char* scales, long srows, long rows, int d,
-                           long ldx, long ldy, float eps, hipStream_t s) {
+static bool launch_ln_rows(const float* x, const float* gamma, const float* beta, float* y, long rows, int d, long ldx, long ldy, float eps,
+                           hipStream_t s) {
     if (d % 256 || d > 1024) return false;
-    // gamma / beta are read as f32x4 and (OUT = 1) four rows' scale dwords leave as one 16-byte store: the public entry points accept
-    // any 4-byte-aligned view, so a pointer that is not 16-byte aligned takes the one-row kernel instead
-    if (((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15) || (OUT == 1 && ((uintptr_t)scales & 15))) return false;
+    // gamma / beta are read as f32x4: the public entry points accept any 4-byte-aligned view, so a pointer that is not 16-byte aligned
+    // takes the one-row kernel instead
+    if (((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15)) return false;
     const dim3 grid((unsigned)((rows + ROWS_PER_BLOCK * LN_RPW - 1) / (ROWS_PER_BLOCK * LN_RPW)));
-    switch (d / 256) {
-        case 1: hipLaunchKernelGGL((layernorm_rows_kernel<1, LN_RPW, IN, OUT>), grid, dim3(256), 0, s, x, gamma, beta, y, scales, srows, rows, ldx, ldy, eps); break;
-        case 2: hipLaunchKernelGGL((layernorm_rows_kernel<2, LN_RPW, IN, OUT>), grid, dim3(256), 0, s, x, gamma, beta, y, scales, srows, rows, ldx, ldy, eps); break;
-        case 3: hipLaunchKernelGGL((layernorm_rows_kernel<3, LN_RPW, IN, OUT>), grid, dim3(256), 0, s, x, gamma, beta, y, scales, srows, rows, ldx, ldy, eps); break;
-        default: hipLaunchKernelGGL((layernorm_rows_kernel<4, LN_RPW, IN, OUT>), grid, dim3(256), 0, s, x, gamma, beta, y, scales, srows, rows, ldx, ldy, eps); break;
-    }
+    with_nv(d, [&](auto nv) {
+        hipLaunchKernelGGL((layernorm_rows_kernel<decltype(nv)::value, LN_RPW>), grid, dim3(256), 0, s, x, gamma, beta, y, rows, ldx, ldy, eps);
+    });
     return true;
 }
 
 // ---- bf16 rows in, MX fp8 out: half a wave per row (round 4, tools/probe/ln_lab.hip) ---------------------------------------------
 // The block-scaled mode's LayerNorm reads the bf16 residual stream the GEMM before it has just written (from other XCDs: nothing of
 // it is in this CU's L2) and is a single round of waves: its time is the latency of that round, not its 29 MB.  Measured in the chain
-// writer -> LayerNorm -> reader at 12608 x 768: the four-rows-per-wave kernel above 15.1 us, one row per wave 10.7, this form 9.1
-// (a byte-for-byte copy of the same shape: 8.7).  A lane holds 8 consecutive elements of each 256-column chunk of ITS half-wave's
-// row -- one 16-byte load and one 8-byte store per chunk, 512 contiguous bytes per half-wave -- and a 32-element MX block is 4 lanes.
-// The fp8 bytes leave with nt stores: the next kernel reads them from other XCDs anyway.  Statistics: the row's 32 lanes on the DPP
-// network, the two 16-lane rows of the half added in a fixed order; used for EVERY row count of a width it covers (batch-invariant).
-// F32IN (round 6, FERN_PREC_MX8_MLP / _MX8_IMG: block-scaled operands over the FP32 residual stream): the same kernel on fp32 rows --
-// two 16-byte loads per chunk and lane -- instead of the four-rows-per-wave kernel (14.0 us at 12608 x 768, 22 launches per step).
-template <int NV, bool F32IN = false>
-__global__ __launch_bounds__(256) void layernorm_half_kernel(const void* xin, const float* gamma, const float* beta, unsigned char* y, unsigned char* scales,
+// writer -> LayerNorm -> reader at 12608 x 768: four rows per wave (the several-rows kernel's layout) 15.1 us, one row per wave 10.7,
+// this form 9.1 (a byte-for-byte copy of the same shape: 8.7).  A lane holds 8 consecutive elements of each 256-column chunk of ITS
+// half-wave's row -- one 16-byte load and one 8-byte store per chunk, 512 contiguous bytes per half-wave -- and a 32-element MX block
+// is 4 lanes.  The fp8 bytes leave with nt stores: the next kernel reads them from other XCDs anyway.  Statistics: the row's 32 lanes
+// on the DPP network, the two 16-lane rows of the half added in a fixed order; used for EVERY row count of a width it covers
+// (batch-invariant).
+// T = float (round 6, FERN_PREC_MX8_MLP / _MX8_IMG: block-scaled operands over the FP32 residual stream): the same kernel on fp32 rows
+// -- two 16-byte loads per chunk and lane -- instead of four rows per wave (14.0 us at 12608 x 768, 22 launches per step).
+template <int NV, class T>
+__global__ __launch_bounds__(256) void layernorm_half_kernel(const T* x, const float* gamma, const float* beta, unsigned char* y, unsigned char* scales,
                                                              long srows, long rows, long ldx, long ldy, float eps) {
     constexpr int D = 256 * NV;
     const int lane = threadIdx.x & 63, l31 = lane & 31, lh = lane >> 5;
@@ -348,36 +367,15 @@ __global__ __launch_bounds__(256) void layernorm_half_kernel(const void* xin, co
     if (rowp >= rows) return;
     const long row = rowp + lh;
     const long rrow = row < rows ? row : rows - 1;             // an odd row count: the last wave's upper half re-reads the last row (not stored)
-    float v[NV][8];
-    if (F32IN) {
-        const float* x = reinterpret_cast<const float*>(xin);
+    float v[NV][8], g[NV][8], bb[NV][8];
 #pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(x + rrow * ldx + (i * 32 + l31) * 8);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(x + rrow * ldx + (i * 32 + l31) * 8 + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { v[i][e] = a[e]; v[i][4 + e] = b[e]; }
-        }
-    } else {
-        const unsigned short* x = reinterpret_cast<const unsigned short*>(xin);
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const uint4 w = *reinterpret_cast<const uint4*>(x + rrow * ldx + (i * 32 + l31) * 8);
-            const unsigned ww[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { v[i][2 * e] = __uint_as_float(ww[e] << 16); v[i][2 * e + 1] = __uint_as_float(ww[e] & 0xffff0000u); }
-        }
-    }
-    float g[NV][8], bb[NV][8];
+    for (int i = 0; i < NV; ++i) load8(v[i], x + rrow * ldx + (i * 32 + l31) * 8);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        const int c = (i * 32 + l31) * 8;
-        const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + c), g1 = *reinterpret_cast<const f32x4*>(gamma + c + 4);
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(beta + c), b1 = *reinterpret_cast<const f32x4*>(beta + c + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { g[i][e] = g0[e]; g[i][4 + e] = g1[e]; bb[i][e] = b0[e]; bb[i][4 + e] = b1[e]; }
+        load8(g[i], gamma + (i * 32 + l31) * 8);
+        load8(bb[i], beta + (i * 32 + l31) * 8);
     }
-    auto half_sum = [&](float t) {      // over the 32 lanes of this lane's half
+    const auto half_sum = [&](float t) {      // over the 32 lanes of this lane's half
         t += dpp_move<0xB1>(t);
         t += dpp_move<0x4E>(t);
         t += dpp_move<0x141>(t);
@@ -385,78 +383,60 @@ __global__ __launch_bounds__(256) void layernorm_half_kernel(const void* xin, co
         const float lo = lane_f(t, 0) + lane_f(t, 16), hi = lane_f(t, 32) + lane_f(t, 48);
         return lh ? hi : lo;
     };
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sum += v[i][e];
-    const float mean = half_sum(sum) / (float)D;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { const float t = v[i][e] - mean; q += t * t; }
-    const float rstd = rsqrtf(half_sum(q) / (float)D + eps);
+    const float mean = ln_mean(v, half_sum, (float)D);
+    const float rstd = ln_rstd(v, mean, [](int) { return true; }, half_sum, (float)D, eps);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         float o[8];
-        float am = 0.f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { o[e] = (v[i][e] - mean) * rstd * g[i][e] + bb[i][e]; am = fmaxf(am, fabsf(o[e])); }
-        am = quad_max(am);
-        const unsigned e8 = mx_scale_byte(am);
-        const float inv = mx_inv_scale(e8);
-        if (row < rows) {
-            unsigned* dst = reinterpret_cast<unsigned*>(y + row * ldy + (i * 32 + l31) * 8);
-            __builtin_nontemporal_store(pack4_fp8(o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv), dst);
-            __builtin_nontemporal_store(pack4_fp8(o[4] * inv, o[5] * inv, o[6] * inv, o[7] * inv), dst + 1);
-            // blocks 8i .. 8i+7 of the row, 4 lanes each (mx_scale_offset: k tile = block / 4, byte = block % 4)
-            if ((l31 & 3) == 0) scales[mx_scale_offset(row, i * 8 + (l31 >> 2), srows)] = (unsigned char)e8;
-        }
+        for (int e = 0; e < 8; ++e) o[e] = ln_affine(v[i][e], mean, rstd, g[i][e], bb[i][e]);
+        store_mx8<true>(o, row < rows, y + row * ldy, (i * 32 + l31) * 8, scales, srows, row, lane);
     }
 }
-template <bool F32IN>
-static bool launch_ln_half(const void* x, const float* gamma, const float* beta, unsigned char* y, unsigned char* scales, long srows, long rows, int d,
+template <class T>
+static bool launch_ln_half(const T* x, const float* gamma, const float* beta, unsigned char* y, unsigned char* scales, long srows, long rows, int d,
                            long ldx, long ldy, float eps, hipStream_t s) {
     if (d % 256 || d > 1024 || (ldx & 7) || (ldy & 7) || ((uintptr_t)x & 15) || ((uintptr_t)y & 7) || ((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15)) return false;
     const dim3 grid((unsigned)((rows + ROWS_PER_BLOCK * 2 - 1) / (ROWS_PER_BLOCK * 2)));
-    switch (d / 256) {
-        case 1: hipLaunchKernelGGL((layernorm_half_kernel<1, F32IN>), grid, dim3(256), 0, s, x, gamma, beta, y, scales, srows, rows, ldx, ldy, eps); break;
-        case 2: hipLaunchKernelGGL((layernorm_half_kernel<2, F32IN>), grid, dim3(256), 0, s, x, gamma, beta, y, scales, srows, rows, ldx, ldy, eps); break;
-        case 3: hipLaunchKernelGGL((layernorm_half_kernel<3, F32IN>), grid, dim3(256), 0, s, x, gamma, beta, y, scales, srows, rows, ldx, ldy, eps); break;
-        default: hipLaunchKernelGGL((layernorm_half_kernel<4, F32IN>), grid, dim3(256), 0, s, x, gamma, beta, y, scales, srows, rows, ldx, ldy, eps); break;
-    }
+    with_nv(d, [&](auto nv) {
+        hipLaunchKernelGGL((layernorm_half_kernel<decltype(nv)::value, T>), grid, dim3(256), 0, s, x, gamma, beta, y, scales, srows, rows, ldx, ldy, eps);
+    });
     return true;
 }
 
-// Patch rows of a [b, 3, img, img] image batch, block-scale quantised: row (image, gy, gx) = the 3 x patch x patch pixels of one
-// patch in (channel, y, x) order -- the k order of conv1's [width, 3 * patch * patch] weight -- so that the patch embedding of the
-// block-scaled mode is a plain MX GEMM.  One wave per patch; a lane holds 4 consecutive x of one (channel, y) per step.
+// ---- patch rows of a [b, 3, img, img] image batch ------------------------------------------------------------------------------
+// Row (image, gy, gx) = the 3 x patch x patch pixels of one patch in (channel, y, x) order -- the k order of conv1's
+// [width, 3 * patch * patch] weight -- so that the patch embedding is a plain GEMM.  One wave per patch.
+struct PatchRow {
+    const float* src;      // the patch's top left pixel in channel 0
+    int img, patch, pp;
+    __device__ const float* at(int k) const {      // element k of the row
+        const int ch = k / pp, rem = k % pp;
+        return src + ((long)ch * img + rem / patch) * img + rem % patch;
+    }
+};
+__device__ __forceinline__ PatchRow patch_row(const float* images, long row, int img, int patch, int grid) {
+    const int g2 = grid * grid;
+    const long b = row / g2;
+    const int gy = (int)(row % g2) / grid, gx = (int)(row % g2) % grid;
+    return PatchRow{images + b * 3L * img * img + (long)(gy * patch) * img + gx * patch, img, patch, patch * patch};
+}
+
+// Block-scale quantised (the patch embedding of the block-scaled mode is a plain MX GEMM); a lane holds 4 consecutive x of one
+// (channel, y) per step.
 __global__ __launch_bounds__(256) void im2col_mx8_kernel(const float* images, unsigned char* y, unsigned char* scales, long srows, long rows,
                                                          int img, int patch, int grid) {
     const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
-    const int pp = patch * patch, d = 3 * pp, g2 = grid * grid;
-    const long b = row / g2;
-    const int gy = (int)(row % g2) / grid, gx = (int)(row % g2) % grid;
-    const float* src = images + b * 3L * img * img + (long)(gy * patch) * img + gx * patch;
-    unsigned char* yr = y + row * d;
+    const PatchRow p = patch_row(images, row, img, patch, grid);
+    const int d = 3 * p.pp;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int k = (i * 64 + lane) * 4;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (k < d) {
-            const int ch = k / pp, rem = k % pp;
-            v = *reinterpret_cast<const f32x4*>(src + ((long)ch * img + rem / patch) * img + rem % patch);
-        }
-        const float am = oct_max(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-        if (k < d) {
-            const unsigned e = mx_scale_byte(am);
-            const float inv = mx_inv_scale(e);
-            *reinterpret_cast<unsigned*>(yr + k) = pack4_fp8(v[0] * inv, v[1] * inv, v[2] * inv, v[3] * inv);
-            if ((lane & 7) == 0) scales[mx_scale_offset(row, k >> 5, srows)] = (unsigned char)e;
-        }
+        if (k < d) v = load4(p.at(k));
+        store_mx8(v, k < d, y + row * d, k, scales, srows, row, lane);
     }
 }
 
@@ -466,22 +446,12 @@ __global__ __launch_bounds__(256) void im2col_bf16_kernel(const float* images, u
     const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
-    const int pp = patch * patch, d = 3 * pp, g2 = grid * grid;
-    const long b = row / g2;
-    const int gy = (int)(row % g2) / grid, gx = (int)(row % g2) % grid;
-    const float* src = images + b * 3L * img * img + (long)(gy * patch) * img + gx * patch;
-    unsigned short* yr = y + row * d;
+    const PatchRow p = patch_row(images, row, img, patch, grid);
+    const int d = 3 * p.pp;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int k = (i * 64 + lane) * 4;
-        if (k < d) {
-            const int ch = k / pp, rem = k % pp;
-            const f32x4 v = *reinterpret_cast<const f32x4*>(src + ((long)ch * img + rem / patch) * img + rem % patch);
-            uint2 o;
-            o.x = (unsigned)f32_to_bf16_bits(v[0]) | ((unsigned)f32_to_bf16_bits(v[1]) << 16);
-            o.y = (unsigned)f32_to_bf16_bits(v[2]) | ((unsigned)f32_to_bf16_bits(v[3]) << 16);
-            *reinterpret_cast<uint2*>(yr + k) = o;
-        }
+        if (k < d) store4_bf16(y + row * d + k, load4(p.at(k)));
     }
 }
 
@@ -492,59 +462,9 @@ __global__ __launch_bounds__(256) void patch_rows_f32_kernel(const float* images
     const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
-    const int pp = patch * patch, d = 3 * pp, g2 = grid * grid;
-    const long b = row / g2;
-    const int gy = (int)(row % g2) / grid, gx = (int)(row % g2) % grid;
-    const float* src = images + b * 3L * img * img + (long)(gy * patch) * img + gx * patch;
-    float* yr = y + row * kp;
-    for (int k = lane; k < kp; k += 64) {
-        float v = 0.0f;
-        if (k < d) {
-            const int ch = k / pp, rem = k % pp;
-            v = src[((long)ch * img + rem / patch) * img + rem % patch];
-        }
-        yr[k] = v;
-    }
-}
-
-// bf16 or fp32 rows up to 4096 wide (a lane holds 8 consecutive elements: a 32-block is 4 lanes)
-__global__ __launch_bounds__(256) void quantize_mx8_kernel(const unsigned short* xb, const float* xf, long ldx, unsigned char* y, long ldy,
-                                                           unsigned char* scales, long srows, long rows, int d) {
-    const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= rows) return;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int c = (i * 64 + lane) * 8;
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = 0.f;
-        if (c < d) {
-            if (xb) {
-                const uint4 t = *reinterpret_cast<const uint4*>(xb + row * ldx + c);
-                const unsigned w[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[2 * e] = __uint_as_float(w[e] << 16); v[2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u); }
-            } else {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(xf + row * ldx + c), b = *reinterpret_cast<const f32x4*>(xf + row * ldx + c + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
-            }
-        }
-        float am = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(v[e]));
-        am = quad_max(am);
-        if (c < d) {
-            const unsigned e8 = mx_scale_byte(am);
-            const float inv = mx_inv_scale(e8);
-            uint2 o;
-            o.x = pack4_fp8(v[0] * inv, v[1] * inv, v[2] * inv, v[3] * inv);
-            o.y = pack4_fp8(v[4] * inv, v[5] * inv, v[6] * inv, v[7] * inv);
-            *reinterpret_cast<uint2*>(y + row * ldy + c) = o;
-            if ((lane & 3) == 0) scales[mx_scale_offset(row, c >> 5, srows)] = (unsigned char)e8;
-        }
-    }
+    const PatchRow p = patch_row(images, row, img, patch, grid);
+    const int d = 3 * p.pp;
+    for (int k = lane; k < kp; k += 64) y[row * kp + k] = k < d ? *p.at(k) : 0.0f;
 }
 
 __global__ __launch_bounds__(256) void l2norm_kernel(const float* x, const float* x2, long ldx, float* y, long ldy, long rows, int d,
@@ -942,41 +862,41 @@ __global__ __launch_bounds__(256) void attnpool_tokens_kernel(const float* x, co
 static inline bool bad_width(int d) { return d <= 0 || (d & 3) || d > 64 * 4 * MAXV; }
 static inline dim3 row_grid(long rows) { return dim3((unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)); }
 
+template <class T, class Out>
+static hipError_t launch_ln_row(const T* x, const float* res, const float* gamma, const float* beta, Out out, long rows, int d, long ldx, float eps,
+                                hipStream_t s) {
+    hipLaunchKernelGGL((layernorm_kernel<T, Out>), row_grid(rows), dim3(256), 0, s, x, gamma, beta, out, rows, d, ldx, eps, res);
+    return hipGetLastError();
+}
 hipError_t launch_layernorm(const float* x, const float* res, const float* gamma, const float* beta, float* y, long rows, int d,
                             long ldx, long ldy, float eps, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     if (bad_width(d) || (ldx & 3) || (ldy & 3)) return hipErrorInvalidValue;
-    if (!res && launch_ln_rows<0, 0>(x, gamma, beta, y, nullptr, 0, rows, d, ldx, ldy, eps, s)) return hipGetLastError();
-    hipLaunchKernelGGL(layernorm_kernel, row_grid(rows), dim3(256), 0, s, x, res, gamma, beta, y, rows, d, ldx, ldy, eps);
-    return hipGetLastError();
+    if (!res && launch_ln_rows(x, gamma, beta, y, rows, d, ldx, ldy, eps, s)) return hipGetLastError();
+    return launch_ln_row(x, res, gamma, beta, RowToF32{y, ldy}, rows, d, ldx, eps, s);
 }
 hipError_t launch_layernorm_bf16(const float* x, const float* gamma, const float* beta, unsigned short* y, long rows, int d, long ldx,
                                  long ldy, float eps, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     if (bad_width(d) || (ldx & 3) || (ldy & 3)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(layernorm_bf16_kernel, row_grid(rows), dim3(256), 0, s, x, gamma, beta, y, rows, d, ldx, ldy, eps);
-    return hipGetLastError();
+    return launch_ln_row(x, nullptr, gamma, beta, RowToBf16{y, ldy}, rows, d, ldx, eps, s);
 }
 hipError_t launch_layernorm_fp8(const float* x, const float* gamma, const float* beta, unsigned char* y, float* scale, long rows, int d,
                                 long ldx, long ldy, float eps, hipStream_t s) {
     if (rows <= 0) return hipSuccess;
     if (bad_width(d) || (ldx & 3) || (ldy & 3)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(layernorm_fp8_kernel, row_grid(rows), dim3(256), 0, s, x, gamma, beta, y, scale, rows, d, ldx, ldy, eps);
-    return hipGetLastError();
+    return launch_ln_row(x, nullptr, gamma, beta, RowToFp8{y, ldy, scale}, rows, d, ldx, eps, s);
 }
+// the half-wave kernel where it accepts the call (the towers' rows: d = 256 NV, contiguous, 16-byte aligned), else one row per wave
 hipError_t launch_layernorm_mx8(const float* x, const float* gamma, const float* beta, unsigned char* y, unsigned char* scales, long srows,
                                 long rows, int d, long ldx, long ldy, float eps, hipStream_t s, const unsigned short* x_bf16) {
     if (rows <= 0) return hipSuccess;
     if (d <= 0 || d % 128 || d > 256 * MAXV || (ldx & 3) || (ldy & 3) || srows < rows) return hipErrorInvalidValue;
-    if (x_bf16 ? launch_ln_half<false>(x_bf16, gamma, beta, y, scales, srows, rows, d, ldx, ldy, eps, s)
-               : launch_ln_half<true>(x, gamma, beta, y, scales, srows, rows, d, ldx, ldy, eps, s))
+    if (x_bf16 ? launch_ln_half(x_bf16, gamma, beta, y, scales, srows, rows, d, ldx, ldy, eps, s)
+               : launch_ln_half(x, gamma, beta, y, scales, srows, rows, d, ldx, ldy, eps, s))
         return hipGetLastError();
-    if (x_bf16 ? launch_ln_rows<1, 1>(x_bf16, gamma, beta, y, scales, srows, rows, d, ldx, ldy, eps, s)
-               : launch_ln_rows<0, 1>(x, gamma, beta, y, scales, srows, rows, d, ldx, ldy, eps, s))
-        return hipGetLastError();
-    if (x_bf16) hipLaunchKernelGGL(layernorm_mx8_kernel<true>, row_grid(rows), dim3(256), 0, s, x, x_bf16, gamma, beta, y, scales, srows, rows, d, ldx, ldy, eps);
-    else hipLaunchKernelGGL(layernorm_mx8_kernel<false>, row_grid(rows), dim3(256), 0, s, x, x_bf16, gamma, beta, y, scales, srows, rows, d, ldx, ldy, eps);
-    return hipGetLastError();
+    const RowToMx8 out{y, ldy, scales, srows};
+    return x_bf16 ? launch_ln_row(x_bf16, nullptr, gamma, beta, out, rows, d, ldx, eps, s) : launch_ln_row(x, nullptr, gamma, beta, out, rows, d, ldx, eps, s);
 }
 hipError_t launch_im2col_mx8(const float* images, unsigned char* y, unsigned char* scales, long srows, int b, int img, int patch, int grid,
                              hipStream_t s) {

@@ -34,12 +34,19 @@ struct RowRegs {
     f32x4 v[MAXV];
 };
 
-__device__ __forceinline__ void row_load(RowRegs& r, const float* x, int d, int lane) {
+// Four consecutive elements of a lane as fp32: one 16-byte load of fp32, or one 8-byte load of bf16 (widened exactly).
+__device__ __forceinline__ f32x4 load4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 load4(const unsigned short* p) {
+    const uint2 w = *reinterpret_cast<const uint2*>(p);
+    return f32x4{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u)};
+}
+template <class T>      // fp32 rows, or bf16 rows (the block-scaled mode's residual stream)
+__device__ __forceinline__ void row_load(RowRegs& r, const T* x, int d, int lane) {
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int c = (i * 64 + lane) * 4;
         f32x4 t = {0.f, 0.f, 0.f, 0.f};
-        if (c < d) t = *reinterpret_cast<const f32x4*>(x + c);
+        if (c < d) t = load4(x + c);
         r.v[i] = t;
     }
 }

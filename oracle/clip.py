@@ -36,7 +36,7 @@ _INV448 = torch.tensor(1.0 / 448.0, dtype=torch.float32)
 
 
 def _q8(x):
-    """Per-row fp8 quantisation as the product does it (csrc/elem.hip:quantize_rows_fp8_kernel): scale = max|row| * (1/448)
+    """Per-row fp8 quantisation as the product does it (csrc/elem.hip: row_store_fp8, the store of quantize_rows_fp8_kernel and of LN -> fp8): scale = max|row| * (1/448)
     (1 for a zero row), q = e4m3fn(x * (1 / scale)), round to nearest even.  Returns (q as fp32, scale)."""
     am = x.abs().amax(dim=-1, keepdim=True)
     sc = torch.where(am > 0, am * _INV448, torch.ones_like(am))
@@ -45,8 +45,8 @@ def _q8(x):
 
 
 def mx8_quantize(x):
-    """MX (block-scaled) e4m3fn quantisation as the product does it (csrc/elem.hip: quantize_mx8_kernel / layernorm_mx8_kernel;
-    include/fern.h: fern_quantize_mx8): per (row, 32 consecutive k) one E8M0 byte e = the smallest power-of-two exponent with
+    """MX (block-scaled) e4m3fn quantisation as the product does it (csrc/elem.hip: store_mx8, the store of quantize_mx8_kernel, the LN -> MX
+    kernels and im2col_mx8_kernel; include/fern.h: fern_quantize_mx8): per (row, 32 consecutive k) one E8M0 byte e = the smallest power-of-two exponent with
     max|block| * 2^-(e-127) <= 448, read off the maximum's exponent and mantissa bits (448 = 1.75 * 2^8), clamped to [1, 253];
     q = e4m3fn(x * 2^(127-e)) -- exact scaling, round-to-nearest-even cast.  Returns (q [.., D] float8_e4m3fn, e [.., D/32] uint8)."""
     shp = x.shape

@@ -1,5 +1,5 @@
 """Kernel-level parity of the producers that fuse a quantiser into another kernel: LayerNorm -> bf16 / per-row fp8 / MX8 (the
-half-wave, one-row and several-rows kernels), the attention kernel's block-scaled output, im2col -> bf16 / MX8, reached through
+half-wave and one-row kernels, and the several-rows fp32 kernel), the attention kernel's block-scaled output, im2col -> bf16 / MX8, reached through
 fern_layernorm_q / fern_attention_mx8 / fern_im2col_q, i.e. through the launchers the towers call.  Every MX output is written
 with scale_rows > rows into a sentinel-filled scale array, and the padding rows must come back untouched."""
 import pytest
@@ -110,7 +110,8 @@ def _check_fp64_rule(y8, e_got, y64, tol):
 @pytest.mark.parametrize("d", [128, 256, 384, 512, 640, 768, 1024])
 def test_layernorm_bf16_and_fp8_are_bit_exact(engine, rows, d):
     """LN -> bf16 == to_bf16(layernorm(x)); LN -> fp8 == quantize_rows_fp8(layernorm(x)), bytes and scale floats.  The fused kernels
-    share the one-row kernel's statistics (row_layernorm), so the fp32 values they round are those fern_layernorm returns."""
+    are the one-row kernel with another store (layernorm_kernel<float, Out>: one row_layernorm, and LN -> fp8 stores through the
+    row_store_fp8 that quantize_rows_fp8_kernel uses), so the fp32 values they round are those fern_layernorm returns."""
     x, gamma, beta = _ln_inputs(rows, d, 7 * d + rows)
     xc = x.cuda()
     ln = engine.layernorm(xc, gamma, beta, EPS, residual=torch.zeros_like(xc))      # the one-row kernel
@@ -127,7 +128,7 @@ def test_layernorm_bf16_and_fp8_are_bit_exact(engine, rows, d):
 @pytest.mark.parametrize("d", [128, 384, 640])
 @pytest.mark.parametrize("bf16", [False, True])
 def test_layernorm_mx8_one_row_kernel_is_bit_exact(engine, rows, d, bf16):
-    """Widths that are not a multiple of 256 take layernorm_mx8_kernel<XB> (one row per wave, fp32 or bf16 rows): equal to
+    """Widths that are not a multiple of 256 take layernorm_kernel<T, RowToMx8> (one row per wave, fp32 or bf16 rows): equal to
     quantize_mx8(layernorm(x)) bit for bit, and to the fp64 rule.  scale_rows = rows + 5, padding untouched."""
     x, gamma, beta = _ln_inputs(rows, d, 11 * d + rows, bf16)
     ln = engine.layernorm(x.cuda(), gamma, beta, EPS)
@@ -148,10 +149,10 @@ def test_layernorm_mx8_one_row_kernel_is_bit_exact(engine, rows, d, bf16):
 @pytest.mark.parametrize("d", [256, 768, 1024])
 @pytest.mark.parametrize("bf16", [False, True])
 def test_layernorm_mx8_several_rows_kernel_is_bit_exact(engine, rows, d, bf16):
-    """A row stride with ldx % 8 == 4 (every pointer 16-byte aligned) is outside the half-wave kernel's 16-byte row loads, so the
-    launcher takes layernorm_rows_kernel<NV, 4, IN, 1> (four rows per wave, scales gathered into one dword per row and 128-k tile).
-    Equal to quantize_mx8(layernorm(x)) bit for bit, with a scale_rows > rows that is a multiple of 4 (the 16-byte stores wherever
-    a wave's four rows are all present) and one that is not (per-row stores only), padding untouched."""
+    """(The name is from the four-rows-per-wave MX kernel these inputs once reached; the 18 cases keep their ids.)  A row stride with ldx % 8 == 4 (every pointer 16-byte aligned) is outside the half-wave kernel's 16-byte row loads, so at
+    these widths, too, the launcher falls to the one-row kernel (layernorm_kernel<T, RowToMx8>; the four-rows-per-wave MX kernel
+    that once took such calls is gone).  Equal to quantize_mx8(layernorm(x)) bit for bit, with a scale_rows > rows that is a
+    multiple of 4 and one that is not, padding untouched."""
     x, gamma, beta = _ln_inputs(rows, d, 13 * d + rows, bf16)
     ldx = d + 4
     buf = torch.zeros(rows, ldx, dtype=torch.bfloat16 if bf16 else torch.float32)
@@ -173,7 +174,7 @@ def test_layernorm_mx8_several_rows_kernel_is_bit_exact(engine, rows, d, bf16):
 @pytest.mark.parametrize("d", [256, 512, 768, 1024])
 @pytest.mark.parametrize("bf16", [False, True])
 def test_layernorm_mx8_half_wave_kernel_fp64_rule(engine, rows, d, bf16):
-    """The towers' MX LayerNorm (layernorm_half_kernel<NV, F32IN>: half a wave per row, statistics added in another order than the
+    """The towers' MX LayerNorm (layernorm_half_kernel<NV, T>: half a wave per row, statistics added in another order than the
     one-row kernel, so its fp32 values may differ in the last bits) against mx8_quantize of an fp64 LayerNorm, under the fp64 rule
     (_check_fp64_rule, DELTA above).  The excused fraction must stay below 1e-3."""
     x, gamma, beta = _ln_inputs(rows, d, 17 * d + rows, bf16)
@@ -192,7 +193,7 @@ def test_layernorm_mx8_half_wave_kernel_fp64_rule(engine, rows, d, bf16):
 
 @pytest.mark.parametrize("d", [256, 512, 768, 1024])
 def test_layernorm_several_rows_kernel_equals_one_row_kernel(engine, d):
-    """layernorm(x) (layernorm_rows_kernel<NV, 4, 0, 0>) == layernorm(x, residual=zeros) (layernorm_kernel, one row per wave) bit for
+    """layernorm(x) (layernorm_rows_kernel<NV, 4>) == layernorm(x, residual=zeros) (layernorm_kernel<float, RowToF32>, one row per wave) bit for
     bit: the "statement for statement" claim that makes a row's LayerNorm independent of the kernel its batch size picks."""
     for rows in (1, 6, 197):
         x, gamma, beta = _ln_inputs(rows, d, 19 * d + rows)

@@ -1,4 +1,5 @@
-// Lab bench of the block-scaled mode's LayerNorm (bf16 rows in, e4m3 + E8M0 block scales out; elem.hip layernorm_rows_kernel<3,4,1,1>):
+// Lab bench of the block-scaled mode's LayerNorm (bf16 rows in, e4m3 + E8M0 block scales out; the four-rows-per-wave form
+// elem.hip had before layernorm_half_kernel<3, unsigned short>, which came out of this bench):
 // why does it take ~12 us for 29 MB?  Stand-alone.  Each variant runs in the chain  writer (rewrites the bf16 rows from another
 // workgroup -> row mapping, as the GEMM epilogue before it does)  ->  LayerNorm variant  ->  reader (reads the fp8 bytes, as the next
 // GEMM does), and is timed by its own start / stop events (hipExtLaunchKernelGGL).
