@@ -76,6 +76,12 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fern_rank_count_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_i64, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fern_rank_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_i64, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fern_sim_topk_from": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fern_sim_topk_page": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_i64,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fern_sim_topk_items": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                     c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fern_item_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_void_p, c_int, c_i64, c_void_p,

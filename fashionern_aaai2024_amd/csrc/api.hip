@@ -2537,6 +2537,109 @@ extern "C" int fern_rank_count_filtered(fern_ctx* c, const float* q, const float
     return rank_count_impl(c, call, keys_in, m, out_count, stream);
 }
 
+// Ranking pages (include/fern.h: fern_rank_select, fern_sim_topk_from, fern_sim_topk_page; page.hip), per query chunk: the deep stage's
+// score rows S [m, ld] once (exact: the fp32 MFMA chain; bf16: the sweep's store form; ineligible pairs stored as -inf), then
+//   select   the multi-workgroup radix select on the rows: the key at each place, SEL_T places per walk;
+//   from     the deep stage's select + radix fallback with a per-query key ceiling (margin 0: the stored scores are the ranking scores);
+//   page     both on the same rows: the select writes the key at place offsets[b] into workspace, which is the selection's ceiling.
+// A chunk keeps its score rows plus the select's histograms inside the deep stage's budget.  Nothing is read back.
+struct PageCall {
+    RankCall call;
+    long ld() const { return score_ld(call.N); }
+    long chunk() const { return budget_chunk(ld(), (double)SEL_T * (8 * 256 * sizeof(unsigned) + 9 * sizeof(SelectState) + 8)); }      // ... and the select's workspace
+    ScoreForm form() const { return call.N == 0 ? SCORES_NONE : call.gallery ? SCORES_EXACT : SCORES_SWEEP; }
+};
+static PageCall page_call(const char* fn, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D, int64_t idx_offset,
+                          const int32_t* exclude_idx, const uint32_t* tags, const uint32_t* mask, const uint32_t* value, int K = 0,
+                          float* out_scores = nullptr, int32_t* out_idx = nullptr) {
+    // fp32 rows rank when they are given: there is no pre-filtered form, so a bf16 copy beside them is not looked at
+    return PageCall{{fn, q, gallery, gallery ? nullptr : gallery_bf16, nullptr, B, N, D, idx_offset, exclude_idx, row_tags(tags, mask, value), K, out_scores, out_idx}};
+}
+static int page_check(fern_ctx* c, const PageCall& p, bool outs_ok, int count, int kmax) {
+    FERN_TRY(rank_check(c, p.call, GALLERY_EITHER, outs_ok, count, kmax));
+    return p.chunk() < 1 ? over_budget(p.call) : FERN_OK;
+}
+// keys[b][j] = the key at place places[b][j] of the m queries `a` starts at, on their score rows r (an empty gallery has no places)
+static int select_places(fern_ctx* c, const RankCall& a, int mq, const ScoreRows& r, long ld, const int32_t* places, int m, int clamp,
+                         unsigned long long* keys, hipStream_t s) {
+    if (a.N == 0) {
+        HIP_TRY(hipMemsetAsync(keys, 0, (size_t)mq * m * sizeof(unsigned long long), s));
+        return FERN_OK;
+    }
+    SelectState* states; unsigned* hist; unsigned long long* found;
+    FERN_TRY(ws_get(c, (size_t)9 * mq * SEL_T, &states));
+    FERN_TRY(ws_get(c, (size_t)mq * SEL_T * 8 * 256, &hist));
+    FERN_TRY(ws_get(c, (size_t)mq * SEL_T, &found));
+    HIP_TRY(hipMemsetAsync(hist, 0, (size_t)mq * SEL_T * 8 * 256 * sizeof(unsigned), s));      // on the stream: re-run by a replayed graph
+    for (int t0 = 0; t0 < m; t0 += SEL_T)
+        HIP_TRY(launch_rank_select(r.S, ld, mq, a.N, places + t0, m, std::min(SEL_T, m - t0), clamp, a.exclude, a.idx_offset, states, hist, found,
+                                   keys + t0, m, s));
+    return FERN_OK;
+}
+// the deep stage's selection of the chunk under per-query ceilings
+static int select_under(const RankCall& a, int mq, const ScoreRows& r, long ld, const unsigned long long* ceil, hipStream_t s) {
+    HIP_TRY(launch_deep_select(r.S, ld, a.N, mq, a.K, nullptr, nullptr, nullptr, a.D, a.exclude, a.idx_offset, a.out_scores, a.out_idx, r.flags, r.state, s, ceil));
+    if (a.N > 0) HIP_TRY(launch_deep_fallback(r.S, ld, a.N, mq, a.K, a.exclude, a.idx_offset, a.out_scores, a.out_idx, r.flags, r.state, s, ceil));
+    return FERN_OK;
+}
+
+extern "C" int fern_rank_select(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                                const int32_t* places, int m, int64_t idx_offset, const int32_t* exclude_idx, uint64_t* out_keys,
+                                const uint32_t* tags, const uint32_t* mask, const uint32_t* value, void* stream) {
+    const PageCall p = page_call("fern_rank_select", q, gallery, gallery_bf16, B, N, D, idx_offset, exclude_idx, tags, mask, value);
+    FERN_TRY(page_check(c, p, places && out_keys, m, 0));
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    return for_query_chunks(c, s, B, p.chunk(), [&](long o, int mq) -> int {
+        const RankCall a = p.call.at(o);
+        ScoreRows r;
+        StageTimer st(c, s);
+        FERN_TRY(score_rows(c, a, mq, p.ld(), p.form(), st, s, &r));
+        FERN_TRY(select_places(c, a, mq, r, p.ld(), places + o * m, m, 0, reinterpret_cast<unsigned long long*>(out_keys) + o * m, s));
+        st.commit(mq, (int)N, D);
+        return FERN_OK;
+    });
+}
+
+extern "C" int fern_sim_topk_from(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D, int K,
+                                  const uint64_t* from_keys, float* out_scores, int32_t* out_idx, int64_t idx_offset, const int32_t* exclude_idx,
+                                  const uint32_t* tags, const uint32_t* mask, const uint32_t* value, void* stream) {
+    const PageCall p = page_call("fern_sim_topk_from", q, gallery, gallery_bf16, B, N, D, idx_offset, exclude_idx, tags, mask, value, K, out_scores, out_idx);
+    FERN_TRY(page_check(c, p, from_keys && out_scores && out_idx, K, 1024));
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    return for_query_chunks(c, s, B, p.chunk(), [&](long o, int mq) -> int {
+        const RankCall a = p.call.at(o);
+        ScoreRows r;
+        StageTimer st(c, s);
+        FERN_TRY(score_rows(c, a, mq, p.ld(), p.form(), st, s, &r));
+        FERN_TRY(select_under(a, mq, r, p.ld(), reinterpret_cast<const unsigned long long*>(from_keys) + o, s));
+        st.commit(mq, (int)N, D);
+        return FERN_OK;
+    });
+}
+
+extern "C" int fern_sim_topk_page(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D, int K,
+                                  const int32_t* offsets, float* out_scores, int32_t* out_idx, int64_t idx_offset, const int32_t* exclude_idx,
+                                  const uint32_t* tags, const uint32_t* mask, const uint32_t* value, void* stream) {
+    const PageCall p = page_call("fern_sim_topk_page", q, gallery, gallery_bf16, B, N, D, idx_offset, exclude_idx, tags, mask, value, K, out_scores, out_idx);
+    FERN_TRY(page_check(c, p, offsets && out_scores && out_idx, K, 1024));
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    return for_query_chunks(c, s, B, p.chunk(), [&](long o, int mq) -> int {
+        const RankCall a = p.call.at(o);
+        ScoreRows r;
+        unsigned long long* ceil;      // the key at place offsets[b]: 0 past the end of the ranking, which makes nothing eligible
+        StageTimer st(c, s);
+        FERN_TRY(score_rows(c, a, mq, p.ld(), p.form(), st, s, &r));
+        FERN_TRY(ws_get(c, (size_t)mq, &ceil));
+        FERN_TRY(select_places(c, a, mq, r, p.ld(), offsets + o, 1, 1, ceil, s));
+        FERN_TRY(select_under(a, mq, r, p.ld(), ceil, s));
+        st.commit(mq, (int)N, D);
+        return FERN_OK;
+    });
+}
+
 // ------------------------------------------------------------------------------------------------
 // image side: PIL-exact 8-bit resampling + ToTensor/Normalize
 // ------------------------------------------------------------------------------------------------

@@ -495,13 +495,28 @@ hipError_t launch_deep_exact_scores(const float* q, const float* gallery, int B,
 // Per query the top-K keys of its score row S[b] (ld % 4 == 0): bound from row-group maxima, collection, bitonic sort in LDS.  q != null:
 // S holds bf16-sweep approximations, the certified margin (meta = fern_gallery_prepare's) selects survivors that are rescored exactly from
 // the fp32 `gallery` (D % 64 == 0, D <= 768).  A query without room sets state[b] = 1 and flags[0] = 1 (flags[0] zeroed before).
+// ceil (device, [B], null: none): per query a ranking key with the GLOBAL row index; a row whose key make_key(score, n + idx_offset) is
+// greater than ceil[b] is treated exactly like a row scoring -inf, wherever the kernels form a row's key (margin 0 forms only: q == null).
 hipError_t launch_deep_select(const float* S, long ld, long N, int B, int K, const float* q, const float* meta, const float* gallery, int D,
-                              const int* exclude, long idx_offset, float* out_scores, int* out_idx, int* flags, int* state, hipStream_t s);
-// Gated on flags[0] / state[b]: the exact top-K of S[b] by radix select (no capacity).
+                              const int* exclude, long idx_offset, float* out_scores, int* out_idx, int* flags, int* state, hipStream_t s,
+                              const unsigned long long* ceil = nullptr);
+// Gated on flags[0] / state[b]: the exact top-K of S[b] by radix select (no capacity).  ceil: as above.
 hipError_t launch_deep_fallback(const float* S, long ld, long N, int B, int K, const int* exclude, long idx_offset, float* out_scores, int* out_idx,
-                                const int* flags, const int* state, hipStream_t s);
+                                const int* flags, const int* state, hipStream_t s, const unsigned long long* ceil = nullptr);
 // launch_topk_merge for 64 < K <= 1024, R * K <= 16 384.
 hipError_t launch_topk_merge_deep(const float* scores, const int* idx, float* out_scores, int* out_idx, int R, int B, int K, hipStream_t s);
+
+// ---- ranking pages (page.hip): the key at a place of a stored score row, any depth --------------------------------------------------------
+// Radix select over S [B, ld] (ld % 4 == 0), every query's row spread over many workgroups: out_keys[b * ostride + t] = the key
+// make_key(S[b][n], n + idx_offset) that holds the 0-based place places[b * pstride + t] of query b's ranking, t < nt <= SEL_T; 0 for a place
+// < 0 (clamp != 0: a negative place counts as 0) or past the rows that take a place.  Rows scoring -inf and the excluded row take none.
+// Workspace: states [9, B, SEL_T] (one set per digit level), hist [B, SEL_T, 8, 256], ZERO before the call and zero again after it,
+// found [B, SEL_T].  N >= 1.
+constexpr int SEL_T = 8;                      // places per walk of the row
+struct SelectState { unsigned long long prefix; unsigned need, flag; };      // digits fixed so far; the place among the keys that match them (0: no row); page.hip: SEL_*
+hipError_t launch_rank_select(const float* S, long ld, int B, long N, const int* places, int pstride, int nt, int clamp, const int* exclude,
+                              long idx_offset, SelectState* states, unsigned* hist, unsigned long long* found, unsigned long long* out_keys,
+                              long ostride, hipStream_t s);
 
 // ---- item-level ranking (items.hip): galleries whose rows belong to items -------------------------------------------------------------
 // Which rows of a stored score matrix S [B, ld] can represent an item, and under which key: row n of query b carries

@@ -209,8 +209,11 @@ __device__ __forceinline__ void sort_keys_desc(u64* keys, int n) {      // keys:
     else sort_lds_desc<NT, 16>(keys, n);
 }
 
+// CEIL: ceil[b] is a ranking key with the GLOBAL row index; a row whose key is greater is masked to -inf where the row is loaded, so the group
+// maxima, the collection and the fallback gate all see it as a row that takes no place (the fallback applies the same rule to its keys).
+template <bool CEIL>
 __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, long ld, long N, int K, DeepMargin mg, const int* exclude, long idx_offset,
-                                                              int cap, float* out_scores, int* out_idx, int* flags, int* state) {
+                                                              int cap, float* out_scores, int* out_idx, int* flags, int* state, const u64* ceil) {
     __shared__ __attribute__((aligned(16))) u64 ckey[DEEP_CAP];
     __shared__ unsigned surv[DEEP_CAP];
     __shared__ __attribute__((aligned(16))) float tiles[DEEP_WAVES * 2 * RESC_ROWS * RESC_TLD];
@@ -227,6 +230,7 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
         const long er = (long)exclude[b] - idx_offset;
         if (er >= 0 && er < N) drop = er;
     }
+    const u64 ck = CEIL ? ceil[b] : ~0ull;
     const long n4 = N & ~3L;
     constexpr long STEP = (long)DEEP_NT * 4 * DEEP_UB;
     // one batch: DEEP_UB unconditional loads on clamped addresses, then masked (positions past the row and the excluded row -> -inf)
@@ -243,6 +247,10 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[u][e] = in ? v[u][e] : -INFINITY;
             if (drop >= i && drop < i + 4) v[u][drop - i] = -INFINITY;
+            if constexpr (CEIL) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[u][e] = make_key(v[u][e], (unsigned)(i + e + idx_offset)) > ck ? -INFINITY : v[u][e];
+            }
         }
     };
     // pass 1: sixteen running maxima per thread (one per batch slot); the running sum turns NaN if any score is NaN
@@ -259,7 +267,8 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
         }
     }
     const bool has_tail = tid < (int)(N - n4) && n4 + tid != drop;
-    const float tail = has_tail ? row[n4 + tid] : -INFINITY;
+    float tail = has_tail ? row[n4 + tid] : -INFINITY;
+    if constexpr (CEIL) tail = make_key(tail, (unsigned)(n4 + tid + idx_offset)) > ck ? -INFINITY : tail;
     gmax[0] = fmaxf(gmax[0], tail);
     nsum += tail;
     const float margin = mg.q ? deep_margin(mg, b, fred) : 0.0f;
@@ -346,7 +355,7 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
 // wave and digit value); the K keys >= T are collected and sorted.  Rows scoring -inf (and the excluded row) take no place, as in the
 // selection kernel.
 __global__ __launch_bounds__(DEEP_NT) void deep_fallback_kernel(const float* S, long ld, long N, int K, const int* exclude, long idx_offset,
-                                                                float* out_scores, int* out_idx, const int* flags, const int* state) {
+                                                                float* out_scores, int* out_idx, const int* flags, const int* state, const u64* ceil) {
     if (flags[0] == 0 || state[blockIdx.x] == 0) return;
     __shared__ __attribute__((aligned(16))) u64 ckey[4 * DEEP_NT];      // >= 1024: the K keys
     __shared__ int hist[256];
@@ -360,6 +369,8 @@ __global__ __launch_bounds__(DEEP_NT) void deep_fallback_kernel(const float* S, 
         const long er = (long)exclude[b] - idx_offset;
         if (er >= 0 && er < N) drop = er;
     }
+    const u64 ck = ceil ? ceil[b] : ~0ull;          // a key with the global index: compared with the row's global key, never rebased
+    auto under = [&](float v, long n) { return !ceil || make_key(v, (unsigned)(n + idx_offset)) <= ck; };
     u64 prefix = 0, mask = 0;
     int need = K;
     for (int d = 7; d >= 0; --d) {
@@ -369,7 +380,7 @@ __global__ __launch_bounds__(DEEP_NT) void deep_fallback_kernel(const float* S, 
             const long n = n0 + tid;
             const float v = n < N ? row[n] : -INFINITY;
             const u64 key = make_key(v, (unsigned)n);
-            const bool match = n < N && n != drop && v != -INFINITY && (key & mask) == prefix;
+            const bool match = n < N && n != drop && v != -INFINITY && under(v, n) && (key & mask) == prefix;
             const int digit = (int)((key >> (8 * d)) & 255);
             const u64 m = __ballot(match);
             if (m) {
@@ -414,7 +425,7 @@ __global__ __launch_bounds__(DEEP_NT) void deep_fallback_kernel(const float* S, 
             const long n = n0 + tid;
             const float v = n < N ? row[n] : -INFINITY;
             const u64 key = make_key(v, (unsigned)n);
-            const bool hit = n < N && n != drop && v != -INFINITY && key >= prefix;
+            const bool hit = n < N && n != drop && v != -INFINITY && under(v, n) && key >= prefix;
             const u64 m = __ballot(hit);
             if (m) {
                 const int leader = __ffsll((long long)m) - 1;
@@ -471,23 +482,27 @@ hipError_t launch_deep_exact_scores(const float* q, const float* gallery, int B,
 }
 
 hipError_t launch_deep_select(const float* S, long ld, long N, int B, int K, const float* q, const float* meta, const float* gallery, int D,
-                              const int* exclude, long idx_offset, float* out_scores, int* out_idx, int* flags, int* state, hipStream_t s) {
+                              const int* exclude, long idx_offset, float* out_scores, int* out_idx, int* flags, int* state, hipStream_t s,
+                              const unsigned long long* ceil) {
     if (B <= 0) return hipSuccess;
-    if (K < 1 || K > 1024 || N < 0 || (ld & 3) || ld < N) return hipErrorInvalidValue;
+    if (K < 1 || K > 1024 || N < 0 || (ld & 3) || ld < N || (ceil && q)) return hipErrorInvalidValue;
     if (q && (!meta || !gallery || D < 64 || D % 64 || D > DEEP_MAX_D)) return hipErrorInvalidValue;
     // test hook: FERN_RANK_DEEP_CAP=c shrinks the collection capacity so that tests reach the fallback
     static const int cap_override = [] { const char* e = std::getenv("FERN_RANK_DEEP_CAP"); return e ? std::atoi(e) : 0; }();
     const int cap = cap_override >= 1 && cap_override <= DEEP_CAP ? cap_override : DEEP_CAP;
     const DeepMargin mg{q, meta, gallery, D};
-    FERN_LAUNCH(deep_select_kernel, dim3(B), dim3(DEEP_NT), 0, s, S, ld, N, K, mg, exclude, idx_offset, cap, out_scores, out_idx, flags, state);
+    if (ceil)
+        FERN_LAUNCH(deep_select_kernel<true>, dim3(B), dim3(DEEP_NT), 0, s, S, ld, N, K, mg, exclude, idx_offset, cap, out_scores, out_idx, flags, state, ceil);
+    else
+        FERN_LAUNCH(deep_select_kernel<false>, dim3(B), dim3(DEEP_NT), 0, s, S, ld, N, K, mg, exclude, idx_offset, cap, out_scores, out_idx, flags, state, ceil);
     return hipGetLastError();
 }
 
 hipError_t launch_deep_fallback(const float* S, long ld, long N, int B, int K, const int* exclude, long idx_offset, float* out_scores, int* out_idx,
-                                const int* flags, const int* state, hipStream_t s) {
+                                const int* flags, const int* state, hipStream_t s, const unsigned long long* ceil) {
     if (B <= 0) return hipSuccess;
     if (K < 1 || K > 1024 || N < 0 || ld < N) return hipErrorInvalidValue;
-    FERN_LAUNCH(deep_fallback_kernel, dim3(B), dim3(DEEP_NT), 0, s, S, ld, N, K, exclude, idx_offset, out_scores, out_idx, flags, state);
+    FERN_LAUNCH(deep_fallback_kernel, dim3(B), dim3(DEEP_NT), 0, s, S, ld, N, K, exclude, idx_offset, out_scores, out_idx, flags, state, ceil);
     return hipGetLastError();
 }
 

@@ -192,6 +192,26 @@ def rank_sharded(engine, queries: torch.Tensor, gallery_shard: torch.Tensor, sha
     return engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
 
 
+def rank_from_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: int, k: int, from_keys, exclude_idx=None, row_filter=None):
+    """Gallery-sharded CONTINUATION of a result list for the SAME query batch on every rank: `FernEngine.sim_topk_from` on the shard with
+    ``idx_offset = shard_start`` -- the cursor `from_keys` [B] carries a global row index, so every shard answers "my best k at or below
+    this key" whether or not it owns the cursor's row -- then the all-gather and merge of `rank_sharded`.  Returns the global
+    (scores, idx) on every rank; `engine.next_from` of it is the next cursor.  World 1 makes no collective.  `row_filter`: the SHARD's.
+    Random access by OFFSET on a sharded gallery is out of scope: a global select is not additive over shards (the key at a global
+    place is not a function of the shards' keys at any local places), so sharded callers page by cursor."""
+    rank, world = world_info()
+    kw = {} if row_filter is None else {"row_filter": row_filter}
+    s, i = engine.sim_topk_from(queries, gallery_shard, k, from_keys, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
+    if world == 1:
+        return s, i
+    b, kk = s.shape
+    all_s = torch.empty((world * b, kk), dtype=s.dtype, device=s.device)
+    all_i = torch.empty((world * b, kk), dtype=i.dtype, device=i.device)
+    _all_gather_into(all_s, s)
+    _all_gather_into(all_i, i)
+    return engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
+
+
 def route_rows(slots, bounds) -> List[np.ndarray]:
     """Host-side partition of a gallery UPDATE by owning shard.  `slots` [m] are global gallery rows (the slots of a sharded
     `live_gallery.LiveGallery`: shard r holds rows [bounds[r], bounds[r + 1]) and its store has ``slot_offset = bounds[r]``), `bounds`

@@ -156,6 +156,27 @@ class ItemMap:
         return self.items.to(device).contiguous()
 
 
+def ranking_keys(scores: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """int64 bits of the public 64-bit ranking key (include/fern.h: fern_rank_keys) of every slot of a top-K result:
+    ``orderable(score) << 32 | (0xFFFFFFFF - idx)`` with `idx` the global row index -- score descending, index ascending as one unsigned
+    compare.  An unfilled slot (idx < 0) gives 0.  Computed in torch on the result's device."""
+    bits = scores.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    order = torch.where(bits >= 0x80000000, bits ^ 0xFFFFFFFF, bits | 0x80000000)
+    gi = idx.to(torch.int64)
+    keys = (order << 32) | (0xFFFFFFFF - gi.clamp(min=0))
+    return torch.where(gi >= 0, keys, torch.zeros_like(keys))
+
+
+def next_from(scores: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """int64 [B]: the cursor of the page that follows the result (scores, idx) [B,k] -- what `FernEngine.sim_topk_from` takes as
+    `from_keys`: the key of the last FILLED place minus 1 (keys are unique per row, so nothing lies between them); 0, which makes
+    nothing eligible, when the page has no filled place."""
+    keys = ranking_keys(scores, idx)
+    filled = (idx >= 0).sum(dim=1)
+    last = keys.gather(1, (filled - 1).clamp(min=0)[:, None])[:, 0]
+    return torch.where(filled > 0, last - 1, torch.zeros_like(last))
+
+
 class FernEngine:
     """One native context on one GPU.  Not thread-safe (one per device per process)."""
 
@@ -595,6 +616,59 @@ class FernEngine:
             keys = torch.where(ok, keys, torch.zeros_like(keys))
         ranks = self.rank_count(q, gallery, keys, idx_offset, exclude_idx, row_filter)
         return ranks[:, 0] if flat else ranks
+
+    # ---- ranking pages ----------------------------------------------------------------------------
+    def _page_call(self, q, gallery, exclude_idx, row_filter):
+        """Shared argument handling of the page entry points: (q, g32, g16, n, exclude, (tags, mask, value))."""
+        q, g32, g16 = self._rank_forms(q, gallery)
+        g = g32 if g32 is not None else g16
+        b, n = q.shape[0], g.shape[0]
+        filt = (None, None, None)
+        if row_filter is not None:
+            if not isinstance(row_filter, RowFilter):
+                raise TypeError("row_filter must be a RowFilter")
+            filt = row_filter.resolve(b, n, self.device)
+        return q, g32, g16, n, self._exclude(exclude_idx, b), filt
+
+    def rank_select(self, q, gallery, places, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None) -> torch.Tensor:
+        """int64 [B,m] ([B] for flat `places`): the bits of the ranking key of the row at each 0-based place of the ordering `sim_topk`
+        defines, at any depth (include/fern.h: fern_rank_select) -- the inverse of `rank_count`; 0 for a place < 0 or past the rows that
+        take a place.  `gallery`: an fp32 tensor or a `PreparedGallery` (exact fp32-chain scores) or a bf16 tensor."""
+        flat = torch.as_tensor(places).dim() == 1
+        q, g32, g16, n, ex, (tags, mask, value) = self._page_call(q, gallery, exclude_idx, row_filter)
+        pl = self._per_query(places, q.shape[0], torch.int32, "places")
+        keys = self._empty(*pl.shape, dtype=torch.int64)
+        _lib.check(self.lib.fern_rank_select(self._h, _ptr(q), _ptr(g32), _ptr(g16), q.shape[0], n, q.shape[1], _ptr(pl), pl.shape[1],
+                                             int(idx_offset), _ptr(ex), _ptr(keys), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_rank_select")
+        return keys[:, 0] if flat else keys
+
+    def sim_topk_from(self, q, gallery, k: int, from_keys, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
+        """(scores, idx) [B,k]: the exact top-K, 1 <= k <= 1024, among the rows whose ranking key is <= `from_keys` [B] (int64 bits; a
+        cursor from `next_from`, -1 = everything, 0 = nothing) -- include/fern.h: fern_sim_topk_from.  The cursor carries a GLOBAL row
+        index, so the same cursor continues the list on every shard of a gallery (`idx_offset`)."""
+        q, g32, g16, n, ex, (tags, mask, value) = self._page_call(q, gallery, exclude_idx, row_filter)
+        b = q.shape[0]
+        fk = torch.as_tensor(from_keys).to(device=self.device, dtype=torch.int64).contiguous()
+        if tuple(fk.shape) != (b,):
+            raise ValueError("from_keys must be [B]")
+        scores, idx = self._topk_out(b, k)
+        _lib.check(self.lib.fern_sim_topk_from(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, n, q.shape[1], int(k), _ptr(fk), _ptr(scores), _ptr(idx),
+                                               int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_sim_topk_from")
+        return scores, idx
+
+    def rank_page(self, q, gallery, offset, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
+        """(scores, idx) [B,k]: places [offset, offset + k) of every query's ranking, at any depth (include/fern.h: fern_sim_topk_page);
+        `offset` an int or [B]; slots past the end -inf / -1.  offset 0 is `sim_topk_deep`."""
+        q, g32, g16, n, ex, (tags, mask, value) = self._page_call(q, gallery, exclude_idx, row_filter)
+        b = q.shape[0]
+        off = torch.as_tensor(offset).to(device=self.device, dtype=torch.int32)
+        off = off.expand(b).contiguous() if off.dim() == 0 else off.contiguous()
+        if tuple(off.shape) != (b,):
+            raise ValueError("offset must be an int or [B]")
+        scores, idx = self._topk_out(b, k)
+        _lib.check(self.lib.fern_sim_topk_page(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, n, q.shape[1], int(k), _ptr(off), _ptr(scores), _ptr(idx),
+                                               int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_sim_topk_page")
+        return scores, idx
 
     # ---- item-level ranking -----------------------------------------------------------------------
     def _item_call(self, q, gallery, items, exclude_idx, row_filter):

@@ -134,6 +134,10 @@ def build_parser(kind: str) -> ArgumentParser:
                    help="build every gallery the way a serving process grows one: fuse the index in chunks of ROWS rows and append each to a "
                         "LiveGallery (in-place upserts into a store of capacity N) instead of fusing and preparing it in one piece -- the same "
                         "gallery bytes, the same numbers; single process only")
+    p.add_argument("--dump-ranking", type=int, default=0, metavar="DEPTH",
+                   help="after the recalls also write the first DEPTH gallery rows of every query's full ranking (any depth; -1 past the end) "
+                        "as ranking_<split>.npy, int32 [Q, DEPTH], into --dump-dir")
+    p.add_argument("--dump-dir", type=str, default=".", help="where --dump-ranking writes")
     p.add_argument("--force-quick-gelu", action="store_true",
                    help="QuickGELU, x * sigmoid(1.702 x), in both CLIP towers' MLPs: open_clip's force_quick_gelu, what it turns on for "
                         "pretrained='openai' -- needed for OpenAI's checkpoints (RN50x4's only public weights); default: the config's own "
@@ -174,6 +178,8 @@ def _evaluate(kind, args, triples, clip_model, model, device, fn, say):
     if getattr(args, "merged_gallery", False):
         if args.rank_metrics:
             raise SystemExit("--rank-metrics is not available with --merged-gallery")
+        if args.dump_ranking:
+            raise SystemExit("--dump-ranking is not available with --merged-gallery")
         results = merged_category_metrics(kind, triples, clip_model, model, device, args)
         for (split, _, _), res in zip(triples, results):
             say(split, "recalls:", res)
@@ -193,6 +199,15 @@ def _evaluate(kind, args, triples, clip_model, model, device, fn, say):
                 raise SystemExit(f"--rank-metrics is not available for {kind}")
             say(split, "rank metrics:", rank_fn(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size,
                                                args.num_workers, args.clip_model_name))
+        if args.dump_ranking:
+            from . import rank_metrics as _rd
+            ranking = _rd.ranking_dump(kind, relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size,
+                                       args.num_workers, args.clip_model_name, args.dump_ranking)
+            if fd.world_info()[0] == 0:
+                os.makedirs(args.dump_dir, exist_ok=True)
+                path = os.path.join(args.dump_dir, f"ranking_{split}.npy")
+                np.save(path, ranking)
+                say(split, "ranking to depth %d:" % args.dump_ranking, path)
         if getattr(args, "item_level", False):
             from . import rank_metrics as _rm
             res_items = _rm.compute_200k_item_metrics(relative, clip_model, feats, local, names, model, device, args.feature_dim, args.batch_size,

@@ -29,6 +29,7 @@ import torch
 from torch.utils.data import DataLoader, Subset
 
 from .. import distributed as fd
+from ..engine import next_from
 from ..tokenizer import get_tokenizer
 from ..utils import collate_fn, host_threads, make_loader
 
@@ -448,6 +449,28 @@ def target_ranks(model, predicted, index_fused, rows, exclude=None, row_filter=N
         block[: stop - start] = ranks
         ranks = fd.all_gather_shards(block, q)
     return ranks.cpu().numpy()
+
+
+def ranking_to_depth(engine, pred, fused, depth: int, page: int = 1024, exclude_idx=None, row_filter=None) -> np.ndarray:
+    """The first `depth` gallery rows of every query's full ranking as a host int32 array [Q, depth], -1 past the end of a ranking --
+    the columns of the reference's argsort (test_fiq.py:49-50; what utils/visualize.py and sorted_index_names read) to any depth.
+    Filled by CURSOR pages of at most `page` <= 1024 places (FernEngine.sim_topk_from + `engine.next_from`): every page continues
+    where the previous one ended, nothing is sorted twice and no [Q, N] matrix is formed.  `exclude_idx` / `row_filter` as in `_ranked`."""
+    if depth < 1 or not 1 <= page <= 1024:
+        raise ValueError("ranking_to_depth needs depth >= 1 and 1 <= page <= 1024")
+    q = pred.shape[0]
+    out = np.full((q, depth), -1, dtype=np.int32)
+    ex = None if exclude_idx is None else torch.as_tensor(exclude_idx, dtype=torch.int32)
+    kw = {} if row_filter is None else {"row_filter": row_filter}
+    cursor = torch.full((q,), -1, dtype=torch.int64)          # all ones: everything is eligible
+    for lo in range(0, depth, page):
+        k = min(page, depth - lo)
+        scores, idx = engine.sim_topk_from(pred, fused, k, cursor, exclude_idx=ex, **kw)
+        cursor = next_from(scores, idx)
+        out[:, lo:lo + k] = idx.cpu().numpy()
+    if hasattr(engine, "sync"):
+        engine.sync()
+    return out
 
 
 def retrieval_metrics(ranks, ks) -> Dict[str, float]:

@@ -60,3 +60,15 @@ def compute_200k_item_metrics(relative_val_dataset, clip_model, index_features, 
                                                                       device, feature_dim, batch_size, num_workers, clip_model_name)
     index_fused = _common.fuse_index(model, index_features, index_local_features, prepared=True)
     return _common.recalls_items(model, predicted, index_fused, index_names, target_names, ks)
+
+
+def ranking_dump(kind, relative_val_dataset, clip_model, index_features, index_local_features, index_names, model, device, feature_dim,
+                 batch_size, num_workers, clip_model_name, depth: int) -> np.ndarray:
+    """--dump-ranking: the first `depth` gallery rows of every query's full ranking, int32 [Q, depth] with -1 past the end
+    (`_common.ranking_to_depth`) -- the reference's sorted_index_names (test_fiq.py:49-51) as row numbers, to any depth.  CIRR's
+    rankings are without the query's reference image (test_cirr.py:55-62)."""
+    out = _common.generate_predictions(kind, clip_model, relative_val_dataset, model, index_names, index_features, device, feature_dim,
+                                       batch_size, num_workers, clip_model_name)
+    index_fused = _common.fuse_index(model, index_features, index_local_features, prepared=True)
+    ex = _common._unique_rows(index_names, out["references"], "reference").astype(np.int32) if kind == "cirr" else None
+    return _common.ranking_to_depth(_common._engine_of(model), out["predicted"], index_fused, depth, exclude_idx=ex)

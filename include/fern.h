@@ -414,6 +414,44 @@ FERN_API int fern_rank_count_filtered(fern_ctx* ctx, const float* q /*[B,D]*/, c
                                       const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const uint64_t* keys /*[B,m]*/,
                                       int m, int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/, int32_t* out_count /*[B,m]*/,
                                       const uint32_t* tags /*[N]*/, const uint32_t* mask /*[B]*/, const uint32_t* value /*[B]*/, void* stream);
+/* Ranking pages: the rows at places [offset, offset + K) of a query's ranking, at any depth.  The reference's full argsort of 1 - q @ g.T
+ * (run/test/test_fiq.py:49-50) answers two questions about every place: which place a named row holds -- fern_rank_keys + fern_rank_count
+ * above -- and which row holds a place, which the top-K entry points answer for places 0 .. 1023 only.  These three answer the second
+ * question at any depth, without forming a sorted [B, N] matrix: a radix select over the stored score rows of a query chunk finds the
+ * ranking KEY at a place (at most eight passes over a row, every row spread over many workgroups, no capacity, deterministic: each digit is
+ * picked from a summed integer histogram), and the deep stage's selection takes a per-query key CEILING: rows whose key is greater take no place.
+ * They follow the contract of the ranks and item entry points: asynchronous on `stream`, nothing read back, graph-capturable after one
+ * warm-up call; the gallery form follows from the pointers: `gallery` given: the exact fp32 fma-chain scores in oracle/chain.c order
+ * (gallery_bf16 is ignored), D % 32 == 0; gallery_bf16 only: the values fern_sweep_bf16_scores produces, D % 64 == 0, D <= 768.  There is no
+ * certified pre-filtered form: whether a row's exact key lies at or below a ceiling cannot be decided from an approximate score within
+ * eps_b of it.  tags == NULL: unfiltered (mask / value ignored); otherwise fern_sim_topk_filtered's predicate.  idx_offset / exclude_idx
+ * as everywhere else; rows scoring -inf, the excluded row and ineligible rows take no place.  Queries are processed in chunks whose [m, N]
+ * fp32 score rows stay inside the deep stage's 1.1 GB workspace; a single query that does not fit is an argument error.
+ * fern_rank_select: out_keys[b][j] = the ranking key (orderable(score) << 32 | ~global_index) of the row at 0-based place places[b][j] of
+ *     query b's ranking; 0 when the place is < 0 or at or past the number of rows that take a place.  The inverse of fern_rank_count: on
+ *     finite scores fern_rank_count of a returned key is the place asked for, and the key equals fern_rank_keys of the row at that place
+ *     bit for bit.  Any m >= 1: one walk of a row serves 8 places. */
+FERN_API int fern_rank_select(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                              const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const int32_t* places /*[B,m]*/, int m,
+                              int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/, uint64_t* out_keys /*[B,m]*/,
+                              const uint32_t* tags /*[N] or NULL*/, const uint32_t* mask /*[B]*/, const uint32_t* value /*[B]*/, void* stream);
+/* fern_sim_topk_from: the exact top-K, 1 <= K <= 1024, among the rows whose ranking key is <= from_keys[b] (device): a result list continued
+ *     from a cursor.  A key of 0 makes nothing eligible (every slot -inf / -1); ~0 makes everything eligible, and the result is then
+ *     fern_sim_topk_deep's (with tags: fern_sim_topk_filtered's) bit for bit.  The key carries the GLOBAL row index, which need not belong
+ *     to this gallery (shard): rows are compared as (orderable(score), ~(n + idx_offset)) against the 64-bit key, the ceiling is never
+ *     rebased by idx_offset into 32 bits.  So every shard answers "my best K at or below this key" and fern_topk_merge merges the answers.
+ *     The cursor of the page after a result is (the key of its last filled place) - 1: keys are unique per row. */
+FERN_API int fern_sim_topk_from(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                                const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, int K, const uint64_t* from_keys /*[B]*/,
+                                float* out_scores /*[B,K]*/, int32_t* out_idx /*[B,K]*/, int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/,
+                                const uint32_t* tags /*[N] or NULL*/, const uint32_t* mask /*[B]*/, const uint32_t* value /*[B]*/, void* stream);
+/* fern_sim_topk_page: places [offsets[b], offsets[b] + K) of query b (offsets int32, device; a negative offset counts as 0), 1 <= K <= 1024;
+ *     slots past the end of the ranking are -inf / -1.  The fused form: a chunk's score rows are computed once, the select writes the key at
+ *     place offsets[b] into workspace and the ceilinged selection runs on the same rows.  offset 0 gives fern_sim_topk_deep's bits. */
+FERN_API int fern_sim_topk_page(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                                const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, int K, const int32_t* offsets /*[B]*/,
+                                float* out_scores /*[B,K]*/, int32_t* out_idx /*[B,K]*/, int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/,
+                                const uint32_t* tags /*[N] or NULL*/, const uint32_t* mask /*[B]*/, const uint32_t* value /*[B]*/, void* stream);
 /* Item-level ranking: galleries whose rows belong to items.  The reference's galleries are not all made of distinct rows: in Fashion200k
  * the gallery name of an image is its caption (dataloader/fashion200k_patch.py:282-290), index_names holds many duplicates and
  * run/test/test_200k.py:52-60 scores "any row with the target's name"; a product with several photographs is the same case.  Here the
