@@ -77,4 +77,16 @@ __device__ __forceinline__ float rescore_rows(const unsigned* surv, int s0, int 
     return acc;
 }
 
+// One round of one wave: the exact chains of surv[s0 .. s0 + 32) with the deepest ring D allows, stored as ranking keys keys[s0 ..].
+__device__ __forceinline__ void rescore_keys(const unsigned* surv, int s0, int ns, const float* qrow, const float* gallery, int D, float* tl,
+                                             unsigned long long* keys) {
+    const int lane = threadIdx.x & 63, nsteps = D / RESC_CH;
+    float acc;
+    if (nsteps % 8 == 0) acc = rescore_rows<8>(surv, s0, ns, qrow, gallery, D, tl);
+    else if (nsteps % 10 == 0) acc = rescore_rows<10>(surv, s0, ns, qrow, gallery, D, tl);      // D = 640 (RN50x4): 20 steps, 40 loads in flight
+    else if (nsteps % 4 == 0) acc = rescore_rows<4>(surv, s0, ns, qrow, gallery, D, tl);
+    else acc = rescore_rows<2>(surv, s0, ns, qrow, gallery, D, tl);
+    if (lane < RESC_ROWS && s0 + lane < ns) keys[s0 + lane] = make_key(acc, surv[s0 + lane]);
+}
+
 }  // namespace fern

@@ -14,13 +14,11 @@
 // (topk_sample_bound_kernel) and select the exact top-K from the lists (topk_candidates_kernel).  kernels.h: TopkFilter.
 #include "kernels.h"
 #include "rescore.h"
+#include "select.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace fern {
-
-typedef unsigned long long u64;
 
 // Cross-lane moves without the LDS crossbar: a wave-uniform source lane is a v_readlane_b32 (SGPR lane select), the
 // shift-by-one of the sorted list is a DPP wave_shr:1 move.  ds_bpermute-based __shfl made every insertion a chain of
@@ -115,16 +113,7 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const float* scores, con
         }
         wave_offer(best, cand, K, lane);
     }
-    if (lane < K) {
-        float s = -INFINITY;
-        int gi = -1;
-        if (best != 0) {
-            s = unorderable((unsigned)(best >> 32));
-            gi = (int)(0xFFFFFFFFu - (unsigned)best);
-        }
-        out_scores[(long)b * K + lane] = s;
-        out_idx[(long)b * K + lane] = gi;
-    }
+    if (lane < K) write_key(best, 0, out_scores + (long)b * K + lane, out_idx + (long)b * K + lane);
 }
 
 // ---- fused sweep + selection (kernels.h: TopkFilter) -----------------------------------------------------------------
@@ -327,44 +316,15 @@ __device__ __forceinline__ u64 select_kth_largest(const unsigned (&h)[PER], LoOf
 // the real row.  Fewer than K sample rows -> bound 0 (accept all).  Also resets the query's list counters.
 // NT threads: 256 (four waves: a barrier among them is a fraction of the 16-wave one, and a bisection step is mostly barrier) for
 // samples of <= 4096 rows, 1024 for the larger ones (registers: PER keys per thread).
-// Pre-filter form (margin.q != null; api.hip: fern_sim_topk_prefiltered): the sample scores are the bf16 sweep's APPROXIMATIONS s~ of
-// the exact fp32 scores s.  With q~ = bf16(q), g~ = bf16(g):  s - s~ = q.(g - g~) + (q - q~).g~  (+ the two accumulations' rounding), so
-//     |s - s~| <= eps_b = ||q_b|| E + ||q_b - q~_b|| G~ + slack,   E = max_n ||g_n - g~_n||, G~ = max_n ||g~_n||   (Cauchy-Schwarz)
-// for EVERY gallery row -- E, G~, G = max ||g_n|| come from fern_gallery_prepare, the query's two norms are computed here.  If T~ is
-// the K-th best approximate score of the whole gallery, every row of the exact top-K has s~ >= T~ - 2 eps (K rows have s >= T~ - eps,
-// so the exact K-th best is >= T~ - eps, and a row at or above it has s~ >= s - eps).  The sample's K-th best is <= T~, so the bound
-// published for the sweep is (sample K-th best) - margin, margin = 2 eps_b, as a key with the lowest index part; margin_out[b] keeps
-// the margin for the rescoring kernel.  slack covers fp32 accumulation in both dot products (D 2^-21 ||q|| max(G, G~): four times
-// the textbook D u bound each, the MFMA's internal adder tree is not specified) and the rounding of the norms themselves.
+// Pre-filter form (margin.q != null; api.hip: fern_sim_topk_prefiltered): the sample scores are the bf16 sweep's approximations, and the
+// sample's K-th best is <= T~ (select.h has the argument), so the bound published for the sweep is (sample K-th best) - margin as a key
+// with the lowest index part; margin_out[b] keeps the margin for the rescoring kernel.
 struct BoundMargin {
     const float* q;          // [B, D] fp32 queries (null: no margin -- the sample scores ARE the ranking scores)
     int D;
     const float* meta;       // fern_gallery_prepare: {E, G~, G}
     float* margin_out;       // [B]
 };
-template <int NT>
-__device__ __forceinline__ float bound_margin_of(const BoundMargin& m, int b, float* fred) {
-    const int tid = threadIdx.x;
-    float a = 0.f, e = 0.f;
-    for (int i = tid; i < m.D; i += NT) {
-        const float v = m.q[(long)b * m.D + i];
-        const float d = v - bf16_bits_to_f32(f32_to_bf16_bits(v));      // exact
-        a += v * v;
-        e += d * d;
-    }
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) { a += __shfl_xor(a, x); e += __shfl_xor(e, x); }
-    if ((tid & 63) == 0) { fred[tid >> 6] = a; fred[NT / 64 + (tid >> 6)] = e; }
-    __syncthreads();
-    a = 0.f; e = 0.f;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) { a += fred[w]; e += fred[NT / 64 + w]; }
-    __syncthreads();
-    const float nq = sqrtf(a), eq = sqrtf(e);
-    const float E = m.meta[0], Gt = m.meta[1], G = m.meta[2];
-    const float eps = (nq * E + eq * Gt) * 1.00390625f + (float)m.D * 4.76837158203125e-7f * nq * fmaxf(G, Gt);      // (1 + 2^-8); D 2^-21
-    return 2.0f * eps * 1.0009765625f;      // NaN (a NaN / inf row or query) makes every compare below accept: the exact pass sorts it out
-}
 
 template <int PER, int NT>
 __global__ __launch_bounds__(NT) void topk_sample_bound_kernel(const float* scores, long ld, long S, int R, int K, const int* exclude,
@@ -375,8 +335,9 @@ __global__ __launch_bounds__(NT) void topk_sample_bound_kernel(const float* scor
     const float* row = scores + (long)b * ld;
     float margin = 0.f;
     if (mg.q) {
-        margin = bound_margin_of<NT>(mg, b, reinterpret_cast<float*>(red));
+        margin = margin_finish<NT / 64>(margin_accumulate<NT>(mg.q + (long)b * mg.D, mg.D), mg.D, mg.meta, reinterpret_cast<float*>(red));
         if (tid == 0) mg.margin_out[b] = margin;
+        __syncthreads();                                 // the selection below reuses red
     }
     // sample column of the excluded gallery row (if it was sampled at all): it must not count towards the K rows of the bound
     long drop = -1;
@@ -417,40 +378,48 @@ __global__ __launch_bounds__(NT) void topk_sample_bound_kernel(const float* scor
 // candidates (lists near full) take the streaming path.
 constexpr int CAND_PER = 24;                    // keys per thread
 constexpr int CAND_MAX = CAND_PER * 256;        // 6144 keys x 8 bytes of LDS
-__global__ __launch_bounds__(256) void topk_candidates_kernel(TopkFilter f, int K, long idx_offset, float* out_scores, int* out_idx,
-                                                              int* flags, int* state) {
-    __shared__ u64 c_key[CAND_MAX];
-    __shared__ int red[32];
-    __shared__ u64 lists[4][64];
-    __shared__ int wtotal[4], over[4], nsel;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int cnt_raw = f.count[(long)b * RANK_SLOTS + tid];      // thread t owns list t
-    const int cnt = cnt_raw < f.cap ? cnt_raw : f.cap;
-    const bool overflow_w = __any(cnt_raw > f.cap);
-    const int incl = wave_inclusive_sum(cnt, lane);
-    if (lane == 63) { wtotal[wave] = incl; over[wave] = overflow_w ? 1 : 0; }
-    if (tid == 0) nsel = 0;
-    __syncthreads();
-    if ((over[0] | over[1] | over[2] | over[3]) != 0) {
-        // More rows reached the sampled bound than a list holds (a sample that missed a cluster of good rows, a gallery of
-        // near-ties): this query goes to the exact pass (rank_exact_kernel), which has no capacity anywhere.
-        if (tid == 0) { state[b] = 1; flags[0] = 1; }
-        return;
+// A query's candidate lists -> the 256 threads' registers, for both select kernels.  Thread t owns list t.
+//   begin   the list's count (clamped to the capacity), the wave's overflow vote and prefix sum -> wtotal / over (LDS; the caller's barrier
+//           follows).  SPEC > 0: the list's first SPEC entries are requested together with its count (entries past the count are stale
+//           and dropped later): one round trip instead of two for the ~K R / 256 entries a list typically holds;
+//   overflow / total   after that barrier.  overflow: more rows reached the sampled bound than a list holds (a sample that missed a
+//           cluster of good rows, a gallery of near-ties) -- the query goes to the exact pass (rank_exact_kernel: no capacity anywhere);
+//   finish  (total <= CAND_MAX) every thread walks ITS list, eight independent loads in flight per round -- lists hold ~K * R / 256 <= 16
+//           keys, so this is one or two round trips -- and drops the keys at its prefix-sum offset in c_key; then the keys are dealt
+//           round-robin: mine[j] = key tid + 256 j (0 past the total), h[j] its score word.  One barrier inside, none behind.
+template <int SPEC>
+struct CandGather {
+    const u64* mylist;
+    const int *wtotal, *over;
+    u64 first[SPEC > 0 ? SPEC : 1];
+    int cnt, incl;
+    __device__ __forceinline__ void begin(const TopkFilter& f, int b, int* wtotal_s, int* over_s) {
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        mylist = f.cand + ((long)b * RANK_SLOTS + tid) * f.cap;
+        wtotal = wtotal_s;
+        over = over_s;
+#pragma unroll
+        for (int u = 0; u < SPEC; ++u) first[u] = u < f.cap ? mylist[u] : 0;
+        const int cnt_raw = f.count[(long)b * RANK_SLOTS + tid];
+        cnt = cnt_raw < f.cap ? cnt_raw : f.cap;
+        const bool overflow_w = __any(cnt_raw > f.cap);
+        incl = wave_inclusive_sum(cnt, lane);
+        if (lane == 63) { wtotal_s[wave] = incl; over_s[wave] = overflow_w ? 1 : 0; }
     }
-    int base = incl - cnt;
-    for (int w = 0; w < wave; ++w) base += wtotal[w];
-    const int total = wtotal[0] + wtotal[1] + wtotal[2] + wtotal[3];
-    const u64* cand = f.cand + (long)b * RANK_SLOTS * f.cap;
-    u64 best = 0;                                        // wave 0 ends up with the sorted top-64 (lane i = i-th best)
-    if (total <= CAND_MAX) {
-        // gather: every thread walks ITS list (thread t = list t), eight independent loads in flight per round -- lists hold
-        // ~K * R / 256 <= 16 keys, so this is one or two round trips -- and drops the keys at its prefix-sum offset in LDS
+    __device__ __forceinline__ bool overflow() const { return (over[0] | over[1] | over[2] | over[3]) != 0; }
+    __device__ __forceinline__ int total() const { return wtotal[0] + wtotal[1] + wtotal[2] + wtotal[3]; }
+    __device__ __forceinline__ void finish(u64* c_key, int total, u64 (&mine)[CAND_PER], unsigned (&h)[CAND_PER]) const {
+        const int tid = threadIdx.x, wave = tid >> 6;
+        int base = incl - cnt;
+        for (int w = 0; w < wave; ++w) base += wtotal[w];
+#pragma unroll
+        for (int u = 0; u < SPEC; ++u)
+            if (u < cnt) c_key[base + u] = first[u];
         int maxc = cnt;
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(maxc, m); maxc = o > maxc ? o : maxc; }
-        const u64* mylist = cand + (long)tid * f.cap;
 #pragma unroll 1
-        for (int e0 = 0; e0 < maxc; e0 += 8) {
+        for (int e0 = SPEC; e0 < maxc; e0 += 8) {
             u64 key[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) key[u] = e0 + u < cnt ? mylist[e0 + u] : 0;
@@ -459,14 +428,36 @@ __global__ __launch_bounds__(256) void topk_candidates_kernel(TopkFilter f, int 
                 if (e0 + u < cnt) c_key[base + e0 + u] = key[u];
         }
         __syncthreads();
-        u64 mine[CAND_PER];
-        unsigned h[CAND_PER];
 #pragma unroll
         for (int j = 0; j < CAND_PER; ++j) {
             const int i = tid + 256 * j;
             mine[j] = i < total ? c_key[i] : 0;
             h[j] = (unsigned)(mine[j] >> 32);
         }
+    }
+};
+
+__global__ __launch_bounds__(256) void topk_candidates_kernel(TopkFilter f, int K, long idx_offset, float* out_scores, int* out_idx,
+                                                              int* flags, int* state) {
+    __shared__ u64 c_key[CAND_MAX];
+    __shared__ int red[32];
+    __shared__ u64 lists[4][64];
+    __shared__ int wtotal[4], over[4], nsel;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    CandGather<0> gather;                                // (no speculative loads here)
+    gather.begin(f, b, wtotal, over);
+    if (tid == 0) nsel = 0;
+    __syncthreads();
+    if (gather.overflow()) {
+        if (tid == 0) { state[b] = 1; flags[0] = 1; }
+        return;
+    }
+    const int total = gather.total();
+    u64 best = 0;                                        // wave 0 ends up with the sorted top-64 (lane i = i-th best)
+    if (total <= CAND_MAX) {
+        u64 mine[CAND_PER];
+        unsigned h[CAND_PER];
+        gather.finish(c_key, total, mine, h);
         const int want = total < K ? total : K;          // fewer candidates than K: all of them rank
         u64 kth = 0;
         __syncthreads();                                 // every thread holds its keys in registers: c_key's head becomes the fast path's compact list
@@ -484,9 +475,10 @@ __global__ __launch_bounds__(256) void topk_candidates_kernel(TopkFilter f, int 
         best = sort64_desc(lane < ns ? lists[0][lane] : 0, lane);
     } else {
         // streaming path (lists near full: > CAND_MAX candidates): the sorted wave lists of wave_offer
+        const u64* cand = f.cand + (long)b * RANK_SLOTS * f.cap;
 #pragma unroll 1
         for (int j = 0; j < 64; ++j) {
-            const int n = __builtin_amdgcn_readlane(cnt, j);
+            const int n = __builtin_amdgcn_readlane(gather.cnt, j);
             wave_offer(best, lane < n ? cand[(long)(wave * 64 + j) * f.cap + lane] : 0, K, lane);
         }
         lists[wave][lane] = best;
@@ -495,16 +487,7 @@ __global__ __launch_bounds__(256) void topk_candidates_kernel(TopkFilter f, int 
 #pragma unroll 1
         for (int w = 1; w < 4; ++w) best = merge_sorted_desc(best, lists[w][lane], lane);
     }
-    if (lane < K) {
-        float sc = -INFINITY;
-        int idx = -1;
-        if (best != 0) {
-            sc = unorderable((unsigned)(best >> 32));
-            idx = (int)((long)(0xFFFFFFFFu - (unsigned)best) + idx_offset);
-        }
-        out_scores[(long)b * K + lane] = sc;
-        out_idx[(long)b * K + lane] = idx;
-    }
+    if (lane < K) write_key(best, idx_offset, out_scores + (long)b * K + lane, out_idx + (long)b * K + lane);
 }
 
 // ---- certified pre-filter: select on the approximate keys, then rescore the survivors exactly ---------------------------------------
@@ -532,17 +515,9 @@ constexpr int RESC_TILE_FLOATS = 4 * 2 * RESC_ROWS * RESC_TLD;      // the four 
 // second selection, no sort.  D % 64 == 0.
 __device__ __forceinline__ void rescore_and_rank(const unsigned* surv, int ns, const float* qrow, const float* gallery, int D, float* tiles,
                                                  u64* x_key, int K, long idx_offset, float* out_scores, int* out_idx) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, wave = tid >> 6;
     float* tl = tiles + wave * (2 * RESC_ROWS * RESC_TLD);
-    const int nsteps = D / RESC_CH;
-    for (int s0 = wave * RESC_ROWS; s0 < ns; s0 += 4 * RESC_ROWS) {
-        float acc;
-        if (nsteps % 8 == 0) acc = rescore_rows<8>(surv, s0, ns, qrow, gallery, D, tl);
-        else if (nsteps % 10 == 0) acc = rescore_rows<10>(surv, s0, ns, qrow, gallery, D, tl);      // D = 640 (RN50x4): 20 steps, 40 loads in flight
-        else if (nsteps % 4 == 0) acc = rescore_rows<4>(surv, s0, ns, qrow, gallery, D, tl);
-        else acc = rescore_rows<2>(surv, s0, ns, qrow, gallery, D, tl);
-        if (lane < RESC_ROWS && s0 + lane < ns) x_key[s0 + lane] = make_key(acc, surv[s0 + lane]);
-    }
+    for (int s0 = wave * RESC_ROWS; s0 < ns; s0 += 4 * RESC_ROWS) rescore_keys(surv, s0, ns, qrow, gallery, D, tl, x_key);
     if (tid < 4) x_key[ns + tid] = 0;                // the counting loop reads four keys at a time: zeros never count (x_key holds RESC_MAX + 4)
     __syncthreads();
     // rank by counting: keys are distinct (the index is part of the key); four keys per pair of LDS reads
@@ -553,12 +528,9 @@ __device__ __forceinline__ void rescore_and_rank(const unsigned* surv, int ns, c
             const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(x_key + j0), c = *reinterpret_cast<const ulonglong2*>(x_key + j0 + 2);
             rank += (a.x > key) + (a.y > key) + (c.x > key) + (c.y > key);
         }
-        if (rank < K) {
-            out_scores[rank] = unorderable((unsigned)(key >> 32));
-            out_idx[rank] = (int)((long)(0xFFFFFFFFu - (unsigned)key) + idx_offset);
-        }
+        if (rank < K) write_row(key, idx_offset, out_scores + rank, out_idx + rank);
     }
-    for (int r = ns + tid; r < K; r += 256) { out_scores[r] = -INFINITY; out_idx[r] = -1; }      // fewer survivors than K: the gallery ran out
+    for (int r = ns + tid; r < K; r += 256) write_key(0, idx_offset, out_scores + r, out_idx + r);      // fewer survivors than K: the gallery ran out
 }
 
 static_assert(RESC_TILE_FLOATS * 4 <= CAND_MAX * 8, "the four waves' (double-buffered) tiles overlay the candidate keys");
@@ -570,55 +542,20 @@ __global__ __launch_bounds__(256) void topk_rescore_kernel(TopkFilter f, const f
     __shared__ __attribute__((aligned(16))) float qrow[1024];
     __shared__ int red[32];
     __shared__ int wtotal[4], over[4], nsurv;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u64* mylist = f.cand + ((long)b * RANK_SLOTS + tid) * f.cap;      // thread t owns list t
-    // the list's first entries are requested together with its count (entries past the count are stale and dropped below): one
-    // round trip instead of two for the ~K R / 256 entries a list typically holds
-    constexpr int SPEC = 8;
-    u64 first[SPEC];
-#pragma unroll
-    for (int u = 0; u < SPEC; ++u) first[u] = u < f.cap ? mylist[u] : 0;
-    const int cnt_raw = f.count[(long)b * RANK_SLOTS + tid];
-    const int cnt = cnt_raw < f.cap ? cnt_raw : f.cap;
-    const bool overflow_w = __any(cnt_raw > f.cap);
-    const int incl = wave_inclusive_sum(cnt, lane);
-    if (lane == 63) { wtotal[wave] = incl; over[wave] = overflow_w ? 1 : 0; }
+    const int b = blockIdx.x, tid = threadIdx.x;
+    CandGather<8> gather;
+    gather.begin(f, b, wtotal, over);
     if (tid == 0) nsurv = 0;
     for (int i = tid; i < D; i += 256) qrow[i] = q[(long)b * D + i];
     __syncthreads();
-    const int total = wtotal[0] + wtotal[1] + wtotal[2] + wtotal[3];
-    if ((over[0] | over[1] | over[2] | over[3]) != 0 || total > CAND_MAX) {
+    const int total = gather.total();
+    if (gather.overflow() || total > CAND_MAX) {
         if (tid == 0) { state[b] = 1; flags[0] = 1; }
         return;
     }
-    int base = incl - cnt;
-    for (int w = 0; w < wave; ++w) base += wtotal[w];
-    {
-#pragma unroll
-        for (int u = 0; u < SPEC; ++u)
-            if (u < cnt) c_key[base + u] = first[u];
-        int maxc = cnt;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(maxc, m); maxc = o > maxc ? o : maxc; }
-#pragma unroll 1
-        for (int e0 = SPEC; e0 < maxc; e0 += 8) {
-            u64 key[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) key[u] = e0 + u < cnt ? mylist[e0 + u] : 0;
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (e0 + u < cnt) c_key[base + e0 + u] = key[u];
-        }
-    }
-    __syncthreads();
     u64 mine[CAND_PER];
     unsigned h[CAND_PER];
-#pragma unroll
-    for (int j = 0; j < CAND_PER; ++j) {
-        const int i = tid + 256 * j;
-        mine[j] = i < total ? c_key[i] : 0;
-        h[j] = (unsigned)(mine[j] >> 32);
-    }
+    gather.finish(c_key, total, mine, h);
     const int want = total < K ? total : K;
     u64 kth = 0;
     __syncthreads();                                 // keys are in registers: c_key's head becomes the fast path's compact list
@@ -687,27 +624,22 @@ __device__ __forceinline__ void exact_topk_inline(const float* qrow, const float
     if (wave != 0) return;
 #pragma unroll 1
     for (int w = 1; w < 4; ++w) best = merge_sorted_desc(best, wl[w][lane], lane);
-    if (lane < K) {
-        float sc = -INFINITY;
-        int idx = -1;
-        if (best != 0) {
-            sc = unorderable((unsigned)(best >> 32));
-            idx = (int)((long)(0xFFFFFFFFu - (unsigned)best) + idx_offset);
-        }
-        os[lane] = sc;
-        oi[lane] = idx;
-    }
+    if (lane < K) write_key(best, idx_offset, os + lane, oi + lane);
 }
 
 constexpr int DENSE_SEG = 1024;                 // collected keys per wave (4 segments)
 constexpr int DENSE_UB = 16;                    // 16-byte loads a thread keeps in flight while it walks the score row
 constexpr int DENSE_BATCH = 1024 * DENSE_UB;    // floats the workgroup covers per batch
+
+// a cut as the bound the exact pass starts from (a cut that is no number: no bound)
+__device__ __forceinline__ u64 bound_key(float cut) { return cut == cut ? (u64)orderable(cut) << 32 : 0ull; }
+
 // NB > 0: the row fits NB batches, which stay in registers between the two passes (N <= NB * 16384); NB = 0: any N, the row is read
 // twice (the second time from this XCD's L2).
 template <int NB>
 __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* approx, long ld, long N, const float* q, const float* gallery, int D,
                                                                  BoundMargin mg, int K, const int* exclude, long exclude_off, long idx_offset,
-                                                                 float* out_scores, int* out_idx, u64* thr_key, int* flags, int* state, int* done, int stop, int inline_exact,
+                                                                 float* out_scores, int* out_idx, u64* thr_key, int* flags, int* state, int* done, int inline_exact,
                                                                  RowTags rt) {
     // rt.tags != null: `approx` holds the MASKED sweep's scores (ineligible rows are -inf, so no walk collects them while the cut is a
     // number); the only places that look at the gallery itself again are the exact fallbacks, which apply the predicate.
@@ -717,7 +649,7 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     __shared__ __attribute__((aligned(16))) u64 x_key[RESC_MAX + 4];
     __shared__ unsigned surv[RESC_MAX];
     __shared__ __attribute__((aligned(16))) float qrow[1024];
-    __shared__ int red[32];
+    __shared__ float fred[8];                                                // margin_finish<4>
     __shared__ unsigned wmax[4];
     __shared__ int wcnt[4];
     __shared__ int nsurv;
@@ -757,14 +689,8 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
             if (drop >= i && drop < i + 4) dst[u][drop - i] = -INFINITY;     // (rare: the excluded row)
         }
     };
-    // the query's two norms (bound_margin_of): loads issued now, reduced after pass 1
-    float qa = 0.f, qe = 0.f;
-    for (int i = tid; i < D; i += 256) {
-        const float x = q[(long)b * D + i];
-        const float dd = x - bf16_bits_to_f32(f32_to_bf16_bits(x));
-        qa += x * x;
-        qe += dd * dd;
-    }
+    // the query's two norms (select.h): loads issued now, reduced after pass 1
+    const QueryNorms qn = margin_accumulate<256>(q + (long)b * D, D);
     // pass 1: every thread's maximum score.  fmax drops NaNs; the running SUM of the scores is NaN whenever one of them is (or when
     // +inf meets -inf: a false alarm that only costs speed) -- a NaN anywhere makes the wave collect everything.
     float fmax_t = -INFINITY, nsum = 0.f;
@@ -790,21 +716,7 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     if (tid < (int)(N - n4) && n4 + tid != drop) { tail = row[n4 + tid]; fmax_t = fmaxf(fmax_t, tail); nsum += tail; }
     const bool nan_t = nsum != nsum;
     unsigned tmax = fmax_t == -INFINITY ? 0u : orderable(fmax_t);      // 0 = "no row": a thread without rows, or only -inf scores
-    if (stop == 1) { if (tmax == 0x12345) out_idx[0] = 1; return; }
-    // margin (bound_margin_of's arithmetic on the sums started above)
-    float margin;
-    {
-        float* fred = reinterpret_cast<float*>(red);
-#pragma unroll
-        for (int x = 32; x >= 1; x >>= 1) { qa += __shfl_xor(qa, x); qe += __shfl_xor(qe, x); }
-        if (lane == 0) { fred[wave] = qa; fred[4 + wave] = qe; }
-        __syncthreads();
-        const float a = fred[0] + fred[1] + fred[2] + fred[3], e = fred[4] + fred[5] + fred[6] + fred[7];
-        const float nq = sqrtf(a), eq = sqrtf(e);
-        const float E = mg.meta[0], Gt = mg.meta[1], G = mg.meta[2];
-        const float eps = (nq * E + eq * Gt) * 1.00390625f + (float)D * 4.76837158203125e-7f * nq * fmaxf(G, Gt);
-        margin = 2.0f * eps * 1.0009765625f;
-    }
+    const float margin = margin_finish<4>(qn, D, mg.meta, fred);
     const unsigned sorted = sort64_desc_u32(tmax, lane);
     const int tw = (K + 3) / 4;
     const unsigned vw = (unsigned)__builtin_amdgcn_readlane((int)sorted, tw - 1);
@@ -821,20 +733,14 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     if (l0 == 0) break;      // (uniform) no bound -- tiny galleries, or NaN scores
     if (rt.tags && !(margin < INFINITY)) break;      // (uniform) filtered: a cut that is no number would collect the masked rows too
     const float cut0 = unorderable(l0) - margin;
-    if (stop == 2) { if (cut0 == 0.12345f) out_idx[0] = 1; return; }
     // (This kernel runs ONCE per CU on a cold instruction cache: its time follows the bytes of code it executes.  A second, never-taken
     // copy of the collection code (an "accept everything" form for tiny galleries) cost 4 us; those queries go to the exact pass instead.)
-    // pass 2: collect the rows at or above cut0 into THIS WAVE's segment -- one compare + ballot per element, no atomics (one returning
-    // LDS atomic per hit was ~200 cycles each); stored as raw (score bits, row), keyed after the pass
+    // pass 2: collect the rows at or above cut0 into THIS WAVE's segment (wave_append), stored as raw (score bits, row), keyed after
+    // the pass
     u64* seg = ckey[wave];
     int wn = 0;                                      // wave-uniform: entries in the segment so far
     auto collect_one = [&](float val, long n, bool hit) {
-        const u64 m = __ballot(hit);
-        if (m) {
-            const int pos = wn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-            if (hit && pos < DENSE_SEG) seg[pos] = ((u64)__float_as_uint(val) << 32) | (unsigned)n;
-            wn += __popcll(m);
-        }
+        wave_append(hit, wn, DENSE_SEG, [&](int pos) { seg[pos] = ((u64)__float_as_uint(val) << 32) | (unsigned)n; });
     };
     auto collect_batch = [&](long base, const f32x4e (&src)[DENSE_UB]) {
 #pragma unroll
@@ -850,8 +756,7 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
             }
         }
     };
-    if (stop == 21) {
-    } else if (NB > 0) {
+    if (NB > 0) {
 #pragma unroll
         for (int nb = 0; nb < NBR; ++nb) collect_batch((long)nb * DENSE_BATCH, v[nb]);
     } else {
@@ -872,9 +777,8 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     __syncthreads();
     const int c0 = wcnt[0], c1 = wcnt[1], c2 = wcnt[2], c3 = wcnt[3];
     const int nc = c0 + c1 + c2 + c3;
-    if (stop == 3 || stop == 21) { if (tid == 0) out_idx[(long)b * K] = nc; return; }
     if (c0 > DENSE_SEG || c1 > DENSE_SEG || c2 > DENSE_SEG || c3 > DENSE_SEG) {
-        fallback_thr = cut0 == cut0 ? (u64)orderable(cut0) << 32 : 0ull;
+        fallback_thr = bound_key(cut0);
         break;
     }
     // the i-th collected key (segments in wave order)
@@ -903,12 +807,10 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
             }
             if (rank == K - 1) kth_hi = (unsigned)(key >> 32);
         }
-        if (stop == 36) return;
         __syncthreads();
         khi = kth_hi;
     }
     const float cut = khi != 0 ? unorderable(khi) - margin : -INFINITY;
-    if (stop == 4) { if (cut == 0.12345f) out_idx[0] = 1; return; }
     for (int i = tid; i < nc; i += 256) {
         const u64 key = key_at(i);
         if (!(unorderable((unsigned)(key >> 32)) < cut)) {
@@ -918,9 +820,8 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     }
     __syncthreads();
     const int ns = nsurv;
-    if (stop == 5) { if (tid == 0) out_idx[(long)b * K] = ns; return; }
     if (ns > RESC_MAX) {
-        fallback_thr = cut == cut && khi != 0 ? (u64)orderable(cut) << 32 : 0ull;
+        fallback_thr = khi != 0 ? bound_key(cut) : 0ull;
         break;
     }
     rescore_and_rank(surv, ns, qrow, gallery, D, tiles, x_key, K, idx_offset, out_scores + (long)b * K, out_idx + (long)b * K);
@@ -966,7 +867,7 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
     __shared__ unsigned surv[RESC_MAX];
     __shared__ __attribute__((aligned(16))) float qrow[1024];
     __shared__ int tlist[4][TILES_SEG];
-    __shared__ int red[32];
+    __shared__ float fred[8];                        // margin_finish<4>
     __shared__ unsigned wmax[4];
     __shared__ int wcnt[4], tcnt[4];
     __shared__ int nsurv;
@@ -993,13 +894,7 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
 #pragma unroll
         for (int u = 0; u < TILES_TB; ++u) tv[u] = base + u * 256 + tid < ntiles ? tv[u] : -INFINITY;
     };
-    float qa = 0.f, qe = 0.f;
-    for (int i = tid; i < D; i += 256) {
-        const float x = q[(long)b * D + i];
-        const float dd = x - bf16_bits_to_f32(f32_to_bf16_bits(x));
-        qa += x * x;
-        qe += dd * dd;
-    }
+    const QueryNorms qn = margin_accumulate<256>(q + (long)b * D, D);      // reduced after the walk, as in topk_dense_rescore_kernel
     float fmax_t = -INFINITY;
     for (long base = 0; base < (HOLD ? 1 : ntiles); base += 256 * TILES_TB) {
         load_tiles(base);
@@ -1007,19 +902,7 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
         for (int u = 0; u < TILES_TB; u += 2) fmax_t = fmaxf(fmax_t, fmaxf(tv[u], tv[u + 1]));
     }
     const unsigned tmx = fmax_t == -INFINITY ? 0u : orderable(fmax_t);      // 0 = "no tile"
-    float margin;
-    {
-        float* fred = reinterpret_cast<float*>(red);
-#pragma unroll
-        for (int x = 32; x >= 1; x >>= 1) { qa += __shfl_xor(qa, x); qe += __shfl_xor(qe, x); }
-        if (lane == 0) { fred[wave] = qa; fred[4 + wave] = qe; }
-        __syncthreads();
-        const float a = fred[0] + fred[1] + fred[2] + fred[3], e = fred[4] + fred[5] + fred[6] + fred[7];
-        const float nq = sqrtf(a), eq = sqrtf(e);
-        const float E = mg.meta[0], Gt = mg.meta[1], G = mg.meta[2];
-        const float eps = (nq * E + eq * Gt) * 1.00390625f + (float)D * 4.76837158203125e-7f * nq * fmaxf(G, Gt);
-        margin = 2.0f * eps * 1.0009765625f;
-    }
+    const float margin = margin_finish<4>(qn, D, mg.meta, fred);
     const unsigned sorted = sort64_desc_u32(tmx, lane);
     const int tw = (K + (drop >= 0 ? 1 : 0) + 3) / 4;
     const unsigned vw = (unsigned)__builtin_amdgcn_readlane((int)sorted, tw - 1);
@@ -1038,15 +921,8 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
     for (long base = 0; base < (HOLD ? 1 : ntiles); base += 256 * TILES_TB) {
         if (!HOLD) load_tiles(base);
 #pragma unroll
-        for (int u = 0; u < TILES_TB; ++u) {
-            const bool hit = !(tv[u] < cut0);        // masked positions are -inf < cut0 (cut0 is finite)
-            const u64 m = __ballot(hit);
-            if (m) {
-                const int pos = tn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-                if (hit && pos < TILES_SEG) tl[pos] = (int)(base + u * 256 + tid);
-                tn += __popcll(m);
-            }
-        }
+        for (int u = 0; u < TILES_TB; ++u)           // masked positions are -inf < cut0 (cut0 is finite)
+            wave_append(!(tv[u] < cut0), tn, TILES_SEG, [&](int pos) { tl[pos] = (int)(base + u * 256 + tid); });
     }
     if (lane == 0) tcnt[wave] = tn;
     __syncthreads();
@@ -1056,7 +932,7 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
         break;
     }
     const int p1 = t0, p2 = t0 + t1, p3 = p2 + t2, nt = p3 + t3;
-    // gather: 8 lanes x 16 bytes per listed tile, four rounds of loads in flight; hits go to the wave's segment as (score bits, row)
+    // gather: 8 lanes x 16 bytes per listed tile, four rounds of loads in flight; hits go to the wave's segment as ranking keys
     u64* seg = ckey[wave];
     int wn = 0;
     const int items = nt * 8;
@@ -1077,13 +953,8 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const long n = nn[u] + j;
-                const bool hit = in && n < N && n != drop && !(val[u][j] < cut0);
-                const u64 m = __ballot(hit);
-                if (m) {
-                    const int pos = wn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-                    if (hit && pos < DENSE_SEG) seg[pos] = make_key(val[u][j], (unsigned)n);
-                    wn += __popcll(m);
-                }
+                wave_append(in && n < N && n != drop && !(val[u][j] < cut0), wn, DENSE_SEG,
+                            [&](int pos) { seg[pos] = make_key(val[u][j], (unsigned)n); });
             }
         }
     }
@@ -1162,7 +1033,6 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
 // list of the wave (64 entries, one per lane, kept in LDS: lists[wave][query]); after the pass the four wave lists of a query are
 // merged into partial[b][g], and the last workgroup to finish a query (a ticket in done[b]) merges the partial lists and writes the
 // ranking.  Nothing here has a capacity: whatever the gallery looks like, the result is the exact top-K.
-typedef float f32x16e __attribute__((ext_vector_type(16)));
 typedef short bf16x8e __attribute__((ext_vector_type(8)));
 constexpr int EXACT_QB = 32;                    // flagged queries per gallery pass (the A rows of one MFMA tile)
 template <bool BF16>
@@ -1216,10 +1086,10 @@ __global__ __launch_bounds__(256) void rank_exact_kernel(const float* q, const v
             const long n = t * 32 + l31;
             const long nc = n < N ? n : N - 1;
             const unsigned tag = rt.tags ? rt.tags[nc] : 0u;
-            f32x16e acc;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+            f32x16 acc;
             if (BF16) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
                 const unsigned short* grow = reinterpret_cast<const unsigned short*>(gallery) + nc * D;
                 for (int ks = 0; ks < D / 16; ++ks) {
                     const f32x4e a0 = *reinterpret_cast<const f32x4e*>(qrow + ks * 16 + lh * 8);
@@ -1231,13 +1101,7 @@ __global__ __launch_bounds__(256) void rank_exact_kernel(const float* q, const v
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, acc, 0, 0, 0);
                 }
             } else {
-                const float* grow = reinterpret_cast<const float*>(gallery) + nc * D;
-                for (int g8 = 0; g8 < D / 8; ++g8) {
-                    const f32x4e af = *reinterpret_cast<const f32x4e*>(qrow + g8 * 8 + lh * 4);
-                    const f32x4e bf = *reinterpret_cast<const f32x4e*>(grow + g8 * 8 + lh * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[e], bf[e], acc, 0, 0, 0);
-                }
+                acc = score_tile_f32(qrow, reinterpret_cast<const float*>(gallery) + nc * D, D, lh);
             }
             // which queries of the chunk have a score at or above their bound in this tile (wave-uniform bit mask)
             unsigned qmask = 0;
@@ -1286,16 +1150,7 @@ __global__ __launch_bounds__(256) void rank_exact_kernel(const float* q, const v
                     const u64 other = __hip_atomic_load(&partial[((long)b * G + gg) * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     top = gg == 0 ? other : merge_sorted_desc(top, other, lane);
                 }
-                if (lane < K) {
-                    float sc = -INFINITY;
-                    int idx = -1;
-                    if (top != 0) {
-                        sc = unorderable((unsigned)(top >> 32));
-                        idx = (int)((long)(0xFFFFFFFFu - (unsigned)top) + idx_offset);
-                    }
-                    out_scores[(long)b * K + lane] = sc;
-                    out_idx[(long)b * K + lane] = idx;
-                }
+                if (lane < K) write_key(top, idx_offset, out_scores + (long)b * K + lane, out_idx + (long)b * K + lane);
             }
         }
         __syncthreads();                                            // the lists are re-zeroed for the next chunk
@@ -1353,12 +1208,10 @@ hipError_t launch_topk_dense_rescore(const float* approx, long ld, long N, const
                         idx_offset, out_scores, out_idx, thr_key, flags, state, done, inline_exact, rt);
         return hipGetLastError();
     }
-    // lab switch (tools/rank_bench.py): FERN_DENSE_STOP=k ends the kernel after phase k (results are then garbage) to attribute its time
-    static const int stop = [] { const char* e = getenv("FERN_DENSE_STOP"); return e ? atoi(e) : 0; }();
     const long n4 = N & ~3L;
 #define FERN_DENSE_GO(NB)                                                                                                                       \
     FERN_LAUNCH(topk_dense_rescore_kernel<NB>, dim3(B), dim3(256), 0, s, approx, ld, N, q, gallery, D, mg, K, exclude, exclude_off, idx_offset, \
-                out_scores, out_idx, thr_key, flags, state, done, stop, inline_exact, rt)
+                out_scores, out_idx, thr_key, flags, state, done, inline_exact, rt)
     if (n4 <= 1L * DENSE_BATCH) FERN_DENSE_GO(1);
     else if (n4 <= 2L * DENSE_BATCH) FERN_DENSE_GO(2);
     else if (n4 <= 3L * DENSE_BATCH) FERN_DENSE_GO(3);

@@ -9,7 +9,7 @@
 //                       L = the K-th largest group maximum: K rows (one per group) score >= L, so the K-th best score T >= L;
 //               pass 2  the rows with score >= L - margin are collected into LDS as ranking keys (<= cap of them);
 //               sort    one bitonic sort of the collected keys (registers, lane shuffles, LDS only across waves);
-//               margin 0 (exact and bf16 forms): the first K keys are the answer.  Pre-filter (margin = 2 eps_b, topk.hip: BoundMargin):
+//               margin 0 (exact and bf16 forms): the first K keys are the answer.  Pre-filter (margin = 2 eps_b, select.h):
 //                       T~ = the K-th sorted approximate key, the survivors (s~ >= T~ - margin) are a prefix of the sorted keys; they
 //                       get their exact chain scores (rescore.h) and are sorted again;
 //   fallback  a query without room (more than `cap` collected rows: tie floods, near-constant galleries; a NaN score; a margin that is
@@ -19,14 +19,12 @@
 // Keys are topk.hip's: orderable(score) << 32 | ~index, so the first K' <= 64 places are those of fern_sim_topk* bit for bit.
 #include "kernels.h"
 #include "rescore.h"
+#include "select.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace fern {
-
-typedef unsigned long long u64;
-typedef float f32x16d __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ u64 deep_shfl_xor64(u64 v, int m) {
     const unsigned lo = __shfl_xor((unsigned)v, m), hi = __shfl_xor((unsigned)(v >> 32), m);
@@ -91,20 +89,9 @@ __device__ __forceinline__ void sort_lds_desc(u64* keys, int n) {
     __syncthreads();
 }
 
-__device__ __forceinline__ void write_key(u64 key, long idx_offset, float* os, int* oi) {
-    float sc = -INFINITY;
-    int idx = -1;
-    if (key != 0) {
-        sc = unorderable((unsigned)(key >> 32));
-        idx = (int)((long)(0xFFFFFFFFu - (unsigned)key) + idx_offset);
-    }
-    *os = sc;
-    *oi = idx;
-}
-
 // ---- exact scores ------------------------------------------------------------------------------------------------------------------
-// S[b][n] = the fp32 score of query b and gallery row n from v_mfma_f32_32x32x2_f32, k fed exactly as rank_exact_kernel feeds it (lane half
-// h: k = 8 g8 + 4 h + e), i.e. the oracle/chain.c order.  Workgroup (x, y): queries 32 y .. 32 y + 31, wave w the 32-row tiles
+// S[b][n] = the fp32 score of query b and gallery row n from score_tile_f32 (select.h), as rank_exact_kernel takes it: the oracle/chain.c
+// order.  Workgroup (x, y): queries 32 y .. 32 y + 31, wave w the 32-row tiles
 // 4 x + w + j * 4 gridDim.x.  GATED: runs only if flags[0] is set and writes only the rows of flagged queries (state[b] != 0);
 // otherwise it also zeroes flags[0..3] for the selection that follows.
 // rt.tags != null (a per-query row filter, kernels.h: RowTags; kernel-uniform branch -- this kernel is MFMA-bound on fp32 operands, the
@@ -144,15 +131,7 @@ __global__ __launch_bounds__(256) void deep_exact_scores_kernel(const float* q, 
         const long n = t * 32 + l31;
         const float* grow = gallery + (n < N ? n : N - 1) * D;
         const unsigned tag = tagged ? rt.tags[n < N ? n : N - 1] : 0u;      // issued in front of the row's loads
-        f32x16d acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-        for (int g8 = 0; g8 < D / 8; ++g8) {
-            const f32x4e af = *reinterpret_cast<const f32x4e*>(qrow + g8 * 8 + lh * 4);
-            const f32x4e bf = *reinterpret_cast<const f32x4e*>(grow + g8 * 8 + lh * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[e], bf[e], acc, 0, 0, 0);
-        }
+        const f32x16 acc = score_tile_f32(qrow, grow, D, lh);
         if (n < N) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -176,30 +155,6 @@ struct DeepMargin {
     const float* gallery;    // [N, D] fp32: the survivors' exact chains
     int D;
 };
-
-// topk.hip's bound_margin_of arithmetic: 2 eps_b with eps_b = ||q|| E + ||q - bf16(q)|| G~ + D 2^-21 ||q|| max(G, G~) (+ rounding slack)
-__device__ __forceinline__ float deep_margin(const DeepMargin& mg, int b, float* fred) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float a = 0.f, e = 0.f;
-    for (int i = tid; i < mg.D; i += DEEP_NT) {
-        const float v = mg.q[(long)b * mg.D + i];
-        const float d = v - bf16_bits_to_f32(f32_to_bf16_bits(v));
-        a += v * v;
-        e += d * d;
-    }
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) { a += __shfl_xor(a, x); e += __shfl_xor(e, x); }
-    if (lane == 0) { fred[wave] = a; fred[DEEP_WAVES + wave] = e; }
-    __syncthreads();
-    a = 0.f; e = 0.f;
-#pragma unroll
-    for (int w = 0; w < DEEP_WAVES; ++w) { a += fred[w]; e += fred[DEEP_WAVES + w]; }
-    __syncthreads();
-    const float nq = sqrtf(a), eq = sqrtf(e);
-    const float E = mg.meta[0], Gt = mg.meta[1], G = mg.meta[2];
-    const float eps = (nq * E + eq * Gt) * 1.00390625f + (float)mg.D * 4.76837158203125e-7f * nq * fmaxf(G, Gt);
-    return 2.0f * eps * 1.0009765625f;
-}
 
 template <int NT>
 __device__ __forceinline__ void sort_keys_desc(u64* keys, int n) {      // keys: 16 NT entries
@@ -271,7 +226,8 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
     if constexpr (CEIL) tail = make_key(tail, (unsigned)(n4 + tid + idx_offset)) > ck ? -INFINITY : tail;
     gmax[0] = fmaxf(gmax[0], tail);
     nsum += tail;
-    const float margin = mg.q ? deep_margin(mg, b, fred) : 0.0f;
+    // (uniform; fred is written once per query, and the vote below is a barrier)
+    const float margin = mg.q ? margin_finish<DEEP_WAVES>(margin_accumulate<DEEP_NT>(mg.q + (long)b * mg.D, mg.D), mg.D, mg.meta, fred) : 0.0f;
     // no room for a NaN score or a margin that is not finite: the exact fallback ranks this query
     if (__syncthreads_or(nsum != nsum || !(margin < INFINITY))) {
         if (tid == 0) { state[b] = 1; flags[0] = 1; }
@@ -336,15 +292,7 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
     const int ns = nsurv;
     // exact chains of the survivors (32 per wave and round), written over the approximate keys
     float* tl = tiles + wave * (2 * RESC_ROWS * RESC_TLD);
-    const int nsteps = mg.D / RESC_CH;
-    for (int s0 = wave * RESC_ROWS; s0 < ns; s0 += DEEP_WAVES * RESC_ROWS) {
-        float acc;
-        if (nsteps % 8 == 0) acc = rescore_rows<8>(surv, s0, ns, qrow, mg.gallery, mg.D, tl);
-        else if (nsteps % 10 == 0) acc = rescore_rows<10>(surv, s0, ns, qrow, mg.gallery, mg.D, tl);
-        else if (nsteps % 4 == 0) acc = rescore_rows<4>(surv, s0, ns, qrow, mg.gallery, mg.D, tl);
-        else acc = rescore_rows<2>(surv, s0, ns, qrow, mg.gallery, mg.D, tl);
-        if (lane < RESC_ROWS && s0 + lane < ns) ckey[s0 + lane] = make_key(acc, surv[s0 + lane]);
-    }
+    for (int s0 = wave * RESC_ROWS; s0 < ns; s0 += DEEP_WAVES * RESC_ROWS) rescore_keys(surv, s0, ns, qrow, mg.gallery, mg.D, tl, ckey);
     __syncthreads();
     sort_keys_desc<DEEP_NT>(ckey, ns);
     for (int r = tid; r < K; r += DEEP_NT) write_key(r < ns ? ckey[r] : 0ull, idx_offset, os + r, oi + r);

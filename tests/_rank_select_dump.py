@@ -1,0 +1,168 @@
+"""Raw results of the ranking select kernels (csrc/topk.hip, csrc/topk_deep.hip, csrc/select.h) on seeded inputs, for comparing two
+BUILDS of the library bit for bit: a change to those files that is meant to move no bit is run once on each build and every array
+compared.  A script, not a collected test.  Usage: python tests/_rank_select_dump.py out.npz
+
+Every case saves `<name>.s` (the scores' bits as uint32) and `<name>.i` (the indices).  The results are deterministic: keys are
+distinct and places come from counting or sorting, so a difference between two builds is a bug, never noise.
+
+With FERN_RANK_CAP set in the environment (the candidate lists' test hook, read once per process: tiny lists overflow) only the cases
+that go through candidate lists run, as `cap_<name>`: their queries then take the gated exact pass (rank_exact_kernel, fp32 and bf16).
+
+Which case reaches which path (api.hip: rank_plan, rank_strategy_for, rank_dense_chunk, sim_topk_deep_impl):
+  plain_*     fp32 tensor gallery: topk_sample_bound_kernel without a margin (<4, 256> for N <= 1024, <16, 256> up to a 4096-row sample,
+              <16, 1024> from N = 300 000, <32, 1024> from N = 1 100 000), topk_candidates_kernel (gather; fewer than K candidates at
+              N = 40), rank_exact_kernel<false> when lists overflow (all-equal gallery)
+  bf16_*      bf16 tensor gallery: the same kernels on the bf16 sweep, rank_exact_kernel<true> on overflow
+  lists_*     prepared gallery, strategy lists: the bound with its margin, topk_rescore_kernel (rescoring rings 8 at D = 512, 10 at
+              D = 640, 4 at D = 128, 2 at D = 64), list overflow -> rank_exact_kernel<false> (all-equal), a NaN row (no certificate)
+  dense_*     prepared gallery, strategy dense, N < 16 384 or a two-block sweep (B = 65, D = 64): topk_dense_rescore_kernel<1> (N <= 16 384:
+              N = 7 and N = 40 have l0 == 0 -> inline exact ranking; the N % 4 tail at 1001 / 1003 / 16 383), <2> (N = 20 000), <3>
+              (N = 40 000), <0> (N = 60 000); K = 1 and 64; the excluded row
+  tiles_*     prepared gallery, strategy dense, N >= 16 384, B <= 64: topk_tiles_rescore_kernel<true> (16 384, 16 411), <false> (262 145);
+              `exclude` for every query (K' = K + 1)
+  equal_*     all-equal galleries: 1025 rows (row walk: 1025 survivors > RESC_MAX -> inline exact behind T~ - margin), 65 537 rows (tile list
+              overflow -> inline exact at D = 64; at D = 512 the gallery is past the inline limit -> flagged, rank_exact_kernel<false>)
+  ties_*      2000 / 5000 identical best rows in a random gallery: survivors > RESC_MAX (fallback bound T~ - margin) / a wave segment
+              overflow (fallback bound l0 - margin), through the row walk (N = 9000), the tiles (N = 20 000) and, at 70 000 x 512, the
+              gated exact pass with a non-zero bound
+  filt_*      RowFilter calls: masked dense row walk (N = 1000), masked tiles (N = 16 411), the deep stage (K = 100); there is no filtered
+              lists form (fern_sim_topk_filtered runs the dense form or the deep stage)
+  nan_*       one NaN gallery row (meta is poisoned: the margin is NaN): row walk, tiles, lists, deep
+  deep_*      deep_exact_scores_kernel + deep_select_kernel: exact (fp32 tensor) and pre-filtered (prepared gallery; rings 4 at D = 128, 8 at
+              D = 768) forms at (3, 1000, 128, K = 1024) and (2, 70 000, 768, K = 100); the bf16 form; 5000 all-equal rows (more than the
+              4096 collected keys: flagged -> gated deep_exact_scores_kernel<true> + deep_fallback_kernel); a cursor page and an offset
+              page (deep_select_kernel<true> / page.hip)
+  merge_*     topk_merge_kernel (K <= 64) and topk_merge_deep_kernel
+"""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def _unit(n, d, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.nn.functional.normalize(torch.randn(n, d, generator=g), dim=-1)
+
+
+def _ties(n, d, nt, seed):
+    """(queries [3, d], gallery [n, d]): rows 0 .. nt - 1 are one row, and it is every query's best."""
+    gal = _unit(n, d, seed)
+    gal[:nt] = gal[0]
+    q = torch.nn.functional.normalize(gal[0][None, :] + 0.1 * _unit(3, d, seed + 1), dim=-1)
+    return q, gal
+
+
+def compute(eng, lists_only=False):
+    """{name: int array}; the same seeded inputs in every process."""
+    from fashionern_aaai2024_amd.engine import RowFilter, next_from
+    out = {}
+    pre = "cap_" if lists_only else ""
+
+    def put(name, res):
+        s, i = res
+        out[f"{pre}{name}.s"] = s.contiguous().view(torch.int32).cpu().numpy().view(np.uint32)
+        out[f"{pre}{name}.i"] = i.cpu().numpy()
+
+    def prepared(gal):
+        return eng.prepare_gallery(gal.cuda())
+
+    ex5 = torch.tensor([3, -1, 999, 0, 17], dtype=torch.int32)
+
+    # ---- candidate lists: plain, bf16, pre-filtered -------------------------------------------------------------------------------
+    eng.set_rank_strategy("lists")
+    for b, n, d, k in [(3, 1000, 64, 50), (64, 9001, 640, 50), (3, 40, 64, 50), (4, 5000, 512, 1), (4, 5000, 128, 64)] + \
+                      ([] if lists_only else [(2, 300_000, 64, 10), (2, 1_100_000, 64, 10)]):
+        q, gal = _unit(b, d, 10 + n), _unit(n, d, 20 + n)
+        put(f"plain_{b}_{n}_{d}_{k}", eng.sim_topk(q, gal, k))
+        if n <= 9001:
+            put(f"bf16_{b}_{n}_{d}_{k}", eng.sim_topk_bf16(q, eng.gallery_to_bf16(gal.cuda()), k))
+        if n <= 300_000:
+            put(f"lists_{b}_{n}_{d}_{k}", eng.sim_topk(q, prepared(gal), k))
+    q, gal = _unit(5, 128, 31), _unit(3000, 128, 32)
+    put("plain_exclude", eng.sim_topk(q, gal, 10, exclude_idx=ex5))
+    put("lists_exclude", eng.sim_topk(q, prepared(gal), 10, exclude_idx=ex5))
+    put("lists_exclude_offset", eng.sim_topk(q, prepared(gal), 10, idx_offset=1000, exclude_idx=ex5 + 1000))
+    q, gal = _unit(2, 64, 33), _unit(1, 64, 34).repeat(1025, 1)
+    put("plain_equal_1025", eng.sim_topk(q, gal, 50))
+    put("bf16_equal_1025", eng.sim_topk_bf16(q, eng.gallery_to_bf16(gal.cuda()), 50))
+    put("lists_equal_1025", eng.sim_topk(q, prepared(gal), 50))
+    q, gal = _unit(3, 64, 35), _unit(9001, 64, 36)
+    gal[4321] = float("nan")
+    put("nan_lists", eng.sim_topk(q, prepared(gal), 10))
+    if lists_only:
+        return out
+
+    # ---- dense: the row walk ------------------------------------------------------------------------------------------------------
+    eng.set_rank_strategy("dense")
+    for b, n, d, k in [(3, 40, 64, 10), (3, 40, 64, 50), (2, 7, 64, 10), (3, 1000, 64, 50), (3, 1000, 512, 1), (3, 1000, 640, 64), (3, 1001, 128, 50),
+                       (3, 1003, 64, 50), (4, 16383, 64, 50), (65, 20000, 64, 50), (65, 40000, 64, 50), (65, 60000, 64, 50)]:
+        q, gal = _unit(b, d, 40 + n), _unit(n, d, 50 + n)
+        put(f"dense_{b}_{n}_{d}_{k}", eng.sim_topk(q, prepared(gal), k))
+    q, gal = _unit(5, 64, 61), _unit(1003, 64, 62)
+    put("dense_exclude", eng.sim_topk(q, prepared(gal), 10, exclude_idx=torch.tensor([3, -1, 999, 1002, 1001], dtype=torch.int32)))
+    # ---- dense: tile maxima -------------------------------------------------------------------------------------------------------
+    for b, n, d, k in [(3, 16384, 64, 50), (64, 16411, 128, 50), (3, 16411, 64, 1), (3, 16411, 64, 64), (2, 262145, 64, 50)]:
+        q, gal = _unit(b, d, 70 + n), _unit(n, d, 80 + n)
+        pg = prepared(gal)
+        put(f"tiles_{b}_{n}_{d}_{k}", eng.sim_topk(q, pg, k))
+        if b == 3 and k == 64:      # every query excludes its own best row
+            best = eng.sim_topk(q, pg, 1)[1][:, 0].cpu()
+            put(f"tiles_exclude_{n}", eng.sim_topk(q, pg, 50, exclude_idx=best))
+    # ---- floods of ties -----------------------------------------------------------------------------------------------------------
+    q = _unit(3, 64, 91)
+    put("equal_1025", eng.sim_topk(q, prepared(_unit(1, 64, 92).repeat(1025, 1)), 50))
+    put("equal_65537", eng.sim_topk(q, prepared(_unit(1, 64, 92).repeat(65537, 1)), 50))
+    put("equal_65537_gated", eng.sim_topk(_unit(3, 512, 93), prepared(_unit(1, 512, 94).repeat(65537, 1)), 50))
+    for n, d, nt in [(9000, 64, 2000), (9000, 64, 5000), (20000, 64, 2000), (20000, 64, 5000), (70000, 512, 2000)]:
+        q, gal = _ties(n, d, nt, 100 + nt)
+        put(f"ties_{n}_{d}_{nt}", eng.sim_topk(q, prepared(gal), 10))
+    # ---- row filters --------------------------------------------------------------------------------------------------------------
+    for n in (1000, 16411):
+        q, gal = _unit(4, 64, 110 + n), _unit(n, 64, 120 + n)
+        tags = torch.arange(n, dtype=torch.int32) % 7
+        filt = RowFilter(tags, mask=torch.tensor([0xFF, 0xFF, 0, 0xFF], dtype=torch.int32), value=torch.tensor([3, 5, 0, 9], dtype=torch.int32))
+        put(f"filt_{n}", eng.sim_topk(q, prepared(gal), 50, row_filter=filt))
+        put(f"filt_exclude_{n}", eng.sim_topk(q, prepared(gal), 50, exclude_idx=torch.tensor([3, 5, -1, 0], dtype=torch.int32), row_filter=filt))
+        if n == 1000:
+            put("filt_deep_prefiltered", eng.sim_topk_deep(q, prepared(gal), 100, row_filter=filt))
+            put("filt_deep_exact", eng.sim_topk_deep(q, gal, 100, row_filter=filt))
+    # ---- a NaN row ----------------------------------------------------------------------------------------------------------------
+    for n in (1000, 20000):
+        q, gal = _unit(3, 64, 130 + n), _unit(n, 64, 140 + n)
+        gal[n // 3] = float("nan")
+        put(f"nan_dense_{n}", eng.sim_topk(q, prepared(gal), 10))
+        if n == 1000:
+            put("nan_deep", eng.sim_topk_deep(q, prepared(gal), 100))
+    # ---- deep ranking -------------------------------------------------------------------------------------------------------------
+    eng.set_rank_strategy("auto")
+    for b, n, d, k in [(3, 1000, 128, 1024), (2, 70000, 768, 100)]:
+        q, gal = _unit(b, d, 150 + n), _unit(n, d, 160 + n)
+        put(f"deep_exact_{b}_{n}_{d}_{k}", eng.sim_topk_deep(q, gal, k))
+        put(f"deep_prefiltered_{b}_{n}_{d}_{k}", eng.sim_topk_deep(q, prepared(gal), k))
+        if n == 1000:
+            put("deep_bf16", eng.sim_topk_deep(q, eng.gallery_to_bf16(gal.cuda()), 100))
+            put("deep_exclude", eng.sim_topk_deep(q, prepared(gal), 100, exclude_idx=torch.tensor([3, -1, 999], dtype=torch.int32)))
+            first = eng.sim_topk_deep(q, gal, 100)
+            put("deep_cursor_page", eng.sim_topk_from(q, gal, 100, next_from(*first)))
+            put("deep_offset_page", eng.rank_page(q, gal, 37, 100))
+    q, gal = _unit(2, 64, 171), _unit(1, 64, 172).repeat(5000, 1)
+    put("deep_equal_exact", eng.sim_topk_deep(q, gal, 100))
+    put("deep_equal_prefiltered", eng.sim_topk_deep(q, prepared(gal), 100))
+    # ---- merges of ranked lists ---------------------------------------------------------------------------------------------------
+    for k in (10, 100):
+        q = _unit(4, 64, 180 + k)
+        parts = [eng.sim_topk_deep(q, _unit(60 + 50 * r, 64, 190 + r), k, idx_offset=1000 * r) for r in range(3)]      # 60 rows < K = 100: -1 slots
+        put(f"merge_{k}", eng.topk_merge(torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts])))
+    return out
+
+
+if __name__ == "__main__":
+    from fashionern_aaai2024_amd.engine import FernEngine
+    eng = FernEngine("cuda:0")
+    arrays = compute(eng, lists_only="FERN_RANK_CAP" in os.environ)
+    torch.cuda.synchronize()
+    np.savez(sys.argv[-1], **arrays)
+    print(f"{len(arrays)} arrays -> {sys.argv[-1]}")
