@@ -17,8 +17,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libfern.so")
-SOURCES = ["api.hip", "gemm.hip", "gemm_bf16.hip", "gemm_tuner.hip", "gemm_pp.hip", "attn.hip", "elem.hip", "topk.hip", "topk_deep.hip", "items.hip", "rank.hip", "page.hip", "image.hip", "sweep_bf16.hip", "live.hip"]
-HEADERS = ["kernels.h", "gemm_epilogue.h", "gemm_pp.h", "gemm_tuner.h", "rescore.h", "select.h", "row_ops.h", "live.h", os.path.join("..", "..", "include", "fern.h")]
+SOURCES = ["api_ctx.hip", "api_weights.hip", "api_fusion.hip", "api_towers.hip", "api.hip", "api_blocks.hip", "gemm.hip", "gemm_bf16.hip", "gemm_tuner.hip", "gemm_pp.hip", "attn.hip", "elem.hip", "topk.hip", "topk_deep.hip", "items.hip", "rank.hip", "page.hip", "image.hip", "sweep_bf16.hip", "live.hip"]
+HEADERS = ["ctx.h", "kernels.h", "gemm_epilogue.h", "gemm_pp.h", "gemm_tuner.h", "rescore.h", "select.h", "row_ops.h", "live.h", os.path.join("..", "..", "include", "fern.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-DFERN_BUILD"]
 
 
@@ -95,7 +95,7 @@ def build_lib(force: bool = False, verbose: bool = True) -> str:
         json.dump(usage[src], open(side, "w"))
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1, 16)) as ex:      # 16: a shared machine's share of CPUs
         objs = list(ex.map(compile_one, SOURCES))
     # Every kernel's registers / scratch / LDS as the compiler reports them.  A kernel that SPILLS is a build error: scratch
     # traffic inside an MFMA loop (or an epilogue that drags the whole kernel's occupancy down) is a silent 2x, and it has

@@ -1184,7 +1184,7 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
     return launch_cfg(c, p, s);
 }
 
-// fern's GEMM pairs (api.hip: run_gemm_pair): p1 = the image tower's GEMM, p2 = the text tower's GEMM of the same layer.  One launch when
+// fern's GEMM pairs (api_ctx.hip: run_gemm_pair): p1 = the image tower's GEMM, p2 = the text tower's GEMM of the same layer.  One launch when
 // p1's tuned plan is a mixed plan and both calls are plain (row-independent epilogue, plain loader, same arithmetic family); two launches
 // otherwise -- also the first time a shape is seen (launch_gemm tunes it; the next call finds the plan) and for the pairs that the one-launch
 // form does not speed up (pair_wins, timed once per pair of shapes).  FERN_GEMM_PAIR=0 turns it off.

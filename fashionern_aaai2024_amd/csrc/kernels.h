@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI layer (api.hip) and the kernel translation units.
+// Internal launcher interface between the C-ABI layer (api*.hip) and the kernel translation units.
 // gfx950 only; no portability shims.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,7 +14,7 @@
 namespace fern {
 
 // ---- kernel-precise launch timing (fern_prof_enable) ----------------------------------------------------------------------------
-// While a LaunchTimer is armed on the calling thread (api.hip arms one around every GEMM / attention launch of an instrumented pass),
+// While a LaunchTimer is armed on the calling thread (api_ctx.hip arms one around every GEMM / attention launch of an instrumented pass),
 // FERN_LAUNCH dispatches through hipExtLaunchKernelGGL with a (start, stop) event pair: the events carry the DISPATCH's own begin /
 // end timestamps -- what rocprofv3's kernel trace reports -- instead of the stream-marker interval of hipEventRecord, which added
 // the marker packets and the dispatch latency (~3-5 us) to every launch (a fifth of a 25 us block-scaled GEMM).  Not armed: a plain
@@ -169,7 +169,7 @@ struct GemmParams {
     const unsigned short* Wb;
     int out_bf16;                 // plain epilogues: store C as bf16 (ldc in elements) instead of fp32
     // block-scaled family, EPI_BIAS_RESIDUAL with out_bf16: the residual stream itself is bf16 (Rb [M, ldc] bf16 in, C bf16 out,
-    // may alias): C = bf16(acc + bias + float(Rb)) -- one rounding per residual add (FERN_PREC_MX8's token stream, api.hip)
+    // may alias): C = bf16(acc + bias + float(Rb)) -- one rounding per residual add (FERN_PREC_MX8's token stream, api_towers.hip)
     const unsigned short* Rb;
     // fp8 (OCP e4m3fn) operand form: Ab / Wb point at fp8 bytes (strides in elements = bytes), K % 64 == 0; the quantisation
     // scales are folded back in the epilogue: C = acc * scale_a[row] * scale_w[col] (+ bias ...)

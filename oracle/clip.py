@@ -132,7 +132,7 @@ def _attention(sd, prefix, x, heads, causal, prec=None, q_rows=None):
 def _block(sd, prefix, x, heads, causal, prec=None):
     """Pre-LN residual block, modeling_clip.py:354-401; MLP :339-351 with exact GELU."""
     reduced = prec in ("bf16", "fp8", "mx8")
-    # the block-scaled mode keeps the residual stream itself in bf16 (csrc/api.hip: tower_forms): one rounding per residual add
+    # the block-scaled mode keeps the residual stream itself in bf16 (csrc/api_towers.hip: tower_forms): one rounding per residual add
     stream_bf16 = prec == "mx8"
     x = _r(x + _attention(sd, prefix + ".attn", _ln(sd, prefix + ".ln_1", x), heads, causal, prec), stream_bf16)
     h = F.gelu(_linear(_ln(sd, prefix + ".ln_2", x), sd[prefix + ".mlp.c_fc.weight"], sd[prefix + ".mlp.c_fc.bias"], prec))
@@ -141,7 +141,7 @@ def _block(sd, prefix, x, heads, causal, prec=None):
 
 
 def _block_mixed(sd, prefix, x, heads, causal, attn_mx):
-    """The mixed blocks (csrc/api.hip: tower_forms, the image tower under mx8mlp / mx8img) over the fp32 residual stream.  FERN_PREC_MX8_MLP (attn_mx False): the
+    """The mixed blocks (csrc/api_towers.hip: tower_forms, the image tower under mx8mlp / mx8img) over the fp32 residual stream.  FERN_PREC_MX8_MLP (attn_mx False): the
     attention half in the bf16 form (LayerNorm-1 -> bf16, bf16 QKV stored as bf16, bf16 attention, bf16 out-proj), the MLP half
     block-scaled (LayerNorm-2 -> e4m3fn + E8M0, c_fc, its GELU output quantised from fp32 with no bf16 round trip, c_proj).
     FERN_PREC_MX8_IMG (attn_mx True): the attention half block-scaled too when head_dim % 32 == 0 (LayerNorm-1 -> MX, MX QKV

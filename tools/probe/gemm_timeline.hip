@@ -7,7 +7,7 @@
 // tools/gemm_timeline.py turns the CSV into the attribution table.
 #define FERN_GEMM_TRACE 1
 #include "../../fashionern_aaai2024_amd/csrc/gemm.hip"
-namespace fern {      // the library defines these in api.hip; the probe never arms the launch timer
+namespace fern {      // the library defines these in api_ctx.hip; the probe never arms the launch timer
 thread_local LaunchTimer* g_launch_timer = nullptr;
 hipEvent_t launch_timer_event() { return nullptr; }
 }  // namespace fern
