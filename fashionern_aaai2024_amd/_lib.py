@@ -74,6 +74,8 @@ SIGNATURES = {
     "fern_rank_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_i64, c_void_p, c_void_p, c_void_p]),
     "fern_sim_topk_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_int, c_void_p, c_void_p, c_i64,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fern_sim_topk_candidates": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fern_rank_count_filtered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_i64, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "fern_rank_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_int, c_void_p, c_int, c_i64, c_void_p, c_void_p,

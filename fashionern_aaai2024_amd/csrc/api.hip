@@ -1,5 +1,5 @@
 // C-ABI layer of libfern.so: the ranking host layer -- one argument check and one score producer under the top-K forms (plain, bf16, pre-filtered,
-// filtered, deep), the item forms, the target ranks and the ranking pages -- with the gallery copies, live-gallery entries, score gathers and list merges.
+// filtered, deep, candidates), the item forms, the target ranks and the ranking pages -- with the gallery copies, live-gallery entries, score gathers and list merges.
 // Beside it: api_ctx / api_weights / api_fusion / api_towers / api_blocks.hip, over ctx.h.  (Named api.hip still: api_rank.hip is a pure rename away.)
 #include <cstdio>
 #include <cstdlib>
@@ -489,6 +489,31 @@ extern "C" int fern_sim_topk_deep(fern_ctx* c, const float* q, const float* gall
     const RankCall call{"fern_sim_topk_deep", q, gallery, gallery_bf16, meta, B, N, D, idx_offset, exclude_idx, {}, K, out_scores, out_idx};
     FERN_TRY(rank_check(c, call, GALLERY_EITHER, out_scores && out_idx, K, 1024));
     return sim_topk_deep_impl(c, call, stream);
+}
+
+// Candidate ranking (include/fern.h: fern_sim_topk_candidates; candidates.hip): one launch per query chunk, one workgroup per query, no
+// workspace and nothing read back.  fp32 rows rank when they are given: a bf16 copy beside them is not looked at.
+extern "C" int fern_sim_topk_candidates(fern_ctx* c, const float* q, const float* gallery, const uint16_t* gallery_bf16, int B, int64_t N, int D,
+                                        const int32_t* cand, int M, int K, float* out_scores, int32_t* out_idx, int32_t* out_place,
+                                        int64_t idx_offset, const int32_t* exclude_idx, const uint32_t* tags, const uint32_t* mask,
+                                        const uint32_t* value, void* stream) {
+    const RankCall call{"fern_sim_topk_candidates", q, gallery, gallery ? nullptr : gallery_bf16, nullptr, B, N, D, idx_offset, exclude_idx,
+                        row_tags(tags, mask, value), K, out_scores, out_idx};
+    if (M < 1 || M > CAND_MAX_M) return fail(FERN_ERR_ARG, std::string(call.fn) + ": need 1<=M<=" + std::to_string(CAND_MAX_M));
+    FERN_TRY(rank_check(c, call, GALLERY_EITHER_OR_EMPTY, cand && out_scores && out_idx, K, 1024));
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    return for_query_chunks(c, s, B, (long)kRankQueryChunk, [&](long o, int m) -> int {
+        const RankCall a = call.at(o);
+        StageTimer st(c, s);
+        st.sweep_begin();
+        HIP_TRY(launch_candidates(a.q, a.gallery, a.gallery_bf16, m, N, D, cand + o * M, M, K, idx_offset, a.exclude, &a.rt, a.out_scores, a.out_idx,
+                                  out_place ? out_place + o * M : nullptr, s));
+        // bytes the launch must move: every named row once per query, the queries, the lists, the results
+        st.sweep_end((double)m * M * D * (a.gallery ? 4 : 2) + (double)m * D * 4 + (double)m * M * (out_place ? 8 : 4) + (double)m * K * 8);
+        st.commit(m, (int)N, D);
+        return FERN_OK;
+    });
 }
 
 // Item-level ranking (include/fern.h: fern_sim_topk_items, fern_item_rank; items.hip), per query chunk: the deep stage's score rows S [m, ld]

@@ -486,6 +486,18 @@ hipError_t launch_rank_count_rows(const float* S, long ld, int B, long N, const 
 // count[b * cstride + t] = keys[b * kstride + t] ? sum over the RANKC_P sets of partial[.][b][t] : -1, t < nt
 hipError_t launch_rank_finalize(const RankCount& rc, int B, int* count, int cstride, hipStream_t s);
 
+// ---- candidate ranking (candidates.hip): every query ranks the set of rows its own list names ----------------------------------------
+// cand [B, M] (device) holds GLOBAL row indices; an entry takes no place if it is < 0, outside [idx_offset, idx_offset + N), the query's
+// excluded row or ineligible under rt (null: unfiltered); a row named twice counts once.  out [B, K]: the exact ranking of the named rows
+// (score descending, global index ascending; unfilled: -inf / -1), the scores bit for bit those of the sweep of the same form: `gallery`
+// given: the fp32 chain (oracle/chain.c order), D % 32 == 0; else gallery_bf16: the bf16 sweep's MFMA arithmetic, D % 64 == 0, D <= 768.
+// out_place (may be null) [B, M]: the 0-based place of every entry in that ranking, -1 for an entry that takes none.  One workgroup per
+// query, no workspace, no atomics.  1 <= M <= CAND_MAX_M, 1 <= K <= 1024.
+constexpr int CAND_MAX_M = 4096;
+hipError_t launch_candidates(const float* q, const float* gallery, const unsigned short* gallery_bf16, int B, long N, int D, const int* cand, int M,
+                             int K, long idx_offset, const int* exclude, const RowTags* rt, float* out_scores, int* out_idx, int* out_place,
+                             hipStream_t s);
+
 // ---- deep top-K (topk_deep.hip): 1 <= K <= 1024 on a stored score row per query ------------------------------------------------
 // S [B, ld] fp32 = exact chain scores of B queries against an fp32 gallery (deep_exact_scores_kernel: the MFMA sequence of
 // launch_rank_exact).  gated != 0: only if flags[0] is set, only the rows of queries with state[b] != 0; gated == 0 also zeroes flags[0..3].

@@ -6,6 +6,7 @@
 //   rank_count_rows_kernel      bf16 form: counting over the score rows the bf16 sweep stored
 //   rank_finalize_kernel        sum of the partial counter sets, -1 for a target without a key
 #include "kernels.h"
+#include "rescore.h"
 
 #include <algorithm>
 
@@ -25,7 +26,7 @@ __device__ __forceinline__ long rank_local_row(int target, long idx_offset, long
 
 // One wave per (query, 16 targets).  A step brings 256 k of the 16 rows and of the query into LDS with one load per lane and row (all
 // 17 in flight behind one wait); lane t < 16 then continues target t's chain over those k in the sweep's order: inside every 8
-// consecutive k, 0 4 1 5 2 6 3 7 (oracle/chain.c).  One rounding per product, as v_mfma_f32_32x32x2_f32 does it.
+// consecutive k, 0 4 1 5 2 6 3 7 (rescore.h: chain_run).
 __global__ __launch_bounds__(64) void rank_keys_kernel(const float* q, const float* gallery, const int* targets, int B, long N, int D, int m,
                                                        long idx_offset, u64* keys) {
     __shared__ __attribute__((aligned(16))) float tile[(RK_T + 1) * RK_LD];
@@ -51,20 +52,7 @@ __global__ __launch_bounds__(64) void rank_keys_kernel(const float* q, const flo
 #pragma unroll
         for (int t = 0; t <= RK_T; ++t) *reinterpret_cast<f32x4k*>(tile + t * RK_LD + lane * 4) = v[t];
         __syncthreads();
-        if (lane < RK_T) {
-            const int kn = min(RK_CH, D - k0);
-            const float* grow = tile + lane * RK_LD;
-            const float* qk = tile + RK_T * RK_LD;
-            for (int k8 = 0; k8 < kn; k8 += 8) {
-                const f32x4k g0 = *reinterpret_cast<const f32x4k*>(grow + k8), g1 = *reinterpret_cast<const f32x4k*>(grow + k8 + 4);
-                const f32x4k q0 = *reinterpret_cast<const f32x4k*>(qk + k8), q1 = *reinterpret_cast<const f32x4k*>(qk + k8 + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    acc = __builtin_fmaf(q0[e], g0[e], acc);
-                    acc = __builtin_fmaf(q1[e], g1[e], acc);
-                }
-            }
-        }
+        if (lane < RK_T) acc = chain_run(tile + lane * RK_LD, tile + RK_T * RK_LD, min(RK_CH, D - k0), acc);
     }
     if (lane < nt) {
         const int t = tg[lane];

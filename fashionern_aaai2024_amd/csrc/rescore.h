@@ -9,6 +9,22 @@ constexpr int RESC_CH = 32;                     // k per step of the transposing
 constexpr int RESC_TLD = RESC_CH + 4;           // floats per tile row (+ 4: lane l's ds_read_b128 of row l starts 4 banks after lane l-1's)
 constexpr int RESC_ROWS = 32;                   // survivors per wave and round
 
+// One lane continues one row's chain over kn staged k (kn % 8 == 0) in the sweep's order: inside every 8 consecutive k, 0 4 1 5 2 6 3 7
+// (oracle/chain.c).  One rounding per product, as v_mfma_f32_32x32x2_f32 does it.  grow / qk: 16-byte aligned, the row's and the query's
+// floats of those k.  The per-lane form of the chain (rank.hip's key producer, candidates.hip for D with an odd number of 32-k steps).
+__device__ __forceinline__ float chain_run(const float* grow, const float* qk, int kn, float acc) {
+    for (int k8 = 0; k8 < kn; k8 += 8) {
+        const f32x4e g0 = *reinterpret_cast<const f32x4e*>(grow + k8), g1 = *reinterpret_cast<const f32x4e*>(grow + k8 + 4);
+        const f32x4e q0 = *reinterpret_cast<const f32x4e*>(qk + k8), q1 = *reinterpret_cast<const f32x4e*>(qk + k8 + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            acc = __builtin_fmaf(q0[e], g0[e], acc);
+            acc = __builtin_fmaf(q1[e], g1[e], acc);
+        }
+    }
+    return acc;
+}
+
 // One wave, 32 survivors surv[s0 .. s0 + 32) (rows past ns redo survivor s0): their exact fp32 chains against qrow.  D = 32 nsteps k,
 // nsteps % RING == 0.  A step is four load instructions (8 rows x 32 floats each: whole 128-byte lines) whose registers go through
 // the wave's LDS tile so that lane l < 32 can continue survivor l's chain over those 32 k.  The loads of the next RING steps are always

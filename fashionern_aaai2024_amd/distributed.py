@@ -212,6 +212,25 @@ def rank_from_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start:
     return engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
 
 
+def rank_candidates_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: int, candidates, k: int, exclude_idx=None, row_filter=None):
+    """Gallery-sharded CANDIDATE ranking of the SAME query batch and the SAME lists on every rank (`FernEngine.sim_topk_candidates`):
+    `candidates` [B,M] hold global row indices, the local call runs with ``idx_offset = shard_start``, so a shard ranks the candidates
+    it owns and the others take no place there; then the all-gather and merge of `rank_sharded`.  Returns the global (scores, idx) on
+    every rank.  `row_filter`: the SHARD's.  No places: a place inside the whole list is not a function of the places inside the shards'
+    parts (count the keys with `rank_of_sharded` instead)."""
+    rank, world = world_info()
+    kw = {} if row_filter is None else {"row_filter": row_filter}
+    s, i = engine.sim_topk_candidates(queries, gallery_shard, candidates, k, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
+    if world == 1:
+        return s, i
+    b, kk = s.shape
+    all_s = torch.empty((world * b, kk), dtype=s.dtype, device=s.device)
+    all_i = torch.empty((world * b, kk), dtype=i.dtype, device=i.device)
+    _all_gather_into(all_s, s)
+    _all_gather_into(all_i, i)
+    return engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
+
+
 def route_rows(slots, bounds) -> List[np.ndarray]:
     """Host-side partition of a gallery UPDATE by owning shard.  `slots` [m] are global gallery rows (the slots of a sharded
     `live_gallery.LiveGallery`: shard r holds rows [bounds[r], bounds[r + 1]) and its store has ``slot_offset = bounds[r]``), `bounds`

@@ -548,6 +548,34 @@ class FernEngine:
                                                _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_deep")
         return scores, idx
 
+    def sim_topk_candidates(self, q, gallery, candidates, k: int, idx_offset: int = 0, exclude_idx=None,
+                            row_filter: Optional[RowFilter] = None, places: bool = False):
+        """(scores, idx) [B,k], with `places` also place int32 [B,M]: every query ranked inside its own list of gallery rows
+        (include/fern.h: fern_sim_topk_candidates; run/test/test_cirr.py:55-69 ranks inside a named member set).  `candidates` [B,M]
+        holds global row indices (a tensor, numpy array or list; 1 <= M <= 4096); an entry that is negative, outside this gallery
+        (shard), the query's excluded row or ineligible under `row_filter` takes no place, a row named twice counts once.  Scores and
+        order are those of `sim_topk_deep` on the same gallery form (fp32 tensor or `PreparedGallery`: the fp32 chain; bf16 tensor: the
+        bf16 similarity); 1 <= k <= 1024, places past the list are -inf / -1.  place[b][j]: the 0-based place of entry j, -1 if none."""
+        q, g32, g16 = self._rank_forms(q, gallery)
+        g = g32 if g32 is not None else g16
+        b, n = q.shape[0], g.shape[0]
+        cd = torch.as_tensor(candidates)
+        if cd.dim() != 2 or cd.shape[0] != b or cd.dtype.is_floating_point or cd.dtype == torch.bool:
+            raise ValueError(f"candidates must be an integer [B = {b}, M], got {tuple(cd.shape)} {cd.dtype}")
+        cd = cd.to(device=self.device, dtype=torch.int32).contiguous()
+        tags = mask = value = None
+        if row_filter is not None:
+            if not isinstance(row_filter, RowFilter):
+                raise TypeError("row_filter must be a RowFilter")
+            tags, mask, value = row_filter.resolve(b, n, self.device)
+        scores, idx = self._topk_out(b, k)
+        place = self._empty(*cd.shape, dtype=torch.int32) if places else None
+        ex = self._exclude(exclude_idx, b)
+        _lib.check(self.lib.fern_sim_topk_candidates(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, n, q.shape[1], _ptr(cd), cd.shape[1], int(k),
+                                                     _ptr(scores), _ptr(idx), _ptr(place), int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask),
+                                                     _ptr(value), _stream()), "fern_sim_topk_candidates")
+        return (scores, idx, place) if places else (scores, idx)
+
     # ---- exact target ranks ---------------------------------------------------------------------
     def _rank_forms(self, q, gallery):
         """(q, fp32 gallery or None, bf16 gallery or None): the gallery forms of `sim_topk_deep`; a PreparedGallery ranks on its

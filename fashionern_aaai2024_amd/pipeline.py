@@ -19,10 +19,11 @@ class QueryResult:
     """Top-K of one submitted batch; `scores` / `idx` are valid on the caller's stream after `wait()`."""
 
     def __init__(self, scores: torch.Tensor, idx: torch.Tensor, fused: torch.Tensor, event: torch.cuda.Event, member_scores=None,
-                 start_event: Optional[torch.cuda.Event] = None, item: Optional[torch.Tensor] = None):
+                 start_event: Optional[torch.cuda.Event] = None, item: Optional[torch.Tensor] = None, place: Optional[torch.Tensor] = None):
         self.scores, self.idx, self.fused, self._event, self.member_scores = scores, idx, fused, event, member_scores
         self._start = start_event
         self.item = item      # submit(items=...): the item id of every place [B,k]; None for a row-level ranking
+        self.place = place    # submit(candidates=...): the place of every list entry inside its query's list [B,M] (-1: takes none); else None
 
     @property
     def start_event(self) -> Optional[torch.cuda.Event]:
@@ -39,7 +40,7 @@ class QueryResult:
     def wait(self) -> Tuple[torch.Tensor, torch.Tensor]:
         cur = torch.cuda.current_stream()
         cur.wait_event(self._event)
-        for t in (self.scores, self.idx, self.fused, self.item):
+        for t in (self.scores, self.idx, self.fused, self.item, self.place):
             if t is not None:
                 t.record_stream(cur)
         return self.scores, self.idx
@@ -118,7 +119,7 @@ class ComposedQueryPipeline:
 
     def submit(self, images: Optional[torch.Tensor], tokens: torch.Tensor, local: torch.Tensor, gallery: torch.Tensor, k: int,
                exclude_idx=None, members=None, idx_offset: int = 0, ref_feats: Optional[torch.Tensor] = None,
-               row_filter: Optional[RowFilter] = None, items: Optional[ItemMap] = None) -> QueryResult:
+               row_filter: Optional[RowFilter] = None, items: Optional[ItemMap] = None, candidates=None) -> QueryResult:
         """images [B,3,S,S], tokens [B,77] int64, local [B,13,D] (device tensors), fused gallery [N,D] fp32 -- or a `PreparedGallery`
         of it (engine.prepare_gallery: the same exact fp32 ranking through the certified bf16 pre-filter, the form a serving process
         keeps), or bf16, which selects the bf16 sweep -- -> QueryResult.  `exclude_idx` [B] drops one gallery index per query and `members` [B,m]
@@ -130,6 +131,9 @@ class ComposedQueryPipeline:
         pointer of a captured graph, its per-query mask / value travel through the lane's static buffers like `exclude_idx`.  `items`
         (`ItemMap`): the ranking is item-level (engine.sim_topk_items: one place per item, represented by its best eligible row) and
         `QueryResult.item` holds the item id of every place; the ids are a static pointer of a captured graph, like the tags.
+        `candidates` [B,M] (global row indices; a tensor, numpy array or list): every query is ranked inside its own list
+        (engine.sim_topk_candidates) on every gallery form, `QueryResult.place` holds the place of every entry; the lists travel through
+        the lane's static buffers like `exclude_idx`, so a replayed graph sees new contents of the same shape.  Not with `items`.
         A gallery that CHANGES between submits (`live_gallery.LiveGallery`; its `full=True` views keep a captured graph valid) is updated
         under a two-line protocol -- ``pipe.fence(); live.append(rows)`` on the caller's stream: `fence` orders the update behind every
         lane still sweeping the store, and the next `submit` waits for the caller's stream, so it sees the update."""
@@ -138,6 +142,8 @@ class ComposedQueryPipeline:
         if members is not None and gallery.dtype != torch.float32:
             raise ValueError("members (subset scores) need an fp32 gallery: gather_scores has no bf16 form, and converting the "
                              "gallery per step would copy all of it")
+        if candidates is not None and items is not None:
+            raise ValueError("candidates rank rows inside a list, items rank items: give one of them")
         alone = self._runs_alone(("rank", None if images is None else tuple(images.shape), tuple(tokens.shape), tuple(gallery.shape), gallery.dtype))
         lane = self._next
         self._next = (self._next + 1) % len(self.engines)
@@ -151,7 +157,10 @@ class ComposedQueryPipeline:
             if not isinstance(items, ItemMap):
                 raise TypeError("items must be an ItemMap")
             item_ids = ItemMap(items.resolve(gallery.shape[0], eng.device), items.n_items)
-        args = (images, tokens, local, exclude_idx, members, ref_feats, mask, value)
+        cand = None
+        if candidates is not None:
+            cand = torch.as_tensor(candidates).to(device=eng.device, dtype=torch.int32).contiguous()
+        args = (images, tokens, local, exclude_idx, members, ref_feats, mask, value, cand)
         with torch.cuda.stream(stream):
             ev0 = None
             if self.timing:
@@ -165,8 +174,8 @@ class ComposedQueryPipeline:
             ev.record(stream)
         if alone:
             stream.synchronize()
-        fused, scores, idx, member_scores, item = outs
-        return QueryResult(scores, idx, fused, ev, member_scores, ev0, item)
+        fused, scores, idx, member_scores, item, place = outs
+        return QueryResult(scores, idx, fused, ev, member_scores, ev0, item, place)
 
     def submit_fuse(self, tokens: torch.Tensor, local: torch.Tensor, ref_rows: torch.Tensor, index_features: torch.Tensor) -> "FusedResult":
         """The query loop of the reference harness as ONE lane job (run/test/test_fiq.py:98-118): tokens [B,77] int64 and local
@@ -197,15 +206,18 @@ class ComposedQueryPipeline:
 
     @staticmethod
     def _step(eng, args, gallery, k, idx_offset, tags=None, items=None):
-        images, tokens, local, exclude_idx, members, ref_feats, mask, value = args
+        images, tokens, local, exclude_idx, members, ref_feats, mask, value, cand = args
         if ref_feats is None and images.shape[0] == tokens.shape[0]:
             ref, tg, ts = eng.encode_pair(images, tokens)      # both towers in one pass: the text layers' GEMMs ride in the image layers' launches (fp32 / f32x3 / mx8img)
         else:
             ref = eng.encode_image(images) if ref_feats is None else ref_feats
             tg, ts = eng.encode_text(tokens)
         fused = eng.dvr_fuse(ref, local, tg, ts)
-        item = None
-        if items is not None:                                   # item-level ranking: every k <= 1024, filtered or not
+        item = place = None
+        if cand is not None:                                    # candidate ranking: every k <= 1024, every gallery form, filtered or not
+            scores, idx, place = eng.sim_topk_candidates(fused, gallery, cand, k, idx_offset=idx_offset, exclude_idx=exclude_idx,
+                                                         row_filter=None if tags is None else RowFilter(tags, mask, value), places=True)
+        elif items is not None:                                 # item-level ranking: every k <= 1024, filtered or not
             scores, idx, item = eng.sim_topk_items(fused, gallery, items, k, idx_offset=idx_offset, exclude_idx=exclude_idx,
                                                    row_filter=None if tags is None else RowFilter(tags, mask, value))
         elif tags is not None:                                  # filtered ranking: every k <= 1024, every gallery form
@@ -217,7 +229,7 @@ class ComposedQueryPipeline:
         else:
             scores, idx = eng.sim_topk(fused, gallery, k, idx_offset=idx_offset, exclude_idx=exclude_idx)
         member_scores = eng.gather_scores(fused, gallery, members) if members is not None else None
-        return fused, scores, idx, member_scores, item
+        return fused, scores, idx, member_scores, item, place
 
     def _replay(self, lane, eng, stream, args, gallery, k, idx_offset, tags=None, items=None):
         key = tuple((tuple(a.shape), a.dtype) if a is not None else None for a in args) + (

@@ -146,6 +146,11 @@ def build_parser(kind: str) -> ArgumentParser:
         p.add_argument("--merged-gallery", action="store_true",
                        help="keep the three categories in ONE gallery (concatenated in category order, tag = category ordinal), fused and prepared "
                             "once, and rank all queries against it with a per-query row filter -- the same recalls as the three separate indexes")
+    if kind == "cirr":
+        p.add_argument("--subset-candidates", action="store_true",
+                       help="rank the target among the query's img_set members with the candidate ranking (the members are the query's list, the "
+                            "subset rank is the target's place in it: the ranking's own score bits, any gallery form) instead of gathering the "
+                            "members' scores and sorting them on the host -- the same recalls")
     if kind == "200k":
         p.add_argument("--item-level", action="store_true",
                        help="after the recalls also print the ITEM-level numbers: the items are the distinct gallery names, every item takes one "
@@ -254,7 +259,7 @@ def main(kind: str) -> None:
         triples = [(split,) + synthetic_split(kind, cfg, args.feature_dim, args.synthetic_gallery, args.synthetic_queries, args.seed + i)
                    for i, split in enumerate(splits)]
     from . import _common
-    with _common.incremental_index(args.incremental_index):
+    with _common.incremental_index(args.incremental_index), _common.cirr_subset("candidates" if getattr(args, "subset_candidates", False) else "gather"):
         results = _evaluate(kind, args, triples, clip_model, model, device, fn, say)
     avg = [mean(r[j] for r in results) for j in range(len(results[0]))]
     if kind == "cirr":

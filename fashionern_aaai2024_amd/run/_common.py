@@ -396,8 +396,30 @@ def recalls_items(model, predicted, index_fused, index_names, target_names, ks) 
     return retrieval_metrics(places.cpu().numpy(), ks)
 
 
-def recalls_cirr(model, predicted, index_fused, index_names, reference_names, target_names, group_members):
-    """CIRR: reference image removed from each ranking; global R@1/5/10/50 + subset R@1/2/3 (test_cirr.py:55-80)."""
+_cirr_subset = "gather"      # set by `cirr_subset` (the CIRR driver's --subset-candidates)
+
+
+@contextlib.contextmanager
+def cirr_subset(mode: str):
+    """While active, `recalls_cirr` calls that do not name `subset` themselves use `mode` ("gather" or "candidates")."""
+    global _cirr_subset
+    if mode not in ("gather", "candidates"):
+        raise ValueError(f"subset must be 'gather' or 'candidates', got {mode!r}")
+    saved, _cirr_subset = _cirr_subset, mode
+    try:
+        yield
+    finally:
+        _cirr_subset = saved
+
+
+def recalls_cirr(model, predicted, index_fused, index_names, reference_names, target_names, group_members, subset=None):
+    """CIRR: reference image removed from each ranking; global R@1/5/10/50 + subset R@1/2/3 (test_cirr.py:55-80).  `subset`: how the
+    target is ranked among the query's img_set members -- "gather" (the default): the members' scores are gathered and sorted on the host,
+    fp32 galleries only; "candidates": the members are the query's candidate list and the target's rank is its place in the candidate
+    ranking (FernEngine.sim_topk_candidates: the ranking's own score bits, any gallery form, nothing sorted on the host)."""
+    subset = _cirr_subset if subset is None else subset
+    if subset not in ("gather", "candidates"):
+        raise ValueError(f"subset must be 'gather' or 'candidates', got {subset!r}")
     q = len(target_names)
     eng = _engine_of(model)
     tgt = _unique_rows(index_names, target_names, "target")
@@ -413,6 +435,15 @@ def recalls_cirr(model, predicted, index_fused, index_names, reference_names, ta
         assert rows.count(tgt[i]) == 1, "target must appear exactly once among the group members (test_cirr.py:69)"
         member_rows[i, :len(rows)] = rows
     start, stop, per = _my_rows(q)
+    if subset == "candidates":
+        pl = torch.full((per if fd.world_info()[1] > 1 else q, width), -1, dtype=torch.int32, device=predicted.device)
+        if stop > start:
+            pl[: stop - start] = eng.sim_topk_candidates(predicted[start:stop], index_fused, torch.as_tensor(member_rows[start:stop], dtype=torch.int32),
+                                                         1, places=True)[2]
+        pl = fd.all_gather_shards(pl, q).cpu().numpy()
+        ranks = pl[member_rows == tgt[:, None]].astype(np.int64)      # the target appears exactly once among a query's members
+        grp = tuple(_pct((ranks < k).sum(), q) for k in (1, 2, 3))
+        return grp + glob
     sc = torch.zeros((per if fd.world_info()[1] > 1 else q, width), dtype=torch.float32, device=predicted.device)
     if stop > start:
         sc[: stop - start] = eng.gather_scores(predicted[start:stop], index_fused, torch.as_tensor(member_rows[start:stop], dtype=torch.int32))

@@ -414,6 +414,29 @@ FERN_API int fern_rank_count_filtered(fern_ctx* ctx, const float* q /*[B,D]*/, c
                                       const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D, const uint64_t* keys /*[B,m]*/,
                                       int m, int64_t idx_offset, const int32_t* exclude_idx /*[B] or NULL*/, int32_t* out_count /*[B,m]*/,
                                       const uint32_t* tags /*[N]*/, const uint32_t* mask /*[B]*/, const uint32_t* value /*[B]*/, void* stream);
+/* Candidate ranking: every query ranks inside its OWN list of gallery rows.  The reference ranks CIRR's target inside the query's named
+ * member set by the ranking's own scores (run/test/test_cirr.py:55-69); a serving process has such a set whenever a refined query is ranked
+ * over the rows an earlier page returned, or a catalogue database answers a request with a list of row ids.  A tag field cannot express a
+ * set per query (sets overlap, and there are 32 bits), and fern_gather_scores returns other score bits in no order.
+ * Query b ranks the SET of rows named by cand[b][0 .. M) (device, global row indices in the frame of idx_offset, like exclude_idx and
+ * rank targets).  An entry takes no place if it is negative, outside [idx_offset, idx_offset + N), equal to exclude_idx[b] or ineligible
+ * under the row filter (tags == NULL: unfiltered; otherwise fern_sim_topk_filtered's predicate); a row named more than once counts once.
+ * The result is the exact ranking of the whole gallery with every other row removed: the score bits the other entry points return for
+ * that (query, row) on that gallery form, the same order (score descending, global index ascending), unfilled places -inf / -1.
+ * The gallery form follows from the pointers: `gallery` given: the exact fp32 fma-chain scores in oracle/chain.c order (gallery_bf16 is
+ * ignored: a prepared gallery ranks from its fp32 rows, with or without its copy), D % 32 == 0; gallery_bf16 only: the values
+ * fern_sweep_bf16_scores produces, D % 64 == 0, D <= 768.
+ * Limits: 1 <= M <= 4096, 1 <= K <= 1024 (K may exceed M: the extra places are padded), any B >= 0, N >= 0.  A longer list is a row
+ * filter's job (fern_sim_topk_filtered) or a full ranking's.
+ * out_place (may be NULL) [B, M]: out_place[b][j] = the 0-based place of entry j in query b's candidate ranking -- the number of distinct
+ * place-taking candidates with a greater key -- or -1 if the entry takes no place; duplicates share a place.
+ * Asynchronous on `stream`, nothing read back, no workspace, graph-capturable after one warm-up call; one launch per 1024 queries. */
+FERN_API int fern_sim_topk_candidates(fern_ctx* ctx, const float* q /*[B,D]*/, const float* gallery /*[N,D] f32 or NULL*/,
+                                      const uint16_t* gallery_bf16 /*[N,D] or NULL*/, int B, int64_t N, int D,
+                                      const int32_t* cand /*[B,M] device, global indices*/, int M, int K, float* out_scores /*[B,K]*/,
+                                      int32_t* out_idx /*[B,K]*/, int32_t* out_place /*[B,M] or NULL*/, int64_t idx_offset,
+                                      const int32_t* exclude_idx /*[B] or NULL*/, const uint32_t* tags /*[N] or NULL: unfiltered*/,
+                                      const uint32_t* mask /*[B]*/, const uint32_t* value /*[B]*/, void* stream);
 /* Ranking pages: the rows at places [offset, offset + K) of a query's ranking, at any depth.  The reference's full argsort of 1 - q @ g.T
  * (run/test/test_fiq.py:49-50) answers two questions about every place: which place a named row holds -- fern_rank_keys + fern_rank_count
  * above -- and which row holds a place, which the top-K entry points answer for places 0 .. 1023 only.  These three answer the second
