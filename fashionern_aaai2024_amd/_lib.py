@@ -117,6 +117,8 @@ SIGNATURES = {
     "fern_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_float, c_void_p]),
     "fern_attention": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "fern_pooled_attention": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                      c_int, c_int, c_int, c_int, c_void_p]),
     "fern_attention_bf16": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                     c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "fern_layernorm_q": (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p, c_i64, c_i64,

@@ -191,8 +191,32 @@ extern "C" int fern_attention_bf16(fern_ctx* c, const uint16_t* q, int64_t ldq, 
     return run_attention(c, attn_desc_b(q, ldq, k, ldk, v, ldv, out, ldo, batch, heads, head_dim, s_q, s_k, causal, scale), (hipStream_t)stream);
 }
 
-// ---- the fused producers of the towers' operands (kernel-level parity tests): the launchers the blocks call, nothing else ----
 static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// One query per (image, head) over tokens whose K / V are not projected: the launch of the fp32 towers' last ViT block and of the
+// ResNet's attention pool.  Its scratch is a fresh workspace frame of this context.
+extern "C" int fern_pooled_attention(fern_ctx* c, const float* q, int64_t ldq, const float* tokens, int64_t ldt, int64_t image_stride,
+                                     const float* wk, const float* wv, const float* bv, float* out, int64_t ldo, int batch, int heads,
+                                     int head_dim, int s, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_pooled_attention: ctx is NULL");
+    if (!q || !tokens || !wk || !wv || !bv || !out) return fail(FERN_ERR_ARG, "fern_pooled_attention: NULL argument");
+    const int64_t E = (int64_t)heads * head_dim;
+    if (batch <= 0 || heads <= 0 || head_dim <= 0 || head_dim % 4 || head_dim > 128 || E > POOLED_MAX_E || s <= 0 || s > POOLED_MAX_KEYS)
+        return fail(FERN_ERR_ARG, "fern_pooled_attention: need head_dim % 4 == 0, head_dim <= 128, heads * head_dim <= " +
+                                      std::to_string(POOLED_MAX_E) + ", 1 <= s <= " + std::to_string(POOLED_MAX_KEYS));
+    if (ldq < E || ldt < E || ldo < E || ldq % 4 || ldt % 4 || ldo % 4 || image_stride % 4 || image_stride < (int64_t)(s - 1) * ldt + E)
+        return fail(FERN_ERR_ARG, "fern_pooled_attention: need ldq, ldt, ldo >= heads * head_dim, strides % 4 == 0, image_stride >= (s - 1) * ldt + heads * head_dim");
+    if (misaligned16(q) || misaligned16(tokens) || misaligned16(wk) || misaligned16(wv) || misaligned16(bv) || misaligned16(out))
+        return fail(FERN_ERR_ARG, "fern_pooled_attention: pointers must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    const hipStream_t st = (hipStream_t)stream;
+    FERN_TRY(ws_begin(c, st));
+    PooledAttnParams a{q, (long)ldq, tokens, (long)ldt, (long)image_stride, wk, wv, (long)E, bv, out, (long)ldo, nullptr, nullptr,
+                       batch, heads, head_dim, s, 1.0f / std::sqrt((float)head_dim)};
+    return run_pooled_attention(c, a, st);
+}
+
+// ---- the fused producers of the towers' operands (kernel-level parity tests): the launchers the blocks call, nothing else ----
 
 extern "C" int fern_layernorm_q(fern_ctx* c, const void* x, int x_is_bf16, int64_t ldx, const float* gamma, const float* beta, int out_form,
                                 void* y, int64_t ldy, void* scales, int64_t scale_rows, int64_t rows, int d, float eps, void* stream) {

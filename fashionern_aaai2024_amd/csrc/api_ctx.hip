@@ -343,6 +343,21 @@ int fern::api::run_attention(fern_ctx* c, const AttnParams& a, hipStream_t s) {
     HIP_TRY_PROF(le, c, slot);
     return prof_close(c, slot, s);
 }
+// The pooled single-query attention (attn.hip): its two [batch, heads, E] scratch rows come from the arena, its three dispatches are ONE
+// attention record priced at the flops they do: the fold and the value projection (2 b E^2 each), the scores and the weighted token
+// sum (2 b heads S E each).  p.qt / p.u are filled in here.
+int fern::api::run_pooled_attention(fern_ctx* c, const PooledAttnParams& p, hipStream_t s) {
+    PooledAttnParams a = p;
+    const double E = (double)a.heads * a.hd;
+    if (a.batch <= 0 || a.heads <= 0 || a.hd <= 0) return fail(FERN_ERR_ARG, "pooled attention: bad shape");
+    FERN_TRY(ws_get(c, (size_t)a.batch * a.heads * (size_t)E, &a.qt));
+    FERN_TRY(ws_get(c, (size_t)a.batch * a.heads * (size_t)E, &a.u));
+    int slot;
+    FERN_TRY(prof_open(c, PROF_ATTN, 4.0 * a.batch * E * E + 4.0 * a.batch * a.heads * (double)a.S * E, s, &slot, a.batch * a.heads, 1, (int)E, 2));
+    const hipError_t le = launch_pooled_attention(a, s);
+    HIP_TRY_PROF(le, c, slot);
+    return prof_close(c, slot, s);
+}
 
 // ---- precision and activation of the CLIP towers --------------------------------------------------------------------------------
 extern "C" int fern_set_precision(fern_ctx* c, int precision) {

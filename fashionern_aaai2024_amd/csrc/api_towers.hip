@@ -193,9 +193,11 @@ static int tower_block(fern_ctx* c, const Tower& T, int l, hipStream_t s) {
 }
 
 // Last ViT block: only the class token is consumed afterwards (ln_post on token 0, modeling_clip.py:876-877), so
-// K/V are projected for every token but Q, the attention output, out_proj and the MLP run for the class rows only.
-// Equal to the full block on the rows that are read only to TOLERANCE since round 5: the single-query attention kernel and the
-// 512-wide split-K c_proj add their products in another order than the full block's kernels (fp32 parity mode included).
+// Q, the attention output, out_proj and the MLP run for the class rows only.  The reduced forms project K/V for every token; the fp32
+// forms do not project them at all: with one query per (image, head) both projections fold into the query and the output (attn.hip:
+// pooled single-query attention -- exact algebra, the key bias cancels in the softmax).
+// Equal to the full block on the rows that are read only to TOLERANCE since round 5, and still: the single-query attention (folded or
+// not) and the 512-wide split-K c_proj add their products in another order than the full block's kernels (fp32 parity mode included).
 // V.Xb (FERN_PREC_MX8 with its bf16 residual stream): the stream itself -- the token-level LayerNorm reads it as the full blocks do and
 // only the class rows are widened to fp32 (X is then not read: round 5 dropped the 58 MB bf16 -> fp32 pass over the whole stream).
 static int clip_block_cls_only(fern_ctx* c, const Tower& V, const ClipBlockW& Bk, float* CLS /*[b,width] out*/, float* T0 /*[b,width]*/,
@@ -207,12 +209,18 @@ static int clip_block_cls_only(fern_ctx* c, const Tower& V, const ClipBlockW& Bk
     LinearW kv{Bk.qkv.w + (size_t)width * width, Bk.qkv.b + width, 2 * width, width, Bk.qkv.wb + (size_t)width * width,
                Bk.qkv.w8 ? Bk.qkv.w8 + (size_t)width * width : nullptr, Bk.qkv.sw ? Bk.qkv.sw + width : nullptr,
                Bk.qkv.wm ? Bk.qkv.wm + (size_t)width * width : nullptr, Bk.qkv.swm ? Bk.qkv.swm + (size_t)width * 4 : nullptr, Bk.qkv.swm_rows};
-    // token-level ln_1 and the K/V projection of all tokens (fp32 output) in the attention half's form; this block stays BF16 under
-    // FERN_PREC_MX8_IMG as under FERN_PREC_MX8_MLP
+    // token-level ln_1 in the attention half's form; this block stays BF16 under FERN_PREC_MX8_IMG as under FERN_PREC_MX8_MLP
     const Form f = c->precision == FERN_PREC_MX8_IMG ? BF16 : V.attn;
-    GemmParams pk;
-    FERN_TRY(ln_gemm(V, f, Bk.ln1, kv, QKV + width, 3 * width, EPI_BIAS, false, s, &pk));
-    FERN_TRY(run_gemm_form(c, f, pk, s));                                                              // K, V for all tokens
+    // The fp32 data flow (fp32, f32x3) attends over ln_1(x) itself and never projects K / V; the reduced forms (their oracles restate the
+    // rounding points of the projected K / V) and shapes past the pooled kernels' limits project them for every token (fp32 output).
+    const bool pooled = f == F32 && S <= POOLED_MAX_KEYS && width <= POOLED_MAX_E && hd <= 128;
+    if (pooled) {
+        HIP_TRY(launch_layernorm(X, nullptr, Bk.ln1.g, Bk.ln1.b, V.XN, V.R(), width, width, width, 1e-5f, s));
+    } else {
+        GemmParams pk;
+        FERN_TRY(ln_gemm(V, f, Bk.ln1, kv, QKV + width, 3 * width, EPI_BIAS, false, s, &pk));
+        FERN_TRY(run_gemm_form(c, f, pk, s));                                                          // K, V for all tokens
+    }
     if (f == F32) {
         HIP_TRY(launch_gather_rows(V.XN, width, T0, width, batch, width, 1, S, 0, nullptr, s));        // ln_1(x)[:, 0]
     } else {      // the class-row chain below stays fp32 in every form
@@ -222,10 +230,17 @@ static int clip_block_cls_only(fern_ctx* c, const Tower& V, const ClipBlockW& Bk
     }
     LinearW qw{Bk.qkv.w, Bk.qkv.b, width, width};
     FERN_TRY(run_gemm(c, gemm_desc(T0, width, qw, T1, width, batch, EPI_BIAS), s));                    // Q for the class rows
-    // one query per (batch, head): q rows are [batch, 1]; K/V are read in place from the packed buffer
-    AttnParams a{T1, QKV + width, QKV + 2 * width, T0, (long)width, 3L * width, 3L * width, (long)width,
-                 batch, heads, hd, 1, S, 0, 1.0f / std::sqrt((float)hd)};
-    FERN_TRY(run_attention(c, a, s));
+    if (pooled) {
+        // one query per (batch, head) over ln_1(x) itself: K / V of the tokens are never formed (attn.hip: the pooled single-query attention)
+        PooledAttnParams a{T1, (long)width, V.XN, (long)width, (long)S * width, kv.w, kv.w + (size_t)width * width, (long)width, kv.b + width,
+                           T0, (long)width, nullptr, nullptr, batch, heads, hd, S, 1.0f / std::sqrt((float)hd)};
+        FERN_TRY(run_pooled_attention(c, a, s));
+    } else {
+        // one query per (batch, head): q rows are [batch, 1]; K/V are read in place from the packed buffer
+        AttnParams a{T1, QKV + width, QKV + 2 * width, T0, (long)width, 3L * width, 3L * width, (long)width,
+                     batch, heads, hd, 1, S, 0, 1.0f / std::sqrt((float)hd)};
+        FERN_TRY(run_attention(c, a, s));
+    }
     if (Xb) HIP_TRY(launch_gather_rows_bf16(Xb, width, CLS, width, batch, width, S, s));               // residual x[:, 0]
     else HIP_TRY(launch_gather_rows(X, width, CLS, width, batch, width, 1, S, 0, nullptr, s));
     GemmParams po = gemm_desc(T0, width, Bk.out, CLS, width, batch, EPI_BIAS_RESIDUAL);
@@ -393,7 +408,7 @@ static int resnet_chunk(fern_ctx* c, const float* images, float* out, int b, hip
     }
     {
         const int hf = S / 32;
-        max_act = std::max(max_act, (size_t)b * (hf * hf + 1) * 2 * (size_t)(w * 32));      // attention-pool K/V
+        max_act = std::max(max_act, (size_t)b * (hf * hf + 1) * (size_t)(w * 32));      // attention-pool token rows (their K/V are never formed)
     }
     float* buf[6];
     for (auto& p : buf) FERN_TRY(ws_get(c, max_act, &p));
@@ -431,12 +446,13 @@ static int resnet_chunk(fern_ctx* c, const float* images, float* out, int b, hip
     }
     // AttentionPool2d: NHWC rows of one image are already its HW tokens
     const int HW = H * H, E = w * 32, heads = cf.r_heads, hd = E / heads;
-    float *T = buf[2], *T0 = buf[3], *MEAN = buf[3] + (size_t)b * E, *KV = buf[4], *Q = buf[5], *ATT = buf[5] + (size_t)b * E;
+    float *T = buf[2], *T0 = buf[3], *MEAN = buf[3] + (size_t)b * E, *Q = buf[5], *ATT = buf[5] + (size_t)b * E;
     HIP_TRY(launch_attnpool_tokens(X, MEAN, R.pos, T, T0, b, HW, E, s));
-    FERN_TRY(run_gemm(c, gemm_desc(T, E, R.kv, KV, 2 * E, b * (HW + 1), EPI_BIAS), s));
     FERN_TRY(run_gemm(c, gemm_desc(T0, E, R.q, Q, E, b, EPI_BIAS), s));
-    AttnParams a{Q, KV, KV + E, ATT, (long)E, 2L * E, 2L * E, (long)E, b, heads, hd, 1, HW + 1, 0, 1.0f / std::sqrt((float)hd)};
-    FERN_TRY(run_attention(c, a, s));
+    // one query per (image, head) over the token rows themselves (attn.hip: the pooled single-query attention)
+    PooledAttnParams a{Q, (long)E, T, (long)E, (long)(HW + 1) * E, R.kv.w, R.kv.w + (size_t)E * E, (long)E, R.kv.b + E,
+                       ATT, (long)E, nullptr, nullptr, b, heads, hd, HW + 1, 1.0f / std::sqrt((float)hd)};
+    FERN_TRY(run_pooled_attention(c, a, s));
     return run_gemm(c, gemm_desc(ATT, E, R.cproj, out, cf.embed_dim, b, EPI_BIAS), s);
 }
 

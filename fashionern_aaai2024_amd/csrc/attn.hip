@@ -582,6 +582,233 @@ __global__ __launch_bounds__(256) void attn_f32_single_query_kernel(AttnParams p
     if (wave == 0 && lane < hd)
         p.out[(long)b * p.ldo + (long)h * hd + lane] = (((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane]) * (1.0f / sum);
 }
+
+// ---- ONE query per (image, head) over UNPROJECTED tokens (clip_block_cls_only in the fp32 forms, the ResNet's attention pool) ---------
+// With a single query the K / V projections of every token fold into the query and into the output:
+//   q_h . (Wk_h t_j + bk_h) = (Wk_h^T q_h) . t_j + const   (softmax drops the constant: no key bias anywhere below)
+//   sum_j p_j (Wv_h t_j + bv_h) = Wv_h (sum_j p_j t_j) + bv_h   (sum_j p_j = 1)
+// Three dispatches: fold (qt = scale Wk_h^T q_h), scores + softmax + weighted token sum (u), value projection (out = bv + Wv_h u).
+// Every sum has one order, a function of (S, E, heads) alone: a lane adds its columns (keys, d) in ascending order, 64 lanes combine in
+// the xor tree (lane_fold), waves combine in wave order.  Rows of a batch tile share loads and nothing else, so a row's bits do not
+// depend on the batch.
+static_assert(POOLED_MAX_KEYS == SQ1_MAX_KEYS, "the pooled form takes the key counts of the single-query kernel");
+
+// The xor-tree sum over 64 lanes of N values per lane at once: a step exchanges half of the values and keeps the other half, so N values
+// cost N - 1 + (steps left at one value) shuffles instead of 6 N.  Each value's tree is the one of `v += __shfl_xor(v, m)`, m = 32 .. 1
+// (an addition's two operands only swap sides).  Afterwards v[0] of lane L is the total of value index
+// (L & 32 ? N/2 : 0) + (L & 16 ? N/4 : 0) + ... (terms while the count is above one).
+template <int N, int M>
+__device__ __forceinline__ void lane_fold(float* v, int lane) {
+    if constexpr (M >= 1) {
+        if constexpr (N > 1) {
+            constexpr int H = N / 2;
+            const bool up = (lane & M) != 0;
+#pragma unroll
+            for (int i = 0; i < H; ++i) {
+                const float send = up ? v[i] : v[i + H];
+                const float keep = up ? v[i + H] : v[i];
+                v[i] = keep + __shfl_xor(send, M);
+            }
+            lane_fold<H, M / 2>(v, lane);
+        } else {
+            v[0] += __shfl_xor(v[0], M);
+            lane_fold<1, M / 2>(v, lane);
+        }
+    }
+}
+__device__ __forceinline__ float dot4_acc(const float4& a, const float4& b, float acc) {      // ascending column order
+    acc = __builtin_fmaf(a.x, b.x, acc);
+    acc = __builtin_fmaf(a.y, b.y, acc);
+    acc = __builtin_fmaf(a.z, b.z, acc);
+    return __builtin_fmaf(a.w, b.w, acc);
+}
+__device__ __forceinline__ void axpy4(float a, const float4& x, float4& y) {
+    y.x = __builtin_fmaf(a, x.x, y.x);
+    y.y = __builtin_fmaf(a, x.y, y.y);
+    y.z = __builtin_fmaf(a, x.z, y.z);
+    y.w = __builtin_fmaf(a, x.w, y.w);
+}
+
+constexpr int POOL_BT = 16;      // images per workgroup of the fold and of the value projection: they share one read of the weight rows
+constexpr int POOL_HG = 4;       // heads per workgroup of the token passes: they share one read of the image's tokens
+constexpr int POOL_NW = 8;       // waves of a token-pass workgroup
+
+// Fold: qt[b, h, e] = scale * sum_d q[b, h hd + d] Wk[h hd + d, e], d ascending.  One wave per (batch tile, 256 columns, head); lane = 4
+// columns, so a weight row is read as it lies.
+__global__ __launch_bounds__(64) void pooled_fold_kernel(PooledAttnParams p) {
+    __shared__ float qs[POOL_BT * 128];
+    const int lane = threadIdx.x, b0 = blockIdx.x * POOL_BT, h = blockIdx.z, hd = p.hd, E = p.heads * hd;
+    for (int idx = lane; idx < POOL_BT * hd; idx += 64) {
+        const int i = idx / hd, d = idx - i * hd;
+        const int b = b0 + i < p.batch ? b0 + i : p.batch - 1;
+        qs[idx] = p.q[(long)b * p.ldq + (long)h * hd + d];
+    }
+    __syncthreads();
+    const int col = blockIdx.y * 256 + lane * 4;
+    if (col >= E) return;
+    float4 acc[POOL_BT];
+#pragma unroll
+    for (int i = 0; i < POOL_BT; ++i) acc[i] = float4{0.f, 0.f, 0.f, 0.f};
+    const float* w = p.wk + (long)h * hd * p.ldw + col;
+#pragma unroll 4
+    for (int d = 0; d < hd; ++d) {
+        const float4 w4 = *reinterpret_cast<const float4*>(w + (long)d * p.ldw);
+#pragma unroll
+        for (int i = 0; i < POOL_BT; ++i) axpy4(qs[i * hd + d], w4, acc[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < POOL_BT; ++i) {
+        if (b0 + i >= p.batch) break;
+        const float4 r{acc[i].x * p.scale, acc[i].y * p.scale, acc[i].z * p.scale, acc[i].w * p.scale};
+        *reinterpret_cast<float4*>(p.qt + ((long)(b0 + i) * p.heads + h) * E + col) = r;
+    }
+}
+
+// Scores, softmax and the weighted token sum of one (image, group of POOL_HG heads): u[b, h, :] = sum_j p_j t[b, j, :].  Lane = 4 columns
+// of a 256-column chunk.  Scores: a wave takes four keys at a time and walks the chunks in ascending order against the group's folded
+// queries (LDS); the 16 (key, head) partials of a lane go through one lane_fold.  Weighted sum: per chunk wave w adds keys w, w + 8, ...
+// in ascending order, the eight partial rows are added in wave order and scaled by 1 / sum.  Both passes read the image's tokens
+// (0.6 - 0.8 MB: L2) once per head group.
+__global__ __launch_bounds__(POOL_NW * 64) void pooled_tokens_kernel(PooledAttnParams p) {
+    extern __shared__ __align__(16) float pool_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x, h0 = blockIdx.y * POOL_HG, S = p.S, E = p.heads * p.hd;
+    float* qs = pool_lds;                                  // [POOL_HG][E]
+    float* red = qs + (size_t)POOL_HG * E;                 // [POOL_NW][POOL_HG][256]
+    float* sc = red + POOL_NW * POOL_HG * 256;             // [POOL_HG][S]
+    float* sinv = sc + (size_t)POOL_HG * S;                // [POOL_HG]
+    // a group past the last head repeats it (loads stay unconditional); its rows are not stored
+    for (int idx = tid * 4; idx < POOL_HG * E; idx += POOL_NW * 256) {
+        const int g = idx / E, e = idx - g * E;
+        const int h = h0 + g < p.heads ? h0 + g : p.heads - 1;
+        *reinterpret_cast<float4*>(qs + idx) = *reinterpret_cast<const float4*>(p.qt + ((long)b * p.heads + h) * E + e);
+    }
+    __syncthreads();
+    const float* tb = p.tok + (long)b * p.img_stride;
+    for (int j0 = wave * 4; j0 < S; j0 += POOL_NW * 4) {
+        float acc[4 * POOL_HG];
+#pragma unroll
+        for (int i = 0; i < 4 * POOL_HG; ++i) acc[i] = 0.f;
+        const float* tr[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) tr[u] = tb + (long)(j0 + u < S ? j0 + u : S - 1) * p.ldt;
+        for (int c = lane * 4; c < E; c += 256) {
+            float4 t4[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) t4[u] = *reinterpret_cast<const float4*>(tr[u] + c);
+#pragma unroll
+            for (int g = 0; g < POOL_HG; ++g) {
+                const float4 q4 = *reinterpret_cast<const float4*>(qs + (size_t)g * E + c);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) acc[u * POOL_HG + g] = dot4_acc(q4, t4[u], acc[u * POOL_HG + g]);
+            }
+        }
+        lane_fold<4 * POOL_HG, 32>(acc, lane);
+        const int idx = (lane >> 2) & 15, j = j0 + idx / POOL_HG;
+        if ((lane & 3) == 0 && j < S) sc[(idx % POOL_HG) * S + j] = acc[0];
+    }
+    __syncthreads();
+    if (wave < POOL_HG) {      // softmax statistics of head `wave`: lane-strided, then the xor tree
+        float* s = sc + (size_t)wave * S;
+        float mx = -INFINITY;
+        for (int j = lane; j < S; j += 64) mx = fmaxf(mx, s[j]);
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
+        float sum = 0.f;
+        for (int j = lane; j < S; j += 64) {
+            const float e = expf(s[j] - mx);
+            s[j] = e;
+            sum += e;
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m);
+        if (lane == 0) sinv[wave] = 1.0f / sum;
+    }
+    __syncthreads();
+    for (int c0 = 0; c0 < E; c0 += 256) {
+        const int c = c0 + lane * 4;
+        float4 acc[POOL_HG];
+#pragma unroll
+        for (int g = 0; g < POOL_HG; ++g) acc[g] = float4{0.f, 0.f, 0.f, 0.f};
+        if (c < E) {
+#pragma unroll 4
+            for (int j = wave; j < S; j += POOL_NW) {
+                const float4 t4 = *reinterpret_cast<const float4*>(tb + (long)j * p.ldt + c);
+#pragma unroll
+                for (int g = 0; g < POOL_HG; ++g) axpy4(sc[g * S + j], t4, acc[g]);
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < POOL_HG; ++g) *reinterpret_cast<float4*>(red + ((wave * POOL_HG + g) * 256 + lane * 4)) = acc[g];
+        __syncthreads();
+        for (int o = tid; o < POOL_HG * 256; o += POOL_NW * 64) {
+            const int g = o >> 8, cl = o & 255;
+            if (c0 + cl < E && h0 + g < p.heads) {
+                float sum = red[g * 256 + cl];
+#pragma unroll
+                for (int w = 1; w < POOL_NW; ++w) sum += red[(w * POOL_HG + g) * 256 + cl];
+                p.u[((long)b * p.heads + h0 + g) * E + c0 + cl] = sum * sinv[g];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Value projection: out[b, h hd + d] = bv[h hd + d] + Wv[h hd + d, :] . u[b, h, :].  A wave holds 4 weight rows x POOL_BT images; lane = 4
+// columns of a 256-column chunk, chunks ascending; the 64 partials of a lane go through one lane_fold, which leaves value (row r, image i)
+// in lane 16 r + i.
+__global__ __launch_bounds__(256) void pooled_vproj_kernel(PooledAttnParams p) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b0 = blockIdx.x * POOL_BT, d0 = blockIdx.y * 16 + wave * 4, h = blockIdx.z, hd = p.hd, E = p.heads * hd;
+    if (d0 >= hd) return;
+    float acc[4 * POOL_BT];
+#pragma unroll
+    for (int i = 0; i < 4 * POOL_BT; ++i) acc[i] = 0.f;
+    const float* wr[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wr[r] = p.wv + ((long)h * hd + (d0 + r < hd ? d0 + r : hd - 1)) * p.ldw;
+    const float* ur[POOL_BT];
+#pragma unroll
+    for (int i = 0; i < POOL_BT; ++i) ur[i] = p.u + ((long)(b0 + i < p.batch ? b0 + i : p.batch - 1) * p.heads + h) * E;
+    for (int c = lane * 4; c < E; c += 256) {
+        float4 w4[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) w4[r] = *reinterpret_cast<const float4*>(wr[r] + c);
+#pragma unroll
+        for (int i = 0; i < POOL_BT; ++i) {
+            const float4 u4 = *reinterpret_cast<const float4*>(ur[i] + c);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r * POOL_BT + i] = dot4_acc(w4[r], u4, acc[r * POOL_BT + i]);
+        }
+    }
+    lane_fold<4 * POOL_BT, 32>(acc, lane);
+    const int d = d0 + lane / POOL_BT, b = b0 + lane % POOL_BT;
+    if (d < hd && b < p.batch) p.out[(long)b * p.ldo + (long)h * hd + d] = p.bv[h * hd + d] + acc[0];
+}
+
+hipError_t launch_pooled_attention(const PooledAttnParams& p, hipStream_t s) {
+    const long E = (long)p.heads * p.hd;
+    if (p.batch <= 0 || p.heads <= 0 || p.hd <= 0 || (p.hd & 3) || p.hd > 128 || E > POOLED_MAX_E || p.S <= 0 || p.S > POOLED_MAX_KEYS)
+        return hipErrorInvalidValue;
+    if ((p.ldq & 3) || (p.ldt & 3) || (p.img_stride & 3) || (p.ldw & 3) || (p.ldo & 3) || p.ldq < E || p.ldt < E || p.ldw < E || p.ldo < E)
+        return hipErrorInvalidValue;
+    for (const void* ptr : {(const void*)p.q, (const void*)p.tok, (const void*)p.wk, (const void*)p.wv, (const void*)p.bv, (const void*)p.out,
+                            (const void*)p.qt, (const void*)p.u})
+        if (!ptr || (reinterpret_cast<uintptr_t>(ptr) & 15)) return hipErrorInvalidValue;
+    const unsigned bt = (p.batch + POOL_BT - 1) / POOL_BT, ec = (unsigned)((E + 255) / 256);
+    const size_t lds = sizeof(float) * ((size_t)POOL_HG * E + POOL_NW * POOL_HG * 256 + (size_t)POOL_HG * p.S + POOL_HG);
+    static size_t lds_allowed = 48 * 1024;
+    if (lds > lds_allowed) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(pooled_tokens_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        lds_allowed = lds;
+    }
+    FERN_LAUNCH(pooled_fold_kernel, dim3(bt, ec, p.heads), dim3(64), 0, s, p);
+    FERN_LAUNCH(pooled_tokens_kernel, dim3(p.batch, (p.heads + POOL_HG - 1) / POOL_HG), dim3(POOL_NW * 64), lds, s, p);
+    FERN_LAUNCH(pooled_vproj_kernel, dim3(bt, (p.hd + 15) / 16, p.heads), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_attention(const AttnParams& p, hipStream_t s) {
     if (p.batch <= 0 || p.heads <= 0 || p.s_q <= 0 || p.s_k <= 0 || p.s_k > ATTN_MAX_KEYS) return hipErrorInvalidValue;
     if (p.causal && p.s_q != p.s_k) return hipErrorInvalidValue;

@@ -188,6 +188,7 @@ int run_gemm_pair(fern_ctx* c, const GemmParams& p1, const GemmParams& p2, hipSt
 int run_gemm_b(fern_ctx* c, const GemmParams& p, hipStream_t s);
 int run_gemm_b_pair(fern_ctx* c, const GemmParams& p1, const GemmParams& p2, hipStream_t s);
 int run_attention(fern_ctx* c, const AttnParams& a, hipStream_t s);
+int run_pooled_attention(fern_ctx* c, const PooledAttnParams& p, hipStream_t s);      // qt / u come from the arena
 GemmParams gemm_desc(const float* A, long lda, const LinearW& L, float* C, long ldc, int M, int epi);
 GemmParams gemm_desc_b(const unsigned short* A, long lda, const LinearW& L, void* C, long ldc, int M, int epi, bool out_bf16);
 GemmParams gemm_desc_f8(const unsigned char* A8, const float* sa, long lda, const LinearW& L, void* C, long ldc, int M, int epi, bool out_bf16);

@@ -327,6 +327,21 @@ struct AttnParams {
 };
 constexpr int ATTN_MAX_KEYS = 4096;      // validation bound of the non-causal forms (causal: 96, the text context)
 hipError_t launch_attention(const AttnParams& p, hipStream_t s);   // hipErrorInvalidValue for unsupported shapes
+// ONE query per (image, head) over tokens whose K / V were never projected (attn.hip: pooled single-query attention):
+// out[b, h hd + d] = bv[h hd + d] + Wv[h hd + d, :] . sum_j softmax_j(scale (Wk_h^T q_h) . t_j) t_j.  The key bias is the same for every key
+// of a softmax, so it has no argument.  E = heads * hd.
+struct PooledAttnParams {
+    const float* q; long ldq;                    // [batch, E] projected queries, bias included
+    const float* tok; long ldt, img_stride;      // [batch, S, E] tokens: row stride, per-image stride (floats)
+    const float* wk; const float* wv; long ldw;  // [E, E] rows of the in-proj weight in their native [out, in] layout
+    const float* bv;                             // [E]
+    float* out; long ldo;                        // [batch, E], heads concatenated
+    float* qt; float* u;                         // scratch [batch, heads, E] each: the folded queries, the weighted token sums
+    int batch, heads, hd, S;
+    float scale;
+};
+constexpr int POOLED_MAX_KEYS = 1024, POOLED_MAX_E = 4096;
+hipError_t launch_pooled_attention(const PooledAttnParams& p, hipStream_t s);   // three dispatches; hipErrorInvalidValue for unsupported shapes
 
 // ---- row-wise / element-wise kernels (elem.hip) -------------------------------------------------
 hipError_t launch_layernorm(const float* x, const float* res, const float* gamma, const float* beta, float* y,

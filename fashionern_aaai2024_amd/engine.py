@@ -991,6 +991,17 @@ class FernEngine:
                                            int(bool(causal)), sc, _stream()), "fern_attention")
         return out
 
+    def pooled_attention(self, q, tokens, wk, wv, bv, heads: int) -> torch.Tensor:
+        """One query per (image, head) over unprojected tokens (include/fern.h: fern_pooled_attention): q [B,E] (projected, bias
+        included), tokens [B,S,E], wk / wv [E,E] in [out, in] layout, bv [E] -> [B,E]."""
+        q, tokens = self._f32(q), self._f32(tokens)
+        b, s, e = tokens.shape
+        wk, wv, bv = self._f32(wk, (e, e)), self._f32(wv, (e, e)), self._f32(bv, (e,))
+        out = torch.empty_like(q)
+        _lib.check(self.lib.fern_pooled_attention(self._h, _ptr(q), e, _ptr(tokens), e, s * e, _ptr(wk), _ptr(wv), _ptr(bv), _ptr(out), e,
+                                                  b, heads, e // heads, s, _stream()), "fern_pooled_attention")
+        return out
+
     def attention_bf16(self, q, k, v, heads: int, causal=False, scale=None) -> torch.Tensor:
         """bf16 operand form of `attention`: q/k/v bf16 [B,S,W] (fp32 inputs are rounded first) -> bf16 [B,Sq,W]."""
         def b16(x):

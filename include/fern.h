@@ -629,6 +629,18 @@ FERN_API int fern_layernorm(fern_ctx* ctx, const float* x, const float* residual
 FERN_API int fern_attention(fern_ctx* ctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
                    int64_t ldv, float* out, int64_t ldo, int batch, int heads, int head_dim, int s_q,
                    int s_k, int causal, float scale, void* stream);
+/* Attention of ONE query per (image, head) over tokens whose keys and values are NOT projected: what the last ViT block (class token)
+ * and the ModifiedResNet's attention pool run in the fp32 data flow.  With E = heads * head_dim:
+ *   out[b, h hd + d] = bv[h hd + d] + Wv[h hd + d, :] . sum_j p_j t[b, j, :],   p = softmax_j((Wk_h^T q[b, h]) . t[b, j, :] / sqrt(hd))
+ * which equals softmax(q (t Wk^T + bk)^T / sqrt(hd)) (t Wv^T + bv) for every key bias bk (a constant per softmax), so none is taken.
+ * q [batch, E] is the projected query, its bias included; tokens [batch, s, E] with row stride ldt and image stride image_stride
+ * (floats); wk, wv [E, E] are the key and value rows of the in-proj weight in their [out, in] layout, leading dimension E; bv [E];
+ * out [batch, E].  head_dim % 4 == 0, <= 128; E <= 4096; 1 <= s <= 1024; ldq, ldt, ldo >= E, every stride % 4 == 0, pointers 16-byte
+ * aligned.  Every sum has one order that depends on (s, E, heads) alone: a row's bits do not depend on the batch around it.  The
+ * scratch is a fresh workspace frame of ctx; no host synchronisation. */
+FERN_API int fern_pooled_attention(fern_ctx* ctx, const float* q, int64_t ldq, const float* tokens, int64_t ldt, int64_t image_stride,
+                   const float* wk, const float* wv, const float* bv, float* out, int64_t ldo, int batch, int heads,
+                   int head_dim, int s, void* stream);
 /* bf16 operand form (perf mode of the CLIP towers): q/k/v/out hold bf16 bit patterns (strides in elements, % 8 == 0);
  * QK^T and PV on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, `scale` applied to the fp32 scores, softmax statistics
  * in fp32, the un-normalised weights rounded to bf16 for the PV product.  head_dim % 8 == 0, <= 96; s_k <= 4096 (causal: <= 96),
