@@ -126,6 +126,11 @@ SIGNATURES = {
     "fern_attention_mx8": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64,
                                    c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "fern_im2col_q": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p]),
+    "fern_conv3x3_nhwc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fern_conv1x1_nhwc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fern_stem_conv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fern_avgpool_nhwc": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fern_attnpool_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "fern_prof_enable": (c_int, [c_void_p, c_int]),
     "fern_prof_collect": (c_int, [c_void_p, C.POINTER(ProfStats)]),
     "fern_tuner_export": (c_i64, [C.c_char_p, c_i64]),

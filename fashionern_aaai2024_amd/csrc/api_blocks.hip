@@ -287,3 +287,88 @@ extern "C" int fern_im2col_q(fern_ctx* c, const float* images, int b, int img, i
                                   (hipStream_t)stream));
     return FERN_OK;
 }
+
+// ---- the ModifiedResNet's kernels (kernel-level parity tests): the tower's own descriptors and launchers behind an argument check ----
+
+// b * H * W pixel rows as an int, or -1
+static int pixel_rows(int b, int H, int W) {
+    const int64_t m = (int64_t)b * H * W;
+    return m > INT32_MAX ? -1 : (int)m;
+}
+
+extern "C" int fern_conv3x3_nhwc(fern_ctx* c, const float* x, const float* w, const float* bias, float* out, int b, int H, int W, int cin, int cout,
+                                 void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_conv3x3_nhwc: ctx is NULL");
+    if (b < 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0) return fail(FERN_ERR_ARG, "fern_conv3x3_nhwc: bad argument");
+    if (b == 0) return FERN_OK;
+    if (!x || !w || !bias || !out) return fail(FERN_ERR_ARG, "fern_conv3x3_nhwc: NULL argument");
+    const int M = pixel_rows(b, H, W);
+    if (cin % 16 || cin > INT32_MAX / 9 || M < 0) return fail(FERN_ERR_ARG, "fern_conv3x3_nhwc: need cin % 16 == 0 and b * H * W < 2^31");
+    if (misaligned16(x) || misaligned16(w)) return fail(FERN_ERR_ARG, "fern_conv3x3_nhwc: x and w must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    const hipStream_t st = (hipStream_t)stream;
+    // the out-of-image taps' source: the finalised tower uploads one with its weights, here it is a zeroed piece of a fresh workspace frame
+    float* zeros;
+    FERN_TRY(ws_begin(c, st));
+    FERN_TRY(ws_get(c, (size_t)64, &zeros));
+    HIP_TRY(hipMemsetAsync(zeros, 0, 64 * sizeof(float), st));
+    const ConvW cw{w, bias, cout, 9 * cin};
+    return run_gemm(c, conv3x3_desc(x, cw, out, b, H, W, cin, zeros), st);
+}
+
+extern "C" int fern_conv1x1_nhwc(fern_ctx* c, const float* x, const float* w, const float* bias, const float* residual, float* out, int M, int cin,
+                                 int cout, int relu, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_conv1x1_nhwc: ctx is NULL");
+    if (M < 0 || cin <= 0 || cout <= 0) return fail(FERN_ERR_ARG, "fern_conv1x1_nhwc: bad argument");
+    if (M == 0) return FERN_OK;
+    if (!x || !w || !bias || !out) return fail(FERN_ERR_ARG, "fern_conv1x1_nhwc: NULL argument");
+    if (residual && !relu) return fail(FERN_ERR_ARG, "fern_conv1x1_nhwc: a residual is added before the ReLU only (fern_gemm has BIAS_RESIDUAL)");
+    if (cin % 16) return fail(FERN_ERR_ARG, "fern_conv1x1_nhwc: need cin % 16 == 0");
+    if (misaligned16(x) || misaligned16(w)) return fail(FERN_ERR_ARG, "fern_conv1x1_nhwc: x and w must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    const ConvW cw{w, bias, cout, cin};
+    GemmParams p = conv_desc(x, cw, out, M, residual ? EPI_BIAS_RESIDUAL_RELU : relu ? EPI_BIAS_RELU : EPI_BIAS);
+    p.R = residual;
+    return run_gemm(c, p, (hipStream_t)stream);
+}
+
+extern "C" int fern_stem_conv(fern_ctx* c, const float* images, const float* w, const float* bias, float* out, int b, int S, int cout_pad,
+                              void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_stem_conv: ctx is NULL");
+    if (b < 0 || S <= 0 || cout_pad <= 0) return fail(FERN_ERR_ARG, "fern_stem_conv: bad argument");
+    if (b == 0) return FERN_OK;
+    if (!images || !w || !bias || !out) return fail(FERN_ERR_ARG, "fern_stem_conv: NULL argument");
+    if (S % 2 || cout_pad % 4 || pixel_rows(b, S / 2, S / 2) < 0) return fail(FERN_ERR_ARG, "fern_stem_conv: need S % 2 == 0, cout_pad % 4 == 0 and b * (S / 2)^2 < 2^31");
+    if (misaligned16(bias) || misaligned16(out)) return fail(FERN_ERR_ARG, "fern_stem_conv: bias and out must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_stem_conv(images, w, bias, out, b, S, cout_pad, (hipStream_t)stream));
+    return FERN_OK;
+}
+
+extern "C" int fern_avgpool_nhwc(fern_ctx* c, const float* x, float* y, int b, int H, int W, int C, int k, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_avgpool_nhwc: ctx is NULL");
+    if (b < 0 || H <= 0 || W <= 0 || C <= 0 || k < 1) return fail(FERN_ERR_ARG, "fern_avgpool_nhwc: bad argument");
+    if (b == 0) return FERN_OK;
+    if (!x || !y) return fail(FERN_ERR_ARG, "fern_avgpool_nhwc: NULL argument");
+    if (C % 4 || H % k || W % k || pixel_rows(b, H, W) < 0) return fail(FERN_ERR_ARG, "fern_avgpool_nhwc: need C % 4 == 0, H % k == 0, W % k == 0 and b * H * W < 2^31");
+    if (misaligned16(x) || misaligned16(y)) return fail(FERN_ERR_ARG, "fern_avgpool_nhwc: pointers must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(launch_avgpool_nhwc(x, y, b, H, W, C, k, (hipStream_t)stream));
+    return FERN_OK;
+}
+
+extern "C" int fern_attnpool_tokens(fern_ctx* c, const float* x, const float* pos, float* T, float* T0, int b, int HW, int C, void* stream) {
+    if (!c) return fail(FERN_ERR_ARG, "fern_attnpool_tokens: ctx is NULL");
+    if (b < 0 || HW <= 0 || C <= 0) return fail(FERN_ERR_ARG, "fern_attnpool_tokens: bad argument");
+    if (b == 0) return FERN_OK;
+    if (!x || !pos || !T || !T0) return fail(FERN_ERR_ARG, "fern_attnpool_tokens: NULL argument");
+    if (C % 4 || HW == INT32_MAX || pixel_rows(b, HW + 1, 1) < 0) return fail(FERN_ERR_ARG, "fern_attnpool_tokens: need C % 4 == 0 and b * (HW + 1) < 2^31");
+    if (misaligned16(x) || misaligned16(pos) || misaligned16(T) || misaligned16(T0)) return fail(FERN_ERR_ARG, "fern_attnpool_tokens: pointers must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    const hipStream_t st = (hipStream_t)stream;
+    float* mean;      // [b, C], the tower's arena slot
+    FERN_TRY(ws_begin(c, st));
+    FERN_TRY(ws_get(c, (size_t)b * C, &mean));
+    HIP_TRY(launch_attnpool_tokens(x, mean, pos, T, T0, b, HW, C, st));
+    return FERN_OK;
+}

@@ -380,16 +380,19 @@ static int vit_chunk(fern_ctx* c, const float* images, float* out, int b, hipStr
 // ---- open_clip ModifiedResNet (RN50x4).  Activations are NHWC, so every 1x1 convolution is a plain GEMM over the pixel
 // rows, every 3x3 convolution the same GEMM with the 3x3-window A loader, BatchNorm is folded into the weights and the
 // ReLU / residual add live in the GEMM epilogue.
-static GemmParams conv_desc(const float* A, const ConvW& W, float* C, int M, int epi) {
+GemmParams fern::api::conv_desc(const float* A, const ConvW& W, float* C, int M, int epi) {
     GemmParams p{};
     p.A = A; p.lda = W.k; p.W = W.w; p.ldw = W.k; p.bias = W.b; p.C = C; p.ldc = W.cout;
     p.M = M; p.N = W.cout; p.K = W.k; p.epi = epi; p.aload = ALOAD_PLAIN;
     return p;
 }
-static int conv3x3(fern_ctx* c, const float* A, const ConvW& W, float* C, int b, int H, int Wd, int cin, hipStream_t s) {
+GemmParams fern::api::conv3x3_desc(const float* A, const ConvW& W, float* C, int b, int H, int Wd, int cin, const float* zeros) {
     GemmParams p = conv_desc(A, W, C, b * H * Wd, EPI_BIAS_RELU);
-    p.aload = ALOAD_CONV3; p.conv_h = H; p.conv_w = Wd; p.conv_c = cin; p.zeros = c->clip.res.zeros;
-    return run_gemm(c, p, s);
+    p.aload = ALOAD_CONV3; p.conv_h = H; p.conv_w = Wd; p.conv_c = cin; p.zeros = zeros;
+    return p;
+}
+static int conv3x3(fern_ctx* c, const float* A, const ConvW& W, float* C, int b, int H, int Wd, int cin, hipStream_t s) {
+    return run_gemm(c, conv3x3_desc(A, W, C, b, H, Wd, cin, c->clip.res.zeros), s);
 }
 
 static int resnet_chunk(fern_ctx* c, const float* images, float* out, int b, hipStream_t s) {

@@ -194,6 +194,9 @@ GemmParams gemm_desc_b(const unsigned short* A, long lda, const LinearW& L, void
 GemmParams gemm_desc_f8(const unsigned char* A8, const float* sa, long lda, const LinearW& L, void* C, long ldc, int M, int epi, bool out_bf16);
 GemmParams gemm_desc_mx(const unsigned char* A8, const unsigned char* sa, long srows, long lda, const LinearW& L, void* C, long ldc, int M, int epi, bool out_bf16);
 int clip_mlp_epi(const fern_ctx* c);      // c_fc epilogue of the CLIP towers' MLPs
+// the ModifiedResNet's convolutions over NHWC pixel rows (api_towers.hip): a 1x1 as a plain GEMM, a 3x3 / stride 1 / pad 1 through the window loader
+GemmParams conv_desc(const float* A, const ConvW& W, float* C, int M, int epi);
+GemmParams conv3x3_desc(const float* A, const ConvW& W, float* C, int b, int H, int Wd, int cin, const float* zeros);
 
 // ---- checks that entry points of several files make ---------------------------------------------
 int check_fresh(fern_ctx* c, const char* fn);            // weight-reading entry points: a fork made before the parent's last re-finalisation must not run

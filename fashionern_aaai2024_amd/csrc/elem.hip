@@ -1052,7 +1052,7 @@ hipError_t launch_sr_finalize(const float* partial, int nb, const float* bc, con
 }
 hipError_t launch_stem_conv(const float* img, const float* w, const float* bias, float* out, int B, int S, int cout_pad, hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    if ((S & 1) || (cout_pad & 3)) return hipErrorInvalidValue;
+    if (S <= 0 || (S & 1) || cout_pad <= 0 || (cout_pad & 3)) return hipErrorInvalidValue;
     if (cout_pad == 48) {      // RN50x4's stem width (40 channels, padded to the next conv's k granularity): all channels of a pixel in one thread
         const long npix = (long)B * (S / 2) * (S / 2);
         hipLaunchKernelGGL(stem_conv_px_kernel<12>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, img, w, bias, out, B, S);
@@ -1064,14 +1064,14 @@ hipError_t launch_stem_conv(const float* img, const float* w, const float* bias,
 }
 hipError_t launch_avgpool_nhwc(const float* x, float* y, int B, int H, int W, int C, int k, hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    if ((C & 3) || k < 1 || H % k || W % k) return hipErrorInvalidValue;
+    if (C <= 0 || (C & 3) || k < 1 || H <= 0 || W <= 0 || H % k || W % k) return hipErrorInvalidValue;
     const long total = (long)B * (H / k) * (W / k) * (C / 4);
     hipLaunchKernelGGL(avgpool_nhwc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, y, B, H, W, C, k);
     return hipGetLastError();
 }
 hipError_t launch_attnpool_tokens(const float* x, float* mean, const float* pos, float* T, float* T0, int B, int HW, int C, hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    if (C & 3) return hipErrorInvalidValue;
+    if (C <= 0 || (C & 3) || HW <= 0) return hipErrorInvalidValue;      // HW == 0: the mean token would be 0 / 0
     hipLaunchKernelGGL(mean_tokens_kernel, dim3((unsigned)(((long)B * (C / 4) + 255) / 256)), dim3(256), 0, s, x, mean, B, HW, C);
     const long total = (long)B * (HW + 1) * (C / 4);
     hipLaunchKernelGGL(attnpool_tokens_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, mean, pos, T, T0, B, HW, C);

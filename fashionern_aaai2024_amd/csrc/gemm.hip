@@ -1160,7 +1160,9 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
     g_last_dispatches = 1;
     if (p.M <= 0 || p.N <= 0) return hipSuccess;
     if (p.K <= 0 || (p.K % 16) != 0 || (p.ldw & 3) || (p.aload == ALOAD_PLAIN && (p.lda & 3))) return hipErrorInvalidValue;
-    if (p.aload == ALOAD_CONV3 && (p.conv_c % 16 || p.K != 9 * p.conv_c || !p.zeros || p.M % (p.conv_h * p.conv_w))) return hipErrorInvalidValue;
+    if (p.aload == ALOAD_CONV3 && (p.conv_h <= 0 || p.conv_w <= 0 || p.conv_c <= 0 || p.conv_c % 16 || p.K != 9 * p.conv_c || !p.zeros ||
+                                   ((uintptr_t)p.zeros & 15) || p.M % (p.conv_h * p.conv_w)))
+        return hipErrorInvalidValue;
     if (((uintptr_t)p.A & 15) || ((uintptr_t)p.W & 15)) return hipErrorInvalidValue;
     if (p.aload == ALOAD_IM2COL && ((p.patch & 3) || (p.img & 3))) return hipErrorInvalidValue;
     if (p.ksplit > 1 && (p.aload != ALOAD_PLAIN || !p.kpart || p.K % (p.ksplit * 64) || (p.N & 3))) return hipErrorInvalidValue;

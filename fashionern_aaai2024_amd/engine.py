@@ -1084,6 +1084,60 @@ class FernEngine:
         _lib.check(self.lib.fern_im2col_q(self._h, _ptr(x), b, img, patch, int(out_form), _ptr(y), _ptr(sc), srows, _stream()), "fern_im2col_q")
         return y if out_form == QFORM_BF16 else (y, sc)
 
+    # ---- the ModifiedResNet's kernels through the tower's launchers (include/fern.h: fern_conv3x3_nhwc ...) ----
+    def conv3x3_nhwc(self, x, w, bias) -> torch.Tensor:
+        """relu(conv3x3(x, stride 1, zero padding 1) + bias): x [b,H,W,cin] NHWC, w [cout, 9*cin] in (ky, kx, c) order -> [b,H,W,cout]."""
+        x = self._f32(x)
+        b, h, wd, cin = x.shape
+        w = self._f32(w)
+        cout = w.shape[0]
+        w, bias = self._f32(w, (cout, 9 * cin)), self._f32(bias, (cout,))
+        out = self._empty(b, h, wd, cout)
+        _lib.check(self.lib.fern_conv3x3_nhwc(self._h, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), b, h, wd, cin, cout, _stream()),
+                   "fern_conv3x3_nhwc")
+        return out
+
+    def conv1x1_nhwc(self, x, w, bias, residual=None, relu=True) -> torch.Tensor:
+        """x [M,cin] w [cout,cin]^T + bias over pixel rows; relu(.) when `relu`, relu(. + residual [M,cout]) with a residual."""
+        x, w = self._f32(x), self._f32(w)
+        m, cin = x.shape
+        cout = w.shape[0]
+        w, bias = self._f32(w, (cout, cin)), self._f32(bias, (cout,))
+        residual = None if residual is None else self._f32(residual, (m, cout))
+        out = self._empty(m, cout)
+        _lib.check(self.lib.fern_conv1x1_nhwc(self._h, _ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(out), m, cin, cout, int(bool(relu)),
+                                              _stream()), "fern_conv1x1_nhwc")
+        return out
+
+    def stem_conv(self, images, w, bias) -> torch.Tensor:
+        """relu(conv3x3(images, stride 2, zero padding 1) + bias): images [b,3,S,S] NCHW, w [cout_pad, 27] in (c, ky, kx) order ->
+        [b,S/2,S/2,cout_pad] NHWC."""
+        x = self._f32(images)
+        b, _, s, _ = x.shape
+        w = self._f32(w)
+        cp = w.shape[0]
+        w, bias = self._f32(w, (cp, 27)), self._f32(bias, (cp,))
+        out = self._empty(b, s // 2, s // 2, cp)
+        _lib.check(self.lib.fern_stem_conv(self._h, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), b, s, cp, _stream()), "fern_stem_conv")
+        return out
+
+    def avgpool_nhwc(self, x, k: int) -> torch.Tensor:
+        """Mean over k x k windows (stride k) of x [b,H,W,C] NHWC -> [b,H/k,W/k,C]."""
+        x = self._f32(x)
+        b, h, wd, ch = x.shape
+        out = self._empty(b, h // k, wd // k, ch)
+        _lib.check(self.lib.fern_avgpool_nhwc(self._h, _ptr(x), _ptr(out), b, h, wd, ch, int(k), _stream()), "fern_avgpool_nhwc")
+        return out
+
+    def attnpool_tokens(self, x, pos):
+        """The attention pool's token rows: x [b,HW,C], pos [HW+1,C] -> (T [b,HW+1,C] = [mean(x) + pos[0]; x + pos[1:]], T0 [b,C] = T[:,0])."""
+        x = self._f32(x)
+        b, hw, ch = x.shape
+        pos = self._f32(pos, (hw + 1, ch))
+        t, t0 = self._empty(b, hw + 1, ch), self._empty(b, ch)
+        _lib.check(self.lib.fern_attnpool_tokens(self._h, _ptr(x), _ptr(pos), _ptr(t), _ptr(t0), b, hw, ch, _stream()), "fern_attnpool_tokens")
+        return t, t0
+
     # ---- profiling ----------------------------------------------------------------------------
     def prof_enable(self, on: bool) -> None:
         _lib.check(self.lib.fern_prof_enable(self._h, int(on)), "fern_prof_enable")

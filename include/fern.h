@@ -671,6 +671,32 @@ FERN_API int fern_attention_mx8(fern_ctx* ctx, const uint16_t* q, int64_t ldq, c
                        int head_dim, int s_q, int s_k, int causal, float scale, void* stream);
 FERN_API int fern_im2col_q(fern_ctx* ctx, const float* images, int b, int img, int patch, int out_form, void* y, void* scales,
                   int64_t scale_rows, void* stream);
+/* The kernels of the open_clip ModifiedResNet image tower (RN50x4), each behind the launcher the tower calls with the descriptor the
+ * tower builds, so that tile choice, tuner and forced configurations are the tower's own.  Activations are NHWC fp32 with the channel
+ * count as the row stride; BatchNorm is whatever the caller folded into w / bias.  Arguments are validated before any HIP call;
+ * b == 0 (M == 0) returns FERN_OK without a launch.
+ * fern_conv3x3_nhwc: out [b,H,W,cout] = relu(conv3x3(x [b,H,W,cin], stride 1, zero padding 1) + bias), w [cout, 9 * cin] with
+ *   k = (ky * 3 + kx) * cin + c: the fp32 GEMM over the b * H * W pixel rows with the 3x3-window LDS-DMA loader (taps outside the
+ *   image come from a zeroed piece of a fresh workspace frame of ctx).  cin % 16 == 0, b * H * W < 2^31, x and w 16-byte aligned.
+ * fern_conv1x1_nhwc: out [M,cout] = x [M,cin] w [cout,cin]^T + bias, then relu when `relu`, and relu(. + residual [M,cout]) when a
+ *   residual is given (the bottleneck's closing convolution; `relu` must then be set): the fp32 GEMM over pixel rows with the
+ *   tower's three epilogues.  cin % 16 == 0, x and w 16-byte aligned.
+ * fern_stem_conv: out [b,S/2,S/2,cout_pad] (NHWC) = relu(conv3x3(images [b,3,S,S] NCHW, stride 2, zero padding 1) + bias),
+ *   w [cout_pad, 27] with k = (c * 3 + ky) * 3 + kx.  S % 2 == 0, cout_pad % 4 == 0 (48 runs the one-thread-per-pixel kernel, bit
+ *   identical per channel to the other); bias and out 16-byte aligned.
+ * fern_avgpool_nhwc: y [b,H/k,W/k,C] = the mean over k x k windows of x [b,H,W,C] (stride k).  C % 4 == 0, H % k == 0, W % k == 0,
+ *   pointers 16-byte aligned.
+ * fern_attnpool_tokens: the attention pool's token rows, T [b,HW+1,C]: T[i,0] = mean_j x[i,j] + pos[0], T[i,j+1] = x[i,j] + pos[j+1]
+ *   for x [b,HW,C], pos [HW+1,C]; T0 [b,C] = T[:,0] (the compact query rows).  HW >= 1, C % 4 == 0, pointers 16-byte aligned; the
+ *   [b,C] means go through a fresh workspace frame of ctx. */
+FERN_API int fern_conv3x3_nhwc(fern_ctx* ctx, const float* x, const float* w, const float* bias, float* out, int b, int H, int W, int cin,
+                      int cout, void* stream);
+FERN_API int fern_conv1x1_nhwc(fern_ctx* ctx, const float* x, const float* w, const float* bias, const float* residual, float* out, int M,
+                      int cin, int cout, int relu, void* stream);
+FERN_API int fern_stem_conv(fern_ctx* ctx, const float* images, const float* w, const float* bias, float* out, int b, int S, int cout_pad,
+                   void* stream);
+FERN_API int fern_avgpool_nhwc(fern_ctx* ctx, const float* x, float* y, int b, int H, int W, int C, int k, void* stream);
+FERN_API int fern_attnpool_tokens(fern_ctx* ctx, const float* x, const float* pos, float* T, float* T0, int b, int HW, int C, void* stream);
 
 /* The GEMM launchers time their tile candidates once per new shape (all candidates are bit-identical).  This
  * returns the choices made so far in this process as text, one line per shape ("f32|bf16|fp8 M N K epilogue loader cfg");

@@ -49,6 +49,20 @@ def test_ctypes_loader_and_error_reporting_without_gpu():
     assert b"fern_im2col_q: ctx is NULL" in lib.fern_last_error()
 
 
+def test_resnet_block_entries_refuse_a_null_context_before_any_hip_call():
+    lib = _lib.load()
+    calls = {
+        "fern_conv3x3_nhwc": (None, None, None, None, None, 1, 4, 4, 16, 16, None),
+        "fern_conv1x1_nhwc": (None, None, None, None, None, None, 16, 16, 16, 1, None),
+        "fern_stem_conv": (None, None, None, None, None, 1, 8, 16, None),
+        "fern_avgpool_nhwc": (None, None, None, 1, 4, 4, 16, 2, None),
+        "fern_attnpool_tokens": (None, None, None, None, None, 1, 4, 16, None),
+    }
+    for name, args in calls.items():
+        assert getattr(lib, name)(*args) == -1, name
+        assert f"{name}: ctx is NULL".encode() in lib.fern_last_error()
+
+
 def test_code_object_targets_gfx950_only():
     out = subprocess.run(["strings", "-n", "6", build.LIB], capture_output=True, text=True).stdout
     assert "gfx950" in out
