@@ -25,6 +25,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from .engine import per_query
+
 
 def init_from_env(backend: Optional[str] = None) -> Tuple[int, int, int]:
     """Initialise the default process group from RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* (torchrun contract).
@@ -114,14 +116,14 @@ def all_gather_shards(block: torch.Tensor, n_total: int, out: Optional[torch.Ten
     return full[:n_total]
 
 
-def _all_reduce_max(x: torch.Tensor) -> torch.Tensor:
-    """In-place MAX all-reduce of a small fp32 tensor (through the host under the gloo debug backend with device tensors)."""
+def _all_reduce(x: torch.Tensor, op) -> torch.Tensor:
+    """In-place all-reduce of a small tensor (through the host under the gloo debug backend with device tensors)."""
     if dist.get_backend() == "gloo" and x.is_cuda:
         h = x.cpu()
-        dist.all_reduce(h, op=dist.ReduceOp.MAX)
+        dist.all_reduce(h, op=op)
         x.copy_(h)
     else:
-        dist.all_reduce(x, op=dist.ReduceOp.MAX)
+        dist.all_reduce(x, op=op)
     return x
 
 
@@ -147,7 +149,7 @@ def all_gather_prepared(engine, block: torch.Tensor, n_total: int, out=None):
     f32 = all_gather_shards(mine.f32, n_total, out=None if out is None else out.f32)
     b16 = all_gather_shards(mine.bf16, n_total, out=None if out is None else out.bf16)
     meta = mine.meta.clone() if out is None else out.meta.copy_(mine.meta)
-    _all_reduce_max(meta)
+    _all_reduce(meta, dist.ReduceOp.MAX)
     return PreparedGallery(f32, b16, meta)
 
 
@@ -173,23 +175,36 @@ def rank_replicated(engine, queries: torch.Tensor, gallery: torch.Tensor, k: int
     return engine.sim_topk(queries, gallery, k, exclude_idx=exclude_idx)
 
 
+def _filter_kw(row_filter) -> dict:
+    """An unfiltered call passes NO `row_filter` keyword: an engine that does not know filters serves it."""
+    return {} if row_filter is None else {"row_filter": row_filter}
+
+
+def _gather_merge(engine, scores: torch.Tensor, idx: torch.Tensor, extra: Optional[torch.Tensor] = None):
+    """The shards' local [B, K] lists (global indices) -> (scores, idx, gathered): every list is all-gathered as [world, B, K] and the
+    first two are merged (`engine.topk_merge`: score descending, global index ascending).  `gathered` is the all-gathered (idx, extra)
+    for a caller that looks something up beside the merge.  World 1: the local lists, None, no collective."""
+    rank, world = world_info()
+    if world == 1:
+        return scores, idx, None
+    b, kk = scores.shape
+    full = [torch.empty((world * b, kk), dtype=t.dtype, device=t.device)      # concatenated along dim 0 == [world, B, K]
+            for t in (scores, idx, extra) if t is not None]
+    for out, t in zip(full, (scores, idx, extra)):
+        _all_gather_into(out, t)
+    full = [t.view(world, b, kk) for t in full]
+    merged_s, merged_i = engine.topk_merge(full[0], full[1])
+    return merged_s, merged_i, tuple(full[1:])
+
+
 def rank_sharded(engine, queries: torch.Tensor, gallery_shard: torch.Tensor, shard_start: int, k: int, exclude_idx=None, row_filter=None):
     """Gallery-sharded ranking of the SAME query batch on every rank: local top-K with global indices, all-gather of
     the [B, K] candidates, merge.  Returns the global (scores, idx) on every rank.  k > 64: the deep ranking and the wide merge.
     `row_filter`: the SHARD's `RowFilter` -- tags shard with the rows, mask / value are the same on every rank; the filtered lists
     merge exactly like the unfiltered ones."""
-    rank, world = world_info()
     rank_fn = engine.sim_topk_deep if k > 64 else engine.sim_topk
-    kw = {} if row_filter is None else {"row_filter": row_filter}
-    s, i = rank_fn(queries, gallery_shard, k, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
-    if world == 1:
-        return s, i
-    b, kk = s.shape
-    all_s = torch.empty((world * b, kk), dtype=s.dtype, device=s.device)      # concatenated along dim 0 == [world, B, K]
-    all_i = torch.empty((world * b, kk), dtype=i.dtype, device=i.device)
-    _all_gather_into(all_s, s)
-    _all_gather_into(all_i, i)
-    return engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
+    s, i = rank_fn(queries, gallery_shard, k, idx_offset=shard_start, exclude_idx=exclude_idx, **_filter_kw(row_filter))
+    return _gather_merge(engine, s, i)[:2]
 
 
 def rank_from_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: int, k: int, from_keys, exclude_idx=None, row_filter=None):
@@ -199,17 +214,8 @@ def rank_from_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start:
     (scores, idx) on every rank; `engine.next_from` of it is the next cursor.  World 1 makes no collective.  `row_filter`: the SHARD's.
     Random access by OFFSET on a sharded gallery is out of scope: a global select is not additive over shards (the key at a global
     place is not a function of the shards' keys at any local places), so sharded callers page by cursor."""
-    rank, world = world_info()
-    kw = {} if row_filter is None else {"row_filter": row_filter}
-    s, i = engine.sim_topk_from(queries, gallery_shard, k, from_keys, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
-    if world == 1:
-        return s, i
-    b, kk = s.shape
-    all_s = torch.empty((world * b, kk), dtype=s.dtype, device=s.device)
-    all_i = torch.empty((world * b, kk), dtype=i.dtype, device=i.device)
-    _all_gather_into(all_s, s)
-    _all_gather_into(all_i, i)
-    return engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
+    s, i = engine.sim_topk_from(queries, gallery_shard, k, from_keys, idx_offset=shard_start, exclude_idx=exclude_idx, **_filter_kw(row_filter))
+    return _gather_merge(engine, s, i)[:2]
 
 
 def rank_candidates_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: int, candidates, k: int, exclude_idx=None, row_filter=None):
@@ -218,17 +224,8 @@ def rank_candidates_sharded(engine, queries: torch.Tensor, gallery_shard, shard_
     it owns and the others take no place there; then the all-gather and merge of `rank_sharded`.  Returns the global (scores, idx) on
     every rank.  `row_filter`: the SHARD's.  No places: a place inside the whole list is not a function of the places inside the shards'
     parts (count the keys with `rank_of_sharded` instead)."""
-    rank, world = world_info()
-    kw = {} if row_filter is None else {"row_filter": row_filter}
-    s, i = engine.sim_topk_candidates(queries, gallery_shard, candidates, k, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
-    if world == 1:
-        return s, i
-    b, kk = s.shape
-    all_s = torch.empty((world * b, kk), dtype=s.dtype, device=s.device)
-    all_i = torch.empty((world * b, kk), dtype=i.dtype, device=i.device)
-    _all_gather_into(all_s, s)
-    _all_gather_into(all_i, i)
-    return engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
+    s, i = engine.sim_topk_candidates(queries, gallery_shard, candidates, k, idx_offset=shard_start, exclude_idx=exclude_idx, **_filter_kw(row_filter))
+    return _gather_merge(engine, s, i)[:2]
 
 
 def route_rows(slots, bounds) -> List[np.ndarray]:
@@ -247,15 +244,17 @@ def route_rows(slots, bounds) -> List[np.ndarray]:
     return [np.nonzero(owner == r)[0] for r in range(b.size - 1)]
 
 
-def _all_reduce_sum(x: torch.Tensor) -> torch.Tensor:
-    """In-place SUM all-reduce of an integer tensor (through the host under the gloo debug backend with device tensors)."""
-    if dist.get_backend() == "gloo" and x.is_cuda:
-        h = x.cpu()
-        dist.all_reduce(h, op=dist.ReduceOp.SUM)
-        x.copy_(h)
-    else:
-        dist.all_reduce(x, op=dist.ReduceOp.SUM)
-    return x
+def _count_keys(keys: torch.Tensor, count) -> torch.Tensor:
+    """The target-rank sequence over the shards.  `keys` int64 [B, m] hold each target's key on the shard that owns it and 0 on every
+    other, so their SUM all-reduce is exact, wrap-around included; `count(keys)` is this shard's int32 [B, m] count of what outranks
+    them, -1 for a key of 0 -- which is -1 on every rank: summed as 0, restored after the SUM.  Two small collectives; world 1 makes
+    none and returns `count(keys)` as it is."""
+    rank, world = world_info()
+    if world == 1:
+        return count(keys)
+    _all_reduce(keys, dist.ReduceOp.SUM)
+    counts = _all_reduce(count(keys).clamp(min=0), dist.ReduceOp.SUM)
+    return torch.where(keys == 0, torch.full_like(counts, -1), counts)
 
 
 def rank_of_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: int, targets, exclude_idx=None, row_filter=None):
@@ -265,31 +264,19 @@ def rank_of_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start: i
     collectives of [B, m] integers; world 1 makes none.  Returns int32 shaped like `targets` on every rank; -1 for a target < 0,
     outside the gallery, or equal to the query's excluded row.  `row_filter`: the SHARD's `RowFilter` (tags shard with the rows): only
     eligible rows are counted, and the shard that owns a target drops its key when the target is not eligible (-1 on every rank)."""
-    rank, world = world_info()
-    t = torch.as_tensor(targets)
-    flat = t.dim() == 1
-    t2 = (t[:, None] if flat else t).to(dtype=torch.int32)
+    t2, restore = per_query(targets, queries.shape[0], torch.int32, "targets")
     keys = engine.rank_keys(queries, gallery_shard, t2, idx_offset=shard_start)
-    kw = {}
     if row_filter is not None:
-        kw["row_filter"] = row_filter
         n = gallery_shard.shape[0]
-        tags, mask, value = row_filter.resolve(keys.shape[0], n, keys.device)
         local = t2.to(device=keys.device, dtype=torch.int64) - int(shard_start)
         mine = (local >= 0) & (local < n)
-        ok = (tags[local.clamp(0, max(n - 1, 0))] & mask[:, None]) == value[:, None] if n else mine
+        ok = row_filter.eligible(*row_filter.resolve(keys.shape[0], n, keys.device), local)
         keys = torch.where(mine & ~ok, torch.zeros_like(keys), keys)
-    if world > 1:
-        _all_reduce_sum(keys)
-    if exclude_idx is not None:
+    if exclude_idx is not None:      # on every rank alike, so before or after the keys' SUM is the same
         ex = torch.as_tensor(exclude_idx).to(device=keys.device, dtype=torch.int32)
         keys = torch.where(t2.to(keys.device) == ex[:, None], torch.zeros_like(keys), keys)
-    counts = engine.rank_count(queries, gallery_shard, keys, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
-    if world > 1:
-        counts = counts.clamp(min=0)                 # a keyless target is -1 on every rank: summed as 0, restored below
-        _all_reduce_sum(counts)
-        counts = torch.where(keys == 0, torch.full_like(counts, -1), counts)
-    return counts[:, 0] if flat else counts
+    return restore(_count_keys(keys, lambda ky: engine.rank_count(queries, gallery_shard, ky, idx_offset=shard_start, exclude_idx=exclude_idx,
+                                                                  **_filter_kw(row_filter))))
 
 
 def _require_unsplit_items(items) -> None:
@@ -317,25 +304,16 @@ def rank_items_sharded(engine, queries: torch.Tensor, gallery_shard, shard_start
     `_require_unsplit_items`).  Then a shard's list holds the true representative of every item it lists, the lists share no item and
     merge like row lists (`topk_merge`); the item ids travel beside the merge and are looked up by the merged global row index.
     Returns (scores, idx, item) on every rank."""
-    rank, world = world_info()
     _require_unsplit_items(items)
-    kw = {} if row_filter is None else {"row_filter": row_filter}
-    s, i, it = engine.sim_topk_items(queries, gallery_shard, items, k, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
-    if world == 1:
+    s, i, it = engine.sim_topk_items(queries, gallery_shard, items, k, idx_offset=shard_start, exclude_idx=exclude_idx, **_filter_kw(row_filter))
+    ms, mi, gathered = _gather_merge(engine, s, i, it)
+    if gathered is None:
         return s, i, it
-    b, kk = s.shape
-    all_s = torch.empty((world * b, kk), dtype=s.dtype, device=s.device)      # concatenated along dim 0 == [world, B, K]
-    all_i = torch.empty((world * b, kk), dtype=i.dtype, device=i.device)
-    all_t = torch.empty((world * b, kk), dtype=it.dtype, device=it.device)
-    _all_gather_into(all_s, s)
-    _all_gather_into(all_i, i)
-    _all_gather_into(all_t, it)
-    ms, mi = engine.topk_merge(all_s.view(world, b, kk), all_i.view(world, b, kk))
     # a global row index appears in one list only: sort each query's gathered indices once, look the merged ones up
-    cat_i = all_i.view(world, b, kk).permute(1, 0, 2).reshape(b, world * kk).to(torch.int64)
-    cat_t = all_t.view(world, b, kk).permute(1, 0, 2).reshape(b, world * kk)
-    sorted_i, perm = cat_i.sort(dim=1)
-    pos = torch.searchsorted(sorted_i, mi.to(torch.int64).contiguous()).clamp(max=world * kk - 1)
+    b, wk = s.shape[0], gathered[0].shape[0] * s.shape[1]
+    cat_i, cat_t = (t.permute(1, 0, 2).reshape(b, wk) for t in gathered)
+    sorted_i, perm = cat_i.to(torch.int64).sort(dim=1)
+    pos = torch.searchsorted(sorted_i, mi.to(torch.int64).contiguous()).clamp(max=wk - 1)
     mt = cat_t.gather(1, perm.gather(1, pos))
     return ms, mi, torch.where(mi >= 0, mt, torch.full_like(mt, -1))
 
@@ -348,19 +326,12 @@ def item_rank_of_sharded(engine, queries: torch.Tensor, gallery_shard, shard_sta
     a -1.  Returns int32 shaped like `target_items` on every rank; -1 for an id outside [0, n_items) or an item without an eligible row."""
     rank, world = world_info()
     _require_unsplit_items(items)
-    t = torch.as_tensor(target_items)
-    flat = t.dim() == 1
-    t2 = (t[:, None] if flat else t).to(dtype=torch.int32)
-    kw = {} if row_filter is None else {"row_filter": row_filter}
+    t2, restore = per_query(target_items, queries.shape[0], torch.int32, "target_items")
+    kw = dict(idx_offset=shard_start, exclude_idx=exclude_idx, **_filter_kw(row_filter))
     if world == 1:
-        ranks = engine.item_rank_of(queries, gallery_shard, items, t2, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
-        return ranks[:, 0] if flat else ranks
-    keys = engine.item_keys(queries, gallery_shard, items, t2, idx_offset=shard_start, exclude_idx=exclude_idx, **kw)
-    _all_reduce_sum(keys)
-    counts = engine.item_count(queries, gallery_shard, items, keys, idx_offset=shard_start, exclude_idx=exclude_idx, **kw).clamp(min=0)
-    _all_reduce_sum(counts)                              # an item without a key is -1 on every rank: summed as 0, restored here
-    counts = torch.where(keys == 0, torch.full_like(counts, -1), counts)
-    return counts[:, 0] if flat else counts
+        return restore(engine.item_rank_of(queries, gallery_shard, items, t2, **kw))
+    keys = engine.item_keys(queries, gallery_shard, items, t2, **kw)
+    return restore(_count_keys(keys, lambda ky: engine.item_count(queries, gallery_shard, items, ky, **kw)))
 
 
 def share_gemm_tiles(engine, src: int = 0) -> None:

@@ -119,6 +119,15 @@ class RowFilter:
             out.append((t.to(device).expand(b) if t.dim() == 0 else t.to(device)).contiguous())
         return tuple(out)
 
+    @staticmethod
+    def eligible(tags: torch.Tensor, mask: torch.Tensor, value: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
+        """bool [B,m]: whether the LOCAL gallery row rows[b][j] is eligible for query b, from the resolved (tags [n], mask [B],
+        value [B]).  Rows are clamped into [0, n) -- the caller knows which ones lie outside -- and nothing is eligible when n == 0."""
+        n = tags.shape[0]
+        if n == 0:
+            return torch.zeros(rows.shape, dtype=torch.bool, device=rows.device)
+        return (tags[rows.to(torch.int64).clamp(0, n - 1)] & mask[:, None]) == value[:, None]
+
 
 class ItemMap:
     """Which item every gallery row belongs to (include/fern.h: fern_sim_topk_items): `items` [N] holds one integer id per row, ids in
@@ -175,6 +184,42 @@ def next_from(scores: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     filled = (idx >= 0).sum(dim=1)
     last = keys.gather(1, (filled - 1).clamp(min=0)[:, None])[:, 0]
     return torch.where(filled > 0, last - 1, torch.zeros_like(last))
+
+
+def per_query(t, b: int, dtype, what: str, device=None):
+    """(t2, restore): a per-query argument given as [B] or [B,m] (`targets`, `places`, `keys`) as a contiguous [B,m] tensor of `dtype`
+    (moved to `device` when one is given), and the function that gives a [B,m] result the caller's shape back (column 0 of it when `t`
+    was flat)."""
+    t = torch.as_tensor(t).to(device=device, dtype=dtype)
+    flat = t.dim() == 1
+    if flat:
+        t = t[:, None]
+    if t.dim() != 2 or t.shape[0] != b or t.shape[1] < 1:
+        raise ValueError(f"{what} must be [B] or [B,m] with m >= 1, got {tuple(t.shape)}")
+    return t.contiguous(), (lambda out: out[:, 0] if flat else out)
+
+
+_NO_ITEMS = object()      # `_rank_call(items=...)` of a wrapper that takes no ItemMap: None is refused like any other non-ItemMap
+
+
+class _RankCall:
+    """What the arguments every ranking wrapper shares resolve to (`FernEngine._rank_call`): the fp32 queries and the gallery's forms,
+    B / N / D, the converted `exclude_idx`, the resolved filter (`tags`, `mask`, `value`: all None without one) and, with an `ItemMap`,
+    the resolved ids and `n_items` -- and the two argument runs the entry points of include/fern.h share."""
+
+    __slots__ = ("eng", "q", "g32", "g16", "meta", "b", "n", "d", "ex", "tags", "mask", "value", "items", "n_items")
+
+    def head(self, prepared: bool = False):
+        """The leading (ctx, q, gallery, gallery_bf16, B, N, D).  An entry point without `meta` ranks a PreparedGallery on its fp32 rows
+        and is not handed the bf16 copy; `prepared`: the (..., gallery_bf16, meta, B, N, D) of the entry points that take all three."""
+        if prepared:
+            return (self.eng._h, _ptr(self.q), _ptr(self.g32), _ptr(self.g16), _ptr(self.meta), self.b, self.n, self.d)
+        return (self.eng._h, _ptr(self.q), _ptr(self.g32), _ptr(self.g16 if self.g32 is None else None), self.b, self.n, self.d)
+
+    @property
+    def tail(self):
+        """The trailing (tags, mask, value, stream) of every entry point that takes a filter."""
+        return (_ptr(self.tags), _ptr(self.mask), _ptr(self.value), _stream())
 
 
 class FernEngine:
@@ -471,20 +516,29 @@ class FernEngine:
         """The (scores fp32, idx int32) [B,k] outputs of a top-K call."""
         return self._empty(b, k), self._empty(b, k, dtype=torch.int32)
 
+    def _rank_call(self, q, gallery, exclude_idx=None, row_filter=None, items=_NO_ITEMS, bf16_ok: bool = True) -> _RankCall:
+        """The arguments every ranking wrapper shares, resolved once (`_RankCall`): what is left to a wrapper is its own extra
+        argument, its outputs and one library call.  The only place that checks the filter's (and the item map's) type."""
+        if items is not _NO_ITEMS and not isinstance(items, ItemMap):
+            raise TypeError("items must be an ItemMap")
+        if row_filter is not None and not isinstance(row_filter, RowFilter):
+            raise TypeError("row_filter must be a RowFilter")
+        c = _RankCall()
+        c.eng = self
+        c.q, c.g32, c.g16, c.meta = self._gallery_forms(q, gallery, bf16_ok)
+        c.b, (c.n, c.d) = c.q.shape[0], (c.g32 if c.g32 is not None else c.g16).shape
+        c.items, c.n_items = (None, 0) if items is _NO_ITEMS else (items.resolve(c.n, self.device), items.n_items)
+        c.tags, c.mask, c.value = (None, None, None) if row_filter is None else row_filter.resolve(c.b, c.n, self.device)
+        c.ex = self._exclude(exclude_idx, c.b)
+        return c
+
     def _sim_topk_filtered(self, q, gallery, k: int, idx_offset, exclude_idx, row_filter: RowFilter):
         """The filtered form of `sim_topk` / `sim_topk_deep` / `sim_topk_bf16` (include/fern.h: fern_sim_topk_filtered): the exact
         ranking of the rows that are eligible for each query, 1 <= k <= 1024, any gallery form."""
-        if not isinstance(row_filter, RowFilter):
-            raise TypeError("row_filter must be a RowFilter")
-        q, g32, g16, meta = self._gallery_forms(q, gallery)
-        g = g32 if g32 is not None else g16
-        b = q.shape[0]
-        tags, mask, value = row_filter.resolve(b, g.shape[0], self.device)
-        scores, idx = self._topk_out(b, k)
-        ex = self._exclude(exclude_idx, b)
-        _lib.check(self.lib.fern_sim_topk_filtered(self._h, _ptr(q), _ptr(g32), _ptr(g16), _ptr(meta), b, g.shape[0], q.shape[1], int(k),
-                                                   _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask), _ptr(value),
-                                                   _stream()), "fern_sim_topk_filtered")
+        c = self._rank_call(q, gallery, exclude_idx, row_filter)
+        scores, idx = self._topk_out(c.b, k)
+        _lib.check(self.lib.fern_sim_topk_filtered(*c.head(prepared=True), int(k), _ptr(scores), _ptr(idx), int(idx_offset), _ptr(c.ex),
+                                                   *c.tail), "fern_sim_topk_filtered")
         return scores, idx
 
     def sim_topk(self, q, gallery, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
@@ -495,12 +549,10 @@ class FernEngine:
             return self._sim_topk_filtered(q, gallery, k, idx_offset, exclude_idx, row_filter)
         if isinstance(gallery, PreparedGallery):
             return self._sim_topk_prefiltered(q, gallery, k, idx_offset, exclude_idx)
-        q, g, _, _ = self._gallery_forms(q, gallery, bf16_ok=False)
-        b = q.shape[0]
-        scores, idx = self._topk_out(b, k)
-        ex = self._exclude(exclude_idx, b)
-        _lib.check(self.lib.fern_sim_topk(self._h, _ptr(q), _ptr(g), b, g.shape[0], q.shape[1], int(k), _ptr(scores), _ptr(idx),
-                                          int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk")
+        c = self._rank_call(q, gallery, exclude_idx, bf16_ok=False)
+        scores, idx = self._topk_out(c.b, k)
+        _lib.check(self.lib.fern_sim_topk(self._h, _ptr(c.q), _ptr(c.g32), c.b, c.n, c.d, int(k), _ptr(scores), _ptr(idx),
+                                          int(idx_offset), _ptr(c.ex), _stream()), "fern_sim_topk")
         return scores, idx
 
     def sweep_bf16_scores(self, q, pg: "PreparedGallery", tile_max: bool = True):
@@ -524,12 +576,10 @@ class FernEngine:
         _lib.check(self.lib.fern_rank_set_strategy(self._h, code), "fern_rank_set_strategy")
 
     def _sim_topk_prefiltered(self, q, pg: PreparedGallery, k: int, idx_offset: int = 0, exclude_idx=None):
-        q, g, _, _ = self._gallery_forms(q, pg)
-        b = q.shape[0]
-        scores, idx = self._topk_out(b, k)
-        ex = self._exclude(exclude_idx, b)
-        _lib.check(self.lib.fern_sim_topk_prefiltered(self._h, _ptr(q), _ptr(g), _ptr(pg.bf16), _ptr(pg.meta), b, g.shape[0], q.shape[1], int(k),
-                                                      _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_prefiltered")
+        c = self._rank_call(q, pg, exclude_idx)
+        scores, idx = self._topk_out(c.b, k)
+        _lib.check(self.lib.fern_sim_topk_prefiltered(*c.head(prepared=True), int(k), _ptr(scores), _ptr(idx), int(idx_offset), _ptr(c.ex),
+                                                      _stream()), "fern_sim_topk_prefiltered")
         return scores, idx
 
     def sim_topk_deep(self, q, gallery, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
@@ -539,13 +589,10 @@ class FernEngine:
         `row_filter`: rank only the rows that are eligible for each query (`RowFilter`)."""
         if row_filter is not None:
             return self._sim_topk_filtered(q, gallery, k, idx_offset, exclude_idx, row_filter)
-        q, g32, g16, meta = self._gallery_forms(q, gallery)
-        g = g32 if g32 is not None else g16
-        b = q.shape[0]
-        scores, idx = self._topk_out(b, k)
-        ex = self._exclude(exclude_idx, b)
-        _lib.check(self.lib.fern_sim_topk_deep(self._h, _ptr(q), _ptr(g32), _ptr(g16), _ptr(meta), b, g.shape[0], q.shape[1], int(k),
-                                               _ptr(scores), _ptr(idx), int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_deep")
+        c = self._rank_call(q, gallery, exclude_idx)
+        scores, idx = self._topk_out(c.b, k)
+        _lib.check(self.lib.fern_sim_topk_deep(*c.head(prepared=True), int(k), _ptr(scores), _ptr(idx), int(idx_offset), _ptr(c.ex),
+                                               _stream()), "fern_sim_topk_deep")
         return scores, idx
 
     def sim_topk_candidates(self, q, gallery, candidates, k: int, idx_offset: int = 0, exclude_idx=None,
@@ -556,176 +603,110 @@ class FernEngine:
         (shard), the query's excluded row or ineligible under `row_filter` takes no place, a row named twice counts once.  Scores and
         order are those of `sim_topk_deep` on the same gallery form (fp32 tensor or `PreparedGallery`: the fp32 chain; bf16 tensor: the
         bf16 similarity); 1 <= k <= 1024, places past the list are -inf / -1.  place[b][j]: the 0-based place of entry j, -1 if none."""
-        q, g32, g16 = self._rank_forms(q, gallery)
-        g = g32 if g32 is not None else g16
-        b, n = q.shape[0], g.shape[0]
+        c = self._rank_call(q, gallery, exclude_idx, row_filter)
         cd = torch.as_tensor(candidates)
-        if cd.dim() != 2 or cd.shape[0] != b or cd.dtype.is_floating_point or cd.dtype == torch.bool:
-            raise ValueError(f"candidates must be an integer [B = {b}, M], got {tuple(cd.shape)} {cd.dtype}")
+        if cd.dim() != 2 or cd.shape[0] != c.b or cd.dtype.is_floating_point or cd.dtype == torch.bool:
+            raise ValueError(f"candidates must be an integer [B = {c.b}, M], got {tuple(cd.shape)} {cd.dtype}")
         cd = cd.to(device=self.device, dtype=torch.int32).contiguous()
-        tags = mask = value = None
-        if row_filter is not None:
-            if not isinstance(row_filter, RowFilter):
-                raise TypeError("row_filter must be a RowFilter")
-            tags, mask, value = row_filter.resolve(b, n, self.device)
-        scores, idx = self._topk_out(b, k)
+        scores, idx = self._topk_out(c.b, k)
         place = self._empty(*cd.shape, dtype=torch.int32) if places else None
-        ex = self._exclude(exclude_idx, b)
-        _lib.check(self.lib.fern_sim_topk_candidates(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, n, q.shape[1], _ptr(cd), cd.shape[1], int(k),
-                                                     _ptr(scores), _ptr(idx), _ptr(place), int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask),
-                                                     _ptr(value), _stream()), "fern_sim_topk_candidates")
+        _lib.check(self.lib.fern_sim_topk_candidates(*c.head(), _ptr(cd), cd.shape[1], int(k), _ptr(scores), _ptr(idx), _ptr(place),
+                                                     int(idx_offset), _ptr(c.ex), *c.tail), "fern_sim_topk_candidates")
         return (scores, idx, place) if places else (scores, idx)
 
     # ---- exact target ranks ---------------------------------------------------------------------
-    def _rank_forms(self, q, gallery):
-        """(q, fp32 gallery or None, bf16 gallery or None): the gallery forms of `sim_topk_deep`; a PreparedGallery ranks on its
-        fp32 rows (its bf16 copy is not read)."""
-        q, g32, g16, _ = self._gallery_forms(q, gallery)
-        return q, g32, (g16 if g32 is None else None)
+    def _keys_of(self, c: _RankCall, tg: torch.Tensor, idx_offset) -> torch.Tensor:
+        keys = self._empty(*tg.shape, dtype=torch.int64)
+        _lib.check(self.lib.fern_rank_keys(*c.head(), _ptr(tg), tg.shape[1], int(idx_offset), _ptr(keys), _stream()), "fern_rank_keys")
+        return keys
 
-    def _per_query(self, t, b: int, dtype, what: str) -> torch.Tensor:
-        t = torch.as_tensor(t).to(device=self.device, dtype=dtype)
-        if t.dim() == 1:
-            t = t[:, None]
-        if t.dim() != 2 or t.shape[0] != b or t.shape[1] < 1:
-            raise ValueError(f"{what} must be [B] or [B,m] with m >= 1, got {tuple(t.shape)}")
-        return t.contiguous()
+    def _count_of(self, c: _RankCall, ky: torch.Tensor, idx_offset) -> torch.Tensor:
+        count = self._empty(*ky.shape, dtype=torch.int32)
+        if c.tags is not None:
+            _lib.check(self.lib.fern_rank_count_filtered(*c.head(), _ptr(ky), ky.shape[1], int(idx_offset), _ptr(c.ex), _ptr(count), *c.tail),
+                       "fern_rank_count_filtered")
+        else:
+            _lib.check(self.lib.fern_rank_count(*c.head(), _ptr(ky), ky.shape[1], int(idx_offset), _ptr(c.ex), _ptr(count), _stream()),
+                       "fern_rank_count")
+        return count
 
     def rank_keys(self, q, gallery, targets, idx_offset: int = 0) -> torch.Tensor:
         """int64 [B,m]: the bits of the 64-bit ranking keys (include/fern.h: fern_rank_keys) of the gallery rows `targets` (global
         indices, [B] or [B,m]); 0 for a target < 0 or outside [idx_offset, idx_offset + N)."""
-        q, g32, g16 = self._rank_forms(q, gallery)
-        g = g32 if g32 is not None else g16
-        tg = self._per_query(targets, q.shape[0], torch.int32, "targets")
-        keys = self._empty(*tg.shape, dtype=torch.int64)
-        _lib.check(self.lib.fern_rank_keys(self._h, _ptr(q), _ptr(g32), _ptr(g16), q.shape[0], g.shape[0], q.shape[1], _ptr(tg), tg.shape[1],
-                                           int(idx_offset), _ptr(keys), _stream()), "fern_rank_keys")
-        return keys
+        c = self._rank_call(q, gallery)
+        return self._keys_of(c, per_query(targets, c.b, torch.int32, "targets", self.device)[0], idx_offset)
 
     def rank_count(self, q, gallery, keys, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None) -> torch.Tensor:
         """int32 [B,m]: per key the number of rows of `gallery` whose ranking key is greater (include/fern.h: fern_rank_count); the
         row `exclude_idx[b]` (global index) is not counted; -1 for a key of 0.  Counts of gallery shards add up.  `row_filter`: only
         the rows that are eligible for the query are counted (fern_rank_count_filtered)."""
-        q, g32, g16 = self._rank_forms(q, gallery)
-        g = g32 if g32 is not None else g16
-        b = q.shape[0]
-        ky = self._per_query(keys, b, torch.int64, "keys")
-        ex = self._exclude(exclude_idx, b)
-        count = self._empty(*ky.shape, dtype=torch.int32)
-        if row_filter is not None:
-            if not isinstance(row_filter, RowFilter):
-                raise TypeError("row_filter must be a RowFilter")
-            tags, mask, value = row_filter.resolve(b, g.shape[0], self.device)
-            _lib.check(self.lib.fern_rank_count_filtered(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, g.shape[0], q.shape[1], _ptr(ky), ky.shape[1],
-                                                         int(idx_offset), _ptr(ex), _ptr(count), _ptr(tags), _ptr(mask), _ptr(value), _stream()),
-                       "fern_rank_count_filtered")
-            return count
-        _lib.check(self.lib.fern_rank_count(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, g.shape[0], q.shape[1], _ptr(ky), ky.shape[1],
-                                            int(idx_offset), _ptr(ex), _ptr(count), _stream()), "fern_rank_count")
-        return count
+        c = self._rank_call(q, gallery, exclude_idx, row_filter)
+        return self._count_of(c, per_query(keys, c.b, torch.int64, "keys", self.device)[0], idx_offset)
 
     def rank_of(self, q, gallery, targets, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None) -> torch.Tensor:
         """int32, shaped like `targets` ([B] or [B,m]): the 0-based position of each target row in the ordering `sim_topk` defines
         (score descending, gallery index ascending) -- what the reference reads off its full argsort (run/test/test_fiq.py:49-60) --
         at any depth.  -1 for a target that is < 0, outside the gallery, or the query's excluded row.  `row_filter`: the position
         among the rows that are eligible for the query; -1 for a target that is not eligible itself."""
-        flat = torch.as_tensor(targets).dim() == 1
-        keys = self.rank_keys(q, gallery, targets, idx_offset)
-        if exclude_idx is not None:
-            ex = self._exclude(exclude_idx, keys.shape[0])
-            tg = self._per_query(targets, keys.shape[0], torch.int32, "targets")
-            keys = torch.where(tg == ex[:, None], torch.zeros_like(keys), keys)
-        if row_filter is not None:      # ineligible targets lose their key on the device, like the excluded row
-            tg = self._per_query(targets, keys.shape[0], torch.int32, "targets")
-            n = gallery.shape[0]
-            tags, mask, value = row_filter.resolve(keys.shape[0], n, self.device)
-            local = (tg.to(torch.int64) - int(idx_offset)).clamp(0, max(n - 1, 0))
-            ok = (tags[local] & mask[:, None]) == value[:, None] if n else torch.zeros_like(tg, dtype=torch.bool)
+        c = self._rank_call(q, gallery, exclude_idx, row_filter)      # everything is converted once: the two calls share it
+        tg, restore = per_query(targets, c.b, torch.int32, "targets", self.device)
+        keys = self._keys_of(c, tg, idx_offset)
+        if c.ex is not None:
+            keys = torch.where(tg == c.ex[:, None], torch.zeros_like(keys), keys)
+        if c.tags is not None:          # ineligible targets lose their key on the device, like the excluded row
+            ok = RowFilter.eligible(c.tags, c.mask, c.value, tg.to(torch.int64) - int(idx_offset))
             keys = torch.where(ok, keys, torch.zeros_like(keys))
-        ranks = self.rank_count(q, gallery, keys, idx_offset, exclude_idx, row_filter)
-        return ranks[:, 0] if flat else ranks
+        return restore(self._count_of(c, keys, idx_offset))
 
     # ---- ranking pages ----------------------------------------------------------------------------
-    def _page_call(self, q, gallery, exclude_idx, row_filter):
-        """Shared argument handling of the page entry points: (q, g32, g16, n, exclude, (tags, mask, value))."""
-        q, g32, g16 = self._rank_forms(q, gallery)
-        g = g32 if g32 is not None else g16
-        b, n = q.shape[0], g.shape[0]
-        filt = (None, None, None)
-        if row_filter is not None:
-            if not isinstance(row_filter, RowFilter):
-                raise TypeError("row_filter must be a RowFilter")
-            filt = row_filter.resolve(b, n, self.device)
-        return q, g32, g16, n, self._exclude(exclude_idx, b), filt
-
     def rank_select(self, q, gallery, places, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None) -> torch.Tensor:
         """int64 [B,m] ([B] for flat `places`): the bits of the ranking key of the row at each 0-based place of the ordering `sim_topk`
         defines, at any depth (include/fern.h: fern_rank_select) -- the inverse of `rank_count`; 0 for a place < 0 or past the rows that
         take a place.  `gallery`: an fp32 tensor or a `PreparedGallery` (exact fp32-chain scores) or a bf16 tensor."""
-        flat = torch.as_tensor(places).dim() == 1
-        q, g32, g16, n, ex, (tags, mask, value) = self._page_call(q, gallery, exclude_idx, row_filter)
-        pl = self._per_query(places, q.shape[0], torch.int32, "places")
+        c = self._rank_call(q, gallery, exclude_idx, row_filter)
+        pl, restore = per_query(places, c.b, torch.int32, "places", self.device)
         keys = self._empty(*pl.shape, dtype=torch.int64)
-        _lib.check(self.lib.fern_rank_select(self._h, _ptr(q), _ptr(g32), _ptr(g16), q.shape[0], n, q.shape[1], _ptr(pl), pl.shape[1],
-                                             int(idx_offset), _ptr(ex), _ptr(keys), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_rank_select")
-        return keys[:, 0] if flat else keys
+        _lib.check(self.lib.fern_rank_select(*c.head(), _ptr(pl), pl.shape[1], int(idx_offset), _ptr(c.ex), _ptr(keys), *c.tail),
+                   "fern_rank_select")
+        return restore(keys)
 
     def sim_topk_from(self, q, gallery, k: int, from_keys, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
         """(scores, idx) [B,k]: the exact top-K, 1 <= k <= 1024, among the rows whose ranking key is <= `from_keys` [B] (int64 bits; a
         cursor from `next_from`, -1 = everything, 0 = nothing) -- include/fern.h: fern_sim_topk_from.  The cursor carries a GLOBAL row
         index, so the same cursor continues the list on every shard of a gallery (`idx_offset`)."""
-        q, g32, g16, n, ex, (tags, mask, value) = self._page_call(q, gallery, exclude_idx, row_filter)
-        b = q.shape[0]
+        c = self._rank_call(q, gallery, exclude_idx, row_filter)
         fk = torch.as_tensor(from_keys).to(device=self.device, dtype=torch.int64).contiguous()
-        if tuple(fk.shape) != (b,):
+        if tuple(fk.shape) != (c.b,):
             raise ValueError("from_keys must be [B]")
-        scores, idx = self._topk_out(b, k)
-        _lib.check(self.lib.fern_sim_topk_from(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, n, q.shape[1], int(k), _ptr(fk), _ptr(scores), _ptr(idx),
-                                               int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_sim_topk_from")
+        scores, idx = self._topk_out(c.b, k)
+        _lib.check(self.lib.fern_sim_topk_from(*c.head(), int(k), _ptr(fk), _ptr(scores), _ptr(idx), int(idx_offset), _ptr(c.ex), *c.tail),
+                   "fern_sim_topk_from")
         return scores, idx
 
     def rank_page(self, q, gallery, offset, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
         """(scores, idx) [B,k]: places [offset, offset + k) of every query's ranking, at any depth (include/fern.h: fern_sim_topk_page);
         `offset` an int or [B]; slots past the end -inf / -1.  offset 0 is `sim_topk_deep`."""
-        q, g32, g16, n, ex, (tags, mask, value) = self._page_call(q, gallery, exclude_idx, row_filter)
-        b = q.shape[0]
+        c = self._rank_call(q, gallery, exclude_idx, row_filter)
         off = torch.as_tensor(offset).to(device=self.device, dtype=torch.int32)
-        off = off.expand(b).contiguous() if off.dim() == 0 else off.contiguous()
-        if tuple(off.shape) != (b,):
+        off = off.expand(c.b).contiguous() if off.dim() == 0 else off.contiguous()
+        if tuple(off.shape) != (c.b,):
             raise ValueError("offset must be an int or [B]")
-        scores, idx = self._topk_out(b, k)
-        _lib.check(self.lib.fern_sim_topk_page(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, n, q.shape[1], int(k), _ptr(off), _ptr(scores), _ptr(idx),
-                                               int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_sim_topk_page")
+        scores, idx = self._topk_out(c.b, k)
+        _lib.check(self.lib.fern_sim_topk_page(*c.head(), int(k), _ptr(off), _ptr(scores), _ptr(idx), int(idx_offset), _ptr(c.ex), *c.tail),
+                   "fern_sim_topk_page")
         return scores, idx
 
     # ---- item-level ranking -----------------------------------------------------------------------
-    def _item_call(self, q, gallery, items, exclude_idx, row_filter):
-        """Shared argument handling of the item entry points: (q, g32, g16, n, items, n_items, exclude, (tags, mask, value))."""
-        if not isinstance(items, ItemMap):
-            raise TypeError("items must be an ItemMap")
-        q, g32, g16 = self._rank_forms(q, gallery)
-        g = g32 if g32 is not None else g16
-        b, n = q.shape[0], g.shape[0]
-        it = items.resolve(n, self.device)
-        filt = (None, None, None)
-        if row_filter is not None:
-            if not isinstance(row_filter, RowFilter):
-                raise TypeError("row_filter must be a RowFilter")
-            filt = row_filter.resolve(b, n, self.device)
-        return q, g32, g16, n, it, items.n_items, self._exclude(exclude_idx, b), filt
-
     def sim_topk_items(self, q, gallery, items: ItemMap, k: int, idx_offset: int = 0, exclude_idx=None, row_filter: Optional[RowFilter] = None):
         """Item-level exact top-K, 1 <= k <= 1024 (include/fern.h: fern_sim_topk_items): the row ranking of `sim_topk_deep` (exclude_idx
         and `row_filter` applied first) with every row but the first of its item removed.  Returns (scores, idx, item) [B,k]: the
         representative row's score, its global index and its item id; unfilled places -inf / -1 / -1.  `gallery`: an fp32 tensor or a
         `PreparedGallery` (exact fp32-chain scores) or a bf16 tensor (the bf16 similarity)."""
-        q, g32, g16, n, it, g_items, ex, (tags, mask, value) = self._item_call(q, gallery, items, exclude_idx, row_filter)
-        b = q.shape[0]
-        scores, idx = self._topk_out(b, k)
-        item = self._empty(b, k, dtype=torch.int32)
-        _lib.check(self.lib.fern_sim_topk_items(self._h, _ptr(q), _ptr(g32), _ptr(g16), b, n, q.shape[1], int(k), _ptr(it), g_items, _ptr(scores),
-                                                _ptr(idx), _ptr(item), int(idx_offset), _ptr(ex), _ptr(tags), _ptr(mask), _ptr(value), _stream()),
-                   "fern_sim_topk_items")
+        c = self._rank_call(q, gallery, exclude_idx, row_filter, items)
+        scores, idx = self._topk_out(c.b, k)
+        item = self._empty(c.b, k, dtype=torch.int32)
+        _lib.check(self.lib.fern_sim_topk_items(*c.head(), int(k), _ptr(c.items), c.n_items, _ptr(scores), _ptr(idx), _ptr(item),
+                                                int(idx_offset), _ptr(c.ex), *c.tail), "fern_sim_topk_items")
         return scores, idx, item
 
     def item_rank_of(self, q, gallery, items: ItemMap, target_items, idx_offset: int = 0, exclude_idx=None,
@@ -733,34 +714,33 @@ class FernEngine:
         """int32, shaped like `target_items` ([B] or [B,m]): the number of items that come before each target item in the ranking
         `sim_topk_items` defines, at any depth (include/fern.h: fern_item_rank); -1 for an id outside [0, n_items) or an item without
         an eligible row for the query."""
-        flat = torch.as_tensor(target_items).dim() == 1
-        q, g32, g16, n, it, g_items, ex, (tags, mask, value) = self._item_call(q, gallery, items, exclude_idx, row_filter)
-        tg = self._per_query(target_items, q.shape[0], torch.int32, "target_items")
+        c = self._rank_call(q, gallery, exclude_idx, row_filter, items)
+        tg, restore = per_query(target_items, c.b, torch.int32, "target_items", self.device)
         ranks = self._empty(*tg.shape, dtype=torch.int32)
-        _lib.check(self.lib.fern_item_rank(self._h, _ptr(q), _ptr(g32), _ptr(g16), q.shape[0], n, q.shape[1], _ptr(it), g_items, _ptr(tg), tg.shape[1],
-                                           int(idx_offset), _ptr(ex), _ptr(ranks), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_item_rank")
-        return ranks[:, 0] if flat else ranks
+        _lib.check(self.lib.fern_item_rank(*c.head(), _ptr(c.items), c.n_items, _ptr(tg), tg.shape[1], int(idx_offset), _ptr(c.ex), _ptr(ranks),
+                                           *c.tail), "fern_item_rank")
+        return restore(ranks)
 
     def item_keys(self, q, gallery, items: ItemMap, target_items, idx_offset: int = 0, exclude_idx=None,
                   row_filter: Optional[RowFilter] = None) -> torch.Tensor:
         """int64 [B,m]: the bits of the ranking key of each target item's representative row in this gallery (shard); 0 when the shard
         holds no eligible row of the item (include/fern.h: fern_item_keys)."""
-        q, g32, g16, n, it, g_items, ex, (tags, mask, value) = self._item_call(q, gallery, items, exclude_idx, row_filter)
-        tg = self._per_query(target_items, q.shape[0], torch.int32, "target_items")
+        c = self._rank_call(q, gallery, exclude_idx, row_filter, items)
+        tg, _ = per_query(target_items, c.b, torch.int32, "target_items", self.device)
         keys = self._empty(*tg.shape, dtype=torch.int64)
-        _lib.check(self.lib.fern_item_keys(self._h, _ptr(q), _ptr(g32), _ptr(g16), q.shape[0], n, q.shape[1], _ptr(it), g_items, _ptr(tg), tg.shape[1],
-                                           int(idx_offset), _ptr(ex), _ptr(keys), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_item_keys")
+        _lib.check(self.lib.fern_item_keys(*c.head(), _ptr(c.items), c.n_items, _ptr(tg), tg.shape[1], int(idx_offset), _ptr(c.ex), _ptr(keys),
+                                           *c.tail), "fern_item_keys")
         return keys
 
     def item_count(self, q, gallery, items: ItemMap, keys, idx_offset: int = 0, exclude_idx=None,
                    row_filter: Optional[RowFilter] = None) -> torch.Tensor:
         """int32 [B,m]: per key the number of this gallery's (shard's) items whose representative's key is greater; -1 for a key of 0
         (include/fern.h: fern_item_count).  Counts of shards that share no item add up."""
-        q, g32, g16, n, it, g_items, ex, (tags, mask, value) = self._item_call(q, gallery, items, exclude_idx, row_filter)
-        ky = self._per_query(keys, q.shape[0], torch.int64, "keys")
+        c = self._rank_call(q, gallery, exclude_idx, row_filter, items)
+        ky, _ = per_query(keys, c.b, torch.int64, "keys", self.device)
         count = self._empty(*ky.shape, dtype=torch.int32)
-        _lib.check(self.lib.fern_item_count(self._h, _ptr(q), _ptr(g32), _ptr(g16), q.shape[0], n, q.shape[1], _ptr(it), g_items, _ptr(ky), ky.shape[1],
-                                            int(idx_offset), _ptr(ex), _ptr(count), _ptr(tags), _ptr(mask), _ptr(value), _stream()), "fern_item_count")
+        _lib.check(self.lib.fern_item_count(*c.head(), _ptr(c.items), c.n_items, _ptr(ky), ky.shape[1], int(idx_offset), _ptr(c.ex), _ptr(count),
+                                            *c.tail), "fern_item_count")
         return count
 
     def gallery_to_bf16(self, gallery) -> torch.Tensor:
@@ -831,12 +811,10 @@ class FernEngine:
             return self._sim_topk_filtered(q, gallery_bf16, k, idx_offset, exclude_idx, row_filter)
         if not isinstance(gallery_bf16, torch.Tensor) or gallery_bf16.dtype != torch.bfloat16:
             raise ValueError("gallery must be a contiguous bf16 [N,D] device tensor sharing D with q")
-        q, _, g, _ = self._gallery_forms(q, gallery_bf16)
-        b = q.shape[0]
-        scores, idx = self._topk_out(b, k)
-        ex = self._exclude(exclude_idx, b)
-        _lib.check(self.lib.fern_sim_topk_bf16(self._h, _ptr(q), _ptr(g), b, g.shape[0], q.shape[1], int(k), _ptr(scores), _ptr(idx),
-                                               int(idx_offset), _ptr(ex), _stream()), "fern_sim_topk_bf16")
+        c = self._rank_call(q, gallery_bf16, exclude_idx)
+        scores, idx = self._topk_out(c.b, k)
+        _lib.check(self.lib.fern_sim_topk_bf16(self._h, _ptr(c.q), _ptr(c.g16), c.b, c.n, c.d, int(k), _ptr(scores), _ptr(idx),
+                                               int(idx_offset), _ptr(c.ex), _stream()), "fern_sim_topk_bf16")
         return scores, idx
 
     def gather_scores(self, q, gallery, idx):
@@ -1002,14 +980,16 @@ class FernEngine:
                                                   b, heads, e // heads, s, _stream()), "fern_pooled_attention")
         return out
 
+    def _b16(self, x) -> torch.Tensor:
+        """A [B,S,W] attention operand as a contiguous bf16 device tensor; anything but bf16 is rounded from fp32 first."""
+        if x.dtype != torch.bfloat16:
+            x3 = self._f32(x)
+            return self.to_bf16(x3.reshape(-1, x3.shape[-1])).reshape(x3.shape)
+        return x.to(self.device).contiguous()
+
     def attention_bf16(self, q, k, v, heads: int, causal=False, scale=None) -> torch.Tensor:
         """bf16 operand form of `attention`: q/k/v bf16 [B,S,W] (fp32 inputs are rounded first) -> bf16 [B,Sq,W]."""
-        def b16(x):
-            if x.dtype != torch.bfloat16:
-                x3 = self._f32(x)
-                return self.to_bf16(x3.reshape(-1, x3.shape[-1])).reshape(x3.shape)
-            return x.to(self.device).contiguous()
-        q, k, v = b16(q), b16(k), b16(v)
+        q, k, v = self._b16(q), self._b16(k), self._b16(v)
         b, sq, w = q.shape
         sk = k.shape[1]
         hd = w // heads
@@ -1048,12 +1028,7 @@ class FernEngine:
         """attention_bf16 with the block-scaled output of FERN_PREC_MX8 / _MX8_IMG (include/fern.h: fern_attention_mx8): q/k/v bf16
         [B,S,W] (fp32 inputs are rounded first) -> (e4m3fn bytes [B*Sq, ldo] as uint8, E8M0 scales [W/128, scale_rows, 4]).  `out`: an
         existing uint8 [B*Sq, ldo] array to write into (columns >= W are not written), `scales` as in quantize_mx8."""
-        def b16(x):
-            if x.dtype != torch.bfloat16:
-                x3 = self._f32(x)
-                return self.to_bf16(x3.reshape(-1, x3.shape[-1])).reshape(x3.shape)
-            return x.to(self.device).contiguous()
-        q, k, v = b16(q), b16(k), b16(v)
+        q, k, v = self._b16(q), self._b16(k), self._b16(v)
         b, sq, w = q.shape
         sk = k.shape[1]
         hd = w // heads

@@ -15,21 +15,30 @@ import numpy as np
 import torch
 
 
-def cosine_topk(q: torch.Tensor, g: torch.Tensor, k: int, idx_offset: int = 0, exclude_idx=None):
+def masked_scores(scores, idx_offset=0, exclude_idx=None, eligible=None):
+    """A copy of `scores` [B, N] with the excluded row (a global index per query) and the ineligible rows (bool [B, N]) at -inf:
+    the one place where a row is taken out of a ranking."""
+    s = np.array(scores, dtype=np.float32, copy=True)
+    b, n = s.shape
+    if eligible is not None:
+        s[~np.asarray(eligible, dtype=bool)] = -np.inf
+    if exclude_idx is not None:
+        ex = np.asarray(exclude_idx, dtype=np.int64) - idx_offset
+        for r in np.nonzero((ex >= 0) & (ex < n))[0]:
+            s[r, ex[r]] = -np.inf
+    return s
+
+
+def cosine_topk(q: torch.Tensor, g: torch.Tensor, k: int, idx_offset: int = 0, exclude_idx=None, eligible=None):
     """Top-k of ``q @ g.T`` per query row: (scores [B,k] desc, idx [B,k] int32 = local row + idx_offset).
 
     ``exclude_idx`` ([B] int, global index or -1): that gallery row is removed from the query's ranking
-    (CIRR drops the reference image, test_cirr.py:55-58).  Slots beyond the available rows get
-    score -inf and index -1.
+    (CIRR drops the reference image, test_cirr.py:55-58); ``eligible`` (bool [B,N]): so is every row that is
+    not eligible for the query.  Slots beyond the available rows get score -inf and index -1.
     """
-    scores = (q.float() @ g.float().T)
+    ex = None if exclude_idx is None else torch.as_tensor(exclude_idx).cpu().numpy()
+    scores = torch.from_numpy(masked_scores((q.float() @ g.float().T).detach().numpy(), idx_offset, ex, eligible))
     b, n = scores.shape
-    if exclude_idx is not None:
-        ex = torch.as_tensor(exclude_idx, dtype=torch.long) - idx_offset
-        ok = (ex >= 0) & (ex < n)
-        rows = torch.arange(b)[ok]
-        scores = scores.clone()
-        scores[rows, ex[ok]] = float("-inf")
     order = torch.sort(scores, dim=1, descending=True, stable=True)
     kk = min(k, n)
     out_s = torch.full((b, k), float("-inf"))

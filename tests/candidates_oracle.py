@@ -1,10 +1,9 @@
 """The CPU oracle of candidate ranking (include/fern.h: fern_sim_topk_candidates), without a second copy of the ranking rules.
 TEST INFRASTRUCTURE.
 
-``candidates_oracle()`` returns a subclass of the filtered oracle (tests/filtered_oracle.py, itself over the rank protocol stub of
-tests/test_rank_of_cpu.py) with ``sim_topk_candidates``.  Scores are ``oracle.chain.chain_scores`` (the fp32 chain of oracle/chain.c),
-the order is that of the stub's ``_make_keys`` (score descending, global index ascending as one unsigned compare), and the set semantics
-are restated here in a few lines of numpy:
+``candidates_oracle()`` returns the rank oracle over ``oracle.chain.chain_scores`` (tests/rank_oracle.py: ``CandidatesOracle``; the fp32
+chain of oracle/chain.c), whose ``sim_topk_candidates`` orders by ``_make_keys`` (score descending, global index ascending as one
+unsigned compare).  The set semantics are restated here in a few lines of numpy:
 
     query b ranks the SET of rows named by candidates[b]; an entry takes no place if it is negative, outside [idx_offset, idx_offset + N),
     equal to exclude_idx[b] or ineligible under the row filter; a row named twice counts once; place[b][j] = the number of distinct
@@ -13,9 +12,6 @@ are restated here in a few lines of numpy:
 from __future__ import annotations
 
 import numpy as np
-import torch
-
-from oracle import chain
 
 
 def valid_entries(cand, n, idx_offset=0, exclude_idx=None, eligible=None):
@@ -53,24 +49,5 @@ def rank_candidates(scores, cand, k, idx_offset=0, exclude_idx=None, eligible=No
 
 
 def candidates_oracle():
-    from filtered_oracle import eligible, filtered_oracle
-    from test_rank_of_cpu import _make_keys
-
-    class CandidatesOracle(filtered_oracle()):
-        def _scores(self, q, gallery):
-            g = self._rows(gallery).float().cpu().numpy()
-            if g.shape[0] == 0:
-                return np.zeros((q.shape[0], 0), dtype=np.float32)
-            return chain.chain_scores(np.ascontiguousarray(q.float().cpu().numpy()), np.ascontiguousarray(g))
-
-        def sim_topk_candidates(self, q, gallery, candidates, k, idx_offset=0, exclude_idx=None, row_filter=None, places=False):
-            s = self._scores(q, gallery)
-            b, n = s.shape
-            cand = np.asarray(torch.as_tensor(candidates).cpu().numpy(), dtype=np.int64)
-            ex = None if exclude_idx is None else torch.as_tensor(exclude_idx).cpu().numpy()
-            el = None if row_filter is None else eligible(row_filter, b, n).numpy()
-            out_s, out_i, place = rank_candidates(s, cand, k, idx_offset, ex, el, _make_keys)
-            out = (torch.from_numpy(out_s), torch.from_numpy(out_i))
-            return out + (torch.from_numpy(place),) if places else out
-
+    from rank_oracle import CandidatesOracle
     return CandidatesOracle

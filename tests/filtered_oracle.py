@@ -1,87 +1,11 @@
-"""The CPU oracle of filtered ranking, without a second copy of the ranking rules.  TEST INFRASTRUCTURE.
+"""The CPU oracle of filtered ranking: tests/rank_oracle.py under the name its first users import.  TEST INFRASTRUCTURE.
 
-``filtered_oracle()`` returns a subclass of the test-only ``OracleEngine`` (through the rank protocol stub of tests/test_rank_of_cpu.py)
-whose ``sim_topk`` / ``sim_topk_deep`` / ``rank_count`` / ``rank_of`` accept ``row_filter=`` (``fashionern_aaai2024_amd.engine.RowFilter``):
-gallery row n is eligible for query b iff ``(tags[n] & mask[b]) == value[b]``.  A filtered ranking is the unfiltered one of
-``oracle.rank.cosine_topk`` with the ineligible rows' scores set to -inf, so the tie rule (score descending, index ascending) and the
-(-inf, -1) padding are the oracle's own.
+``filtered_oracle()`` returns ``RankOracle``, whose ranking methods accept ``row_filter=`` (``fashionern_aaai2024_amd.engine.RowFilter``):
+a filtered ranking is the unfiltered one of ``oracle.rank.cosine_topk`` with the ineligible rows' scores set to -inf, so the tie rule
+(score descending, index ascending) and the (-inf, -1) padding are the oracle's own.
 """
-from __future__ import annotations
-
-import numpy as np
-import torch
-
-from oracle import rank as orank
-
-
-def eligible(row_filter, b: int, n: int) -> torch.Tensor:
-    """bool [B, N] on the CPU."""
-    tags, mask, value = row_filter.resolve(b, n, "cpu")
-    return (tags[None, :] & mask[:, None]) == value[:, None]
+from rank_oracle import RankOracle, eligible      # noqa: F401
 
 
 def filtered_oracle():
-    from test_rank_of_cpu import _make_keys, _rank_stub
-
-    class FilteredOracle(_rank_stub()):
-        def sim_topk(self, q, gallery, k, idx_offset=0, exclude_idx=None, row_filter=None):
-            q, g = q.float().cpu(), self._rows(gallery).float().cpu()
-            if row_filter is None:
-                return orank.cosine_topk(q, g, k, idx_offset, exclude_idx)
-            scores = q @ g.T
-            b, n = scores.shape
-            scores = torch.where(eligible(row_filter, b, n), scores, torch.full_like(scores, float("-inf")))
-            if exclude_idx is not None:
-                ex = torch.as_tensor(exclude_idx, dtype=torch.long) - idx_offset
-                ok = (ex >= 0) & (ex < n)
-                scores[torch.arange(b)[ok], ex[ok]] = float("-inf")
-            order = torch.sort(scores, dim=1, descending=True, stable=True)
-            kk = min(k, n)
-            out_s = torch.full((b, k), float("-inf"))
-            out_i = torch.full((b, k), -1, dtype=torch.int32)
-            out_s[:, :kk] = order.values[:, :kk]
-            out_i[:, :kk] = (order.indices[:, :kk] + idx_offset).to(torch.int32)
-            out_i[torch.isinf(out_s) & (out_s < 0)] = -1
-            return out_s, out_i
-
-        sim_topk_deep = sim_topk
-
-        def rank_count(self, q, gallery, keys, idx_offset=0, exclude_idx=None, row_filter=None):
-            if row_filter is None:
-                return super().rank_count(q, gallery, keys, idx_offset, exclude_idx)
-            s = self._scores(q, gallery)
-            b, n = s.shape
-            k = self._2d(keys, np.int64).view(np.uint64)
-            row_keys = _make_keys(s, np.broadcast_to(np.arange(n) + idx_offset, s.shape))
-            row_keys = np.where(eligible(row_filter, b, n).numpy(), row_keys, np.uint64(0))
-            if exclude_idx is not None:
-                ex = np.asarray(torch.as_tensor(exclude_idx).numpy(), dtype=np.int64) - idx_offset
-                for r in np.nonzero((ex >= 0) & (ex < n))[0]:
-                    row_keys[r, ex[r]] = 0
-            count = (row_keys[:, :, None] > k[:, None, :]).sum(axis=1)
-            return torch.from_numpy(np.where(k == 0, -1, count).astype(np.int32))
-
-        def rank_of(self, q, gallery, targets, idx_offset=0, exclude_idx=None, row_filter=None):
-            if row_filter is None:
-                return super().rank_of(q, gallery, targets, idx_offset, exclude_idx)
-            s = self._scores(q, gallery).copy()
-            b, n = s.shape
-            el = eligible(row_filter, b, n).numpy()
-            s[~el] = -np.inf
-            flat = torch.as_tensor(targets).dim() == 1
-            t = self._2d(targets, np.int64)
-            local = t - idx_offset
-            ok = (t >= 0) & (local >= 0) & (local < n)
-            ok &= np.take_along_axis(el, np.where(ok, local, 0), axis=1)
-            if exclude_idx is not None:
-                ex = np.asarray(torch.as_tensor(exclude_idx).numpy(), dtype=np.int64) - idx_offset
-                for r in np.nonzero((ex >= 0) & (ex < n))[0]:
-                    s[r, ex[r]] = -np.inf
-                    ok[r] &= local[r] != ex[r]
-            order = np.argsort(-s, axis=1, kind="stable")
-            place = np.empty_like(order)
-            np.put_along_axis(place, order, np.broadcast_to(np.arange(n), order.shape), axis=1)
-            out = np.where(ok, np.take_along_axis(place, np.where(ok, local, 0), axis=1), -1).astype(np.int32)
-            return torch.from_numpy(out[:, 0] if flat else out)
-
-    return FilteredOracle
+    return RankOracle

@@ -3,25 +3,13 @@
 A numpy restatement of the definition, on any [B, N] score matrix: apply `exclude_idx` and the row filter, sort the rows stably by
 (score descending, index ascending), keep the first row of every item, pad.  A rank is the position of the target item in that list.
 `chain_item_topk` / `chain_item_ranks` feed it oracle.chain's fp32-chain scores (as tests/test_gpu_rank_deep.py:_oracle does);
-`items_oracle()` returns a subclass of the test-only OracleEngine with the item protocol of FernEngine for the CPU tests.
+`items_oracle()` returns the engine that serves them as the item protocol of FernEngine to the CPU tests (tests/rank_oracle.py).
 """
 from __future__ import annotations
 
 import numpy as np
-import torch
 
-
-def masked_scores(scores, idx_offset=0, exclude_idx=None, eligible=None):
-    """A copy of `scores` [B, N] with the excluded row (a global index per query) and the ineligible rows (bool [B, N]) at -inf."""
-    s = np.array(scores, dtype=np.float32, copy=True)
-    b, n = s.shape
-    if eligible is not None:
-        s[~np.asarray(eligible, dtype=bool)] = -np.inf
-    if exclude_idx is not None:
-        ex = np.asarray(exclude_idx, dtype=np.int64) - idx_offset
-        for r in np.nonzero((ex >= 0) & (ex < n))[0]:
-            s[r, ex[r]] = -np.inf
-    return s
+from oracle.rank import masked_scores
 
 
 def item_lists(masked, items, n_items):
@@ -79,47 +67,5 @@ def chain_item_ranks(q, g, items, n_items, target_items, idx_offset=0, exclude_i
 
 
 def items_oracle():
-    from filtered_oracle import eligible as _eligible, filtered_oracle
-    from test_rank_of_cpu import _make_keys
-
-    class ItemsOracle(filtered_oracle()):
-        """The filtered oracle engine + FernEngine's item protocol, from its own scores (q @ g.T)."""
-
-        def _item_masked(self, q, gallery, items, idx_offset, exclude_idx, row_filter):
-            s = self._scores(q, gallery)
-            ids = items.resolve(s.shape[1], "cpu").numpy()
-            el = None if row_filter is None else _eligible(row_filter, *s.shape).numpy()
-            ex = None if exclude_idx is None else torch.as_tensor(exclude_idx).numpy()
-            return masked_scores(s, idx_offset, ex, el), ids
-
-        def sim_topk_items(self, q, gallery, items, k, idx_offset=0, exclude_idx=None, row_filter=None):
-            m, ids = self._item_masked(q, gallery, items, idx_offset, exclude_idx, row_filter)
-            return tuple(torch.from_numpy(a) for a in item_topk(m, ids, items.n_items, k, idx_offset))
-
-        def item_rank_of(self, q, gallery, items, target_items, idx_offset=0, exclude_idx=None, row_filter=None):
-            m, ids = self._item_masked(q, gallery, items, idx_offset, exclude_idx, row_filter)
-            out = item_ranks(m, ids, items.n_items, self._2d(target_items, np.int64))
-            return torch.from_numpy(out[:, 0] if torch.as_tensor(target_items).dim() == 1 else out)
-
-        def _best(self, q, gallery, items, idx_offset, exclude_idx, row_filter):
-            """uint64 [B, n_items]: the key of every item's representative in this gallery (shard), 0 when it has none."""
-            m, ids = self._item_masked(q, gallery, items, idx_offset, exclude_idx, row_filter)
-            best = np.zeros((m.shape[0], items.n_items), dtype=np.uint64)
-            for r, (rows, its) in enumerate(item_lists(m, ids, items.n_items)):
-                best[r, its] = _make_keys(m[r, rows], rows + idx_offset)
-            return best
-
-        def item_keys(self, q, gallery, items, target_items, idx_offset=0, exclude_idx=None, row_filter=None):
-            best = self._best(q, gallery, items, idx_offset, exclude_idx, row_filter)
-            t = self._2d(target_items, np.int64)
-            ok = (t >= 0) & (t < items.n_items)
-            keys = np.where(ok, np.take_along_axis(best, np.where(ok, t, 0), axis=1), np.uint64(0))
-            return torch.from_numpy(keys.view(np.int64).copy())
-
-        def item_count(self, q, gallery, items, keys, idx_offset=0, exclude_idx=None, row_filter=None):
-            best = self._best(q, gallery, items, idx_offset, exclude_idx, row_filter)
-            k = self._2d(keys, np.int64).view(np.uint64)
-            count = (best[:, :, None] > k[:, None, :]).sum(axis=1)
-            return torch.from_numpy(np.where(k == 0, -1, count).astype(np.int32))
-
-    return ItemsOracle
+    from rank_oracle import RankOracle
+    return RankOracle

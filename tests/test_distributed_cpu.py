@@ -1,36 +1,21 @@
 """CPU, world_size 2 over gloo: the multi-GPU layout (gallery shard + all_gather, query DP, sharded top-K merge)
 is placement-independent and reproduces the single-process ordering exactly.  Compute = TEST-ONLY OracleEngine."""
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+import gloo
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, n, out_dir):
-    sys.path.insert(0, HERE)
-    sys.path.insert(0, os.path.dirname(HERE))
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    torch.set_num_threads(2)
+def _worker(rank, world, n, out_dir):
     from oracle_engine import OracleEngine
     from fashionern_aaai2024_amd import distributed as fd
     from fashionern_aaai2024_amd import synth
-    r, w, _ = fd.init_from_env("gloo")
-    assert (r, w) == (rank, world)
     d = 128
     eng = OracleEngine()
     eng.load_tensors(synth.fusion_state_dict(d, seed=3))
@@ -79,8 +64,6 @@ def _worker(rank, world, port, n, out_dir):
     if rank == 0:
         np.savez(os.path.join(out_dir, "r0.npz"), gallery=gallery.numpy(), s=s_all.numpy(), i=i_all.numpy(), s_sh=s_sh.numpy(), i_sh=i_sh.numpy(),
                  ef=ef.numpy(), el=el.numpy(), en=np.array(en))
-    dist.barrier()
-    dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("n", [101, 64, 1])
@@ -89,8 +72,7 @@ def test_two_rank_layout_matches_single_process(tmp_path, n):
     from oracle_engine import OracleEngine
     from fashionern_aaai2024_amd import synth
     from oracle import rank as orank
-    port = _free_port()
-    mp.spawn(_worker, args=(2, port, n, str(tmp_path)), nprocs=2, join=True)
+    gloo.spawn(2, _worker, n, str(tmp_path))
     got = np.load(tmp_path / "r0.npz")
     d = 128
     eng = OracleEngine()
@@ -122,13 +104,9 @@ def test_shard_rows_cover_everything_once():
             assert all(stop - start <= per for start, stop, per in spans)
 
 
-def _harness_worker(rank, world, port, out_dir):
+def _harness_worker(rank, world, out_dir):
     """The run/test_* harness under torch.distributed: sharded gallery encode, sharded gallery fusion + all-gather, query data
     parallel, gathered rankings.  Every rank must return the recall tuples of the single-process run."""
-    sys.path.insert(0, HERE)
-    sys.path.insert(0, os.path.dirname(HERE))
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    torch.set_num_threads(2)
     import json
     import synthetic_data as sdata
     from oracle_engine import OracleEngine
@@ -137,7 +115,6 @@ def _harness_worker(rank, world, port, out_dir):
     from fashionern_aaai2024_amd.model import ERN
     from fashionern_aaai2024_amd.run import test_200k, test_cirr, test_fiq, test_shoes, test_val
     from fashionern_aaai2024_amd.tokenizer import register_tokenizer
-    fd.init_from_env("gloo")
     register_tokenizer("stub", sdata.stub_tokenizer)
     meta = json.load(open(os.path.join(HERE, "golden", "harness.json")))
     d, n, q = meta["d"], meta["n"], meta["q"]
@@ -157,8 +134,6 @@ def _harness_worker(rank, world, port, out_dir):
             assert targets == [it[1] for it in rel.items] and pred.shape == (q, d)
             out["fiq_pred"] = pred.numpy().tolist()
     json.dump(out, open(os.path.join(out_dir, f"harness_r{rank}.json"), "w"))
-    dist.barrier()
-    dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -166,8 +141,7 @@ def test_harness_under_torch_distributed_reproduces_reference_recalls(tmp_path, 
     """SURVEY 8e / VERDICT r2 item 1c: run/test_{fiq,cirr,200k,shoes,val} with WORLD_SIZE > 1 (gloo) -- recall tuples equal the
     imported reference's (tests/golden/harness.json), on every rank; world 3 leaves ragged query / gallery shards."""
     import json
-    port = _free_port()
-    mp.spawn(_harness_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
+    gloo.spawn(world, _harness_worker, str(tmp_path))
     meta = json.load(open(os.path.join(HERE, "golden", "harness.json")))
     gold = np.load(os.path.join(HERE, "golden", "harness.npz"))
     for r in range(world):
@@ -190,20 +164,14 @@ class _TunerStub:
         self.text = text
 
 
-def _world8_worker(rank, world, port, out_dir):
+def _world8_worker(rank, world, out_dir):
     """every collective helper of the path at WORLD = 8 over gloo with the block types the GPU job moves --
     bf16 gallery shards and int32 index blocks as BYTE views (no dtype support needed from the backend: the RCCL call sees uint8
     too), fp32 score blocks, ragged gathers with objects, the tuner-plan broadcast, and the sharded ranking's candidate gathers."""
-    sys.path.insert(0, HERE)
-    sys.path.insert(0, os.path.dirname(HERE))
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    torch.set_num_threads(1)
     from oracle_engine import OracleEngine
     from fashionern_aaai2024_amd import distributed as fd
     from fashionern_aaai2024_amd import synth
-    r, w, _ = fd.init_from_env("gloo")
-    assert (r, w) == (rank, world) and fd.world_info() == (rank, world)
-    n, d, k = 1003, 64, 9                                              # ragged: the last shard is short
+    n, d, k = 1003, 64, 9                                             # ragged: the last shard is short
     start, stop, per = fd.shard_rows(n, rank, world)
     full = torch.from_numpy(synth.unit_rows(n, d, tag="w8"))
     # (1) bf16 shards through _all_gather_into / all_gather_shards, also into a pre-allocated store (`out=`, bench.py's gallery store)
@@ -243,11 +211,8 @@ def _world8_worker(rank, world, port, out_dir):
     s_re, i_re = fd.rank_replicated(eng, q, full, k, exclude_idx=ex)
     assert torch.equal(i_sh, i_re) and torch.equal(s_sh, s_re)
     open(os.path.join(out_dir, f"ok{rank}"), "w").write("ok")
-    dist.barrier()
-    dist.destroy_process_group()
 
 
 def test_world8_collectives_move_bf16_and_int32_blocks_as_bytes(tmp_path):
-    port = _free_port()
-    mp.spawn(_world8_worker, args=(8, port, str(tmp_path)), nprocs=8, join=True)
+    gloo.spawn(8, _world8_worker, str(tmp_path), threads=1)
     assert sorted(os.listdir(tmp_path)) == [f"ok{r}" for r in range(8)]

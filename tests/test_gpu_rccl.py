@@ -52,7 +52,7 @@ whole = eng.prepare_gallery(g)
 pg = fd.all_gather_prepared(eng, g, 1000)
 store = PreparedGallery(torch.empty_like(g), torch.empty(g.shape, dtype=torch.bfloat16, device=dev), torch.zeros(4, device=dev))
 pg2 = fd.all_gather_prepared(eng, g, 1000, out=store)
-m = fd._all_reduce_max(whole.meta.clone())
+m = fd._all_reduce(whole.meta.clone(), dist.ReduceOp.MAX)
 q = torch.nn.functional.normalize(torch.randn(8, 512, device=dev), dim=-1)
 s0, i0 = eng.sim_topk(q, whole, 50)
 s1, i1 = eng.sim_topk(q, pg2, 50)

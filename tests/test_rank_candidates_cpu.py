@@ -3,14 +3,13 @@ point fern_sim_topk_candidates (header, library, ctypes table, ABI version), the
 distributed.rank_candidates_sharded over gloo with the oracle engine."""
 import os
 import re
-import socket
-import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+import gloo
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -158,14 +157,6 @@ def test_recalls_cirr_subset_and_pipeline_keywords_exist():
 
 
 # ---- world 2 over gloo -----------------------------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _sharded_case():
     """Operands in {-1, 0, 1} / 8 (exact scores, many ties); 701 rows over two ranks are 351 + 350; lists that straddle the cut, with
     duplicates, negatives and entries past the gallery."""
@@ -183,28 +174,21 @@ def _sharded_case():
     return gallery, q, cand, ex, flt, RowFilter
 
 
-def _worker(rank, world, port, out_dir):
-    sys.path.insert(0, HERE)
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    torch.set_num_threads(2)
+def _worker(rank, world, out_dir):
     from candidates_oracle import candidates_oracle
     from fashionern_aaai2024_amd import distributed as fd
-    fd.init_from_env("gloo")
     gallery, q, cand, ex, (tags, mask, value), RowFilter = _sharded_case()
     eng = candidates_oracle()()
     start, stop, _ = fd.shard_rows(gallery.shape[0], rank, world)
     s, i = fd.rank_candidates_sharded(eng, q, gallery[start:stop], start, cand, 50)
     s2, i2 = fd.rank_candidates_sharded(eng, q, gallery[start:stop], start, cand, 120, exclude_idx=ex, row_filter=RowFilter(tags[start:stop], mask, value))
     np.savez(os.path.join(out_dir, f"r{rank}.npz"), s=s.numpy(), i=i.numpy(), s2=s2.numpy(), i2=i2.numpy())
-    dist.barrier()
-    dist.destroy_process_group()
 
 
 def test_sharded_candidate_ranking_equals_the_unsharded_oracle(tmp_path):
     from candidates_oracle import candidates_oracle
     from fashionern_aaai2024_amd import distributed as fd
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    gloo.spawn(2, _worker, str(tmp_path))
     gallery, q, cand, ex, (tags, mask, value), RowFilter = _sharded_case()
     eng = candidates_oracle()()
     s, i = eng.sim_topk_candidates(q, gallery, cand, 50)

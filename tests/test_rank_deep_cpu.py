@@ -2,13 +2,12 @@
 k > 64 routing of distributed.rank_replicated / rank_sharded to sim_topk_deep and the wide topk_merge (world 2 over gloo)."""
 import os
 import re
-import socket
-import sys
 
 import numpy as np
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+import gloo
+from oracle_engine import OracleEngine
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -47,41 +46,27 @@ def test_deep_argument_errors_name_the_function():
     assert b"fern_topk_merge" in lib.fern_last_error()
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+class DeepStub(OracleEngine):
+    """OracleEngine with the deep entry point and a record of what the ranking helpers called."""
+    def __init__(self):
+        super().__init__()
+        self.calls = []
+
+    def sim_topk(self, q, gallery, k, idx_offset=0, exclude_idx=None):
+        self.calls.append(("sim_topk", k))
+        return super().sim_topk(q, gallery, k, idx_offset, exclude_idx)
+
+    def sim_topk_deep(self, q, gallery, k, idx_offset=0, exclude_idx=None):
+        self.calls.append(("sim_topk_deep", k))
+        return super().sim_topk(q, gallery, k, idx_offset, exclude_idx)
+
+    def topk_merge(self, scores, idx):
+        self.calls.append(("topk_merge", scores.shape[2]))
+        return super().topk_merge(scores, idx)
 
 
-def _worker(rank, world, port, out_dir):
-    sys.path.insert(0, HERE)
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    torch.set_num_threads(2)
-    from oracle_engine import OracleEngine
+def _worker(rank, world, out_dir):
     from fashionern_aaai2024_amd import distributed as fd
-
-    class DeepStub(OracleEngine):
-        """OracleEngine with the deep entry point and a record of what the ranking helpers called."""
-        def __init__(self):
-            super().__init__()
-            self.calls = []
-
-        def sim_topk(self, q, gallery, k, idx_offset=0, exclude_idx=None):
-            self.calls.append(("sim_topk", k))
-            return super().sim_topk(q, gallery, k, idx_offset, exclude_idx)
-
-        def sim_topk_deep(self, q, gallery, k, idx_offset=0, exclude_idx=None):
-            self.calls.append(("sim_topk_deep", k))
-            return super().sim_topk(q, gallery, k, idx_offset, exclude_idx)
-
-        def topk_merge(self, scores, idx):
-            self.calls.append(("topk_merge", scores.shape[2]))
-            return super().topk_merge(scores, idx)
-
-    fd.init_from_env("gloo")
     n, d = 701, 32
     g = torch.Generator().manual_seed(5)
     gallery = torch.nn.functional.normalize(torch.randn(n, d, generator=g), dim=-1)
@@ -94,13 +79,11 @@ def _worker(rank, world, port, out_dir):
     small = fd.rank_replicated(eng, q, gallery, 7)
     np.savez(os.path.join(out_dir, f"r{rank}.npz"), s_rep=s_rep.numpy(), i_rep=i_rep.numpy(), s_sh=s_sh.numpy(), i_sh=i_sh.numpy(),
              calls=np.array([f"{a}:{b}" for a, b in eng.calls]), small=small[1].numpy())
-    dist.barrier()
-    dist.destroy_process_group()
 
 
 def test_distributed_ranking_routes_deep_k(tmp_path):
     from oracle import rank as orank
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    gloo.spawn(2, _worker, str(tmp_path))
     n, d = 701, 32
     g = torch.Generator().manual_seed(5)
     gallery = torch.nn.functional.normalize(torch.randn(n, d, generator=g), dim=-1)

@@ -5,14 +5,13 @@ OracleEngine (tests/filtered_oracle.py) against the recall tuples captured from 
 import json
 import os
 import re
-import socket
-import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+import gloo
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -214,14 +213,6 @@ def test_unfiltered_harness_calls_do_not_pass_the_keyword():
 
 
 # ---- world 2 over gloo -------------------------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _sharded_case():
     """Operands in {-1, 0, 1} / 8: every dot product is exact in fp32 in any summation order, so a shard's scores are the whole
     gallery's bit for bit (and ties abound).  Ragged: 701 rows over two ranks are 351 + 350.  Tags: category = row % 3 in bits 0-1,
@@ -240,14 +231,9 @@ def _sharded_case():
     return gallery, q, targets, ex, tags, mask, value, RowFilter
 
 
-def _worker(rank, world, port, out_dir):
-    sys.path.insert(0, HERE)
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    torch.set_num_threads(2)
+def _worker(rank, world, out_dir):
     from filtered_oracle import filtered_oracle
     from fashionern_aaai2024_amd import distributed as fd
-    fd.init_from_env("gloo")
     gallery, q, targets, ex, tags, mask, value, RowFilter = _sharded_case()
     eng = filtered_oracle()()
     start, stop, _ = fd.shard_rows(gallery.shape[0], rank, world)
@@ -256,13 +242,11 @@ def _worker(rank, world, port, out_dir):
     s, i = fd.rank_sharded(eng, q, gallery[start:stop], start, 50, exclude_idx=ex, row_filter=flt)
     s2, i2 = fd.rank_sharded(eng, q, gallery[start:stop], start, 200, row_filter=flt)
     np.savez(os.path.join(out_dir, f"r{rank}.npz"), ranks=ranks.numpy(), s=s.numpy(), i=i.numpy(), s2=s2.numpy(), i2=i2.numpy())
-    dist.barrier()
-    dist.destroy_process_group()
 
 
 def test_filtered_sharded_ranking_equals_the_unsharded_result(tmp_path):
     from filtered_oracle import filtered_oracle
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    gloo.spawn(2, _worker, str(tmp_path))
     gallery, q, targets, ex, tags, mask, value, RowFilter = _sharded_case()
     eng = filtered_oracle()()
     flt = RowFilter(tags, mask, value)

@@ -1,20 +1,21 @@
 """Item-level ranking without a GPU: the C ABI entry points (header, library, ctypes table, argument checks), `ItemMap`'s rules,
 `run/_common.recalls_items` and the 200k driver flag on the TEST-ONLY oracle engine (tests/items_oracle.py), and
 `distributed.rank_items_sharded` / `item_rank_of_sharded` over gloo in worlds of two and three."""
+import json
 import os
 import re
-import socket
-import sys
 import types
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+import gloo
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
+META = json.load(open(os.path.join(HERE, "golden", "harness.json")))
 
 
 # ---- C ABI -----------------------------------------------------------------------------------------------------------------------
@@ -139,7 +140,6 @@ def test_200k_item_metrics_on_the_duplicate_name_fixture():
     item places are the oracle's."""
     import items_oracle as io
     import synthetic_data as sdata
-    from test_rank_of_cpu import META
     from fashionern_aaai2024_amd import synth
     from fashionern_aaai2024_amd.model import ERN
     from fashionern_aaai2024_amd.run import rank_metrics, test_200k
@@ -161,14 +161,6 @@ def test_200k_item_metrics_on_the_duplicate_name_fixture():
 
 
 # ---- worlds of two and three over gloo ---------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _sharded_case():
     """Operands in {-1, 0, 1} / 8: every dot product is exact in fp32 in any summation order, so a shard's scores are the whole gallery's
     bit for bit (and ties abound).  702 rows = 18 blocks of 39 rows, every block four items of 1, 5, 13 and 20 rows: the shard boundaries
@@ -189,14 +181,9 @@ def _sharded_case():
     return gallery, q, ItemMap(torch.from_numpy(ids), 80), ItemMap(torch.arange(n) // 40, 80), targets, ex, flt, RowFilter
 
 
-def _worker(rank, world, port, out_dir):
-    sys.path.insert(0, HERE)
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    torch.set_num_threads(2)
+def _worker(rank, world, out_dir):
     import items_oracle as io
     from fashionern_aaai2024_amd import distributed as fd
-    fd.init_from_env("gloo")
     gallery, q, items, split, targets, ex, (tags, mask, value), RowFilter = _sharded_case()
     eng = io.items_oracle()()
     start, stop, _ = fd.shard_rows(gallery.shape[0], rank, world)
@@ -217,14 +204,12 @@ def _worker(rank, world, port, out_dir):
             raised.append(int("every item's rows inside one shard" in str(e)))
     out["raised"] = torch.tensor(raised)
     np.savez(os.path.join(out_dir, f"r{rank}.npz"), **{k: v.numpy() for k, v in out.items()})
-    dist.barrier()
-    dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_item_ranking_equals_the_unsharded_result(tmp_path, world):
     import items_oracle as io
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    gloo.spawn(world, _worker, str(tmp_path))
     gallery, q, items, split, targets, ex, (tags, mask, value), RowFilter = _sharded_case()
     eng = io.items_oracle()()
     flt = RowFilter(tags, mask, value)

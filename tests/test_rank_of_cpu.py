@@ -4,14 +4,14 @@ the imported reference harness (tests/golden/harness.json, the TEST-ONLY OracleE
 import json
 import os
 import re
-import socket
-import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+import gloo
+from rank_oracle import RankOracle
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -62,73 +62,6 @@ def test_retrieval_metrics_on_hand_made_ranks():
 
 
 # ---- the harness against the oracle engine -----------------------------------------------------------------------------------------
-def _orderable(s):
-    u = np.ascontiguousarray(s, dtype=np.float32).view(np.uint32)
-    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
-
-
-def _make_keys(scores, idx):
-    """include/fern.h's ranking key: orderable(score) << 32 | ~global index, as uint64."""
-    return (_orderable(scores).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - idx.astype(np.uint64))
-
-
-def _rank_stub():
-    from oracle_engine import OracleEngine
-
-    class RankStub(OracleEngine):
-        """OracleEngine + the rank protocol of FernEngine, from its own scores (q @ g.T): `rank_of` by a stable argsort, `rank_keys` /
-        `rank_count` by the key definition of include/fern.h (what the sharded helper is built from)."""
-
-        def _scores(self, q, gallery):
-            return (q.float().cpu() @ self._rows(gallery).float().cpu().T).numpy()
-
-        @staticmethod
-        def _2d(t, dtype):
-            t = np.asarray(torch.as_tensor(t).cpu().numpy(), dtype=dtype)
-            return t[:, None] if t.ndim == 1 else t
-
-        def rank_keys(self, q, gallery, targets, idx_offset=0):
-            s = self._scores(q, gallery)
-            t = self._2d(targets, np.int64)
-            local = t - idx_offset
-            ok = (t >= 0) & (local >= 0) & (local < s.shape[1])
-            ts = np.take_along_axis(s, np.where(ok, local, 0), axis=1) if s.shape[1] else np.zeros(t.shape, dtype=np.float32)
-            keys = np.where(ok, _make_keys(ts, np.where(ok, t, 0)), np.uint64(0))
-            return torch.from_numpy(keys.view(np.int64).copy())
-
-        def rank_count(self, q, gallery, keys, idx_offset=0, exclude_idx=None):
-            s = self._scores(q, gallery)
-            b, n = s.shape
-            k = self._2d(keys, np.int64).view(np.uint64)
-            row_keys = _make_keys(s, np.broadcast_to(np.arange(n) + idx_offset, s.shape))
-            if exclude_idx is not None:
-                ex = np.asarray(torch.as_tensor(exclude_idx).numpy(), dtype=np.int64) - idx_offset
-                for r in np.nonzero((ex >= 0) & (ex < n))[0]:
-                    row_keys[r, ex[r]] = 0
-            count = (row_keys[:, :, None] > k[:, None, :]).sum(axis=1)
-            return torch.from_numpy(np.where(k == 0, -1, count).astype(np.int32))
-
-        def rank_of(self, q, gallery, targets, idx_offset=0, exclude_idx=None):
-            s = self._scores(q, gallery).copy()
-            b, n = s.shape
-            flat = torch.as_tensor(targets).dim() == 1
-            t = self._2d(targets, np.int64)
-            local = t - idx_offset
-            ok = (t >= 0) & (local >= 0) & (local < n)
-            if exclude_idx is not None:
-                ex = np.asarray(torch.as_tensor(exclude_idx).numpy(), dtype=np.int64) - idx_offset
-                for r in np.nonzero((ex >= 0) & (ex < n))[0]:
-                    s[r, ex[r]] = -np.inf
-                    ok[r] &= local[r] != ex[r]
-            order = np.argsort(-s, axis=1, kind="stable")
-            place = np.empty_like(order)
-            np.put_along_axis(place, order, np.broadcast_to(np.arange(n), order.shape), axis=1)
-            out = np.where(ok, np.take_along_axis(place, np.where(ok, local, 0), axis=1), -1).astype(np.int32)
-            return torch.from_numpy(out[:, 0] if flat else out)
-
-    return RankStub
-
-
 def _build(kind):
     import synthetic_data as sdata
     from fashionern_aaai2024_amd import synth
@@ -138,7 +71,7 @@ def _build(kind):
     register_tokenizer("stub", sdata.stub_tokenizer)
     d, n, q = META["d"], META["n"], META["q"]
     clip = sdata.StubCLIP(d).eval()
-    model = ERN(clip, d, "cpu", engine=_rank_stub()())
+    model = ERN(clip, d, "cpu", engine=RankOracle())
     model.load_state_dict(synth.fusion_state_dict(d, seed=META["fusion_seed"]))
     gal = sdata.Gallery(n, d, seed=META["gallery_seed"], dup_names=(kind == "200k"))
     rel = sdata.RelativeDataset(gal, q, kind, seed=META["relative_seed"])
@@ -178,14 +111,6 @@ def test_ranks_below_50_agree_with_the_golden_top50_lists():
 
 
 # ---- world 2 over gloo -------------------------------------------------------------------------------------------------------------
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _sharded_case():
     """Operands in {-1, 0, 1} / 8: every dot product is exact in fp32 in any summation order, so a shard's scores are the whole
     gallery's bit for bit (and ties abound).  Ragged: 701 rows over two ranks are 351 + 350."""
@@ -198,28 +123,21 @@ def _sharded_case():
     return gallery, q, targets, ex
 
 
-def _worker(rank, world, port, out_dir):
-    sys.path.insert(0, HERE)
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    torch.set_num_threads(2)
+def _worker(rank, world, out_dir):
     from fashionern_aaai2024_amd import distributed as fd
-    fd.init_from_env("gloo")
     gallery, q, targets, ex = _sharded_case()
-    eng = _rank_stub()()
+    eng = RankOracle()
     start, stop, _ = fd.shard_rows(gallery.shape[0], rank, world)
     plain = fd.rank_of_sharded(eng, q, gallery[start:stop], start, targets)
     excl = fd.rank_of_sharded(eng, q, gallery[start:stop], start, targets, exclude_idx=ex)
     flat = fd.rank_of_sharded(eng, q, gallery[start:stop], start, targets[:, 0])
     np.savez(os.path.join(out_dir, f"r{rank}.npz"), plain=plain.numpy(), excl=excl.numpy(), flat=flat.numpy())
-    dist.barrier()
-    dist.destroy_process_group()
 
 
 def test_rank_of_sharded_equals_the_unsharded_ranks(tmp_path):
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    gloo.spawn(2, _worker, str(tmp_path))
     gallery, q, targets, ex = _sharded_case()
-    eng = _rank_stub()()
+    eng = RankOracle()
     plain = eng.rank_of(q, gallery, targets).numpy()
     excl = eng.rank_of(q, gallery, targets, exclude_idx=ex).numpy()
     assert (plain[1, 2], plain[3, 1]) == (-1, -1) and (excl[2, 2], excl[3, 0], excl[4, 0]) == (-1, -1, -1)
@@ -235,6 +153,6 @@ def test_rank_of_sharded_makes_no_collective_in_a_world_of_one():
     from fashionern_aaai2024_amd import distributed as fd
     assert not (dist.is_available() and dist.is_initialized())
     gallery, q, targets, ex = _sharded_case()
-    eng = _rank_stub()()
+    eng = RankOracle()
     got = fd.rank_of_sharded(eng, q, gallery, 0, targets, exclude_idx=ex)
     assert np.array_equal(got.numpy(), eng.rank_of(q, gallery, targets, exclude_idx=ex).numpy())

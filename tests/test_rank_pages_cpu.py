@@ -4,14 +4,13 @@ distributed.rank_from_sharded over gloo and run/_common.ranking_to_depth, the la
 key definition of include/fern.h."""
 import os
 import re
-import sys
 
 import numpy as np
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
-from test_rank_of_cpu import _free_port, _make_keys, _rank_stub
+import gloo
+from rank_oracle import RankOracle, _make_keys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -97,33 +96,7 @@ def test_next_from_on_full_partial_and_empty_pages():
     assert g[2] == 0                                      # no filled place: the cursor that makes nothing eligible
 
 
-# ---- the stub engine -----------------------------------------------------------------------------------------------------------------
-def _page_stub():
-    class PageStub(_rank_stub()):
-        """The rank protocol stub + `sim_topk_from` by the key definition: the k greatest row keys that are <= the cursor."""
-
-        def sim_topk_from(self, q, gallery, k, from_keys, idx_offset=0, exclude_idx=None):
-            s = self._scores(q, gallery)
-            b, n = s.shape
-            keys = _make_keys(s, np.broadcast_to(np.arange(n) + idx_offset, s.shape)).copy()
-            ceil = np.asarray(torch.as_tensor(from_keys).numpy(), dtype=np.int64).view(np.uint64)
-            keys[keys > ceil[:, None]] = 0
-            if exclude_idx is not None:
-                ex = np.asarray(torch.as_tensor(exclude_idx).numpy(), dtype=np.int64) - idx_offset
-                for r in np.nonzero((ex >= 0) & (ex < n))[0]:
-                    keys[r, ex[r]] = 0
-            out_s = np.full((b, k), -np.inf, dtype=np.float32)
-            out_i = np.full((b, k), -1, dtype=np.int32)
-            for r in range(b):
-                order = np.argsort(keys[r], kind="stable")[::-1][:k]
-                order = order[keys[r, order] != 0]
-                out_s[r, :len(order)] = s[r, order]
-                out_i[r, :len(order)] = order + idx_offset
-            return torch.from_numpy(out_s), torch.from_numpy(out_i)
-
-    return PageStub
-
-
+# ---- the oracle engine (tests/rank_oracle.py: `sim_topk_from` by the key definition) ---------------------------------------------------
 def _case():
     """Operands in {-1, 0, 1} / 8: every dot product is exact in fp32 in any order, so a shard's scores are the whole gallery's bit for
     bit and ties abound.  Ragged: 701 rows over two ranks are 351 + 350."""
@@ -153,26 +126,19 @@ def _follow(fn, b):
     return np.concatenate(pages, axis=1)
 
 
-def _worker(rank, world, port, out_dir):
-    sys.path.insert(0, HERE)
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    torch.set_num_threads(2)
+def _worker(rank, world, out_dir):
     from fashionern_aaai2024_amd import distributed as fd
-    fd.init_from_env("gloo")
     gallery, q = _case()
-    eng = _page_stub()()
+    eng = RankOracle()
     start, stop, _ = fd.shard_rows(gallery.shape[0], rank, world)
     ex = torch.tensor([3, -1, 400, 700], dtype=torch.int32)
     got = _follow(lambda c: fd.rank_from_sharded(eng, q, gallery[start:stop], start, PAGE, c), q.shape[0])
     excl = _follow(lambda c: fd.rank_from_sharded(eng, q, gallery[start:stop], start, PAGE, c, exclude_idx=ex), q.shape[0])
     np.savez(os.path.join(out_dir, f"r{rank}.npz"), got=got, excl=excl)
-    dist.barrier()
-    dist.destroy_process_group()
 
 
 def test_sharded_cursor_pages_equal_the_unsharded_ranking(tmp_path):
-    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
+    gloo.spawn(2, _worker, str(tmp_path))
     gallery, q = _case()
     order = _stable_ranking(q, gallery)
     n = gallery.shape[0]
@@ -196,7 +162,7 @@ def test_rank_from_sharded_makes_no_collective_in_a_world_of_one():
     from fashionern_aaai2024_amd import distributed as fd
     assert not (dist.is_available() and dist.is_initialized())
     gallery, q = _case()
-    eng = _page_stub()()
+    eng = RankOracle()
     got = _follow(lambda c: fd.rank_from_sharded(eng, q, gallery, 0, PAGE, c), q.shape[0])
     n = gallery.shape[0]
     assert np.array_equal(got[:, :n], _stable_ranking(q, gallery)) and (got[:, n:] == -1).all()
@@ -208,7 +174,7 @@ def test_ranking_to_depth_fills_cursor_pages_past_1024():
     g = torch.Generator().manual_seed(11)
     gallery = torch.randint(-1, 2, (1700, 32), generator=g).float() / 8
     q = torch.randint(-1, 2, (3, 32), generator=g).float() / 8
-    eng = _page_stub()()
+    eng = RankOracle()
     order = _stable_ranking(q, gallery)
     got = ranking_to_depth(eng, q, gallery, 1500)
     assert got.dtype == np.int32 and got.shape == (3, 1500)
