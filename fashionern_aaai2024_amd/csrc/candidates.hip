@@ -5,7 +5,7 @@
 //              atomics, nothing depends on arrival order);
 //   scores     fp32 rows: each survivor's sequential fp32 chain (oracle/chain.c order), a wave taking 32 survivors per round through
 //              rescore.h's ring (rescore_keys) when D is a whole, even number of 32-k steps, else 16 per round through its per-lane
-//              form (chain_run, rank.hip's key producer) -- the same chain;
+//              form (chain_rows_lane, as rank.hip's key producer) -- the same chain;
 //              bf16 rows: the sweep's v_mfma_f32_32x32x16_bf16 with the sweep's operand roles -- A = the query rounded to bf16 (every A
 //              row holds it), B = 32 candidate rows per round, lane (l31, lh) loading row l31's 16-byte k fragments straight from the
 //              gathered row, k ascending 16 at a time from a zero accumulator -- so a score has the sweep's bits;
@@ -27,10 +27,9 @@ typedef short bf16x8c __attribute__((ext_vector_type(8)));
 constexpr int CAND_NT = 256;
 constexpr int CAND_WAVES = CAND_NT / 64;
 constexpr int CAND_TILE = 2 * RESC_ROWS * RESC_TLD;      // floats of one wave's chain tile (rescore.h: double buffered)
-constexpr int CAND_ODD_T = 16;                           // per-lane form: rows per wave and round ...
-constexpr int CAND_ODD_CH = 128;                         // ... k per step ...
-constexpr int CAND_ODD_LD = CAND_ODD_CH + 4;             // ... floats per tile row (+ 4: as rank.hip's RK_LD)
-static_assert((CAND_ODD_T + 1) * CAND_ODD_LD <= CAND_TILE, "the per-lane form's rows and the query's step fit one wave's chain tile");
+constexpr int CAND_ODD_T = CHAIN_T;                      // per-lane form (rescore.h: chain_rows_lane): rows per wave and round ...
+constexpr int CAND_ODD_CH = 128;                         // ... k per step
+static_assert(chain_tile_floats<CAND_ODD_CH>() <= CAND_TILE, "the per-lane form's rows and the query's step fit one wave's chain tile");
 constexpr unsigned short CAND_NONE = 0xFFFFu;            // an entry that takes no place
 
 enum CandForm : int { CAND_F32_RING = 0, CAND_F32_LANE = 1, CAND_BF16 = 2 };
@@ -58,30 +57,6 @@ __host__ __device__ inline CandLds cand_lds(int M, int D, int form) {
     return l;
 }
 
-// exclusive scan of one count per thread over the workgroup (wave shuffles + the four wave totals in wtot); returns the thread's
-// offset, *total the sum.  Two barriers inside: wtot may be reused after it returns.
-__device__ __forceinline__ int cand_block_scan(int v, int* wtot, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const int o = __shfl_up(inc, s);
-        if (lane >= s) inc += o;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    int base = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < CAND_WAVES; ++w) {
-        const int t = wtot[w];
-        base += w < wave ? t : 0;
-        sum += t;
-    }
-    __syncthreads();
-    *total = sum;
-    return base + inc - v;
-}
-
 template <int FORM>
 __global__ __launch_bounds__(CAND_NT) void candidates_kernel(const float* __restrict__ q, const void* __restrict__ gallery, long N, int D,
                                                              const int* __restrict__ cand, int M, int K, long idx_offset,
@@ -102,7 +77,7 @@ __global__ __launch_bounds__(CAND_NT) void candidates_kernel(const float* __rest
     // ---- validity: survivors compacted in entry order ----
     const int ex = exclude ? exclude[b] : -1;
     const bool tagged = rt.tags != nullptr;
-    const unsigned fm = tagged ? rt.mask[b] : 0u, fv = tagged ? rt.value[b] : 0u;
+    const QueryTags qt = query_tags(rt, b);
     if (FORM == CAND_BF16) {      // the query's bf16 image, rounded as the sweep rounds it
         unsigned short* qb = reinterpret_cast<unsigned short*>(cand_smem + L.qb);
         for (int i = tid; i < D; i += CAND_NT) qb[i] = f32_to_bf16_bits(qrow[i]);
@@ -113,9 +88,10 @@ __global__ __launch_bounds__(CAND_NT) void candidates_kernel(const float* __rest
         const int c = j < M ? list[j] : -1;
         const long r = (long)c - idx_offset;
         bool ok = c >= 0 && r >= 0 && r < N && !(exclude && c == ex);
-        if (ok && tagged) ok = row_eligible(rt.tags[r], fm, fv);
+        if (ok && tagged) ok = row_eligible(rt.tags[r], qt.mask, qt.value);
         int total;
-        const int p = ns + cand_block_scan(ok ? 1 : 0, wtot, &total);
+        const int p = ns + block_exclusive_scan<CAND_WAVES>(ok ? 1 : 0, wtot, total);
+        __syncthreads();                                     // wtot is written again by the next round
         if (ok) surv[p] = (unsigned)r;
         if (j < M) ent[j] = ok ? (unsigned short)p : CAND_NONE;
         ns += total;
@@ -128,34 +104,12 @@ __global__ __launch_bounds__(CAND_NT) void candidates_kernel(const float* __rest
         for (int s0 = wave * RESC_ROWS; s0 < ns; s0 += CAND_WAVES * RESC_ROWS)
             rescore_keys(surv, s0, ns, qrow, reinterpret_cast<const float*>(gallery), D, tl, ckey);
     } else if (FORM == CAND_F32_LANE) {
-        // 16 survivors per wave and round: a step brings 128 k of the 16 rows and of the query into the wave's tile (eight 16-byte loads
-        // per lane and one of the query, all in flight behind one wait), lane t < 16 continues survivor t's chain over them
+        // 16 survivors per wave and round through the per-lane chain stager, 128 k per step (eight 16-byte loads per lane and one of
+        // the query); the four waves run their rounds independently: the stager synchronises inside the wave only
         float* tl = reinterpret_cast<float*>(cand_smem + L.scratch) + wave * CAND_TILE;
         const float* g = reinterpret_cast<const float*>(gallery);
-        const int lrow = lane >> 5, lcol = (lane & 31) * 4;
         for (int s0 = wave * CAND_ODD_T; s0 < ns; s0 += CAND_WAVES * CAND_ODD_T) {
-            const float* src[CAND_ODD_T / 2];
-#pragma unroll
-            for (int i = 0; i < CAND_ODD_T / 2; ++i) {
-                const int s = s0 + 2 * i + lrow;
-                src[i] = g + (long)surv[s < ns ? s : s0] * D;
-            }
-            float acc = 0.0f;
-            for (int k0 = 0; k0 < D; k0 += CAND_ODD_CH) {
-                const int kc = k0 + lcol;
-                const bool in = kc < D;
-                f32x4e v[CAND_ODD_T / 2 + 1];
-#pragma unroll
-                for (int i = 0; i < CAND_ODD_T / 2; ++i) v[i] = *reinterpret_cast<const f32x4e*>(src[i] + (in ? kc : 0));
-                v[CAND_ODD_T / 2] = *reinterpret_cast<const f32x4e*>(qrow + (in ? kc : 0));
-                __builtin_amdgcn_wave_barrier();             // (one wave, LDS in order: the previous step's chain reads come first)
-#pragma unroll
-                for (int i = 0; i < CAND_ODD_T / 2; ++i) *reinterpret_cast<f32x4e*>(tl + (2 * i + lrow) * CAND_ODD_LD + lcol) = v[i];
-                if (lrow == 0) *reinterpret_cast<f32x4e*>(tl + CAND_ODD_T * CAND_ODD_LD + lcol) = v[CAND_ODD_T / 2];
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_wave_barrier();
-                if (lane < CAND_ODD_T) acc = chain_run(tl + lane * CAND_ODD_LD, tl + CAND_ODD_T * CAND_ODD_LD, min(CAND_ODD_CH, D - k0), acc);
-            }
+            const float acc = chain_rows_lane<CAND_ODD_CH>([&](int t) { return g + (long)surv[s0 + t < ns ? s0 + t : s0] * D; }, qrow, D, tl);
             if (lane < CAND_ODD_T && s0 + lane < ns) ckey[s0 + lane] = make_key(acc, surv[s0 + lane]);
         }
     } else {
@@ -229,7 +183,8 @@ __global__ __launch_bounds__(CAND_NT) void candidates_kernel(const float* __rest
         keep += mine[e] != 0ull ? 1 : 0;
     }
     int nd;
-    int at = cand_block_scan(keep, wtot, &nd);                // (its first barrier: every read above is done)
+    int at = block_exclusive_scan<CAND_WAVES>(keep, wtot, nd);      // (its barrier: every read above is done)
+    __syncthreads();
 #pragma unroll
     for (int e = 0; e < 16; ++e)
         if (mine[e] != 0ull) skey[at++] = mine[e];
@@ -279,7 +234,8 @@ hipError_t launch_candidates(const float* q, const float* gallery, const unsigne
                              hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (M < 1 || M > CAND_MAX_M || K < 1 || K > 1024 || D <= 0) return hipErrorInvalidValue;
-    const RowTags tags = rt ? *rt : RowTags{nullptr, nullptr, nullptr};
+    RowTags tags;
+    if (!row_tags_arg(rt, tags)) return hipErrorInvalidValue;
     if (gallery || N <= 0) {      // (an empty gallery has no survivors: the form does not matter)
         if (D % 32) return hipErrorInvalidValue;
         if ((D / 32) % 2 == 0)

@@ -283,8 +283,7 @@ __device__ __forceinline__ void rank_count_epilogue(const GemmParams& p, f32x16 
     }
     for (int i = threadIdx.x; i < BM; i += blockDim.x) {
         const int qi = bm * BM + i;
-        const long ex = (rc.exclude && qi < p.M) ? (long)rc.exclude[qi] - rc.exclude_off : -1;
-        sex[i] = (ex >= 0 && ex < p.N) ? (int)ex : -1;
+        sex[i] = (int)excluded_local_row(qi < p.M ? rc.exclude : nullptr, qi, rc.exclude_off, p.N);      // (queries past M: no row)
     }
     const bool tagged = rc.rt.tags != nullptr;                // (kernel-uniform)
     unsigned* smask = reinterpret_cast<unsigned*>(sex + BM);  // [BM] masks, [BM] values, [BN] tags

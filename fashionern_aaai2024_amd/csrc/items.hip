@@ -15,31 +15,24 @@
 //   item_keys_kernel, item_count_kernel   a place is a count over the table: #{g : best[b][g] > best[b][t]}; no selection is needed.
 // Rows whose id is outside [0, G) belong to no item: they carry key 0 everywhere and never index the table.
 #include "kernels.h"
+#include "wave.h"
 
 #include <algorithm>
 #include <cstdint>
 
 namespace fern {
 
-typedef unsigned long long u64;
-typedef float f32x4i __attribute__((ext_vector_type(4)));
 typedef int i32x4i __attribute__((ext_vector_type(4)));
 
 constexpr int ITEM_NT = 256;                    // threads per workgroup: four waves, 256 rows per wave and step
 constexpr int ITEM_T = 8;                       // targets per pass of the count kernel over a query's table
 
-__device__ __forceinline__ u64 item_shfl_up64(u64 v, int d) {
-    const unsigned lo = __shfl_up((unsigned)v, d), hi = __shfl_up((unsigned)(v >> 32), d);
-    return ((u64)hi << 32) | lo;
-}
-
 // Rows i .. i + 3 (i % 4 == 0, i < ld) of query b: v = the stored scores, g = the item id (-1: outside [0, G) or past the gallery), k = the
-// ranking key, 0 unless the row can represent its item for this query: inside the gallery, not the excluded row, eligible under the row
-// filter (applied here again, not only through the -inf the score producers store), an id inside [0, G) and a score above -inf (rows
-// scoring -inf take no place in the row ranking either).
-__device__ __forceinline__ void item_quad(const ItemRows& r, const float* row, long i, long drop, unsigned qmask, unsigned qvalue, f32x4i& v,
-                                          u64 (&k)[4], int (&g)[4]) {
-    v = *reinterpret_cast<const f32x4i*>(row + i);
+// ranking key, 0 unless the row can represent its item for this query: the row-key rule (kernels.h: stored_row_key -- inside the
+// gallery, not the excluded row, a score above -inf) and, as conditions of this stage, an id inside [0, G) and a row that is eligible
+// under the row filter (applied here again, not only through the -inf the score producers store).
+__device__ __forceinline__ void item_quad(const ItemRows& r, const float* row, long i, long drop, QueryTags qt, f32x4& v, u64 (&k)[4], int (&g)[4]) {
+    v = *reinterpret_cast<const f32x4*>(row + i);
     int id[4];
     if (r.aligned && i + 3 < r.N) {
         const i32x4i t = *reinterpret_cast<const i32x4i*>(r.items + i);
@@ -53,17 +46,11 @@ __device__ __forceinline__ void item_quad(const ItemRows& r, const float* row, l
     for (int e = 0; e < 4; ++e) {
         const long n = i + e;
         const bool in = n < r.N && (unsigned)id[e] < (unsigned)r.G;
-        bool ok = in && n != drop && v[e] != -INFINITY;
-        if (r.rt.tags && ok) ok = row_eligible(r.rt.tags[n], qmask, qvalue);
+        u64 key = in ? stored_row_key(v[e], n, r.N, drop, r.idx_offset) : 0ull;
+        if (r.rt.tags && key != 0 && !row_eligible(r.rt.tags[n], qt.mask, qt.value)) key = 0ull;
         g[e] = in ? id[e] : -1;
-        k[e] = ok ? make_key(v[e], (unsigned)(n + r.idx_offset)) : 0ull;
+        k[e] = key;
     }
-}
-
-__device__ __forceinline__ long item_drop_row(const ItemRows& r, int b) {
-    if (!r.exclude) return -1;
-    const long er = (long)r.exclude[b] - r.idx_offset;
-    return er >= 0 && er < r.N ? er : -1;
 }
 
 // Workgroup (x, b): wave w takes the 256-row steps 4 x + w + j * 4 gridDim.x of query b's score row; lane l rows 4 l .. 4 l + 3 of a step.
@@ -71,15 +58,15 @@ __global__ __launch_bounds__(ITEM_NT) void item_best_kernel(const float* S, long
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* row = S + (long)b * ld;
     u64* bb = best + (long)b * r.G;
-    const long drop = item_drop_row(r, b);
-    const unsigned qmask = r.rt.tags ? r.rt.mask[b] : 0u, qvalue = r.rt.tags ? r.rt.value[b] : 0u;
+    const long drop = excluded_local_row(r.exclude, b, r.idx_offset, r.N);
+    const QueryTags qt = query_tags(r.rt, b);
     const long nq = (r.N + 3) & ~3L;
     for (long base = ((long)blockIdx.x * 4 + wave) * 256; base < nq; base += (long)gridDim.x * 1024) {      // (wave-uniform)
         const long i = base + lane * 4;
-        f32x4i v;
+        f32x4 v;
         u64 k[4] = {0ull, 0ull, 0ull, 0ull};
         int g[4] = {-1, -1, -1, -1};
-        if (i < nq) item_quad(r, row, i, drop, qmask, qvalue, v, k, g);
+        if (i < nq) item_quad(r, row, i, drop, qt, v, k, g);
         // runs inside the lane: the LAST row of a run ends up with the run's maximum
 #pragma unroll
         for (int e = 1; e < 4; ++e)
@@ -93,14 +80,14 @@ __global__ __launch_bounds__(ITEM_NT) void item_best_kernel(const float* S, long
         int sf = !(uni && joins_prev);
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
-            const u64 pv = item_shfl_up64(sv, d);
+            const u64 pv = shfl_up64(sv, d);
             const int pf = __shfl_up(sf, d);
             if (lane >= d) {
                 if (!sf && pv > sv) sv = pv;
                 sf |= pf;
             }
         }
-        const u64 cin = item_shfl_up64(sv, 1);      // what the run the lane continues has gathered so far
+        const u64 cin = shfl_up64(sv, 1);      // what the run the lane continues has gathered so far
         bool first = true;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -120,18 +107,18 @@ __global__ __launch_bounds__(ITEM_NT) void item_keep_best_kernel(float* S, long 
     const int b = blockIdx.y;
     float* row = S + (long)b * ld;
     const u64* bb = best + (long)b * r.G;
-    const long drop = item_drop_row(r, b);
-    const unsigned qmask = r.rt.tags ? r.rt.mask[b] : 0u, qvalue = r.rt.tags ? r.rt.value[b] : 0u;
+    const long drop = excluded_local_row(r.exclude, b, r.idx_offset, r.N);
+    const QueryTags qt = query_tags(r.rt, b);
     const long nq = (r.N + 3) & ~3L;
     for (long i = ((long)blockIdx.x * ITEM_NT + threadIdx.x) * 4; i < nq; i += (long)gridDim.x * ITEM_NT * 4) {
-        f32x4i v;
+        f32x4 v;
         u64 k[4];
         int g[4];
-        item_quad(r, row, i, drop, qmask, qvalue, v, k, g);
-        f32x4i o;
+        item_quad(r, row, i, drop, qt, v, k, g);
+        f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = (k[e] != 0 && k[e] == bb[g[e] >= 0 ? g[e] : 0]) ? v[e] : -INFINITY;
-        *reinterpret_cast<f32x4i*>(row + i) = o;
+        *reinterpret_cast<f32x4*>(row + i) = o;
     }
 }
 
@@ -171,9 +158,8 @@ __global__ __launch_bounds__(ITEM_NT) void item_count_kernel(const u64* best, in
     }
 #pragma unroll
     for (int t = 0; t < ITEM_T; ++t) {
-#pragma unroll
-        for (int x = 32; x >= 1; x >>= 1) cnt[t] += __shfl_xor(cnt[t], x);
-        if (lane == 0) part[wave][t] = cnt[t];
+        const int c = wave_sum_i32(cnt[t]);
+        if (lane == 0) part[wave][t] = c;
     }
     __syncthreads();
     if (tid < ITEM_T && t0 + tid < m) {
@@ -187,7 +173,8 @@ __global__ __launch_bounds__(ITEM_NT) void item_count_kernel(const u64* best, in
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------
 static bool item_rows_ok(const ItemRows& r, long ld) {
     if (r.N < 0 || r.G < 1 || (ld & 3) || ld < ((r.N + 3) & ~3L) || (r.N > 0 && !r.items)) return false;
-    return !r.rt.tags || (r.rt.mask && r.rt.value);
+    RowTags rt;
+    return row_tags_arg(&r.rt, rt);
 }
 static ItemRows item_rows_aligned(ItemRows r) {
     r.aligned = (reinterpret_cast<uintptr_t>(r.items) & 15) == 0;

@@ -82,8 +82,15 @@ struct RowTags {
     const unsigned* mask;                 // [B]
     const unsigned* value;                // [B]
 };
+struct QueryTags { unsigned mask, value; };      // one query's filter; {0, 0} passes every tag
+// A launcher's optional filter as the kernels take it: null or a filter without tags -> unfiltered.  false: tags without mask / value.
+inline bool row_tags_arg(const RowTags* in, RowTags& out) {
+    out = (in && in->tags) ? *in : RowTags{nullptr, nullptr, nullptr};
+    return !out.tags || (out.mask && out.value);
+}
 #ifdef __HIPCC__
 __device__ __forceinline__ bool row_eligible(unsigned tag, unsigned mask, unsigned value) { return (tag & mask) == value; }
+__device__ __forceinline__ QueryTags query_tags(const RowTags& rt, int b) { return rt.tags ? QueryTags{rt.mask[b], rt.value[b]} : QueryTags{0u, 0u}; }
 #endif
 // ---- exact target ranks: counting sweep (EPI_RANK_COUNT of the fp32 GEMM, rank.hip for the bf16 form) -----------------------------
 // A rank is a count: rows whose key (make_key: score descending, index ascending) is greater than the target's key.  One gallery pass
@@ -239,6 +246,23 @@ __device__ __forceinline__ float unorderable(unsigned k) {
 }
 __device__ __forceinline__ unsigned long long make_key(float score, unsigned idx) {
     return ((unsigned long long)orderable(score) << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+}
+// ---- the row-key rule: what position n of query b's stored score row S[b] stands for ------------------------------------------------
+// It carries make_key(S[b][n], n + idx_offset) if n < N, n is not the query's excluded row and the score is above -inf (the score
+// producers store -inf for a pair the row filter rules out), and 0 -- the key that is greater than nothing and takes no place --
+// otherwise.  A consumer with a further condition (an item id in range, the filter applied again, a ceiling key) adds it as a
+// conjunct of its own.
+// The query's excluded row as a LOCAL row of a gallery (shard) of N rows whose row 0 has the global index `off`; -1: none of them.
+__device__ __forceinline__ long excluded_local_row(const int* exclude, int b, long off, long N) {
+    if (!exclude) return -1;
+    const long er = (long)exclude[b] - off;
+    return (er >= 0 && er < N) ? er : -1;
+}
+// The rule's condition on its own, for a walk that forms the key unconditionally and gates every use of it (page.hip: a select per
+// key in the walk measured +3 %).  Everyone else takes stored_row_key.
+__device__ __forceinline__ bool row_takes_place(float score, long n, long N, long drop) { return n < N && n != drop && score != -__builtin_inff(); }
+__device__ __forceinline__ unsigned long long stored_row_key(float score, long n, long N, long drop, long idx_offset) {
+    return row_takes_place(score, n, N, drop) ? make_key(score, (unsigned)(n + idx_offset)) : 0ull;
 }
 // the score part of a bound as the float the fast reject compares with: !(acc < bound) lets every key >= thr_key through
 // (and NaNs, which rank first as keys); 0 = accept all -> NaN, ~0 = reject all -> +inf
@@ -546,9 +570,8 @@ hipError_t launch_rank_select(const float* S, long ld, int B, long N, const int*
                               long ostride, hipStream_t s);
 
 // ---- item-level ranking (items.hip): galleries whose rows belong to items -------------------------------------------------------------
-// Which rows of a stored score matrix S [B, ld] can represent an item, and under which key: row n of query b carries
-// make_key(S[b][n], n + idx_offset) if n < N, n is not the query's excluded row (exclude[b] - idx_offset), the row is eligible under rt,
-// items[n] is inside [0, G) and the score is above -inf; 0 otherwise.
+// Which rows of a stored score matrix S [B, ld] can represent an item, and under which key: the row-key rule above (stored_row_key,
+// exclude[b] in idx_offset's frame) with two more conditions -- the row is eligible under rt and items[n] is inside [0, G).
 struct ItemRows {
     const int* items;                     // [N] item id per gallery row
     int G;                                // number of items: ids outside [0, G) belong to no item

@@ -8,23 +8,21 @@
 //                        (select_pick; redundantly, no kernel in between: the pick is a pure function of integer sums, so every workgroup
 //                        gets the same state and the result does not depend on the order workgroups arrive in); workgroup x = 0 stores it.
 //                        Walk: blockIdx.y = query, the workgroups of a query stride over its row with 16-byte loads; per place the keys that
-//                        match the prefix are counted by digit value in an LDS histogram (one atomic per wave and leading digit value), the
+//                        match the prefix are counted by digit value in an LDS histogram (wave.h: wave_hist_add, one atomic per wave and leading digit value), the
 //                        workgroup's histograms are added into hist [m, SEL_T, 8, 256] with vector atomics.  One walk serves SEL_T places;
 //                        digit 7 is counted once for all of them (no prefix is fixed yet).
 //                        A place whose picked bucket held ONE key is `single`: the next walk reads that key off the row instead of
 //                        counting (one writer, so still deterministic), after which the place is `found`.  A query whose places are all
 //                        found (or hold no row) returns after the prologue: random scores end a walk or two early, tie floods need all 8;
 //   select_emit_kernel   level 0 -> out_keys (0 for a place without a row); zeroes the query's histograms for the next call.
-// Rows scoring -inf (ineligible pairs are stored so), positions past N and the query's excluded row have no key.  No capacity anywhere and
-// nothing read back.
+// Rows scoring -inf (ineligible pairs are stored so), positions past N and the query's excluded row have no key (kernels.h:
+// stored_row_key).  No capacity anywhere and nothing read back.
 #include "kernels.h"
+#include "wave.h"
 
 #include <algorithm>
 
 namespace fern {
-
-typedef unsigned long long u64;
-typedef float f32x4p __attribute__((ext_vector_type(4)));
 
 constexpr int SEL_NT = 256;               // threads per workgroup = digit values
 constexpr int SEL_ROWS = SEL_NT * 4;      // row positions of one workgroup step
@@ -94,7 +92,7 @@ __global__ __launch_bounds__(SEL_NT) void select_pass_kernel(const float* S, lon
     __shared__ unsigned h[SEL_T][256];
     __shared__ SelectState cur[SEL_T];
     __shared__ unsigned wtot[SEL_T][4];
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const int b = blockIdx.y, tid = threadIdx.x;
     const bool first = d == 7;                 // no digit fixed yet: every place matches the same keys, one histogram serves them all
     unsigned* hq = hist + (long)b * SEL_T * 8 * 256;
     u64* fq = found + (long)b * SEL_T;
@@ -128,22 +126,17 @@ __global__ __launch_bounds__(SEL_NT) void select_pass_kernel(const float* S, lon
 #pragma unroll
     for (int t = 0; t < SEL_T; ++t) h[t][tid] = 0;
     __syncthreads();
-    long drop = -1;
-    if (exclude) {
-        const long er = (long)exclude[b] - idx_offset;
-        if (er >= 0 && er < N) drop = er;
-    }
+    const long drop = excluded_local_row(exclude, b, idx_offset, N);
     const float* row = S + (long)b * ld;
     for (long base = (long)blockIdx.x * SEL_ROWS; base < N; base += (long)gridDim.x * SEL_ROWS) {
         const long i = base + (long)tid * 4;
-        const f32x4p v = *reinterpret_cast<const f32x4p*>(row + (i < N ? i : 0));      // ld % 4 == 0: the whole vector is inside the row
+        const f32x4 v = *reinterpret_cast<const f32x4*>(row + (i < N ? i : 0));      // ld % 4 == 0: the whole vector is inside the row
         u64 key[4];
         bool valid[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const long n = i + e;
-            valid[e] = n < N && n != drop && v[e] != -INFINITY;
-            key[e] = make_key(v[e], (unsigned)(n + idx_offset));
+            valid[e] = row_takes_place(v[e], i + e, N, drop);      // stored_row_key in two halves: the key is formed unconditionally,
+            key[e] = make_key(v[e], (unsigned)(i + e + idx_offset));      // `valid` gates every use of it (a select per key measured +3 %)
         }
 #pragma unroll
         for (int t = 0; t < SEL_T; ++t) {
@@ -163,16 +156,7 @@ __global__ __launch_bounds__(SEL_NT) void select_pass_kernel(const float* S, lon
             }
             if (__ballot(any) == 0) continue;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const u64 m = __ballot(match[e]);
-                if (m == 0) continue;
-                const int digit = (int)((key[e] >> (8 * d)) & 255);
-                const int leader = __ffsll((long long)m) - 1;
-                const int dl = __builtin_amdgcn_readlane(digit, leader);
-                const u64 same = __ballot(match[e] && digit == dl);      // (three such rounds per wave measured slower than one)
-                if (lane == leader) atomicAdd(&h[t][dl], (unsigned)__popcll(same));
-                if (match[e] && digit != dl) atomicAdd(&h[t][digit], 1u);
-            }
+            for (int e = 0; e < 4; ++e) wave_hist_add(match[e], (int)((key[e] >> (8 * d)) & 255), h[t]);
         }
     }
     __syncthreads();

@@ -12,48 +12,28 @@
 
 namespace fern {
 
-typedef float f32x4k __attribute__((ext_vector_type(4)));
-typedef unsigned long long u64;
-
-constexpr int RK_T = 16;                 // targets per wave
+constexpr int RK_T = CHAIN_T;            // targets per wave
 constexpr int RK_CH = 256;               // k per step: one 16-byte load per lane and row
-constexpr int RK_LD = RK_CH + 4;         // floats per tile row (+ 4: lane l's ds_read_b128 of row l starts 4 banks after lane l - 1's)
 
 __device__ __forceinline__ long rank_local_row(int target, long idx_offset, long N) {      // -1: not a row of this gallery
     const long r = (long)target - idx_offset;
     return (target >= 0 && r >= 0 && r < N) ? r : -1;
 }
 
-// One wave per (query, 16 targets).  A step brings 256 k of the 16 rows and of the query into LDS with one load per lane and row (all
-// 17 in flight behind one wait); lane t < 16 then continues target t's chain over those k in the sweep's order: inside every 8
-// consecutive k, 0 4 1 5 2 6 3 7 (rescore.h: chain_run).
+// One wave per (query, 16 targets): the per-lane chain stager (rescore.h: chain_rows_lane) at 256 k per step -- one load per lane and
+// row, all 17 in flight behind one wait; lane t < 16 ends up with target t's chain in the sweep's order.
 __global__ __launch_bounds__(64) void rank_keys_kernel(const float* q, const float* gallery, const int* targets, int B, long N, int D, int m,
                                                        long idx_offset, u64* keys) {
-    __shared__ __attribute__((aligned(16))) float tile[(RK_T + 1) * RK_LD];
+    __shared__ __attribute__((aligned(16))) float tile[chain_tile_floats<RK_CH>()];
     const int b = blockIdx.x, t0 = blockIdx.y * RK_T, lane = threadIdx.x;
     const int nt = min(RK_T, m - t0);
     const int* tg = targets + (long)b * m + t0;
-    const float* src[RK_T];
-#pragma unroll
-    for (int t = 0; t < RK_T; ++t) {
-        const long r = t < nt ? rank_local_row(tg[t], idx_offset, N) : -1;
-        src[t] = gallery + (r < 0 ? 0 : r) * D;              // (a target without a row reads row 0; its key is 0 below)
-    }
-    const float* qrow = q + (long)b * D;
-    float acc = 0.0f;
-    for (int k0 = 0; k0 < D; k0 += RK_CH) {
-        const int kc = k0 + lane * 4;
-        const bool in = kc < D;
-        f32x4k v[RK_T + 1];
-#pragma unroll
-        for (int t = 0; t < RK_T; ++t) v[t] = *reinterpret_cast<const f32x4k*>(src[t] + (in ? kc : 0));
-        v[RK_T] = *reinterpret_cast<const f32x4k*>(qrow + (in ? kc : 0));
-        __syncthreads();                                     // the previous step's chain reads are done
-#pragma unroll
-        for (int t = 0; t <= RK_T; ++t) *reinterpret_cast<f32x4k*>(tile + t * RK_LD + lane * 4) = v[t];
-        __syncthreads();
-        if (lane < RK_T) acc = chain_run(tile + lane * RK_LD, tile + RK_T * RK_LD, min(RK_CH, D - k0), acc);
-    }
+    const float acc = chain_rows_lane<RK_CH>(
+        [&](int t) {
+            const long r = t < nt ? rank_local_row(tg[t], idx_offset, N) : -1;
+            return gallery + (r < 0 ? 0 : r) * D;            // (a target without a row reads row 0; its key is 0 below)
+        },
+        q + (long)b * D, D, tile);
     if (lane < nt) {
         const int t = tg[lane];
         keys[(long)b * m + t0 + lane] = rank_local_row(t, idx_offset, N) >= 0 ? make_key(acc, (unsigned)t) : 0ull;
@@ -81,23 +61,24 @@ __global__ __launch_bounds__(256) void rank_keys_scores_kernel(const float* S, l
     keys[i] = rank_local_row(t, idx_offset, N) >= 0 ? make_key(S[b * ld + (b & 63) * m + j], (unsigned)t) : 0ull;
 }
 
-// Stored score rows S [B, ld]: blockIdx.y = query, the workgroups of a query stride over its row.  Per-lane counts, one xor tree per
+// Stored score rows S [B, ld]: blockIdx.y = query, the workgroups of a query stride over its row.  Per-lane counts, one wave sum per
 // target at the end, one add per wave and target into the partial set of the wave.
 __global__ __launch_bounds__(256) void rank_count_rows_kernel(const float* S, long ld, long N, RankCount rc, int B) {
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
     u64 tk[RANKC_T];
 #pragma unroll
     for (int t = 0; t < RANKC_T; ++t) tk[t] = t < rc.nt ? rc.keys[(long)b * rc.kstride + t] : ~0ull;
-    const long ex = rc.exclude ? (long)rc.exclude[b] - rc.exclude_off : -1;
+    const long ex = excluded_local_row(rc.exclude, b, rc.exclude_off, N);
     // a per-query row filter (kernels.h: RowTags): the sweep stored its ineligible rows as -inf; they carry key 0 here like the excluded row
     const bool tagged = rc.rt.tags != nullptr;
-    const unsigned fm = tagged ? rc.rt.mask[b] : 0u, fv = tagged ? rc.rt.value[b] : 0u;
+    const QueryTags qt = query_tags(rc.rt, b);
     int cnt[RANKC_T];
 #pragma unroll
     for (int t = 0; t < RANKC_T; ++t) cnt[t] = 0;
     const float* row = S + (long)b * ld;
     for (long n = (long)blockIdx.x * 256 + tid; n < N; n += (long)gridDim.x * 256) {
-        const bool ok = n != ex && (!tagged || row_eligible(rc.rt.tags[n], fm, fv));
+        // (not stored_row_key: a row that scores -inf of its own counts here as it does in the fp32 form's epilogue, which sees no stored row)
+        const bool ok = n != ex && (!tagged || row_eligible(rc.rt.tags[n], qt.mask, qt.value));
         const u64 key = ok ? make_key(row[n], (unsigned)(n + rc.idx_offset)) : 0ull;
 #pragma unroll
         for (int t = 0; t < RANKC_T; ++t) cnt[t] += key > tk[t] ? 1 : 0;
@@ -105,9 +86,7 @@ __global__ __launch_bounds__(256) void rank_count_rows_kernel(const float* S, lo
     int* part = rc.partial + (long)((blockIdx.x * 4 + (tid >> 6)) & (RANKC_P - 1)) * B * RANKC_T + (long)b * RANKC_T;
 #pragma unroll
     for (int t = 0; t < RANKC_T; ++t) {
-        int v = cnt[t];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+        const int v = wave_sum_i32(cnt[t]);
         if (lane == 0 && t < rc.nt && v != 0) atomicAdd(&part[t], v);
     }
 }

@@ -1,13 +1,12 @@
-// Device pieces shared by the ranking select kernels (topk.hip, topk_deep.hip): the certificate margin of the pre-filter, the ranking
-// key's way back to (score, global index), the ballot-and-append of a wave into its own segment, and the fp32 MFMA tile score.
-// (The exact chains of the survivors are rescore.h, which the two files include beside this one.)
+// Ranking policy shared by the select kernels (topk.hip, topk_deep.hip, candidates.hip): the certificate margin of the pre-filter, the
+// ranking key's way back to (score, global index), and the fp32 MFMA tile score.  (The wave and workgroup primitives are wave.h, the
+// row-key rule is kernels.h, the exact chains of the survivors are rescore.h.)
 #pragma once
 #include "kernels.h"
-#include "rescore.h"      // f32x4e (score_tile_f32's operand loads)
+#include "wave.h"
 
 namespace fern {
 
-typedef unsigned long long u64;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---- the certificate margin ------------------------------------------------------------------------------------------------------
@@ -72,19 +71,6 @@ __device__ __forceinline__ void write_key(u64 key, long idx_offset, float* os, i
     *oi = idx;
 }
 
-// ---- a wave appends its lanes' hits to its own segment ---------------------------------------------------------------------------
-// One compare + ballot per element, no atomics (one returning LDS atomic per hit was ~200 cycles each).  wn (wave-uniform) counts every
-// hit, stored or not: wn > cap afterwards means the segment overflowed.  store(pos) writes the lane's entry.
-template <class Store>
-__device__ __forceinline__ void wave_append(bool hit, int& wn, int cap, Store store) {
-    const u64 m = __ballot(hit);
-    if (m) {
-        const int pos = wn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-        if (hit && pos < cap) store(pos);
-        wn += __popcll(m);
-    }
-}
-
 // ---- one 32 x 32 fp32 score tile -------------------------------------------------------------------------------------------------
 // v_mfma_f32_32x32x2_f32 per 8-group g8 and e = 0..3, lane half lh feeding k = 8 g8 + 4 lh + e (gemm.hip's sweep): THE chain order
 // (oracle/chain.c) every bit-identity test pins.  qrow / grow: this lane's A row (query) and B row (gallery row, clamped by the caller).
@@ -94,8 +80,8 @@ __device__ __forceinline__ f32x16 score_tile_f32(const float* qrow, const float*
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
     for (int g8 = 0; g8 < D / 8; ++g8) {
-        const f32x4e af = *reinterpret_cast<const f32x4e*>(qrow + g8 * 8 + lh * 4);
-        const f32x4e bf = *reinterpret_cast<const f32x4e*>(grow + g8 * 8 + lh * 4);
+        const f32x4 af = *reinterpret_cast<const f32x4*>(qrow + g8 * 8 + lh * 4);
+        const f32x4 bf = *reinterpret_cast<const f32x4*>(grow + g8 * 8 + lh * 4);
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[e], bf[e], acc, 0, 0, 0);
     }

@@ -12,6 +12,8 @@
 // The score matrix is never materialised: the sweep (gemm.hip EPI_TOPK_FILTER / sweep_bf16.hip) appends only the scores that
 // reach a per-query bound to candidate lists; the two kernels here compute that bound from a row sample of the gallery
 // (topk_sample_bound_kernel) and select the exact top-K from the lists (topk_candidates_kernel).  kernels.h: TopkFilter.
+// The lane moves, the bitonic network, the wave reductions and the workgroup scan are wave.h; the excluded row and the query's
+// filter words come from kernels.h's row-key rule; margins and key writers are select.h, the exact chains rescore.h.
 #include "kernels.h"
 #include "rescore.h"
 #include "select.h"
@@ -19,60 +21,6 @@
 #include <algorithm>
 
 namespace fern {
-
-// Cross-lane moves without the LDS crossbar: a wave-uniform source lane is a v_readlane_b32 (SGPR lane select), the
-// shift-by-one of the sorted list is a DPP wave_shr:1 move.  ds_bpermute-based __shfl made every insertion a chain of
-// ~4 dependent ~120-cycle LDS round trips; these are plain VALU/SALU latencies.
-__device__ __forceinline__ u64 shfl64(u64 v, int src) {       // src must be wave-uniform
-    const int l = __builtin_amdgcn_readfirstlane(src);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 shfl64v(u64 v, int src) {      // per-lane source
-    const unsigned lo = __shfl((unsigned)v, src), hi = __shfl((unsigned)(v >> 32), src);
-    return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 shfl_up64(u64 v) {             // lane i <- lane i-1 (lane 0 keeps its value)
-    const int lo = __builtin_amdgcn_update_dpp((int)(unsigned)v, (int)(unsigned)v, 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(unsigned)(v >> 32), (int)(unsigned)(v >> 32), 0x138, 0xf, 0xf, false);
-    return ((u64)(unsigned)hi << 32) | (unsigned)lo;
-}
-
-__device__ __forceinline__ u64 shfl_xor64(u64 v, int m) {
-    const unsigned lo = __shfl_xor((unsigned)v, m), hi = __shfl_xor((unsigned)(v >> 32), m);
-    return ((u64)hi << 32) | lo;
-}
-// v holds a BITONIC sequence across the lanes: sort it descending (lane 0 = largest) with log2(64) compare-exchange stages.
-__device__ __forceinline__ u64 bitonic_finish_desc(u64 v, int lane) {
-#pragma unroll
-    for (int st = 32; st >= 1; st >>= 1) {
-        const u64 o = shfl_xor64(v, st);
-        const bool low = (lane & st) == 0;                         // the lower lane of a pair keeps the larger key
-        v = low ? (v > o ? v : o) : (v > o ? o : v);
-    }
-    return v;
-}
-// Top-64 of the union of two descending-sorted 64-entry lists: max(a[i], b[63-i]) is bitonic and holds exactly those.
-__device__ __forceinline__ u64 merge_sorted_desc(u64 a, u64 b_sorted, int lane) {
-    const u64 r = shfl64v(b_sorted, 63 - lane);
-    return bitonic_finish_desc(a > r ? a : r, lane);
-}
-// Full bitonic sort (descending) of one key per lane.
-__device__ __forceinline__ u64 sort64_desc(u64 v, int lane) {
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j >= 1; j >>= 1) {
-            const u64 o = shfl_xor64(v, j);
-            const bool desc = (lane & k) == 0 || k == 64;          // final pass: whole wave descending
-            const bool low = (lane & j) == 0;
-            const bool keep_max = desc ? low : !low;
-            v = keep_max ? (v > o ? v : o) : (v > o ? o : v);
-        }
-    }
-    return v;
-}
 
 // Offer one candidate per lane (key 0 = no candidate) to the wave's sorted list `best` (lane i = i-th best).  Few
 // survivors of the threshold test are inserted one by one (O(1) wave ops each); many (list still filling) are sorted and
@@ -82,7 +30,7 @@ __device__ __forceinline__ void wave_offer(u64& best, u64 cand, int K, int lane)
     u64 mask = __ballot(cand > thr);
     if (mask == 0) return;                                        // the common case after warm-up: nothing beats the K-th entry
     if (__popcll(mask) > 6) {
-        best = merge_sorted_desc(best, sort64_desc(cand, lane), lane);
+        best = merge_sorted_desc(best, sort_desc(cand, lane), lane);
         return;
     }
     while (mask) {
@@ -91,7 +39,7 @@ __device__ __forceinline__ void wave_offer(u64& best, u64 cand, int K, int lane)
         mask &= mask - 1;
         if (c > thr) {                                            // wave-uniform
             const int pos = __popcll(__ballot(best > c));        // entries that stay ahead of c
-            const u64 up = shfl_up64(best);
+            const u64 up = dpp_shr1_64(best);
             best = lane < pos ? best : (lane == pos ? c : up);
             thr = shfl64(best, K - 1);
         }
@@ -124,32 +72,7 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const float* scores, con
 // (PER compares per thread, a DPP wave sum, four partial sums through LDS, one barrier) and halves the range, which starts at
 // [min, max] of the keys -- so the step count is log2 of the keys' spread, not of the key width.  Keys are 64-bit = hi
 // (orderable score) << 32 | lo (~index): first the hi word, then lo among the keys that share the k-th hi (usually one key).
-__device__ __forceinline__ int wave_sum_i32(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);      // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);      // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);     // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false);     // row_mirror: every lane holds its 16-lane row's sum
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
-           __builtin_amdgcn_readlane(v, 48);
-}
-__device__ __forceinline__ int wave_inclusive_sum(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d);
-        v += lane >= d ? t : 0;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { const unsigned o = __shfl_xor(v, m); v = o < v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { const unsigned o = __shfl_xor(v, m); v = o > v ? o : v; }
-    return v;
-}
+// (The wave reductions, the scan and the bitonic network used from here on are wave.h.)
 // Workgroup helper (NW waves): `red` is 4 * NW words of LDS; `step` alternates the half used so that one barrier per
 // reduction is enough (a wave can only reach step + 2 after every wave has read step's sums).
 template <int NW>
@@ -187,20 +110,6 @@ struct WgReduce {
 // than k of the thousands.  Those are compacted into LDS (one prefix sum) and ranked by counting (every candidate reads the
 // compact list once, broadcast reads): the candidate with k - 1 keys above it is the answer.  Four barriers in all.  More than
 // CAPF candidates (tie-heavy galleries: thousands of keys share the k-th score) fall back to the bisection.
-__device__ __forceinline__ unsigned sort64_desc_u32(unsigned v, int lane) {
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j >= 1; j >>= 1) {
-            const unsigned o = __shfl_xor(v, j);
-            const bool desc = (lane & k) == 0 || k == 64;
-            const bool low = (lane & j) == 0;
-            const bool keep_max = desc ? low : !low;
-            v = keep_max ? (v > o ? v : o) : (v > o ? o : v);
-        }
-    }
-    return v;
-}
 constexpr int SELECT_CAPF = 512;
 // returns true and the k-th largest key in `out` when the fast path applies; every thread must call it (barriers inside);
 // ck: SELECT_CAPF keys of LDS, red: 4 * NW + 8 ints of LDS.  The caller has checked that at least k keys exist.
@@ -210,7 +119,7 @@ __device__ __forceinline__ bool select_kth_fast(const unsigned (&h)[PER], LoOf l
     unsigned tmax = 0;
 #pragma unroll
     for (int j = 0; j < PER; ++j) tmax = h[j] > tmax ? h[j] : tmax;
-    const unsigned sorted = sort64_desc_u32(tmax, lane);
+    const unsigned sorted = sort_desc(tmax, lane);
     const int tw = (k + NW - 1) / NW;                                   // <= 64: k <= 64
     const unsigned vw = (unsigned)__builtin_amdgcn_readlane((int)sorted, tw - 1);
     unsigned* ured = reinterpret_cast<unsigned*>(red);
@@ -223,15 +132,8 @@ __device__ __forceinline__ bool select_kth_fast(const unsigned (&h)[PER], LoOf l
     int cnt = 0;
 #pragma unroll
     for (int j = 0; j < PER; ++j) cnt += h[j] >= l0;
-    const int incl = wave_inclusive_sum(cnt, lane);
-    if (lane == 63) red[NW + wave] = incl;
-    __syncthreads();
-    int base = incl - cnt, total = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        base += w < wave ? red[NW + w] : 0;
-        total += red[NW + w];
-    }
+    int total;
+    int base = block_exclusive_scan<NW>(cnt, red + NW, total);
     if (total > SELECT_CAPF) return false;                               // uniform
 #pragma unroll
     for (int j = 0; j < PER; ++j)
@@ -409,15 +311,13 @@ struct CandGather {
     __device__ __forceinline__ bool overflow() const { return (over[0] | over[1] | over[2] | over[3]) != 0; }
     __device__ __forceinline__ int total() const { return wtotal[0] + wtotal[1] + wtotal[2] + wtotal[3]; }
     __device__ __forceinline__ void finish(u64* c_key, int total, u64 (&mine)[CAND_PER], unsigned (&h)[CAND_PER]) const {
-        const int tid = threadIdx.x, wave = tid >> 6;
-        int base = incl - cnt;
-        for (int w = 0; w < wave; ++w) base += wtotal[w];
+        const int tid = threadIdx.x;
+        int sum;
+        const int base = block_scan_base<4>(incl, cnt, wtotal, sum);      // (begin published the wave totals; the caller's barrier is between)
 #pragma unroll
         for (int u = 0; u < SPEC; ++u)
             if (u < cnt) c_key[base + u] = first[u];
-        int maxc = cnt;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { const int o = __shfl_xor(maxc, m); maxc = o > maxc ? o : maxc; }
+        const int maxc = (int)wave_max_u32((unsigned)cnt);                // cnt >= 0
 #pragma unroll 1
         for (int e0 = SPEC; e0 < maxc; e0 += 8) {
             u64 key[8];
@@ -472,7 +372,7 @@ __global__ __launch_bounds__(256) void topk_candidates_kernel(TopkFilter f, int 
         __syncthreads();
         if (wave != 0) return;
         const int ns = nsel < 64 ? nsel : 64;
-        best = sort64_desc(lane < ns ? lists[0][lane] : 0, lane);
+        best = sort_desc(lane < ns ? lists[0][lane] : 0, lane);
     } else {
         // streaming path (lists near full: > CAND_MAX candidates): the sorted wave lists of wave_offer
         const u64* cand = f.cand + (long)b * RANK_SLOTS * f.cap;
@@ -595,28 +495,15 @@ __global__ __launch_bounds__(256) void topk_rescore_kernel(TopkFilter f, const f
 // paid for a case that almost never happens.  One CU streams the whole fp32 gallery (~60 GB/s): the launcher allows it up to 128 MB.
 // tags != null: rows that are ineligible for this query ((tags[n] & mask) != value) are skipped like the excluded row.
 __device__ __forceinline__ void exact_topk_inline(const float* qrow, const float* gallery, long N, int D, long drop, int K, long idx_offset,
-                                                  float* os, int* oi, u64 (*wl)[64], const unsigned* tags = nullptr, unsigned mask = 0u,
-                                                  unsigned value = 0u) {
+                                                  float* os, int* oi, u64 (*wl)[64], const unsigned* tags = nullptr, QueryTags qt = {0u, 0u}) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     u64 best = 0;
 #pragma unroll 1
     for (long n0 = (long)wave * 64; n0 < N; n0 += 256) {
         const long n = n0 + lane;
         u64 key = 0;
-        if (n < N && n != drop && (!tags || row_eligible(tags[n], mask, value))) {
-            const float* g = gallery + n * D;
-            float acc = 0.0f;
-            for (int k8 = 0; k8 < D; k8 += 8) {
-                const f32x4e g0 = *reinterpret_cast<const f32x4e*>(g + k8), g1 = *reinterpret_cast<const f32x4e*>(g + k8 + 4);
-                const f32x4e q0 = *reinterpret_cast<const f32x4e*>(qrow + k8), q1 = *reinterpret_cast<const f32x4e*>(qrow + k8 + 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    acc = __builtin_fmaf(q0[e], g0[e], acc);
-                    acc = __builtin_fmaf(q1[e], g1[e], acc);
-                }
-            }
-            key = make_key(acc, (unsigned)n);
-        }
+        if (n < N && n != drop && (!tags || row_eligible(tags[n], qt.mask, qt.value)))
+            key = make_key(chain_run(gallery + n * D, qrow, D, 0.0f), (unsigned)n);
         wave_offer(best, key, K, lane);
     }
     wl[wave][lane] = best;
@@ -658,14 +545,10 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     const float* row = approx + (long)b * ld;
     if (tid == 0) { nsurv = 0; kth_hi = 0; state[b] = 0; done[b] = 0; }
     for (int i = tid; i < D; i += 256) qrow[i] = q[(long)b * D + i];
-    long drop = -1;
-    if (exclude) {
-        const long er = (long)exclude[b] - exclude_off;
-        if (er >= 0 && er < N) drop = er;
-    }
+    const long drop = excluded_local_row(exclude, b, exclude_off, N);
     const long n4 = N & ~3L;
     constexpr int NBR = NB > 0 ? NB : 1;
-    f32x4e v[NBR][DENSE_UB];
+    f32x4 v[NBR][DENSE_UB];
     // This kernel runs ONE wave per SIMD (64 workgroups on 64 CUs): every VALU instruction of a phase is 4 cycles of its latency, so
     // the walks over the row are written for instruction count -- float maxima (v_max3_f32) instead of orderable keys, the excluded
     // row handled by a separate (rare) path, keys built only for the ~100 collected rows.
@@ -674,11 +557,11 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     // row was written by the sweep from other XCDs: it comes from HBM / the Infinity Cache at 1-2 us a round trip.
     // Loaded values are SANITISED once (positions past the row and the excluded row become -inf), so that the two walks are one
     // v_max3 / one v_cmp per element.
-    auto load_batch = [&](long base, f32x4e (&dst)[DENSE_UB]) {
+    auto load_batch = [&](long base, f32x4 (&dst)[DENSE_UB]) {
 #pragma unroll
         for (int u = 0; u < DENSE_UB; ++u) {
             const long i = base + u * 1024L + tid * 4;
-            dst[u] = *reinterpret_cast<const f32x4e*>(row + (i < n4 ? i : 0));
+            dst[u] = *reinterpret_cast<const f32x4*>(row + (i < n4 ? i : 0));
         }
 #pragma unroll
         for (int u = 0; u < DENSE_UB; ++u) {
@@ -694,7 +577,7 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     // pass 1: every thread's maximum score.  fmax drops NaNs; the running SUM of the scores is NaN whenever one of them is (or when
     // +inf meets -inf: a false alarm that only costs speed) -- a NaN anywhere makes the wave collect everything.
     float fmax_t = -INFINITY, nsum = 0.f;
-    auto max_batch = [&](const f32x4e (&src)[DENSE_UB]) {
+    auto max_batch = [&](const f32x4 (&src)[DENSE_UB]) {
 #pragma unroll
         for (int u = 0; u < DENSE_UB; ++u) {
             fmax_t = fmaxf(fmaxf(fmax_t, src[u][0]), fmaxf(src[u][1], fmaxf(src[u][2], src[u][3])));
@@ -717,7 +600,7 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     const bool nan_t = nsum != nsum;
     unsigned tmax = fmax_t == -INFINITY ? 0u : orderable(fmax_t);      // 0 = "no row": a thread without rows, or only -inf scores
     const float margin = margin_finish<4>(qn, D, mg.meta, fred);
-    const unsigned sorted = sort64_desc_u32(tmax, lane);
+    const unsigned sorted = sort_desc(tmax, lane);
     const int tw = (K + 3) / 4;
     const unsigned vw = (unsigned)__builtin_amdgcn_readlane((int)sorted, tw - 1);
     if (lane == 0) wmax[wave] = __any(nan_t) ? 0u : vw;                 // a NaN score anywhere in the wave's share: collect everything
@@ -742,7 +625,7 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     auto collect_one = [&](float val, long n, bool hit) {
         wave_append(hit, wn, DENSE_SEG, [&](int pos) { seg[pos] = ((u64)__float_as_uint(val) << 32) | (unsigned)n; });
     };
-    auto collect_batch = [&](long base, const f32x4e (&src)[DENSE_UB]) {
+    auto collect_batch = [&](long base, const f32x4 (&src)[DENSE_UB]) {
 #pragma unroll
         for (int u = 0; u < DENSE_UB; ++u) {
             const long i = base + u * 1024L + tid * 4;
@@ -829,7 +712,7 @@ __global__ __launch_bounds__(256) void topk_dense_rescore_kernel(const float* ap
     } while (0);
     if (inline_exact) {      // small galleries: ranked exactly right here
         exact_topk_inline(qrow, gallery, N, D, drop, K, idx_offset, out_scores + (long)b * K, out_idx + (long)b * K, wlists, rt.tags,
-                          rt.tags ? rt.mask[b] : 0u, rt.tags ? rt.value[b] : 0u);
+                          query_tags(rt, b));
     } else if (tid == 0) {   // flagged for the gated exact pass
         state[b] = 1;
         flags[0] = 1;
@@ -878,11 +761,7 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
     const long ntiles = (N + 31) >> 5;
     if (tid == 0) { nsurv = 0; kth_hi = 0; state[b] = 0; done[b] = 0; }
     for (int i = tid; i < D; i += 256) qrow[i] = q[(long)b * D + i];
-    long drop = -1;
-    if (exclude) {
-        const long er = (long)exclude[b] - exclude_off;
-        if (er >= 0 && er < N) drop = er;
-    }
+    const long drop = excluded_local_row(exclude, b, exclude_off, N);
     // tile maxima: TILES_TB unconditional loads on clamped addresses (topk_dense_rescore_kernel's note), masked afterwards
     float tv[TILES_TB];
     auto load_tiles = [&](long base) {
@@ -903,7 +782,7 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
     }
     const unsigned tmx = fmax_t == -INFINITY ? 0u : orderable(fmax_t);      // 0 = "no tile"
     const float margin = margin_finish<4>(qn, D, mg.meta, fred);
-    const unsigned sorted = sort64_desc_u32(tmx, lane);
+    const unsigned sorted = sort_desc(tmx, lane);
     const int tw = (K + (drop >= 0 ? 1 : 0) + 3) / 4;
     const unsigned vw = (unsigned)__builtin_amdgcn_readlane((int)sorted, tw - 1);
     if (lane == 0) wmax[wave] = vw;
@@ -937,7 +816,7 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
     int wn = 0;
     const int items = nt * 8;
     for (int e0 = 0; e0 < items; e0 += 1024) {
-        f32x4e val[4];
+        f32x4 val[4];
         long nn[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -945,7 +824,7 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
             const int w = (slot >= p1) + (slot >= p2) + (slot >= p3);
             const int tile = tlist[w][slot - (w == 0 ? 0 : w == 1 ? p1 : w == 2 ? p2 : p3)];
             nn[u] = (long)tile * 32 + (ec & 7) * 4;
-            val[u] = *reinterpret_cast<const f32x4e*>(row + nn[u]);      // ld covers whole tiles (launcher)
+            val[u] = *reinterpret_cast<const f32x4*>(row + nn[u]);      // ld covers whole tiles (launcher)
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -1013,7 +892,7 @@ __global__ __launch_bounds__(256) void topk_tiles_rescore_kernel(const float* ap
     } while (0);
     if (inline_exact) {
         exact_topk_inline(qrow, gallery, N, D, drop, K, idx_offset, out_scores + (long)b * K, out_idx + (long)b * K, wlists, rt.tags,
-                          rt.tags ? rt.mask[b] : 0u, rt.tags ? rt.value[b] : 0u);
+                          query_tags(rt, b));
     } else if (tid == 0) {
         state[b] = 1;
         flags[0] = 1;
@@ -1057,12 +936,8 @@ __global__ __launch_bounds__(256) void rank_exact_kernel(const float* q, const v
         fl[u] = b < B && state[b] != 0;
         cnt += fl[u];
     }
-    const int incl = wave_inclusive_sum(cnt, lane);
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    int base = incl - cnt;
-    for (int w = 0; w < wave; ++w) base += wtot[w];
-    const int nflag = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    int nflag;
+    int base = block_exclusive_scan<4>(cnt, wtot, nflag);
 #pragma unroll
     for (int u = 0; u < 4; ++u)
         if (fl[u]) flagged[base++] = tid * 4 + u;
@@ -1073,8 +948,9 @@ __global__ __launch_bounds__(256) void rank_exact_kernel(const float* q, const v
             const int b = flagged[c0 + (tid < nq ? tid : 0)];
             thr_s[tid] = tid < nq ? thr_key[b] : ~0ull;
             ex_s[tid] = (tid < nq && exclude) ? (long)exclude[b] - exclude_off : -1;
-            mk_s[tid] = (tid < nq && rt.tags) ? rt.mask[b] : 0u;
-            vl_s[tid] = (tid < nq && rt.tags) ? rt.value[b] : 0u;
+            const QueryTags qt = tid < nq ? query_tags(rt, b) : QueryTags{0u, 0u};
+            mk_s[tid] = qt.mask;
+            vl_s[tid] = qt.value;
         }
         for (int i = tid; i < 4 * EXACT_QB * 64; i += 256) (&lists[0][0][0])[i] = 0;
         __syncthreads();
@@ -1092,8 +968,8 @@ __global__ __launch_bounds__(256) void rank_exact_kernel(const float* q, const v
                 for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
                 const unsigned short* grow = reinterpret_cast<const unsigned short*>(gallery) + nc * D;
                 for (int ks = 0; ks < D / 16; ++ks) {
-                    const f32x4e a0 = *reinterpret_cast<const f32x4e*>(qrow + ks * 16 + lh * 8);
-                    const f32x4e a1 = *reinterpret_cast<const f32x4e*>(qrow + ks * 16 + lh * 8 + 4);
+                    const f32x4 a0 = *reinterpret_cast<const f32x4*>(qrow + ks * 16 + lh * 8);
+                    const f32x4 a1 = *reinterpret_cast<const f32x4*>(qrow + ks * 16 + lh * 8 + 4);
                     bf16x8e af;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { af[e] = (short)f32_to_bf16_bits(a0[e]); af[4 + e] = (short)f32_to_bf16_bits(a1[e]); }
@@ -1194,8 +1070,8 @@ hipError_t launch_topk_dense_rescore(const float* approx, long ld, long N, const
                                      int* out_idx, unsigned long long* thr_key, int* flags, int* state, int* done, hipStream_t s, int inline_exact,
                                      const float* tmax, long ldt, const RowTags* rtp) {
     if (B <= 0) return hipSuccess;
-    const RowTags rt = (rtp && rtp->tags) ? *rtp : RowTags{nullptr, nullptr, nullptr};
-    if (rt.tags && (!rt.mask || !rt.value)) return hipErrorInvalidValue;
+    RowTags rt;
+    if (!row_tags_arg(rtp, rt)) return hipErrorInvalidValue;
     if (K < 1 || K > 64 || D < 64 || D % 64 || D > 1024 || N < 1 || (ld & 3) || !meta) return hipErrorInvalidValue;
     const BoundMargin mg{q, D, meta, nullptr};
     if (tmax && N >= TILES_MIN_N) {                  // selection on the sweep's tile maxima
@@ -1225,8 +1101,8 @@ hipError_t launch_rank_exact(const float* q, const void* gallery, int gallery_bf
                              unsigned long long* partial, int groups, int* done, float* out_scores, int* out_idx, const int* gate,
                              hipStream_t s, const RowTags* rtp) {
     if (B <= 0 || N <= 0) return hipSuccess;
-    const RowTags rt = (rtp && rtp->tags) ? *rtp : RowTags{nullptr, nullptr, nullptr};
-    if (rt.tags && (!rt.mask || !rt.value)) return hipErrorInvalidValue;
+    RowTags rt;
+    if (!row_tags_arg(rtp, rt)) return hipErrorInvalidValue;
     if (K < 1 || K > 64 || groups < 1 || B > 1024 || D % (gallery_bf16 ? 16 : 8)) return hipErrorInvalidValue;
     if (gallery_bf16)
         FERN_LAUNCH(rank_exact_kernel<true>, dim3(groups), dim3(256), 0, s, q, gallery, B, N, D, K, state, thr_key, exclude, exclude_off,

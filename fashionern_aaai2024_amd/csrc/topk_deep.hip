@@ -26,11 +26,6 @@
 
 namespace fern {
 
-__device__ __forceinline__ u64 deep_shfl_xor64(u64 v, int m) {
-    const unsigned lo = __shfl_xor((unsigned)v, m), hi = __shfl_xor((unsigned)(v >> 32), m);
-    return ((u64)hi << 32) | lo;
-}
-
 // ---- block bitonic sort (descending) of NT * P keys: thread t holds elements t * P .. t * P + P - 1 in registers -------------------
 // Stages with J < P are register swaps, J < 64 P lane shuffles, the rest (a handful) go through `buf` (NT * P keys of LDS).
 template <int NT, int P, int K, int J>
@@ -50,7 +45,7 @@ __device__ __forceinline__ void bsort_stage(u64 (&v)[P], u64* buf) {
     } else if constexpr (J < 64 * P) {
 #pragma unroll
         for (int r = 0; r < P; ++r) {
-            const u64 o = deep_shfl_xor64(v[r], J / P);
+            const u64 o = shfl_xor64(v[r], J / P);
             const int e = tid * P + r;
             const bool keep_max = ((e & K) == 0) == ((e & J) == 0);
             v[r] = keep_max ? (v[r] > o ? v[r] : o) : (v[r] > o ? o : v[r]);
@@ -180,20 +175,16 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
     float* os = out_scores + (long)b * K;
     int* oi = out_idx + (long)b * K;
     if (tid == 0) { ncoll = 0; nsurv = 0; state[b] = 0; }
-    long drop = -1;
-    if (exclude) {
-        const long er = (long)exclude[b] - idx_offset;
-        if (er >= 0 && er < N) drop = er;
-    }
+    const long drop = excluded_local_row(exclude, b, idx_offset, N);
     const u64 ck = CEIL ? ceil[b] : ~0ull;
     const long n4 = N & ~3L;
     constexpr long STEP = (long)DEEP_NT * 4 * DEEP_UB;
     // one batch: DEEP_UB unconditional loads on clamped addresses, then masked (positions past the row and the excluded row -> -inf)
-    auto load_batch = [&](long base, f32x4e (&v)[DEEP_UB]) {
+    auto load_batch = [&](long base, f32x4 (&v)[DEEP_UB]) {
 #pragma unroll
         for (int u = 0; u < DEEP_UB; ++u) {
             const long i = base + ((long)u * DEEP_NT + tid) * 4;
-            v[u] = *reinterpret_cast<const f32x4e*>(row + (i < n4 ? i : 0));
+            v[u] = *reinterpret_cast<const f32x4*>(row + (i < n4 ? i : 0));
         }
 #pragma unroll
         for (int u = 0; u < DEEP_UB; ++u) {
@@ -213,7 +204,7 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
 #pragma unroll
     for (int g = 0; g < 16; ++g) gmax[g] = -INFINITY;
     for (long base = 0; base < n4; base += STEP) {
-        f32x4e v[DEEP_UB];
+        f32x4 v[DEEP_UB];
         load_batch(base, v);
 #pragma unroll
         for (int u = 0; u < DEEP_UB; ++u) {
@@ -243,17 +234,10 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
     const float cut0 = lkey != 0 ? unorderable(lkey) - margin : -INFINITY;
     // pass 2: rows with score >= cut0 (never -inf: padding / excluded) -> ranking keys in ckey (one LDS atomic per wave and hit ballot)
     auto collect = [&](float val, long n, bool hit) {
-        const u64 m = __ballot(hit);
-        if (m) {
-            int p0 = 0;
-            if (lane == 0) p0 = atomicAdd(&ncoll, __popcll(m));
-            p0 = __builtin_amdgcn_readlane(p0, 0);
-            const int pos = p0 + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-            if (hit && pos < cap) ckey[pos] = make_key(val, (unsigned)n);
-        }
+        wave_append_shared(hit, &ncoll, cap, [&](int pos) { ckey[pos] = make_key(val, (unsigned)n); });
     };
     for (long base = 0; base < n4; base += STEP) {
-        f32x4e v[DEEP_UB];
+        f32x4 v[DEEP_UB];
         load_batch(base, v);
 #pragma unroll
         for (int u = 0; u < DEEP_UB; ++u) {
@@ -284,8 +268,7 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
         cnt += keep;
         if (keep) surv[r] = 0xFFFFFFFFu - (unsigned)ckey[r];
     }
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) cnt += __shfl_xor(cnt, x);
+    cnt = wave_sum_i32(cnt);
     if (lane == 0) atomicAdd(&nsurv, cnt);
     for (int i = tid; i < mg.D; i += DEEP_NT) qrow[i] = mg.q[(long)b * mg.D + i];
     __syncthreads();
@@ -300,23 +283,20 @@ __global__ __launch_bounds__(DEEP_NT) void deep_select_kernel(const float* S, lo
 
 // ---- fallback: radix select on the stored (exact / bf16) row, no capacity ---------------------------------------------------------------
 // Gated on flags[0] and state[b].  T = the K-th largest key of the row, one 8-bit digit per pass over the row (LDS histogram, one atomic per
-// wave and digit value); the K keys >= T are collected and sorted.  Rows scoring -inf (and the excluded row) take no place, as in the
-// selection kernel.
+// wave and digit value: wave_hist_add); the K keys >= T are collected and sorted.  A row's key is the row-key rule's (kernels.h:
+// stored_row_key -- rows scoring -inf and the excluded row take no place, as in the selection kernel) on the LOCAL index, with the
+// ceiling as a further condition.
 __global__ __launch_bounds__(DEEP_NT) void deep_fallback_kernel(const float* S, long ld, long N, int K, const int* exclude, long idx_offset,
                                                                 float* out_scores, int* out_idx, const int* flags, const int* state, const u64* ceil) {
     if (flags[0] == 0 || state[blockIdx.x] == 0) return;
     __shared__ __attribute__((aligned(16))) u64 ckey[4 * DEEP_NT];      // >= 1024: the K keys
     __shared__ int hist[256];
     __shared__ int need_s, sel_s, ncoll;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int b = blockIdx.x, tid = threadIdx.x;
     const float* row = S + (long)b * ld;
     float* os = out_scores + (long)b * K;
     int* oi = out_idx + (long)b * K;
-    long drop = -1;
-    if (exclude) {
-        const long er = (long)exclude[b] - idx_offset;
-        if (er >= 0 && er < N) drop = er;
-    }
+    const long drop = excluded_local_row(exclude, b, idx_offset, N);
     const u64 ck = ceil ? ceil[b] : ~0ull;          // a key with the global index: compared with the row's global key, never rebased
     auto under = [&](float v, long n) { return !ceil || make_key(v, (unsigned)(n + idx_offset)) <= ck; };
     u64 prefix = 0, mask = 0;
@@ -327,17 +307,9 @@ __global__ __launch_bounds__(DEEP_NT) void deep_fallback_kernel(const float* S, 
         for (long n0 = 0; n0 < N; n0 += DEEP_NT) {
             const long n = n0 + tid;
             const float v = n < N ? row[n] : -INFINITY;
-            const u64 key = make_key(v, (unsigned)n);
-            const bool match = n < N && n != drop && v != -INFINITY && under(v, n) && (key & mask) == prefix;
-            const int digit = (int)((key >> (8 * d)) & 255);
-            const u64 m = __ballot(match);
-            if (m) {
-                const int leader = __ffsll((long long)m) - 1;
-                const int dl = __builtin_amdgcn_readlane(digit, leader);
-                const u64 same = __ballot(match && digit == dl);
-                if (lane == leader) atomicAdd(&hist[dl], __popcll(same));
-                if (match && digit != dl) atomicAdd(&hist[digit], 1);
-            }
+            const u64 key = stored_row_key(v, n, N, drop, 0);      // the select keys: on the LOCAL index
+            const bool match = key != 0 && under(v, n) && (key & mask) == prefix;
+            wave_hist_add(match, (int)((key >> (8 * d)) & 255), hist);
         }
         __syncthreads();
         if (tid == 0) {
@@ -372,17 +344,9 @@ __global__ __launch_bounds__(DEEP_NT) void deep_fallback_kernel(const float* S, 
         for (long n0 = 0; n0 < N; n0 += DEEP_NT) {
             const long n = n0 + tid;
             const float v = n < N ? row[n] : -INFINITY;
-            const u64 key = make_key(v, (unsigned)n);
-            const bool hit = n < N && n != drop && v != -INFINITY && under(v, n) && key >= prefix;
-            const u64 m = __ballot(hit);
-            if (m) {
-                const int leader = __ffsll((long long)m) - 1;
-                int p0 = 0;
-                if (lane == leader) p0 = atomicAdd(&ncoll, __popcll(m));
-                p0 = __builtin_amdgcn_readlane(p0, leader);
-                const int pos = p0 + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
-                if (hit && pos < 4 * DEEP_NT) ckey[pos] = make_key(v, (unsigned)n);
-            }
+            const u64 key = stored_row_key(v, n, N, drop, 0);
+            const bool hit = key != 0 && under(v, n) && key >= prefix;
+            wave_append_shared(hit, &ncoll, 4 * DEEP_NT, [&](int pos) { ckey[pos] = key; });
         }
         __syncthreads();
     }
@@ -420,8 +384,8 @@ hipError_t launch_deep_exact_scores(const float* q, const float* gallery, int B,
     const long ntiles = (N + 31) / 32;
     const int gy = (B + 31) / 32;
     const int gx = (int)std::min<long>((ntiles + 3) / 4, std::max(1, 2048 / gy));
-    const RowTags tags = (rt && rt->tags) ? *rt : RowTags{nullptr, nullptr, nullptr};
-    if (tags.tags && (!tags.mask || !tags.value)) return hipErrorInvalidValue;
+    RowTags tags;
+    if (!row_tags_arg(rt, tags)) return hipErrorInvalidValue;
     if (gated)
         FERN_LAUNCH(deep_exact_scores_kernel<true>, dim3(gx, gy), dim3(256), 0, s, q, gallery, B, N, D, S, ld, flags, state, tags);
     else

@@ -1,8 +1,9 @@
-"""Raw results of the ranking select kernels (csrc/topk.hip, csrc/topk_deep.hip, csrc/select.h) on seeded inputs, for comparing two
-BUILDS of the library bit for bit: a change to those files that is meant to move no bit is run once on each build and every array
-compared.  A script, not a collected test.  Usage: python tests/_rank_select_dump.py out.npz
+"""Raw results of the ranking kernels (csrc/topk.hip, topk_deep.hip, rank.hip, items.hip, page.hip, candidates.hip and the headers they
+share) on seeded inputs, for comparing two BUILDS of the library bit for bit: a change to those files that is meant to move no bit is
+run once on each build and every array compared.  A script, not a collected test.  Usage: python tests/_rank_select_dump.py out.npz
 
-Every case saves `<name>.s` (the scores' bits as uint32) and `<name>.i` (the indices).  The results are deterministic: keys are
+Every case saves `<name>.s` (the scores' bits as uint32) and `<name>.i` (the indices), or `<name>.r` (ranks, keys) for the calls that
+return one integer array.  The results are deterministic: keys are
 distinct and places come from counting or sorting, so a difference between two builds is a bug, never noise.
 
 With FERN_RANK_CAP set in the environment (the candidate lists' test hook, read once per process: tiny lists overflow) only the cases
@@ -33,6 +34,23 @@ Which case reaches which path (api.hip: rank_plan, rank_strategy_for, rank_dense
               4096 collected keys: flagged -> gated deep_exact_scores_kernel<true> + deep_fallback_kernel); a cursor page and an offset
               page (deep_select_kernel<true> / page.hip)
   merge_*     topk_merge_kernel (K <= 64) and topk_merge_deep_kernel
+  rankof_*    rank_of (`.r` = the ranks): fp32 rows -> rank_keys_kernel (m = 1: one lane of a wave, 16: a full group, 17: a group of one;
+              D = 288: two 256-k steps, the second partial -- the engine takes D % 32 == 0, so 264 is not a shape) + the EPI_RANK_COUNT
+              epilogue + rank_finalize_kernel; bf16 rows (D = 64 and 320) -> rank_gather_bf16_kernel, the sweep, rank_keys_scores_kernel,
+              rank_count_rows_kernel.  Each with the query's excluded row among the targets, a target outside the gallery, a shard
+              (idx_offset = 1000) and a RowFilter (the filtered count)
+  items_*     sim_topk_items (`.x` = the item ids) and item_rank_of on fp32 and bf16 rows: item_best_kernel, item_keep_best_kernel,
+              item_gather_kernel, item_keys_kernel, item_count_kernel (nine targets: two groups).  N = 1030 in runs of 1, 3, 5 and 300
+              rows (inside a lane, across lanes, across the 256-row wave step), two ids outside [0, G), every query's best row excluded,
+              a filter on a shard; N = 1027 with the ids one element off 16-byte alignment (item_quad's scalar id loads)
+  select_*    rank_select, eight places (place 0, a negative one, the last row, one past the rows): select_init / pass / emit.  Random
+              scores (walks end early through `single`), all rows equal (all eight digits), one row; the excluded row on a shard
+  cand_*      sim_topk_candidates with places (`.x`): candidates_kernel<ring> (D = 64), <lane> (D = 96: chain_rows_lane), <bf16>; M = 1,
+              33, 600 (every row named twice, a negative entry, one outside the shard, the excluded row), K = 5 and 700, a filter on a shard
+
+With FERN_RANK_DEEP_CAP set (the deep stage's test hook, read once per process: a collection of a few keys overflows) only the `dcap_*`
+cases run: all-equal and random score rows through deep_fallback_kernel (exact, pre-filtered -> the gated deep_exact_scores_kernel<true>),
+and sim_topk_from on them (deep_select_kernel<true> -> deep_fallback_kernel with a ceiling), plain and with an excluded row on a shard.
 """
 import os
 import sys
@@ -55,19 +73,44 @@ def _ties(n, d, nt, seed):
     return q, gal
 
 
-def compute(eng, lists_only=False):
+def _item_ids(n):
+    """[n] item ids in runs of 1, 3, 5 and 300 rows, and the number of items."""
+    lens = torch.tensor([1, 3, 5, 300]).repeat(n // 309 + 1)
+    ids = torch.repeat_interleave(torch.arange(lens.numel()), lens)[:n].to(torch.int32)
+    return ids, int(ids.max()) + 1
+
+
+def compute(eng, lists_only=False, deep_cap=False):
     """{name: int array}; the same seeded inputs in every process."""
-    from fashionern_aaai2024_amd.engine import RowFilter, next_from
+    from fashionern_aaai2024_amd.engine import ItemMap, RowFilter, next_from
     out = {}
-    pre = "cap_" if lists_only else ""
+    pre = "cap_" if lists_only else "dcap_" if deep_cap else ""
 
     def put(name, res):
-        s, i = res
+        s, i = res[0], res[1]
         out[f"{pre}{name}.s"] = s.contiguous().view(torch.int32).cpu().numpy().view(np.uint32)
         out[f"{pre}{name}.i"] = i.cpu().numpy()
+        if len(res) > 2:            # item ids / places
+            out[f"{pre}{name}.x"] = res[2].cpu().numpy()
+
+    def puti(name, t):
+        out[f"{pre}{name}.r"] = t.cpu().numpy()
 
     def prepared(gal):
         return eng.prepare_gallery(gal.cuda())
+
+    if deep_cap:
+        # ---- the radix fallback of the deep stage, with and without a ceiling ------------------------------------------------------
+        for tag, q, gal in [("equal", _unit(2, 64, 171), _unit(1, 64, 172).repeat(5000, 1)), ("random", _unit(3, 128, 173), _unit(1000, 128, 174))]:
+            first = eng.sim_topk_deep(q, gal, 100)
+            put(f"deep_{tag}_exact", first)
+            put(f"deep_{tag}_prefiltered", eng.sim_topk_deep(q, prepared(gal), 100))
+            put(f"deep_{tag}_from", eng.sim_topk_from(q, gal, 100, next_from(*first)))
+            ex = torch.tensor([1003, -1, 1000][:q.shape[0]], dtype=torch.int32)
+            first = eng.sim_topk_deep(q, gal, 100, idx_offset=1000, exclude_idx=ex)
+            put(f"deep_{tag}_offset", first)
+            put(f"deep_{tag}_from_offset", eng.sim_topk_from(q, gal, 100, next_from(*first), idx_offset=1000, exclude_idx=ex))
+        return out
 
     ex5 = torch.tensor([3, -1, 999, 0, 17], dtype=torch.int32)
 
@@ -156,13 +199,75 @@ def compute(eng, lists_only=False):
         q = _unit(4, 64, 180 + k)
         parts = [eng.sim_topk_deep(q, _unit(60 + 50 * r, 64, 190 + r), k, idx_offset=1000 * r) for r in range(3)]      # 60 rows < K = 100: -1 slots
         put(f"merge_{k}", eng.topk_merge(torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts])))
+    # ---- exact target ranks ---------------------------------------------------------------------------------------------------------
+    gen = torch.Generator().manual_seed(300)
+    # (the engine takes D % 32 == 0 for fp32 rows and D % 64 == 0 for bf16 rows: D = 288 is the smallest second, partial 256-k step)
+    for b, n, d in [(3, 1000, 64), (2, 300, 288), (2, 300, 320)]:
+        q, gal = _unit(b, d, 200 + n + d), _unit(n, d, 210 + n + d)
+        tags = torch.arange(n, dtype=torch.int32) % 7
+        filt = RowFilter(tags, mask=torch.tensor([0xFF, 0, 0xFF][:b], dtype=torch.int32), value=torch.tensor([3, 0, 5][:b], dtype=torch.int32))
+        ex = torch.tensor([3, -1, 7][:b], dtype=torch.int32)
+        forms = ([("f32", gal)] if d != 320 else []) + ([("bf16", eng.gallery_to_bf16(gal.cuda()))] if d % 64 == 0 else [])
+        for form, g in forms:
+            for m in (1, 16, 17):
+                tg = torch.randint(0, n, (b, m), generator=gen, dtype=torch.int32)
+                tg[0, 0] = 3                                                                # query 0's excluded row
+                tg[b - 1, m - 1] = n + 5                                                    # outside the gallery
+                puti(f"rankof_{form}_{n}_{d}_{m}", eng.rank_of(q, g, tg))
+                puti(f"rankof_{form}_{n}_{d}_{m}_exclude_offset", eng.rank_of(q, g, tg + 1000, idx_offset=1000, exclude_idx=ex + 1000))
+                puti(f"rankof_{form}_{n}_{d}_{m}_filt", eng.rank_of(q, g, tg, exclude_idx=ex, row_filter=filt))
+    # ---- items ----------------------------------------------------------------------------------------------------------------------
+    for n, shift in [(1030, 0), (1027, 1)]:
+        q, gal = _unit(3, 64, 220 + n), _unit(n, 64, 230 + n)
+        ids, G = _item_ids(n)
+        ids[10], ids[500] = -1, G + 5                                                       # rows of no item
+        buf = torch.cat([torch.zeros(shift, dtype=torch.int32), ids]).cuda()
+        items = ItemMap(buf[shift:], n_items=G)                                             # shift = 1: ids that are not 16-byte aligned
+        tg = torch.tensor([[0, 1, 2, 3, 4, 5, G - 1, -1, G + 5]] * 3, dtype=torch.int32)    # nine targets: two groups of the count kernel
+        filt = RowFilter(torch.arange(n, dtype=torch.int32) % 7, mask=torch.tensor([0xFF, 0, 0xFF], dtype=torch.int32),
+                         value=torch.tensor([3, 0, 5], dtype=torch.int32))
+        for form, g in [("f32", gal), ("bf16", eng.gallery_to_bf16(gal.cuda()))]:
+            first = eng.sim_topk_items(q, g, items, 10)
+            put(f"items_{form}_{n}", first)
+            puti(f"items_{form}_{n}_rank", eng.item_rank_of(q, g, items, tg))
+            best = first[1][:, 0].cpu().to(torch.int32)                                     # every query excludes the row that is its best item's best
+            put(f"items_{form}_{n}_exclude", eng.sim_topk_items(q, g, items, 10, exclude_idx=best))
+            puti(f"items_{form}_{n}_exclude_rank", eng.item_rank_of(q, g, items, tg, exclude_idx=best))
+            put(f"items_{form}_{n}_filt_offset", eng.sim_topk_items(q, g, items, 10, idx_offset=1000, exclude_idx=best + 1000, row_filter=filt))
+            puti(f"items_{form}_{n}_filt_offset_rank", eng.item_rank_of(q, g, items, tg, idx_offset=1000, exclude_idx=best + 1000, row_filter=filt))
+    # ---- pages: the row at a place ----------------------------------------------------------------------------------------------------
+    q = _unit(3, 64, 240)
+    for tag, gal in [("random_3000", _unit(3000, 64, 241)), ("equal_3000", _unit(1, 64, 242).repeat(3000, 1)), ("one_row", _unit(1, 64, 243))]:
+        n = gal.shape[0]
+        places = torch.tensor([[0, -1, n - 1, n, 5, 100, n // 2, n - 2]] * 3, dtype=torch.int32)      # the last row, one past the rows
+        puti(f"select_{tag}", eng.rank_select(q, gal, places))
+        puti(f"select_{tag}_exclude_offset", eng.rank_select(q, gal, places, idx_offset=1000, exclude_idx=torch.tensor([1003, -1, 1000], dtype=torch.int32)))
+    # ---- candidates -------------------------------------------------------------------------------------------------------------------
+    n = 2000
+    tags = torch.arange(n, dtype=torch.int32) % 7
+    filt = RowFilter(tags, mask=torch.tensor([0xFF, 0, 0xFF], dtype=torch.int32), value=torch.tensor([3, 0, 5], dtype=torch.int32))
+    ex = torch.tensor([3, -1, 7], dtype=torch.int32)
+    for form, d in [("ring", 64), ("lane", 96), ("bf16", 64)]:
+        q, gal = _unit(3, d, 250 + d), _unit(n, d, 260 + d)
+        g = eng.gallery_to_bf16(gal.cuda()) if form == "bf16" else gal
+        for m in (1, 33, 600):
+            cd = torch.randint(0, n, (3, m), generator=gen, dtype=torch.int32)
+            if m > 1:
+                cd[:, 3], cd[:, 5], cd[:, 7], cd[0, 9] = cd[:, 2], -1, n + 50, 3            # named twice, negative, outside, the excluded row
+            if m == 600:
+                cd[:, 300:] = cd[:, :300]                                                   # every row twice
+            for k in (5, 700):
+                put(f"cand_{form}_{m}_{k}", eng.sim_topk_candidates(q, g, cd, k, places=True))
+                if m > 1:
+                    put(f"cand_{form}_{m}_{k}_filt_offset",
+                        eng.sim_topk_candidates(q, g, cd + 1000, k, idx_offset=1000, exclude_idx=ex + 1000, row_filter=filt, places=True))
     return out
 
 
 if __name__ == "__main__":
     from fashionern_aaai2024_amd.engine import FernEngine
     eng = FernEngine("cuda:0")
-    arrays = compute(eng, lists_only="FERN_RANK_CAP" in os.environ)
+    arrays = compute(eng, lists_only="FERN_RANK_CAP" in os.environ, deep_cap="FERN_RANK_DEEP_CAP" in os.environ)
     torch.cuda.synchronize()
     np.savez(sys.argv[-1], **arrays)
     print(f"{len(arrays)} arrays -> {sys.argv[-1]}")
