@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libfern.so")
 SOURCES = ["api_ctx.hip", "api_weights.hip", "api_fusion.hip", "api_towers.hip", "api.hip", "api_blocks.hip", "gemm.hip", "gemm_bf16.hip", "gemm_tuner.hip", "gemm_pp.hip", "attn.hip", "elem.hip", "topk.hip", "topk_deep.hip", "items.hip", "rank.hip", "candidates.hip", "page.hip", "image.hip", "sweep_bf16.hip", "live.hip"]
-HEADERS = ["ctx.h", "kernels.h", "gemm_epilogue.h", "gemm_pp.h", "gemm_tuner.h", "rescore.h", "select.h", "wave.h", "row_ops.h", "live.h", os.path.join("..", "..", "include", "fern.h")]
+HEADERS = ["ctx.h", "kernels.h", "gemm_epilogue.h", "gemm_tile.h", "gemm_pp.h", "gemm_tuner.h", "rescore.h", "select.h", "wave.h", "row_ops.h", "live.h", os.path.join("..", "..", "include", "fern.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-DFERN_BUILD"]
 
 

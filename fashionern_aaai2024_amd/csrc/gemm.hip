@@ -15,7 +15,7 @@
 //     ds_read_b128 feeds four MFMAs; both operands use the same permutation, so the sum is unchanged;
 //   * workgroup ids are remapped so that each XCD (private L2) owns a contiguous run of tiles.
 #include "kernels.h"
-#include "gemm_epilogue.h"
+#include "gemm_tile.h"
 #include "gemm_tuner.h"
 
 #include <algorithm>
@@ -56,13 +56,8 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_f32_kernel(Ge
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    // ---- XCD-aware, bijective workgroup -> tile map (n fastest inside an XCD's contiguous run) ----
-    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    const int bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int bm = swz / nbn, bn = swz % nbn;
+    const TileAt at = tile_at<BM, BN>(blockIdx.x, p.M, p.N);
+    const int bm = at.bm, bn = at.bn, nbn = at.nbn;
 
     // ---- per-thread staging coordinates ----
     const int c4 = tid % C4;     // float4 column inside the k tile
@@ -71,8 +66,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_f32_kernel(Ge
     const float* w_base[WJ];
 #pragma unroll
     for (int j = 0; j < AJ; ++j) {
-        int row = bm * BM + r0 + RSTEP * j;
-        row = row < p.M ? row : p.M - 1;
+        const int row = clamp_row(bm * BM + r0 + RSTEP * j, p.M);
         if (p.aload == ALOAD_IM2COL) {
             const int g2 = p.grid * p.grid;
             const int b = row / g2, pr = row % g2;
@@ -84,8 +78,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void gemm_f32_kernel(Ge
     }
 #pragma unroll
     for (int j = 0; j < WJ; ++j) {
-        int row = bn * BN + r0 + RSTEP * j;
-        row = row < p.N ? row : p.N - 1;
+        const int row = clamp_row(bn * BN + r0 + RSTEP * j, p.N);
         w_base[j] = p.W + sample_row(row, p.w_sample) * p.ldw;
     }
 
@@ -187,13 +180,10 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
     constexpr int NW = WAVES_M * WAVES_N;
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int ROWS = BM + BN;                        // A rows then W rows
-    constexpr int C4 = BKT / 4;                          // 16-byte chunks per tile row (4 or 8)
-    constexpr int RPP = 64 / C4;                         // tile rows per 1 KiB piece (16 or 8)
+    using TR = TileRows<BKT * 4>;                        // 64- or 128-byte tile rows
+    constexpr int C4 = TR::C4, RPP = TR::RPP;
     constexpr int PIECES = ROWS / RPP;
     constexpr int PPW = (PIECES + NW - 1) / NW;          // pieces per wave per tile (the last ones may not exist: guarded, wave-uniform)
-    // swizzle: chunk c of row r lives at position c ^ f(r); f(r) = (r >> 2) & 3 for 64-byte rows, (r >> 1) & 7 for 128-byte rows
-    constexpr int FSH = BKT == 16 ? 2 : 1;
-    constexpr int FMASK = C4 - 1;
 
     constexpr int TILE = ROWS * BKT;                     // floats per buffer; smem holds two
     int kbeg = 0, klen = p.K;
@@ -209,13 +199,12 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    int bm = swz / nbn, bn = swz % nbn;
+    const TileAt at = tile_at<BM, BN>(bid, p.M, p.N);
+    int bm = at.bm, bn = at.bn;
+    const int nbn = at.nbn;
 #ifdef FERN_GEMM_TRACE
     if (const int sw = p.packed >> 8) {        // probe: column stripes of `sw` tiles, rows fastest across a stripe's columns
+        const int nbm = (p.M + BM - 1) / BM, swz = bm * nbn + bn;
         const int stripe = sw * nbm, nfull = nbn / sw;
         if (swz < nfull * stripe) { const int r = swz % stripe; bm = r / sw; bn = (swz / stripe) * sw + r % sw; }
         else { const int r = swz - nfull * stripe, w = nbn - nfull * sw; bm = r / w; bn = nfull * sw + r % w; }
@@ -229,11 +218,10 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
     for (int j = 0; j < PPW; ++j) {
         const int piece = wave + NW * j;                       // wave-uniform
         const int trow = piece * RPP + lane / C4;              // row in the [A; W] tile-row space (BM, BN multiples of 32)
-        const int chunk = (lane & FMASK) ^ ((trow >> FSH) & FMASK);   // logical chunk stored at position lane % C4
+        const int chunk = TR::store_chunk(lane, trow);         // logical chunk stored at position lane % C4
         cb[j] = cy[j] = cx[j] = 0;
         if (trow < BM) {
-            int row = bm * BM + trow;
-            row = row < p.M ? row : p.M - 1;
+            const int row = clamp_row(bm * BM + trow, p.M);
             if (CONV) {
                 const int hw = p.conv_h * p.conv_w;
                 cb[j] = row / hw;
@@ -248,8 +236,7 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
 #endif
             }
         } else {
-            int row = bn * BN + (trow - BM);
-            row = row < p.N ? row : p.N - 1;
+            const int row = clamp_row(bn * BN + (trow - BM), p.N);
             src[j] = p.W + sample_row(row, p.w_sample) * p.ldw + chunk * 4 + kbeg;
 #ifdef FERN_GEMM_TRACE
             if (p.packed & 1) src[j] = p.W + (long)row * 16 + chunk * 4;
@@ -277,8 +264,7 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
                 const bool inside = yy >= 0 && yy < p.conv_h && xx >= 0 && xx < p.conv_w;
                 g = inside ? src[j] + (((long)cb[j] * p.conv_h + yy) * p.conv_w + xx) * p.conv_c + c0 : p.zeros + (lane & 3) * 4;
             }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                             (__attribute__((address_space(3))) void*)(smem + buf * TILE + piece * 256), 16, 0, 0);
+            lds_dma16(g, smem + buf * TILE + piece * 256);
         }
     };
 
@@ -290,7 +276,7 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    const int sw = (l31 >> FSH) & FMASK;                        // read-side swizzle of this lane's rows
+    const int sw = TR::read_swizzle(l31);                       // read-side swizzle of this lane's rows
     // f32x3 (SPLIT = 3): fp32 operands split IN REGISTERS, after the LDS read, into three bf16 planes by truncation (x1 = top 16
     // bits of x -- one v_perm_b32 packs two --, r1 = x - x1 exactly, x2 = top 16 bits of r1, ...: 8 + 8 + 8 mantissa bits), the six
     // products of total order <= 4 on v_mfma_f32_32x32x16_bf16 (32 cycles each against two 64-cycle fp32 MFMAs).  The two 8-groups
@@ -298,44 +284,22 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
     // exact arithmetic is the fp32 kernel's own (measured 1.7-2.3e-6 of the output rms against 2.0e-6), at 1.4-1.5x its speed; it
     // is NOT the fp32 fma chain, so nothing that must be bit-identical to the sweep's scores may use it.  Every configuration walks
     // k in the same order with the same six products: results are bit-identical across tile shapes and batch-invariant.
-    typedef short bf16x8s __attribute__((ext_vector_type(8)));
-    typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
     constexpr int NPL = SPLIT > 0 ? SPLIT : 1;
-    typedef float f32x2s __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x2s __attribute__((ext_vector_type(2)));
-    auto split = [&](const f32x4& g0, const f32x4& g1, bf16x8s (&pl)[NPL]) {
-        f32x2s x[4] = {{g0[0], g0[1]}, {g0[2], g0[3]}, {g1[0], g1[1]}, {g1[2], g1[3]}};      // pairs: the residual is one packed fp32 subtract
-#pragma unroll
-        for (int lv = 0; lv < NPL; ++lv) {
-            u32x4s packed;
-#pragma unroll
-            for (int q2 = 0; q2 < 4; ++q2)      // bytes 2-3 of two floats -> one dword of two bf16
-                packed[q2] = __builtin_amdgcn_perm(__float_as_uint(x[q2][1]), __float_as_uint(x[q2][0]), 0x07060302u);
-            pl[lv] = __builtin_bit_cast(bf16x8s, packed);
-            if (lv + 1 < NPL) {
-#pragma unroll
-                for (int q2 = 0; q2 < 4; ++q2) {
-                    const u32x2s top = __builtin_bit_cast(u32x2s, x[q2]) & 0xFFFF0000u;
-                    x[q2] = x[q2] - __builtin_bit_cast(f32x2s, top);
-                }
-            }
-        }
-    };
     auto compute_split = [&](int buf) {
         static_assert(SPLIT == 0 || BKT == 16, "the split form pairs the two 8-groups of a 16-k tile");
         const float* As = smem + buf * TILE;
         const float* Ws = As + BM * BKT;
-        bf16x8s ap[TM][NPL], bp[TN][NPL];
+        bf16x8 ap[TM][NPL], bp[TN][NPL];
         const int pc0 = ((0 + lh) ^ sw) * 4, pc1 = ((2 + lh) ^ sw) * 4;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const float* r = &As[(wm * WM + i * 32 + l31) * BKT];
-            split(*reinterpret_cast<const f32x4*>(r + pc0), *reinterpret_cast<const f32x4*>(r + pc1), ap[i]);
+            split_bf16_planes<NPL>(*reinterpret_cast<const f32x4*>(r + pc0), *reinterpret_cast<const f32x4*>(r + pc1), ap[i]);
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const float* r = &Ws[(wn * WN + j * 32 + l31) * BKT];
-            split(*reinterpret_cast<const f32x4*>(r + pc0), *reinterpret_cast<const f32x4*>(r + pc1), bp[j]);
+            split_bf16_planes<NPL>(*reinterpret_cast<const f32x4*>(r + pc0), *reinterpret_cast<const f32x4*>(r + pc1), bp[j]);
         }
         // products in order of the planes they need -- a1 b1 | a1 b2, a2 b1 | a2 b2, a1 b3, a3 b1 -- so that the VALU work of the
         // deeper planes can run under the MFMAs of the shallower ones (left to hipcc's scheduler: pinning 1 MFMA : 6 VALU groups with
@@ -398,7 +362,7 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
 #endif
     FERN_TRACE_MARK();
     stage(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     FERN_TRACE_MARK();
     // Waves inside the main loop outrank co-resident waves that are in their prologue or epilogue: the epilogue is a few thousand
@@ -409,7 +373,7 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
     __builtin_amdgcn_s_setprio(2);
     for (int kt = 0; kt < nk; ++kt) {
         if (kt + 1 < nk) stage((kt + 1) & 1, (kt + 1) * BKT);   // the other buffer is free: every wave passed the last barrier
-        if (SYNC == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // A/B variant: drain the copy before computing
+        if (SYNC == 1) wait_vmcnt<0>();   // A/B variant: drain the copy before computing
         compute(kt & 1);
         if (SYNC == 2) __builtin_amdgcn_sched_barrier(0);
 #ifdef FERN_GEMM_TRACE_PHASES      // three stamps per k tile: MFMAs issued | own DMA landed | barrier passed (pins the order: attribution only)
@@ -428,7 +392,7 @@ __device__ __forceinline__ void glds_tile(GemmParams p, const int bid, float* sm
     else if (FILT) filter_epilogue<BM, BN, WM, WN, TM, TN>(p, acc, bm, bn, wm, wn, l31, lh);
     else gemm_epilogue<BM, BN, WM, WN, TM, TN, WAVES_N>(p, acc, bm, bn, nbn, wm, wn, l31, lh, tid);
 #ifdef FERN_GEMM_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     FERN_TRACE_MARK();
     if (tr && lane == 0) tr[3] = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
@@ -473,34 +437,8 @@ __global__ __launch_bounds__((BM / 128) * (BN / 64) * 64, 2) void gemm_f32x3_sha
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int l31 = lane & 31, lh = lane >> 5;
-    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    const int bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int bm = swz / nbn, bn = swz % nbn;
-
-    typedef short bf16x8s __attribute__((ext_vector_type(8)));
-    typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-    typedef float f32x2s __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x2s __attribute__((ext_vector_type(2)));
-    auto split = [&](const f32x4& g0, const f32x4& g1, bf16x8s (&pl)[3]) {      // glds_tile's split(), statement for statement
-        f32x2s x[4] = {{g0[0], g0[1]}, {g0[2], g0[3]}, {g1[0], g1[1]}, {g1[2], g1[3]}};
-#pragma unroll
-        for (int lv = 0; lv < 3; ++lv) {
-            u32x4s packed;
-#pragma unroll
-            for (int q2 = 0; q2 < 4; ++q2) packed[q2] = __builtin_amdgcn_perm(__float_as_uint(x[q2][1]), __float_as_uint(x[q2][0]), 0x07060302u);
-            pl[lv] = __builtin_bit_cast(bf16x8s, packed);
-            if (lv + 1 < 3) {
-#pragma unroll
-                for (int q2 = 0; q2 < 4; ++q2) {
-                    const u32x2s top = __builtin_bit_cast(u32x2s, x[q2]) & 0xFFFF0000u;
-                    x[q2] = x[q2] - __builtin_bit_cast(f32x2s, top);
-                }
-            }
-        }
-    };
+    const TileAt at = tile_at<BM, BN>(blockIdx.x, p.M, p.N);
+    const int bm = at.bm, bn = at.bn, nbn = at.nbn;
 
     const float* src[UPT];
     int dst[UPT];
@@ -509,13 +447,9 @@ __global__ __launch_bounds__((BM / 128) * (BN / 64) * 64, 2) void gemm_f32x3_sha
         const int unit = tid + NT * u;
         const int trow = unit >> 1, h = unit & 1;
         if (trow < BM) {
-            int row = bm * BM + trow;
-            row = row < p.M ? row : p.M - 1;
-            src[u] = p.A + (long)row * p.lda + h * 4;
+            src[u] = p.A + (long)clamp_row(bm * BM + trow, p.M) * p.lda + h * 4;
         } else {
-            int row = bn * BN + (trow - BM);
-            row = row < p.N ? row : p.N - 1;
-            src[u] = p.W + (long)row * p.ldw + h * 4;
+            src[u] = p.W + (long)clamp_row(bn * BN + (trow - BM), p.N) * p.ldw + h * 4;
         }
         dst[u] = h * HALF + trow * 16;
     }
@@ -533,10 +467,10 @@ __global__ __launch_bounds__((BM / 128) * (BN / 64) * 64, 2) void gemm_f32x3_sha
     auto publish = [&](const f32x4 (&gs)[UPT][2], int buf) {
 #pragma unroll
         for (int u = 0; u < UPT; ++u) {
-            bf16x8s pl[3];
-            split(gs[u][0], gs[u][1], pl);
+            bf16x8 pl[3];
+            split_bf16_planes<3>(gs[u][0], gs[u][1], pl);      // glds_tile's split: the same plane bits
 #pragma unroll
-            for (int lv = 0; lv < 3; ++lv) *reinterpret_cast<bf16x8s*>(smem + buf * BUF + lv * PLANE + dst[u]) = pl[lv];
+            for (int lv = 0; lv < 3; ++lv) *reinterpret_cast<bf16x8*>(smem + buf * BUF + lv * PLANE + dst[u]) = pl[lv];
         }
     };
 
@@ -551,13 +485,13 @@ __global__ __launch_bounds__((BM / 128) * (BN / 64) * 64, 2) void gemm_f32x3_sha
     const int arow = lh * HALF + (wm * WM + l31) * 16, wrow = lh * HALF + (BM + wn * WN + l31) * 16;
     auto compute = [&](int buf) {
         const char* P = smem + buf * BUF;
-        bf16x8s ap[TM][3], bp[TN][3];
+        bf16x8 ap[TM][3], bp[TN][3];
 #pragma unroll
         for (int lv = 0; lv < 3; ++lv) {
 #pragma unroll
-            for (int i = 0; i < TM; ++i) ap[i][lv] = *reinterpret_cast<const bf16x8s*>(P + lv * PLANE + arow + i * 512);
+            for (int i = 0; i < TM; ++i) ap[i][lv] = *reinterpret_cast<const bf16x8*>(P + lv * PLANE + arow + i * 512);
 #pragma unroll
-            for (int j = 0; j < TN; ++j) bp[j][lv] = *reinterpret_cast<const bf16x8s*>(P + lv * PLANE + wrow + j * 512);
+            for (int j = 0; j < TN; ++j) bp[j][lv] = *reinterpret_cast<const bf16x8*>(P + lv * PLANE + wrow + j * 512);
         }
 #pragma unroll
         for (int ord = 0; ord < 3; ++ord)
@@ -728,20 +662,15 @@ __global__ __launch_bounds__(256) void gemm_f32_skinny_kernel(GemmParams p) {
         // 16-byte chunk c of row r lives at position c ^ f(r); f makes every ds_read_b128 group hit 16 distinct bank quads
         const int chunk = (lane & (C4 - 1)) ^ (BKT == 32 ? ((trow >> 1) & 7) : (trow & 15));
         if (trow < BM) {
-            int row = bm * BM + trow;
-            row = row < p.M ? row : p.M - 1;
-            src[j] = p.A + (long)row * p.lda + chunk * 4 + kbeg;
+            src[j] = p.A + (long)clamp_row(bm * BM + trow, p.M) * p.lda + chunk * 4 + kbeg;
         } else {
-            int row = bn * BN + (trow - BM);
-            row = row < p.N ? row : p.N - 1;
-            src[j] = p.W + sample_row(row, p.w_sample) * p.ldw + chunk * 4 + kbeg;
+            src[j] = p.W + sample_row(clamp_row(bn * BN + (trow - BM), p.N), p.w_sample) * p.ldw + chunk * 4 + kbeg;
         }
     }
     auto stage = [&](int buf, int k0) {
 #pragma unroll
         for (int j = 0; j < PPW; ++j)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + k0),
-                                             (__attribute__((address_space(3))) void*)(smem + buf * TILE + (wave + NW * j) * 256), 16, 0, 0);
+            lds_dma16(src[j] + k0, smem + buf * TILE + (wave + NW * j) * 256);
     };
 
     f32x4v acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -776,8 +705,8 @@ __global__ __launch_bounds__(256) void gemm_f32_skinny_kernel(GemmParams p) {
         if (t < nk) stage(t, t * BKT);
     int slot = 0;
     for (int kt = 0; kt < nk; ++kt) {
-        if (kt + STAGES - 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW * (STAGES - 2)) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (kt + STAGES - 2 < nk) wait_vmcnt<PPW * (STAGES - 2)>();
+        else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         if (kt + STAGES - 1 < nk) {
             int fill = slot + STAGES - 1;
@@ -884,7 +813,7 @@ static bool launch_glds_8_11(int c, dim3 grid, const GemmParams& p, hipStream_t 
     }
 }
 static hipError_t launch_cfg(int c, const GemmParams& p, hipStream_t s) {
-    const int nb = ((p.M + kCfgs[c].bm - 1) / kCfgs[c].bm) * ((p.N + kCfgs[c].bn - 1) / kCfgs[c].bn);
+    const int nb = tile_blocks(kCfgs[c].bm, kCfgs[c].bn, p);
     const int ks = p.ksplit > 1 ? p.ksplit : 1;
     const dim3 grid(nb, ks);
     if (p.epi == EPI_TOPK_FILTER) {      // the filtered sweep: LDS-DMA family, own instantiations
@@ -1097,7 +1026,7 @@ static bool split_family_ok(const GemmParams& p) {
     return p.split == 3 && split_ok(p) && p.M >= 256 && p.K % 16 == 0;
 }
 static hipError_t launch_cfg_split(int c, const GemmParams& p, hipStream_t s) {
-    const int nb = ((p.M + kCfgsS[c].bm - 1) / kCfgsS[c].bm) * ((p.N + kCfgsS[c].bn - 1) / kCfgsS[c].bn);
+    const int nb = tile_blocks(kCfgsS[c].bm, kCfgsS[c].bn, p);
     switch (c) {
         case 0: FERN_LAUNCH((gemm_f32_glds_kernel<128, 128, 64, 64, 16, 3, false, 0, false, 3>), dim3(nb), dim3(256), 0, s, p); break;
         case 1: FERN_LAUNCH((gemm_f32_glds_kernel<256, 128, 128, 64, 16, 2, false, 0, false, 3>), dim3(nb), dim3(256), 0, s, p); break;

@@ -11,7 +11,7 @@
 // consecutive k values a lane feeds to one 32x32x16 MFMA (lane half h supplies k = 16*kk + 8*h .. +7 of both
 // operands).  Every configuration adds the 16-wide k groups in ascending order, so all of them produce bit-identical
 // results and a row's result does not depend on the batch it is part of.
-#include "gemm_epilogue.h"
+#include "gemm_tile.h"
 #include "gemm_tuner.h"
 
 #include <algorithm>
@@ -19,10 +19,6 @@
 #include <cstdlib>
 
 namespace fern {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef long i64x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // FP8: the operands are OCP e4m3fn bytes and the MFMA is v_mfma_f32_32x32x16_fp8_fp8 (same rate as bf16, half the bytes):
 // a BKE-element tile row is then BKE bytes, one ds_read_b128 holds the fragments of TWO consecutive MFMA k-steps (low /
@@ -41,13 +37,10 @@ __device__ __forceinline__ void bf16_tile_body(const GemmParams& p, const int bi
     constexpr int ROWS = BM + BN;                        // A rows then W rows
     constexpr int ES = FP8 ? 1 : 2;                      // operand element size (bytes)
     constexpr int RB = BKE * ES;                         // bytes per tile row (64 or 128)
-    constexpr int C4 = RB / 16;                          // 16-byte chunks per tile row
-    constexpr int RPP = 64 / C4;                         // tile rows per 1 KiB piece
-    constexpr int PIECES = ROWS / RPP;
+    using TR = TileRows<RB>;
+    constexpr int PIECES = ROWS / TR::RPP;
     static_assert(PIECES % NW == 0, "pieces must divide over the waves");
     constexpr int PPW = PIECES / NW;
-    constexpr int FSH = RB == 64 ? 2 : 1;                // chunk c of row r lives at position c ^ ((r >> FSH) & FMASK)
-    constexpr int FMASK = C4 - 1;
     constexpr int TILE = ROWS * RB;                      // bytes per stage
 
     // (the caller's ONE __shared__ object -- see gemm.hip: a second one makes hipcc drain the DMA before every first fragment read)
@@ -59,19 +52,15 @@ __device__ __forceinline__ void bf16_tile_body(const GemmParams& p, const int bi
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    // XCD-aware bijective workgroup -> tile map (n fastest inside an XCD's contiguous run)
-    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int bm = swz / nbn, bn = swz % nbn;
+    const TileAt at = tile_at<BM, BN>(bid, p.M, p.N);
+    const int bm = at.bm, bn = at.bn, nbn = at.nbn;
 
     const char* src[PPW];
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {
         const int piece = wave + NW * j;                       // wave-uniform
-        const int trow = piece * RPP + lane / C4;              // row in the [A; W] tile-row space
-        const int chunk = (lane & FMASK) ^ ((trow >> FSH) & FMASK);
+        const int trow = piece * TR::RPP + lane / TR::C4;      // row in the [A; W] tile-row space
+        const int chunk = TR::store_chunk(lane, trow);
         if (trow < BM) {
             int row = bm * BM + trow;
             row = row < p.M ? row : p.M - 1;
@@ -86,8 +75,7 @@ __device__ __forceinline__ void bf16_tile_body(const GemmParams& p, const int bi
 #pragma unroll
         for (int j = 0; j < PPW; ++j) {
             const int piece = wave + NW * j;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (long)k0 * ES),
-                                             (__attribute__((address_space(3))) void*)(smem + buf * TILE + piece * 1024), 16, 0, 0);
+            lds_dma16(src[j] + (long)k0 * ES, smem + buf * TILE + piece * 1024);
         }
     };
 
@@ -99,7 +87,7 @@ __device__ __forceinline__ void bf16_tile_body(const GemmParams& p, const int bi
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    const int sw = (l31 >> FSH) & FMASK;
+    const int sw = TR::read_swizzle(l31);
     auto compute = [&](int buf) {
         const char* As = smem + buf * TILE;
         const char* Ws = As + BM * RB;
@@ -145,11 +133,11 @@ __device__ __forceinline__ void bf16_tile_body(const GemmParams& p, const int bi
     int slot = 0;                                   // ring slot of tile kt
     for (int kt = 0; kt < nk; ++kt) {
         if (kt + STAGES - 2 < nk) {                 // steady state: STAGES-2 younger tiles issued after tile kt
-            if (STAGES == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (STAGES == 3) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW) : "memory");
+            if (STAGES == 2) wait_vmcnt<0>();
+            else if (STAGES == 3) wait_vmcnt<PPW>();
+            else wait_vmcnt<2 * PPW>();
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
         }
         __builtin_amdgcn_s_barrier();
         if (kt + STAGES - 1 < nk) {
@@ -180,9 +168,6 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, MINW) void gemm_bf16_gl
 // bytes (step 0, h 0), (step 0, h 1), (step 1, h 0), (step 1, h 1), so a tile's scales are (BM + BN) consecutive dwords per operand
 // block, staged by 4-byte LDS-DMA pieces of 64 rows behind the tile's data.  A lane reads its row's dword, shifts it right by 8h
 // and opsel (0 / 2) picks the step's byte; its data are the two swizzled 16-byte chunks h and 2 + h of the step.  Every configuration adds the 64-wide k steps in ascending order.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-
 template <int BM, int BN, int STAGES, int RB>
 constexpr int mx8_tile_lds() { return STAGES * (((BM + BN) * RB + (BM + BN) * 4 + 1023) / 1024 * 1024); }
 // body / wrapper split as for the bf16 kernel above
@@ -194,11 +179,8 @@ __device__ __forceinline__ void mx8_tile_body(const GemmParams& p, const int bid
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int ROWS = BM + BN;
     static_assert(RB == 128 || RB == 64, "tile rows are one or two 64-k MFMA steps");   // RB: bytes (= k) per tile row
-    constexpr int C4 = RB / 16;                          // 16-byte chunks per tile row
-    constexpr int RPP = 64 / C4;                         // tile rows per 1 KiB piece
-    constexpr int FSH = RB == 64 ? 2 : 1;                // chunk c of row r lives at position c ^ ((r >> FSH) & FMASK)
-    constexpr int FMASK = C4 - 1;
-    constexpr int PIECES = ROWS / RPP;
+    using TR = TileRows<RB>;
+    constexpr int PIECES = ROWS / TR::RPP;
     static_assert(PIECES % NW == 0, "pieces must divide over the waves");
     constexpr int PPW = PIECES / NW;
     constexpr int SP = ROWS / 64;                        // 256-byte scale pieces (64 rows x 1 dword)
@@ -214,18 +196,15 @@ __device__ __forceinline__ void mx8_tile_body(const GemmParams& p, const int bid
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int bm = swz / nbn, bn = swz % nbn;
+    const TileAt at = tile_at<BM, BN>(bid, p.M, p.N);
+    const int bm = at.bm, bn = at.bn, nbn = at.nbn;
 
     const char* src[PPW];
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {
         const int piece = wave + NW * j;
-        const int trow = piece * RPP + lane / C4;
-        const int chunk = (lane & FMASK) ^ ((trow >> FSH) & FMASK);
+        const int trow = piece * TR::RPP + lane / TR::C4;
+        const int chunk = TR::store_chunk(lane, trow);
         if (trow < BM) {
             int row = bm * BM + trow;
             row = row < p.M ? row : p.M - 1;
@@ -258,14 +237,12 @@ __device__ __forceinline__ void mx8_tile_body(const GemmParams& p, const int bid
 #pragma unroll
         for (int j = 0; j < PPW; ++j) {
             const int piece = wave + NW * j;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (long)kt * RB),
-                                             (__attribute__((address_space(3))) void*)(smem + buf * TILE + piece * 1024), 16, 0, 0);
+            lds_dma16(src[j] + (long)kt * RB, smem + buf * TILE + piece * 1024);
         }
 #pragma unroll
         for (int j = 0; j < SPW; ++j) {
             const int sp = (wave + NW * j) % SP;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ssrc[j] + (RB == 64 ? kt >> 1 : kt) * sstep[j]),
-                                             (__attribute__((address_space(3))) void*)(smem + buf * TILE + DATA + sp * 256), 4, 0, 0);
+            lds_dma4(ssrc[j] + (RB == 64 ? kt >> 1 : kt) * sstep[j], smem + buf * TILE + DATA + sp * 256);
         }
     };
 
@@ -277,7 +254,7 @@ __device__ __forceinline__ void mx8_tile_body(const GemmParams& p, const int bid
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    const int sw = (l31 >> FSH) & FMASK;
+    const int sw = TR::read_swizzle(l31);
     auto compute = [&](int buf, int kt) {
         const char* As = smem + buf * TILE;
         const char* Ws = As + BM * RB;
@@ -320,9 +297,9 @@ __device__ __forceinline__ void mx8_tile_body(const GemmParams& p, const int bid
     for (int kt = 0; kt < nk; ++kt) {
         // tiles kt+1 .. kt+STAGES-2 may stay in flight; near the end fewer have been issued
         const int younger = nk - 1 - kt < STAGES - 2 ? nk - 1 - kt : STAGES - 2;
-        if (STAGES >= 4 && younger == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (PPW + SPW)) : "memory");
-        else if (STAGES >= 3 && younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW + SPW) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (STAGES >= 4 && younger == 2) wait_vmcnt<2 * (PPW + SPW)>();
+        else if (STAGES >= 3 && younger == 1) wait_vmcnt<PPW + SPW>();
+        else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         if (kt + STAGES - 1 < nk) {
             int fill = slot + STAGES - 1;
@@ -395,7 +372,7 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64, MINW) void gemm_mx8_ker
 
 // ---- tile configurations of the three families (gemm_tuner.h: kCfgsB, kCfgsF8, kCfgsMx) -----------------------------------------------
 static hipError_t launch_cfg_b(int c, const GemmParams& p, hipStream_t s) {
-    const int nb = ((p.M + kCfgsB[c].bm - 1) / kCfgsB[c].bm) * ((p.N + kCfgsB[c].bn - 1) / kCfgsB[c].bn);
+    const int nb = tile_blocks(kCfgsB[c].bm, kCfgsB[c].bn, p);
     switch (c) {
         case 0: FERN_LAUNCH((gemm_bf16_glds_kernel<128, 128, 64, 64, 32, 2, 4>), dim3(nb), dim3(256), 0, s, p); break;
         case 1: FERN_LAUNCH((gemm_bf16_glds_kernel<256, 128, 64, 64, 32, 3, 2>), dim3(nb), dim3(512), 0, s, p); break;
@@ -412,7 +389,7 @@ static hipError_t launch_cfg_b(int c, const GemmParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 static hipError_t launch_cfg_f8(int c, const GemmParams& p, hipStream_t s) {
-    const int nb = ((p.M + kCfgsF8[c].bm - 1) / kCfgsF8[c].bm) * ((p.N + kCfgsF8[c].bn - 1) / kCfgsF8[c].bn);
+    const int nb = tile_blocks(kCfgsF8[c].bm, kCfgsF8[c].bn, p);
     switch (c) {
         case 0: FERN_LAUNCH((gemm_bf16_glds_kernel<128, 128, 64, 64, 64, 2, 4, true>), dim3(nb), dim3(256), 0, s, p); break;
         case 1: FERN_LAUNCH((gemm_bf16_glds_kernel<256, 128, 64, 64, 64, 3, 2, true>), dim3(nb), dim3(512), 0, s, p); break;
@@ -425,7 +402,7 @@ static hipError_t launch_cfg_f8(int c, const GemmParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 static hipError_t launch_cfg_mx(int c, const GemmParams& p, hipStream_t s) {
-    const int nb = ((p.M + kCfgsMx[c].bm - 1) / kCfgsMx[c].bm) * ((p.N + kCfgsMx[c].bn - 1) / kCfgsMx[c].bn);
+    const int nb = tile_blocks(kCfgsMx[c].bm, kCfgsMx[c].bn, p);
     switch (c) {
         case 0: FERN_LAUNCH((gemm_mx8_kernel<128, 128, 64, 64, 2, 2>), dim3(nb), dim3(256), 0, s, p); break;
         case 1: FERN_LAUNCH((gemm_mx8_kernel<256, 128, 64, 64, 2, 2>), dim3(nb), dim3(512), 0, s, p); break;
@@ -507,7 +484,7 @@ static int tune_shape_b(const FamilyB& fam, const GemmParams& p, hipStream_t s, 
         if (t[c] > 1e29f) continue;
         float score = t[c];
         if (conc > 1) {
-            const double nwg = (double)((p.M + fam.cfgs[c].bm - 1) / fam.cfgs[c].bm) * ((p.N + fam.cfgs[c].bn - 1) / fam.cfgs[c].bn);
+            const double nwg = tile_blocks(fam.cfgs[c].bm, fam.cfgs[c].bn, p);
             const double share = std::min(1.0, nwg / (256.0 * fam.cfgs[c].per_cu));
             score *= (float)std::pow(share, share_exponent());
         }

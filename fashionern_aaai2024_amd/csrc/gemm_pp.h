@@ -33,42 +33,34 @@
 //             2T+2, by G0 after barrier 4T+3.
 // What it reaches, the elimination runs and the per-phase stamps: profiles/r06_pp_lab.txt, DESIGN.md 4 / 8 / 9.
 #pragma once
-#include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 
 namespace fern {
-
-typedef short pp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef int pp_i32x4 __attribute__((ext_vector_type(4)));
-typedef int pp_i32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int PP_BM = 256, PP_BN = 256, PP_RB = 64;
 constexpr int PP_UNIT = 256 * PP_RB;        // 16 KiB: the A (or W) rows of one k tile
 constexpr int PP_SLOT = 2 * PP_UNIT;        // 32 KiB
 constexpr int PP_SCALE_SLOTS = 4, PP_SCALE_BYTES = 2048;      // block-scaled family: one dword per (row, 128 k) for 512 rows
 
-template <int N>
-__device__ __forceinline__ void pp_wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // wait until all but the `younger` most recent vector-memory operations of this wave are done (wave-uniform value, 0 .. 9+)
 __device__ __forceinline__ void pp_wait_vmcnt_dyn(int younger) {
-    if (younger == 8) { pp_wait_vmcnt<8>(); return; }      // the steady states of the two operand kinds first (one compare each)
-    if (younger == 9) { pp_wait_vmcnt<9>(); return; }
+    if (younger == 8) { wait_vmcnt<8>(); return; }      // the steady states of the two operand kinds first (one compare each)
+    if (younger == 9) { wait_vmcnt<9>(); return; }
     switch (younger) {
-        case 0: pp_wait_vmcnt<0>(); break;
-        case 1: pp_wait_vmcnt<1>(); break;
-        case 2: pp_wait_vmcnt<2>(); break;
-        case 3: pp_wait_vmcnt<3>(); break;
-        case 4: pp_wait_vmcnt<4>(); break;
-        case 5: pp_wait_vmcnt<5>(); break;
-        case 6: pp_wait_vmcnt<6>(); break;
-        case 7: pp_wait_vmcnt<7>(); break;
-        case 8: pp_wait_vmcnt<8>(); break;
-        case 9: pp_wait_vmcnt<9>(); break;
-        case 10: pp_wait_vmcnt<10>(); break;
-        case 11: pp_wait_vmcnt<11>(); break;
-        default: pp_wait_vmcnt<12>(); break;
+        case 0: wait_vmcnt<0>(); break;
+        case 1: wait_vmcnt<1>(); break;
+        case 2: wait_vmcnt<2>(); break;
+        case 3: wait_vmcnt<3>(); break;
+        case 4: wait_vmcnt<4>(); break;
+        case 5: wait_vmcnt<5>(); break;
+        case 6: wait_vmcnt<6>(); break;
+        case 7: wait_vmcnt<7>(); break;
+        case 8: wait_vmcnt<8>(); break;
+        case 9: wait_vmcnt<9>(); break;
+        case 10: wait_vmcnt<10>(); break;
+        case 11: wait_vmcnt<11>(); break;
+        default: wait_vmcnt<12>(); break;
     }
 }
 
@@ -141,17 +133,12 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmParams p) {
     const int wr = wave >> 2, wc = wave & 3;             // waves w and w + 4 share a SIMD: one of each group per SIMD
     const int l31 = lane & 31, lh = lane >> 5;
 
-    // XCD-aware bijective workgroup -> tile map (n fastest inside an XCD's contiguous run)
-    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nwg = nbm * nbn;
-    const int bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int swz = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    const int bm = swz / nbn, bn = swz % nbn;
+    const TileAt at = tile_at<BM, BN>(blockIdx.x, p.M, p.N);
+    const int bm = at.bm, bn = at.bn, nbn = at.nbn;
 
     // ---- staging sources: a unit is 16 pieces of 1 KiB = 16 rows x 64 B each; wave w stages pieces w and w + 8 of every unit.
     // LDS-DMA writes lane-linear (lane l -> byte 16 l of the piece), so the bank swizzle is applied on the SOURCE chunk:
-    // chunk c of row r is stored at position c ^ ((r >> 2) & 3).
+    // chunk c of row r is stored at position c ^ ((r >> 2) & 3)  (gemm_tile.h: TileRows<64>, folded for pieces of 16 rows).
     const char* srcA[GPU_];
     const char* srcW[GPU_];
     {
@@ -200,23 +187,19 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmParams p) {
         if (p.packed & 16) {      // unit T covers rows 128 (T & 1) .. of the tile and the 128-byte k range T >> 1
 #pragma unroll
             for (int j = 0; j < GPU_; ++j)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (long)(T >> 1) * 128 + (long)(T & 1) * 128 * (unit ? p.ldw : p.lda) * ES),
-                                                 (__attribute__((address_space(3))) void*)(smem + slot * SLOT + unit * UNIT + (wave + 8 * j) * 1024), 16, 0, 0);
+                lds_dma16(src[j] + (long)(T >> 1) * 128 + (long)(T & 1) * 128 * (unit ? p.ldw : p.lda) * ES, smem + slot * SLOT + unit * UNIT + (wave + 8 * j) * 1024);
             return;
         }
 #endif
 #pragma unroll
         for (int j = 0; j < GPU_; ++j)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (long)T * RB),
-                                             (__attribute__((address_space(3))) void*)(smem + slot * SLOT + unit * UNIT + (wave + 8 * j) * 1024), 16, 0, 0);
+            lds_dma16(src[j] + (long)T * RB, smem + slot * SLOT + unit * UNIT + (wave + 8 * j) * 1024);
     };
     auto stage_one = [&](const char* const (&src)[GPU_], int unit, int T, int j) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[j] + (long)T * RB),
-                                         (__attribute__((address_space(3))) void*)(smem + (T % NB) * SLOT + unit * UNIT + (wave + 8 * j) * 1024), 16, 0, 0);
+        lds_dma16(src[j] + (long)T * RB, smem + (T % NB) * SLOT + unit * UNIT + (wave + 8 * j) * 1024);
     };
     auto stage_scales = [&](int T) {      // T even: the dwords of 128-k tile T / 2
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcS + (long)(T >> 1) * stepS),
-                                         (__attribute__((address_space(3))) void*)(smem + RING + ((T >> 1) % PP_SCALE_SLOTS) * PP_SCALE_BYTES + wave * 256), 4, 0, 0);
+        lds_dma4(srcS + (long)(T >> 1) * stepS, smem + RING + ((T >> 1) % PP_SCALE_SLOTS) * PP_SCALE_BYTES + wave * 256);
     };
     // vector-memory operations a wave issues for k tile T (W unit first, then -- MX, T even -- the scale piece, then the A unit)
     auto ops_of = [&](int T) { return 2 * GPU_ + ((MX && !(T & 1)) ? 1 : 0); };
@@ -258,14 +241,14 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmParams p) {
     const int a_row = (wr * WM + l31) * RB;                       // + i * 32 * RB per accumulator row block
     const int b_row = UNIT + (wc * WN + l31) * RB;                // + n * 32 * RB
 
-    pp_i32x4 af[2][2], bf[TN][2];                                   // [row block of the phase][chunk]
+    i32x4 af[2][2], bf[TN][2];                                   // [row block of the phase][chunk]
     int sa[2] = {0, 0}, sb[TN] = {0, 0};
     auto read_b = [&](int slot, int T) {
         const char* base = smem + slot * SLOT + b_row;
 #pragma unroll
         for (int n = 0; n < TN; ++n) {
-            bf[n][0] = *reinterpret_cast<const pp_i32x4*>(base + n * 32 * RB + c0);
-            bf[n][1] = *reinterpret_cast<const pp_i32x4*>(base + n * 32 * RB + c1);
+            bf[n][0] = *reinterpret_cast<const i32x4*>(base + n * 32 * RB + c0);
+            bf[n][1] = *reinterpret_cast<const i32x4*>(base + n * 32 * RB + c1);
         }
         if (MX) {
             const unsigned* Ss = reinterpret_cast<const unsigned*>(smem + RING + ((T >> 1) % PP_SCALE_SLOTS) * PP_SCALE_BYTES);
@@ -278,8 +261,8 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmParams p) {
         const char* base = smem + slot * SLOT + a_row + half * 64 * RB;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            af[i][0] = *reinterpret_cast<const pp_i32x4*>(base + i * 32 * RB + c0);
-            af[i][1] = *reinterpret_cast<const pp_i32x4*>(base + i * 32 * RB + c1);
+            af[i][0] = *reinterpret_cast<const i32x4*>(base + i * 32 * RB + c0);
+            af[i][1] = *reinterpret_cast<const i32x4*>(base + i * 32 * RB + c1);
         }
         if (MX) {
             const unsigned* Ss = reinterpret_cast<const unsigned*>(smem + RING + ((T >> 1) % PP_SCALE_SLOTS) * PP_SCALE_BYTES);
@@ -297,8 +280,8 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmParams p) {
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int n = 0; n < TN; ++n) {
-                    const pp_i32x8 a8 = __builtin_shufflevector(af[i][0], af[i][1], 0, 1, 2, 3, 4, 5, 6, 7);
-                    const pp_i32x8 b8 = __builtin_shufflevector(bf[n][0], bf[n][1], 0, 1, 2, 3, 4, 5, 6, 7);
+                    const i32x8 a8 = __builtin_shufflevector(af[i][0], af[i][1], 0, 1, 2, 3, 4, 5, 6, 7);
+                    const i32x8 b8 = __builtin_shufflevector(bf[n][0], bf[n][1], 0, 1, 2, 3, 4, 5, 6, 7);
                     acc[2 * half + i][n] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, acc[2 * half + i][n], 0, 0, 0, sa[i], 0, sb[n]);
                     if (i == 0) { __builtin_amdgcn_sched_barrier(0); mid(n); __builtin_amdgcn_sched_barrier(0); }
                 }
@@ -309,8 +292,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmParams p) {
                 for (int i = 0; i < 2; ++i) {
 #pragma unroll
                     for (int n = 0; n < TN; ++n)
-                        acc[2 * half + i][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(pp_bf16x8, af[i][kk]), __builtin_bit_cast(pp_bf16x8, bf[n][kk]),
-                                                                                      acc[2 * half + i][n], 0, 0, 0);
+                        acc[2 * half + i][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[i][kk]), __builtin_bit_cast(bf16x8, bf[n][kk]), acc[2 * half + i][n], 0, 0, 0);
                     if (kk == 0) { __builtin_amdgcn_sched_barrier(0); mid(i); __builtin_amdgcn_sched_barrier(0); }
                 }
         }

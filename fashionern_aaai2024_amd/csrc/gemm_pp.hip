@@ -15,7 +15,7 @@ static int pp_variant() {
 }
 
 hipError_t launch_gemm_pp(bool mx, const GemmParams& p, hipStream_t s) {
-    const int nb = ((p.M + PP_BM - 1) / PP_BM) * ((p.N + PP_BN - 1) / PP_BN);
+    const int nb = tile_blocks(PP_BM, PP_BN, p);
     const int var = pp_variant();
     if (mx && var == 1) FERN_LAUNCH((gemm_pp_kernel<true, 4, 1>), dim3(nb), dim3(512), 0, s, p);
     else if (mx) FERN_LAUNCH((gemm_pp_kernel<true, 4, 0>), dim3(nb), dim3(512), 0, s, p);

@@ -15,15 +15,13 @@
 // appends only the survivors (~K*R of N per query) to per-query candidate lists (kernels.h: TopkFilter, topk.hip).
 #include "kernels.h"
 #include "row_ops.h"
+#include "gemm_tile.h"
 
 #include <algorithm>
 #include <cstdlib>
 
 namespace fern {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16;
 
 __device__ __forceinline__ u16 f32_to_bf16_rne(float f) { return f32_to_bf16_bits(f); }      // round to nearest even (kernels.h)
@@ -73,8 +71,6 @@ constexpr int TAG_SLOT_BYTES = 256;
 constexpr int tail_bytes(int stages, bool mask) {
     return mask && 1024 + 4 * stages * TAG_SLOT_BYTES > QUEUE_BYTES ? 1024 + 4 * stages * TAG_SLOT_BYTES : QUEUE_BYTES;
 }
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // FILTER = false: the sample pass -- tile rows are the gallery rows sample_row(c, R) of S sample columns, scores are stored
 // ([B, ld], 128-byte coalesced).  FILTER = true: the full sweep -- nothing is stored; every finished 32x32 score tile is
@@ -263,16 +259,14 @@ __global__ __launch_bounds__(256) void sweep_bf16_kernel(const float* q, const u
         unsigned char* dst = ring + slot_issue * SLOT_BYTES;
         if (MASK && kc_issue == 0) {      // the tile's tags, in front of its first stage (rows past the end read the last row's tag: masked by n < N)
             const long n = t_issue * ROWS_T + l31;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(rt.tags + (n < N ? n : N - 1)),
-                                             (__attribute__((address_space(3))) void*)(tagring + tslot_issue * TAG_SLOT_BYTES), 4, 0, 0);
+            lds_dma4(rt.tags + (n < N ? n : N - 1), tagring + tslot_issue * TAG_SLOT_BYTES);
             tslot_issue = tslot_issue + 1 == STAGES ? 0 : tslot_issue + 1;
         }
         if ((FILTER || R == 1) && (t_issue + 1) * ROWS_T <= (FILTER ? N : S)) {      // whole tile of consecutive rows (the full sweep; the store-all form S = N, R = 1)
             const unsigned char* base = reinterpret_cast<const unsigned char*>(g) + (t_issue * ROWS_T * D + (long)kc_issue * KSTAGE) * 2;
 #pragma unroll
             for (int p = 0; p < 4; ++p)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + lane_off[p]),
-                                                 (__attribute__((address_space(3))) void*)(dst + p * 1024), 16, 0, 2);      // aux 2 = nt: every gallery byte is read once
+                lds_dma16_nt(base + lane_off[p], dst + p * 1024);      // nt: every gallery byte is read once
         } else {
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
@@ -282,8 +276,7 @@ __global__ __launch_bounds__(256) void sweep_bf16_kernel(const float* q, const u
                 n = n < N ? n : N - 1;
                 const int chunk = (lane & 7) ^ ((row >> 1) & 7);
                 const u16* src = g + n * D + kc_issue * KSTAGE + chunk * 8;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(dst + p * 1024), 16, 0, 2);
+                lds_dma16_nt(src, dst + p * 1024);
             }
         }
         if (++kc_issue == kchunks) { kc_issue = 0; t_issue += GW; }
@@ -374,7 +367,7 @@ __global__ __launch_bounds__(256) void sweep_bf16_kernel(const float* q, const u
                 default: wait_vmcnt<W0>(); break;
             }
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
         }
         const unsigned char* st = ring + slot_read * SLOT_BYTES;
         slot_read = slot_read + 1 == STAGES ? 0 : slot_read + 1;
