@@ -60,10 +60,13 @@ def compute_builds(eng):
     return _run(eng, "build_", BUILD_F32_SHAPES, BUILD_BF16_SHAPES, BUILD_MX_SHAPES, 1000)
 
 
-if __name__ == "__main__":
-    from fashionern_aaai2024_amd.engine import FernEngine
-    eng = FernEngine("cuda:0")
-    arrays = compute(eng)
+def _everything(eng):
+    arrays = dict(stream_switch=np.array([os.environ.get("FERN_ATTN_STREAM") == "1"]), **compute(eng))
     if sys.argv[1] == "--builds":
         arrays.update(compute_builds(eng))
-    np.savez(sys.argv[-1], stream_switch=np.array([os.environ.get("FERN_ATTN_STREAM") == "1"]), **arrays)
+    return arrays
+
+
+if __name__ == "__main__":
+    import _dump
+    _dump.main(_everything)

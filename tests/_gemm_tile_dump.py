@@ -16,27 +16,22 @@ tile does not divide K falls back by design (its arrays then repeat another conf
   topk_prepared.*    sim_topk on a PreparedGallery, B = 3, N = 1000, D = 64 (the bf16 sweep's DMA ring, then the rescoring)
   topk_f32.*         sim_topk on the fp32 tensor (EPI_TOPK_FILTER epilogue of glds_tile)
   rankof             rank_of on the fp32 tensor (EPI_RANK_COUNT epilogue)
-An array of up to 64 KiB is saved as its raw bytes, a larger one as its SHA-256 digest (32 bytes): all of them raw are gigabytes.
+An array of up to 64 KiB is saved as its raw bytes, a larger one as its SHA-256 digest (tests/_dump.py: raw): all of them raw are gigabytes.
+Two files are compared with `python tests/_dump.py diff`.
 """
-import hashlib
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import _dump  # noqa: E402
 import test_gpu_frames as F  # noqa: E402
 
 SHAPES = [(33, 65), (300, 520), (700, 800)]
 QUANT_SHAPES = [(33, 128), (300, 384), (700, 768)]
 KMULS = (1, 2, 3, 5)
 FORCED = dict(F.FORCED, f32x3=list(range(8)))      # f32x3: all of gemm_tuner.h's kCfgsS (kNumCfgsS = 8), as test_every_forced_f32x3_tile_honours_the_frame
-
-
-def _raw(t):
-    b = t.detach().cpu().contiguous().view(torch.uint8).numpy().reshape(-1)
-    return b.copy() if b.size <= 65536 else np.frombuffer(hashlib.sha256(b.tobytes()).digest(), dtype=np.uint8).copy()
 
 
 def _operands(eng, fam, M, N, K):
@@ -70,9 +65,9 @@ def _family(eng, out, family, fams):
                         c, sc = F._contiguous_call(eng, fam, o, M, N, K, epi, out_bf16, inplace)
                         name = f"{fam}_c{cfg}_{M}x{N}x{K}_e{epi}_b{int(out_bf16)}_i{int(inplace)}"
                         if sc is None:
-                            out[name] = _raw(c)
+                            out[name] = _dump.raw(c)
                         else:
-                            out[name + ".q"], out[name + ".s"] = _raw(c), _raw(sc)
+                            out[name + ".q"], out[name + ".s"] = _dump.raw(c), _dump.raw(sc)
     eng.tuner_force_config(family, -1)
 
 
@@ -87,24 +82,15 @@ def compute(eng):
     eng.set_precision("fp32")
 
     g = torch.Generator().manual_seed(11)
-    out["conv3x3"] = _raw(eng.conv3x3_nhwc(torch.randn(1, 5, 5, 32, generator=g), torch.randn(48, 9 * 32, generator=g) * 0.06, torch.randn(48, generator=g)))
+    out["conv3x3"] = _dump.raw(eng.conv3x3_nhwc(torch.randn(1, 5, 5, 32, generator=g), torch.randn(48, 9 * 32, generator=g) * 0.06, torch.randn(48, generator=g)))
     unit = lambda n, d: torch.nn.functional.normalize(torch.randn(n, d, generator=g), dim=-1)      # noqa: E731
     q, gal = unit(3, 64), unit(1000, 64)
     for name, gallery in (("topk_prepared", eng.prepare_gallery(gal.to(F.DEV))), ("topk_f32", gal)):
         s, i = eng.sim_topk(q, gallery, 50)[:2]
-        out[name + ".s"], out[name + ".i"] = _raw(s), _raw(i)
-    out["rankof"] = _raw(eng.rank_of(q, gal, torch.randint(0, 1000, (3, 16), generator=g).to(torch.int32)))
+        out[name + ".s"], out[name + ".i"] = _dump.raw(s), _dump.raw(i)
+    out["rankof"] = _dump.raw(eng.rank_of(q, gal, torch.randint(0, 1000, (3, 16), generator=g).to(torch.int32)))
     return out
 
 
-def main():
-    from fashionern_aaai2024_amd.engine import FernEngine
-    eng = FernEngine("cuda:0")
-    try:
-        np.savez(sys.argv[1], **compute(eng))
-    finally:
-        eng.close()
-
-
 if __name__ == "__main__":
-    main()
+    _dump.main(compute)

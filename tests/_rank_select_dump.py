@@ -59,17 +59,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-
-def _unit(n, d, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.nn.functional.normalize(torch.randn(n, d, generator=g), dim=-1)
+from support import unit  # noqa: E402
 
 
 def _ties(n, d, nt, seed):
     """(queries [3, d], gallery [n, d]): rows 0 .. nt - 1 are one row, and it is every query's best."""
-    gal = _unit(n, d, seed)
+    gal = unit(n, d, seed)
     gal[:nt] = gal[0]
-    q = torch.nn.functional.normalize(gal[0][None, :] + 0.1 * _unit(3, d, seed + 1), dim=-1)
+    q = torch.nn.functional.normalize(gal[0][None, :] + 0.1 * unit(3, d, seed + 1), dim=-1)
     return q, gal
 
 
@@ -101,7 +98,7 @@ def compute(eng, lists_only=False, deep_cap=False):
 
     if deep_cap:
         # ---- the radix fallback of the deep stage, with and without a ceiling ------------------------------------------------------
-        for tag, q, gal in [("equal", _unit(2, 64, 171), _unit(1, 64, 172).repeat(5000, 1)), ("random", _unit(3, 128, 173), _unit(1000, 128, 174))]:
+        for tag, q, gal in [("equal", unit(2, 64, 171), unit(1, 64, 172).repeat(5000, 1)), ("random", unit(3, 128, 173), unit(1000, 128, 174))]:
             first = eng.sim_topk_deep(q, gal, 100)
             put(f"deep_{tag}_exact", first)
             put(f"deep_{tag}_prefiltered", eng.sim_topk_deep(q, prepared(gal), 100))
@@ -118,21 +115,21 @@ def compute(eng, lists_only=False, deep_cap=False):
     eng.set_rank_strategy("lists")
     for b, n, d, k in [(3, 1000, 64, 50), (64, 9001, 640, 50), (3, 40, 64, 50), (4, 5000, 512, 1), (4, 5000, 128, 64)] + \
                       ([] if lists_only else [(2, 300_000, 64, 10), (2, 1_100_000, 64, 10)]):
-        q, gal = _unit(b, d, 10 + n), _unit(n, d, 20 + n)
+        q, gal = unit(b, d, 10 + n), unit(n, d, 20 + n)
         put(f"plain_{b}_{n}_{d}_{k}", eng.sim_topk(q, gal, k))
         if n <= 9001:
             put(f"bf16_{b}_{n}_{d}_{k}", eng.sim_topk_bf16(q, eng.gallery_to_bf16(gal.cuda()), k))
         if n <= 300_000:
             put(f"lists_{b}_{n}_{d}_{k}", eng.sim_topk(q, prepared(gal), k))
-    q, gal = _unit(5, 128, 31), _unit(3000, 128, 32)
+    q, gal = unit(5, 128, 31), unit(3000, 128, 32)
     put("plain_exclude", eng.sim_topk(q, gal, 10, exclude_idx=ex5))
     put("lists_exclude", eng.sim_topk(q, prepared(gal), 10, exclude_idx=ex5))
     put("lists_exclude_offset", eng.sim_topk(q, prepared(gal), 10, idx_offset=1000, exclude_idx=ex5 + 1000))
-    q, gal = _unit(2, 64, 33), _unit(1, 64, 34).repeat(1025, 1)
+    q, gal = unit(2, 64, 33), unit(1, 64, 34).repeat(1025, 1)
     put("plain_equal_1025", eng.sim_topk(q, gal, 50))
     put("bf16_equal_1025", eng.sim_topk_bf16(q, eng.gallery_to_bf16(gal.cuda()), 50))
     put("lists_equal_1025", eng.sim_topk(q, prepared(gal), 50))
-    q, gal = _unit(3, 64, 35), _unit(9001, 64, 36)
+    q, gal = unit(3, 64, 35), unit(9001, 64, 36)
     gal[4321] = float("nan")
     put("nan_lists", eng.sim_topk(q, prepared(gal), 10))
     if lists_only:
@@ -142,29 +139,29 @@ def compute(eng, lists_only=False, deep_cap=False):
     eng.set_rank_strategy("dense")
     for b, n, d, k in [(3, 40, 64, 10), (3, 40, 64, 50), (2, 7, 64, 10), (3, 1000, 64, 50), (3, 1000, 512, 1), (3, 1000, 640, 64), (3, 1001, 128, 50),
                        (3, 1003, 64, 50), (4, 16383, 64, 50), (65, 20000, 64, 50), (65, 40000, 64, 50), (65, 60000, 64, 50)]:
-        q, gal = _unit(b, d, 40 + n), _unit(n, d, 50 + n)
+        q, gal = unit(b, d, 40 + n), unit(n, d, 50 + n)
         put(f"dense_{b}_{n}_{d}_{k}", eng.sim_topk(q, prepared(gal), k))
-    q, gal = _unit(5, 64, 61), _unit(1003, 64, 62)
+    q, gal = unit(5, 64, 61), unit(1003, 64, 62)
     put("dense_exclude", eng.sim_topk(q, prepared(gal), 10, exclude_idx=torch.tensor([3, -1, 999, 1002, 1001], dtype=torch.int32)))
     # ---- dense: tile maxima -------------------------------------------------------------------------------------------------------
     for b, n, d, k in [(3, 16384, 64, 50), (64, 16411, 128, 50), (3, 16411, 64, 1), (3, 16411, 64, 64), (2, 262145, 64, 50)]:
-        q, gal = _unit(b, d, 70 + n), _unit(n, d, 80 + n)
+        q, gal = unit(b, d, 70 + n), unit(n, d, 80 + n)
         pg = prepared(gal)
         put(f"tiles_{b}_{n}_{d}_{k}", eng.sim_topk(q, pg, k))
         if b == 3 and k == 64:      # every query excludes its own best row
             best = eng.sim_topk(q, pg, 1)[1][:, 0].cpu()
             put(f"tiles_exclude_{n}", eng.sim_topk(q, pg, 50, exclude_idx=best))
     # ---- floods of ties -----------------------------------------------------------------------------------------------------------
-    q = _unit(3, 64, 91)
-    put("equal_1025", eng.sim_topk(q, prepared(_unit(1, 64, 92).repeat(1025, 1)), 50))
-    put("equal_65537", eng.sim_topk(q, prepared(_unit(1, 64, 92).repeat(65537, 1)), 50))
-    put("equal_65537_gated", eng.sim_topk(_unit(3, 512, 93), prepared(_unit(1, 512, 94).repeat(65537, 1)), 50))
+    q = unit(3, 64, 91)
+    put("equal_1025", eng.sim_topk(q, prepared(unit(1, 64, 92).repeat(1025, 1)), 50))
+    put("equal_65537", eng.sim_topk(q, prepared(unit(1, 64, 92).repeat(65537, 1)), 50))
+    put("equal_65537_gated", eng.sim_topk(unit(3, 512, 93), prepared(unit(1, 512, 94).repeat(65537, 1)), 50))
     for n, d, nt in [(9000, 64, 2000), (9000, 64, 5000), (20000, 64, 2000), (20000, 64, 5000), (70000, 512, 2000)]:
         q, gal = _ties(n, d, nt, 100 + nt)
         put(f"ties_{n}_{d}_{nt}", eng.sim_topk(q, prepared(gal), 10))
     # ---- row filters --------------------------------------------------------------------------------------------------------------
     for n in (1000, 16411):
-        q, gal = _unit(4, 64, 110 + n), _unit(n, 64, 120 + n)
+        q, gal = unit(4, 64, 110 + n), unit(n, 64, 120 + n)
         tags = torch.arange(n, dtype=torch.int32) % 7
         filt = RowFilter(tags, mask=torch.tensor([0xFF, 0xFF, 0, 0xFF], dtype=torch.int32), value=torch.tensor([3, 5, 0, 9], dtype=torch.int32))
         put(f"filt_{n}", eng.sim_topk(q, prepared(gal), 50, row_filter=filt))
@@ -174,7 +171,7 @@ def compute(eng, lists_only=False, deep_cap=False):
             put("filt_deep_exact", eng.sim_topk_deep(q, gal, 100, row_filter=filt))
     # ---- a NaN row ----------------------------------------------------------------------------------------------------------------
     for n in (1000, 20000):
-        q, gal = _unit(3, 64, 130 + n), _unit(n, 64, 140 + n)
+        q, gal = unit(3, 64, 130 + n), unit(n, 64, 140 + n)
         gal[n // 3] = float("nan")
         put(f"nan_dense_{n}", eng.sim_topk(q, prepared(gal), 10))
         if n == 1000:
@@ -182,7 +179,7 @@ def compute(eng, lists_only=False, deep_cap=False):
     # ---- deep ranking -------------------------------------------------------------------------------------------------------------
     eng.set_rank_strategy("auto")
     for b, n, d, k in [(3, 1000, 128, 1024), (2, 70000, 768, 100)]:
-        q, gal = _unit(b, d, 150 + n), _unit(n, d, 160 + n)
+        q, gal = unit(b, d, 150 + n), unit(n, d, 160 + n)
         put(f"deep_exact_{b}_{n}_{d}_{k}", eng.sim_topk_deep(q, gal, k))
         put(f"deep_prefiltered_{b}_{n}_{d}_{k}", eng.sim_topk_deep(q, prepared(gal), k))
         if n == 1000:
@@ -191,19 +188,19 @@ def compute(eng, lists_only=False, deep_cap=False):
             first = eng.sim_topk_deep(q, gal, 100)
             put("deep_cursor_page", eng.sim_topk_from(q, gal, 100, next_from(*first)))
             put("deep_offset_page", eng.rank_page(q, gal, 37, 100))
-    q, gal = _unit(2, 64, 171), _unit(1, 64, 172).repeat(5000, 1)
+    q, gal = unit(2, 64, 171), unit(1, 64, 172).repeat(5000, 1)
     put("deep_equal_exact", eng.sim_topk_deep(q, gal, 100))
     put("deep_equal_prefiltered", eng.sim_topk_deep(q, prepared(gal), 100))
     # ---- merges of ranked lists ---------------------------------------------------------------------------------------------------
     for k in (10, 100):
-        q = _unit(4, 64, 180 + k)
-        parts = [eng.sim_topk_deep(q, _unit(60 + 50 * r, 64, 190 + r), k, idx_offset=1000 * r) for r in range(3)]      # 60 rows < K = 100: -1 slots
+        q = unit(4, 64, 180 + k)
+        parts = [eng.sim_topk_deep(q, unit(60 + 50 * r, 64, 190 + r), k, idx_offset=1000 * r) for r in range(3)]      # 60 rows < K = 100: -1 slots
         put(f"merge_{k}", eng.topk_merge(torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts])))
     # ---- exact target ranks ---------------------------------------------------------------------------------------------------------
     gen = torch.Generator().manual_seed(300)
     # (the engine takes D % 32 == 0 for fp32 rows and D % 64 == 0 for bf16 rows: D = 288 is the smallest second, partial 256-k step)
     for b, n, d in [(3, 1000, 64), (2, 300, 288), (2, 300, 320)]:
-        q, gal = _unit(b, d, 200 + n + d), _unit(n, d, 210 + n + d)
+        q, gal = unit(b, d, 200 + n + d), unit(n, d, 210 + n + d)
         tags = torch.arange(n, dtype=torch.int32) % 7
         filt = RowFilter(tags, mask=torch.tensor([0xFF, 0, 0xFF][:b], dtype=torch.int32), value=torch.tensor([3, 0, 5][:b], dtype=torch.int32))
         ex = torch.tensor([3, -1, 7][:b], dtype=torch.int32)
@@ -218,7 +215,7 @@ def compute(eng, lists_only=False, deep_cap=False):
                 puti(f"rankof_{form}_{n}_{d}_{m}_filt", eng.rank_of(q, g, tg, exclude_idx=ex, row_filter=filt))
     # ---- items ----------------------------------------------------------------------------------------------------------------------
     for n, shift in [(1030, 0), (1027, 1)]:
-        q, gal = _unit(3, 64, 220 + n), _unit(n, 64, 230 + n)
+        q, gal = unit(3, 64, 220 + n), unit(n, 64, 230 + n)
         ids, G = _item_ids(n)
         ids[10], ids[500] = -1, G + 5                                                       # rows of no item
         buf = torch.cat([torch.zeros(shift, dtype=torch.int32), ids]).cuda()
@@ -236,8 +233,8 @@ def compute(eng, lists_only=False, deep_cap=False):
             put(f"items_{form}_{n}_filt_offset", eng.sim_topk_items(q, g, items, 10, idx_offset=1000, exclude_idx=best + 1000, row_filter=filt))
             puti(f"items_{form}_{n}_filt_offset_rank", eng.item_rank_of(q, g, items, tg, idx_offset=1000, exclude_idx=best + 1000, row_filter=filt))
     # ---- pages: the row at a place ----------------------------------------------------------------------------------------------------
-    q = _unit(3, 64, 240)
-    for tag, gal in [("random_3000", _unit(3000, 64, 241)), ("equal_3000", _unit(1, 64, 242).repeat(3000, 1)), ("one_row", _unit(1, 64, 243))]:
+    q = unit(3, 64, 240)
+    for tag, gal in [("random_3000", unit(3000, 64, 241)), ("equal_3000", unit(1, 64, 242).repeat(3000, 1)), ("one_row", unit(1, 64, 243))]:
         n = gal.shape[0]
         places = torch.tensor([[0, -1, n - 1, n, 5, 100, n // 2, n - 2]] * 3, dtype=torch.int32)      # the last row, one past the rows
         puti(f"select_{tag}", eng.rank_select(q, gal, places))
@@ -248,7 +245,7 @@ def compute(eng, lists_only=False, deep_cap=False):
     filt = RowFilter(tags, mask=torch.tensor([0xFF, 0, 0xFF], dtype=torch.int32), value=torch.tensor([3, 0, 5], dtype=torch.int32))
     ex = torch.tensor([3, -1, 7], dtype=torch.int32)
     for form, d in [("ring", 64), ("lane", 96), ("bf16", 64)]:
-        q, gal = _unit(3, d, 250 + d), _unit(n, d, 260 + d)
+        q, gal = unit(3, d, 250 + d), unit(n, d, 260 + d)
         g = eng.gallery_to_bf16(gal.cuda()) if form == "bf16" else gal
         for m in (1, 33, 600):
             cd = torch.randint(0, n, (3, m), generator=gen, dtype=torch.int32)
@@ -265,9 +262,5 @@ def compute(eng, lists_only=False, deep_cap=False):
 
 
 if __name__ == "__main__":
-    from fashionern_aaai2024_amd.engine import FernEngine
-    eng = FernEngine("cuda:0")
-    arrays = compute(eng, lists_only="FERN_RANK_CAP" in os.environ, deep_cap="FERN_RANK_DEEP_CAP" in os.environ)
-    torch.cuda.synchronize()
-    np.savez(sys.argv[-1], **arrays)
-    print(f"{len(arrays)} arrays -> {sys.argv[-1]}")
+    import _dump
+    _dump.main(lambda eng: compute(eng, lists_only="FERN_RANK_CAP" in os.environ, deep_cap="FERN_RANK_DEEP_CAP" in os.environ))

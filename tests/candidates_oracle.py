@@ -2,7 +2,7 @@
 TEST INFRASTRUCTURE.
 
 ``candidates_oracle()`` returns the rank oracle over ``oracle.chain.chain_scores`` (tests/rank_oracle.py: ``CandidatesOracle``; the fp32
-chain of oracle/chain.c), whose ``sim_topk_candidates`` orders by ``_make_keys`` (score descending, global index ascending as one
+chain of oracle/chain.c), whose ``sim_topk_candidates`` orders by ``make_keys`` (score descending, global index ascending as one
 unsigned compare).  The set semantics are restated here in a few lines of numpy:
 
     query b ranks the SET of rows named by candidates[b]; an entry takes no place if it is negative, outside [idx_offset, idx_offset + N),

@@ -7,12 +7,9 @@ quantised ones for the reduced families); `epi_ref` applies the epilogue."""
 import torch
 import torch.nn.functional as F
 
+from support import close, rand  # noqa: F401  (the shared inputs and the fp32 kernels' bound: re-exported, the families below use them)
+
 EPI_BIAS, EPI_GELU, EPI_RELU, EPI_RESIDUAL, EPI_QUICKGELU = 0, 1, 2, 3, 4
-
-
-def rand(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
 
 
 def epi_ref(base, epi, r=None):
@@ -26,13 +23,6 @@ def epi_ref(base, epi, r=None):
     if epi == EPI_QUICKGELU:
         return base * torch.sigmoid(1.702 * base)
     return base
-
-
-def close(got, ref, rel=2e-5):
-    """The fp32 kernels' bound: max abs error <= rel x the largest reference magnitude."""
-    got, ref = got.detach().cpu().double(), ref.double()
-    err = (got - ref).abs().max().item()
-    assert err <= rel * max(ref.abs().max().item(), 1e-6), f"max abs err {err} vs scale {ref.abs().max().item()}"
 
 
 # ---- fp32 ------------------------------------------------------------------------------------------------------------------------
@@ -92,6 +82,19 @@ def fp8_case(engine, m, n, k, epi):
 def mx_scales_by_block(sc):
     """engine.quantize_mx8's [D/128, R, 4] scale array -> [R, D/32] (block b = k // 32)."""
     return sc.permute(1, 0, 2).reshape(sc.shape[1], -1)
+
+
+def e8m0_byte(m):
+    """E8M0 scale byte of fp32 block maxima, as the kernels compute it (csrc/kernels.h: mx_scale_byte): the exponent that brings the
+    maximum under 448, one more past the 0x600000 mantissa (1.75 x 2^e > 448 x 2^(e-8)), clamped to [1, 253]."""
+    u = m.float().contiguous().view(torch.int32)
+    return ((u >> 23) - 8 + ((u & 0x7FFFFF) > 0x600000).int()).clamp(1, 253)
+
+
+def e4m3_code(v):
+    """e4m3fn bytes of fp32 values (round to nearest even) as int, and their signed position on the code line."""
+    b = v.float().to(torch.float8_e4m3fn).view(torch.uint8).int()
+    return b, torch.where(b >= 128, -(b & 0x7F), b)
 
 
 def mx8_case(engine, m, n, k, epi):

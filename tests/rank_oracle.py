@@ -6,7 +6,7 @@
 * a row leaves a ranking in one place, ``oracle.rank.masked_scores``: the excluded row and the rows that are not ``eligible`` under the
   ``RowFilter`` score -inf;
 * the order is score descending, global index ascending -- a stable sort of the masked scores (``oracle.rank.cosine_topk``), or one
-  unsigned compare of the 64-bit ranking keys (``_make_keys``);
+  unsigned compare of the 64-bit ranking keys (``make_keys``);
 * the item and candidate semantics are the free functions of tests/items_oracle.py and tests/candidates_oracle.py.
 
 ``CandidatesOracle`` is the same protocol over ``oracle.chain.chain_scores`` (the fp32 chain of oracle/chain.c) wherever the protocol
@@ -27,14 +27,14 @@ from oracle_engine import OracleEngine
 from fashionern_aaai2024_amd.engine import RowFilter
 
 
-def _orderable(s):
+def orderable(s):
     u = np.ascontiguousarray(s, dtype=np.float32).view(np.uint32)
     return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
 
 
-def _make_keys(scores, idx):
+def make_keys(scores, idx):
     """include/fern.h's ranking key: orderable(score) << 32 | ~global index, as uint64."""
-    return (_orderable(scores).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - idx.astype(np.uint64))
+    return (orderable(scores).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - idx.astype(np.uint64))
 
 
 def eligible(row_filter, b: int, n: int) -> torch.Tensor:
@@ -67,7 +67,7 @@ class RankOracle(OracleEngine):
     def _row_keys(self, q, gallery, idx_offset, exclude_idx, row_filter):
         """(masked scores, uint64 [B, N] key of every row): 0 for a row that takes no place."""
         m = self._masked(q, gallery, idx_offset, exclude_idx, row_filter)
-        keys = _make_keys(m, np.broadcast_to(np.arange(m.shape[1]) + idx_offset, m.shape))
+        keys = make_keys(m, np.broadcast_to(np.arange(m.shape[1]) + idx_offset, m.shape))
         return m, np.where(m == -np.inf, np.uint64(0), keys)
 
     # ---- K lists -----------------------------------------------------------------------------------------------------------------
@@ -99,7 +99,7 @@ class RankOracle(OracleEngine):
         local = t - idx_offset
         ok = (t >= 0) & (local >= 0) & (local < s.shape[1])
         ts = np.take_along_axis(s, np.where(ok, local, 0), axis=1) if s.shape[1] else np.zeros(t.shape, dtype=np.float32)
-        keys = np.where(ok, _make_keys(ts, np.where(ok, t, 0)), np.uint64(0))
+        keys = np.where(ok, make_keys(ts, np.where(ok, t, 0)), np.uint64(0))
         return torch.from_numpy(keys.view(np.int64).copy())
 
     def rank_count(self, q, gallery, keys, idx_offset=0, exclude_idx=None, row_filter=None):
@@ -143,7 +143,7 @@ class RankOracle(OracleEngine):
         m, ids = self._item_masked(q, gallery, items, idx_offset, exclude_idx, row_filter)
         best = np.zeros((m.shape[0], items.n_items), dtype=np.uint64)
         for r, (rows, its) in enumerate(item_lists(m, ids, items.n_items)):
-            best[r, its] = _make_keys(m[r, rows], rows + idx_offset)
+            best[r, its] = make_keys(m[r, rows], rows + idx_offset)
         return best
 
     def item_keys(self, q, gallery, items, target_items, idx_offset=0, exclude_idx=None, row_filter=None):
@@ -163,7 +163,7 @@ class RankOracle(OracleEngine):
     def sim_topk_candidates(self, q, gallery, candidates, k, idx_offset=0, exclude_idx=None, row_filter=None, places=False):
         s = self._scores(q, gallery)
         cand = np.asarray(torch.as_tensor(candidates).cpu().numpy(), dtype=np.int64)
-        out_s, out_i, place = rank_candidates(s, cand, k, idx_offset, *self._masks(s.shape, exclude_idx, row_filter), _make_keys)
+        out_s, out_i, place = rank_candidates(s, cand, k, idx_offset, *self._masks(s.shape, exclude_idx, row_filter), make_keys)
         out = (torch.from_numpy(out_s), torch.from_numpy(out_i))
         return out + (torch.from_numpy(place),) if places else out
 

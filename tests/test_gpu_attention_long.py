@@ -9,33 +9,14 @@ import numpy as np
 import pytest
 import torch
 
+from gemm_refs import attn_ref, e4m3_code, e8m0_byte, mx_scales_by_block
 from oracle.clip import mx8_dequantize
+from support import close, rand
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = 0xA5
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def _close(got, ref, rel=2e-5):
-    got, ref = got.detach().cpu().double(), ref.double()
-    err = (got - ref).abs().max().item()
-    print(f"max abs err {err:.3e} vs scale {ref.abs().max().item():.3e} (bound {rel * max(ref.abs().max().item(), 1e-6):.3e})")
-    assert err <= rel * max(ref.abs().max().item(), 1e-6), f"max abs err {err} vs scale {ref.abs().max().item()}"
-
-
-def _attn_ref(q, k, v, heads, scale):
-    b, sq, w = q.shape
-    sk, hd = k.shape[1], w // heads
-    qh = q.double().view(b, sq, heads, hd).transpose(1, 2) * scale
-    kh = k.double().view(b, sk, heads, hd).transpose(1, 2)
-    vh = v.double().view(b, sk, heads, hd).transpose(1, 2)
-    return (torch.softmax(qh @ kh.transpose(-1, -2), -1) @ vh).transpose(1, 2).reshape(b, sq, w)
 
 
 LONG_CASES = [  # batch, heads, hd, s_q, s_k (non-causal)
@@ -46,9 +27,9 @@ LONG_CASES = [  # batch, heads, hd, s_q, s_k (non-causal)
 @pytest.mark.parametrize("b,heads,hd,sq,sk", LONG_CASES)
 def test_attention_long(engine, b, heads, hd, sq, sk):
     w = heads * hd
-    q, k, v = _rand(b, sq, w, seed=1), _rand(b, sk, w, seed=2), _rand(b, sk, w, seed=3)
+    q, k, v = rand(b, sq, w, seed=1), rand(b, sk, w, seed=2), rand(b, sk, w, seed=3)
     scale = hd ** -0.5
-    _close(engine.attention(q, k, v, heads, scale=scale), _attn_ref(q, k, v, heads, scale), rel=2e-5)
+    close(engine.attention(q, k, v, heads, scale=scale), attn_ref(q, k, v, heads, False, scale), rel=2e-5)
 
 
 def test_attention_long_sharp_softmax(engine):
@@ -56,10 +37,10 @@ def test_attention_long_sharp_softmax(engine):
     staged chunks -- one spike in the first chunk, one in the last."""
     b, heads, hd, s = 1, 2, 64, 577
     w = heads * hd
-    q, k, v = _rand(b, s, w, seed=4), _rand(b, s, w, seed=5), _rand(b, s, w, seed=6)
+    q, k, v = rand(b, s, w, seed=4), rand(b, s, w, seed=5), rand(b, s, w, seed=6)
     k[:, 570] = q[:, 5] * 4.0          # query 5 sees a huge score at key 570 (the last chunk) after small ones
     k[:, 3] = q[:, 400] * 4.0          # and query 400 at key 3 (the first chunk)
-    _close(engine.attention(q, k, v, heads, scale=1.0), _attn_ref(q, k, v, heads, 1.0), rel=5e-5)
+    close(engine.attention(q, k, v, heads, scale=1.0), attn_ref(q, k, v, heads, False, 1.0), rel=5e-5)
 
 
 def test_attention_refuses_more_than_4096_keys(engine):
@@ -80,20 +61,10 @@ def test_attention_bf16_long(engine, b, heads, hd, sq, sk):
     q, k, v = (torch.randn(b, s, w, generator=g).bfloat16() for s in (sq, sk, sk))
     got = engine.attention_bf16(q.cuda(), k.cuda(), v.cuda(), heads)
     assert got.dtype == torch.bfloat16
-    ref = _attn_ref(q, k, v, heads, hd ** -0.5)
+    ref = attn_ref(q, k, v, heads, False, hd ** -0.5)
     err = (got.float().cpu().double() - ref).abs().max().item()
     print(f"bf16 attention err {err:.3e} (bound {2 ** -7 * max(1.0, ref.abs().max().item()):.3e})")
     assert err < 2 ** -7 * max(1.0, ref.abs().max().item()), err
-
-
-def _e8(m):
-    u = m.float().contiguous().view(torch.int32)
-    return ((u >> 23) - 8 + ((u & 0x7FFFFF) > 0x600000).int()).clamp(1, 253)
-
-
-def _code(v):
-    b = v.float().to(torch.float8_e4m3fn).view(torch.uint8).int()
-    return b, torch.where(b >= 128, -(b & 0x7F), b)
 
 
 @pytest.mark.parametrize("b,heads,hd,s", [(2, 16, 64, 257), (1, 4, 32, 577)])
@@ -116,21 +87,21 @@ def test_attention_mx8_output_long(engine, b, heads, hd, s):
     y8 = y8[:, :w].int()
     sc = sc.cpu()
     assert (sc[:, rows:] == SENTINEL).all(), "scale bytes beyond `rows` were written"
-    e = sc[:, :rows].permute(1, 0, 2).reshape(rows, -1).int()
+    e = mx_scales_by_block(sc[:, :rows]).int()
     # (a) consistency with the bf16 output of the same kernel
     nb = w // 32
     bb = yb.double().reshape(rows, nb, 32)
     half = lambda t: torch.ldexp(torch.ones((), dtype=torch.float64), torch.frexp(t.float())[1] - 9)   # half a bf16 ulp of |t|
     m = bb.abs().amax(-1)
-    e_lo, e_hi = _e8(m - half(m)), _e8(m + half(m))
+    e_lo, e_hi = e8m0_byte(m - half(m)), e8m0_byte(m + half(m))
     sure = e_lo == e_hi
-    assert torch.equal(e[sure], _e8(m)[sure]), "scale byte differs from the bf16 output's block maximum"
+    assert torch.equal(e[sure], e8m0_byte(m)[sure]), "scale byte differs from the bf16 output's block maximum"
     assert ((e >= e_lo) & (e <= e_hi)).all()
     scl = torch.ldexp(torch.ones((), dtype=torch.float64), 127 - e).unsqueeze(-1)
     hb = half(bb.abs())
-    c_ref, _ = _code(bb * scl)
-    c_lo, o_lo = _code((bb - hb) * scl)
-    c_hi, o_hi = _code((bb + hb) * scl)
+    c_ref, _ = e4m3_code(bb * scl)
+    c_lo, o_lo = e4m3_code((bb - hb) * scl)
+    c_hi, o_hi = e4m3_code((bb + hb) * scl)
     got = y8.reshape(rows, nb, 32)
     o_got = torch.where(got >= 128, -(got & 0x7F), got)
     excused = c_lo != c_hi
@@ -140,7 +111,7 @@ def test_attention_mx8_output_long(engine, b, heads, hd, s):
     print(f"attention mx8 b={b} heads={heads} hd={hd} s={s}: excused fraction {frac:.3%}")
     assert frac < 0.05
     # (b) against fp64 attention on the same bf16 operands
-    ref = _attn_ref(q, k, v, heads, hd ** -0.5).reshape(rows, w)
+    ref = attn_ref(q, k, v, heads, False, hd ** -0.5).reshape(rows, w)
     dq = mx8_dequantize(y8.to(torch.uint8).view(torch.float8_e4m3fn), e.to(torch.uint8), torch.float64)
     step = 2.0 ** -4 * torch.maximum(dq.abs(), ref.abs()) + torch.ldexp(torch.ones((), dtype=torch.float64), e - 137).repeat_interleave(32, -1)
     budget = 2 ** -7 * max(1.0, ref.abs().max().item())

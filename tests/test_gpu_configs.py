@@ -23,18 +23,13 @@ from oracle import chain
 from oracle import fusion as ofusion
 from oracle import rank as orank
 
+import support as S
+
 pytestmark = pytest.mark.gpu
-_cache = {}
 
 
 def fused_engine(d):
-    if d not in _cache:
-        eng = FernEngine("cuda:0")
-        sd = synth.fusion_state_dict(d, seed=21)
-        eng.load_tensors(sd)
-        eng.finalize_fusion(d)
-        _cache[d] = (eng, ofusion.as_torch(sd))
-    return _cache[d]
+    return S.fusion_engine(d, seed=21)
 
 
 def unit(n, d, tag):
@@ -44,14 +39,8 @@ def unit(n, d, tag):
 def assert_same_order_up_to_near_ties(q, g, idx, ref_idx, gap=2e-6):
     """The torch oracle sums in BLAS order, the HIP sweep in its own fixed order: the two rankings may differ only where the
     oracle's own fp64-checked scores of the swapped rows are closer than fp32 rounding (`gap`)."""
-    bad = (idx != ref_idx).nonzero().tolist()
-    if not bad:
-        return
-    rows = sorted({r for r, _ in bad})
-    full = {r: (q[r].double() @ g.double().T) for r in rows}
-    for r, p in bad:
-        d = abs(full[r][idx[r, p]].item() - full[r][ref_idx[r, p]].item())
-        assert d < gap, f"query {r} rank {p}: rows {idx[r, p].item()} / {ref_idx[r, p].item()} differ by {d:.3e} in score"
+    rows = sorted(set((idx != ref_idx).nonzero()[:, 0].tolist()))
+    S.assert_same_order_up_to_near_ties({r: q[r].double() @ g.double().T for r in rows}, idx, ref_idx, gap)
 
 
 def check_sorted_and_consistent(eng, q, g, s, i):
@@ -85,8 +74,7 @@ def test_c1_rn50x4_shape_fusion_and_rank(precision):
     rs, ri = orank.cosine_topk(qr, ref, 50)
     assert (s.cpu() - rs).abs().max().item() < 1e-3
     full = qr @ ref.T
-    for row, col in zip(*np.nonzero((i.cpu() != ri).numpy())):       # only near-ties of the oracle itself may swap
-        assert abs(full[row, i[row, col].item()].item() - full[row, ri[row, col]].item()) < 1e-5
+    S.assert_same_order_up_to_near_ties(full, i, ri, gap=1e-5)       # only near-ties of the oracle itself may swap
     ps, pi = eng.sim_topk(q, eng.prepare_gallery(gal), 50)           # the prepared form (bf16 pre-filter + exact rescoring): same bits
     assert torch.equal(ps, s) and torch.equal(pi, i)
     eng.set_precision("fp32")
@@ -186,8 +174,7 @@ def test_c5_one_million_row_gallery():
     rs, ri = orank.cosine_topk(q[:4].cpu(), g.cpu(), 50)
     assert (s[:4].cpu() - rs).abs().max().item() < 1e-4
     full = q[:4].cpu() @ g.cpu().T
-    for row, col in zip(*np.nonzero((i[:4].cpu() != ri).numpy())):
-        assert abs(full[row, i[row, col].item()].item() - full[row, ri[row, col]].item()) < 1e-5
+    S.assert_same_order_up_to_near_ties(full, i[:4], ri, gap=1e-5)
     # sharded over 8 "ranks" with offsets
     per = n // 8
     parts = [eng.sim_topk(q, g[r * per:(r + 1) * per], 50, idx_offset=r * per) for r in range(8)]
@@ -323,8 +310,7 @@ def test_bf16_gallery_sweep(b, n, d):
     kk = min(50, n)
     assert (s.cpu()[:, :kk] - rs[:, :kk]).abs().max().item() < 2e-6          # same operands: only the fp32 summation order differs
     full = q.bfloat16().float() @ g.bfloat16().float().T
-    for row, col in zip(*np.nonzero((i.cpu() != ri).numpy())):
-        assert abs(full[row, i[row, col].item()].item() - full[row, ri[row, col]].item()) < 2e-6
+    S.assert_same_order_up_to_near_ties(full, i, ri, gap=2e-6)
     fs, fi = orank.cosine_topk(q, g, 50)                                       # vs fp32 truth: north_star's 1e-3 at the path's widths
     assert (s.cpu()[:, :kk] - fs[:, :kk]).abs().max().item() < (1e-3 if d >= 512 else 4e-3)
 
@@ -418,8 +404,7 @@ def test_c5_fp8_encoder_with_bf16_similarity_end_to_end(precision):
     rs, ri = _bf16_ref(fused.cpu(), gb.float().cpu(), 50)
     assert (s.cpu() - rs).abs().max().item() < 2e-6
     full = fused.cpu().bfloat16().float() @ gb.float().cpu().T
-    for row, col in zip(*np.nonzero((i.cpu() != ri).numpy())):
-        assert abs(full[row, i[row, col].item()].item() - full[row, ri[row, col]].item()) < 2e-6
+    S.assert_same_order_up_to_near_ties(full, i, ri, gap=2e-6)
     eng.close()
 
 

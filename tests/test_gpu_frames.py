@@ -11,35 +11,18 @@ other byte is a known pattern -- 0xA5 around outputs, NaN (fp32 / bf16 / e4m3fn)
       that a failure names its cause).
 No case had to fall back from (a) to a reference comparison.  Nothing here can reach unmapped memory: every band is 256 rows of ld
 elements, one full workgroup tile of the largest configuration."""
-import ctypes as C
 
 import pytest
 import torch
 
 import gemm_refs as R
 from framed import E8M0_HUGE, FP8_NAN, NAN, SENTINEL, Framed, framed_like, framed_vec
+from support import assert_same_bits, ptr, unit
 from fashionern_aaai2024_amd import _lib
 from fashionern_aaai2024_amd.engine import _stream
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def _p(x, byte_offset=0):
-    """Device pointer of a Framed view / tensor (None stays NULL)."""
-    return None if x is None else C.c_void_p(x.data_ptr() + byte_offset)
-
-
-def _bits(t):
-    """Compare bits, not floats (NaN == NaN, -0.0 != 0.0)."""
-    return t.view({4: torch.int32, 2: torch.int16, 1: torch.uint8}[t.element_size()]) if t.is_floating_point() else t
-
-
-def _same_bits(got, ref, what):
-    assert got.shape == ref.shape and got.dtype == ref.dtype, what
-    if not torch.equal(_bits(got), _bits(ref)):
-        diff = (_bits(got) != _bits(ref)).nonzero()
-        raise AssertionError(f"{what}: {len(diff)} element(s) differ from the contiguous call, the first at {tuple(diff[0].tolist())}")
 
 
 def _moat(t):
@@ -107,8 +90,8 @@ def _contiguous_call(engine, fam, o, M, N, K, epi, out_bf16, inplace):
     if inplace:
         resid = c
     sc = torch.empty(N // 128, M, 4, dtype=torch.uint8, device=DEV) if fam == "mx8q" else None
-    _launch(engine, fam, M, N, K, epi, out_bf16, _p(o["a"]), K, _p(o["w"]), K, _p(o["b"]), _p(resid), _p(c), N,
-            _p(o["sa"]), M, _p(o["sw"]), N, _p(sc), M)
+    _launch(engine, fam, M, N, K, epi, out_bf16, ptr(o["a"]), K, ptr(o["w"]), K, ptr(o["b"]), ptr(resid), ptr(c), N,
+            ptr(o["sa"]), M, ptr(o["sw"]), N, ptr(sc), M)
     torch.cuda.synchronize()
     return c, sc
 
@@ -142,8 +125,8 @@ def _framed_call(engine, fam, o, M, N, K, epi, out_bf16, inplace, gap_mul=1):
         if epi == 3:
             resid = framed_like(o["r"], ldc, NAN)
             frames_in.append(("residual", resid))
-    _launch(engine, fam, M, N, K, epi, out_bf16, _p(fa), lda, _p(fw), ldw, _p(fb), _p(resid), _p(fc), ldc,
-            _p(fsa), sra, _p(fsw), srw, _p(fsc), src)
+    _launch(engine, fam, M, N, K, epi, out_bf16, ptr(fa), lda, ptr(fw), ldw, ptr(fb), ptr(resid), ptr(fc), ldc,
+            ptr(fsa), sra, ptr(fsw), srw, ptr(fsc), src)
     torch.cuda.synchronize()
     what = f"{fam} M={M} N={N} K={K} epi={epi} out_bf16={out_bf16} inplace={inplace} lda={lda} ldc={ldc}"
     fc.assert_intact(f"C of {what}")
@@ -194,9 +177,9 @@ def _walk(engine, fam, M, N, K, gap_mul=1, reference=True, base=None):
         else:
             ref_c, ref_s = base[(epi, out_bf16, inplace)]
         got, sc, what = _framed_call(engine, fam, o, M, N, K, epi, out_bf16, inplace, gap_mul)
-        _same_bits(got, ref_c, what)                                                         # (a)
+        assert_same_bits(got, ref_c, what)                                                         # (a)
         if sc is not None:
-            _same_bits(sc, ref_s, "scales_c of " + what)
+            assert_same_bits(sc, ref_s, "scales_c of " + what)
         _assert_finite(fam, got, sc, what)                                                   # (d)
         if reference and fam != "f32x3":
             _check_reference(engine, fam, o, ref_c, ref_s, M, N, K, epi, out_bf16)           # (b)
@@ -374,17 +357,17 @@ def test_attention_frames(engine, b, heads, hd, sq, sk, causal, bf16):
     if sq == sk:
         ld = 3 * w + gap
         packed = Framed(b * sq, 3 * w, ld, dt, NAN, DEV).load(torch.cat([q, k, v], -1))
-        ptrs = [(_p(packed, i * w * es), ld) for i in range(3)]
+        ptrs = [(ptr(packed, i * w * es), ld) for i in range(3)]
         frames = [("packed QKV", packed)]
     else:
         fq = Framed(b * sq, w, w + gap, dt, NAN, DEV).load(q)
         fkv = Framed(b * sk, 2 * w, 2 * w + 2 * gap, dt, NAN, DEV).load(torch.cat([k, v], -1))
-        ptrs = [(_p(fq), w + gap), (_p(fkv), 2 * w + 2 * gap), (_p(fkv, w * es), 2 * w + 2 * gap)]
+        ptrs = [(ptr(fq), w + gap), (ptr(fkv), 2 * w + 2 * gap), (ptr(fkv, w * es), 2 * w + 2 * gap)]
         frames = [("Q", fq), ("packed KV", fkv)]
     fo = Framed(b * sq, w, w + gap, dt, SENTINEL, DEV)
     entry = engine.lib.fern_attention_bf16 if bf16 else engine.lib.fern_attention
     (pq, ldq), (pk, ldk), (pv, ldv) = ptrs
-    _lib.check(entry(engine._h, pq, ldq, pk, ldk, pv, ldv, _p(fo), w + gap, b, heads, hd, sq, sk, causal, scale, _stream()), "attention")
+    _lib.check(entry(engine._h, pq, ldq, pk, ldk, pv, ldv, ptr(fo), w + gap, b, heads, hd, sq, sk, causal, scale, _stream()), "attention")
     torch.cuda.synchronize()
     what = f"attention bf16={bf16} {(b, heads, hd, sq, sk, causal)}"
     fo.assert_intact("out of " + what)
@@ -392,7 +375,7 @@ def test_attention_frames(engine, b, heads, hd, sq, sk, causal, bf16):
         f.assert_intact(f"{name} (input) of {what}")
     got = fo.contiguous()
     assert torch.isfinite(got.float()).all(), f"{what}: not finite (a K / V row past s_k or a gap column was read into the result)"
-    _same_bits(got, ref_c, what)
+    assert_same_bits(got, ref_c, what)
 
 
 # ====================================================================================================================================
@@ -411,13 +394,13 @@ def test_quantize_rows_fp8_frames(engine, rows, d, bf16):
     fx = framed_like(x, d + 8, NAN)
     fy = Framed(rows, d, d + 8, torch.uint8, SENTINEL, DEV)
     fs = Framed(1, rows, rows, torch.float32, SENTINEL, DEV)
-    _lib.check(engine.lib.fern_quantize_rows_fp8(engine._h, _p(fx), int(bf16), d + 8, _p(fy), d + 8, _p(fs), rows, d, _stream()), "quantize_rows_fp8")
+    _lib.check(engine.lib.fern_quantize_rows_fp8(engine._h, ptr(fx), int(bf16), d + 8, ptr(fy), d + 8, ptr(fs), rows, d, _stream()), "quantize_rows_fp8")
     torch.cuda.synchronize()
     fy.assert_intact("y")
     fs.assert_intact("scale")
     fx.assert_intact("x (input)")
-    _same_bits(fy.contiguous(), y_ref, "fp8 bytes")
-    _same_bits(fs.contiguous()[0], s_ref, "row scales")
+    assert_same_bits(fy.contiguous(), y_ref, "fp8 bytes")
+    assert_same_bits(fs.contiguous()[0], s_ref, "row scales")
     assert torch.isfinite(fs.view).all() and not ((fy.view & 0x7F) == 0x7F).any()
 
 
@@ -436,23 +419,19 @@ def test_quantize_mx8_frames(engine, rows, d, bf16):
     fx = framed_like(x, d + 8, NAN)
     fy = Framed(rows, d, d + 8, torch.uint8, SENTINEL, DEV)
     fs = Framed(d // 128, rows * 4, srows * 4, torch.uint8, SENTINEL, DEV)
-    _lib.check(engine.lib.fern_quantize_mx8(engine._h, _p(fx), int(bf16), d + 8, _p(fy), d + 8, _p(fs), srows, rows, d, _stream()), "quantize_mx8")
+    _lib.check(engine.lib.fern_quantize_mx8(engine._h, ptr(fx), int(bf16), d + 8, ptr(fy), d + 8, ptr(fs), srows, rows, d, _stream()), "quantize_mx8")
     torch.cuda.synchronize()
     fy.assert_intact("y")
     fs.assert_intact("scales")
     fx.assert_intact("x (input)")
-    _same_bits(fy.contiguous(), y_ref, "e4m3fn bytes")
-    _same_bits(fs.contiguous().reshape(d // 128, rows, 4), s_ref, "E8M0 scales")
+    assert_same_bits(fy.contiguous(), y_ref, "e4m3fn bytes")
+    assert_same_bits(fs.contiguous().reshape(d // 128, rows, 4), s_ref, "E8M0 scales")
     assert not ((fy.view & 0x7F) == 0x7F).any() and not (fs.view == 0xFF).any()
 
 
 # ====================================================================================================================================
 # the bf16 sweep
 # ====================================================================================================================================
-def _unit(n, d, seed):
-    return torch.nn.functional.normalize(R.rand(n, d, seed=seed), dim=-1)
-
-
 def _bands(t, fill=NAN):
     """A contiguous operand (no ld in the ABI) with a moat before its first and after its last row."""
     return framed_like(t, t.shape[1], fill)
@@ -464,22 +443,22 @@ def test_sweep_bf16_scores_frames(engine, B, N):
     """fern_sweep_bf16_scores with ld = N + 7 (the entry asks for ld >= N only) and ldt = ceil(N / 32) + 3: scores and tile maxima
     bit-identical to the contiguous call, both output frames intact, NaN after the last gallery row and the last query."""
     D = 64
-    q, gal = _unit(B, D, 41).to(DEV), _unit(N, D, 42).to(DEV)
+    q, gal = unit(B, D, 41).to(DEV), unit(N, D, 42).to(DEV)
     pg = engine.prepare_gallery(gal)
     s_ref, t_ref = engine.sweep_bf16_scores(q, pg)
     nt = (N + 31) // 32
     fq, fg = _bands(q), _bands(pg.bf16)
     fs = Framed(B, N, N + 7, torch.float32, SENTINEL, DEV)
     ft = Framed(B, nt, nt + 3, torch.float32, SENTINEL, DEV)
-    _lib.check(engine.lib.fern_sweep_bf16_scores(engine._h, _p(fq), _p(fg), B, N, D, _p(fs), N + 7, _p(ft), nt + 3, _stream()), "sweep")
+    _lib.check(engine.lib.fern_sweep_bf16_scores(engine._h, ptr(fq), ptr(fg), B, N, D, ptr(fs), N + 7, ptr(ft), nt + 3, _stream()), "sweep")
     torch.cuda.synchronize()
     fs.assert_intact("scores")
     ft.assert_intact("tile_max")
     fq.assert_intact("q (input)")
     fg.assert_intact("gallery (input)")
     assert torch.isfinite(fs.view).all() and torch.isfinite(ft.view).all()
-    _same_bits(fs.contiguous(), s_ref, "scores")
-    _same_bits(ft.contiguous(), t_ref, "tile maxima")
+    assert_same_bits(fs.contiguous(), s_ref, "scores")
+    assert_same_bits(ft.contiguous(), t_ref, "tile maxima")
 
 
 # ====================================================================================================================================
@@ -489,7 +468,7 @@ RANK_N, RANK_D = 100, 64
 
 
 def _rank_inputs(engine, B):
-    q, gal = _unit(B, RANK_D, 51 + B).to(DEV), _unit(RANK_N, RANK_D, 52).to(DEV)
+    q, gal = unit(B, RANK_D, 51 + B).to(DEV), unit(RANK_N, RANK_D, 52).to(DEV)
     return q, gal, engine.prepare_gallery(gal)
 
 
@@ -501,8 +480,8 @@ def _rank_check(fs, fi, ref, what):
     torch.cuda.synchronize()
     fs.assert_intact("out_scores of " + what)      # the bytes right after row B - 1 are what a 16-byte store of a ragged row would hit
     fi.assert_intact("out_idx of " + what)
-    _same_bits(fs.contiguous(), ref[0], "scores of " + what)
-    _same_bits(fi.contiguous(), ref[1], "indices of " + what)
+    assert_same_bits(fs.contiguous(), ref[0], "scores of " + what)
+    assert_same_bits(fi.contiguous(), ref[1], "indices of " + what)
 
 
 RANK_CASES = [(3, 1), (3, 7), (3, 51), (1030, 7)]            # (B, K); B = 1030 crosses the 1024-query plan chunk
@@ -519,18 +498,18 @@ def test_sim_topk_output_frames(engine, B, K):
     fq, fg, fg16 = _bands(q), _bands(gal), _bands(pg.bf16)
     ref = engine.sim_topk(q, gal, K)
     fs, fi = _rank_frames(B, K)
-    _lib.check(lib.fern_sim_topk(h, _p(fq), _p(fg), B, RANK_N, RANK_D, K, _p(fs), _p(fi), 0, None, _stream()), "fern_sim_topk")
+    _lib.check(lib.fern_sim_topk(h, ptr(fq), ptr(fg), B, RANK_N, RANK_D, K, ptr(fs), ptr(fi), 0, None, _stream()), "fern_sim_topk")
     _rank_check(fs, fi, ref, f"fern_sim_topk B={B} K={K}")
     ref = engine.sim_topk_bf16(q, pg.bf16, K)
     fs, fi = _rank_frames(B, K)
-    _lib.check(lib.fern_sim_topk_bf16(h, _p(fq), _p(fg16), B, RANK_N, RANK_D, K, _p(fs), _p(fi), 0, None, _stream()), "fern_sim_topk_bf16")
+    _lib.check(lib.fern_sim_topk_bf16(h, ptr(fq), ptr(fg16), B, RANK_N, RANK_D, K, ptr(fs), ptr(fi), 0, None, _stream()), "fern_sim_topk_bf16")
     _rank_check(fs, fi, ref, f"fern_sim_topk_bf16 B={B} K={K}")
     try:
         for strategy in ("lists", "dense"):
             engine.set_rank_strategy(strategy)
             ref = engine.sim_topk(q, pg, K)
             fs, fi = _rank_frames(B, K)
-            _lib.check(lib.fern_sim_topk_prefiltered(h, _p(fq), _p(fg), _p(fg16), _p(pg.meta), B, RANK_N, RANK_D, K, _p(fs), _p(fi), 0, None,
+            _lib.check(lib.fern_sim_topk_prefiltered(h, ptr(fq), ptr(fg), ptr(fg16), ptr(pg.meta), B, RANK_N, RANK_D, K, ptr(fs), ptr(fi), 0, None,
                                                      _stream()), "fern_sim_topk_prefiltered")
             _rank_check(fs, fi, ref, f"fern_sim_topk_prefiltered ({strategy}) B={B} K={K}")
     finally:
@@ -546,11 +525,11 @@ def test_sim_topk_deep_output_frames(engine, B, K):
     lib, h = engine.lib, engine._h
     q, gal, pg = _rank_inputs(engine, B)
     fq, fg, fg16 = _bands(q), _bands(gal), _bands(pg.bf16)
-    for name, wrapper_gallery, args in (("fp32", gal, (_p(fg), None, None)), ("prepared", pg, (_p(fg), _p(fg16), _p(pg.meta))),
-                                        ("bf16", pg.bf16, (None, _p(fg16), None))):
+    for name, wrapper_gallery, args in (("fp32", gal, (ptr(fg), None, None)), ("prepared", pg, (ptr(fg), ptr(fg16), ptr(pg.meta))),
+                                        ("bf16", pg.bf16, (None, ptr(fg16), None))):
         ref = engine.sim_topk_deep(q, wrapper_gallery, K)
         fs, fi = _rank_frames(B, K)
-        _lib.check(lib.fern_sim_topk_deep(h, _p(fq), *args, B, RANK_N, RANK_D, K, _p(fs), _p(fi), 0, None, _stream()), "fern_sim_topk_deep")
+        _lib.check(lib.fern_sim_topk_deep(h, ptr(fq), *args, B, RANK_N, RANK_D, K, ptr(fs), ptr(fi), 0, None, _stream()), "fern_sim_topk_deep")
         _rank_check(fs, fi, ref, f"fern_sim_topk_deep ({name}) B={B} K={K}")
     for f in (fq, fg, fg16):
         f.assert_intact("a ranking input")
@@ -567,7 +546,7 @@ def test_topk_merge_output_frames(engine, B, K):
     fin_s = Framed(2 * B, K, K, torch.float32, NAN, DEV).load(s.reshape(2 * B, K))
     fin_i = Framed(2 * B, K, K, torch.int32, SENTINEL, DEV).load(i.reshape(2 * B, K))
     fs, fi = _rank_frames(B, K)
-    _lib.check(engine.lib.fern_topk_merge(engine._h, _p(fin_s), _p(fin_i), _p(fs), _p(fi), 2, B, K, _stream()), "fern_topk_merge")
+    _lib.check(engine.lib.fern_topk_merge(engine._h, ptr(fin_s), ptr(fin_i), ptr(fs), ptr(fi), 2, B, K, _stream()), "fern_topk_merge")
     _rank_check(fs, fi, ref, f"fern_topk_merge B={B} K={K}")
     fin_s.assert_intact("shard scores (input)")
     fin_i.assert_intact("shard indices (input)")
@@ -582,7 +561,7 @@ def test_gather_scores_output_frame(engine, B, m):
     fq, fg = _bands(q), _bands(gal)
     fidx = Framed(B, m, m, torch.int32, 0xFF, DEV).load(idx)                              # moat of -1 indices
     fo = Framed(B, m, m, torch.float32, SENTINEL, DEV)
-    _lib.check(engine.lib.fern_gather_scores(engine._h, _p(fq), _p(fg), _p(fidx), _p(fo), B, m, RANK_D, _stream()), "fern_gather_scores")
+    _lib.check(engine.lib.fern_gather_scores(engine._h, ptr(fq), ptr(fg), ptr(fidx), ptr(fo), B, m, RANK_D, _stream()), "fern_gather_scores")
     torch.cuda.synchronize()
     fo.assert_intact(f"out of fern_gather_scores B={B} m={m}")
-    _same_bits(fo.contiguous(), ref, "gathered scores")
+    assert_same_bits(fo.contiguous(), ref, "gathered scores")

@@ -13,28 +13,16 @@ from fashionern_aaai2024_amd.engine import (COMBINER_DVR_FINAL, COMBINER_DVR_GLO
 from oracle import clip as oclip
 from oracle import fusion as ofusion
 
+import support
+from support import maxerr, tower_engine, t as _t      # `t` is a parameter of the dvr_fuse cases
+
 pytestmark = pytest.mark.gpu
 
 FUSION_TOL = 2e-5
-_engines = {}
 
 
 def fusion_engine(d):
-    if d not in _engines:
-        eng = FernEngine("cuda:0")
-        sd = synth.fusion_state_dict(d, seed=11)
-        eng.load_tensors(sd)
-        eng.finalize_fusion(d)
-        _engines[d] = (eng, ofusion.as_torch(sd))
-    return _engines[d]
-
-
-def _t(a):
-    return torch.from_numpy(a)
-
-
-def _maxerr(got, ref):
-    return (got.detach().cpu().double() - ref.double()).abs().max().item()
+    return support.fusion_engine(d, seed=11)
 
 
 @pytest.mark.parametrize("d", [128, 512, 640])
@@ -45,10 +33,10 @@ def test_combiner_and_sr(d):
     for which, prefix in ((COMBINER_TARGET, "Combiner_module"), (COMBINER_DVR_GLOBAL, "DVR.combiner_global"),
                           (COMBINER_DVR_LOCAL, "DVR.combiner_local"), (COMBINER_DVR_FINAL, "DVR.combiner")):
         ref = ofusion.combiner_simple(sd, prefix, img, txt)
-        assert _maxerr(eng.combiner(which, img, txt), ref) < FUSION_TOL
+        assert maxerr(eng.combiner(which, img, txt), ref) < FUSION_TOL
     loc = _t(synth.local_feats(n, d, tag="sl"))
     for which, prefix in ((SR_TARGET, "SR_module"), (SR_DVR, "DVR.SR_module")):
-        assert _maxerr(eng.visual_sr(which, loc), ofusion.visual_sr(sd, prefix, loc)) < FUSION_TOL
+        assert maxerr(eng.visual_sr(which, loc), ofusion.visual_sr(sd, prefix, loc)) < FUSION_TOL
 
 
 @pytest.mark.parametrize("d,n", [(128, 1), (128, 300), (512, 129), (640, 65)])
@@ -56,8 +44,8 @@ def test_index_fuse(d, n):
     eng, sd = fusion_engine(d)
     raw, loc = _t(synth.global_feats(n, d, tag="ir")), _t(synth.local_feats(n, d, tag="il"))
     ref = ofusion.index_fuse(sd, F.normalize(raw, dim=-1), loc)
-    assert _maxerr(eng.index_fuse(raw, loc, normalize_input=True), ref) < FUSION_TOL
-    assert _maxerr(eng.index_fuse(F.normalize(raw, dim=-1), loc), ref) < FUSION_TOL
+    assert maxerr(eng.index_fuse(raw, loc, normalize_input=True), ref) < FUSION_TOL
+    assert maxerr(eng.index_fuse(F.normalize(raw, dim=-1), loc), ref) < FUSION_TOL
 
 
 def test_index_fuse_tiles_large_gallery():
@@ -68,7 +56,7 @@ def test_index_fuse_tiles_large_gallery():
     got = eng.index_fuse(raw, loc, normalize_input=True).cpu()
     sel = torch.cat((torch.arange(0, 64), torch.arange(8160, 8260), torch.arange(n - 50, n)))
     ref = ofusion.index_fuse(sd, F.normalize(raw[sel], dim=-1), loc[sel])
-    assert _maxerr(got[sel], ref) < FUSION_TOL
+    assert maxerr(got[sel], ref) < FUSION_TOL
     small = eng.index_fuse(raw[8192:], loc[8192:], normalize_input=True).cpu()
     assert torch.equal(small, got[8192:])
 
@@ -81,7 +69,7 @@ def test_dvr_fuse(d, b, t):
     ts = _t(synth._normal(42, f"tseq/{d}", (b, t, d)))
     ref = ofusion.dvr_fuse(sd, rl, ts, rg, tg)
     got = eng.dvr_fuse(rg, rl, tg, ts)
-    assert _maxerr(got, ref) < 5e-5
+    assert maxerr(got, ref) < 5e-5
     assert abs(got.norm(dim=1).cpu() - 1).max().item() < 1e-5
 
 
@@ -96,7 +84,7 @@ def test_dvr_fuse_without_cls_token():
     b = 4
     rg, rl = _t(synth.global_feats(b, d, tag="rg")), _t(synth.local_feats(b, d, tag="rl"))
     tg, ts = _t(synth.global_feats(b, d, tag="tg")), _t(synth._normal(42, "tseq", (b, 77, d)))
-    assert _maxerr(eng.dvr_fuse(rg, rl, tg, ts), ofusion.dvr_fuse(sd, rl, ts, rg, tg)) < 5e-5
+    assert maxerr(eng.dvr_fuse(rg, rl, tg, ts), ofusion.dvr_fuse(sd, rl, ts, rg, tg)) < 5e-5
     eng.close()
 
 
@@ -117,44 +105,36 @@ def test_missing_weight_fails_loudly():
 
 @pytest.mark.parametrize("name", ["tiny", "tiny-hd64"])
 def test_clip_towers_tiny(name):
-    cfg = synth.CLIP_CONFIGS[name]
-    sd_np = synth.clip_state_dict(cfg, seed=5)
+    cfg, sd_np, eng = tower_engine(name, seed=5)
     sd = ofusion.as_torch(sd_np)
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(sd_np)
-    eng.finalize_clip(cfg)
     imgs = _t(synth.images(5, cfg))
     ref = oclip.encode_image(sd, cfg, imgs)
     got = eng.encode_image(imgs)
-    assert _maxerr(got, ref) < 2e-4 * max(1.0, ref.abs().max().item())
+    assert maxerr(got, ref) < 2e-4 * max(1.0, ref.abs().max().item())
     for full in (True, False):
         toks = _t(synth.captions(6, cfg, full_length=full))
         rg, rs = oclip.encode_text(sd, cfg, toks)
         g, s = eng.encode_text(toks)
         scale = max(1.0, rs.abs().max().item())
-        assert _maxerr(s, rs) < 2e-4 * scale and _maxerr(g, rg) < 2e-4 * scale
+        assert maxerr(s, rs) < 2e-4 * scale and maxerr(g, rg) < 2e-4 * scale
         g2, _ = eng.encode_text(toks, want_seq=False)
-        assert _maxerr(g2, rg) < 2e-4 * scale
+        assert maxerr(g2, rg) < 2e-4 * scale
     eng.close()
 
 
 def test_clip_vit_b16_full_size():
     """The real ViT-B/16 shape (197 tokens, 12 x 64 heads, 12 layers) on 3 images / captions."""
-    cfg = synth.CLIP_CONFIGS["ViT-B-16"]
-    sd_np = synth.clip_state_dict(cfg, seed=6)
+    cfg, sd_np, eng = tower_engine("ViT-B-16", seed=6)
     sd = ofusion.as_torch(sd_np)
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(sd_np)
-    eng.finalize_clip(cfg)
     imgs = _t(synth.images(3, cfg))
     ref = oclip.encode_image(sd, cfg, imgs)
     got = eng.encode_image(imgs)
     cos = F.cosine_similarity(got.cpu(), ref, dim=-1)
-    assert _maxerr(got, ref) < 1e-3 * max(1.0, ref.abs().max().item()) and (1 - cos).abs().max().item() < 1e-5
+    assert maxerr(got, ref) < 1e-3 * max(1.0, ref.abs().max().item()) and (1 - cos).abs().max().item() < 1e-5
     toks = _t(synth.captions(3, cfg))
     rg, rs = oclip.encode_text(sd, cfg, toks)
     g, s = eng.encode_text(toks)
-    assert _maxerr(s, rs) < 1e-3 * max(1.0, rs.abs().max().item())
+    assert maxerr(s, rs) < 1e-3 * max(1.0, rs.abs().max().item())
     assert (1 - F.cosine_similarity(g.cpu(), rg, dim=-1)).abs().max().item() < 1e-5
     eng.close()
 
@@ -182,24 +162,20 @@ def test_modified_resnet_tower_tiny_and_rn50x4():
     """open_clip ModifiedResNet image tower (RN50x4 for BASELINE configs C1/C3): NHWC GEMM convolutions with the 3x3-window
     LDS-DMA loader, folded BatchNorm, fused ReLU / residual epilogues, attention pool -- against the CPU oracle."""
     for name, n, tol in (("tiny-resnet", 5, 2e-4), ("RN50x4", 2, 1e-3)):
-        cfg = synth.CLIP_CONFIGS[name]
-        sd_np = synth.clip_state_dict(cfg, seed=8)
+        cfg, sd_np, eng = tower_engine(name, seed=8)
         sd = ofusion.as_torch(sd_np)
-        eng = FernEngine("cuda:0")
-        eng.load_tensors(sd_np)
-        eng.finalize_clip(cfg)
         imgs = _t(synth.images(n, cfg))
         ref = oclip.encode_image(sd, cfg, imgs)
         got = eng.encode_image(imgs)
         scale = max(1.0, ref.abs().max().item())
-        assert _maxerr(got, ref) < tol * scale, (name, _maxerr(got, ref), scale)
+        assert maxerr(got, ref) < tol * scale, (name, maxerr(got, ref), scale)
         assert (1 - F.cosine_similarity(got.cpu(), ref, dim=-1)).abs().max().item() < 1e-5
         # batch invariance: one image alone gives the same row
         assert torch.equal(eng.encode_image(imgs[1:2]), got[1:2])
         toks = _t(synth.captions(3, cfg))
         rg, rs = oclip.encode_text(sd, cfg, toks)
         g, s = eng.encode_text(toks)
-        assert _maxerr(s, rs) < 1e-3 * max(1.0, rs.abs().max().item())
+        assert maxerr(s, rs) < 1e-3 * max(1.0, rs.abs().max().item())
         eng.close()
 
 
@@ -210,12 +186,8 @@ def test_clip_towers_bf16_precision(name, n):
     Checked two ways: (1) against the oracle evaluated with the SAME rounding points (only fp32 summation order and
     the occasional operand that lands on the other side of a bf16 rounding boundary differ); (2) against the fp32
     oracle, to state what the mode costs in accuracy (bf16 has 8 mantissa bits: ~4e-3 relative per operand)."""
-    cfg = synth.CLIP_CONFIGS[name]
-    sd_np = synth.clip_state_dict(cfg, seed=11)
+    cfg, sd_np, eng = tower_engine(name, seed=11)
     sd = ofusion.as_torch(sd_np)
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(sd_np)
-    eng.finalize_clip(cfg)
     imgs = _t(synth.images(n, cfg))
     toks = _t(synth.captions(n, cfg))
     fp32_img = eng.encode_image(imgs)
@@ -241,8 +213,8 @@ def test_clip_towers_bf16_precision(name, n):
 
     # (1) same rounding points: tight
     assert cos_err(got, ref_b) < 2e-5 and cos_err(g, rg_b) < 2e-5
-    assert _maxerr(got, ref_b) < 5e-3 * max(1.0, ref_b.abs().max().item())
-    assert _maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
+    assert maxerr(got, ref_b) < 5e-3 * max(1.0, ref_b.abs().max().item())
+    assert maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
     # (2) cost of the mode against the fp32 statement: features stay within 1e-3 in cosine
     assert cos_err(got, ref_f) < 1e-3 and cos_err(g, rg_f) < 1e-3
     assert cos_err(got, ref_f) > 0 and not torch.equal(got, fp32_img)   # the mode really is a different precision
@@ -258,12 +230,8 @@ def test_clip_towers_fp8_precision(name, n):
     6 % change of it) and the flips compound over 11 layers, so the agreement is loose (measured 1.4e-4 ... 1.3e-3 in
     cosine) but the product must sit closer to its restatement than to fp32; (2) vs the fp32 oracle: the cost of the mode,
     reported not hidden -- cosine error of the features 1.3e-3 ... 4.2e-3 (bf16 mode: 1e-5)."""
-    cfg = synth.CLIP_CONFIGS[name]
-    sd_np = synth.clip_state_dict(cfg, seed=11)
+    cfg, sd_np, eng = tower_engine(name, seed=11)
     sd = ofusion.as_torch(sd_np)
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(sd_np)
-    eng.finalize_clip(cfg)
     imgs = _t(synth.images(n, cfg))
     toks = _t(synth.captions(n, cfg))
     fp32_img = eng.encode_image(imgs)
@@ -297,12 +265,8 @@ def test_clip_towers_mx8_precision(name, n):
     scales).  End to end: (1) against the oracle restating the same quantisation points (e4m3 rounding flips compound over the
     layers, as in the per-row fp8 mode, so the agreement is loose but closer than to fp32); (2) against the fp32 oracle, the cost of
     the mode; (3) batch invariance and a clean return to fp32."""
-    cfg = synth.CLIP_CONFIGS[name]
-    sd_np = synth.clip_state_dict(cfg, seed=11)
+    cfg, sd_np, eng = tower_engine(name, seed=11)
     sd = ofusion.as_torch(sd_np)
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(sd_np)
-    eng.finalize_clip(cfg)
     imgs = _t(synth.images(n, cfg))
     toks = _t(synth.captions(n, cfg))
     fp32_img = eng.encode_image(imgs)
@@ -346,12 +310,8 @@ def test_clip_towers_mx8img_and_mx8mlp_precision(name, n):
     points (_block_mixed: MX MLP half -- and for mx8img the MX attention half when head_dim % 32 == 0; tiny-hd48's head_dim 48 takes
     the bf16 attention half -- over the fp32 stream, the bf16 text tower).  (1) close to the restatement, closer than to fp32 and to
     the bf16 restatement; (2) the text features are the bf16 mode's; (3) batch invariance and a clean return to fp32."""
-    cfg = synth.CLIP_CONFIGS[name]
-    sd_np = synth.clip_state_dict(cfg, seed=11)
+    cfg, sd_np, eng = tower_engine(name, seed=11)
     sd = ofusion.as_torch(sd_np)
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(sd_np)
-    eng.finalize_clip(cfg)
     imgs = _t(synth.images(n, cfg))
     toks = _t(synth.captions(n, cfg))
     fp32_img = eng.encode_image(imgs)
@@ -385,15 +345,12 @@ def test_clip_towers_mx8img_and_mx8mlp_precision(name, n):
         # separation to require; on the other towers it measured 2.4x - 16x
         # the text tower is the bf16 block: the bf16 test's bounds
         assert cos_err(g, rg_b) < 2e-5 and cos_err(s, rs_b) < 2e-5
-        assert _maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
+        assert maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
     assert not torch.equal(got["mx8img"], fp32_img) and not torch.equal(got["mx8mlp"], fp32_img)
 
 
 def test_mx8_precision_needs_widths_that_are_multiples_of_128():
-    cfg = synth.CLIP_CONFIGS["tiny-hd64"]                              # ViT width 192
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(synth.clip_state_dict(cfg, seed=1))
-    eng.finalize_clip(cfg)
+    cfg, _, eng = tower_engine("tiny-hd64", seed=1)                              # ViT width 192
     with pytest.raises(FernError, match="multiples of 128"):
         eng.set_precision("mx8")
     assert eng.precision == "fp32"
@@ -401,10 +358,7 @@ def test_mx8_precision_needs_widths_that_are_multiples_of_128():
 
 
 def test_fp8_precision_needs_widths_that_are_multiples_of_64():
-    cfg = synth.CLIP_CONFIGS["tiny"]
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(synth.clip_state_dict(cfg, seed=1))
-    eng.finalize_clip(cfg)
+    cfg, _, eng = tower_engine("tiny", seed=1)
     if cfg.v_width % 64 or cfg.t_width % 64 or cfg.v_mlp % 64 or cfg.t_mlp % 64:
         with pytest.raises(FernError, match="multiples of 64"):
             eng.set_precision("fp8")
@@ -428,8 +382,8 @@ def test_dvr_fuse_reduced_precision(d, b, t):
             eng.set_precision(prec)
             got = eng.dvr_fuse(rg, rl, tg, ts)
             assert torch.equal(eng.dvr_fuse(rg[1:2], rl[1:2], tg[1:2], ts[1:2]), got[1:2])      # batch-invariant
-            assert _maxerr(got, ref_b) < 5e-4                                                    # unit-norm features
-            assert _maxerr(got, ref_f) < 1e-2 and not torch.equal(got, fp32)
+            assert maxerr(got, ref_b) < 5e-4                                                    # unit-norm features
+            assert maxerr(got, ref_f) < 1e-2 and not torch.equal(got, fp32)
             assert abs(got.norm(dim=1).cpu() - 1).max().item() < 1e-5
     finally:
         eng.set_precision("fp32")
@@ -477,11 +431,7 @@ def test_encode_pair_is_bit_identical_to_the_two_encoder_calls(cfg_name, b, prec
     same k order: image features, text global and text seq equal fern_vit_encode_image + fern_text_encode BIT FOR BIT, on the first call
     (two launches per pair while the shapes are tuned), on later calls (one launch), with pairing switched off by a forced tile, and in a
     mode the library does not pair (bf16: the two calls).  b = 65 / 130: the pair path cuts batches above 64 into chunks of 64."""
-    from fashionern_aaai2024_amd.engine import FernEngine
-    cfg = synth.CLIP_CONFIGS[cfg_name]
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(synth.clip_state_dict(cfg, seed=4))
-    eng.finalize_clip(cfg)
+    cfg, _, eng = tower_engine(cfg_name, seed=4)
     if precision in ("bf16", "mx8img") and cfg_name == "tiny":
         eng.close()
         pytest.skip("the tiny tower's widths are outside the reduced-precision modes")
@@ -537,10 +487,7 @@ def test_encode_pair_walks_the_unpaired_tail_layers(v_layers, t_layers, precisio
     the mixed mode (tiny-w256: widths that are multiples of 128, head_dim 64, so mx8img pairs).  Bit for bit the two encoder calls, on the
     first call (which tunes) and the second (which may take the one-launch form), with and without the seq output."""
     from dataclasses import replace
-    cfg = replace(synth.CLIP_CONFIGS["tiny-w256"], v_layers=v_layers, t_layers=t_layers)
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(synth.clip_state_dict(cfg, seed=4))
-    eng.finalize_clip(cfg)
+    cfg, _, eng = tower_engine(replace(synth.CLIP_CONFIGS["tiny-w256"], v_layers=v_layers, t_layers=t_layers), seed=4)
     eng.set_precision(precision)
     b = 3
     imgs = torch.from_numpy(synth.images(b, cfg, 11)).cuda()

@@ -11,6 +11,7 @@ import torch.nn.functional as F
 import gemm_refs
 from gemm_refs import attn_ref as _attn_ref, close as _close, mx_scales_by_block as _mx_scales_by_block, rand as _rand
 from oracle import rank as orank
+from support import assert_same_order_up_to_near_ties, int_unit
 
 pytestmark = pytest.mark.gpu
 
@@ -82,16 +83,10 @@ def test_attention_sharp_softmax(engine):
     _close(engine.attention(q, k, v, heads, scale=1.0), _attn_ref(q, k, v, heads, False, 1.0), rel=5e-5)
 
 
-def _int_unit(n, d, seed):
-    """Rows with entries in {-1,0,1}/8: every dot product is exact in fp32 in any summation order (and ties abound)."""
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-1, 2, (n, d), generator=g).float() / 8.0
-
-
 @pytest.mark.parametrize("B,N,D,K", [(5, 1000, 64, 50), (64, 9001, 128, 51), (3, 40, 32, 50), (2, 64, 32, 64),
                                       (1, 1, 32, 1), (7, 20000, 64, 10), (130, 3000, 64, 50)])
 def test_sim_topk_bit_exact_with_ties(engine, B, N, D, K):
-    q, g = _int_unit(B, D, 1), _int_unit(N, D, 2)
+    q, g = int_unit(B, D, 1), int_unit(N, D, 2)
     rs, ri = orank.cosine_topk(q, g, K)
     s, i = engine.sim_topk(q, g, K)
     assert torch.equal(i.cpu(), ri), "index order differs (tie rule: score desc, index asc)"
@@ -99,7 +94,7 @@ def test_sim_topk_bit_exact_with_ties(engine, B, N, D, K):
 
 
 def test_sim_topk_offset_and_exclude(engine):
-    q, g = _int_unit(9, 64, 3), _int_unit(777, 64, 4)
+    q, g = int_unit(9, 64, 3), int_unit(777, 64, 4)
     ex = torch.tensor([1000 + 5, -1, 1000 + 776, 3, 1000, 1000 + 100, -1, 1000 + 1, 1000 + 2], dtype=torch.int32)
     rs, ri = orank.cosine_topk(q, g, 51, idx_offset=1000, exclude_idx=ex)
     s, i = engine.sim_topk(q, g, 51, idx_offset=1000, exclude_idx=ex)
@@ -121,8 +116,7 @@ def test_sim_topk_random_unit_rows(engine):
     rs, ri = orank.cosine_topk(q, g, 50)
     assert (s - rs).abs().max().item() < 1e-5
     full = q @ g.T
-    for row, p in (i != ri).nonzero().tolist():
-        assert abs(full[row, i[row, p]].item() - full[row, ri[row, p]].item()) < 2e-6
+    assert_same_order_up_to_near_ties(full, i, ri, gap=2e-6)
 
 
 @pytest.mark.parametrize("B,N,D", [(3, 1000, 64), (64, 9001, 640), (130, 3000, 128), (1, 70_000, 512)])
@@ -139,7 +133,7 @@ def test_sim_topk_bit_identical_to_the_fma_chain(engine, B, N, D):
 
 
 def test_gather_scores_and_merge(engine):
-    q, g = _int_unit(6, 64, 5), _int_unit(300, 64, 6)
+    q, g = int_unit(6, 64, 5), int_unit(300, 64, 6)
     idx = torch.tensor([[0, 5, 299, -1, 7, 7]] * 6, dtype=torch.int32)
     assert torch.equal(engine.gather_scores(q, g, idx).cpu(), orank.gather_scores(q, g, idx))
     # shard the gallery 3 ways, top-K per shard with offsets, merge == global top-K
@@ -160,7 +154,7 @@ def test_l2_normalize(engine):
 
 def test_empty_and_degenerate_inputs(engine):
     """Zero-sized batches / galleries are legal (a rank's gallery shard can be empty) and must not launch garbage."""
-    q, g = _int_unit(4, 64, 1), _int_unit(10, 64, 2)
+    q, g = int_unit(4, 64, 1), int_unit(10, 64, 2)
     s, i = engine.sim_topk(q, g[:0], 5)
     assert (i.cpu() == -1).all() and torch.isinf(s.cpu()).all() and (s.cpu() < 0).all()
     s, i = engine.sim_topk(q[:0], g, 5)
@@ -176,11 +170,11 @@ def test_empty_and_degenerate_inputs(engine):
 def test_bad_arguments_are_reported_not_executed(engine):
     from fashionern_aaai2024_amd._lib import FernError
     with pytest.raises(FernError, match="K"):
-        engine.sim_topk(_int_unit(2, 64, 1), _int_unit(10, 64, 2), 65)
+        engine.sim_topk(int_unit(2, 64, 1), int_unit(10, 64, 2), 65)
     with pytest.raises(FernError, match="multiple of 32"):
         engine.gemm(torch.zeros(4, 48), torch.zeros(4, 48))
     with pytest.raises(ValueError):
-        engine.sim_topk(_int_unit(2, 64, 1), _int_unit(10, 32, 2), 5)
+        engine.sim_topk(int_unit(2, 64, 1), int_unit(10, 32, 2), 5)
     # ld < width makes rows overlap and stores race: FERN_ERR_ARG before any launch, and the framed output stays untouched
     import ctypes as C
     from framed import SENTINEL, Framed
@@ -229,7 +223,7 @@ def test_bad_arguments_are_reported_not_executed(engine):
 
 def test_topk_large_gallery_many_segments(engine):
     """200k rows = 25 level-1 segments per query; merge must still be exact (ties included)."""
-    q, g = _int_unit(3, 32, 11), _int_unit(200_000, 32, 12)
+    q, g = int_unit(3, 32, 11), int_unit(200_000, 32, 12)
     rs, ri = orank.cosine_topk(q, g, 51)
     s, i = engine.sim_topk(q, g, 51)
     assert torch.equal(i.cpu(), ri) and torch.equal(s.cpu(), rs)

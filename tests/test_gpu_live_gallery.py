@@ -15,25 +15,11 @@ import torch
 
 from framed import NAN, framed_like
 from oracle import chain
+from support import rand, same_bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 LIVE = 1 << 31
-
-
-def _rand(n, d, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(n, d, generator=g) * scale
-
-
-def _bits(t):
-    """The tensor's bytes as a host integer array (bf16 -> int16, fp32 / int32 -> int32)."""
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32).numpy()
-
-
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
 def _zero_store(n, d, form="prepared"):
@@ -48,7 +34,7 @@ def _zero_store(n, d, form="prepared"):
 def test_upserting_every_row_into_a_zeroed_store_reproduces_prepare(engine, D):
     n = 1001                                               # the last block of four rows is partial
     gen = torch.Generator().manual_seed(D)
-    rows = _rand(n, D, 100 + D) * 10.0 ** (torch.rand(n, 1, generator=gen) * 4 - 2)      # row lengths over four decades
+    rows = rand(n, D, seed=100 + D) * 10.0 ** (torch.rand(n, 1, generator=gen) * 4 - 2)      # row lengths over four decades
     perm = torch.randperm(n, generator=gen)
     want = torch.empty_like(rows)
     want[perm] = rows                                      # row p lands in slot perm[p]
@@ -58,26 +44,26 @@ def test_upserting_every_row_into_a_zeroed_store_reproduces_prepare(engine, D):
     engine.gallery_upsert(rows_d[:cut], slots[:cut], f32, b16, meta)
     engine.gallery_upsert(rows_d[cut:], slots[cut:], f32, b16, meta)
     fresh = engine.prepare_gallery(want)
-    assert _same(f32, want)
-    assert _same(b16, fresh.bf16)
-    assert _same(meta, fresh.meta) and float(meta[3]) == 0.0 and float(meta[2]) > 0.0
+    assert same_bits(f32, want)
+    assert same_bits(b16, fresh.bf16)
+    assert same_bits(meta, fresh.meta) and float(meta[3]) == 0.0 and float(meta[2]) > 0.0
     _, b16_only, _ = _zero_store(n, D, "bf16")            # the bf16-similarity store alone
     engine.gallery_upsert(rows_d, slots, None, b16_only, None)
-    assert _same(b16_only, engine.gallery_to_bf16(want))
+    assert same_bits(b16_only, engine.gallery_to_bf16(want))
     f32_only, _, _ = _zero_store(n, D, "f32")
     engine.gallery_upsert(rows_d, slots, f32_only, None, None)
-    assert _same(f32_only, want)
+    assert same_bits(f32_only, want)
     engine.sync()
 
 
 # ---- 2. frames ------------------------------------------------------------------------------------------------------------------------
 def test_rows_come_through_a_leading_dimension_and_only_the_destination_rows_change(engine):
     n, d, m, ld = 300, 64, 37, 72
-    store = _rand(n, d, 1, 0.3)
+    store = rand(n, d, seed=1, scale=0.3)
     pg = engine.prepare_gallery(store)
     f32, b16, meta = pg.f32.clone(), pg.bf16.clone(), pg.meta.clone()
     before = (f32.clone(), b16.clone())
-    new = _rand(m, d, 2, 0.3)
+    new = rand(m, d, seed=2, scale=0.3)
     src = framed_like(new, ld, NAN, DEV)                   # gap columns and both bands are NaN: a read outside [m, d] poisons the store or meta
     slots = torch.randperm(n, generator=torch.Generator().manual_seed(3))[:m].to(torch.int32)
     engine.gallery_upsert(src.view, slots, f32, b16, meta)
@@ -86,10 +72,10 @@ def test_rows_come_through_a_leading_dimension_and_only_the_destination_rows_cha
     want = store.clone()
     want[slots.long()] = new
     fresh = engine.prepare_gallery(want)
-    assert _same(f32, want) and _same(b16, fresh.bf16)
+    assert same_bits(f32, want) and same_bits(b16, fresh.bf16)
     untouched = torch.ones(n, dtype=torch.bool)
     untouched[slots.long()] = False
-    assert _same(f32[untouched.to(DEV)], before[0][untouched.to(DEV)]) and _same(b16[untouched.to(DEV)], before[1][untouched.to(DEV)])
+    assert same_bits(f32[untouched.to(DEV)], before[0][untouched.to(DEV)]) and same_bits(b16[untouched.to(DEV)], before[1][untouched.to(DEV)])
     assert torch.isfinite(meta).all() and (meta >= pg.meta).all()
     lib, h, p = engine.lib, engine._h, lambda t: None if t is None else t.data_ptr()      # noqa: E731
     sl = slots.to(DEV)
@@ -101,14 +87,14 @@ def test_rows_come_through_a_leading_dimension_and_only_the_destination_rows_cha
         assert call(**kw) == -1 and b"fern_gallery_upsert" in lib.fern_last_error() and why in lib.fern_last_error(), kw
     assert lib.fern_gallery_upsert(h, None, ld, None, 0, p(f32), p(b16), p(meta), n, d, 0, None) == 0      # m == 0: nothing to do
     engine.sync()
-    assert _same(f32, want)
+    assert same_bits(f32, want)
 
 
 # ---- 3. normalize = 1 -----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("D", [36, 512, 1280])
 def test_normalize_equals_l2_normalize_followed_by_a_plain_upsert(engine, D):
     m = 203
-    rows = _rand(m, D, 7 + D) * 10.0 ** (torch.rand(m, 1, generator=torch.Generator().manual_seed(D)) * 6 - 3)
+    rows = rand(m, D, seed=7 + D) * 10.0 ** (torch.rand(m, 1, generator=torch.Generator().manual_seed(D)) * 6 - 3)
     rows[5] = 0.0                                          # F.normalize's eps: 0 / max(0, 1e-12) = 0
     rows[9] = torch.nn.functional.normalize(rows[9], dim=0) * 1e-20      # norm 1e-20 < eps
     slots = torch.randperm(m, generator=torch.Generator().manual_seed(1)).to(torch.int32)
@@ -118,8 +104,8 @@ def test_normalize_equals_l2_normalize_followed_by_a_plain_upsert(engine, D):
     engine.gallery_upsert(unit, slots, *b, normalize=False)
     engine.sync()
     for x, y in zip(a, b):
-        assert _same(x, y)
-    assert _same(a[0][slots.long().to(DEV)], unit)
+        assert same_bits(x, y)
+    assert same_bits(a[0][slots.long().to(DEV)], unit)
     assert float(a[0][int(slots[5])].abs().max()) == 0.0 and torch.isfinite(a[0]).all() and torch.isfinite(a[2]).all()
     norms = a[0].norm(dim=1).cpu()
     assert abs(float(norms[int(slots[0])]) - 1.0) < 1e-5 and float(norms[int(slots[9])]) < 1e-6
@@ -135,18 +121,18 @@ def test_folded_norms_keep_the_prefilter_exact_when_long_rows_replace_short_ones
     from fashionern_aaai2024_amd.live_gallery import LiveGallery
     d, n, k, near = 512, 4096, 50, 400
     norm = torch.nn.functional.normalize
-    base = norm(_rand(1, d, 77), dim=-1)
-    q = norm(base + 0.02 * _rand(8, d, 78) * d ** -0.5, dim=-1)
-    g = norm(_rand(n, d, 79), dim=-1) / 64.0
+    base = norm(rand(1, d, seed=77), dim=-1)
+    q = norm(base + 0.02 * rand(8, d, seed=78) * d ** -0.5, dim=-1)
+    g = norm(rand(n, d, seed=79), dim=-1) / 64.0
     rows = torch.randperm(n, generator=torch.Generator().manual_seed(80))[:near]
-    new = norm(base + 0.03 * _rand(near, d, 81) * d ** -0.5, dim=-1)
+    new = norm(base + 0.03 * rand(near, d, seed=81) * d ** -0.5, dim=-1)
     eng = FernEngine(DEV)
     try:
         live = LiveGallery(eng, n, d)
         slots = live.append(g)
         assert slots.tolist() == list(range(n))
         meta_before = live.meta.clone()
-        assert _same(meta_before, eng.prepare_gallery(g).meta)
+        assert same_bits(meta_before, eng.prepare_gallery(g).meta)
         live.replace(rows.numpy().astype(np.int32), new)
         g[rows] = new
         cs, ci = chain.chain_topk(q.numpy(), g.numpy(), k)
@@ -160,7 +146,7 @@ def test_folded_norms_keep_the_prefilter_exact_when_long_rows_replace_short_ones
             assert np.array_equal(i.cpu().numpy(), ci) and np.array_equal(s.cpu().numpy().view(np.uint32), cs.view(np.uint32)), strategy
         eng.set_rank_strategy("auto")
         meta_new = eng.prepare_gallery(new).meta
-        assert _same(live.meta, torch.maximum(meta_before, meta_new))
+        assert same_bits(live.meta, torch.maximum(meta_before, meta_new))
         assert (live.meta[:3] > 10 * meta_before[:3]).all()      # the change NEEDED the fold: the old bound is far too small
         # the float64 check of test_prepare_reports_the_norms_that_certify_the_margin, for every live row
         meta = live.meta.cpu()
@@ -229,7 +215,7 @@ def _assert_equals_fresh(eng, live, model, q, targets, n_items):
             }
             for name in want:
                 for w, g in zip(want[name], got[name]):
-                    assert _same(w, g), (name, user, full)
+                    assert same_bits(w, g), (name, user, full)
     eng.sync()
     return want
 
@@ -240,19 +226,19 @@ def test_mixed_churn_equals_a_fresh_store_of_the_final_contents(engine):
     r = np.random.default_rng(11)
     live = LiveGallery(engine, cap, d, items=n_items)
     model = _Model(cap, d)
-    g0 = _rand(3000, d, 21, d ** -0.5)
+    g0 = rand(3000, d, seed=21, scale=d ** -0.5)
     g0[17] *= 9.0                                          # one long row sets the maxima
     tags0, items0 = np.arange(3000) % 3, r.integers(0, n_items, 3000).astype(np.int32)
     for a, b in ((0, 1000), (1000, 2500), (2500, 3000)):   # three chunks
         slots = live.append(g0[a:b], tags=tags0[a:b], items=items0[a:b])
         assert slots.tolist() == list(range(a, b))
         model.put(slots, g0[a:b], tags0[a:b], items0[a:b])
-    assert _same(live.meta, engine.prepare_gallery(g0).meta)
-    q = _rand(9, d, 22)
+    assert same_bits(live.meta, engine.prepare_gallery(g0).meta)
+    q = rand(9, d, seed=22)
     targets = torch.from_numpy(r.integers(0, 3000, (9, 3)).astype(np.int32))
     rep = r.choice(3000, 257, replace=False).astype(np.int32)
     rep = rep[rep != 17]
-    new = _rand(rep.size, d, 23, d ** -0.5)
+    new = rand(rep.size, d, seed=23, scale=d ** -0.5)
     live.replace(rep, new)                                 # tags and item ids stay
     model.put(rep, new)
     gone = np.sort(r.choice(3000, 50, replace=False)).astype(np.int32)
@@ -268,7 +254,7 @@ def test_mixed_churn_equals_a_fresh_store_of_the_final_contents(engine):
         live.append(new[:1], tags=[LIVE], items=[0])
     with pytest.raises(ValueError, match="live bit"):
         live.row_filter(LIVE, 0)
-    add = _rand(100, d, 24, d ** -0.5)
+    add = rand(100, d, seed=24, scale=d ** -0.5)
     tags1, items1 = np.arange(100) % 3, r.integers(0, n_items, 100).astype(np.int32)
     slots = live.append(add, tags=tags1, items=items1)
     assert slots[:50].tolist() == gone.tolist() and slots[50:].tolist() == list(range(3000, 3050))      # the lowest free slots first
@@ -276,20 +262,20 @@ def test_mixed_churn_equals_a_fresh_store_of_the_final_contents(engine):
     assert live.n == 3050 and live.n_live == 3050
     _assert_equals_fresh(engine, live, model, q, targets, n_items)
     with pytest.raises(RuntimeError, match="full"):
-        live.append(_rand(151, d, 25), tags=0, items=0)   # 150 slots are free
+        live.append(rand(151, d, seed=25), tags=0, items=0)   # 150 slots are free
     assert live.n == 3050
     # replacing the longest row by a short one leaves meta as it is (an upper bound); refresh() makes it exact again
     meta_before = live.meta.clone()
-    short = _rand(1, d, 26, 0.01 * d ** -0.5)
+    short = rand(1, d, seed=26, scale=0.01 * d ** -0.5)
     live.replace(np.array([17], dtype=np.int32), short)
     model.put([17], short)
-    assert _same(live.meta, meta_before)
+    assert same_bits(live.meta, meta_before)
     exact = engine.prepare_gallery(model.rows[:live.n].to(DEV))
     assert float(exact.meta[2]) < 0.5 * float(meta_before[2])
     _assert_equals_fresh(engine, live, model, q, targets, n_items)      # a loose bound costs nothing but rescoring
     ptrs = (live.gallery().f32.data_ptr(), live.gallery().bf16.data_ptr(), live.meta.data_ptr())
     live.refresh()
-    assert _same(live.meta, exact.meta) and _same(live.gallery().bf16, exact.bf16)
+    assert same_bits(live.meta, exact.meta) and same_bits(live.gallery().bf16, exact.bf16)
     assert ptrs == (live.gallery(full=True).f32.data_ptr(), live.gallery(full=True).bf16.data_ptr(), live.meta.data_ptr())
 
 
@@ -300,7 +286,7 @@ def test_compact_moves_the_highest_live_rows_into_the_holes(engine):
     r = np.random.default_rng(5)
     live = LiveGallery(engine, cap, d, items=n_items)
     model = _Model(cap, d)
-    g = _rand(n, d, 31, d ** -0.5)
+    g = rand(n, d, seed=31, scale=d ** -0.5)
     tags, items = np.arange(n) % 3, r.integers(0, n_items, n).astype(np.int32)
     model.put(live.append(g, tags=tags, items=items), g, tags, items)
     gone = r.choice(n, 120, replace=False).astype(np.int32)
@@ -315,18 +301,18 @@ def test_compact_moves_the_highest_live_rows_into_the_holes(engine):
     assert set(dst.tolist()) == set(gone[gone < n_live].tolist())
     s, t = torch.from_numpy(src.astype(np.int64)).to(DEV), torch.from_numpy(dst.astype(np.int64)).to(DEV)
     for k in ("f32", "bf16", "items"):
-        assert _same(getattr(live, k)[t], before[k][s]), k
+        assert same_bits(getattr(live, k)[t], before[k][s]), k
         keep = torch.ones(cap, dtype=torch.bool, device=DEV)
         keep[t] = False
-        assert _same(getattr(live, k)[keep], before[k][keep]), k      # nothing but the destination rows changed
-    assert _same(live.tags[t], before["tags"][s])
-    assert ((live.tags[s] & -(1 << 31)) == 0).all() and _same(live.tags[s] & 0x7FFFFFFF, before["tags"][s] & 0x7FFFFFFF)      # the sources are free
-    assert _same(live.meta, meta_before)
+        assert same_bits(getattr(live, k)[keep], before[k][keep]), k      # nothing but the destination rows changed
+    assert same_bits(live.tags[t], before["tags"][s])
+    assert ((live.tags[s] & -(1 << 31)) == 0).all() and same_bits(live.tags[s] & 0x7FFFFFFF, before["tags"][s] & 0x7FFFFFFF)      # the sources are free
+    assert same_bits(live.meta, meta_before)
     assert live.row_filter() is None
     model.rows[dst.astype(np.int64)] = model.rows[src.astype(np.int64)]
     model.tags[dst], model.items[dst] = model.tags[src], model.items[src]
     model.tags[src] &= ~LIVE
-    q = _rand(5, d, 32)
+    q = rand(5, d, seed=32)
     targets = torch.from_numpy(r.integers(0, n_live, (5, 2)).astype(np.int32))
     _assert_equals_fresh(engine, live, model, q, targets, n_items)
 
@@ -338,20 +324,20 @@ def test_slots_outside_the_store_write_nothing_and_surface_at_sync():
     eng = FernEngine(DEV)                                  # the flag belongs to the context: keep the session engine's clean
     try:
         cap, d = 50, 64
-        pg = eng.prepare_gallery(_rand(cap, d, 41))
+        pg = eng.prepare_gallery(rand(cap, d, seed=41))
         f32, b16, meta = pg.f32.clone(), pg.bf16.clone(), pg.meta.clone()
         before = (f32.clone(), b16.clone())
-        rows = _rand(5, d, 42)
+        rows = rand(5, d, seed=42)
         slots = torch.tensor([3, -1, 7, cap, 9], dtype=torch.int32)
         eng.gallery_upsert(rows, slots, f32, b16, meta)     # asynchronous: the launch itself succeeds
         with pytest.raises(FernError, match=r"fern_sync.*fern_gallery_upsert.*position (1|3) "):
             eng.sync()
         want = before[0].clone()
         want[[3, 7, 9]] = rows[[0, 2, 4]].to(DEV)
-        assert _same(f32, want)                            # the valid rows of the call were written, nothing else changed
+        assert same_bits(f32, want)                            # the valid rows of the call were written, nothing else changed
         want16 = before[1].clone()
         want16[[3, 7, 9]] = eng.gallery_to_bf16(rows)[[0, 2, 4]]
-        assert _same(b16, want16)
+        assert same_bits(b16, want16)
         eng.sync()                                         # reported once
         tags = torch.zeros(cap, dtype=torch.int32, device=DEV)
         eng.scatter_u32(torch.tensor([5, 6, 7], dtype=torch.int32), torch.tensor([2, cap + 3, 4], dtype=torch.int32), tags)
@@ -362,10 +348,10 @@ def test_slots_outside_the_store_write_nothing_and_surface_at_sync():
         eng.gallery_move(torch.tensor([0, 60], dtype=torch.int32), torch.tensor([1, 2], dtype=torch.int32), f32, b16, tags)
         with pytest.raises(FernError, match=r"fern_gallery_move.*position 1 "):
             eng.sync()
-        assert _same(f32[1], f32[0]) and _same(b16[1], b16[0]) and _same(f32[2], want[2])
+        assert same_bits(f32[1], f32[0]) and same_bits(b16[1], b16[0]) and same_bits(f32[2], want[2])
         eng.gallery_upsert(rows, torch.tensor([10, 11, 12, 13, 14], dtype=torch.int32), f32, b16, meta)      # the next call works
         eng.sync()
-        assert _same(f32[10:15], rows.to(DEV))
+        assert same_bits(f32[10:15], rows.to(DEV))
     finally:
         eng.close()
 
@@ -399,7 +385,7 @@ def test_a_captured_lane_graph_survives_an_append_to_the_full_view():
         assert int(i0.max()) < n                           # free slots of the full view are not eligible
         for res in results[1:]:
             s, i = res.wait()
-            assert _same(s, s0) and _same(i, i0)
+            assert same_bits(s, s0) and same_bits(i, i0)
         pipe.fence()                                       # the update below must not overtake a lane still sweeping the store
         slots = live.append(first.fused, normalize=True)
         assert slots.tolist() == list(range(n, n + b))
@@ -411,7 +397,7 @@ def test_a_captured_lane_graph_survives_an_append_to_the_full_view():
         # direct calls on the lane's engine come last: they may move its workspace, which drops the lane's graphs by design
         for rows, (gs, gi) in ((n, (s0, i0)), (n + b, (s, i))):
             ws, wi = e.sim_topk(first.fused, e.prepare_gallery(live.gallery().f32[:rows].clone()), k)
-            assert _same(gs, ws) and _same(gi, wi), rows
+            assert same_bits(gs, ws) and same_bits(gi, wi), rows
         e.sync()
     finally:
         pipe.close()
@@ -443,4 +429,4 @@ def test_incremental_index_gives_the_recalls_and_the_gallery_bytes_of_the_one_sh
     assert n % 64 and n > 64                               # several chunks and a ragged last one
     fused = _common.fuse_index(model, feats, local)
     fresh = model.engine.prepare_gallery(fused)
-    assert _same(view.f32, fused) and _same(view.bf16, fresh.bf16) and _same(view.meta, fresh.meta)
+    assert same_bits(view.f32, fused) and same_bits(view.bf16, fresh.bf16) and same_bits(view.meta, fresh.meta)

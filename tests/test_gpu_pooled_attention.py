@@ -11,8 +11,8 @@ import pytest
 import torch
 
 from fashionern_aaai2024_amd import synth
-from fashionern_aaai2024_amd.engine import FernEngine
 from oracle import clip as oclip, fusion as ofusion
+from support import rand, tower_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -26,17 +26,13 @@ SHAPES = [(1, 1, 64, 1),          # a single key
 REL = 1e-5
 
 
-def _rand(*shape, seed, scale=1.0):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float32) * scale
-
-
 @functools.lru_cache(maxsize=None)
 def _case(b, S, E, heads):
     """Operands of one shape: layer-normed-looking tokens, projection weights at the towers' scale, a NON-ZERO key bias."""
-    q = _rand(b, E, seed=1)
-    t = _rand(b, S, E, seed=2)
-    wk, wv = _rand(E, E, seed=3, scale=1.2 / E ** 0.5), _rand(E, E, seed=4, scale=1.2 / E ** 0.5)
-    bk, bv = _rand(E, seed=5, scale=0.5), _rand(E, seed=6, scale=0.5)
+    q = rand(b, E, seed=1)
+    t = rand(b, S, E, seed=2)
+    wk, wv = rand(E, E, seed=3, scale=1.2 / E ** 0.5), rand(E, E, seed=4, scale=1.2 / E ** 0.5)
+    bk, bv = rand(E, seed=5, scale=0.5), rand(E, seed=6, scale=0.5)
     return q, t, wk, wv, bk, bv
 
 
@@ -80,21 +76,10 @@ def test_rows_do_not_depend_on_the_batch(engine):
         assert torch.equal(engine.pooled_attention(q[i:i + 1], t[i:i + 1], wk, wv, bv, 3), full[i:i + 1]), i
 
 
-def _tower(name, seed, edit=None):
-    cfg = synth.CLIP_CONFIGS[name]
-    sd_np = synth.clip_state_dict(cfg, seed=seed)
-    if edit:
-        edit(cfg, sd_np)
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(sd_np)
-    eng.finalize_clip(cfg)
-    return cfg, sd_np, eng
-
-
 @pytest.mark.parametrize("name,b", [("tiny", 65), ("tiny-resnet", 129)])
 def test_tower_rows_do_not_depend_on_the_batch_across_chunks(name, b):
     """b = 65 crosses the ViT walker's chunk of 64 images, b = 129 the ResNet walker's chunk of 128."""
-    cfg, _, eng = _tower(name, 5)
+    cfg, _, eng = tower_engine(name, 5)
     imgs = torch.from_numpy(synth.images(b, cfg, 21)).cuda()
     full = eng.encode_image(imgs)
     for i in (0, 1, 15, 16, 63, 64, b - 2, b - 1):
@@ -115,7 +100,7 @@ def _scale_key_bias(cfg, sd):
 
 @pytest.mark.parametrize("name", ["tiny", "tiny-resnet"])
 def test_tower_with_a_large_key_bias_matches_the_oracle(name):
-    cfg, sd_np, eng = _tower(name, 5, _scale_key_bias)
+    cfg, sd_np, eng = tower_engine(name, 5, _scale_key_bias)
     imgs = torch.from_numpy(synth.images(5, cfg))
     ref = oclip.encode_image(ofusion.as_torch(sd_np), cfg, imgs)
     got = eng.encode_image(imgs).cpu()
@@ -126,7 +111,7 @@ def test_tower_with_a_large_key_bias_matches_the_oracle(name):
 
 
 def test_pair_path_is_bit_identical_to_the_two_encoder_calls():
-    cfg, _, eng = _tower("tiny", 4)
+    cfg, _, eng = tower_engine("tiny", 4)
     imgs = torch.from_numpy(synth.images(7, cfg, 11)).cuda()
     toks = torch.from_numpy(synth.captions(7, cfg, 11)).cuda()
     ref_i = eng.encode_image(imgs)

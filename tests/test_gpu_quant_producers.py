@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 from fashionern_aaai2024_amd.engine import QFORM_BF16, QFORM_FP8, QFORM_MX8
+from gemm_refs import e4m3_code, e8m0_byte, mx_scales_by_block
 from oracle.clip import mx8_dequantize, mx8_quantize
 
 pytestmark = pytest.mark.gpu
@@ -55,19 +56,7 @@ def _by_block(sc, rows):
     """[d/128, scale_rows, 4] scale array -> [rows, d/32] (block b = k // 32), after checking that the padding rows are untouched."""
     sc = sc.cpu()
     assert (sc[:, rows:] == SENTINEL).all(), "scale bytes beyond `rows` were written"
-    return sc[:, :rows].permute(1, 0, 2).reshape(rows, -1)
-
-
-def _e8(m):
-    """E8M0 byte of fp32 block maxima, as the kernels compute it (csrc/kernels.h: mx_scale_byte)."""
-    u = m.float().contiguous().view(torch.int32)
-    return ((u >> 23) - 8 + ((u & 0x7FFFFF) > 0x600000).int()).clamp(1, 253)
-
-
-def _code(v):
-    """e4m3fn bytes of fp32 values (round to nearest even) as int, and their signed position on the code line."""
-    b = v.float().to(torch.float8_e4m3fn).view(torch.uint8).int()
-    return b, torch.where(b >= 128, -(b & 0x7F), b)
+    return mx_scales_by_block(sc[:, :rows])
 
 
 def _ord(b):
@@ -85,16 +74,16 @@ def _check_fp64_rule(y8, e_got, y64, tol):
     tb = tol.reshape(rows, nb, 32)
     m = blk.abs().amax(-1)
     tm = tb.amax(-1)
-    e_lo, e_hi, e_mid = _e8((m - tm).clamp_min(0)), _e8(m + tm), _e8(m)
+    e_lo, e_hi, e_mid = e8m0_byte((m - tm).clamp_min(0)), e8m0_byte(m + tm), e8m0_byte(m)
     e_got = e_got.int()
     exact_blk = e_lo == e_hi
     assert torch.equal(e_got[exact_blk], e_mid[exact_blk].int()), "scale byte differs outside the excused blocks"
     assert ((e_got >= e_lo) & (e_got <= e_hi) & (e_hi - e_lo <= 1)).all(), "scale byte outside its excuse"
     sc = torch.ldexp(torch.ones((), dtype=torch.float64), 127 - e_got).unsqueeze(-1)
     v, tv = blk * sc, tb * sc
-    c_ref, o_ref = _code(v)
-    c_lo, o_lo = _code(v - tv)
-    c_hi, o_hi = _code(v + tv)
+    c_ref, o_ref = e4m3_code(v)
+    c_lo, o_lo = e4m3_code(v - tv)
+    c_hi, o_hi = e4m3_code(v + tv)
     got = y8.cpu().int().reshape(rows, nb, 32)
     o_got = _ord(got)
     excused = c_lo != c_hi
@@ -267,15 +256,15 @@ def test_attention_mx8_output(engine, b, heads, hd, s, causal):
     bb = yb.double().reshape(rows, nb, 32)
     half = lambda t: torch.ldexp(torch.ones((), dtype=torch.float64), torch.frexp(t.float())[1] - 9)   # half a bf16 ulp of |t| (2^(E-8))
     m = bb.abs().amax(-1)
-    e_lo, e_hi = _e8(m - half(m)), _e8(m + half(m))
+    e_lo, e_hi = e8m0_byte(m - half(m)), e8m0_byte(m + half(m))
     sure = e_lo == e_hi
-    assert torch.equal(e[sure], _e8(m)[sure]), "scale byte differs from the bf16 output's block maximum"
+    assert torch.equal(e[sure], e8m0_byte(m)[sure]), "scale byte differs from the bf16 output's block maximum"
     assert ((e >= e_lo) & (e <= e_hi)).all()
     scl = torch.ldexp(torch.ones((), dtype=torch.float64), 127 - e).unsqueeze(-1)
     hb = half(bb.abs())
-    c_ref, o_ref = _code(bb * scl)
-    c_lo, o_lo = _code((bb - hb) * scl)
-    c_hi, o_hi = _code((bb + hb) * scl)
+    c_ref, o_ref = e4m3_code(bb * scl)
+    c_lo, o_lo = e4m3_code((bb - hb) * scl)
+    c_hi, o_hi = e4m3_code((bb + hb) * scl)
     got = y8.reshape(rows, nb, 32)
     o_got = _ord(got)
     excused = c_lo != c_hi

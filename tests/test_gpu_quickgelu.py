@@ -5,7 +5,6 @@ families the tolerances their GELU cases have in test_gpu_kernels.py; fp32 / f32
 1e-3 (full size) of the feature scale; the reduced modes the constants of test_gpu_fusion.py / test_gpu_towers_long.py
 (MIXED_BOUNDS included) against the patched oracle's restatement (tests/quickgelu_oracle.py).
 """
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -17,19 +16,12 @@ from oracle import clip as oclip
 from oracle import fusion as ofusion
 
 import quickgelu_oracle as qo
+from gemm_refs import mx_scales_by_block
+from support import close, cos_err, maxerr, rand, t, tower_engine
 
 pytestmark = pytest.mark.gpu
 
 MIXED_BOUNDS = {"mx8img": 2e-3, "mx8mlp": 1e-3}      # test_gpu_fusion.py
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
 
 
 def _quick64(x):
@@ -37,40 +29,16 @@ def _quick64(x):
     return x * torch.sigmoid(1.702 * x)
 
 
-def _maxerr(got, ref):
-    return (got.detach().cpu().double() - ref.double()).abs().max().item()
-
-
-def _close(got, ref, rel=2e-5):
-    got, ref = got.detach().cpu().double(), ref.double()
-    err = (got - ref).abs().max().item()
-    print(f"max abs err {err:.3e} vs scale {ref.abs().max().item():.3e}")
-    assert err <= rel * max(ref.abs().max().item(), 1e-6), f"max abs err {err} vs scale {ref.abs().max().item()}"
-
-
-def _cos_err(a, b):
-    a, b = a.cpu().double(), b.double()
-    return (1 - F.cosine_similarity(a.flatten(-1 if a.dim() == 2 else 1), b.flatten(-1 if b.dim() == 2 else 1), dim=-1)).abs().max().item()
-
-
-def _quick_engine(cfg, seed, quick=True):
-    cfg = synth.resolve_clip_config(cfg, force_quick_gelu=quick)
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(synth.clip_state_dict(cfg, seed=seed))
-    eng.finalize_clip(cfg)
-    return eng, cfg
-
-
 # ==== a. GEMM level =================================================================================================================
 @pytest.mark.parametrize("M,N,K", [(2304, 3072, 768), (12608, 3072, 768), (1000, 520, 256), (129, 513, 128), (257, 129, 32), (64, 3072, 768),
                                     (1, 32, 32), (37, 200, 96)])
 def test_gemm_quickgelu_matches_float64(engine, M, N, K):
     """fp32 family: deep, ragged-edge and skinny (M <= 128: the 16x16 kernel) shapes, with and without a bias."""
-    a, w, b = _rand(M, K, seed=1), _rand(N, K, seed=2, scale=K ** -0.5), _rand(N, seed=3)
+    a, w, b = rand(M, K, seed=1), rand(N, K, seed=2, scale=K ** -0.5), rand(N, seed=3)
     ref = a.double() @ w.double().T
-    _close(engine.gemm(a, w, b, epilogue=EPI_BIAS_QUICKGELU), _quick64(ref + b.double()))
+    close(engine.gemm(a, w, b, epilogue=EPI_BIAS_QUICKGELU), _quick64(ref + b.double()))
     if M <= 1000:
-        _close(engine.gemm(a, w, None, epilogue=EPI_BIAS_QUICKGELU), _quick64(ref))
+        close(engine.gemm(a, w, None, epilogue=EPI_BIAS_QUICKGELU), _quick64(ref))
 
 
 def test_gemm_quickgelu_saturates_cleanly(engine):
@@ -81,7 +49,7 @@ def test_gemm_quickgelu_saturates_cleanly(engine):
     got = engine.gemm(a, w, b, epilogue=EPI_BIAS_QUICKGELU).cpu()
     assert torch.isfinite(got).all()
     assert (got[:, :32] == 0).all() and torch.equal(got[:, 32:64], b[32:64].expand(64, 32))
-    _close(got[:, 64:], _quick64(b[64:].expand(64, 32)))
+    close(got[:, 64:], _quick64(b[64:].expand(64, 32)))
 
 
 @pytest.mark.parametrize("m,n,k", [(1000, 520, 256), (4096, 768, 768), (300, 96, 64)])
@@ -89,7 +57,7 @@ def test_gemm_quickgelu_f32x3(m, n, k):
     """f32x3 family (M >= 256): fp32-accurate (test_gemm_f32x3_is_fp32_accurate_and_configuration_independent's rule), all eight tile
     configurations and the mixed plans bit-identical, batch-invariant."""
     eng = FernEngine("cuda:0")
-    a, w, b = _rand(m, k, seed=31), _rand(n, k, seed=32, scale=k ** -0.5), _rand(n, seed=33)
+    a, w, b = rand(m, k, seed=31), rand(n, k, seed=32, scale=k ** -0.5), rand(n, seed=33)
     epi = EPI_BIAS_QUICKGELU
     ref = _quick64(a.double() @ w.double().T + b.double())
     run = lambda: eng.gemm(a, w, b, epilogue=epi).cpu()  # noqa: E731
@@ -108,7 +76,7 @@ def test_gemm_quickgelu_f32x3(m, n, k):
             outs.append(run())
     for o in outs[1:]:
         assert torch.equal(o, outs[0]), "f32x3 tile configurations must be bit-identical"
-    _close(outs[0], ref)
+    close(outs[0], ref)
     rms = ref.pow(2).mean().sqrt().item()
     err_x3, err_f32 = (outs[0].double() - ref).abs().max().item(), (exact.double() - ref).abs().max().item()
     print(f"f32x3 {err_x3:.3e} fp32 {err_f32:.3e} rms {rms:.3e}")
@@ -122,11 +90,11 @@ def test_gemm_quickgelu_every_fp32_tile_configuration_is_bit_identical(engine):
     """The family invariant: every forced tile configuration, mixed plan and bulk + remainder plan gives the same bits, and a row's bits do not
     depend on the batch it travels in (M = 64 rides the 16x16 kernel)."""
     m, n, k = 3000, 768, 768
-    a, w, b = _rand(m, k, seed=21), _rand(n, k, seed=22, scale=k ** -0.5), _rand(n, seed=23)
+    a, w, b = rand(m, k, seed=21), rand(n, k, seed=22, scale=k ** -0.5), rand(n, seed=23)
     epi, kepi = EPI_BIAS_QUICKGELU, 11
     run = lambda x=a: engine.gemm(x, w, b, epilogue=epi).cpu()  # noqa: E731
     base = run()
-    _close(base, _quick64(a.double() @ w.double().T + b.double()))
+    close(base, _quick64(a.double() @ w.double().T + b.double()))
     try:
         for cfg in (0, 1, 2, 3, 8, 9, 10, 11, 12, 13, 14, 15):
             engine.tuner_force_config("f32", cfg)
@@ -168,7 +136,7 @@ def test_gemm_bf16_quickgelu(engine, m, n, k, out_bf16):
     ref = _quick64(ab.double() @ wb.double().T + b.double())
     got = engine.gemm_bf16(ab.cuda(), wb.cuda(), b, epilogue=EPI_BIAS_QUICKGELU, out_bf16=out_bf16)
     assert got.dtype == (torch.bfloat16 if out_bf16 else torch.float32)
-    print(f"max abs err {_maxerr(got.float(), ref):.3e}")
+    print(f"max abs err {maxerr(got.float(), ref):.3e}")
     if out_bf16:
         assert torch.allclose(got.float().cpu().double(), ref, rtol=2 ** -7, atol=1e-3)
     else:
@@ -186,15 +154,11 @@ def test_gemm_fp8_quickgelu(engine, m, n, k, out_bf16):
     qa, qw = a8.cpu().view(torch.float8_e4m3fn).double(), w8.cpu().view(torch.float8_e4m3fn).double()
     ref = _quick64((qa @ qw.T) * (sa.cpu().double().unsqueeze(1) * sw.cpu().double().unsqueeze(0)) + b.double())
     got = engine.gemm_fp8(a8, sa, w8, sw, b, epilogue=EPI_BIAS_QUICKGELU, out_bf16=out_bf16)
-    print(f"max abs err {_maxerr(got.float(), ref):.3e}")
+    print(f"max abs err {maxerr(got.float(), ref):.3e}")
     if out_bf16:
         assert got.dtype == torch.bfloat16 and torch.allclose(got.float().cpu().double(), ref, rtol=2 ** -7, atol=1e-3)
     else:
         assert (got.cpu().double() - ref).abs().max().item() < 1e-4 * max(1.0, ref.abs().max().item())
-
-
-def _mx_scales_by_block(sc):
-    return sc.permute(1, 0, 2).reshape(sc.shape[1], -1)
 
 
 @pytest.mark.parametrize("m,n,k", [(64, 128, 128), (197, 384, 256), (1000, 520, 640), (4096, 768, 768), (333, 2304, 768)])
@@ -207,11 +171,11 @@ def test_gemm_mx8_quickgelu(engine, m, n, k, out_bf16):
     w, b = torch.randn(n, k, generator=g) * k ** -0.5, torch.randn(n, generator=g)
     a8, sa = engine.quantize_mx8(a)
     w8, sw = engine.quantize_mx8(w)
-    qa = mx8_dequantize(a8.cpu().view(torch.float8_e4m3fn), _mx_scales_by_block(sa.cpu()), torch.float64)
-    qw = mx8_dequantize(w8.cpu().view(torch.float8_e4m3fn), _mx_scales_by_block(sw.cpu()), torch.float64)
+    qa = mx8_dequantize(a8.cpu().view(torch.float8_e4m3fn), mx_scales_by_block(sa.cpu()), torch.float64)
+    qw = mx8_dequantize(w8.cpu().view(torch.float8_e4m3fn), mx_scales_by_block(sw.cpu()), torch.float64)
     ref = _quick64(qa @ qw.T + b.double())
     got = engine.gemm_mx8(a8, sa, w8, sw, b, epilogue=EPI_BIAS_QUICKGELU, out_bf16=out_bf16)
-    print(f"max abs err {_maxerr(got.float(), ref):.3e}")
+    print(f"max abs err {maxerr(got.float(), ref):.3e}")
     if out_bf16:
         assert got.dtype == torch.bfloat16 and torch.allclose(got.float().cpu().double(), ref, rtol=2 ** -7, atol=1e-3)
     else:
@@ -294,7 +258,7 @@ def test_bad_activation_and_epilogue_values_are_refused(engine):
     for bad in (-1, 2, 11):
         with pytest.raises(FernError, match="unknown activation"):
             eng.set_clip_activation(bad)
-    a, w = _rand(8, 32), _rand(8, 32)
+    a, w = rand(8, 32), rand(8, 32)
     for bad in (5, 11, -1):
         with pytest.raises(FernError, match="unknown epilogue"):
             eng.gemm(a, w, None, epilogue=bad)
@@ -306,23 +270,23 @@ def test_bad_activation_and_epilogue_values_are_refused(engine):
 @pytest.mark.parametrize("name,n_img,n_txt,tol", [("tiny", 5, 6, 2e-4), ("tiny-hd64", 5, 6, 2e-4), ("ViT-B-16", 2, 2, 1e-3)])
 def test_quickgelu_towers_match_the_in_tree_statement(name, n_img, n_txt, tol, precision):
     gold = qo.load_goldens()
-    eng, cfg = _quick_engine(name, seed=5)
+    cfg, _, eng = tower_engine(name, seed=5, quick=True)
     assert cfg.quick_gelu and eng.clip_cfg is cfg
     eng.set_precision(precision)
-    imgs = _t(synth.images(n_img, cfg, 42))
+    imgs = t(synth.images(n_img, cfg, 42))
     got = eng.encode_image(imgs)
-    ref = _t(gold[f"{name}_image"])
-    print(f"{name} {precision}: image max |d| {_maxerr(got, ref):.3e} scale {ref.abs().max().item():.2f}")
-    assert _maxerr(got, ref) < tol * max(1.0, ref.abs().max().item())
+    ref = t(gold[f"{name}_image"])
+    print(f"{name} {precision}: image max |d| {maxerr(got, ref):.3e} scale {ref.abs().max().item():.2f}")
+    assert maxerr(got, ref) < tol * max(1.0, ref.abs().max().item())
     if precision == "fp32":      # (f32x3 serves M >= 256 only: one image's 197 rows run the exact fp32 kernels, by design)
         assert torch.equal(eng.encode_image(imgs[1:2]), got[1:2])
     for tag, full in (("full", True), ("ragged", False)):
-        toks = _t(synth.captions(n_txt, cfg, 42, full_length=full))
+        toks = t(synth.captions(n_txt, cfg, 42, full_length=full))
         g, s = eng.encode_text(toks)
-        rs, rg = _t(gold[f"{name}_text_{tag}_seq"]), _t(gold[f"{name}_text_{tag}_global"])
+        rs, rg = t(gold[f"{name}_text_{tag}_seq"]), t(gold[f"{name}_text_{tag}_global"])
         scale = max(1.0, rs.abs().max().item())
-        print(f"{name} {precision}: text {tag} max |d| seq {_maxerr(s, rs):.3e} global {_maxerr(g, rg):.3e} scale {scale:.2f}")
-        assert _maxerr(s, rs) < tol * scale and _maxerr(g, rg) < tol * scale
+        print(f"{name} {precision}: text {tag} max |d| seq {maxerr(s, rs):.3e} global {maxerr(g, rg):.3e} scale {scale:.2f}")
+        assert maxerr(s, rs) < tol * scale and maxerr(g, rg) < tol * scale
     eng.close()
 
 
@@ -337,11 +301,11 @@ def test_create_model_surface(name):
     assert m.cfg.quick_gelu
     m.load_state_dict(synth.clip_state_dict(synth.CLIP_CONFIGS[base], seed=5))
     n_img = gold[f"{base}_image"].shape[0]
-    ref = _t(gold[f"{base}_image"])
-    got = m.encode_image(_t(synth.images(n_img, m.cfg, 42)))
-    assert _maxerr(got, ref) < tol * max(1.0, ref.abs().max().item())
+    ref = t(gold[f"{base}_image"])
+    got = m.encode_image(t(synth.images(n_img, m.cfg, 42)))
+    assert maxerr(got, ref) < tol * max(1.0, ref.abs().max().item())
     plain = FernCLIP(base, "cuda:0").init_random(5)
-    assert not plain.cfg.quick_gelu and not torch.equal(plain.encode_image(_t(synth.images(n_img, m.cfg, 42))), got)
+    assert not plain.cfg.quick_gelu and not torch.equal(plain.encode_image(t(synth.images(n_img, m.cfg, 42))), got)
     m.engine.close()
     plain.engine.close()
 
@@ -350,9 +314,9 @@ def test_create_model_surface(name):
 @pytest.mark.parametrize("name,n", [("tiny", 5), ("tiny-hd64", 4), ("ViT-B-16", 3)])
 def test_quickgelu_towers_bf16_precision(name, n):
     """test_clip_towers_bf16_precision's constants."""
-    eng, cfg = _quick_engine(name, seed=11)
+    cfg, _, eng = tower_engine(name, seed=11, quick=True)
     sd = ofusion.as_torch(synth.clip_state_dict(cfg, seed=11))
-    imgs, toks = _t(synth.images(n, cfg)), _t(synth.captions(n, cfg))
+    imgs, toks = t(synth.images(n, cfg)), t(synth.captions(n, cfg))
     fp32_img = eng.encode_image(imgs)
     eng.set_precision("bf16")
     got = eng.encode_image(imgs)
@@ -368,21 +332,21 @@ def test_quickgelu_towers_bf16_precision(name, n):
         ref_b, ref_f = oc.encode_image(sd, cfg, imgs, precision="bf16"), oc.encode_image(sd, cfg, imgs)
         rg_b, rs_b = oc.encode_text(sd, cfg, toks, precision="bf16")
         rg_f, _ = oc.encode_text(sd, cfg, toks)
-    print(f"bf16 {name}: image cos {_cos_err(got, ref_b):.2e} max {_maxerr(got, ref_b):.2e}; text cos {_cos_err(g, rg_b):.2e} seq max {_maxerr(s, rs_b):.2e}; "
-          f"vs fp32 {_cos_err(got, ref_f):.2e} / {_cos_err(g, rg_f):.2e}")
-    assert _cos_err(got, ref_b) < 2e-5 and _cos_err(g, rg_b) < 2e-5
-    assert _maxerr(got, ref_b) < 5e-3 * max(1.0, ref_b.abs().max().item())
-    assert _maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
-    assert _cos_err(got, ref_f) < 1e-3 and _cos_err(g, rg_f) < 1e-3
-    assert _cos_err(got, ref_f) > 0 and not torch.equal(got, fp32_img)
+    print(f"bf16 {name}: image cos {cos_err(got, ref_b):.2e} max {maxerr(got, ref_b):.2e}; text cos {cos_err(g, rg_b):.2e} seq max {maxerr(s, rs_b):.2e}; "
+          f"vs fp32 {cos_err(got, ref_f):.2e} / {cos_err(g, rg_f):.2e}")
+    assert cos_err(got, ref_b) < 2e-5 and cos_err(g, rg_b) < 2e-5
+    assert maxerr(got, ref_b) < 5e-3 * max(1.0, ref_b.abs().max().item())
+    assert maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
+    assert cos_err(got, ref_f) < 1e-3 and cos_err(g, rg_f) < 1e-3
+    assert cos_err(got, ref_f) > 0 and not torch.equal(got, fp32_img)
 
 
 @pytest.mark.parametrize("mode,name,n", [("fp8", "tiny-hd64", 4), ("fp8", "ViT-B-16", 3), ("mx8", "tiny-w256", 4), ("mx8", "tiny-hd48", 4), ("mx8", "ViT-B-16", 3)])
 def test_quickgelu_towers_fp8_and_mx8_precision(mode, name, n):
     """test_clip_towers_fp8_precision's / test_clip_towers_mx8_precision's constants."""
-    eng, cfg = _quick_engine(name, seed=11)
+    cfg, _, eng = tower_engine(name, seed=11, quick=True)
     sd = ofusion.as_torch(synth.clip_state_dict(cfg, seed=11))
-    imgs, toks = _t(synth.images(n, cfg)), _t(synth.captions(n, cfg))
+    imgs, toks = t(synth.images(n, cfg)), t(synth.captions(n, cfg))
     fp32_img = eng.encode_image(imgs)
     eng.set_precision(mode)
     got = eng.encode_image(imgs)
@@ -396,19 +360,19 @@ def test_quickgelu_towers_fp8_and_mx8_precision(mode, name, n):
         ref_q, ref_f = oc.encode_image(sd, cfg, imgs, precision=mode), oc.encode_image(sd, cfg, imgs)
         rg_q, _ = oc.encode_text(sd, cfg, toks, precision=mode)
         rg_f, _ = oc.encode_text(sd, cfg, toks)
-    print(f"{mode} {name}: vs restatement {_cos_err(got, ref_q):.2e} / {_cos_err(g, rg_q):.2e}, vs fp32 {_cos_err(got, ref_f):.2e} / {_cos_err(g, rg_f):.2e}")
-    assert _cos_err(got, ref_q) < 2e-3 and _cos_err(g, rg_q) < 2e-3
-    assert _cos_err(got, ref_q) < _cos_err(got, ref_f) and _cos_err(g, rg_q) < _cos_err(g, rg_f)
-    assert _cos_err(got, ref_f) < 1e-2 and _cos_err(g, rg_f) < 1e-2
-    assert _cos_err(got, ref_f) > 1e-5
+    print(f"{mode} {name}: vs restatement {cos_err(got, ref_q):.2e} / {cos_err(g, rg_q):.2e}, vs fp32 {cos_err(got, ref_f):.2e} / {cos_err(g, rg_f):.2e}")
+    assert cos_err(got, ref_q) < 2e-3 and cos_err(g, rg_q) < 2e-3
+    assert cos_err(got, ref_q) < cos_err(got, ref_f) and cos_err(g, rg_q) < cos_err(g, rg_f)
+    assert cos_err(got, ref_f) < 1e-2 and cos_err(g, rg_f) < 1e-2
+    assert cos_err(got, ref_f) > 1e-5
 
 
 @pytest.mark.parametrize("name,n", [("tiny-w256", 4), ("tiny-hd48", 4), ("ViT-B-16", 3)])
 def test_quickgelu_towers_mx8img_and_mx8mlp_precision(name, n):
     """test_clip_towers_mx8img_and_mx8mlp_precision's constants (MIXED_BOUNDS; the text tower is the bf16 block)."""
-    eng, cfg = _quick_engine(name, seed=11)
+    cfg, _, eng = tower_engine(name, seed=11, quick=True)
     sd = ofusion.as_torch(synth.clip_state_dict(cfg, seed=11))
-    imgs, toks = _t(synth.images(n, cfg)), _t(synth.captions(n, cfg))
+    imgs, toks = t(synth.images(n, cfg)), t(synth.captions(n, cfg))
     fp32_img = eng.encode_image(imgs)
     got, txt = {}, {}
     for mode in ("mx8img", "mx8mlp"):
@@ -425,12 +389,12 @@ def test_quickgelu_towers_mx8img_and_mx8mlp_precision(name, n):
         rg_b, rs_b = oc.encode_text(sd, cfg, toks, precision="bf16")
     for mode in ("mx8img", "mx8mlp"):
         g, s = txt[mode]
-        e_own, e_f, e_b = _cos_err(got[mode], ref[mode]), _cos_err(got[mode], ref["fp32"]), _cos_err(got[mode], ref["bf16"])
-        print(f"{mode} {name}: vs own restatement {e_own:.2e}, vs bf16 {e_b:.2e}, vs fp32 {e_f:.2e}; text vs bf16 {_cos_err(g, rg_b):.2e} / {_cos_err(s, rs_b):.2e}")
+        e_own, e_f, e_b = cos_err(got[mode], ref[mode]), cos_err(got[mode], ref["fp32"]), cos_err(got[mode], ref["bf16"])
+        print(f"{mode} {name}: vs own restatement {e_own:.2e}, vs bf16 {e_b:.2e}, vs fp32 {e_f:.2e}; text vs bf16 {cos_err(g, rg_b):.2e} / {cos_err(s, rs_b):.2e}")
         assert e_own < MIXED_BOUNDS[mode]
         assert e_own < e_f and e_own < e_b
-        assert _cos_err(g, rg_b) < 2e-5 and _cos_err(s, rs_b) < 2e-5
-        assert _maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
+        assert cos_err(g, rg_b) < 2e-5 and cos_err(s, rs_b) < 2e-5
+        assert maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
     assert not torch.equal(got["mx8img"], fp32_img) and not torch.equal(got["mx8mlp"], fp32_img)
 
 
@@ -438,10 +402,10 @@ def test_quickgelu_towers_mx8img_and_mx8mlp_precision(name, n):
 @pytest.mark.parametrize("cfg_name,b,precision", [("ViT-B-16", 64, "fp32"), ("ViT-B-16", 5, "fp32"), ("tiny", 7, "fp32"), ("ViT-B-16", 64, "mx8img"),
                                                   ("ViT-B-16", 65, "mx8img"), ("ViT-B-16", 64, "f32x3")])
 def test_encode_pair_quickgelu_is_bit_identical_to_the_two_encoder_calls(cfg_name, b, precision):
-    eng, cfg = _quick_engine(cfg_name, seed=4)
+    cfg, _, eng = tower_engine(cfg_name, seed=4, quick=True)
     eng.set_precision(precision)
-    imgs = _t(synth.images(b, cfg, 11)).cuda()
-    toks = _t(synth.captions(b, cfg, 11)).cuda()
+    imgs = t(synth.images(b, cfg, 11)).cuda()
+    toks = t(synth.captions(b, cfg, 11)).cuda()
     ref_i = eng.encode_image(imgs)
     ref_g, ref_s = eng.encode_text(toks)
     for rep in range(3):      # 1st call: shapes new to the pair launcher (two launches); later calls: tuned plans, one launch where it wins
@@ -456,7 +420,7 @@ def test_encode_pair_quickgelu_is_bit_identical_to_the_two_encoder_calls(cfg_nam
         assert all(ln in eng.tuner_export() for ln in flipped.splitlines())
         pi, pg, ps = eng.encode_pair(imgs, toks)
         assert torch.equal(pi, ref_i) and torch.equal(pg, ref_g) and torch.equal(ps, ref_s)
-    gelu, _ = _quick_engine(cfg_name, seed=4, quick=False)
+    _, _, gelu = tower_engine(cfg_name, seed=4, quick=False)
     gelu.set_precision(precision)
     assert not torch.equal(gelu.encode_image(imgs), ref_i) and not torch.equal(gelu.encode_text(toks)[0], ref_g)
     gelu.close()
@@ -472,7 +436,7 @@ def test_vit_l14_quickgelu_fp32():
     eng = FernEngine("cuda:0")
     eng.load_tensors(sd_np)
     eng.finalize_clip(cfg)
-    imgs, toks = _t(synth.images(2, cfg, 42)), _t(synth.captions(2, cfg, 42))
+    imgs, toks = t(synth.images(2, cfg, 42)), t(synth.captions(2, cfg, 42))
     got = eng.encode_image(imgs)
     g, s = eng.encode_text(toks)
     eng.close()
@@ -480,9 +444,9 @@ def test_vit_l14_quickgelu_fp32():
         ref = oc.encode_image(sd, cfg, imgs)
         rg, rs = oc.encode_text(sd, cfg, toks)
     cos = F.cosine_similarity(got.cpu(), ref, dim=-1)
-    print(f"ViT-L-14-quickgelu: image max |d| {_maxerr(got, ref):.3e} scale {ref.abs().max().item():.2f}; seq {_maxerr(s, rs):.3e}")
-    assert _maxerr(got, ref) < 1e-3 * max(1.0, ref.abs().max().item()) and (1 - cos).abs().max().item() < 1e-5
-    assert _maxerr(s, rs) < 1e-3 * max(1.0, rs.abs().max().item())
+    print(f"ViT-L-14-quickgelu: image max |d| {maxerr(got, ref):.3e} scale {ref.abs().max().item():.2f}; seq {maxerr(s, rs):.3e}")
+    assert maxerr(got, ref) < 1e-3 * max(1.0, ref.abs().max().item()) and (1 - cos).abs().max().item() < 1e-5
+    assert maxerr(s, rs) < 1e-3 * max(1.0, rs.abs().max().item())
     assert (1 - F.cosine_similarity(g.cpu(), rg, dim=-1)).abs().max().item() < 1e-5
 
 
@@ -490,20 +454,20 @@ def test_vit_l14_quickgelu_fp32():
 def test_resnet_and_rn50x4_text_with_force_quick_gelu(name, n, tol):
     """force_quick_gelu on the towers CLIP4Cir fine-tunes from: the text tower follows the patched oracle (test_modified_resnet_tower_tiny_and_rn50x4's
     bounds); the ModifiedResNet image tower has no GELU, so its output is the GELU config's, bit for bit."""
-    quick, cfg = _quick_engine(name, seed=8)
-    gelu, gcfg = _quick_engine(name, seed=8, quick=False)
+    cfg, _, quick = tower_engine(name, seed=8, quick=True)
+    gcfg, _, gelu = tower_engine(name, seed=8, quick=False)
     assert cfg.quick_gelu and not gcfg.quick_gelu
     sd = ofusion.as_torch(synth.clip_state_dict(cfg, seed=8))
-    toks = _t(synth.captions(n, cfg))
+    toks = t(synth.captions(n, cfg))
     g, s = quick.encode_text(toks)
     with torch.no_grad(), qo.quick_gelu() as oc:
         rg, rs = oc.encode_text(sd, cfg, toks)
     scale = max(1.0, rs.abs().max().item())
-    print(f"{name}: text max |d| seq {_maxerr(s, rs):.3e} global {_maxerr(g, rg):.3e} scale {scale:.2f}")
-    assert _maxerr(s, rs) < tol * scale and _maxerr(g, rg) < tol * scale
+    print(f"{name}: text max |d| seq {maxerr(s, rs):.3e} global {maxerr(g, rg):.3e} scale {scale:.2f}")
+    assert maxerr(s, rs) < tol * scale and maxerr(g, rg) < tol * scale
     assert not torch.equal(gelu.encode_text(toks)[1], s)
     if cfg.v_arch == "resnet":
-        imgs = _t(synth.images(n, cfg))
+        imgs = t(synth.images(n, cfg))
         assert torch.equal(quick.encode_image(imgs), gelu.encode_image(imgs))
     quick.close()
     gelu.close()
@@ -516,20 +480,20 @@ def test_the_setting_is_isolated_to_the_clip_towers():
     d = cfg.embed_dim
     engs = {}
     for quick in (False, True):
-        eng, _ = _quick_engine("tiny", seed=3, quick=quick)
+        _, _, eng = tower_engine("tiny", seed=3, quick=quick)
         eng.load_tensors(synth.fusion_state_dict(d, seed=4))
         eng.finalize_fusion(d)
         engs[quick] = eng
     b = 9
-    rg, rl = _t(synth.global_feats(b, d, tag="rg")), _t(synth.local_feats(b, d, tag="rl"))
-    tg, ts = _t(synth.global_feats(b, d, tag="tg")), _t(synth._normal(42, f"tseq/{d}", (b, 77, d)))
+    rg, rl = t(synth.global_feats(b, d, tag="rg")), t(synth.local_feats(b, d, tag="rl"))
+    tg, ts = t(synth.global_feats(b, d, tag="tg")), t(synth._normal(42, f"tseq/{d}", (b, 77, d)))
     for prec in ("fp32", "bf16"):
         for e in engs.values():
             e.set_precision(prec)
         assert torch.equal(engs[True].dvr_fuse(rg, rl, tg, ts), engs[False].dvr_fuse(rg, rl, tg, ts)), prec
     for e in engs.values():
         e.set_precision("fp32")
-    imgs, toks = _t(synth.images(4, cfg, 7)), _t(synth.captions(4, cfg, 7))
+    imgs, toks = t(synth.images(4, cfg, 7)), t(synth.captions(4, cfg, 7))
     gelu_i, quick_i = engs[False].encode_image(imgs), engs[True].encode_image(imgs)
     gelu_t, quick_t = engs[False].encode_text(toks)[1], engs[True].encode_text(toks)[1]
     assert not torch.equal(gelu_i, quick_i) and not torch.equal(gelu_t, quick_t)
@@ -560,8 +524,8 @@ def test_pipeline_lanes_follow_the_quickgelu_parent():
     assert clip.cfg == cfg
     model = ERN(clip, d, "cuda:0", engine=clip.engine).init_random(4)
     eng = model.engine
-    gal = eng.index_fuse(_t(synth.global_feats(3000, d, tag="pg")), _t(synth.local_feats(3000, d, tag="pgl")), True)
-    batches = [(_t(synth.images(9, cfg, 100 + j)).cuda(), _t(synth.captions(9, cfg, 100 + j)).cuda(), _t(synth.local_feats(9, d, 100 + j)).cuda())
+    gal = eng.index_fuse(t(synth.global_feats(3000, d, tag="pg")), t(synth.local_feats(3000, d, tag="pgl")), True)
+    batches = [(t(synth.images(9, cfg, 100 + j)).cuda(), t(synth.captions(9, cfg, 100 + j)).cuda(), t(synth.local_feats(9, d, 100 + j)).cuda())
                for j in range(6)]
     serial, feats = [], []
     for im, tk, lc in batches:

@@ -1,14 +1,13 @@
 """Candidate ranking on the GPU (include/fern.h: fern_sim_topk_candidates; `FernEngine.sim_topk_candidates`): every query ranks the set
 of gallery rows its own list names.
 
-Oracle: tests/candidates_oracle.py -- oracle/chain.c scores, the set semantics in numpy, the key order of `_make_keys`.  fp32 and prepared
+Oracle: tests/candidates_oracle.py -- oracle/chain.c scores, the set semantics in numpy, the key order of `make_keys`.  fp32 and prepared
 forms: scores, indices and places bit-equal.  bf16 form: bit-equal to the filtered ranking (`sim_topk(row_filter=...)`), whose scores are
 the bf16 sweep's.  Finite inputs only.
 
 The shapes are the smallest at which each path can go wrong: D = 64 / 512 / 640 take rescore.h's ring (2, 8 and 10 deep), D = 96 / 160
 have an odd number of 32-k steps (the per-lane chain); M = 1 / 6 / 33 are under one round, one round and a tail; M = 1500 / 4096 are more
 lists than the 1000-row gallery has rows, so they hold duplicates, several rounds per wave, and the largest sort; K runs below and above M."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -17,27 +16,16 @@ import torch
 
 from candidates_oracle import candidates_oracle
 from framed import SENTINEL, Framed
+from support import assert_same_bits, fresh_engine, gallery, ptr, unit
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 ERR = -1             # FERN_ERR_ARG
 
 
-def _rand(n, d, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(n, d, generator=g)
-
-
-def _unit(n, d, seed):
-    return torch.nn.functional.normalize(_rand(n, d, seed), dim=-1)
-
-
 @pytest.fixture(scope="module")
 def eng():
-    from fashionern_aaai2024_amd.engine import FernEngine
-    e = FernEngine("cuda:0")
-    yield e
-    e.close()
+    yield from fresh_engine()
 
 
 @pytest.fixture(scope="module")
@@ -48,25 +36,13 @@ def oracle():
 @functools.lru_cache(maxsize=None)
 def _data(b, n, d):
     """(q, g) on the CPU, shared by every test of a shape and never changed."""
-    return _unit(b, d, 1000 + d + b), _unit(n, d, 2000 + d)
+    return unit(b, d, 1000 + d + b), unit(n, d, 2000 + d)
 
 
 def _lists(b, m, n, seed, lo=-3, hi=None):
     """int32 [b, m]: random entries in [lo, hi) -- a few negative, a few past the gallery."""
     g = torch.Generator().manual_seed(seed)
     return torch.randint(lo, (n + 3) if hi is None else hi, (b, m), generator=g, dtype=torch.int32)
-
-
-def _equal(got, want, what):
-    names = ("scores", "idx", "place")
-    for name, a, w in zip(names, got, want):
-        a, w = a.cpu(), w.cpu()
-        assert a.shape == w.shape and a.dtype == w.dtype, f"{what}: {name} {tuple(a.shape)} {a.dtype} vs {tuple(w.shape)} {w.dtype}"
-        bits = (lambda t: t.view(torch.int32)) if a.is_floating_point() else (lambda t: t)
-        if not torch.equal(bits(a), bits(w)):
-            bad = (bits(a) != bits(w)).nonzero()
-            r, c = bad[0].tolist()
-            raise AssertionError(f"{what}: {len(bad)} {name} differ, the first at ({r}, {c}): got {a[r, c].item()!r}, want {w[r, c].item()!r}")
 
 
 # ---- fp32 against the chain oracle ---------------------------------------------------------------------------------------------------
@@ -79,7 +55,7 @@ def test_fp32_equals_the_chain_oracle(eng, oracle, D, M, K):
     cand = _lists(B, M, N, 7 * D + M)
     want = oracle.sim_topk_candidates(q, g, cand, K, places=True)
     got = eng.sim_topk_candidates(q.cuda(), g.cuda(), cand.cuda(), K, places=True)
-    _equal(got, want, f"D={D} M={M} K={K}")
+    assert_same_bits(got, want, f"D={D} M={M} K={K}")
     if M >= 1500:
         assert all(len(set(row.tolist())) < M for row in cand)      # the lists hold duplicates
 
@@ -89,7 +65,7 @@ def test_prepared_gallery_ranks_from_its_fp32_rows(eng, oracle):
     q, g = _data(B, N, D)
     cand = _lists(B, M, N, 5)
     pg = eng.prepare_gallery(g.cuda())
-    _equal(eng.sim_topk_candidates(q.cuda(), pg, cand, K, places=True), oracle.sim_topk_candidates(q, g, cand, K, places=True), "prepared")
+    assert_same_bits(eng.sim_topk_candidates(q.cuda(), pg, cand, K, places=True), oracle.sim_topk_candidates(q, g, cand, K, places=True), "prepared")
 
 
 def test_lists_and_numpy_arrays_are_accepted(eng, oracle):
@@ -97,8 +73,8 @@ def test_lists_and_numpy_arrays_are_accepted(eng, oracle):
     q, g = _data(B, N, D)
     cand = _lists(B, M, N, 6)
     want = oracle.sim_topk_candidates(q, g, cand, K)
-    _equal(eng.sim_topk_candidates(q.cuda(), g.cuda(), cand.tolist(), K), want, "list")
-    _equal(eng.sim_topk_candidates(q.cuda(), g.cuda(), cand.numpy().astype(np.int64), K), want, "numpy int64")
+    assert_same_bits(eng.sim_topk_candidates(q.cuda(), g.cuda(), cand.tolist(), K), want, "list")
+    assert_same_bits(eng.sim_topk_candidates(q.cuda(), g.cuda(), cand.numpy().astype(np.int64), K), want, "numpy int64")
 
 
 # ---- ties ----------------------------------------------------------------------------------------------------------------------------
@@ -121,7 +97,7 @@ def test_tied_rows_come_in_index_order(eng, oracle):
                 assert wi[b, p] < wi[b, p + 1]
     assert tied >= 20 * B, f"only {tied} exactly tied neighbours inside the lists"
     got = eng.sim_topk_candidates(q.cuda(), g.cuda(), cand, K, places=True)
-    _equal(got, want, "ties")
+    assert_same_bits(got, want, "ties")
     gs, gi = got[0].cpu().numpy(), got[1].cpu().numpy()
     for b in range(B):
         for p in range(K - 1):
@@ -147,19 +123,12 @@ def _cross():
     return q, g, torch.from_numpy(cand), torch.from_numpy(tags.view(np.int32))
 
 
-def _gallery(eng, form, g):
-    if form == "fp32":
-        return g.cuda()
-    pg = eng.prepare_gallery(g.cuda())
-    return pg if form == "prepared" else pg.bf16
-
-
 @pytest.mark.parametrize("K", (64, 200))
 @pytest.mark.parametrize("form", ("fp32", "prepared", "bf16"))
 def test_equals_the_filtered_ranking(eng, form, K):
     from fashionern_aaai2024_amd.engine import RowFilter
     q, g, cand, tags = _cross()
-    gal = _gallery(eng, form, g)
+    gal = gallery(eng, g, form)
     bit = torch.tensor([1 << b for b in range(XB)], dtype=torch.int64)
     flt = RowFilter(tags.cuda(), bit, bit)
     want = eng.sim_topk(q.cuda(), gal, K, row_filter=flt)
@@ -190,8 +159,8 @@ def test_equals_the_filtered_ranking(eng, form, K):
 def test_shards_merge_to_the_whole_gallery(eng, form):
     q, g, cand, _ = _cross()
     K, cut = 64, 1234
-    whole = eng.sim_topk_candidates(q.cuda(), _gallery(eng, form, g), cand.cuda(), K)
-    halves = [eng.sim_topk_candidates(q.cuda(), _gallery(eng, form, g[a:b].contiguous()), cand.cuda(), K, idx_offset=a)
+    whole = eng.sim_topk_candidates(q.cuda(), gallery(eng, g, form), cand.cuda(), K)
+    halves = [eng.sim_topk_candidates(q.cuda(), gallery(eng, g[a:b].contiguous(), form), cand.cuda(), K, idx_offset=a)
               for a, b in ((0, cut), (cut, XN))]
     merged = eng.topk_merge(torch.stack([h[0] for h in halves]), torch.stack([h[1] for h in halves]))
     assert torch.equal(merged[0], whole[0]) and torch.equal(merged[1], whole[1])
@@ -207,14 +176,10 @@ def test_query_chunks(eng, oracle, B):
     ex = cand[:, 0].clone()
     want = oracle.sim_topk_candidates(q, g, cand, K, exclude_idx=ex, places=True)
     got = eng.sim_topk_candidates(q.cuda(), g.cuda(), cand.cuda(), K, exclude_idx=ex, places=True)
-    _equal(got, want, f"B={B}")
+    assert_same_bits(got, want, f"B={B}")
 
 
 # ---- framed outputs --------------------------------------------------------------------------------------------------------------------
-def _p(x):
-    return None if x is None else C.c_void_p(x.data_ptr())
-
-
 @pytest.mark.parametrize("form", ("fp32", "bf16"))
 @pytest.mark.parametrize("M,K", ((6, 50), (33, 5), (300, 7)))
 def test_outputs_stay_inside_their_frames(eng, form, M, K):
@@ -222,19 +187,19 @@ def test_outputs_stay_inside_their_frames(eng, form, M, K):
     from fashionern_aaai2024_amd.engine import _stream
     B, N, D = 7, 1000, 512
     q, g = _data(B, N, D)
-    gal = _gallery(eng, form, g)
+    gal = gallery(eng, g, form)
     cand = _lists(B, M, N, 70 + M).cuda()
     ref = eng.sim_topk_candidates(q.cuda(), gal, cand, K, places=True)
     fs, fi, fp = (Framed(B, K, K, torch.float32, SENTINEL, DEV), Framed(B, K, K, torch.int32, SENTINEL, DEV),
                   Framed(B, M, M, torch.int32, SENTINEL, DEV))
     qd = q.cuda()
     g32, g16 = (gal, None) if form == "fp32" else (None, gal)
-    _lib.check(eng.lib.fern_sim_topk_candidates(eng._h, _p(qd), _p(g32), _p(g16), B, N, D, _p(cand), M, K, _p(fs), _p(fi), _p(fp), 0, None, None,
+    _lib.check(eng.lib.fern_sim_topk_candidates(eng._h, ptr(qd), ptr(g32), ptr(g16), B, N, D, ptr(cand), M, K, ptr(fs), ptr(fi), ptr(fp), 0, None, None,
                                                 None, None, _stream()), "fern_sim_topk_candidates")
     torch.cuda.synchronize()
     for f, what in ((fs, "out_scores"), (fi, "out_idx"), (fp, "out_place")):
         f.assert_intact(f"{what} M={M} K={K}")
-    _equal((fs.contiguous(), fi.contiguous(), fp.contiguous()), ref, f"framed {form} M={M} K={K}")
+    assert_same_bits((fs.contiguous(), fi.contiguous(), fp.contiguous()), ref, f"framed {form} M={M} K={K}")
 
 
 # ---- refusals --------------------------------------------------------------------------------------------------------------------------
@@ -282,7 +247,7 @@ def test_pipeline_submit_with_candidates(graphs):
             for want, fut in zip(direct, futures):
                 s, i = fut.wait()
                 torch.cuda.current_stream().synchronize()
-                _equal((s, i, fut.place), want, "pipeline")
+                assert_same_bits((s, i, fut.place), want, "pipeline")
     if graphs:
         assert all(lg.graph is not None for d_ in pipe._lane_graphs for lg in d_.values())
     with pytest.raises(ValueError):

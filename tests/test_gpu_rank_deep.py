@@ -13,19 +13,10 @@ import torch
 
 from oracle import chain
 from oracle import rank as orank
+from support import fresh_engine, int_unit, rand, same_bits
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _rand(n, d, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(n, d, generator=g) * scale
-
-
-def _int_unit(n, d, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-1, 2, (n, d), generator=g).float() / 8.0
 
 
 def _oracle(q, g, k, idx_offset=0, exclude_idx=None):
@@ -46,16 +37,9 @@ def _oracle(q, g, k, idx_offset=0, exclude_idx=None):
     return out_s, out_i
 
 
-def _same_bits(s, i, cs, ci):
-    return np.array_equal(i.cpu().numpy(), ci) and np.array_equal(s.cpu().numpy().view(np.uint32), cs.view(np.uint32))
-
-
 @pytest.fixture(scope="module")
 def eng():
-    from fashionern_aaai2024_amd.engine import FernEngine
-    e = FernEngine("cuda:0")
-    yield e
-    e.close()
+    yield from fresh_engine()
 
 
 @pytest.fixture(params=["auto", "lists", "dense", "plain"])
@@ -71,25 +55,25 @@ SHAPES = [(1, 1, 128, 1), (64, 63, 128, 100), (65, 1000, 512, 1024), (64, 46_000
 
 @pytest.mark.parametrize("B,N,D,K", SHAPES)
 def test_exact_form_matches_the_chain(eng, B, N, D, K):
-    q, g = _rand(B, D, seed=B + N), _rand(N, D, seed=N + D, scale=D ** -0.5)
+    q, g = rand(B, D, seed=B + N), rand(N, D, seed=N + D, scale=D ** -0.5)
     s, i = eng.sim_topk_deep(q, g, K)
     cs, ci = _oracle(q, g, K)
-    assert _same_bits(s, i, cs, ci)
+    assert same_bits((s, i), (cs, ci))
 
 
 @pytest.mark.parametrize("B,N,D,K", SHAPES)
 def test_prefiltered_form_equals_the_exact_form(eng, strategy, B, N, D, K):
-    q, g = _rand(B, D, seed=B + N), _rand(N, D, seed=N + D, scale=D ** -0.5)
+    q, g = rand(B, D, seed=B + N), rand(N, D, seed=N + D, scale=D ** -0.5)
     pg = eng.prepare_gallery(g)
     s, i = eng.sim_topk_deep(q, pg, K)
     cs, ci = _oracle(q, g, K)
-    assert _same_bits(s, i, cs, ci)
+    assert same_bits((s, i), (cs, ci))
 
 
 @pytest.mark.parametrize("prec", ["f32x3", "mx8img"])
 @pytest.mark.parametrize("B,N,D,K", [(64, 46_000, 512, 1000), (65, 1000, 640, 100)])
 def test_encoder_precision_does_not_move_the_ranking(eng, prec, B, N, D, K):
-    q, g = _rand(B, D, seed=7 + N), _rand(N, D, seed=8 + D, scale=D ** -0.5)
+    q, g = rand(B, D, seed=7 + N), rand(N, D, seed=8 + D, scale=D ** -0.5)
     pg = eng.prepare_gallery(g)
     cs, ci = _oracle(q, g, K)
     before = eng.precision
@@ -97,25 +81,25 @@ def test_encoder_precision_does_not_move_the_ranking(eng, prec, B, N, D, K):
     try:
         for gal in (g, pg):
             s, i = eng.sim_topk_deep(q, gal, K)
-            assert _same_bits(s, i, cs, ci)
+            assert same_bits((s, i), (cs, ci))
     finally:
         eng.set_precision(before)
 
 
 @pytest.mark.parametrize("B,N,D,K", [(1, 70, 128, 100), (64, 46_000, 512, 1000), (65, 3000, 640, 513), (2, 200_000, 768, 1024)])
 def test_idx_offset_and_exclusions(eng, B, N, D, K):
-    q, g = _rand(B, D, seed=11 + N), _rand(N, D, seed=12 + N, scale=D ** -0.5)
+    q, g = rand(B, D, seed=11 + N), rand(N, D, seed=12 + N, scale=D ** -0.5)
     off = 1_000
     ex = np.array([(off + (7 * r) % N) if r % 3 else -1 for r in range(B)], dtype=np.int32)
     cs, ci = _oracle(q, g, K, off, ex)
     for gal in (g, eng.prepare_gallery(g)):
         s, i = eng.sim_topk_deep(q, gal, K, idx_offset=off, exclude_idx=torch.from_numpy(ex))
-        assert _same_bits(s, i, cs, ci)
+        assert same_bits((s, i), (cs, ci))
 
 
 @pytest.mark.parametrize("B,N,D,K", [(64, 46_000, 512, 1000), (3, 1000, 128, 1024), (2, 70_000, 768, 100)])
 def test_bf16_form_ranks_the_sweep_scores(eng, B, N, D, K):
-    q, g = _rand(B, D, seed=21 + N), _rand(N, D, seed=22 + N, scale=D ** -0.5)
+    q, g = rand(B, D, seed=21 + N), rand(N, D, seed=22 + N, scale=D ** -0.5)
     pg = eng.prepare_gallery(g)
     s, i = eng.sim_topk_deep(q, pg.bf16, K)
     ref = eng.sweep_bf16_scores(q, pg, tile_max=False).cpu()
@@ -128,7 +112,7 @@ def test_bf16_form_ranks_the_sweep_scores(eng, B, N, D, K):
 
 @pytest.mark.parametrize("N,D", [(46_000, 512), (3000, 640)])
 def test_prefix_equals_the_k64_entry_points(eng, N, D):
-    q, g = _rand(64, D, seed=31), _rand(N, D, seed=32, scale=D ** -0.5)
+    q, g = rand(64, D, seed=31), rand(N, D, seed=32, scale=D ** -0.5)
     pg = eng.prepare_gallery(g)
     deep = {"f32": eng.sim_topk_deep(q, g, 1000), "pre": eng.sim_topk_deep(q, pg, 1000), "bf16": eng.sim_topk_deep(q, pg.bf16, 1000)}
     for k in (1, 50, 64):
@@ -141,12 +125,12 @@ def test_prefix_equals_the_k64_entry_points(eng, N, D):
 @pytest.mark.parametrize("B,N,D,K", [(8, 46_000, 512, 1000), (5, 3000, 128, 100), (3, 1000, 64, 1024)])
 def test_tie_floods(eng, B, N, D, K):
     """Thousands of exact ties ({-1, 0, 1} / 8 operands) and a gallery of one repeated row: the fallback's territory."""
-    q = _int_unit(B, D, seed=41)
-    for g in (_int_unit(N, D, seed=42), _int_unit(1, D, seed=43).repeat(N, 1)):
+    q = int_unit(B, D, seed=41)
+    for g in (int_unit(N, D, seed=42), int_unit(1, D, seed=43).repeat(N, 1)):
         cs, ci = _oracle(q, g, K)
         for gal in (g, eng.prepare_gallery(g)):
             s, i = eng.sim_topk_deep(q, gal, K)
-            assert _same_bits(s, i, cs, ci)
+            assert same_bits((s, i), (cs, ci))
 
 
 _CAP_CHILD = r"""
@@ -154,27 +138,28 @@ import sys, numpy as np, torch
 sys.path.insert(0, sys.argv[1])
 sys.path.insert(0, sys.argv[1] + "/tests")
 from fashionern_aaai2024_amd.engine import FernEngine
-from test_gpu_rank_deep import _rand, _int_unit, _oracle, _same_bits
+from support import int_unit, rand, same_bits
+from test_gpu_rank_deep import _oracle
 eng = FernEngine("cuda:0")
 bad = 0
 for B, N, D, K, off in [(64, 46000, 512, 1000, 0), (65, 1000, 640, 100, 5), (3, 20000, 128, 1024, 0)]:
-    q, g = _rand(B, D, seed=B), _rand(N, D, seed=N, scale=D ** -0.5)
+    q, g = rand(B, D, seed=B), rand(N, D, seed=N, scale=D ** -0.5)
     ex = np.array([off + (r * 13) % N for r in range(B)], dtype=np.int32)
     cs, ci = _oracle(q, g, K, off, ex)
     pg = eng.prepare_gallery(g)
     for gal in (g, pg):
         s, i = eng.sim_topk_deep(q, gal, K, idx_offset=off, exclude_idx=torch.from_numpy(ex))
-        bad += not _same_bits(s, i, cs, ci)
+        bad += not same_bits((s, i), (cs, ci))
     s, i = eng.sim_topk_deep(q, pg.bf16, K)
     ref = eng.sweep_bf16_scores(q, pg, tile_max=False).cpu()
     order = torch.sort(ref, dim=1, descending=True, stable=True)
     kk = min(K, N)
     bad += not torch.equal(i.cpu()[:, :kk], order.indices[:, :kk].int())
-g = _int_unit(5000, 128, seed=3)
-q = _int_unit(4, 128, seed=4)
+g = int_unit(5000, 128, seed=3)
+q = int_unit(4, 128, seed=4)
 cs, ci = _oracle(q, g, 700)
 s, i = eng.sim_topk_deep(q, g, 700)
-bad += not _same_bits(s, i, cs, ci)
+bad += not same_bits((s, i), (cs, ci))
 print("mismatches", bad)
 sys.exit(1 if bad else 0)
 """
@@ -202,7 +187,7 @@ def test_wide_merge_matches_the_oracle(eng, R, K):
 
 
 def test_sharded_deep_ranking_merges_to_the_whole_gallery(eng):
-    q, g = _rand(16, 512, seed=51), _rand(46_000, 512, seed=52, scale=512 ** -0.5)
+    q, g = rand(16, 512, seed=51), rand(46_000, 512, seed=52, scale=512 ** -0.5)
     whole = eng.sim_topk_deep(q, g, 1000)
     bounds = np.linspace(0, g.shape[0], 9).astype(int)
     parts = [eng.sim_topk_deep(q, g[a:b], 1000, idx_offset=int(a)) for a, b in zip(bounds[:-1], bounds[1:])]
@@ -211,7 +196,7 @@ def test_sharded_deep_ranking_merges_to_the_whole_gallery(eng):
 
 
 def test_graph_capture_replays_identically(eng):
-    q, g = _rand(64, 512, seed=61).cuda(), _rand(46_000, 512, seed=62, scale=512 ** -0.5).cuda()
+    q, g = rand(64, 512, seed=61).cuda(), rand(46_000, 512, seed=62, scale=512 ** -0.5).cuda()
     pg = eng.prepare_gallery(g)
     for gal in (g, pg, pg.bf16):
         ref = [eng.sim_topk_deep(q, gal, 1000) for _ in range(2)]      # eager twice: the workspace has its size

@@ -2,7 +2,7 @@
 rows with (tags[n] & mask[b]) == value[b].
 
 Oracle: oracle/chain.c scores on the CPU; ineligible, excluded and out-of-gallery entries set to -inf; a stable argsort (score descending,
-index ascending) gives the order; places follow `_places` of tests/test_gpu_rank_of.py.  fp32 and prepared forms: scores and indices
+index ascending) gives the order; places follow `places` of tests/support.py.  fp32 and prepared forms: scores and indices
 bit-equal.  bf16 form: the ranking of the values `sweep_bf16_scores` returns, masked the same way.  Finite inputs only.
 
 The shapes are the smallest at which each code path can go wrong (tiles select from 16 384 rows with a ragged last tile, the
@@ -17,29 +17,12 @@ import pytest
 import torch
 
 from oracle import chain
+from support import fresh_engine, int_unit, places, rand, same_bits, strategy_forms
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KS = (1, 50, 64, 65, 1000)
 ONE = 0x80000000          # tag bit of the single row that filter kind 4 selects (the gallery's last row: the ragged last tile)
-
-
-def _rand(n, d, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(n, d, generator=g) * scale
-
-
-def _int_unit(n, d, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-1, 2, (n, d), generator=g).float() / 8.0
-
-
-def _places(scores):
-    """[B,N] int64: the place of every row in the stable ranking of `scores` (numpy [B,N])."""
-    order = np.argsort(-scores, axis=1, kind="stable")
-    place = np.empty_like(order)
-    np.put_along_axis(place, order, np.broadcast_to(np.arange(scores.shape[1]), order.shape), axis=1)
-    return place
 
 
 def _tags(n, interleaved):
@@ -104,11 +87,6 @@ def _topk(masked, k, idx_offset=0):
     return sc, idx
 
 
-def _same(got, want):
-    s, i = got
-    return np.array_equal(i.cpu().numpy(), want[1]) and np.array_equal(s.cpu().numpy().view(np.int32), want[0].view(np.int32))
-
-
 def _row_filter(tags, mask, value, signed=False):
     from fashionern_aaai2024_amd.engine import RowFilter
     if signed:      # int32 tensors, taken as bits
@@ -119,16 +97,7 @@ def _row_filter(tags, mask, value, signed=False):
 
 @pytest.fixture(scope="module")
 def eng():
-    from fashionern_aaai2024_amd.engine import FernEngine
-    e = FernEngine("cuda:0")
-    yield e
-    e.close()
-
-
-def _forms(eng, g):
-    pg = eng.prepare_gallery(g)
-    return [("fp32", g.cuda(), None), ("prepared-auto", pg, "auto"), ("prepared-plain", pg, "plain"), ("prepared-lists", pg, "lists"),
-            ("prepared-dense", pg, "dense"), ("bf16", pg.bf16, None)]
+    yield from fresh_engine()
 
 
 def _call(eng, label, q, gal, k, **kw):
@@ -144,7 +113,7 @@ def _check_all_forms(eng, q, g, cases, ks=KS):
     qd = q.cuda()
     bad, wants = [], {}
     try:
-        for label, gal, strategy in _forms(eng, g):
+        for label, gal, strategy in strategy_forms(eng, g):
             if strategy:
                 eng.set_rank_strategy(strategy)
             base = exact if label != "bf16" else eng.sweep_bf16_scores(qd, eng.prepare_gallery(g), tile_max=False).cpu().numpy()
@@ -156,7 +125,7 @@ def _check_all_forms(eng, q, g, cases, ks=KS):
                 exd = None if ex is None else torch.from_numpy(ex)
                 for k in ks:
                     got = _call(eng, label, qd, gal, k, idx_offset=off, exclude_idx=exd, row_filter=flt)
-                    if not _same(got, (want[0][:, :k], want[1][:, :k])):
+                    if not same_bits(got, (want[0][:, :k], want[1][:, :k])):
                         bad.append((label, name, k))
     finally:
         eng.set_rank_strategy("auto")
@@ -172,7 +141,7 @@ SHAPES = [(8, 16_390, 64), (5, 3_000, 128), (64, 63, 128), (65, 1_000, 64), (65,
 def test_mixed_filters_equal_the_masked_chain_ranking(eng, B, N, D):
     """Filters (a)-(e) mixed over the batch, tags once in contiguous segments and once interleaved, and (g) combined with exclude_idx
     and an idx_offset -- the excluded row is ineligible for some queries, eligible for others, the single eligible row for kind 4."""
-    q, g = _rand(B, D, seed=B + N), _rand(N, D, seed=N + D, scale=D ** -0.5)
+    q, g = rand(B, D, seed=B + N), rand(N, D, seed=N + D, scale=D ** -0.5)
     off = 1_000
     cases = []
     for shift in range(0, 6 if B < 6 else 1, max(B, 1)):      # small batches: several passes, so that every kind is used
@@ -190,7 +159,7 @@ def test_mixed_filters_equal_the_masked_chain_ranking(eng, B, N, D):
 
 @pytest.mark.parametrize("B,N,D", [(8, 16_390, 64), (65, 1_000, 64), (3, 1_000, 640), (1, 1, 64)])
 def test_all_pass_filter_equals_the_unfiltered_call(eng, B, N, D):
-    q, g = _rand(B, D, seed=3 + N).cuda(), _rand(N, D, seed=4 + N, scale=D ** -0.5)
+    q, g = rand(B, D, seed=3 + N).cuda(), rand(N, D, seed=4 + N, scale=D ** -0.5)
     tags = _tags(N, True)
     zero = np.zeros(B, dtype=np.uint32)
     flt = _row_filter(tags, zero, zero)
@@ -198,7 +167,7 @@ def test_all_pass_filter_equals_the_unfiltered_call(eng, B, N, D):
     scalar = RowFilter(torch.from_numpy(tags).cuda(), 0, 0)
     ex = torch.tensor([(3 * r) % N for r in range(B)], dtype=torch.int32)
     try:
-        for label, gal, strategy in _forms(eng, g):
+        for label, gal, strategy in strategy_forms(eng, g):
             if strategy:
                 eng.set_rank_strategy(strategy)
             for k in KS:
@@ -215,7 +184,7 @@ def test_all_pass_filter_equals_the_unfiltered_call(eng, B, N, D):
 def test_adversarial_gallery_whose_unfiltered_top_is_all_ineligible(eng, B, N, D):
     """(f) every ineligible row gets a component along the queries' directions, so the unfiltered top-K of every query consists of
     ineligible rows only; the filtered result is still the chain's ranking of the eligible ones."""
-    q, g = _rand(B, D, seed=11), _rand(N, D, seed=12, scale=D ** -0.5)
+    q, g = rand(B, D, seed=11), rand(N, D, seed=12, scale=D ** -0.5)
     tags = _tags(N, True)
     mask, value = np.full(B, 3, dtype=np.uint32), np.zeros(B, dtype=np.uint32)      # category 0 of the interleaved three
     elig = _eligible(tags, mask, value)
@@ -232,7 +201,7 @@ def test_adversarial_gallery_whose_unfiltered_top_is_all_ineligible(eng, B, N, D
 @pytest.mark.parametrize("B,N,D", [(8, 16_390, 64), (5, 3_000, 128)])
 def test_tie_heavy_galleries_run_the_fallbacks_filtered(eng, B, N, D):
     """Scores in multiples of 1/64 with thousands of ties: the select kernels have no room and the exact fallbacks rank -- filtered."""
-    q, g = _int_unit(B, D, seed=41), _int_unit(N, D, seed=42)
+    q, g = int_unit(B, D, seed=41), int_unit(N, D, seed=42)
     cat = (np.full(B, 3, dtype=np.uint32), (np.arange(B) % 3).astype(np.uint32))
     groups = (N + 5) // 6
     grp = (np.full(B, 0x7FFFFFFC, dtype=np.uint32), (((11 * np.arange(B) + 2) % groups) << 2).astype(np.uint32))
@@ -249,7 +218,7 @@ import test_gpu_rank_filtered as t
 from fashionern_aaai2024_amd.engine import FernEngine
 eng = FernEngine("cuda:0")
 B, N, D = 5, 3000, 128
-q, g = t._rand(B, D, seed=1), t._rand(N, D, seed=2, scale=D ** -0.5)
+q, g = t.rand(B, D, seed=1), t.rand(N, D, seed=2, scale=D ** -0.5)
 m, v = t._filters(B, N, 1)
 t._check_all_forms(eng, q, g, [("interleaved", t._tags(N, True), m, v, 0, None), ("segments", t._tags(N, False), m, v, 0, None)], ks=(50, 65, 1000))
 print("ok")
@@ -292,7 +261,7 @@ def _expected_ranks(place, t, elig):
 
 @pytest.mark.parametrize("B,N,D", [(8, 16_390, 64), (65, 1_000, 64), (5, 3_000, 128)])
 def test_rank_of_is_the_place_in_the_masked_ranking(eng, B, N, D):
-    q, g = _rand(B, D, seed=31 + N), _rand(N, D, seed=32 + N, scale=D ** -0.5)
+    q, g = rand(B, D, seed=31 + N), rand(N, D, seed=32 + N, scale=D ** -0.5)
     pg = eng.prepare_gallery(g)
     tags = _tags(N, True)
     mask, value = _filters(B, N, 1)
@@ -301,7 +270,7 @@ def test_rank_of_is_the_place_in_the_masked_ranking(eng, B, N, D):
     exact = chain.chain_scores(q.numpy(), g.numpy())
     approx = eng.sweep_bf16_scores(q.cuda(), pg, tile_max=False).cpu().numpy()
     for label, gal, base in (("fp32", g.cuda(), exact), ("prepared", pg, exact), ("bf16", pg.bf16, approx)):
-        place = _places(_masked(base, elig))
+        place = places(_masked(base, elig))
         for m in (1, 8, 13):
             t = _rank_targets(B, N, m, seed=m, place=place, elig=elig)
             got = eng.rank_of(q.cuda(), gal, torch.from_numpy(t), row_filter=flt)
@@ -317,7 +286,7 @@ def test_rank_of_is_the_place_in_the_masked_ranking(eng, B, N, D):
 def test_filtered_counts_of_two_shards_add_up(eng, form):
     from fashionern_aaai2024_amd.engine import RowFilter
     B, N, D, m = 8, 16_390, 64, 5
-    q, g = _rand(B, D, seed=51).cuda(), _rand(N, D, seed=52, scale=D ** -0.5)
+    q, g = rand(B, D, seed=51).cuda(), rand(N, D, seed=52, scale=D ** -0.5)
     gal = g.cuda() if form == "fp32" else eng.gallery_to_bf16(g)
     tags = torch.from_numpy(_tags(N, True).view(np.int32)).cuda()          # int32 bits: torch indexes and slices them on the device
     mask, value = (torch.from_numpy(a.view(np.int32)).cuda() for a in _filters(B, N, 1))

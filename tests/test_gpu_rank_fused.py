@@ -14,14 +14,10 @@ import pytest
 import torch
 
 from oracle import rank as orank
+from support import assert_same_order_up_to_near_ties, int_unit
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _int_unit(n, d, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-1, 2, (n, d), generator=g).float() / 8.0
 
 
 def sample_row(c, r):
@@ -45,7 +41,7 @@ def test_sample_misses_every_good_row_overflow_then_exact_pass(engine):
     lists, scores from the sweep's own MFMA sequence).  The other queries take the normal path in the same launch.  (A query's
     candidates live in 256 lists of 64 entries: ~96k survivors are ~375 per list.)"""
     n, d, k = 100_000, 64, 50
-    q, g = _int_unit(4, d, 21), _int_unit(n, d, 22)
+    q, g = int_unit(4, d, 21), int_unit(n, d, 22)
     q[0] = torch.where(q[0] == 0, torch.full_like(q[0], 0.125), q[0])
     s, r = plan(n)
     assert r == 24 and (n - s) // 256 > 64
@@ -65,8 +61,8 @@ def test_all_scores_equal_only_the_index_breaks_ties(engine, n):
     """Every gallery row is the same vector: all scores tie, the ranking is 0, 1, 2, ... and the bound has to cut on the
     index part of the key or every row would survive."""
     d, k = 64, 50
-    q = _int_unit(3, d, 5)
-    g = _int_unit(1, d, 6).repeat(n, 1)
+    q = int_unit(3, d, 5)
+    g = int_unit(1, d, 6).repeat(n, 1)
     rs, ri = orank.cosine_topk(q, g, k)
     sc, ix = engine.sim_topk(q, g, k)
     engine.sync()
@@ -79,7 +75,7 @@ def test_excluded_row_inside_the_sample_does_not_tighten_the_bound(engine):
     rows of the bound, the true K-th result could be filtered out."""
     n, d, k = 70_000, 64, 5
     s, r = plan(n)
-    q, g = _int_unit(6, d, 31), _int_unit(n, d, 32)
+    q, g = int_unit(6, d, 31), int_unit(n, d, 32)
     ex_rows = [sample_row(c, r) for c in (0, 17, 500, s - 1, 3, 9)]
     for b, row in enumerate(ex_rows):
         g[row] = torch.sign(q[b]) / 8.0 + (q[b] == 0) * 0.125     # the best possible score for query b
@@ -96,7 +92,7 @@ def test_excluded_row_inside_the_sample_does_not_tighten_the_bound(engine):
 def test_bf16_sweep_query_blocks_and_ragged_batches(engine, b):
     """fern_sim_topk_bf16 runs one sweep launch per 64-query block over shared plan buffers."""
     n, d, k = 30_011, 128, 50
-    q, g = _int_unit(b, d, 41), _int_unit(n, d, 42)
+    q, g = int_unit(b, d, 41), int_unit(n, d, 42)
     rs, ri = orank.cosine_topk(q, g, k)
     sc, ix = engine.sim_topk_bf16(q, engine.gallery_to_bf16(g), k)
     assert torch.equal(ix.cpu(), ri) and torch.equal(sc.cpu(), rs)
@@ -105,7 +101,7 @@ def test_bf16_sweep_query_blocks_and_ragged_batches(engine, b):
 def test_large_query_batches_cross_the_plan_chunk(engine):
     """B > 1024 crosses the per-plan query chunk; B = 1024 / K = 51 with exclusions is BASELINE config C4's shape."""
     n, d = 21_552, 64
-    q, g = _int_unit(1300, d, 51), _int_unit(n, d, 52)
+    q, g = int_unit(1300, d, 51), int_unit(n, d, 52)
     ex = torch.randint(0, n, (1300,), generator=torch.Generator().manual_seed(3), dtype=torch.int32)
     rs, ri = orank.cosine_topk(q, g, 51, exclude_idx=ex)
     sc, ix = engine.sim_topk(q, g, 51, exclude_idx=ex)
@@ -123,8 +119,7 @@ def test_random_unit_rows_identical_order_up_to_fp32_near_ties(engine):
     sc, ix = sc.cpu(), ix.cpu()
     assert (sc - rs).abs().max().item() < 1e-5
     full = q.double() @ g.double().T
-    for row, pos in (ix != ri).nonzero().tolist():
-        assert abs(full[row, ix[row, pos]].item() - full[row, ri[row, pos]].item()) < 2e-6
+    assert_same_order_up_to_near_ties(full, ix, ri, gap=2e-6)
 
 
 _SCRIPT = r"""
@@ -183,9 +178,9 @@ def test_periodic_gallery_does_not_pile_into_one_list(engine):
     """ADVICE r2: a base set tiled up to a large gallery (period a multiple of 256) puts every copy of a top item 256k rows apart;
     with list = row % 256 they all shared one list and overflowed it twice.  Lists are now chosen by a hash of the row's 256-block,
     and whatever still overflows is ranked by the exact pass: the top-50 are the 50 lowest-index copies of the best items."""
-    base = _int_unit(1024, 64, 31)
+    base = int_unit(1024, 64, 31)
     g = base.repeat(300, 1)                                # 307 200 rows, period 1024
-    q = _int_unit(5, 64, 32)
+    q = int_unit(5, 64, 32)
     rs, ri = orank.cosine_topk(q, g, 50)
     s, i = engine.sim_topk(q, g, 50)
     assert torch.equal(i.cpu(), ri) and torch.equal(s.cpu(), rs)

@@ -12,18 +12,9 @@ import torch
 
 import items_oracle as io
 from oracle import chain
+from support import fresh_engine, gallery, int_unit, rand, same_bits
 
 pytestmark = pytest.mark.gpu
-
-
-def _rand(n, d, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(n, d, generator=g) * scale
-
-
-def _int_unit(n, d, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-1, 2, (n, d), generator=g).float() / 8.0
 
 
 def _runs(sizes, n_items, seed):
@@ -59,17 +50,14 @@ CASES = [(name, form) for name, sh in SHAPES.items() for form in sh[6]]
 
 @pytest.fixture(scope="module")
 def eng():
-    from fashionern_aaai2024_amd.engine import FernEngine
-    e = FernEngine("cuda:0")
-    yield e
-    e.close()
+    yield from fresh_engine()
 
 
 @functools.lru_cache(maxsize=None)
 def _case(name):
     """(q, g, items, chain scores) of a shape: computed once, shared, never written to."""
     B, N, D, K, G, layout, _ = SHAPES[name]
-    q, g = _rand(B, D, seed=B + N), _rand(N, D, seed=N + D, scale=D ** -0.5)
+    q, g = rand(B, D, seed=B + N), rand(N, D, seed=N + D, scale=D ** -0.5)
     s = chain.chain_scores(q.numpy(), g.numpy())
     s.setflags(write=False)
     return q, g, layout(), s
@@ -88,31 +76,20 @@ def _scores(eng, name, form):
     return _bf16_scores[name]
 
 
-def _gallery(eng, g, form):
-    g = g.cuda()
-    return g if form == "fp32" else eng.prepare_gallery(g) if form == "prepared" else eng.prepare_gallery(g).bf16
-
-
 def _item_map(items, n_items):
     from fashionern_aaai2024_amd.engine import ItemMap
     return ItemMap(torch.from_numpy(np.asarray(items, dtype=np.int32)).cuda(), n_items)
-
-
-def _same(got, want):
-    s, i, t = (x.cpu().numpy() for x in got)
-    ws, wi, wt = want
-    return np.array_equal(i, wi) and np.array_equal(t, wt) and np.array_equal(s.view(np.uint32), ws.view(np.uint32))
 
 
 @pytest.mark.parametrize("name,form", CASES)
 def test_topk_items_equals_the_oracle(eng, name, form):
     B, N, D, K, G, _, _ = SHAPES[name]
     q, g, items, _ = _case(name)
-    got = eng.sim_topk_items(q.cuda(), _gallery(eng, g, form), _item_map(items, G), K)
+    got = eng.sim_topk_items(q.cuda(), gallery(eng, g, form), _item_map(items, G), K)
     want = io.item_topk(io.masked_scores(_scores(eng, name, form)), items, G, K)
-    assert _same(got, want)
+    assert same_bits(got, want)
     if name == "identity":                                   # every row its own item: the row ranking itself
-        s, i = eng.sim_topk_deep(q.cuda(), _gallery(eng, g, form), K)
+        s, i = eng.sim_topk_deep(q.cuda(), gallery(eng, g, form), K)
         assert torch.equal(got[1], i) and torch.equal(got[0].view(torch.int32), s.view(torch.int32)) and torch.equal(got[2], i)
 
 
@@ -120,7 +97,7 @@ def test_topk_items_equals_the_oracle(eng, name, form):
 def test_small_galleries_equal_the_deduplicated_deep_list(eng, name, form):
     B, N, D, K, G, _, _ = SHAPES[name]
     q, g, items, _ = _case(name)
-    gal = _gallery(eng, g, form)
+    gal = gallery(eng, g, form)
     s, i = (x.cpu().numpy() for x in eng.sim_topk_deep(q.cuda(), gal, N))
     ws = np.full((B, K), -np.inf, dtype=np.float32)
     wi = np.full((B, K), -1, dtype=np.int32)
@@ -132,14 +109,14 @@ def test_small_galleries_equal_the_deduplicated_deep_list(eng, name, form):
                 seen.add(items[r])
                 ws[b, o], wi[b, o], wt[b, o] = sc, r, items[r]
                 o += 1
-    assert _same(eng.sim_topk_items(q.cuda(), gal, _item_map(items, G), K), (ws, wi, wt))
+    assert same_bits(eng.sim_topk_items(q.cuda(), gal, _item_map(items, G), K), (ws, wi, wt))
 
 
 # ---- contract cases at (3, 1 000, 128) -------------------------------------------------------------------------------------------
 def test_k_beyond_the_items_is_padded(eng):
     q, g, items, s = _case("uneven")
     got = eng.sim_topk_items(q.cuda(), g.cuda(), _item_map(items, 37), 100)
-    assert _same(got, io.item_topk(io.masked_scores(s), items, 37, 100))
+    assert same_bits(got, io.item_topk(io.masked_scores(s), items, 37, 100))
     s_, i_, t_ = (x.cpu().numpy() for x in got)
     assert (i_[:, 37:] == -1).all() and (t_[:, 37:] == -1).all() and np.isneginf(s_[:, 37:]).all() and (i_[:, :37] >= 0).all()
 
@@ -154,7 +131,7 @@ def test_idx_offset_and_exclusions_move_the_representative(eng):
     ex = np.array([best_of_big[0] + off, 3 + off, -1], dtype=np.int32)
     got = eng.sim_topk_items(q.cuda(), g.cuda(), _item_map(items, 37), 37, idx_offset=off, exclude_idx=torch.from_numpy(ex))
     want = io.item_topk(io.masked_scores(s, off, ex), items, 37, 37, off)
-    assert _same(got, want)
+    assert same_bits(got, want)
     i_, t_ = got[1].cpu().numpy(), got[2].cpu().numpy()
     rep0 = int(i_[0][list(t_[0]).index(big)]) - off
     assert rep0 != best_of_big[0] and items[rep0] == big     # represented by its next row
@@ -177,16 +154,16 @@ def test_row_filter_removes_items_and_rows(eng, form):
     q, g, items, _ = _case("uneven")
     s = _scores(eng, "uneven", form)
     flt, elig = _filter_case(items)
-    got = eng.sim_topk_items(q.cuda(), _gallery(eng, g, form), _item_map(items, 37), 37, row_filter=flt)
-    assert _same(got, io.item_topk(io.masked_scores(s, eligible=elig), items, 37, 37))
+    got = eng.sim_topk_items(q.cuda(), gallery(eng, g, form), _item_map(items, 37), 37, row_filter=flt)
+    assert same_bits(got, io.item_topk(io.masked_scores(s, eligible=elig), items, 37, 37))
     t_ = got[2].cpu().numpy()
     assert (t_[0][t_[0] >= 0] % 2 == 0).all() and (t_[0] >= 0).sum() < 37
     assert (got[1].cpu().numpy()[1][t_[1] >= 0] % 2 == 1).all()      # odd rows only: singletons on even rows are gone too
     # mask = value = 0 is the unfiltered call
     from fashionern_aaai2024_amd.engine import RowFilter
     open_ = RowFilter(flt.tags, 0, 0)
-    a = eng.sim_topk_items(q.cuda(), _gallery(eng, g, form), _item_map(items, 37), 37, row_filter=open_)
-    b = eng.sim_topk_items(q.cuda(), _gallery(eng, g, form), _item_map(items, 37), 37)
+    a = eng.sim_topk_items(q.cuda(), gallery(eng, g, form), _item_map(items, 37), 37, row_filter=open_)
+    b = eng.sim_topk_items(q.cuda(), gallery(eng, g, form), _item_map(items, 37), 37)
     assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(a, b))
 
 
@@ -197,7 +174,7 @@ def test_ids_outside_the_range_are_ignored(eng):
     ids[5::11] = 37
     ids[500:520] = 1 << 30
     got = eng.sim_topk_items(q.cuda(), g.cuda(), _item_map(ids, 37), 64)
-    assert _same(got, io.item_topk(io.masked_scores(s), ids, 37, 64))
+    assert same_bits(got, io.item_topk(io.masked_scores(s), ids, 37, 64))
     i_ = got[1].cpu().numpy()
     assert not np.isin(i_[i_ >= 0] % 7, [0]).any()
     ranks = eng.item_rank_of(q.cuda(), g.cuda(), _item_map(ids, 37), torch.tensor([[-1, 37, 1 << 30, int(items[100])]] * 3, dtype=torch.int32))
@@ -207,8 +184,8 @@ def test_ids_outside_the_range_are_ignored(eng):
 @pytest.mark.parametrize("layout", ["interleaved", "contiguous"])
 def test_all_ties_are_broken_by_row_index(eng, layout):
     N, D = 1000, 128
-    g = _int_unit(1, D, seed=3).repeat(N, 1)
-    q = _int_unit(3, D, seed=4)
+    g = int_unit(1, D, seed=3).repeat(N, 1)
+    q = int_unit(3, D, seed=4)
     items = (np.arange(N) % 10 if layout == "interleaved" else np.arange(N) // 100).astype(np.int32)
     s, i, t = (x.cpu().numpy() for x in eng.sim_topk_items(q.cuda(), g.cuda(), _item_map(items, 10), 10))
     first = np.arange(10) if layout == "interleaved" else np.arange(10) * 100
@@ -221,7 +198,7 @@ def _flood():
     """30 000 copies of the best-scoring row, spread over 5 000 items (six rows each, interleaved), then 4 001 ordinary items: after the
     reduction 5 000 representatives tie at the top -- more than the select kernel collects -- so the radix fallback ranks them."""
     B, N, D = 2, 46_001, 768
-    q, g = _int_unit(B, D, seed=31), _int_unit(N, D, seed=32)
+    q, g = int_unit(B, D, seed=31), int_unit(N, D, seed=32)
     g[:30_000] = (q[0] + q[1]).sign() / 8.0
     items = np.concatenate([np.arange(30_000) % 5000, 5000 + (np.arange(N - 30_000) // 4)]).astype(np.int32)
     s = chain.chain_scores(q.numpy(), g.numpy())
@@ -235,10 +212,10 @@ def test_tie_flood_reaches_the_fallback(eng, form):
     G, K = 5000 + 4001, 1000
     if form == "bf16":                                       # operands in {-1, 0, 1} / 8 are exact in bf16: the sweep's values still tie
         s = eng.sweep_bf16_scores(q.cuda(), eng.prepare_gallery(g.cuda()), tile_max=False).cpu().numpy()
-    got = eng.sim_topk_items(q.cuda(), _gallery(eng, g, form), _item_map(items, G), K)
-    assert _same(got, io.item_topk(io.masked_scores(s), items, G, K))
+    got = eng.sim_topk_items(q.cuda(), gallery(eng, g, form), _item_map(items, G), K)
+    assert same_bits(got, io.item_topk(io.masked_scores(s), items, G, K))
     assert np.array_equal(got[1].cpu().numpy(), np.tile(np.arange(K), (2, 1)))
-    ranks = eng.item_rank_of(q.cuda(), _gallery(eng, g, form), _item_map(items, G), torch.tensor([[4999, 0, 5000]] * 2, dtype=torch.int32))
+    ranks = eng.item_rank_of(q.cuda(), gallery(eng, g, form), _item_map(items, G), torch.tensor([[4999, 0, 5000]] * 2, dtype=torch.int32))
     assert np.array_equal(ranks.cpu().numpy(), io.item_ranks(io.masked_scores(s), items, G, [[4999, 0, 5000]] * 2))
     assert ranks[0, 0] == 4999 and ranks[0, 1] == 0
 
@@ -248,7 +225,7 @@ def test_tie_flood_reaches_the_fallback(eng, form):
 def test_item_rank_is_the_place_in_the_full_item_list(eng, name, form):
     B, N, D, K, G, _, _ = SHAPES[name]
     q, g, items, _ = _case(name)
-    gal, im = _gallery(eng, g, form), _item_map(items, G)
+    gal, im = gallery(eng, g, form), _item_map(items, G)
     _, _, t = eng.sim_topk_items(q.cuda(), gal, im, G)
     targets = torch.arange(G, dtype=torch.int32).repeat(B, 1)
     ranks = eng.item_rank_of(q.cuda(), gal, im, targets).cpu().numpy()
@@ -290,7 +267,7 @@ def test_graph_capture_replays_on_new_queries_and_exclusions(eng):
     B, N, D, K, G, _, _ = SHAPES["interleaved"]
     _, g, items, _ = _case("interleaved")
     g, im = g.cuda(), _item_map(items, G)
-    q = _rand(B, D, seed=61).cuda()
+    q = rand(B, D, seed=61).cuda()
     ex = torch.tensor([(3 * r) % N for r in range(B)], dtype=torch.int32).cuda()
     eng.sim_topk_items(q, g, im, K, exclude_idx=ex)          # one eager call: the workspace exists
     stream = torch.cuda.Stream()
@@ -299,7 +276,7 @@ def test_graph_capture_replays_on_new_queries_and_exclusions(eng):
     with torch.cuda.graph(graph, stream=stream):
         out = eng.sim_topk_items(q, g, im, K, exclude_idx=ex)
     for seed in (63, 64):
-        q.copy_(_rand(B, D, seed=seed))
+        q.copy_(rand(B, D, seed=seed))
         ex.copy_(torch.tensor([(seed * r + 1) % N for r in range(B)], dtype=torch.int32))
         graph.replay()
         torch.cuda.synchronize()
@@ -307,7 +284,7 @@ def test_graph_capture_replays_on_new_queries_and_exclusions(eng):
         want = eng.sim_topk_items(q, g, im, K, exclude_idx=ex)
         assert all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(out, want))
         s = chain.chain_scores(q.cpu().numpy(), g.cpu().numpy())
-        assert _same(out, io.item_topk(io.masked_scores(s, 0, ex.cpu().numpy()), items, G, K))
+        assert same_bits(out, io.item_topk(io.masked_scores(s, 0, ex.cpu().numpy()), items, G, K))
 
 
 def test_pipeline_submit_with_items_eager_and_replayed():
@@ -359,7 +336,7 @@ def test_argument_errors_are_refused_with_a_message(eng):
     assert rank(0) == -1 and b"fern_item_rank: need G >= 1" in lib.fern_last_error()
     assert rank(5, items=None) == -1 and b"fern_item_rank: items is NULL" in lib.fern_last_error()
     assert rank(5, m=0) == -1 and b"fern_item_rank: need m >= 1" in lib.fern_last_error()
-    q, g = _rand(2, 128, seed=1).cuda(), _rand(10, 128, seed=2).cuda()
+    q, g = rand(2, 128, seed=1).cuda(), rand(10, 128, seed=2).cuda()
     with pytest.raises(FernError, match="fern_sim_topk_items"):
         eng.sim_topk_items(q, g, _item_map(np.zeros(10, np.int32), 1), 1025)
     with pytest.raises(ValueError, match="gallery has 10 rows"):

@@ -7,26 +7,9 @@ import pytest
 import torch
 
 from oracle import chain
+from support import fresh_engine, int_unit, places, rand, strategy_forms
 
 pytestmark = pytest.mark.gpu
-
-
-def _rand(n, d, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(n, d, generator=g) * scale
-
-
-def _int_unit(n, d, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-1, 2, (n, d), generator=g).float() / 8.0
-
-
-def _places(scores):
-    """[B,N] int64: the place of every row in the stable ranking of `scores` (numpy [B,N])."""
-    order = np.argsort(-scores, axis=1, kind="stable")
-    place = np.empty_like(order)
-    np.put_along_axis(place, order, np.broadcast_to(np.arange(scores.shape[1]), order.shape), axis=1)
-    return place
 
 
 def _expected(place, targets, idx_offset=0, exclude=None):
@@ -70,10 +53,7 @@ def _targets(b, n, m, seed, place=None, idx_offset=0, exclude=None):
 
 @pytest.fixture(scope="module")
 def eng():
-    from fashionern_aaai2024_amd.engine import FernEngine
-    e = FernEngine("cuda:0")
-    yield e
-    e.close()
+    yield from fresh_engine()
 
 
 SHAPES = [(1, 1, 128), (64, 63, 128), (64, 46_000, 512), (3, 46_000, 768), (1025, 1000, 640), (2, 200_000, 640)]
@@ -81,8 +61,8 @@ SHAPES = [(1, 1, 128), (64, 63, 128), (64, 46_000, 512), (3, 46_000, 768), (1025
 
 @pytest.mark.parametrize("B,N,D", SHAPES)
 def test_fp32_ranks_equal_the_chain_oracle(eng, B, N, D):
-    q, g = _rand(B, D, seed=B + N), _rand(N, D, seed=N + D, scale=D ** -0.5)
-    place = _places(chain.chain_scores(q.numpy(), g.numpy()))
+    q, g = rand(B, D, seed=B + N), rand(N, D, seed=N + D, scale=D ** -0.5)
+    place = places(chain.chain_scores(q.numpy(), g.numpy()))
     qd, gd = q.cuda(), g.cuda()
     ex = np.array([(7 * r) % N if r % 3 else -1 for r in range(B)], dtype=np.int32)
     for m in (1, 3, 8, 13):
@@ -98,9 +78,9 @@ def test_fp32_ranks_equal_the_chain_oracle(eng, B, N, D):
 
 @pytest.mark.parametrize("B,N,D", [(8, 46_000, 512), (5, 3000, 128), (3, 1000, 64)])
 def test_tie_heavy_galleries(eng, B, N, D):
-    q, g = _int_unit(B, D, seed=41), _int_unit(N, D, seed=42)
+    q, g = int_unit(B, D, seed=41), int_unit(N, D, seed=42)
     s = chain.chain_scores(q.numpy(), g.numpy())
-    place = _places(s)
+    place = places(s)
     t = _targets(B, N, 13, seed=3, place=place)
     valid = (t >= 0) & (t < N)
     ts = np.take_along_axis(s, np.where(valid, t, 0), axis=1)
@@ -111,19 +91,13 @@ def test_tie_heavy_galleries(eng, B, N, D):
         assert np.array_equal(got.cpu().numpy(), _expected(place, t))
 
 
-def _forms(eng, g):
-    pg = eng.prepare_gallery(g)
-    return [("fp32", g.cuda(), None), ("prepared-auto", pg, "auto"), ("prepared-plain", pg, "plain"), ("prepared-lists", pg, "lists"),
-            ("prepared-dense", pg, "dense"), ("bf16", pg.bf16, None)]
-
-
 @pytest.mark.parametrize("B,N,D", [(64, 46_000, 512), (5, 3000, 640)])
 def test_every_place_of_the_list_stages_is_its_own_rank(eng, B, N, D):
-    q, g = _rand(B, D, seed=71 + N).cuda(), _rand(N, D, seed=72 + N, scale=D ** -0.5)
+    q, g = rand(B, D, seed=71 + N).cuda(), rand(N, D, seed=72 + N, scale=D ** -0.5)
     off = 1_000
     ex = torch.tensor([off + (11 * r) % N for r in range(B)], dtype=torch.int32)
     try:
-        for label, gal, strategy in _forms(eng, g):
+        for label, gal, strategy in strategy_forms(eng, g):
             if strategy:
                 eng.set_rank_strategy(strategy)
             for idx_offset, exclude in ((0, None), (off, None), (off, ex)):
@@ -143,9 +117,9 @@ def test_every_place_of_the_list_stages_is_its_own_rank(eng, B, N, D):
 
 @pytest.mark.parametrize("B,N,D", [(64, 46_000, 512), (3, 1000, 128), (70, 20_000, 768)])
 def test_bf16_form_ranks_the_sweep_scores(eng, B, N, D):
-    q, g = _rand(B, D, seed=21 + N), _rand(N, D, seed=22 + N, scale=D ** -0.5)
+    q, g = rand(B, D, seed=21 + N), rand(N, D, seed=22 + N, scale=D ** -0.5)
     pg = eng.prepare_gallery(g)
-    place = _places(eng.sweep_bf16_scores(q, pg, tile_max=False).cpu().numpy())
+    place = places(eng.sweep_bf16_scores(q, pg, tile_max=False).cpu().numpy())
     ex = np.array([(5 * r) % N if r % 2 else -1 for r in range(B)], dtype=np.int32)
     for m in (1, 8, 13):
         t = _targets(B, N, m, seed=m, place=place, exclude=ex)
@@ -156,7 +130,7 @@ def test_bf16_form_ranks_the_sweep_scores(eng, B, N, D):
 @pytest.mark.parametrize("form", ["fp32", "bf16"])
 def test_counts_add_up_over_ragged_shards(eng, form):
     B, N, D, m = 16, 46_000, 512, 5
-    q, g = _rand(B, D, seed=51).cuda(), _rand(N, D, seed=52, scale=D ** -0.5)
+    q, g = rand(B, D, seed=51).cuda(), rand(N, D, seed=52, scale=D ** -0.5)
     gal = g.cuda() if form == "fp32" else eng.gallery_to_bf16(g)
     t = torch.from_numpy(_targets(B, N, m, seed=9))
     ex = torch.tensor([(13 * r) % N for r in range(B)], dtype=torch.int32)
@@ -177,7 +151,7 @@ def test_counts_add_up_over_ragged_shards(eng, form):
 @pytest.mark.parametrize("prec", ["f32x3", "mx8img"])
 def test_encoder_precision_does_not_move_the_ranks(eng, prec):
     B, N, D = 300, 46_000, 512                                 # M >= 256: a plain GEMM of this shape would run the f32x3 split
-    q, g = _rand(B, D, seed=7).cuda(), _rand(N, D, seed=8, scale=D ** -0.5).cuda()
+    q, g = rand(B, D, seed=7).cuda(), rand(N, D, seed=8, scale=D ** -0.5).cuda()
     t = torch.from_numpy(_targets(B, N, 8, seed=1))
     ref = eng.rank_of(q, g, t)
     before = eng.precision
@@ -190,8 +164,8 @@ def test_encoder_precision_does_not_move_the_ranks(eng, prec):
 
 def test_graph_capture_replays_on_new_inputs(eng):
     B, N, D, m = 64, 46_000, 512, 8
-    g = _rand(N, D, seed=62, scale=D ** -0.5).cuda()
-    q, t = _rand(B, D, seed=61).cuda(), torch.from_numpy(_targets(B, N, m, seed=2)).cuda()
+    g = rand(N, D, seed=62, scale=D ** -0.5).cuda()
+    q, t = rand(B, D, seed=61).cuda(), torch.from_numpy(_targets(B, N, m, seed=2)).cuda()
     ex = torch.tensor([(3 * r) % N for r in range(B)], dtype=torch.int32).cuda()
     eng.rank_of(q, g, t, exclude_idx=ex)                       # one eager call: tile choice and workspace exist
     stream = torch.cuda.Stream()
@@ -200,7 +174,7 @@ def test_graph_capture_replays_on_new_inputs(eng):
     with torch.cuda.graph(graph, stream=stream):
         out = eng.rank_of(q, g, t, exclude_idx=ex)
     for seed in (63, 64):
-        q.copy_(_rand(B, D, seed=seed))
+        q.copy_(rand(B, D, seed=seed))
         t.copy_(torch.from_numpy(_targets(B, N, m, seed=seed)))
         graph.replay()
         torch.cuda.synchronize()
@@ -213,7 +187,7 @@ def test_null_context_and_bad_shapes_are_refused(eng):
     assert b"fern_rank_keys" in lib.fern_last_error()
     assert lib.fern_rank_count(None, None, None, None, 1, 1, 32, None, 1, 0, None, None, None) == -1
     assert b"fern_rank_count" in lib.fern_last_error()
-    q, g = _rand(2, 48, seed=1).cuda(), _rand(10, 48, seed=2).cuda()
+    q, g = rand(2, 48, seed=1).cuda(), rand(10, 48, seed=2).cuda()
     with pytest.raises(Exception, match="fern_rank_keys"):
         eng.rank_keys(q, g, torch.zeros(2, 1, dtype=torch.int32))
 

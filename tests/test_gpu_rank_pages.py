@@ -11,20 +11,12 @@ import pytest
 import torch
 
 from oracle import chain
+from rank_oracle import make_keys
+from support import assert_same_bits, int_unit, rand
 
 pytestmark = pytest.mark.gpu
 
 ALL = -1                     # the cursor ~0 as int64 bits: everything is eligible
-
-
-def _rand(n, d, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(n, d, generator=g) * scale
-
-
-def _int_unit(n, d, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-1, 2, (n, d), generator=g).float() / 8.0
 
 
 def _rankings(scores, idx_offset=0, exclude=None, eligible=None):
@@ -57,20 +49,10 @@ def _slice(rankings, offsets, k):
     return s, i
 
 
-def _host(t):
-    return t.cpu().numpy() if torch.is_tensor(t) else t
-
-
 def _same(got, want):
-    gs, gi = _host(got[0]), _host(got[1])
-    assert gs.dtype == np.float32 and gi.dtype == np.int32
-    assert np.array_equal(gi, want[1])
-    assert np.array_equal(gs.view(np.uint32), want[0].view(np.uint32))
-
-
-def _orderable(s):
-    u = np.ascontiguousarray(s, dtype=np.float32).view(np.uint32)
-    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    """(scores, idx) of a call, tensors or arrays, against the oracle's arrays: float32 / int32, bit for bit."""
+    assert want[0].dtype == np.float32 and want[1].dtype == np.int32
+    assert_same_bits(tuple(got[:2]), tuple(want[:2]))
 
 
 def _keys_at(rankings, places):
@@ -79,7 +61,7 @@ def _keys_at(rankings, places):
     for r, (rs, ri) in enumerate(rankings):
         for j, p in enumerate(places[r]):
             if 0 <= p < len(ri):
-                out[r, j] = (np.uint64(_orderable(rs[p:p + 1])[0]) << np.uint64(32)) | np.uint64(0xFFFFFFFF - int(ri[p]))
+                out[r, j] = make_keys(rs[p:p + 1], ri[p:p + 1])[0]
     return out
 
 
@@ -99,7 +81,7 @@ def eng(engine):
 # ---- pages against oracle slices -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B,N,D", [(5, 3000, 128), (3, 1001, 64), (2, 1, 128), (4, 63, 128)])
 def test_pages_equal_oracle_slices(eng, B, N, D):
-    q, g = _rand(B, D, seed=B + N), _rand(N, D, seed=N + D, scale=D ** -0.5)
+    q, g = rand(B, D, seed=B + N), rand(N, D, seed=N + D, scale=D ** -0.5)
     ranks = _rankings(chain.chain_scores(q.numpy(), g.numpy()))
     qd, gd = q.cuda(), g.cuda()
     for k in (1, 50, 64, 1024):
@@ -114,7 +96,7 @@ def test_pages_equal_oracle_slices(eng, B, N, D):
 # ---- tie-heavy data ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B,N,D", [(5, 3000, 128), (3, 1000, 64)])
 def test_tie_heavy_pages_and_selects_split_runs_by_index(eng, B, N, D):
-    q, g = _int_unit(B, D, seed=41), _int_unit(N, D, seed=42)
+    q, g = int_unit(B, D, seed=41), int_unit(N, D, seed=42)
     ranks = _rankings(chain.chain_scores(q.numpy(), g.numpy()))
     offsets = [1, 63, 64, 500, N // 2 + 1, 999, N - 51]
     # the data is what the test is about: at most page boundaries the score at place `offset` is shared with another row
@@ -137,8 +119,8 @@ def test_a_tie_flood_pages_through_the_capacity_free_fallback(eng):
     (6000, 8990) fit the kernel's capacity again."""
     from fashionern_aaai2024_amd.engine import next_from
     B, N, D = 2, 9000, 64
-    q = _int_unit(B, D, seed=61)
-    g = _int_unit(1, D, seed=62).repeat(N, 1)
+    q = int_unit(B, D, seed=61)
+    g = int_unit(1, D, seed=62).repeat(N, 1)
     ranks = _rankings(chain.chain_scores(q.numpy(), g.numpy()))
     assert all(np.array_equal(r[1], np.arange(N)) for r in ranks)
     qd, gd = q.cuda(), g.cuda()
@@ -163,7 +145,7 @@ def _spread_places(b, n, m, seed):
 
 @pytest.mark.parametrize("B,N,D", [(5, 3000, 128), (1025, 300, 64)])
 def test_rank_select_inverts_rank_keys_and_rank_count(eng, B, N, D):
-    q, g = _rand(B, D, seed=3 + B), _rand(N, D, seed=5 + N, scale=D ** -0.5)
+    q, g = rand(B, D, seed=3 + B), rand(N, D, seed=5 + N, scale=D ** -0.5)
     ranks = _rankings(chain.chain_scores(q.numpy(), g.numpy()))
     qd, gd = q.cuda(), g.cuda()
     for m in (1, 3, 8, 13):
@@ -184,7 +166,7 @@ def test_rank_select_inverts_rank_keys_and_rank_count(eng, B, N, D):
 def test_cursor_pages_concatenate_to_the_whole_ranking(eng):
     from fashionern_aaai2024_amd.engine import next_from
     B, N, D, K = 3, 2500, 128, 1024
-    q, g = _rand(B, D, seed=8), _rand(N, D, seed=9, scale=D ** -0.5)
+    q, g = rand(B, D, seed=8), rand(N, D, seed=9, scale=D ** -0.5)
     ranks = _rankings(chain.chain_scores(q.numpy(), g.numpy()))
     qd, gd = q.cuda(), g.cuda()
     cursor = torch.full((B,), ALL, dtype=torch.int64)
@@ -208,7 +190,7 @@ def test_cursor_pages_concatenate_to_the_whole_ranking(eng):
 def test_ranking_to_depth_on_the_engine(eng):
     from fashionern_aaai2024_amd.run._common import ranking_to_depth
     B, N, D = 3, 1300, 64
-    q, g = _int_unit(B, D, seed=71), _int_unit(N, D, seed=72)
+    q, g = int_unit(B, D, seed=71), int_unit(N, D, seed=72)
     ranks = _rankings(chain.chain_scores(q.numpy(), g.numpy()))
     got = ranking_to_depth(eng, q.cuda(), g.cuda(), 1500)
     assert got.dtype == np.int32 and got.shape == (B, 1500)
@@ -222,7 +204,7 @@ def test_ranking_to_depth_on_the_engine(eng):
 def test_a_global_cursor_continues_the_list_on_every_shard(eng):
     from fashionern_aaai2024_amd.engine import next_from
     B, N, D, K, CUT = 6, 701, 64, 100, 351
-    q, g = _int_unit(B, D, seed=51), _int_unit(N, D, seed=52)
+    q, g = int_unit(B, D, seed=51), int_unit(N, D, seed=52)
     ranks = _rankings(chain.chain_scores(q.numpy(), g.numpy()))
     qd, gd = q.cuda(), g.cuda()
     first = eng.sim_topk_deep(qd, gd, K)
@@ -242,7 +224,7 @@ def test_a_global_cursor_continues_the_list_on_every_shard(eng):
 def test_exclusion_offset_and_row_filter(eng):
     from fashionern_aaai2024_amd.engine import RowFilter, next_from
     B, N, D, OFF = 5, 3000, 128, 1000
-    q, g = _rand(B, D, seed=21), _rand(N, D, seed=22, scale=D ** -0.5)
+    q, g = rand(B, D, seed=21), rand(N, D, seed=22, scale=D ** -0.5)
     rng = np.random.default_rng(23)
     tags = (rng.integers(0, 3, size=N) | (rng.integers(0, 16, size=N) << 4)).astype(np.int32)      # a three-valued field below other bits
     mask = np.array([3, 3, 0, 3, 3], dtype=np.int32)
@@ -282,7 +264,7 @@ def test_exclusion_offset_and_row_filter(eng):
 def test_bf16_and_prepared_gallery_forms(eng):
     from fashionern_aaai2024_amd.engine import next_from
     B, N, D = 4, 3001, 128
-    q, g = _rand(B, D, seed=31), _rand(N, D, seed=32, scale=D ** -0.5)
+    q, g = rand(B, D, seed=31), rand(N, D, seed=32, scale=D ** -0.5)
     pg = eng.prepare_gallery(g.cuda())
     qd = q.cuda()
     approx = eng.sweep_bf16_scores(qd, pg, tile_max=False).cpu().numpy()      # the bf16 form ranks exactly these values
@@ -304,7 +286,7 @@ def test_bf16_and_prepared_gallery_forms(eng):
 # ---- argument refusals -------------------------------------------------------------------------------------------------------------------
 def test_argument_refusals_name_the_function(eng):
     from fashionern_aaai2024_amd._lib import FernError
-    q, g = _rand(2, 64, seed=1).cuda(), _rand(10, 64, seed=2).cuda()
+    q, g = rand(2, 64, seed=1).cuda(), rand(10, 64, seed=2).cuda()
     cursor = torch.full((2,), ALL, dtype=torch.int64)
     for k in (0, 1025):
         with pytest.raises(FernError, match=r"\(-1\): fern_sim_topk_page: need 1<=K<=1024"):
@@ -316,14 +298,14 @@ def test_argument_refusals_name_the_function(eng):
     p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
     assert eng.lib.fern_rank_select(eng._h, p(q), p(g), None, 2, 10, 64, p(places), 0, 0, None, p(keys), None, None, None, None) == -1
     assert b"fern_rank_select: need m >= 1" in eng.lib.fern_last_error()
-    q48, g48 = _rand(2, 48, seed=1).cuda(), _rand(10, 48, seed=2).cuda()
+    q48, g48 = rand(2, 48, seed=1).cuda(), rand(10, 48, seed=2).cuda()
     with pytest.raises(FernError, match=r"\(-1\): fern_sim_topk_page: the fp32 form needs D % 32 == 0"):
         eng.rank_page(q48, g48, 0, 5)
     with pytest.raises(FernError, match=r"\(-1\): fern_rank_select: the fp32 form needs D % 32 == 0"):
         eng.rank_select(q48, g48, places)
     with pytest.raises(FernError, match=r"\(-1\): fern_sim_topk_from: the fp32 form needs D % 32 == 0"):
         eng.sim_topk_from(q48, g48, 5, cursor)
-    q1k, g1k = _rand(2, 1024, seed=1).cuda(), _rand(10, 1024, seed=2).cuda().bfloat16()
+    q1k, g1k = rand(2, 1024, seed=1).cuda(), rand(10, 1024, seed=2).cuda().bfloat16()
     with pytest.raises(FernError, match=r"\(-1\): fern_sim_topk_page: a bf16-only gallery needs D % 64 == 0, D <= 768"):
         eng.rank_page(q1k, g1k, 0, 5)
     with pytest.raises(FernError, match=r"\(-1\): fern_rank_select: a bf16-only gallery needs D % 64 == 0, D <= 768"):

@@ -12,18 +12,9 @@ import torch
 
 from oracle import chain
 from oracle import rank as orank
+from support import fresh_engine, int_unit, rand, same_bits
 
 pytestmark = pytest.mark.gpu
-
-
-def _rand(n, d, seed, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(n, d, generator=g) * scale
-
-
-def _int_unit(n, d, seed):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-1, 2, (n, d), generator=g).float() / 8.0
 
 
 @pytest.fixture(params=["auto", "lists", "dense"])
@@ -38,14 +29,7 @@ def engine(request):
 
 @pytest.fixture(scope="module")
 def _session_engine():
-    from fashionern_aaai2024_amd.engine import FernEngine
-    eng = FernEngine("cuda:0")
-    yield eng
-    eng.close()
-
-
-def _same_bits(s, i, cs, ci):
-    return np.array_equal(i.cpu().numpy(), ci) and np.array_equal(s.cpu().numpy().view(np.uint32), cs.view(np.uint32))
+    yield from fresh_engine()
 
 
 @pytest.mark.parametrize("B,N,D", [(3, 1000, 64), (64, 9001, 640), (130, 3000, 128), (1, 70_000, 512), (64, 46_000, 512), (5, 40, 64), (2, 7, 1024),
@@ -53,12 +37,12 @@ def _same_bits(s, i, cs, ci):
 def test_prefiltered_ranking_is_bit_identical_to_the_fma_chain(engine, B, N, D):
     """Random operands at the shapes of test_sim_topk_bit_identical_to_the_fma_chain plus BASELINE C2's (64 x 46 000 x 512) and
     galleries smaller than K: same bits as the sequential fp32 fma chain, same ranking -- and the same as the plain fp32 stage."""
-    q, g = _rand(B, D, seed=B + N), _rand(N, D, seed=N + D, scale=D ** -0.5)
+    q, g = rand(B, D, seed=B + N), rand(N, D, seed=N + D, scale=D ** -0.5)
     pg = engine.prepare_gallery(g)
     s, i = engine.sim_topk(q, pg, 50)
     cs, ci = chain.chain_topk(q.numpy(), g.numpy(), 50)
     m = min(N, 50)                                         # fewer rows than K: the tail is (-inf, -1)
-    assert _same_bits(s[:, :m], i[:, :m], cs, ci)
+    assert same_bits((s[:, :m], i[:, :m]), (cs, ci))
     assert (i[:, m:].cpu() == -1).all() and torch.isinf(s[:, m:].cpu()).all()
     s0, i0 = engine.sim_topk(q, g, 50)
     assert torch.equal(s, s0) and torch.equal(i, i0)
@@ -68,7 +52,7 @@ def test_prepare_reports_the_norms_that_certify_the_margin(engine):
     """meta = {max ||g - bf16(g)||, max ||bf16(g)||, max ||g||}; with them |exact - bf16 score| <= eps_b of include/fern.h for every
     (query, row) -- checked against the actual errors of the bf16 operands in float64."""
     d = 512
-    q, g = _rand(32, d, 5, 0.7), _rand(20_000, d, 6, d ** -0.5)
+    q, g = rand(32, d, seed=5, scale=0.7), rand(20_000, d, seed=6, scale=d ** -0.5)
     g[17] *= 9.0                                           # one long row sets the maxima
     pg = engine.prepare_gallery(g)
     gb = g.bfloat16().float()
@@ -89,24 +73,24 @@ def test_rows_inside_the_margin_are_rescored_not_trusted(engine, near):
     far inside the bf16 error (~1e-3): the bf16 ranking of them is scrambled -- asserted -- and only the exact rescoring can order
     them.  400 rows fit the rescoring kernel; 3000 exceed its 1024 survivors and take the exact pass.  Result = the chain's, bit for bit."""
     d, n, k = 512, 30_000, 50
-    base = torch.nn.functional.normalize(_rand(1, d, 77), dim=-1)
-    q = torch.nn.functional.normalize(base + 0.02 * _rand(8, d, 78) * d ** -0.5, dim=-1)
-    g = torch.nn.functional.normalize(_rand(n, d, 79), dim=-1)
+    base = torch.nn.functional.normalize(rand(1, d, seed=77), dim=-1)
+    q = torch.nn.functional.normalize(base + 0.02 * rand(8, d, seed=78) * d ** -0.5, dim=-1)
+    g = torch.nn.functional.normalize(rand(n, d, seed=79), dim=-1)
     rows = torch.randperm(n, generator=torch.Generator().manual_seed(80))[:near]
-    g[rows] = torch.nn.functional.normalize(base + 0.03 * _rand(near, d, 81) * d ** -0.5, dim=-1)
+    g[rows] = torch.nn.functional.normalize(base + 0.03 * rand(near, d, seed=81) * d ** -0.5, dim=-1)
     cs, ci = chain.chain_topk(q.numpy(), g.numpy(), k)
     approx = (q.bfloat16().float() @ g.bfloat16().float().T).topk(k, dim=1).indices
     scrambled = sum(set(a.tolist()) != set(b.tolist()) for a, b in zip(approx, torch.from_numpy(ci.astype(np.int64))))
     assert scrambled >= 6, "the case must be one where the bf16 scores pick the wrong rows"
     s, i = engine.sim_topk(q, engine.prepare_gallery(g), k)
-    assert _same_bits(s, i, cs, ci)
+    assert same_bits((s, i), (cs, ci))
 
 
 @pytest.mark.parametrize("n", [1, 63, 1025, 65_537])
 def test_all_scores_equal_only_the_index_breaks_ties(engine, n):
     d, k = 64, 50
-    q = _int_unit(3, d, 5)
-    g = _int_unit(1, d, 6).repeat(n, 1)
+    q = int_unit(3, d, 5)
+    g = int_unit(1, d, 6).repeat(n, 1)
     rs, ri = orank.cosine_topk(q, g, k)
     s, i = engine.sim_topk(q, engine.prepare_gallery(g), k)
     engine.sync()
@@ -117,7 +101,7 @@ def test_exclusion_offsets_and_large_batches(engine):
     """CIRR's shape (BASELINE C4): B crosses the 1024-query plan chunk and the 128-query sweep blocks, K = 51, one excluded
     gallery index per query, idx_offset of a gallery shard."""
     n, d = 21_552, 64
-    q, g = _rand(1300, d, 51), _rand(n, d, 52, d ** -0.5)
+    q, g = rand(1300, d, seed=51), rand(n, d, seed=52, scale=d ** -0.5)
     ex = torch.randint(0, n, (1300,), generator=torch.Generator().manual_seed(3), dtype=torch.int32) + 7000
     pg = engine.prepare_gallery(g)
     s, i = engine.sim_topk(q, pg, 51, idx_offset=7000, exclude_idx=ex)
@@ -136,7 +120,7 @@ def test_large_dense_gallery_with_exclusions_spread_over_the_row(engine):
     """A gallery beyond the three register-held batches of the dense kernel (49 152 rows: the streaming path), the excluded row of each
     query is its best row, spread over the whole row range; N is not a multiple of anything."""
     n, d, k = 150_001, 64, 50
-    q, g = _rand(7, d, 61), _rand(n, d, 62, d ** -0.5)
+    q, g = rand(7, d, seed=61), rand(n, d, seed=62, scale=d ** -0.5)
     ex_rows = [0, 37_000, 49_151, 49_152, 75_001, 120_000, 150_000]
     for b, row in enumerate(ex_rows):
         g[row] = q[b] * 3.0
@@ -151,7 +135,7 @@ def test_large_dense_gallery_with_exclusions_spread_over_the_row(engine):
 def test_excluded_row_is_the_best_row_and_a_sampled_row(engine):
     from test_gpu_rank_fused import plan, sample_row                     # the plain plan's sample; the pre-filter's is denser at this N
     n, d, k = 70_000, 64, 5
-    q, g = _int_unit(6, d, 31), _int_unit(n, d, 32)
+    q, g = int_unit(6, d, 31), int_unit(n, d, 32)
     s_rows = max(n // 32, min(n, 4096))
     r = n // s_rows
     ex_rows = [sample_row(c, r) for c in (0, 17, 500, s_rows - 1, 3, 9)]
@@ -167,16 +151,16 @@ def test_excluded_row_is_the_best_row_and_a_sampled_row(engine):
 def test_rows_of_very_different_lengths(engine):
     """Un-normalised operands: the margin scales with the longest gallery row, so short rows' scores sit deep inside it."""
     n, d, k = 20_000, 128, 50
-    q = _rand(9, d, 91) * 3.7
-    g = _rand(n, d, 92) * torch.logspace(-1, 1.3, n)[torch.randperm(n, generator=torch.Generator().manual_seed(93))][:, None]
+    q = rand(9, d, seed=91) * 3.7
+    g = rand(n, d, seed=92) * torch.logspace(-1, 1.3, n)[torch.randperm(n, generator=torch.Generator().manual_seed(93))][:, None]
     cs, ci = chain.chain_topk(q.numpy(), g.numpy(), k)
     s, i = engine.sim_topk(q, engine.prepare_gallery(g), k)
-    assert _same_bits(s, i, cs, ci)
+    assert same_bits((s, i), (cs, ci))
 
 
 def test_prepared_gallery_is_refilled_in_place_and_feeds_the_pipeline_entry_points(engine):
     d = 64
-    g1, g2, q = _rand(5000, d, 1, 0.1), _rand(5000, d, 2, 0.1), _rand(4, d, 3)
+    g1, g2, q = rand(5000, d, seed=1, scale=0.1), rand(5000, d, seed=2, scale=0.1), rand(4, d, seed=3)
     pg = engine.prepare_gallery(g1)
     pg2 = engine.prepare_gallery(g2, out=pg)
     assert pg2.bf16.data_ptr() == pg.bf16.data_ptr() and pg2.meta.data_ptr() == pg.meta.data_ptr()
@@ -196,7 +180,7 @@ def test_sweep_scores_are_the_bf16_products_and_tile_maxima_the_maxima_of_32_row
     the same rounded operands), inside the certified eps_b of the exact score; tile_max[b][t] is bit for bit the largest of
     scores[b][32 t : 32 t + 32] -- the dense form reads those instead of the rows."""
     eng = _session_engine
-    q, g = _rand(B, D, seed=3 * B + N), _rand(N, D, seed=N - D, scale=D ** -0.5)
+    q, g = rand(B, D, seed=3 * B + N), rand(N, D, seed=N - D, scale=D ** -0.5)
     pg = eng.prepare_gallery(g)
     scores, tmax = eng.sweep_bf16_scores(q, pg)
     scores, tmax = scores.cpu(), tmax.cpu()
@@ -217,7 +201,7 @@ def test_tile_maxima_form_beyond_one_register_batch_and_with_split_query_blocks(
     >= 131 072 rows (the sweep runs one 64-query block per launch so that it can leave tile maxima); the smallest gallery of the form;
     excluded rows = each query's best row, in tiles spread over the whole gallery; D = 768 / 192: the sweep's generic form (queries in
     LDS, no compile-time D), the second with more than 64 queries.  Bits of the fp32 stage, every time."""
-    q, g = _rand(B, D, seed=B + N), _rand(N, D, seed=N + D, scale=D ** -0.5)
+    q, g = rand(B, D, seed=B + N), rand(N, D, seed=N + D, scale=D ** -0.5)
     ex_rows = [(b * 7919 * 31 + 5) % N for b in range(B)]
     for b, row in enumerate(ex_rows):
         g[row] = q[b] * 2.0
@@ -230,30 +214,30 @@ def test_tile_maxima_form_beyond_one_register_batch_and_with_split_query_blocks(
     assert i[:, 0].cpu().tolist() == ex_rows
     nq = min(B, 6)
     cs, ci = chain.chain_topk(q[:nq].numpy(), g.numpy(), 50)
-    assert _same_bits(s[:nq], i[:nq], cs, ci)
+    assert same_bits((s[:nq], i[:nq]), (cs, ci))
 
 
 def test_more_listed_tiles_than_the_kernel_holds_takes_the_exact_ranking(engine):
     """6 000 rows within 1e-4 of each other spread over ~2 700 of the gallery's 3 125 tiles: every wave lists more than its 512 tiles and
     the query is ranked exactly behind the bound it had reached -- the chain's result, bit for bit."""
     d, n, k, near = 128, 100_000, 50, 6000
-    base = torch.nn.functional.normalize(_rand(1, d, 7), dim=-1)
-    q = torch.nn.functional.normalize(base + 0.02 * _rand(4, d, 8) * d ** -0.5, dim=-1)
-    g = torch.nn.functional.normalize(_rand(n, d, 9), dim=-1)
+    base = torch.nn.functional.normalize(rand(1, d, seed=7), dim=-1)
+    q = torch.nn.functional.normalize(base + 0.02 * rand(4, d, seed=8) * d ** -0.5, dim=-1)
+    g = torch.nn.functional.normalize(rand(n, d, seed=9), dim=-1)
     rows = torch.randperm(n, generator=torch.Generator().manual_seed(10))[:near]
-    g[rows] = torch.nn.functional.normalize(base + 0.03 * _rand(near, d, 11) * d ** -0.5, dim=-1)
+    g[rows] = torch.nn.functional.normalize(base + 0.03 * rand(near, d, seed=11) * d ** -0.5, dim=-1)
     assert len(set((rows // 32).tolist())) > 2048
     cs, ci = chain.chain_topk(q.numpy(), g.numpy(), k)
     s, i = engine.sim_topk(q, engine.prepare_gallery(g), k)
-    assert _same_bits(s, i, cs, ci)
+    assert same_bits((s, i), (cs, ci))
 
 
 def test_gallery_past_the_inline_exact_limit_sends_floods_to_the_gated_exact_pass(engine):
     """300 000 x 128 fp32 = 154 MB: beyond what one workgroup may stream by itself, so a query without room (all rows equal: every tile is
     listed) is flagged for the gated exact-pass launch instead; ties break by index."""
     d, k, n = 128, 50, 300_000
-    q = _int_unit(3, d, 5)
-    g = _int_unit(1, d, 6).repeat(n, 1)
+    q = int_unit(3, d, 5)
+    g = int_unit(1, d, 6).repeat(n, 1)
     g[123_456] = torch.sign(q[1]) / 8.0 + (q[1] == 0) * 0.125           # one row stands out for query 1
     rs, ri = orank.cosine_topk(q, g, k)
     s, i = engine.sim_topk(q, engine.prepare_gallery(g), k)
@@ -264,7 +248,7 @@ def test_non_finite_rows_leave_no_certificate_and_the_stage_falls_back_to_the_ex
     """An inf / NaN gallery row makes the margin non-finite: nothing is certified, every query takes the exact ranking -- the same bits as
     the fp32 stage on that gallery."""
     n, d, k = 40_000, 64, 50
-    q, g = _rand(6, d, 1), _rand(n, d, 2, d ** -0.5)
+    q, g = rand(6, d, seed=1), rand(n, d, seed=2, scale=d ** -0.5)
     g[777, 3] = float("inf")
     pg = engine.prepare_gallery(g)
     s, i = engine.sim_topk(q, pg, k)
@@ -277,7 +261,7 @@ def test_prepared_shards_with_offsets_merge_to_the_unsharded_ranking(engine):
     offset and the queries' global exclusions, the per-shard top-K lists are merged (fern_topk_merge).  Shards of very different sizes
     take different forms of the stage (row walk, tile maxima, lists) -- the merged result is the unsharded fp32 ranking, bit for bit."""
     n, d, k = 120_000, 128, 50
-    q, g = _rand(40, d, 71), _rand(n, d, 72, d ** -0.5)
+    q, g = rand(40, d, seed=71), rand(n, d, seed=72, scale=d ** -0.5)
     ex = torch.randint(0, n, (40,), generator=torch.Generator().manual_seed(7), dtype=torch.int32)
     for b in range(40):
         g[int(ex[b])] = q[b] * 1.5                                     # the excluded row would rank first
@@ -294,7 +278,7 @@ def test_prepared_shards_with_offsets_merge_to_the_unsharded_ranking(engine):
 def test_smallest_and_largest_k_with_exclusions(engine, k):
     """K = 1 and K = 64 (the ABI's limits) with an excluded best row: the tile-maxima bound needs ceil((K + 1) / 4) tiles per wave."""
     n, d = 33_000, 64
-    q, g = _rand(9, d, 5 + k), _rand(n, d, 6 + k, d ** -0.5)
+    q, g = rand(9, d, seed=5 + k), rand(n, d, seed=6 + k, scale=d ** -0.5)
     ex_rows = [(b * 3671 + 11) % n for b in range(9)]
     for b, row in enumerate(ex_rows):
         g[row] = q[b] * 2.0
@@ -305,4 +289,4 @@ def test_smallest_and_largest_k_with_exclusions(engine, k):
         s0, i0 = engine.sim_topk(q, g, k, exclude_idx=exclude)
         assert torch.equal(s, s0) and torch.equal(i, i0)
     cs, ci = chain.chain_topk(q.numpy(), g.numpy(), k)
-    assert _same_bits(s, i, cs, ci) and i[:, 0].cpu().tolist() == ex_rows
+    assert same_bits((s, i), (cs, ci)) and i[:, 0].cpu().tolist() == ex_rows

@@ -12,9 +12,9 @@ import torch
 import torch.nn.functional as F
 
 from fashionern_aaai2024_amd import synth
-from fashionern_aaai2024_amd.engine import FernEngine
 from oracle import clip as oclip
 from oracle import fusion as ofusion
+from support import cos_err, maxerr, t, tower_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -23,24 +23,8 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 MIXED_BOUNDS = {"mx8img": 2e-3, "mx8mlp": 1e-3}      # test_gpu_fusion.py
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
-
-
-def _maxerr(got, ref):
-    return (got.detach().cpu().double() - ref.double()).abs().max().item()
-
-
-def cos_err(a, b):
-    return (1 - F.cosine_similarity(a.cpu().double().flatten(-1 if a.dim() == 2 else 1), b.double().flatten(-1 if b.dim() == 2 else 1), dim=-1)).abs().max().item()
-
-
 def _tower(name, seed):
-    cfg = synth.CLIP_CONFIGS[name]
-    sd_np = synth.clip_state_dict(cfg, seed=seed)
-    eng = FernEngine("cuda:0")
-    eng.load_tensors(sd_np)
-    eng.finalize_clip(cfg)
+    cfg, sd_np, eng = tower_engine(name, seed)
     return cfg, ofusion.as_torch(sd_np), eng
 
 
@@ -49,22 +33,22 @@ def _tower(name, seed):
 def test_clip_towers_tiny_long(name):
     """test_clip_towers_tiny's bound against the oracle, and the same bound against the in-tree statement's outputs (clip_long.npz)."""
     cfg, sd, eng = _tower(name, 5)
-    imgs = _t(synth.images(5, cfg, 42))
+    imgs = t(synth.images(5, cfg, 42))
     ref = oclip.encode_image(sd, cfg, imgs)
     got = eng.encode_image(imgs)
-    print(f"{name}: max |d| vs oracle {_maxerr(got, ref):.2e} (scale {ref.abs().max().item():.2f})")
-    assert _maxerr(got, ref) < 2e-4 * max(1.0, ref.abs().max().item())
+    print(f"{name}: max |d| vs oracle {maxerr(got, ref):.2e} (scale {ref.abs().max().item():.2f})")
+    assert maxerr(got, ref) < 2e-4 * max(1.0, ref.abs().max().item())
     if name != "tiny-p14-short":                      # the fixture holds the two 290-token towers (seed 5, input seed 42)
-        gold = _t(np.load(os.path.join(GOLD, "clip_long.npz"))[f"{name}_image"])
-        print(f"{name}: max |d| vs clip_long.npz {_maxerr(got, gold):.2e}")
-        assert _maxerr(got, gold) < 2e-4 * max(1.0, gold.abs().max().item())
+        gold = t(np.load(os.path.join(GOLD, "clip_long.npz"))[f"{name}_image"])
+        print(f"{name}: max |d| vs clip_long.npz {maxerr(got, gold):.2e}")
+        assert maxerr(got, gold) < 2e-4 * max(1.0, gold.abs().max().item())
     assert torch.equal(eng.encode_image(imgs[1:2]), got[1:2])
     for full in (True, False):
-        toks = _t(synth.captions(6, cfg, full_length=full))
+        toks = t(synth.captions(6, cfg, full_length=full))
         rg, rs = oclip.encode_text(sd, cfg, toks)
         g, s = eng.encode_text(toks)
         scale = max(1.0, rs.abs().max().item())
-        assert _maxerr(s, rs) < 2e-4 * scale and _maxerr(g, rg) < 2e-4 * scale
+        assert maxerr(s, rs) < 2e-4 * scale and maxerr(g, rg) < 2e-4 * scale
     eng.close()
 
 
@@ -73,18 +57,18 @@ def test_clip_full_size_long(name, n_img, n_txt):
     """test_clip_vit_b16_full_size's bounds on the open_clip shapes that are new by name: ViT-L/14 (257 tokens, 16 x 64 heads, 24 layers,
     patch 14; both towers -- its text tower is 768 wide), ViT-L/14@336 (577 tokens) and ViT-B/32."""
     cfg, sd, eng = _tower(name, 6)
-    imgs = _t(synth.images(n_img, cfg))
+    imgs = t(synth.images(n_img, cfg))
     ref = oclip.encode_image(sd, cfg, imgs)
     got = eng.encode_image(imgs)
     cos = F.cosine_similarity(got.cpu(), ref, dim=-1)
-    print(f"{name}: image max |d| {_maxerr(got, ref):.2e} (scale {ref.abs().max().item():.2f}), 1 - cos {(1 - cos).abs().max().item():.2e}")
-    assert _maxerr(got, ref) < 1e-3 * max(1.0, ref.abs().max().item()) and (1 - cos).abs().max().item() < 1e-5
+    print(f"{name}: image max |d| {maxerr(got, ref):.2e} (scale {ref.abs().max().item():.2f}), 1 - cos {(1 - cos).abs().max().item():.2e}")
+    assert maxerr(got, ref) < 1e-3 * max(1.0, ref.abs().max().item()) and (1 - cos).abs().max().item() < 1e-5
     if n_txt:
-        toks = _t(synth.captions(n_txt, cfg))
+        toks = t(synth.captions(n_txt, cfg))
         rg, rs = oclip.encode_text(sd, cfg, toks)
         g, s = eng.encode_text(toks)
-        print(f"{name}: text seq max |d| {_maxerr(s, rs):.2e}, global 1 - cos {(1 - F.cosine_similarity(g.cpu(), rg, dim=-1)).abs().max().item():.2e}")
-        assert _maxerr(s, rs) < 1e-3 * max(1.0, rs.abs().max().item())
+        print(f"{name}: text seq max |d| {maxerr(s, rs):.2e}, global 1 - cos {(1 - F.cosine_similarity(g.cpu(), rg, dim=-1)).abs().max().item():.2e}")
+        assert maxerr(s, rs) < 1e-3 * max(1.0, rs.abs().max().item())
         assert (1 - F.cosine_similarity(g.cpu(), rg, dim=-1)).abs().max().item() < 1e-5
     eng.close()
 
@@ -94,7 +78,7 @@ def test_chunk_boundaries_change_no_row(precision):
     """70 tiny-long images (290 tokens: 43 per chunk, so 43 + 27) equal the rows of two calls of 35 (one chunk each), bit for bit."""
     cfg, _, eng = _tower("tiny-long", 5)
     eng.set_precision(precision)
-    imgs = _t(synth.images(70, cfg))
+    imgs = t(synth.images(70, cfg))
     full = eng.encode_image(imgs)
     assert torch.equal(full[:35], eng.encode_image(imgs[:35])) and torch.equal(full[35:], eng.encode_image(imgs[35:]))
     eng.close()
@@ -118,7 +102,7 @@ def _mode_run(eng, imgs, toks, mode, fp32_img):
 def test_long_towers_bf16_precision(name):
     """test_clip_towers_bf16_precision's assertions and constants."""
     cfg, sd, eng = _tower(name, 11)
-    imgs, toks = _t(synth.images(4, cfg)), _t(synth.captions(4, cfg))
+    imgs, toks = t(synth.images(4, cfg)), t(synth.captions(4, cfg))
     fp32_img = eng.encode_image(imgs)
     eng.set_precision("bf16")
     child = eng.fork()                                                 # a forked context shares the weights, the padded conv1 copy included
@@ -132,8 +116,8 @@ def test_long_towers_bf16_precision(name):
     rg_f, _ = oclip.encode_text(sd, cfg, toks)
     print(f"bf16 {name}: vs restatement {cos_err(got, ref_b):.2e} / {cos_err(g, rg_b):.2e}, vs fp32 {cos_err(got, ref_f):.2e}")
     assert cos_err(got, ref_b) < 2e-5 and cos_err(g, rg_b) < 2e-5
-    assert _maxerr(got, ref_b) < 5e-3 * max(1.0, ref_b.abs().max().item())
-    assert _maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
+    assert maxerr(got, ref_b) < 5e-3 * max(1.0, ref_b.abs().max().item())
+    assert maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
     assert cos_err(got, ref_f) < 1e-3 and cos_err(g, rg_f) < 1e-3
     assert cos_err(got, ref_f) > 0 and not torch.equal(got, fp32_img)
 
@@ -142,7 +126,7 @@ def test_long_towers_bf16_precision(name):
 def test_tiny_long_fp8_and_mx8_precision(mode):
     """test_clip_towers_fp8_precision / test_clip_towers_mx8_precision's assertions and constants."""
     cfg, sd, eng = _tower("tiny-long", 11)
-    imgs, toks = _t(synth.images(4, cfg)), _t(synth.captions(4, cfg))
+    imgs, toks = t(synth.images(4, cfg)), t(synth.captions(4, cfg))
     fp32_img = eng.encode_image(imgs)
     got, g, _ = _mode_run(eng, imgs, toks, mode, fp32_img)
     eng.close()
@@ -160,7 +144,7 @@ def test_tiny_long_fp8_and_mx8_precision(mode):
 def test_long_towers_mixed_precision(name, modes):
     """test_clip_towers_mx8img_and_mx8mlp_precision's assertions and constants."""
     cfg, sd, eng = _tower(name, 11)
-    imgs, toks = _t(synth.images(4, cfg)), _t(synth.captions(4, cfg))
+    imgs, toks = t(synth.images(4, cfg)), t(synth.captions(4, cfg))
     fp32_img = eng.encode_image(imgs)
     runs = {m: _mode_run(eng, imgs, toks, m, fp32_img) for m in modes}
     eng.close()
@@ -173,7 +157,7 @@ def test_long_towers_mixed_precision(name, modes):
         assert e_own < MIXED_BOUNDS[mode]
         assert e_own < e_f and e_own < e_b
         assert cos_err(g, rg_b) < 2e-5 and cos_err(s, rs_b) < 2e-5      # the text tower is the bf16 block
-        assert _maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
+        assert maxerr(s, rs_b) < 5e-3 * max(1.0, rs_b.abs().max().item())
         assert not torch.equal(got, fp32_img)
 
 
@@ -187,7 +171,7 @@ def test_vit_l14_reduced_modes():
     """The relations that catch a wrong rounding point -- closer to the mode's own restatement than to fp32 (and, mx8img, than to the bf16
     restatement); a wrong one puts e_own at the mode-to-mode distance (oracle side: mx8img-vs-fp32 2.9e-3, bf16-vs-fp32 1.2e-5)."""
     cfg, sd, eng = _tower("ViT-L-14", 11)
-    imgs = _t(synth.images(3, cfg))
+    imgs = t(synth.images(3, cfg))
     got = {}
     for mode in ("mx8img", "bf16"):
         eng.set_precision(mode)
@@ -211,7 +195,7 @@ def test_vit_l14_reduced_modes():
 def test_encode_pair_long_is_bit_identical_to_the_two_encoder_calls(name, b, precision):
     cfg, _, eng = _tower(name, 7)
     eng.set_precision(precision)
-    imgs, toks = _t(synth.images(b, cfg)), _t(synth.captions(b, cfg))
+    imgs, toks = t(synth.images(b, cfg)), t(synth.captions(b, cfg))
     ref_i = eng.encode_image(imgs)
     ref_g, ref_s = eng.encode_text(toks)
     for rep in range(2):      # the first call tunes the pair shapes (two launches per pair), later calls may take the one-launch form

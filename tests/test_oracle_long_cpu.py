@@ -9,13 +9,10 @@ import torch
 
 from fashionern_aaai2024_amd import synth
 from oracle import clip as oclip, fusion as ofusion
+from support import t
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CLIP_SEED, INPUT_SEED = 5, 42
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
 
 
 def test_long_tower_shapes():

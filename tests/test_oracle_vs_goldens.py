@@ -12,13 +12,10 @@ from fashionern_aaai2024_amd import synth
 from oracle import clip as oclip
 from oracle import fusion as ofusion
 from oracle import rank as orank
+from support import t
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 FUSION_SEED, CLIP_SEED, INPUT_SEED = 11, 5, 42
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
 
 
 @pytest.fixture(scope="module")

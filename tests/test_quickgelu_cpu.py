@@ -15,13 +15,10 @@ from fashionern_aaai2024_amd import _lib, synth
 from oracle import clip as oclip, fusion as ofusion
 
 import quickgelu_oracle as qo
+from support import t
 
 CLIP_SEED, INPUT_SEED = 5, 42
 TOWERS = [("tiny", 5, 6, 2e-5), ("tiny-hd64", 5, 6, 2e-5), ("ViT-B-16", 2, 2, 2e-4)]
-
-
-def t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
 
 
 # ---- 1. patched oracle against the fixture ---------------------------------------------------------------------------------------

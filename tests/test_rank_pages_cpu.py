@@ -10,7 +10,7 @@ import torch
 import torch.distributed as dist
 
 import gloo
-from rank_oracle import RankOracle, _make_keys
+from rank_oracle import RankOracle, make_keys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -77,7 +77,7 @@ def test_ranking_keys_equal_the_numpy_key_definition():
     s, i = _result(4, 9, [9, 9, 4, 0], seed=1)
     s[1, :3] = [np.float32(3.5), np.float32(-0.0), np.float32(-2.25)]
     i[1, :3] = [0, 2 ** 31 - 2, 7]
-    want = np.where(i >= 0, _make_keys(s, np.where(i >= 0, i, 0).astype(np.int64)), np.uint64(0))
+    want = np.where(i >= 0, make_keys(s, np.where(i >= 0, i, 0).astype(np.int64)), np.uint64(0))
     got = ranking_keys(torch.from_numpy(s), torch.from_numpy(i))
     assert got.dtype == torch.int64 and tuple(got.shape) == (4, 9)
     assert np.array_equal(got.numpy().view(np.uint64), want)
@@ -87,7 +87,7 @@ def test_ranking_keys_equal_the_numpy_key_definition():
 def test_next_from_on_full_partial_and_empty_pages():
     from fashionern_aaai2024_amd.engine import next_from
     s, i = _result(3, 6, [6, 2, 0], seed=2)
-    keys = _make_keys(s, np.where(i >= 0, i, 0).astype(np.int64))
+    keys = make_keys(s, np.where(i >= 0, i, 0).astype(np.int64))
     got = next_from(torch.from_numpy(s), torch.from_numpy(i))
     assert got.dtype == torch.int64 and tuple(got.shape) == (3,)
     g = got.numpy().view(np.uint64)
